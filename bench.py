@@ -48,9 +48,6 @@ import time
 os.environ.setdefault("OMP_NUM_THREADS", "1")
 os.environ.setdefault("OPENBLAS_NUM_THREADS", "1")
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-# HIP maps streams onto 4 hardware queues by default; the batches' streams plus RCCL's own then share queues
-# and serialise (measured: 359 k instead of 413 k traj/s with the gather on).  Must be set before HIP starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 for p_ in (REPO, os.path.join(REPO, "neo-planner_amd"), os.path.join(REPO, "tools")):
@@ -62,6 +59,7 @@ import numpy as np
 HBM_PEAK_GBPS = 8000.0      # MI355X_MICROARCH.md: HBM3E peak
 CANOPY = 80                 # floating boxes per 3-D scene (synth.canopy_boxes)
 LINE_LIMIT = 4096           # bytes of the final stdout line (the driver's parser gave up at 20 KB in round 4)
+DUMP_LIMIT = 64_000_000    # bytes of all --dump-outputs files together
 
 
 def parse(argv=None):
@@ -89,6 +87,9 @@ def parse(argv=None):
     ap.add_argument("--report-sections", default="all",
                     help="comma list of tools/bench_report.py sections to run: retries, budget, esdf, cfg1, parity (default all); "
                          "profile runs ask for `esdf` alone so that the counters of a launch shape belong to one kind of launch")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float64; rank 0; "
+                         f"a fixed, seeded sample of trajectories when all of them exceed {DUMP_LIMIT // 10**6} MB)")
     ap.add_argument("--details", default=None,
                     help="where the full report goes (default gpurun_out/bench_details.json, /tmp when that is not writable)")
     ap.add_argument("--esdf-order", default="spatial", choices=["spatial", "index"],
@@ -431,6 +432,24 @@ def write_details(a, out):
     return None
 
 
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: `arrays` maps a name to an array whose first axis is the trajectory (batch-major over the step's
+    request batches).  Every array goes to path/<name>.npy as float64, with `index.npy` naming the trajectories kept: all
+    of them when they fit in `limit` bytes, else a sorted sample drawn with a fixed seed (the same rows for the same
+    arguments, so that two builds can be compared file for file).  Returns the number of trajectories written."""
+    rows = {len(v) for v in arrays.values()}
+    assert len(rows) == 1, rows
+    N = rows.pop()
+    per_row = 8 * (1 + sum(int(np.prod(v.shape[1:])) for v in arrays.values()))     # (+1: the index column)
+    k = min(N, (limit - 1024 * (1 + len(arrays))) // per_row)      # (1 KB per file for the .npy header)
+    idx = np.arange(N) if k == N else np.sort(np.random.default_rng(0).choice(N, k, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "index.npy"), idx.astype(np.float64))
+    for name, v in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(v[idx], dtype=np.float64))
+    return k
+
+
 # ================================================================== one rank
 def workload_sets(a, rank, M, D, n_sets, n_scenes):
     """request batches of this rank: list of (head, tail, wp, ts)"""
@@ -662,11 +681,13 @@ class Rank:
         self.ctx.check(self.ctx.lib.neo_profile_read(self.ctx.h, which, ctypes.byref(launches), ctypes.byref(kms)))
         return int(launches.value), float(kms.value)
 
-    def time_mode(self, mode, d2h=False):
+    def time_mode(self, mode, d2h=False, keep=False):
         """W warm-up steps, then exactly K timed steps of the hot path in arithmetic mode `mode`, fenced by a barrier
         and a device synchronisation on both sides; returns the timing and what the launches of the last step left.
         d2h: every launch is followed by the copy of its final points and statuses to pinned host memory (what a host-side
-        caller sees; returns only the elapsed time)"""
+        caller sees; returns only the elapsed time)
+        keep: also return every batch's results of the last timed step (`last_step`, host arrays), copied before the
+        launches alone below overwrite the first batches' buffers"""
         torch, ctx, a = self.torch, self.ctx, self.a
         bpm = self.bp if mode == a.dtype else self.planner_for(mode)
         bpm._sync()
@@ -687,6 +708,13 @@ class Rank:
         ctx.set_stream(None)
         if d2h:
             return dict(mode=mode, elapsed=el)
+        last_step = None
+        if keep:
+            # what optimize_dev hands its caller, trajectory by trajectory: final points, cost terms at the final point and
+            # at the one before it, iterations, evaluations, status
+            last_step = {k_: torch.cat([bt[f_] for bt in self.batches]).cpu().numpy()
+                         for k_, f_ in (("x", "x"), ("costs", "costs"), ("costs_last", "last"), ("nit", "nit"),
+                                        ("nfev", "nfev"), ("status", "status"))}
         launches, kms = self.kernel_time(self._lib.NEO_KERNEL_OPTIMIZE)
         # one launch ALONE on the chip (outside the timed region): what a caller with a single request batch gets -- with
         # `--streams` launches in flight each one lasts longer than it would by itself
@@ -717,7 +745,7 @@ class Rank:
         bytes_launch = (float(nsamp_all.sum()) * 8 * self.esz + float(nfev_all.sum()) * (2 * self.n * 4 + 20)) / self.n_sets
         b0_ = self.batches[0]
         return dict(mode=mode, elapsed=el, kernel_ms=kms / max(launches, 1), launches=launches, nfev_all=nfev_all, solo_ms=solo, solo_ms_range=solo_range,
-                    nsamp_all=nsamp_all, status_all=status_all, accepted_frac=float(accepted.mean()),
+                    nsamp_all=nsamp_all, status_all=status_all, accepted_frac=float(accepted.mean()), last_step=last_step,
                     bytes_launch=bytes_launch, mean_nit=float(b0_["nit"].float().mean().item()),
                     b0=dict(x=b0_["x"].clone(), last=b0_["last"].clone(), nfev=b0_["nfev"].clone()))
 
@@ -810,8 +838,12 @@ def main():
     esdf_build = R.esdf_build_time() if (rank == 0 and world == 1) else None
 
     t_gpu0 = time.time()
-    main_run = R.time_mode(a.dtype)
+    main_run = R.time_mode(a.dtype, keep=bool(a.dump_outputs) and rank == 0)
     elapsed = main_run["elapsed"]
+    last_step = main_run.pop("last_step")
+    if last_step is not None:
+        dump_outputs(a.dump_outputs, last_step)
+        del last_step
     # the same steps with the D2H copy of every batch's final points and statuses behind its launch (one GPU, full reports)
     host_visible = R.time_mode(a.dtype, d2h=True)["elapsed"] if (world == 1 and rank == 0 and not a.no_report) else None
     rank_rate = B * n_sets * a.steps / elapsed
@@ -938,6 +970,12 @@ def dry_run(a, rank, world, n):
     os.environ.setdefault("MASTER_PORT", "29517")
     backend = "gloo" if a.dist_backend == "nccl" else a.dist_backend
     dist_.init_process_group(backend, rank=rank, world_size=world)
+
+    def fence():
+        # a barrier made of a CPU collective: dist.barrier() asks torch for the machine's accelerator, which starts HIP
+        # (and opens the GPU) in every rank of this GPU-free run
+        dist_.all_reduce(torch.zeros(1))
+
     B = 64
     x = torch.full((B, n), float(rank), dtype=torch.float64)
     scenes = None
@@ -951,11 +989,11 @@ def dry_run(a, rank, world, n):
         x[:, 1] = (rank * scenes + torch.arange(scenes, dtype=torch.float64)).repeat_interleave(rows)
     costs = torch.ones(B, 4, dtype=torch.float64) * (rank + 1)
     w = torch.tensor([1.0, 1.0, 1.0, 10000.0], dtype=torch.float64)
-    dist_.barrier()
+    fence()
     t0 = time.perf_counter()
     for _ in range(a.steps):
         g = sharding.gather_results(sharding.pack_results(x, costs, w), world, force=True)
-    dist_.barrier()
+    fence()
     el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     dist_.all_reduce(el, op=dist_.ReduceOp.MAX)
     ok = all(float(g[r * B, 0]) == float(r) and abs(float(g[r * B, n]) - (r + 1) * 10003.0) < 1e-3 for r in range(world))
@@ -969,7 +1007,7 @@ def dry_run(a, rank, world, n):
                           "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * float(el) / max(a.steps, 1),
                           "dry_run": True, "ranks": dist_.get_world_size(), "gather_ok": bool(ok),
                           "dist_backend": backend, **extra}), flush=True)
-    dist_.barrier()
+    fence()
     dist_.destroy_process_group()
 
 
