@@ -2,17 +2,20 @@
 """
 bench.py -- trajectories/sec of the batched replan inner loop on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` without a torch.distributed environment launches the N ranks itself (one child process per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set for each, rendezvous on 127.0.0.1) before anything touches a GPU.
 
-This file holds the driver contract only: the workload, the timed region, the roofline figure of the dominant kernel
-from HIP events, the CPU baseline, and ONE COMPACT JSON line (< 4 KB; `compact_line`, size-tested on the CPU).
-Everything else a one-GPU run reports -- the other arithmetic modes' parity tables, the retry chain, the stand-alone
-ESDF-lookup kernel's layouts / orders, cfg1, the reference-fixture replays, the CPU-vs-CPU controls -- is produced by
-tools/bench_report.py and written to the side file the line names (`"details"`), never to stdout.
+A plain run does only what the headline figure needs: it sets up the workload, runs W warm-up and K timed steps, writes
+`--dump-outputs` if asked, and prints ONE COMPACT JSON line (< 4 KB; `compact_line`, size-tested on the CPU) with the
+driver contract and the roofline figure of the dominant kernel from the HIP events of the timed steps.
+`--full` adds everything else, all of it outside the timed region: the other arithmetic modes, the D2H-inclusive rate,
+launches alone on the chip, the ESDF build time, the CPU baseline and cpu_native (a HIP-free child process), the counter
+traffic of committed profiles, and the sections of tools/bench_report.py -- the other modes' parity tables, the retry
+chain, the stand-alone ESDF-lookup kernel's layouts / orders, cfg1, the reference-fixture replays, the CPU-vs-CPU
+controls.  A full run writes its whole report to the side file the line names (`"details"`), never to stdout.
 
 Workload (config.workload): BASELINE.json configs[1] -- per GPU one 300^3-voxel fp32 ESDF of a synthetic
 random-forest scene (pillars + floating canopy boxes) resident in HBM in the corner-brick layout
@@ -27,13 +30,14 @@ every batch are gathered with one RCCL all_gather inside the timed region.
 
 Arithmetic modes: `--dtype f32x` (default, the headline: BASELINE.json's cfg2 is an fp32
 configuration) computes everything in fp32; `f32` keeps the coefficient solve, adjoint and optimiser in fp64; `f64` is
-the parity mode (`value_parity_mode`).  With one GPU all three are timed in the same run under the same protocol.
+the parity mode (`value_parity_mode`).  With one GPU and `--full` all three are timed in the same run under the same
+protocol.
 
 The compact line: the driver contract keys, `config`, `roofline` (dominant kernel = optimize_kernel; achieved =
 algorithmic bytes per launch -- samples visited x 8 corners x e B + evaluations x (2 n 4 + 20) B, SURVEY.md 8.d2 -- over
-the mean launch duration from HIP events on the kernel's stream), `esdf_kernel` (the ESDF-lookup kernel alone),
-`cpu_baseline` (the loop-faithful NumPy / SciPy port on the usable host cores, bounded sample), `cpu_native`, `modes`,
-`single_batch_traj_per_s`, `details`.
+the mean launch duration from HIP events on the kernel's stream), `modes`; with `--full` also `esdf_kernel` (the
+ESDF-lookup kernel alone), `cpu_baseline` (the loop-faithful NumPy / SciPy port on the usable host cores, bounded
+sample), `cpu_native`, `single_batch_traj_per_s`, `details`.
 """
 import argparse
 import ctypes
@@ -77,15 +81,20 @@ def parse(argv=None):
     ap.add_argument("--layout", default="brick", choices=["linear", "yz4", "cell8", "brick"],
                     help="voxel order of the field in HBM (include/neo_planner.h NEO_LAYOUT_*); brick = one 128-byte line per block "
                          "of 2 x 2 x 2 cells (default since round 4), yz4 = the round-2/3 default: one line per 8 cells along x")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="wall budget of the NumPy-port sample")
-    ap.add_argument("--native-seconds", type=float, default=4.0, help="wall budget of each cpu_native run")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-retries", action="store_true", help="skip the warm_start_plan retry-chain measurement")
-    ap.add_argument("--no-modes", action="store_true", help="time only the --dtype mode (cfg2 on one GPU times all three)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other arithmetic modes, the D2H-inclusive rate, launches alone, the ESDF "
+                         "build time, the CPU baselines and tools/bench_report.py's sections, plus the side file of the whole "
+                         "report (a plain run times the steps and prints the line, nothing else)")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="wall budget of the NumPy-port sample (--full)")
+    ap.add_argument("--native-seconds", type=float, default=4.0, help="wall budget of each cpu_native run (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-retries", action="store_true", help="--full without the warm_start_plan retry-chain measurement")
+    ap.add_argument("--no-modes", action="store_true",
+                    help="--full times only the --dtype mode (cfg2 on one GPU otherwise times all three)")
     ap.add_argument("--no-report", action="store_true",
-                    help="the timed region and the compact line only: nothing of tools/bench_report.py runs")
+                    help="--full without tools/bench_report.py: nothing of it runs")
     ap.add_argument("--report-sections", default="all",
-                    help="comma list of tools/bench_report.py sections to run: retries, budget, esdf, cfg1, parity (default all); "
+                    help="comma list of tools/bench_report.py sections a --full run runs: retries, budget, esdf, cfg1, parity (default all); "
                          "profile runs ask for `esdf` alone so that the counters of a launch shape belong to one kind of launch")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the timed path returned in its last timed step to DIR/<name>.npy (float64; rank 0; "
@@ -515,7 +524,7 @@ class Rank:
         self.ctx = ctx = npa.Context(local_rank, stream=tstream.cuda_stream)
         self.bp = self.planner_for(a.dtype)
         self.bp._sync()
-        self.want_cpu = world == 1 and rank == 0 and not a.no_cpu
+        self.want_cpu = a.full and world == 1 and rank == 0 and not a.no_cpu
         self.g3 = npa.ESDF3D.from_occupancy(torch.from_numpy(self.occ).to(dev), self.res, synth.DOMAIN_ORIGIN, store=self.store,
                                             layout=a.layout, ctx=ctx, want_dist=self.want_cpu)
         self.slots = None
@@ -723,7 +732,7 @@ class Rank:
         # batches, each launched by itself (round 5; batch 0 alone moved 6.05 -> 6.99 ms with a change that made every
         # evaluation faster), the range beside it.
         solo, solo_range = None, None
-        if self.rank == 0 and not self.use_dist:
+        if a.full and self.rank == 0 and not self.use_dist:
             each = []
             for bt in self.batches[:8]:
                 ctx.check(ctx.lib.neo_profile_reset(ctx.h))
@@ -826,16 +835,16 @@ def main():
         return dry_run(a, rank, world, 3 * a.waypoints + a.waypoints + 1)
     a.default_workload = (a.config == "cfg2" and a.batch == 4096 and a.waypoints == 20 and a.grid == 300
                           and a.dtype == "f32x" and a.layout == "brick" and not a.planar)
-    # one GPU, cfg2: all three arithmetic modes are timed under the same protocol
+    # one GPU, cfg2, --full: all three arithmetic modes are timed under the same protocol
     modes = [a.dtype] + ([m_ for m_ in ("f32x", "f32", "f64") if m_ != a.dtype]
-                         if (a.config == "cfg2" and world == 1 and not a.no_modes) else [])
+                         if (a.full and a.config == "cfg2" and world == 1 and not a.no_modes) else [])
     R = Rank(a, rank, local_rank, world, use_dist)
     torch, dist_ = R.torch, R.dist
     B, M, D, n, n_sets = R.B, R.M, R.D, R.n, R.n_sets
     report = None
-    if rank == 0 and not a.no_report:
+    if a.full and rank == 0 and not a.no_report:
         import bench_report as report
-    esdf_build = R.esdf_build_time() if (rank == 0 and world == 1) else None
+    esdf_build = R.esdf_build_time() if (a.full and rank == 0 and world == 1) else None
 
     t_gpu0 = time.time()
     main_run = R.time_mode(a.dtype, keep=bool(a.dump_outputs) and rank == 0)
@@ -845,7 +854,7 @@ def main():
         dump_outputs(a.dump_outputs, last_step)
         del last_step
     # the same steps with the D2H copy of every batch's final points and statuses behind its launch (one GPU, full reports)
-    host_visible = R.time_mode(a.dtype, d2h=True)["elapsed"] if (world == 1 and rank == 0 and not a.no_report) else None
+    host_visible = R.time_mode(a.dtype, d2h=True)["elapsed"] if (a.full and world == 1 and rank == 0 and not a.no_report) else None
     rank_rate = B * n_sets * a.steps / elapsed
     rccl_ranks, per_rank, gather_ok = None, None, None
     if use_dist:
@@ -947,7 +956,7 @@ def main():
             out["cpu_native"] = cpu_out["cpu_native"]
         if report:
             report.extend(R, out, mode_runs, cpu_out, arr)
-        details = write_details(a, out)
+        details = write_details(a, out) if (a.full or a.details) else None
         # RCCL prints a version banner through C stdio; push it out first so that the JSON is the last line
         try:
             ctypes.CDLL(None).fflush(None)

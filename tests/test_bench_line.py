@@ -106,3 +106,14 @@ def test_traffic_figures_come_only_from_a_profile_of_this_workload_and_kernel():
     R2.kernel_symbol = lambda name: "void neo::optimize_kernel<3, 2, double"
     t2 = bench_report.kernel_traffic(R2, "optimize_kernel@4096")
     assert t2["source"] is None or ("r05" not in t2["source"] and "r06" not in t2["source"])
+
+
+def test_full_is_off_by_default_and_not_part_of_the_workload():
+    """`--full` adds measurements outside the timed region: a plain run is the default, and a committed counter profile of a
+    `--full` command belongs to the same workload as a plain run of the same flags"""
+    import bench
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import bench_report
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    assert bench_report.command_workload("python3 bench.py --full --steps 3") == bench_report.command_workload("bench.py")
+    assert bench_report.command_workload("bench.py --full --config cfg5") != bench_report.command_workload("bench.py")

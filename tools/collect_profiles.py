@@ -64,7 +64,7 @@ def main():
     extra = [a for a in args if a != "--trace-only"]
     os.makedirs(out, exist_ok=True)
     os.environ["TMPDIR"] = "/tmp"
-    bench = ["python3", "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-modes", "--no-retries",
+    bench = ["python3", "bench.py", "--steps", "3", "--warmup", "1", "--full", "--no-cpu", "--no-modes", "--no-retries",
              "--report-sections", "esdf"] + extra
     d = os.path.join(out, "trace")
     rc = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] + bench,

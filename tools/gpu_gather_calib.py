@@ -74,7 +74,7 @@ def main():
             if k in row["Kernel_Name"]:
                 return f"{k}@{int(row['Grid_Size']) // max(int(row['Workgroup_Size']), 1)}"
         return None
-    c = counters(["python3", "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-modes"], out, "bench", match)
+    c = counters(["python3", "bench.py", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-modes"], out, "bench", match)
     for k, v in c.items():
         v["rdreq_bytes"] = true_bytes(v)
         v["fetch_size_bytes"] = v.get("FETCH_SIZE", 0) * 1024
