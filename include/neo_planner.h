@@ -302,19 +302,23 @@ int neo_optimize_sample_counter(neo_ctx *ctx, int64_t *dev_counts);
  * counts and status are stored -- for each trajectory it completes.  A host that sees the counter reach k may copy the result
  * arrays on another stream: the k finished trajectories are final (preset status[] to -1 to tell them apart, and copy status[]
  * FIRST: a trajectory marked finished in that copy is final in every array copied after it), bit for bit what the
- * completed launch leaves.  NULL switches it off.  Plain launches of optimize_kernel only (not the
- * lane-group kernel, not budgeted launches -- which exist to END a launch early instead). */
+ * completed launch leaves.  NULL switches it off.  Plain launches of optimize_kernel only: while a counter is set, a
+ * launch that would run the lane-group kernel (NEO_FLAG_LANE_GROUPS) and every neo_optimize_batch_budget_dev call (budgeted
+ * launches exist to END a launch early instead) return NEO_ERR_INVALID with a neo_last_error message, before anything is
+ * launched; the context stays usable. */
 int neo_optimize_progress_counter(neo_ctx *ctx, int32_t *counter);
 /* diagnostics: optional DEVICE array [B][cap][4] that the next neo_optimize_batch[_dev] launches fill with one record
  * per counted evaluation of every trajectory -- (f, line-search step, quadrature samples, iteration) -- so that a run
  * can be laid beside the CPU optimiser's evaluation by evaluation (tools/classify_divergence.py); NULL switches it off.
- * Not supported by the lane-group kernel. */
+ * Not supported by the lane-group kernel: while a trace (or trace_xg) is set, a launch that would run it
+ * (NEO_FLAG_LANE_GROUPS) returns NEO_ERR_INVALID with a neo_last_error message, before anything is launched; budgeted
+ * launches refuse it the same way. */
 int neo_optimize_trace(neo_ctx *ctx, double *dev_trace, int cap);
 /* diagnostics: optional DEVICE array [B][cap][2][n] that receives, per counted evaluation, the evaluated point x_k
  * and its gradient g_k (as doubles, whatever arithmetic the kernel ran in).  With neo_optimize_trace's (f, step, ...)
  * records this is everything needed to re-evaluate a device run point by point on the CPU oracle and to re-derive
  * every line-search / restart decision on the host (tests/test_gpu_replay.py).  `cap` must equal neo_optimize_trace's
- * when both are on; NULL switches it off.  Not supported by the lane-group kernel. */
+ * when both are on; NULL switches it off.  Refused like neo_optimize_trace by lane-group and budgeted launches. */
 int neo_optimize_trace_xg(neo_ctx *ctx, double *dev_xg, int cap);
 /* optional DEVICE permutation [B] for the next neo_optimize_batch_dev launches: workgroup i works on
  * trajectory order[i].  Results stay in the caller's order.  Workgroups start in index order, so
@@ -327,7 +331,8 @@ int neo_optimize_trace_xg(neo_ctx *ctx, double *dev_xg, int cap);
 int neo_optimize_dispatch_order(neo_ctx *ctx, const int32_t *dev_order, int B);
 /* the expected-effort order computed ON THE DEVICE from a batch's resident start points (round 6): key = time slack of the
  * guess, sum(T) v_max / |goal - start|, largest first, ties by index -- what neo_planner_amd.BatchPlanner.expected_effort_order
- * computes on the host: a keys kernel and a stable descending radix sort (rocPRIM) on the context's stream.  `scratch`
+ * computes on the host (a key that is not finite -- NaN or infinite start, goal or duration -- is 0 on both): a keys kernel and
+ * a stable descending radix sort (rocPRIM) on the context's stream.  `scratch`
  * (neo_effort_order_scratch_bytes(B) bytes, 256-byte aligned; the B keys stay in its first B doubles) and order[B] are the
  * caller's device buffers (several batches in flight on several streams: one pair per batch).  Hand `order` to
  * neo_optimize_dispatch_order. */

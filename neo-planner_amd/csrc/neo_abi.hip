@@ -858,12 +858,19 @@ int fail_locked(neo_ctx *c, int code, const char *msg) {
   return fail(c, code, msg);
 }
 
+// dispatch_opt sends this launch to the lane-group kernel (several small trajectories per wavefront, opt-in):
+// on the reference's own map small planar problems (M = 3 -> n = 7), on 3-D fields small problems in fp32 sampling
+bool lane_group_launch(const neo_ctx *c, int kind, int layout, int D, const OptArgs &a) {
+  if (!(c->params.flags & NEO_FLAG_LANE_GROUPS) || a.slots || a.M > 16 || D * (a.M - 1) + a.M > 32) return false;
+  if (kind == 0) return D == 2;
+  return D == 3 && c->params.sample_dtype == NEO_F32 &&
+         (layout == NEO_LAYOUT_LINEAR || layout == NEO_LAYOUT_YZ4 || layout == NEO_LAYOUT_BRICK);
+}
+
 int dispatch_opt(neo_ctx *c, int kind, int elem, int layout, int D, const OptArgs &a) {
   const bool f32 = c->params.sample_dtype == NEO_F32;
   if (kind == 0) {
-    // small planar problems on the reference's own map (M = 3 -> n = 7): eight replans per wavefront, opt-in
-    if ((c->params.flags & NEO_FLAG_LANE_GROUPS) && D == 2 && !a.slots && a.M <= 16 && D * (a.M - 1) + a.M <= 32)
-      return launch_opt_groups_2d(c, f32, a);
+    if (lane_group_launch(c, kind, layout, D, a)) return launch_opt_groups_2d(c, f32, a);
     const int fl2 = c->params.flags;
     // all-fp32 mode on the reference's own map: the timed arithmetic, pinned to the reference's fixtures there
     if ((fl2 & NEO_FLAG_F32_SOLVE) && f32) return launch_opt_2d_x(c, D, a);
@@ -875,9 +882,7 @@ int dispatch_opt(neo_ctx *c, int kind, int elem, int layout, int D, const OptArg
   }
   if (D != 3) return fail(c, NEO_ERR_INVALID, "a 3-D map needs D = 3");
   const int fl = c->params.flags;
-  if ((fl & NEO_FLAG_LANE_GROUPS) && f32 && (layout == NEO_LAYOUT_LINEAR || layout == NEO_LAYOUT_YZ4 || layout == NEO_LAYOUT_BRICK) && !a.slots &&
-      a.M <= 16 && D * (a.M - 1) + a.M <= 32)
-    return launch_opt_groups(c, elem, layout, a);
+  if (lane_group_launch(c, kind, layout, D, a)) return launch_opt_groups(c, elem, layout, a);
   if ((fl & NEO_FLAG_F32_SOLVE) && f32) return launch_opt_3d_x(c, elem, layout, a);  // all-fp32 mode
   // two trajectories per SIMD for calls that queue for the SIMDs anyway (3-D fields, fp32 sampling; beyond n = 128 with
   // the pairs stored in fp32 so that eight wavefronts still fit a CU's LDS, neo_kernels.hpp pairs_in_f32)
@@ -1589,8 +1594,13 @@ int neo_optimize_batch_from_dev(neo_ctx *c, int scene_id, const int32_t *scene_i
     const char *base = static_cast<const char *>(kind == 0 ? c->table2d : c->table3d);
     table = base + (size_t)it->second.slot * (kind == 0 ? sizeof(Map2D) : sizeof(Map3D));
   }
-  ProfScope ps(c, NEO_KERNEL_OPTIMIZE);
   const OptArgs oa{B, M, table, slots, nmaps, x0, x, head, tail, costs4, costs4_last, nit, nfev, status};
+  // the lane-group kernel records no evaluations and counts no finished trajectories: refuse instead of leaving the
+  // caller's trace zero-filled and its progress counter still
+  if (lane_group_launch(c, kind, layout, D, oa) && (c->trace || c->trace_xg || c->progress))
+    return fail(c, NEO_ERR_INVALID, "lane-group launch (NEO_FLAG_LANE_GROUPS): neo_optimize_trace, neo_optimize_trace_xg "
+                                    "and neo_optimize_progress_counter are not supported");
+  ProfScope ps(c, NEO_KERNEL_OPTIMIZE);
   rc = dispatch_opt(c, kind, elem, layout, D, oa);
   if (rc) return rc;
   HIPCHK(c, hipGetLastError());
@@ -1621,6 +1631,8 @@ int neo_optimize_batch_budget_dev(neo_ctx *c, int scene_id, int B, int M, int D,
   if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "no ESDF for this scene");
   if (it->second.kind == 0 || D != 3) return fail(c, NEO_ERR_INVALID, "budgeted launches: 3-D fields, D = 3");
   if (c->trace || c->trace_xg) return fail(c, NEO_ERR_INVALID, "budgeted launches do not record traces");
+  if (c->progress)
+    return fail(c, NEO_ERR_INVALID, "budgeted launches do not count finished trajectories (neo_optimize_progress_counter)");
   const char *base = static_cast<const char *>(c->table3d);
   const void *table = base + (size_t)it->second.slot * sizeof(Map3D);
   ProfScope ps(c, NEO_KERNEL_OPTIMIZE);
@@ -1919,7 +1931,7 @@ int neo_pack_results_dev(neo_ctx *c, int B, int n, const double *x, const double
 namespace neo {
 // ---- the expected-effort dispatch order on the device (round 6; host form: BatchPlanner.expected_effort_order)
 // key = time slack of the initial guess, sum(T) v_max / |goal - start| (a guess that is far too slow sheds duration over many
-// iterations: rank correlation 0.5 with the evaluation count at cfg2); NaN -> 0 so that the keys are totally ordered
+// iterations: rank correlation 0.5 with the evaluation count at cfg2); a non-finite key -> 0 so that the keys are totally ordered
 __global__ void effort_keys_kernel(int B, int M, int D, double T_min, double T_max, double v_max, const double *__restrict__ x0,
                                    const double *__restrict__ head, const double *__restrict__ tail, double *__restrict__ keys,
                                    int *__restrict__ idx) {
@@ -1934,8 +1946,10 @@ __global__ void effort_keys_kernel(int B, int M, int D, double T_min, double T_m
     const double e = tail[(size_t)b * 3 * D + d] - head[(size_t)b * 3 * D + d];
     d2 += e * e;
   }
-  const double k = sum * v_max / fmax(sqrt(d2), 1e-9);
-  keys[b] = (k == k) ? k : 0.0;
+  // (fmax drops a NaN distance: it must reach the key, which then is non-finite like the host's -> 0)
+  const double dist = sqrt(d2);
+  const double k = dist == dist ? sum * v_max / fmax(dist, 1e-9) : NAN;
+  keys[b] = isfinite(k) ? k : 0.0;
 }
 }  // namespace neo
 

@@ -687,10 +687,13 @@ class BatchPlanner:
     def expected_effort_order(self, head, tail, ts):
         """permutation that starts the runs expected to be long first.  Proxy: time slack of the initial
         guess, sum(ts) * v_max / distance -- a guess that is far too slow needs many iterations to shed
-        duration (measured on the cfg2 batch: rank correlation 0.5 with the evaluation count)."""
+        duration (measured on the cfg2 batch: rank correlation 0.5 with the evaluation count).  A non-finite key (NaN or
+        infinite start, goal or duration) is 0, as on the device (neo_effort_order_dev): such runs start last, in index order."""
         head = np.asarray(head); tail = np.asarray(tail); ts = np.asarray(ts)
-        dist = np.linalg.norm(tail[:, 0] - head[:, 0], axis=1)
-        slack = ts.sum(axis=1) * self.cfg.v_max / np.maximum(dist, 1e-9)
+        with np.errstate(invalid="ignore"):
+            dist = np.linalg.norm(tail[:, 0] - head[:, 0], axis=1)
+            slack = ts.sum(axis=1) * self.cfg.v_max / np.maximum(dist, 1e-9)
+        slack[~np.isfinite(slack)] = 0.0
         return np.argsort(-slack, kind="stable").astype(np.int32)
 
     def expected_effort_order_dev(self, x0, head, tail):

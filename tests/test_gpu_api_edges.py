@@ -778,3 +778,20 @@ def test_effort_order_on_the_device_is_the_host_order():
         assert np.allclose(keys[ok], slack[ok], rtol=1e-13, atol=0)
         if B > 100:
             assert keys[7] == 0.0 and order[-1] == 7 or keys[order[-1]] == 0.0
+    # non-finite endpoints: the key is 0 on both sides (include/neo_planner.h), so the device's permutation IS the host's --
+    # a NaN head, a NaN tail, an infinite head, head and tail both infinite (inf - inf)
+    for D in (3, 2):
+        B, M = 12, 5
+        head, tail, wp, ts = synth.replan_requests(9, B, M - 1, D=D, **(synth.VOLUME if D == 3 else {}))
+        head[2, 0, 1] = np.nan
+        tail[5, 0, 0] = np.nan
+        head[7, 0, D - 1] = np.inf
+        head[9, 0, 0] = tail[9, 0, 0] = np.inf
+        bp = npa.BatchPlanner(sample_dtype="f32")
+        x0 = bp.pack_x(wp, ts)
+        order, keys = bp.expected_effort_order_dev(torch.from_numpy(x0).to(dev), torch.from_numpy(head).to(dev),
+                                                   torch.from_numpy(tail).to(dev))
+        torch.cuda.synchronize()
+        host = bp.expected_effort_order(head, tail, bp.unpack_x(x0, M, D)[1])
+        assert np.array_equal(order.cpu().numpy(), host), (D, order.cpu().numpy(), host)
+        assert np.all(keys.cpu().numpy()[[2, 5, 7, 9]] == 0.0) and host[-4:].tolist() == [2, 5, 7, 9]

@@ -172,3 +172,107 @@ def test_optimize_progressive_yields_every_trajectory_once_with_optimize_s_bits(
     assert chunks[0] >= B // 2 and len(chunks) >= 2            # (the first hand-over holds at least half of the batch)
     for k in ref:
         assert np.array_equal(got[k], ref[k]), k
+
+
+def test_launches_that_cannot_honour_a_trace_or_a_progress_counter_are_refused():
+    """The lane-group kernel records no evaluations and counts no finished trajectories, a budgeted launch counts none:
+    with neo_optimize_trace, _trace_xg or neo_optimize_progress_counter set such a launch returns NEO_ERR_INVALID with a
+    message before anything runs (include/neo_planner.h) -- the caller's trace stays untouched, the counter 0 -- and the
+    context goes on working: a plain launch afterwards is bit for bit one on a fresh context.
+    BatchPlanner.optimize_progressive on a lane-group planner then raises instead of polling a counter that never moves."""
+    import torch
+    NEO_ERR_INVALID = 1
+    ctx, g3 = _scene("brick")
+    dev = torch.device("cuda", 0)
+    pp = lambda v: ctypes.c_void_p(v.data_ptr())
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    m2 = npa.ESDF(ctx=ctx)
+    m2.occupancy_map_cb(synth.OccupancyGridMsg(synth.occupancy_2d(1)))
+
+    def bufs(B, n):
+        return dict(x=torch.zeros(B, n, dtype=torch.float64, device=dev), costs=torch.zeros(B, 4, dtype=torch.float64, device=dev),
+                    last=torch.zeros(B, 4, dtype=torch.float64, device=dev), nit=torch.zeros(B, dtype=torch.int32, device=dev),
+                    nfev=torch.zeros(B, dtype=torch.int32, device=dev), status=torch.full((B,), -1, dtype=torch.int32, device=dev))
+
+    def launch(c, scene, bp, x0, h, tl, o):
+        B, n = x0.shape
+        bp._sync()
+        return c.lib.neo_optimize_batch_from_dev(c.h, scene.scene_id, None, B, (n + h.shape[2]) // (h.shape[2] + 1),
+                                                 h.shape[2], pp(x0), pp(o["x"]), pp(h), pp(tl), pp(o["costs"]),
+                                                 pp(o["last"]), pp(o["nit"]), pp(o["nfev"]), pp(o["status"]))
+
+    B, CAP = 16, 8
+    cases = []
+    for D, scene, mode in ((3, g3, "f32x"), (3, g3, "f32"), (2, m2, "f64")):     # launch_opt_groups / launch_opt_groups_2d
+        head, tail, wp, ts = synth.replan_requests(12, B, 2, D=D, **(synth.VOLUME if D == 3 else {}))
+        grp = npa.BatchPlanner(ctx=ctx, sample_dtype=mode, lane_groups=True)
+        cases.append((scene, grp, t(grp.pack_x(wp, ts)), t(head), t(tail)))
+    for scene, grp, x0, h, tl in cases:
+        n = x0.shape[1]
+        tr = torch.zeros(B, CAP, 4, dtype=torch.float64, device=dev)
+        xg = torch.zeros(B, CAP, 2, n, dtype=torch.float64, device=dev)
+        counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        for name, on, off in (("trace", lambda: ctx.lib.neo_optimize_trace(ctx.h, pp(tr), CAP),
+                               lambda: ctx.lib.neo_optimize_trace(ctx.h, None, 0)),
+                              ("trace_xg", lambda: ctx.lib.neo_optimize_trace_xg(ctx.h, pp(xg), CAP),
+                               lambda: ctx.lib.neo_optimize_trace_xg(ctx.h, None, 0)),
+                              ("progress", lambda: ctx.lib.neo_optimize_progress_counter(ctx.h, pp(counter)),
+                               lambda: ctx.lib.neo_optimize_progress_counter(ctx.h, None))):
+            o = bufs(B, n)
+            torch.cuda.synchronize()
+            ctx.check(on())
+            try:
+                rc = launch(ctx, scene, grp, x0, h, tl, o)
+                msg = ctx.lib.neo_last_error(ctx.h).decode()
+            finally:
+                ctx.check(off())
+            ctx.synchronize()
+            assert rc == NEO_ERR_INVALID and "lane-group" in msg, (name, rc, msg)
+            assert torch.all(o["status"] == -1) and torch.all(o["nfev"] == 0), name          # nothing ran
+        assert not tr.any() and not xg.any() and int(counter[0]) == 0
+    # a budgeted launch with the progress counter set
+    head, tail, wp, ts = synth.replan_requests(13, B, 20, D=3, **synth.VOLUME)
+    bp = npa.BatchPlanner(ctx=ctx, sample_dtype="f32x")
+    bp._sync()
+    x0 = t(bp.pack_x(wp, ts)); h = t(head); tl = t(tail)
+    o = bufs(B, x0.shape[1])
+    state = torch.zeros(B * int(ctx.lib.neo_optimize_state_bytes(21, 3)), dtype=torch.uint8, device=dev)
+    counter = torch.zeros(1, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    ctx.check(ctx.lib.neo_optimize_progress_counter(ctx.h, pp(counter)))
+    try:
+        rc = ctx.lib.neo_optimize_batch_budget_dev(ctx.h, g3.scene_id, B, 21, 3, pp(x0), pp(o["x"]), pp(h), pp(tl), pp(o["costs"]),
+                                                   pp(o["last"]), pp(o["nit"]), pp(o["nfev"]), pp(o["status"]), pp(state), 5,
+                                                   None, 0, 0)
+        msg = ctx.lib.neo_last_error(ctx.h).decode()
+    finally:
+        ctx.check(ctx.lib.neo_optimize_progress_counter(ctx.h, None))
+    ctx.synchronize()
+    assert rc == NEO_ERR_INVALID and "progress" in msg, (rc, msg)
+    assert torch.all(o["status"] == -1) and int(counter[0]) == 0
+    # the context still works: plain, lane-group and budgeted launches afterwards are those of a fresh context, bit for bit
+    ctx2, g3b = _scene("brick")
+    m2b = npa.ESDF(ctx=ctx2)
+    m2b.occupancy_map_cb(synth.OccupancyGridMsg(synth.occupancy_2d(1)))
+    for scene, scene_b, planner, x0_, h_, tl_ in [(g3, g3b, bp, x0, h, tl)] + \
+            [(s, g3b if s is g3 else m2b, p, a, b, c) for s, p, a, b, c in cases]:
+        fresh = npa.BatchPlanner(ctx=ctx2, sample_dtype="f32x" if planner.all_f32 else planner.sample_dtype,
+                                 lane_groups=bool(planner.flags & _lib.NEO_FLAG_LANE_GROUPS))
+        a, b = bufs(*x0_.shape), bufs(*x0_.shape)
+        torch.cuda.synchronize()
+        ctx.check(launch(ctx, scene, planner, x0_, h_, tl_, a))
+        ctx2.check(launch(ctx2, scene_b, fresh, x0_, h_, tl_, b))
+        ctx.synchronize(); ctx2.synchronize()
+        assert torch.all(a["status"] != -1)
+        for k in a:
+            assert torch.equal(a[k], b[k]), k
+    got = bp.optimize_budgeted(g3, x0.cpu().numpy(), head, tail, 7)
+    ref = bp.optimize(g3, x0.cpu().numpy(), head, tail, order=False)
+    for k in ("x", "costs", "nfev", "status"):
+        assert np.array_equal(got[k], ref[k]), k
+    # only now that the refusal is known to work (without it this would poll forever): the generator raises
+    grp = cases[0][1]
+    head, tail, wp, ts = synth.replan_requests(12, B, 2, D=3, **synth.VOLUME)
+    with pytest.raises(_lib.NeoError, match="lane-group"):
+        for _ in grp.optimize_progressive(g3, grp.pack_x(wp, ts), head, tail):
+            pass

@@ -85,6 +85,27 @@ def test_batch_pack_unpack():
     assert np.array_equal(w2, wp) and np.allclose(t2, ts, rtol=1e-14)
 
 
+def test_effort_order_puts_non_finite_keys_last_in_index_order():
+    """BatchPlanner.expected_effort_order: a request whose key sum(T) v_max / |goal - start| is not finite -- a NaN head or
+    tail, an infinite head, head and tail both infinite (inf - inf) -- has key 0 (include/neo_planner.h, the device's rule):
+    it starts after every finite key and the zero keys keep index order"""
+    bp = npa.BatchPlanner()
+    head, tail, wp, ts = synth.replan_requests(3, 9, 4, D=3)
+    head[2, 0, 1] = np.nan
+    tail[4, 0, 0] = np.nan
+    head[5, 0, 2] = np.inf
+    head[7, 0, 0] = tail[7, 0, 0] = np.inf
+    order = bp.expected_effort_order(head, tail, ts)
+    finite = [0, 1, 3, 6, 8]
+    dist = np.linalg.norm(tail[finite, 0] - head[finite, 0], axis=1)
+    slack = ts[finite].sum(axis=1) * bp.cfg.v_max / dist
+    assert np.all(slack > 0) and len(set(slack.tolist())) == len(finite)
+    assert order.tolist() == [finite[i] for i in np.argsort(-slack)] + [2, 4, 5, 7]
+    # a zero distance stays a finite (huge) key: it starts first
+    tail[6, 0] = head[6, 0]
+    assert bp.expected_effort_order(head, tail, ts)[0] == 6
+
+
 def test_synthetic_forest_is_deterministic_and_clear():
     a = synth.forest_boxes(4)
     assert a == synth.forest_boxes(4) and len(a) in (10, 15, 20)
@@ -144,3 +165,16 @@ def test_build_cache_is_keyed_by_content_not_by_time_stamps(tmp_path, monkeypatc
     monkeypatch.setattr(b, "_headers", real)
     monkeypatch.setenv("NEO_FP_CONTRACT", "fast")
     assert b._key() != k_lib                                                    # and so does a changed option
+
+
+def test_trace_parity_cases_reach_the_kernels_they_name():
+    """tests/test_gpu_trace_parity.py names, per row, the optimize_kernel instantiation dispatch_opt sends it to; the kernel
+    statistics of one profiled run of that file (profiles/trace_parity_kernel_stats.csv, rocprofv3 --kernel-trace --stats)
+    hold exactly those instantiations: every row reached the kernel it names, and no other optimize_kernel ran"""
+    import csv
+    import test_gpu_trace_parity as tp
+    named = {p.values[0]["inst"] for p in tp.CASES}
+    with open(os.path.join(REPO, "profiles", "trace_parity_kernel_stats.csv")) as f:
+        ran = {re.sub(r"^void ", "", row["Name"].split("(")[0]).replace("neo::", "")
+               for row in csv.DictReader(f) if "optimize_kernel<" in row["Name"]}
+    assert ran == named, (sorted(ran - named), sorted(named - ran))
