@@ -287,6 +287,53 @@ size_t neo_optimize_workspace_bytes(int B, int M, int D);
 int neo_eval_traj_batch(neo_ctx *ctx, int B, int M, int D, const double *x, const double *head,
                         const double *tail, double hz, int K, double *state, int32_t *count);
 
+/* ---- trajectory audit (ros_node/traj_planner_node.py:333-363: get_weighted_metric) ----
+ * The reference's flight metric of every planned trajectory under perfect tracking, one record per trajectory:
+ *   1. the coefficients are solved from x, head, tail as neo_eval_traj_batch solves them (fp64);
+ *   2. samples at t_k = k * (1 / hz), k < count[b] = len(np.arange(0, sum(T), 1/hz)) -- any number of them;
+ *   3. the sample states are those of neo_eval_traj_batch's rows at the same hz, bit for bit (same piece search,
+ *      same expressions);
+ *   4. d_k = the map's point lookup of the sample position in neo_esdf_query's arithmetic: the nearest cell on the
+ *      2-D reference map (the first two axes, as the sampled cost projects them; 10000 outside), trilinear on 3-D
+ *      fields (fp32 / fp16, every layout);
+ *   5. the record audit[b][NEO_AUDIT_FIELDS] of doubles (fields below), count[b] and flags[b] (NEO_AUDIT_FLAG_*).
+ * v_max, safe_dis and collision_cost_tol come from neo_params.  With D = 2 on the 2-D map every field is the
+ * reference's get_weighted_metric of the planned trajectory (sample interval metric_eva_interval = 0.1 s at hz = 10,
+ * :119; metric weights [1, 1, 100], :204).  D = 3 (3-D fields, or the 2-D map with the first two axes looked up) is this
+ * project's extension: the same formulas over all D axes.  The same call returns the same bits whatever the launch
+ * configuration; ties of MIN_CLEARANCE go to the earliest sample.
+ * Validity: hz must be finite and > 0, and M * T_max * hz < 2^30 (the most samples a trajectory can have); output
+ * buffers must not be NULL; the (map kind, D) pair must be (2-D, 2), (2-D, 3) or (3-D, 3).  NEO_ERR_INVALID with a
+ * neo_last_error message otherwise, before anything is launched.
+ * scene_ids, maps and slots as in neo_optimize_batch / neo_optimize_batch_dev (NULL = all use scene_id; one kind,
+ * element type and layout per call).  weights3: host pointer to the three metric weights, NULL = {1, 1, 100}. */
+enum {
+  NEO_AUDIT_PATH_LENGTH = 0,     /* sum_{k>=1} |p_k - p_{k-1}| over all D axes                        (:341-343) */
+  NEO_AUDIT_FEASIBILITY = 1,     /* sum_k (|v_k|^2 - v_max^2)^3 over the samples where it is > 0       (:346-348) */
+  NEO_AUDIT_COLLISION = 2,       /* sum_k (safe_dis - d_k)^3 over the samples where it is > 0          (:351-355) */
+  NEO_AUDIT_WEIGHTED = 3,        /* w0 * [0] + w1 * [1] + w2 * [2]                                     (:357)     */
+  NEO_AUDIT_MIN_CLEARANCE = 4,   /* min_k d_k (+inf without samples)                                              */
+  NEO_AUDIT_T_MIN_CLEARANCE = 5, /* t_k of the first sample attaining [4] (-1 without samples)                    */
+  NEO_AUDIT_MAX_SPEED = 6,       /* max_k |v_k|                                                                   */
+  NEO_AUDIT_MAX_ACC = 7,         /* max_k |a_k|                                                                   */
+  NEO_AUDIT_T_FIRST_UNSAFE = 8,  /* first t_k with d_k < safe_dis, or -1                                          */
+  NEO_AUDIT_DURATION = 9,        /* sum(T)                                                                        */
+  NEO_AUDIT_FIELDS = 10,
+};
+#define NEO_AUDIT_FLAG_UNSAFE 1      /* some d_k < safe_dis */
+#define NEO_AUDIT_FLAG_METRIC_FAIL 2 /* WEIGHTED > 10 * collision_cost_tol: the reference's failed flight (:359-361) */
+#define NEO_AUDIT_FLAG_OUTSIDE_MAP 4 /* some sample lies outside the map (its d_k is 10000) */
+#define NEO_AUDIT_FLAG_NONFINITE 8   /* the solve failed (exp(-tau) overflow), a state is not finite, or the map-table
+                                        slot is outside the table (_dev): every field NaN, count 0 */
+int neo_audit_traj_batch(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, int M, int D,
+                         const double *x, const double *head, const double *tail, double hz,
+                         const double *weights3, double *audit, int32_t *count, int32_t *flags);
+/* the same with DEVICE pointers, asynchronous on the context's stream; scene_ids is then a device array of map-table
+ * slots (neo_scene_slot) as in neo_optimize_batch_dev, and weights3 stays a host pointer */
+int neo_audit_traj_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, int M, int D,
+                             const double *x, const double *head, const double *tail, double hz,
+                             const double *weights3, double *audit, int32_t *count, int32_t *flags);
+
 /* ---- timing of the device work (bench.py) ----------------------------------
  * When enabled, every kernel launch of the named family is bracketed by HIP events on
  * the context stream; neo_profile_read returns launches and summed milliseconds. */

@@ -1546,6 +1546,40 @@ int neo_sampled_terms_batch_f32(neo_ctx *c, int scene_id, int B, int M, int D, c
 // the L-BFGS pairs (2 * maxcor * n doubles per trajectory) live in LDS: no HBM workspace
 size_t neo_optimize_workspace_bytes(int, int, int) { return 0; }
 
+// the maps of a `_dev` call (neo_optimize_batch_from_dev, neo_audit_traj_batch_dev): with slots, the whole table of the
+// reference scene's kind -- one kernel instantiation serves the whole call, so every map a slot can name (all maps of
+// that kind in this context) must share its element type and layout; without, the one map of scene_id.
+// Call with the context locked and the tables rebuilt.
+struct CallMaps {
+  int kind = 0, elem = 0, layout = 0, nmaps = 1;
+  const void *table = nullptr;
+};
+static int resolve_call_maps(neo_ctx *c, int scene_id, bool with_slots, CallMaps &cm) {
+  if (with_slots) {
+    auto it = c->maps.find(scene_id);
+    if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "no ESDF for the reference scene");
+    cm.kind = it->second.kind;
+    cm.elem = it->second.elem;
+    cm.layout = it->second.m3.layout;
+    for (const auto &kv : c->maps)
+      if (kv.second.kind == cm.kind && (kv.second.elem != cm.elem || (cm.kind == 1 && kv.second.m3.layout != cm.layout)))
+        return fail(c, NEO_ERR_INVALID, "multi-scene call: the context holds maps of this kind with different element "
+                                        "types or layouts");
+    cm.table = cm.kind == 0 ? c->table2d : c->table3d;
+    cm.nmaps = cm.kind == 0 ? c->n2d : c->n3d;
+  } else {
+    auto it = c->maps.find(scene_id);
+    if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "no ESDF for this scene");
+    cm.kind = it->second.kind;
+    cm.elem = it->second.elem;
+    cm.layout = it->second.m3.layout;
+    const char *base = static_cast<const char *>(cm.kind == 0 ? c->table2d : c->table3d);
+    cm.table = base + (size_t)it->second.slot * (cm.kind == 0 ? sizeof(Map2D) : sizeof(Map3D));
+    cm.nmaps = 1;
+  }
+  return NEO_OK;
+}
+
 int neo_optimize_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, int M, int D, double *x,
                            const double *head, const double *tail, double *costs4, double *costs4_last, int32_t *nit,
                            int32_t *nfev, int32_t *status) {
@@ -1566,34 +1600,12 @@ int neo_optimize_batch_from_dev(neo_ctx *c, int scene_id, const int32_t *scene_i
   rc = rebuild_tables(c);
   if (rc) return rc;
   // scene_ids (device array) holds map-table SLOTS when given; a single scene_id is looked up here
-  int kind, elem, layout = 0;
-  const void *table;
+  CallMaps cm;
+  rc = resolve_call_maps(c, scene_id, scene_ids != nullptr, cm);
+  if (rc) return rc;
+  const int kind = cm.kind, elem = cm.elem, layout = cm.layout, nmaps = cm.nmaps;
+  const void *table = cm.table;
   const int *slots = scene_ids;
-  std::vector<int> one;
-  int nmaps = 1;
-  if (scene_ids) {
-    // one kernel instantiation serves the whole call: every map a slot can name (all maps of the reference
-    // scene's kind in this context) must share its element type and layout
-    auto it = c->maps.find(scene_id);
-    if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "no ESDF for the reference scene");
-    kind = it->second.kind;
-    elem = it->second.elem;
-    layout = it->second.m3.layout;
-    for (const auto &kv : c->maps)
-      if (kv.second.kind == kind && (kv.second.elem != elem || (kind == 1 && kv.second.m3.layout != layout)))
-        return fail(c, NEO_ERR_INVALID, "multi-scene call: the context holds maps of this kind with different element "
-                                        "types or layouts");
-    table = kind == 0 ? c->table2d : c->table3d;
-    nmaps = kind == 0 ? c->n2d : c->n3d;
-  } else {
-    auto it = c->maps.find(scene_id);
-    if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "no ESDF for this scene");
-    kind = it->second.kind;
-    elem = it->second.elem;
-    layout = it->second.m3.layout;
-    const char *base = static_cast<const char *>(kind == 0 ? c->table2d : c->table3d);
-    table = base + (size_t)it->second.slot * (kind == 0 ? sizeof(Map2D) : sizeof(Map3D));
-  }
   const OptArgs oa{B, M, table, slots, nmaps, x0, x, head, tail, costs4, costs4_last, nit, nfev, status};
   // the lane-group kernel records no evaluations and counts no finished trajectories: refuse instead of leaving the
   // caller's trace zero-filled and its progress counter still
@@ -1823,6 +1835,89 @@ int neo_eval_traj_batch(neo_ctx *c, int B, int M, int D, const double *x, const 
   }
   HIPCHK(c, hipMemcpyAsync(state, ds, bs * K * 3 * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(count, dcnt, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return NEO_OK;
+}
+
+// ---- trajectory audit (ros_node/traj_planner_node.py:333-363; kernel: neo_audit.hpp)
+// the argument checks both forms make before anything is copied or launched (context unlocked)
+static int audit_check(neo_ctx *c, int B, int M, int D, const double *x, const double *head, const double *tail, double hz,
+                       const double *audit, const int32_t *count, const int32_t *flags) {
+  int rc = check_shape(c, B, M, D);
+  if (rc) return rc;
+  if (!x || !head || !tail || !audit || !count || !flags) return fail_locked(c, NEO_ERR_INVALID, "audit: null buffer");
+  if (!std::isfinite(hz) || !(hz > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "audit: hz must be finite and > 0");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  // a trajectory lasts at most M * T_max: its sample count must fit the kernel's int range with room to spare
+  if (!((double)M * c->params.T_max * hz < (double)(1 << 30)))
+    return fail(c, NEO_ERR_INVALID, "audit: hz too large (M * T_max * hz must stay below 2^30 samples)");
+  return NEO_OK;
+}
+
+int neo_audit_traj_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, int M, int D, const double *x,
+                             const double *head, const double *tail, double hz, const double *weights3, double *audit,
+                             int32_t *count, int32_t *flags) {
+  int rc = audit_check(c, B, M, D, x, head, tail, hz, audit, count, flags);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  rc = rebuild_tables(c);
+  if (rc) return rc;
+  CallMaps cm;
+  rc = resolve_call_maps(c, scene_id, scene_ids != nullptr, cm);
+  if (rc) return rc;
+  if (cm.kind == 1 && D != 3) return fail(c, NEO_ERR_INVALID, "audit: a 3-D map needs D = 3");
+  if (B == 0) return NEO_OK;
+  AuditArgs aa{B, M, cm.table, scene_ids, cm.nmaps, x, head, tail, hz, {1.0, 1.0, 100.0}, audit, count, flags};
+  if (weights3)
+    for (int k = 0; k < 3; ++k) aa.w[k] = weights3[k];
+  rc = dispatch_audit(c, cm.kind, cm.elem, cm.layout, D, aa);
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+int neo_audit_traj_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, int M, int D, const double *x,
+                         const double *head, const double *tail, double hz, const double *weights3, double *audit,
+                         int32_t *count, int32_t *flags) {
+  int rc = audit_check(c, B, M, D, x, head, tail, hz, audit, count, flags);
+  if (rc) return rc;
+  if (B == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> whole_call(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  const size_t n = (size_t)D * (M - 1) + M, bs = (size_t)B;
+  std::vector<int> slots;
+  if (scene_ids) {  // scene ids -> map-table slots, as neo_optimize_batch
+    slots.resize(bs);
+    int kind0 = -1;
+    for (size_t i = 0; i < bs; ++i) {
+      const int s = neo_scene_slot(c, scene_ids[i]);
+      if (s < 0) return fail(c, NEO_ERR_NO_MAP, "no ESDF for one of scene_ids");
+      const int k = c->maps.find(scene_ids[i])->second.kind;
+      if (kind0 < 0) kind0 = k;
+      if (k != kind0) return fail(c, NEO_ERR_INVALID, "scene_ids mix 2-D and 3-D maps");
+      slots[i] = s;
+    }
+  }
+  rc = ensure_scratch(c, bs * (n + 6 * D + NEO_AUDIT_FIELDS) * sizeof(double) + 3 * bs * sizeof(int) + 7 * 256);
+  if (rc) return rc;
+  Carver cv(c->scratch);
+  double *dx = cv.take<double>(bs * n), *dh = cv.take<double>(bs * 3 * D), *dt = cv.take<double>(bs * 3 * D);
+  double *da = cv.take<double>(bs * NEO_AUDIT_FIELDS);
+  int *dslots = cv.take<int>(bs), *dcnt = cv.take<int>(bs), *dfl = cv.take<int>(bs);
+  HIPCHK(c, hipMemcpyAsync(dx, x, bs * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dh, head, bs * 3 * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dt, tail, bs * 3 * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (scene_ids) HIPCHK(c, hipMemcpyAsync(dslots, slots.data(), bs * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  rc = neo_audit_traj_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? dslots : nullptr, B, M, D, dx, dh, dt,
+                                hz, weights3, da, dcnt, dfl);
+  if (rc) {
+    hipStreamSynchronize(c->stream);  // (the slot copy in flight reads `slots`)
+    return rc;
+  }
+  HIPCHK(c, hipMemcpyAsync(audit, da, bs * NEO_AUDIT_FIELDS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(count, dcnt, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(flags, dfl, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return NEO_OK;
 }

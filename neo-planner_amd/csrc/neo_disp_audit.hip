@@ -1,0 +1,38 @@
+// neo_disp_audit.hip -- audit_kernel family: the reference's flight metric (ros_node/traj_planner_node.py:333-363) for a
+// batch of trajectories (neo_audit.hpp), one instantiation per map kind, D, element type and layout
+#include "neo_host.hpp"
+#include "neo_audit.hpp"
+
+namespace neo {
+
+template <int D, class MapT, class LookupT>
+static int launch_audit(neo_ctx *c, const AuditArgs &a) {
+  hipLaunchKernelGGL((audit_kernel<D, MapT, LookupT>), dim3(a.B), dim3(kWave), 0, c->stream, a.B, a.M, c->dev,
+                     static_cast<const MapT *>(a.table), a.slots, a.nmaps, a.x, a.head, a.tail, a.hz, a.w[0], a.w[1],
+                     a.w[2], a.audit, a.count, a.flags);
+  return NEO_OK;
+}
+
+template <typename E>
+static int launch_audit_3d(neo_ctx *c, int layout, const AuditArgs &a) {
+  switch (layout) {
+    case NEO_LAYOUT_LINEAR: return launch_audit<3, Map3D, Lookup3D<double, E, 0>>(c, a);
+    case NEO_LAYOUT_YZ4: return launch_audit<3, Map3D, Lookup3D<double, E, 1>>(c, a);
+    case NEO_LAYOUT_CELL8: return launch_audit<3, Map3D, Lookup3D<double, E, 2>>(c, a);
+    case NEO_LAYOUT_BRICK: return launch_audit<3, Map3D, Lookup3D<double, E, 3>>(c, a);
+    default: return fail(c, NEO_ERR_INVALID, "audit: unknown 3-D layout");
+  }
+}
+
+int dispatch_audit(neo_ctx *c, int kind, int elem, int layout, int D, const AuditArgs &a) {
+  if (kind == 0) {  // the 2-D reference map: D = 2, or D = 3 looked up on its first two axes (as the sampled cost does)
+    if (D == 2) return launch_audit<2, Map2D, Lookup2D<double>>(c, a);
+    return launch_audit<3, Map2D, Lookup2D<double>>(c, a);
+  }
+  if (D != 3) return fail(c, NEO_ERR_INVALID, "audit: a 3-D map needs D = 3");
+  if (elem == NEO_F32) return launch_audit_3d<float>(c, layout, a);
+  if (elem == NEO_F16) return launch_audit_3d<__half>(c, layout, a);
+  return fail(c, NEO_ERR_INVALID, "audit: unsupported 3-D element type");
+}
+
+}  // namespace neo

@@ -163,6 +163,18 @@ struct SampleArgs {
   bool io32 = false;      // neo_sampled_terms_batch_f32_dev (fp32 sampling only)
 };
 
+// neo_audit_traj_batch_dev: one audit_kernel launch (neo_disp_audit.hip)
+struct AuditArgs {
+  int B, M;
+  const void *table;  // map table (or the one map) of the call's kind
+  const int *slots;   // device array [B] of map-table slots, or NULL (all trajectories use table[0])
+  int nmaps;          // entries of `table` (slots are checked against it on the device)
+  const double *x, *head, *tail;
+  double hz, w[3];
+  double *audit;
+  int *count, *flags;
+};
+
 // FLAT slots of the optimiser vectors: n <= 64, 128, 192 or 256 variables
 inline int slots_for(int M, int D) {
   const int n = D * (M - 1) + M;
@@ -173,6 +185,7 @@ inline int slots_for(int M, int D) {
 // ---- per-family dispatch (neo_disp_*.hip)
 int dispatch_eval(neo_ctx *c, const MapEntry &e, int D, const EvalArgs &a);
 int dispatch_sample(neo_ctx *c, const MapEntry &e, int D, const SampleArgs &a);
+int dispatch_audit(neo_ctx *c, int kind, int elem, int layout, int D, const AuditArgs &a);  // neo_disp_audit.hip
 // the families behind dispatch_opt (neo_abi.hip)
 int launch_opt_2d(neo_ctx *c, int D, bool f32, const OptArgs &a);           // neo_disp_opt2d.hip
 int launch_opt_3d_f32(neo_ctx *c, int elem, int layout, const OptArgs &a);  // neo_disp_opt3d_f32.hip

@@ -20,6 +20,11 @@ NEO_EDT_GENERIC_LINES = 1
 NEO_KERNEL_EVAL, NEO_KERNEL_OPTIMIZE, NEO_KERNEL_ESDF_BUILD, NEO_KERNEL_ESDF_SAMPLE = 0, 1, 2, 3
 NEO_FLAG_ONE_WAVE_PER_SIMD, NEO_FLAG_TWO_WAVES_PER_SIMD, NEO_FLAG_LANE_GROUPS = 32, 64, 128
 NEO_FLAG_F32_SOLVE = 2048
+# neo_audit_traj_batch: fields of a record and flag bits
+AUDIT_FIELDS = ("path_length", "feasibility", "collision", "weighted", "min_clearance", "t_min_clearance", "max_speed",
+                "max_acc", "t_first_unsafe", "duration")
+NEO_AUDIT_FIELDS = len(AUDIT_FIELDS)
+NEO_AUDIT_FLAG_UNSAFE, NEO_AUDIT_FLAG_METRIC_FAIL, NEO_AUDIT_FLAG_OUTSIDE_MAP, NEO_AUDIT_FLAG_NONFINITE = 1, 2, 4, 8
 
 # every symbol include/neo_planner.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -34,7 +39,8 @@ EXPORTS = [
     "neo_optimize_batch_from_dev", "neo_optimize_trace_xg", "neo_sampled_terms_dispatch_order",
     "neo_esdf_build_config", "neo_pack_results_dev", "neo_optimize_state_bytes", "neo_optimize_batch_budget_dev",
     "neo_sampled_terms_batch_f32", "neo_sampled_terms_batch_f32_dev", "neo_effort_order_dev",
-    "neo_optimize_progress_counter", "neo_effort_order_scratch_bytes",
+    "neo_optimize_progress_counter", "neo_effort_order_scratch_bytes", "neo_audit_traj_batch",
+    "neo_audit_traj_batch_dev",
 ]
 
 
@@ -96,6 +102,8 @@ def load():
     L.neo_optimize_workspace_bytes.argtypes = [c_i, c_i, c_i]
     L.neo_optimize_workspace_bytes.restype = ctypes.c_size_t
     L.neo_eval_traj_batch.argtypes = [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_d, c_i, c_p, c_p]
+    L.neo_audit_traj_batch.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_d] + [c_p] * 4
+    L.neo_audit_traj_batch_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_d] + [c_p] * 4
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]

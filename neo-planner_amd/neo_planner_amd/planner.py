@@ -69,6 +69,18 @@ def _map_scene(ctx, map, cache):
     return snap.scene_id
 
 
+def _audit_result(audit, count, flags):
+    """neo_audit_traj_batch's record as a dict: the ten fields by name (_lib.AUDIT_FIELDS), count, flags and the masks"""
+    out = {name: audit[:, i] for i, name in enumerate(_lib.AUDIT_FIELDS)}
+    out.update(count=count, flags=flags, unsafe=(flags & _lib.NEO_AUDIT_FLAG_UNSAFE) != 0,
+               metric_fail=(flags & _lib.NEO_AUDIT_FLAG_METRIC_FAIL) != 0)
+    return out
+
+
+def _audit_weights(weights):
+    return None if weights is None else _lib.as_f64(weights).reshape(3)
+
+
 class MinJerkPlanner:
     """MI355X-backed stand-in for expert_planner.py:MinJerkPlanner"""
 
@@ -353,6 +365,21 @@ class MinJerkPlanner:
     def get_full_state_cmd(self, hz=300):
         return self._states(hz)
 
+    def audit(self, hz=10.0):
+        """the reference's flight metric (traj_planner_node.py:333-363) of the current result (int_wpts, ts, head / tail)
+        on the planner's map snapshot, sampled at `hz`: BatchPlanner.audit's dict for this one trajectory"""
+        self.tau = self.map_T2tau(np.asarray(self.ts, dtype=np.float64))
+        x = _lib.as_f64(self._pack_x()).reshape(1, -1)
+        head = _lib.as_f64(self.head_state).reshape(1, 3, self.D)
+        tail = _lib.as_f64(self.tail_state).reshape(1, 3, self.D)
+        self._sync_params()
+        c = self.ctx
+        audit = np.zeros((1, _lib.NEO_AUDIT_FIELDS)); count = np.zeros(1, np.int32); flags = np.zeros(1, np.int32)
+        c.check(c.lib.neo_audit_traj_batch(c.h, self._scene, None, 1, self.M, self.D, _lib.ptr(x), _lib.ptr(head),
+                                           _lib.ptr(tail), float(hz), None, _lib.ptr(audit), _lib.ptr(count),
+                                           _lib.ptr(flags)))
+        return _audit_result(audit, count, flags)
+
     def get_pos_array(self):
         return self._states(10.0)[:, 0, :]       # np.arange(0, sum(ts), 0.1): 1/10.0 == 0.1
 
@@ -508,6 +535,40 @@ class BatchPlanner:
         w = np.asarray(self.cfg.weights, dtype=np.float64)
         return dict(x=x, costs=costs, costs_last=last, nit=nit, nfev=nfev, status=st & 0xff,
                     collision=(st & _lib.NEO_TRAJ_FLAG_COLLISION) != 0, final_cost=(costs * w).sum(axis=1))
+
+    def audit(self, map, x, head, tail, hz=10.0, scene_ids=None, weights=None):
+        """the reference's flight metric (traj_planner_node.py:333-363, get_weighted_metric) of B trajectories x (B, n)
+        under perfect tracking, sampled at `hz` (10: its metric_eva_interval of 0.1 s).  scene_ids as in `optimize`;
+        weights: the three metric weights (None: the reference's [1, 1, 100]).  Returns a dict of (B,) arrays: the ten
+        record fields by name (path_length, feasibility, collision, weighted, min_clearance, t_min_clearance, max_speed,
+        max_acc, t_first_unsafe, duration), count, flags (NEO_AUDIT_FLAG_*) and the masks unsafe / metric_fail"""
+        self._sync()
+        c = self.ctx
+        x = _lib.as_f64(x); head = _lib.as_f64(head); tail = _lib.as_f64(tail)
+        B, n = x.shape
+        D = head.shape[2]
+        M = (n + D) // (D + 1)
+        audit = np.zeros((B, _lib.NEO_AUDIT_FIELDS)); count = np.zeros(B, np.int32); flags = np.zeros(B, np.int32)
+        sid = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32)
+        w = _audit_weights(weights)
+        c.check(c.lib.neo_audit_traj_batch(c.h, map.scene_id, _lib.ptr(sid), B, M, D, _lib.ptr(x), _lib.ptr(head),
+                                           _lib.ptr(tail), float(hz), _lib.ptr(w),
+                                           _lib.ptr(audit), _lib.ptr(count), _lib.ptr(flags)))
+        return _audit_result(audit, count, flags)
+
+    def audit_dev(self, map, x, head, tail, audit, count, flags, hz=10.0, slots=None, weights=None):
+        """`audit` on device tensors, asynchronous on the context's stream: x (B, n), head / tail (B, 3, D) float64,
+        results into audit (B, NEO_AUDIT_FIELDS) float64, count and flags (B,) int32 -- e.g. straight on optimize_dev's
+        results.  `slots`: optional int32 device tensor of map-table slots, as in optimize_dev"""
+        self._sync()
+        B, n = x.shape
+        D = head.shape[2]
+        M = (n + D) // (D + 1)
+        c = self.ctx
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        w = _audit_weights(weights)
+        c.check(c.lib.neo_audit_traj_batch_dev(c.h, map.scene_id, p(slots), B, M, D, p(x), p(head), p(tail), float(hz),
+                                               _lib.ptr(w), p(audit), p(count), p(flags)))
 
     def optimize_budgeted_dev(self, map, x0, x, head, tail, costs, costs_last, nit, nfev, status, state, eval_budget,
                               max_launches=4096):
