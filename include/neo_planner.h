@@ -334,6 +334,49 @@ int neo_audit_traj_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_id
                              const double *x, const double *head, const double *tail, double hz,
                              const double *weights3, double *audit, int32_t *count, int32_t *flags);
 
+/* ---- geo warm start (traj_planner/astar_planner.py, geo_planner.py:19-101) ----
+ * For each request b on a 2-D map: the reference's AstarPlanner.plan(map, start[b], target[b]) -- an 8-connected A* on
+ * the map's grid expanded by 10 m (W + int(10 / res) by H + int(10 / res) cells, origin - 5 m), a cell blocked where the
+ * map's nearest-cell distance of its position is < 0.5 (esdf.py has_collision) -- then
+ * GeoPlanner.prune_path_nodes(map, path), the four key nodes.  Results, all equal to the reference's:
+ *   key_pts[b][4][2]   the pruned nodes (int_wpts = key_pts[b][1:3].T for warm_start_plan);
+ *   path_len[b]        nodes of the reference's path (1 when there is none: [calc_real_pos(target cell)]);
+ *   path_cost[b]       target_node.cost (0 without a path);
+ *   path[b][path_cap][2] the first min(path_len, path_cap) nodes when path is not NULL, NaN after them;
+ *   expansions[b]      nodes the search closed (0 for the short cuts below);
+ *   flags[b]           NEO_GEO_FLAG_*.
+ * Short cuts, exact: start cell == target cell gives the one-node path at once; a target cell that is blocked or outside
+ * the grid gives NO_PATH without a search.  One divergence: a start whose key x + y * W_e falls outside [0, W_e * H_e)
+ * (the reference would search from it) gives START_OUTSIDE and the one-node result.  max_expansions > 0 ends a search
+ * after that many expansions with CAPPED and the one-node result -- NOT the reference's answer; 0 = unbounded.
+ * Each search runs on one slot of a context-owned workspace of 32 bytes per expanded cell and slot, sized from a byte
+ * budget (neo_geo_workspace_budget; default 2 GiB, at most 1024 slots); NEO_ERR_HIP when not even one slot fits or the
+ * allocation fails.  A scene's blocked mask (one bit per expanded cell) is built on first use and kept until the map
+ * changes.  Results do not depend on the slot, the launch or the batch.  The geo calls of one context share the
+ * workspace: issue them on one stream.
+ * Errors, before anything is launched: B < 1, path_cap < 0, path != NULL with path_cap < 1, max_expansions < 0 or a NULL
+ * required buffer: NEO_ERR_INVALID; a scene without a map: NEO_ERR_NO_MAP; a 3-D scene: NEO_ERR_UNSUPPORTED.
+ * scene_ids: NULL (all use scene_id) or B scene ids (host form). */
+#define NEO_GEO_FLAG_NO_PATH 1        /* the open set emptied, or the target cell is blocked or outside the grid */
+#define NEO_GEO_FLAG_START_OUTSIDE 2  /* the start cell's key is outside the grid: not searched */
+#define NEO_GEO_FLAG_CAPPED 4         /* max_expansions reached: not the reference's result */
+#define NEO_GEO_FLAG_PATH_TRUNCATED 8 /* only the copied path was cut to path_cap */
+#define NEO_GEO_FLAG_BAD_SCENE 16     /* _dev: the map-table slot is outside the table; key_pts and path_cost NaN */
+int neo_geo_search_batch(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, const double *start,
+                         const double *target, int max_expansions, int path_cap, double *key_pts, double *path,
+                         int32_t *path_len, double *path_cost, int32_t *expansions, int32_t *flags);
+/* the same with DEVICE pointers, asynchronous on the context's stream; scene_ids is then a device array of 2-D map-table
+ * slots (neo_scene_slot), as in neo_optimize_batch_dev */
+int neo_geo_search_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, const double *start,
+                             const double *target, int max_expansions, int path_cap, double *key_pts, double *path,
+                             int32_t *path_len, double *path_cost, int32_t *expansions, int32_t *flags);
+/* prune_path_nodes alone on caller-given host paths[b][path_stride][2] of path_len[b] (1 <= path_len[b] <= path_stride)
+ * nodes: key_pts[b][4][2] */
+int neo_geo_prune_batch(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, const double *paths,
+                        const int32_t *path_len, int path_stride, double *key_pts);
+/* the byte budget the geo workspace is sized from (takes effect at the next reallocation) */
+int neo_geo_workspace_budget(neo_ctx *ctx, size_t bytes);
+
 /* ---- timing of the device work (bench.py) ----------------------------------
  * When enabled, every kernel launch of the named family is bracketed by HIP events on
  * the context stream; neo_profile_read returns launches and summed milliseconds. */

@@ -983,6 +983,7 @@ int neo_ctx_destroy(neo_ctx *c) {
   hipStreamSynchronize(c->stream);
   if (c->stream != c->home_stream) hipStreamSynchronize(c->home_stream);
   drain_profile(c);
+  geo_release(c);
   for (auto &kv : c->maps)
     if (kv.second.data) hipFree(kv.second.data);
   if (c->order_buf) hipFree(c->order_buf);
@@ -1031,6 +1032,7 @@ static int drop_locked(neo_ctx *c, int scene_id) {
     hipDeviceSynchronize();
     if (it->second.data) hipFree(it->second.data);
     c->maps.erase(it);
+    geo_forget(c, scene_id);
     c->table_dirty = true;
   }
   return NEO_OK;
@@ -1067,6 +1069,7 @@ int neo_esdf_upload_2d(neo_ctx *c, int scene_id, const double *dist, const doubl
   HIPCHK(c, hipStreamSynchronize(c->stream));
   e.data = rec.release();
   e.m2 = Map2D{static_cast<const double4 *>(e.data), W, H, res, ox, oy};
+  e.version = ++c->map_serial;
   c->maps[scene_id] = e;
   c->table_dirty = true;
   return NEO_OK;
@@ -1132,6 +1135,7 @@ int neo_esdf_build_2d(neo_ctx *c, int scene_id, const int8_t *occ, int W, int H,
     const Map2D m{static_cast<const double4 *>(it->second.data), W, H, res, ox, oy};
     if (memcmp(&m, &it->second.m2, sizeof(m)) != 0) c->table_dirty = true;  // same buffer: usually the same descriptor
     it->second.m2 = m;
+    it->second.version = ++c->map_serial;  // new contents: the geo mask is stale
     return NEO_OK;
   }
   drop_locked(c, scene_id);
@@ -1144,6 +1148,7 @@ int neo_esdf_build_2d(neo_ctx *c, int scene_id, const int8_t *occ, int W, int H,
   e.elem = NEO_F64;
   e.data = rec.release();
   e.m2 = Map2D{static_cast<const double4 *>(e.data), W, H, res, ox, oy};
+  e.version = ++c->map_serial;
   c->maps[scene_id] = e;
   c->table_dirty = true;
   return NEO_OK;
@@ -1919,6 +1924,144 @@ int neo_audit_traj_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int
   HIPCHK(c, hipMemcpyAsync(count, dcnt, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(flags, dfl, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return NEO_OK;
+}
+
+// ---- geo warm start (traj_planner/astar_planner.py, geo_planner.py:19-101; kernels: neo_geo.hpp)
+static int geo_check(neo_ctx *c, int B, const double *start, const double *target, int max_expansions, int path_cap,
+                     const double *key_pts, const double *path, const int32_t *path_len, const double *path_cost,
+                     const int32_t *expansions, const int32_t *flags) {
+  if (!c) return NEO_ERR_INVALID;
+  if (B < 1) return fail_locked(c, NEO_ERR_INVALID, "geo: B must be >= 1");
+  if (max_expansions < 0 || path_cap < 0 || (path && path_cap < 1))
+    return fail_locked(c, NEO_ERR_INVALID, "geo: max_expansions and path_cap must be >= 0 (path_cap >= 1 with a path)");
+  if (!start || !target || !key_pts || !path_len || !path_cost || !expansions || !flags)
+    return fail_locked(c, NEO_ERR_INVALID, "geo: null buffer");
+  return NEO_OK;
+}
+
+// the reference scene of a call: it must exist and be 2-D (the reference's A* is 2-D only)
+static int geo_scene_kind(neo_ctx *c, int scene_id) {
+  auto it = c->maps.find(scene_id);
+  if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "geo: no ESDF for this scene");
+  if (it->second.kind != 0) return fail(c, NEO_ERR_UNSUPPORTED, "geo: the A* warm start needs a 2-D map");
+  return NEO_OK;
+}
+
+// host scene ids -> 2-D map-table slots
+static int geo_slots(neo_ctx *c, const int32_t *scene_ids, int B, std::vector<int> &slots) {
+  slots.resize((size_t)B);
+  for (int i = 0; i < B; ++i) {
+    auto it = c->maps.find(scene_ids[i]);
+    if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "geo: no ESDF for one of scene_ids");
+    if (it->second.kind != 0) return fail(c, NEO_ERR_UNSUPPORTED, "geo: one of scene_ids is a 3-D map");
+    slots[i] = it->second.slot;
+  }
+  return NEO_OK;
+}
+
+int neo_geo_search_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const double *start,
+                             const double *target, int max_expansions, int path_cap, double *key_pts, double *path,
+                             int32_t *path_len, double *path_cost, int32_t *expansions, int32_t *flags) {
+  int rc = geo_check(c, B, start, target, max_expansions, path_cap, key_pts, path, path_len, path_cost, expansions, flags);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  rc = rebuild_tables(c);
+  if (rc) return rc;
+  rc = geo_scene_kind(c, scene_id);
+  if (rc) return rc;
+  const GeoArgs ga{B, scene_ids, start, target, max_expansions, path ? path_cap : 0, key_pts, path, path_cost,
+                   path_len, expansions, flags};
+  return geo_search(c, scene_id, ga);
+}
+
+int neo_geo_search_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const double *start,
+                         const double *target, int max_expansions, int path_cap, double *key_pts, double *path,
+                         int32_t *path_len, double *path_cost, int32_t *expansions, int32_t *flags) {
+  int rc = geo_check(c, B, start, target, max_expansions, path_cap, key_pts, path, path_len, path_cost, expansions, flags);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> whole_call(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  rc = rebuild_tables(c);
+  if (rc) return rc;
+  std::vector<int> slots;
+  if (scene_ids) {
+    rc = geo_slots(c, scene_ids, B, slots);
+    if (rc) return rc;
+  } else {
+    rc = geo_scene_kind(c, scene_id);
+    if (rc) return rc;
+  }
+  const size_t bs = (size_t)B, pc = path ? (size_t)path_cap : 0;
+  rc = ensure_scratch(c, bs * (4 + 8 + 1 + 2 * pc) * sizeof(double) + 4 * bs * sizeof(int) + 10 * 256);
+  if (rc) return rc;
+  Carver cv(c->scratch);
+  double *ds = cv.take<double>(2 * bs), *dt = cv.take<double>(2 * bs), *dk = cv.take<double>(8 * bs);
+  double *dc = cv.take<double>(bs), *dp = path ? cv.take<double>(2 * bs * pc) : nullptr;
+  int *dslots = cv.take<int>(bs), *dl = cv.take<int>(bs), *de = cv.take<int>(bs), *df = cv.take<int>(bs);
+  HIPCHK(c, hipMemcpyAsync(ds, start, 2 * bs * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dt, target, 2 * bs * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (scene_ids) HIPCHK(c, hipMemcpyAsync(dslots, slots.data(), bs * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  rc = neo_geo_search_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? dslots : nullptr, B, ds, dt,
+                                max_expansions, path_cap, dk, dp, dl, dc, de, df);
+  if (rc) {
+    hipStreamSynchronize(c->stream);  // (the copies in flight read the caller's buffers)
+    return rc;
+  }
+  HIPCHK(c, hipMemcpyAsync(key_pts, dk, 8 * bs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(path_cost, dc, bs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(path_len, dl, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(expansions, de, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(flags, df, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (path) HIPCHK(c, hipMemcpyAsync(path, dp, 2 * bs * pc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return NEO_OK;
+}
+
+int neo_geo_prune_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const double *paths,
+                        const int32_t *path_len, int path_stride, double *key_pts) {
+  if (!c) return NEO_ERR_INVALID;
+  if (B < 1 || path_stride < 1) return fail_locked(c, NEO_ERR_INVALID, "geo prune: B and path_stride must be >= 1");
+  if (!paths || !path_len || !key_pts) return fail_locked(c, NEO_ERR_INVALID, "geo prune: null buffer");
+  for (int i = 0; i < B; ++i)
+    if (path_len[i] < 1 || path_len[i] > path_stride)
+      return fail_locked(c, NEO_ERR_INVALID, "geo prune: path_len must be in [1, path_stride]");
+  std::lock_guard<std::recursive_mutex> whole_call(c->mu);
+  hipSetDevice(c->device);
+  int rc = rebuild_tables(c);
+  if (rc) return rc;
+  std::vector<int> slots;
+  if (scene_ids) {
+    rc = geo_slots(c, scene_ids, B, slots);
+    if (rc) return rc;
+  } else {
+    rc = geo_scene_kind(c, scene_id);
+    if (rc) return rc;
+  }
+  const size_t bs = (size_t)B, ps = (size_t)path_stride;
+  rc = ensure_scratch(c, bs * (2 * ps + 8) * sizeof(double) + 2 * bs * sizeof(int) + 5 * 256);
+  if (rc) return rc;
+  Carver cv(c->scratch);
+  double *dp = cv.take<double>(2 * bs * ps), *dk = cv.take<double>(8 * bs);
+  int *dl = cv.take<int>(bs), *dslots = cv.take<int>(bs);
+  HIPCHK(c, hipMemcpyAsync(dp, paths, 2 * bs * ps * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dl, path_len, bs * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (scene_ids) HIPCHK(c, hipMemcpyAsync(dslots, slots.data(), bs * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  rc = geo_prune(c, scene_ids ? scene_ids[0] : scene_id, B, scene_ids ? dslots : nullptr, dp, dl, path_stride, dk);
+  if (rc) {
+    hipStreamSynchronize(c->stream);
+    return rc;
+  }
+  HIPCHK(c, hipMemcpyAsync(key_pts, dk, 8 * bs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return NEO_OK;
+}
+
+int neo_geo_workspace_budget(neo_ctx *c, size_t bytes) {
+  if (!c) return NEO_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  c->geo.budget = bytes;
   return NEO_OK;
 }
 

@@ -25,6 +25,25 @@ struct MapEntry {
   Map2D m2{};
   Map3D m3{};
   int slot = -1;  // index into the device-side map table
+  unsigned long long version = 0;  // 2-D maps: a new value at every upload / build (keys the geo blocked mask)
+};
+
+// the geo warm start's device state (neo_disp_geo.hip)
+struct GeoMask {
+  void *bits = nullptr;
+  unsigned long long version = 0;
+};
+struct GeoState {
+  std::map<int, GeoMask> masks;  // by scene id
+  void *cells = nullptr, *heap = nullptr;
+  unsigned *epochs = nullptr;
+  int *work = nullptr;
+  size_t cells_cap = 0;          // cells per slot
+  int nslots = 0;
+  unsigned long long searches = 0;  // requests launched since the stamps were last cleared
+  size_t budget = size_t(2) << 30;
+  void *table = nullptr;         // device GeoScene[]
+  std::vector<char> table_host;  // what `table` holds
 };
 
 struct ProfileSlot {
@@ -73,6 +92,8 @@ struct neo_ctx {
   size_t sample_order_cap = 0;          // (neo_sampled_terms_dispatch_order; never the optimiser's, never caller-owned)
   int sample_order_B = 0;
   int edt_flags = 0;                    // NEO_EDT_* (neo_esdf_build_config)
+  unsigned long long map_serial = 0;    // MapEntry::version source
+  neo::GeoState geo;
 };
 
 namespace neo {
@@ -174,6 +195,21 @@ struct AuditArgs {
   double *audit;
   int *count, *flags;
 };
+
+// neo_geo_search_batch_dev / neo_geo_prune_batch (neo_disp_geo.hip); the context is locked and its tables rebuilt
+struct GeoArgs {
+  int B;
+  const int *slots;  // device array [B] of 2-D map-table slots, or NULL (all requests use scene_id)
+  const double *start, *target;
+  int max_exp, path_cap;
+  double *key_pts, *path, *path_cost;
+  int *path_len, *expansions, *flags;
+};
+int geo_search(neo_ctx *c, int scene_id, const GeoArgs &a);
+int geo_prune(neo_ctx *c, int scene_id, int B, const int *slots, const double *paths, const int *path_len, int stride,
+              double *key_pts);
+void geo_release(neo_ctx *c);             // frees every geo buffer (neo_ctx_destroy)
+void geo_forget(neo_ctx *c, int scene_id);  // frees the scene's mask (map drop)
 
 // FLAT slots of the optimiser vectors: n <= 64, 128, 192 or 256 variables
 inline int slots_for(int M, int D) {

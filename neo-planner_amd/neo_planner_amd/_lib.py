@@ -25,6 +25,9 @@ AUDIT_FIELDS = ("path_length", "feasibility", "collision", "weighted", "min_clea
                 "max_acc", "t_first_unsafe", "duration")
 NEO_AUDIT_FIELDS = len(AUDIT_FIELDS)
 NEO_AUDIT_FLAG_UNSAFE, NEO_AUDIT_FLAG_METRIC_FAIL, NEO_AUDIT_FLAG_OUTSIDE_MAP, NEO_AUDIT_FLAG_NONFINITE = 1, 2, 4, 8
+# neo_geo_search_batch: flag bits
+NEO_GEO_FLAG_NO_PATH, NEO_GEO_FLAG_START_OUTSIDE, NEO_GEO_FLAG_CAPPED, NEO_GEO_FLAG_PATH_TRUNCATED = 1, 2, 4, 8
+NEO_GEO_FLAG_BAD_SCENE = 16
 
 # every symbol include/neo_planner.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -40,7 +43,8 @@ EXPORTS = [
     "neo_esdf_build_config", "neo_pack_results_dev", "neo_optimize_state_bytes", "neo_optimize_batch_budget_dev",
     "neo_sampled_terms_batch_f32", "neo_sampled_terms_batch_f32_dev", "neo_effort_order_dev",
     "neo_optimize_progress_counter", "neo_effort_order_scratch_bytes", "neo_audit_traj_batch",
-    "neo_audit_traj_batch_dev",
+    "neo_audit_traj_batch_dev", "neo_geo_search_batch", "neo_geo_search_batch_dev", "neo_geo_prune_batch",
+    "neo_geo_workspace_budget",
 ]
 
 
@@ -104,6 +108,10 @@ def load():
     L.neo_eval_traj_batch.argtypes = [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_d, c_i, c_p, c_p]
     L.neo_audit_traj_batch.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_d] + [c_p] * 4
     L.neo_audit_traj_batch_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_d] + [c_p] * 4
+    L.neo_geo_search_batch.argtypes = [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i] + [c_p] * 6
+    L.neo_geo_search_batch_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i] + [c_p] * 6
+    L.neo_geo_prune_batch.argtypes = [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p]
+    L.neo_geo_workspace_budget.argtypes = [c_p, ctypes.c_size_t]
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]

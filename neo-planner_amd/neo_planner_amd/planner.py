@@ -570,6 +570,73 @@ class BatchPlanner:
         c.check(c.lib.neo_audit_traj_batch_dev(c.h, map.scene_id, p(slots), B, M, D, p(x), p(head), p(tail), float(hz),
                                                _lib.ptr(w), p(audit), p(count), p(flags)))
 
+    def geo_init(self, map, start, target, scene_ids=None, max_expansions=0, path_cap=0):
+        """the reference's `geo` warm start (geo_planner.py:19-35) for B requests on 2-D maps: AstarPlanner.plan from
+        start (B, 2) to target (B, 2), prune_path_nodes, then int_wpts = pruned[1:3].T and ts = init_T * [1.5, 1, 1.5]
+        (neo_geo_search_batch; every value equal to the reference's).  scene_ids as in `optimize`.  max_expansions > 0
+        caps each search (CAPPED flag; such a result is not the reference's).  Returns a dict: int_wpts (B, 2, 2) and
+        ts (B, 3) ready for `plan`, key_pts (B, 4, 2), path_len, path_cost, expansions, flags (NEO_GEO_FLAG_*), the
+        masks no_path / capped, and paths (B, path_cap, 2) when path_cap > 0"""
+        c = self.ctx
+        start = _lib.as_f64(start).reshape(-1, 2); target = _lib.as_f64(target).reshape(-1, 2)
+        B = start.shape[0]
+        if target.shape[0] != B:
+            raise ValueError("BatchPlanner.geo_init: start and target need the same number of requests")
+        key_pts = np.zeros((B, 4, 2)); cost = np.zeros(B)
+        plen = np.zeros(B, np.int32); nexp = np.zeros(B, np.int32); flags = np.zeros(B, np.int32)
+        paths = np.zeros((B, path_cap, 2)) if path_cap > 0 else None
+        sid = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32)
+        c.check(c.lib.neo_geo_search_batch(c.h, map.scene_id, _lib.ptr(sid), B, _lib.ptr(start), _lib.ptr(target),
+                                           int(max_expansions), int(path_cap), _lib.ptr(key_pts), _lib.ptr(paths),
+                                           _lib.ptr(plen), _lib.ptr(cost), _lib.ptr(nexp), _lib.ptr(flags)))
+        ts = np.empty((B, 3))
+        ts[:] = float(self.cfg.init_T)
+        ts[:, 0] *= 1.5
+        ts[:, -1] *= 1.5
+        out = dict(int_wpts=key_pts[:, 1:3, :].transpose(0, 2, 1).copy(), ts=ts, key_pts=key_pts, path_len=plen,
+                   path_cost=cost, expansions=nexp, flags=flags, no_path=(flags & _lib.NEO_GEO_FLAG_NO_PATH) != 0,
+                   capped=(flags & _lib.NEO_GEO_FLAG_CAPPED) != 0)
+        if paths is not None:
+            out["paths"] = paths
+        return out
+
+    def geo_init_dev(self, map, start, target, key_pts, path_len, path_cost, expansions, flags, slots=None,
+                     max_expansions=0, paths=None):
+        """`geo_init`'s search on device tensors, asynchronous on the context's stream: start / target (B, 2) float64,
+        results into key_pts (B, 4, 2), path_cost (B,) float64, path_len, expansions, flags (B,) int32 and, when given,
+        paths (B, path_cap, 2) float64.  `slots`: optional int32 device tensor of map-table slots, as in optimize_dev"""
+        c = self.ctx
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        B = start.shape[0]
+        cap = 0 if paths is None else paths.shape[1]
+        c.check(c.lib.neo_geo_search_batch_dev(c.h, map.scene_id, p(slots), B, p(start), p(target), int(max_expansions),
+                                               cap, p(key_pts), p(paths), p(path_len), p(path_cost), p(expansions),
+                                               p(flags)))
+
+    def geo_prune(self, map, paths, path_len=None, scene_ids=None):
+        """GeoPlanner.prune_path_nodes (geo_planner.py:61-101) of B given paths: paths (B, L, 2) (the first path_len[b]
+        nodes of row b; all L without path_len) -> key_pts (B, 4, 2)"""
+        c = self.ctx
+        paths = _lib.as_f64(paths)
+        B, L = paths.shape[0], paths.shape[1]
+        plen = np.full(B, L, np.int32) if path_len is None else np.ascontiguousarray(path_len, dtype=np.int32)
+        key_pts = np.zeros((B, 4, 2))
+        sid = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32)
+        c.check(c.lib.neo_geo_prune_batch(c.h, map.scene_id, _lib.ptr(sid), B, _lib.ptr(paths), _lib.ptr(plen), L,
+                                          _lib.ptr(key_pts)))
+        return key_pts
+
+    def geo_plan(self, map, head, tail, scene_ids=None, max_expansions=0, **kw):
+        """`geo_init` from head[:, 0] to tail[:, 0], then `plan(int_wpts=..., ts=...)`: the reference's geo_traj_plan
+        (geo_planner.py:19-35) for a batch of 2-D requests head / tail (B, 2, 2).  Retries re-seed from straight lines,
+        as the reference's warm_start_plan does after a geo start.  `plan`'s dict plus the search's results under
+        "geo" """
+        head = _lib.as_f64(head); tail = _lib.as_f64(tail)
+        g = self.geo_init(map, head[:, 0, :2], tail[:, 0, :2], scene_ids=scene_ids, max_expansions=max_expansions)
+        out = self.plan(map, head, tail, int_wpts=g["int_wpts"], ts=g["ts"], scene_ids=scene_ids, **kw)
+        out["geo"] = g
+        return out
+
     def optimize_budgeted_dev(self, map, x0, x, head, tail, costs, costs_last, nit, nfev, status, state, eval_budget,
                               max_launches=4096):
         """optimize_dev with an evaluation budget per launch (neo_optimize_batch_budget_dev): the first launch gives every

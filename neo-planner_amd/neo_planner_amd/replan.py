@@ -70,6 +70,8 @@ class ReplanLoop:
         with (contextlib.redirect_stdout(sink) if sink else contextlib.nullcontext()):
             if self.mode == "batch":
                 self.planner.batch_plan(self.map, start_2d, self.target_state)
+            elif self.mode == "geo":      # :548-549: A* warm start from the look-ahead state (a GeoPlanner)
+                self.planner.geo_traj_plan(self.map, start, self.target_state)
             else:
                 self.planner.plan(self.map, start_2d, self.target_state)
         self.n_plans += 1
