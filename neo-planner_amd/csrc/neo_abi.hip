@@ -790,7 +790,7 @@ int ensure_pinned(neo_ctx *c, size_t bytes) {
   return NEO_OK;
 }
 
-// bump allocator over the scratch buffer
+// bump allocator over the scratch buffer (device-only work buffers of the ESDF upload / build paths)
 struct Carver {
   char *base;
   size_t off = 0;
@@ -798,10 +798,113 @@ struct Carver {
   template <typename T>
   T *take(size_t count) {
     off = (off + 255) & ~size_t(255);
-    T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+    T *p = reinterpret_cast<T *>(base + off);
     off += count * sizeof(T);
     return p;
   }
+};
+
+// Calls whose whole scratch layout is at most this many bytes go through the pinned mirror: ONE copy in and ONE copy out
+// instead of one per array from pageable memory (a single plan() of the reference's shape: 0.36 -> 0.27 ms; ten such
+// copies cost almost as much as the kernel).  Small calls only: from a megabyte on, the extra pass over the data costs
+// more than the copies' latencies -- 8192 replans of the reference's shape per call: 1.46 M/s direct, 1.28 M/s staged.
+// (neo_optimize_batch, neo_cost_grad_batch, neo_eval_traj_batch; the other host forms pass 0 = never: the mirror has
+// not been measured there.)
+constexpr size_t kStagedUpTo = (size_t)256 * 1024;
+
+// The arrays of one host-pointer call, staged through c->scratch.  Declare the fields in layout order -- in(), then
+// inout(), then out(), each 256-byte aligned -- then upload(), run the `_dev` form on dev() pointers, then download().
+// A null host pointer reserves the field and copies nothing for it (device-only, or the caller did not ask).  The
+// scratch is sized from the declarations.  Calls up to `staged_up_to` bytes move the contiguous input range and the
+// contiguous output range through the pinned mirror of the same layout, whole, null fields included; larger ones copy
+// field by field.  A stage that goes out of scope between upload() and a completed download() (an error return) waits
+// for the stream first: copies in flight read the caller's arrays and the wrapper's locals.
+// The context stays locked for the stage's lifetime (c->scratch and c->pinned are the context's only ones).
+class HostStage {
+ public:
+  template <typename T>
+  struct Ref { int i; };
+
+  HostStage(neo_ctx *c, size_t staged_up_to) : c_(c), staged_up_to_(staged_up_to) { f_.reserve(12); }
+  HostStage(const HostStage &) = delete;
+  HostStage &operator=(const HostStage &) = delete;
+  ~HostStage() {
+    if (in_flight_) hipStreamSynchronize(c_->stream);
+  }
+
+  // `count` elements are copied; `reserve` (>= count) sizes the field when the device side wants more room
+  template <typename T>
+  Ref<T> in(const T *host, size_t count, size_t reserve = 0) { return {add(0, host, nullptr, count * sizeof(T), reserve * sizeof(T))}; }
+  template <typename T>
+  Ref<T> inout(T *host, size_t count) { return {add(1, host, host, count * sizeof(T), 0)}; }
+  template <typename T>
+  Ref<T> out(T *host, size_t count, size_t reserve = 0) { return {add(2, nullptr, host, count * sizeof(T), reserve * sizeof(T))}; }
+
+  // the field's device array: valid from upload() on (growing the scratch moves it), NULL before
+  template <typename T>
+  T *dev(Ref<T> r) const { return dbase_ ? reinterpret_cast<T *>(dbase_ + f_[r.i].off) : nullptr; }
+
+  int upload() {
+    if (!ordered_) return fail(c_, NEO_ERR_INVALID, "internal: staged fields declared out of order");
+    staged_ = staged_up_to_ && end_ <= staged_up_to_;
+    int rc = ensure_scratch(c_, end_ + 256);
+    if (!rc && staged_) rc = ensure_pinned(c_, end_ + 256);
+    if (rc) return rc;
+    dbase_ = static_cast<char *>(c_->scratch);
+    hbase_ = static_cast<char *>(c_->pinned);
+    in_flight_ = true;
+    if (staged_) {
+      for (const Field &f : f_)
+        if (f.src) std::memcpy(hbase_ + f.off, f.src, f.bytes);
+      HIPCHK(c_, hipMemcpyAsync(dbase_, hbase_, std::min(in_end_, end_), hipMemcpyHostToDevice, c_->stream));
+      return NEO_OK;
+    }
+    for (const Field &f : f_)
+      if (f.src) HIPCHK(c_, hipMemcpyAsync(dbase_ + f.off, f.src, f.bytes, hipMemcpyHostToDevice, c_->stream));
+    return NEO_OK;
+  }
+
+  int download() {
+    if (staged_) {
+      const size_t o = std::min(out_begin_, end_);
+      HIPCHK(c_, hipMemcpyAsync(hbase_ + o, dbase_ + o, end_ - o, hipMemcpyDeviceToHost, c_->stream));
+    } else {
+      for (const Field &f : f_)
+        if (f.dst) HIPCHK(c_, hipMemcpyAsync(f.dst, dbase_ + f.off, f.bytes, hipMemcpyDeviceToHost, c_->stream));
+    }
+    HIPCHK(c_, hipStreamSynchronize(c_->stream));
+    in_flight_ = false;
+    if (staged_)
+      for (const Field &f : f_)
+        if (f.dst) std::memcpy(f.dst, hbase_ + f.off, f.bytes);
+    return NEO_OK;
+  }
+
+ private:
+  struct Field {
+    size_t off, bytes;
+    const void *src;  // host array copied up, or NULL
+    void *dst;        // host array copied back, or NULL
+  };
+  int add(int role, const void *src, void *dst, size_t bytes, size_t reserve) {
+    ordered_ = ordered_ && role >= role_;
+    role_ = role;
+    const size_t off = (end_ + 255) & ~size_t(255);
+    if (role >= 1) out_begin_ = std::min(out_begin_, off);
+    if (role == 2) in_end_ = std::min(in_end_, off);
+    end_ = off + std::max(bytes, reserve);
+    f_.push_back({off, bytes, src, dst});
+    return (int)f_.size() - 1;
+  }
+  neo_ctx *c_;
+  size_t staged_up_to_;
+  std::vector<Field> f_;
+  size_t end_ = 0;                  // bytes of the layout (the last field's end)
+  size_t in_end_ = ~size_t(0);      // the input range is [0, first out() field)
+  size_t out_begin_ = ~size_t(0);   // the output range is [first inout() / out() field, end)
+  int role_ = 0;
+  bool ordered_ = true, staged_ = false, in_flight_ = false;
+  char *dbase_ = nullptr, *hbase_ = nullptr;
 };
 
 int rebuild_tables(neo_ctx *c) {
@@ -846,12 +949,35 @@ int check_shape(neo_ctx *c, int B, int M, int D) {
   return NEO_OK;
 }
 
+// host scene ids of a multi-scene call -> map-table slots (context locked).  The maps must all be of one kind, or, for
+// the geo warm start (`geo`: the reference's A* is 2-D only), all 2-D.
+int scene_slots(neo_ctx *c, const int32_t *scene_ids, size_t B, bool geo, std::vector<int> &slots) {
+  int rc = rebuild_tables(c);
+  if (rc) return rc;
+  slots.resize(B);
+  int kind0 = geo ? 0 : -1;
+  for (size_t i = 0; i < B; ++i) {
+    auto it = c->maps.find(scene_ids[i]);
+    if (it == c->maps.end())
+      return fail(c, NEO_ERR_NO_MAP, geo ? "geo: no ESDF for one of scene_ids" : "no ESDF for one of scene_ids");
+    if (kind0 < 0) kind0 = it->second.kind;
+    if (it->second.kind != kind0)
+      return geo ? fail(c, NEO_ERR_UNSUPPORTED, "geo: one of scene_ids is a 3-D map")
+                 : fail(c, NEO_ERR_INVALID, "scene_ids mix 2-D and 3-D maps");
+    slots[i] = it->second.slot;
+  }
+  return NEO_OK;
+}
 
 // From this batch size on the kernels take the two-wavefronts-per-SIMD register allocation (three in the all-fp32
 // mode, always).  Measured in round 3, one launch at a time, two waves against one: fp64 mode +4 % at 1024, +9 % at 2048,
 // +23 % at 3072 trajectories; mixed mode +2 %, +5 %, +23 % (round 2 had found one wave faster up to 2048: 9.1 against
 // 10.1 ms -- before the per-evaluation loads and the spills of the two-waves kernels were gone).
 constexpr int kTwoWavesFromBatch = 1024;
+bool two_waves_wanted(const neo_ctx *c, int B) {
+  const int fl = c->params.flags;
+  return (B >= kTwoWavesFromBatch && !(fl & NEO_FLAG_ONE_WAVE_PER_SIMD)) || (fl & NEO_FLAG_TWO_WAVES_PER_SIMD);
+}
 
 int fail_locked(neo_ctx *c, int code, const char *msg) {
   std::lock_guard<std::recursive_mutex> g(c->mu);
@@ -874,10 +1000,7 @@ int dispatch_opt(neo_ctx *c, int kind, int elem, int layout, int D, const OptArg
     const int fl2 = c->params.flags;
     // all-fp32 mode on the reference's own map: the timed arithmetic, pinned to the reference's fixtures there
     if ((fl2 & NEO_FLAG_F32_SOLVE) && f32) return launch_opt_2d_x(c, D, a);
-    if (D == 2 && slots_for(a.M, D) <= 2 &&
-        ((a.B >= kTwoWavesFromBatch && !(fl2 & NEO_FLAG_ONE_WAVE_PER_SIMD)) ||
-         (fl2 & NEO_FLAG_TWO_WAVES_PER_SIMD)))
-      return launch_opt_2d_w2(c, f32, a);
+    if (D == 2 && slots_for(a.M, D) <= 2 && two_waves_wanted(c, a.B)) return launch_opt_2d_w2(c, f32, a);
     return launch_opt_2d(c, D, f32, a);
   }
   if (D != 3) return fail(c, NEO_ERR_INVALID, "a 3-D map needs D = 3");
@@ -886,15 +1009,11 @@ int dispatch_opt(neo_ctx *c, int kind, int elem, int layout, int D, const OptArg
   if ((fl & NEO_FLAG_F32_SOLVE) && f32) return launch_opt_3d_x(c, elem, layout, a);  // all-fp32 mode
   // two trajectories per SIMD for calls that queue for the SIMDs anyway (3-D fields, fp32 sampling; beyond n = 128 with
   // the pairs stored in fp32 so that eight wavefronts still fit a CU's LDS, neo_kernels.hpp pairs_in_f32)
-  const bool two = f32 && slots_for(a.M, D) <= NEO_W2_MAX_SLOTS &&
-                   ((a.B >= kTwoWavesFromBatch && !(fl & NEO_FLAG_ONE_WAVE_PER_SIMD)) || (fl & NEO_FLAG_TWO_WAVES_PER_SIMD));
-  if (two) return launch_opt_3d_w2(c, elem, layout, a);
+  if (f32 && slots_for(a.M, D) <= NEO_W2_MAX_SLOTS && two_waves_wanted(c, a.B)) return launch_opt_3d_w2(c, elem, layout, a);
   // fp64 sampling (the parity mode): two wavefronts per SIMD for n <= 128 when the batch queues for the SIMDs (the
   // unit is compiled so that these kernels spill 0 - 13 registers, build.py; cfg2 360 k -> 637 k traj/s, M = 25 239 k
   // -> 400 k, M = 32 162 k -> 241 k; four FLAT slots would spill 112)
-  if (!f32 && slots_for(a.M, D) <= 2 &&
-      ((a.B >= kTwoWavesFromBatch && !(fl & NEO_FLAG_ONE_WAVE_PER_SIMD)) || (fl & NEO_FLAG_TWO_WAVES_PER_SIMD)))
-    return launch_opt_3d_f64_w2(c, elem, layout, a);
+  if (!f32 && slots_for(a.M, D) <= 2 && two_waves_wanted(c, a.B)) return launch_opt_3d_f64_w2(c, elem, layout, a);
   return f32 ? launch_opt_3d_f32(c, elem, layout, a) : launch_opt_3d_f64(c, elem, layout, a);
 }
 
@@ -1352,11 +1471,12 @@ int neo_esdf_query(neo_ctx *c, int scene_id, int n, const double *pts, double *d
   if (n == 0) return NEO_OK;
   const MapEntry &e = it->second;
   const int dm = e.kind == 0 ? 2 : 3;
-  int rc = ensure_scratch(c, (size_t)n * (2 * dm + 1) * sizeof(double) + 1024);
+  HostStage st(c, 0);
+  const auto f_p = st.in(pts, (size_t)n * dm);
+  const auto f_d = st.out(dist, (size_t)n), f_g = st.out(grad, (size_t)n * dm);
+  int rc = st.upload();
   if (rc) return rc;
-  Carver cv(c->scratch);
-  double *d_p = cv.take<double>((size_t)n * dm), *d_d = cv.take<double>(n), *d_g = cv.take<double>((size_t)n * dm);
-  HIPCHK(c, hipMemcpyAsync(d_p, pts, (size_t)n * dm * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  double *d_p = st.dev(f_p), *d_d = st.dev(f_d), *d_g = st.dev(f_g);
   const dim3 grid((n + 127) / 128), blk(128);
   if (e.kind == 0)
     hipLaunchKernelGGL((query_kernel<double, Map2D, Lookup2D<double>, 2>), grid, blk, 0, c->stream, n, e.m2, d_p, d_d,
@@ -1367,10 +1487,7 @@ int neo_esdf_query(neo_ctx *c, int scene_id, int n, const double *pts, double *d
   else
     hipLaunchKernelGGL((query_kernel<double, Map3D, Lookup3D<double, __half, 9>, 3>), grid, blk, 0, c->stream, n, e.m3,
                        d_p, d_d, d_g);
-  HIPCHK(c, hipMemcpyAsync(dist, d_d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (grad) HIPCHK(c, hipMemcpyAsync(grad, d_g, (size_t)n * dm * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return NEO_OK;
+  return st.download();
 }
 
 int neo_cost_grad_batch_dev(neo_ctx *c, int scene_id, int B, int M, int D, const double *x, const double *head,
@@ -1399,77 +1516,20 @@ int neo_cost_grad_batch(neo_ctx *c, int scene_id, int B, int M, int D, const dou
   if (rc) return rc;
   if (!x || !head || !tail || !cost || !costs4 || !grad) return fail_locked(c, NEO_ERR_INVALID, "null buffer");
   if (B == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> whole_call(c->mu);  // scratch buffers stay ours until the copies back are done
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
   const size_t n = (size_t)D * (M - 1) + M, bs = (size_t)B;
-  // scratch layout [x | head | tail | cost | costs4 | grad | coeffs | status]; small calls (get_cost / get_grad of one
-  // trajectory) through the pinned mirror: one copy each way, as in neo_optimize_batch
-  size_t o_x, o_h, o_t, o_c, o_c4, o_g, o_co, o_st, o_end;
-  {
-    Carver lay(nullptr);
-    auto at = [&](size_t bytes) { lay.take<char>(0); const size_t o = lay.off; lay.off += bytes; return o; };
-    o_x = at(bs * n * sizeof(double));
-    o_h = at(bs * 3 * D * sizeof(double));
-    o_t = at(bs * 3 * D * sizeof(double));
-    o_c = at(bs * sizeof(double));
-    o_c4 = at(bs * 4 * sizeof(double));
-    o_g = at(bs * n * sizeof(double));
-    o_co = at(bs * 6 * M * D * sizeof(double));
-    o_st = at(bs * sizeof(int));
-    o_end = lay.off;
-  }
-  const bool staged = o_end <= (size_t)256 * 1024;
-  double *dx, *dh, *dt, *dc, *dc4, *dg, *dco;
-  int *dst;
-  {
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    hipSetDevice(c->device);
-    rc = ensure_scratch(c, o_end + 256);
-    if (rc) return rc;
-    if (staged) {
-      rc = ensure_pinned(c, o_end + 256);
-      if (rc) return rc;
-    }
-    char *dbase = static_cast<char *>(c->scratch), *hbase = static_cast<char *>(c->pinned);
-    dx = reinterpret_cast<double *>(dbase + o_x);
-    dh = reinterpret_cast<double *>(dbase + o_h);
-    dt = reinterpret_cast<double *>(dbase + o_t);
-    dc = reinterpret_cast<double *>(dbase + o_c);
-    dc4 = reinterpret_cast<double *>(dbase + o_c4);
-    dg = reinterpret_cast<double *>(dbase + o_g);
-    dco = reinterpret_cast<double *>(dbase + o_co);
-    dst = reinterpret_cast<int *>(dbase + o_st);
-    if (staged) {
-      std::memcpy(hbase + o_x, x, bs * n * sizeof(double));
-      std::memcpy(hbase + o_h, head, bs * 3 * D * sizeof(double));
-      std::memcpy(hbase + o_t, tail, bs * 3 * D * sizeof(double));
-      HIPCHK(c, hipMemcpyAsync(dbase + o_x, hbase + o_x, o_c - o_x, hipMemcpyHostToDevice, c->stream));
-    } else {
-      HIPCHK(c, hipMemcpyAsync(dx, x, bs * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(dh, head, bs * 3 * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(dt, tail, bs * 3 * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-  }
-  rc = neo_cost_grad_batch_dev(c, scene_id, B, M, D, dx, dh, dt, dc, dc4, dg, coeffs ? dco : nullptr, dst);
+  HostStage st(c, kStagedUpTo);  // (get_cost / get_grad of one trajectory: one copy each way)
+  const auto fx = st.in(x, bs * n), fh = st.in(head, bs * 3 * D), ft = st.in(tail, bs * 3 * D);
+  const auto fc = st.out(cost, bs), fc4 = st.out(costs4, bs * 4), fg = st.out(grad, bs * n);
+  const auto fco = st.out(coeffs, bs * 6 * M * D);
+  const auto fst = st.out(status, bs);
+  rc = st.upload();
   if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (staged) {
-    char *dbase = static_cast<char *>(c->scratch), *hbase = static_cast<char *>(c->pinned);
-    HIPCHK(c, hipMemcpyAsync(hbase + o_c, dbase + o_c, o_end - o_c, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(cost, hbase + o_c, bs * sizeof(double));
-    std::memcpy(costs4, hbase + o_c4, bs * 4 * sizeof(double));
-    std::memcpy(grad, hbase + o_g, bs * n * sizeof(double));
-    if (coeffs) std::memcpy(coeffs, hbase + o_co, bs * 6 * M * D * sizeof(double));
-    if (status) std::memcpy(status, hbase + o_st, bs * sizeof(int));
-    return NEO_OK;
-  }
-  HIPCHK(c, hipMemcpyAsync(cost, dc, bs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(costs4, dc4, bs * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(grad, dg, bs * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (coeffs) HIPCHK(c, hipMemcpyAsync(coeffs, dco, bs * 6 * M * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (status) HIPCHK(c, hipMemcpyAsync(status, dst, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return NEO_OK;
+  rc = neo_cost_grad_batch_dev(c, scene_id, B, M, D, st.dev(fx), st.dev(fh), st.dev(ft), st.dev(fc), st.dev(fc4), st.dev(fg),
+                               coeffs ? st.dev(fco) : nullptr, st.dev(fst));
+  if (rc) return rc;
+  return st.download();
 }
 
 // IO32: coeffs / grad_C / grad_T are floats (the _f32 entry points; fp32 sampling only)
@@ -1510,32 +1570,21 @@ static int sampled_terms_host(neo_ctx *c, int scene_id, int B, int M, int D, con
   if (rc) return rc;
   if (!coeffs || !ts || !costs2 || !grad_C || !grad_T) return fail_locked(c, NEO_ERR_INVALID, "null buffer");
   if (B == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> whole_call(c->mu);  // scratch buffers stay ours until the copies back are done
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
   const size_t bs = (size_t)B, nc = (size_t)6 * M * D, es = io32 ? sizeof(float) : sizeof(double);
-  void *dco, *dgc, *dgt;
-  double *dts, *dc2;
-  {
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    hipSetDevice(c->device);
-    rc = ensure_scratch(c, bs * (2 * nc + 2 * M + 2) * sizeof(double) + 6 * 256);
-    if (rc) return rc;
-    Carver cv(c->scratch);
-    dco = cv.take<double>(bs * nc);  // (sized for doubles either way)
-    dts = cv.take<double>(bs * M);
-    dc2 = cv.take<double>(bs * 2);
-    dgc = cv.take<double>(bs * nc);
-    dgt = cv.take<double>(bs * M);
-    HIPCHK(c, hipMemcpyAsync(dco, coeffs, bs * nc * es, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dts, ts, bs * M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
-  rc = sampled_terms_dev(c, scene_id, B, M, D, dco, dts, dc2, dgc, dgt, io32);
+  // coeffs / grad_C / grad_T as bytes: floats or doubles on the wire, sized for doubles either way
+  HostStage st(c, 0);
+  const auto fco = st.in(static_cast<const char *>(coeffs), bs * nc * es, bs * nc * sizeof(double));
+  const auto fts = st.in(ts, bs * M);
+  const auto fc2 = st.out(costs2, bs * 2);
+  const auto fgc = st.out(static_cast<char *>(grad_C), bs * nc * es, bs * nc * sizeof(double));
+  const auto fgt = st.out(static_cast<char *>(grad_T), bs * M * es, bs * M * sizeof(double));
+  rc = st.upload();
   if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  HIPCHK(c, hipMemcpyAsync(costs2, dc2, bs * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(grad_C, dgc, bs * nc * es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(grad_T, dgt, bs * M * es, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return NEO_OK;
+  rc = sampled_terms_dev(c, scene_id, B, M, D, st.dev(fco), st.dev(fts), st.dev(fc2), st.dev(fgc), st.dev(fgt), io32);
+  if (rc) return rc;
+  return st.download();
 }
 
 int neo_sampled_terms_batch(neo_ctx *c, int scene_id, int B, int M, int D, const double *coeffs, const double *ts,
@@ -1683,102 +1732,27 @@ int neo_optimize_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B
   if (rc) return rc;
   if (!x || !head || !tail || !costs4 || !nit || !nfev || !status) return fail_locked(c, NEO_ERR_INVALID, "null buffer");
   if (B == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> whole_call(c->mu);  // scratch buffers stay ours until the copies back are done
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
   const size_t n = (size_t)D * (M - 1) + M, bs = (size_t)B;
-  double *dx, *dh, *dt, *dc4, *dc4l;
-  int *dnit, *dnfev, *dst, *dslots = nullptr;
   std::vector<int> slots;
   if (scene_ids) {
-    slots.resize(bs);
-    int kind0 = -1;
-    for (size_t i = 0; i < bs; ++i) {
-      const int s = neo_scene_slot(c, scene_ids[i]);
-      if (s < 0) return fail(c, NEO_ERR_NO_MAP, "no ESDF for one of scene_ids");
-      const int k = c->maps.find(scene_ids[i])->second.kind;
-      if (kind0 < 0) kind0 = k;
-      if (k != kind0) return fail(c, NEO_ERR_INVALID, "scene_ids mix 2-D and 3-D maps");
-      slots[i] = s;
-    }
-  }
-  // Scratch layout [head | tail | slots | x | costs4 | costs4_last | nit | nfev | status]: the inputs are one contiguous
-  // range ending with x, the outputs one starting with it.  The host side of both copies is a pinned mirror of the
-  // same layout -- one hipMemcpyAsync each way (a single plan() of the reference's shape: 0.36 -> 0.27 ms; ten copies
-  // from and to pageable memory cost almost as much as the kernel).
-  size_t o_h, o_t, o_s, o_x, o_c4, o_c4l, o_nit, o_nfev, o_st, o_end;
-  {
-    Carver lay(nullptr);
-    auto at = [&](size_t bytes) { lay.take<char>(0); const size_t o = lay.off; lay.off += bytes; return o; };
-    o_h = at(bs * 3 * D * sizeof(double));
-    o_t = at(bs * 3 * D * sizeof(double));
-    o_s = at(bs * sizeof(int));
-    o_x = at(bs * n * sizeof(double));
-    o_c4 = at(bs * 4 * sizeof(double));
-    o_c4l = at(bs * 4 * sizeof(double));
-    o_nit = at(bs * sizeof(int));
-    o_nfev = at(bs * sizeof(int));
-    o_st = at(bs * sizeof(int));
-    o_end = lay.off;
-  }
-  // (small calls only: from a megabyte on, the extra pass over the data costs more than the copies' latencies --
-  //  8192 replans of the reference's shape per call: 1.46 M/s direct, 1.28 M/s staged)
-  const bool staged = o_end <= (size_t)256 * 1024;
-  {
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    hipSetDevice(c->device);
-    rc = ensure_scratch(c, o_end + 256);
+    rc = scene_slots(c, scene_ids, bs, false, slots);
     if (rc) return rc;
-    if (staged) {
-      rc = ensure_pinned(c, o_end + 256);
-      if (rc) return rc;
-    }
-    char *dbase = static_cast<char *>(c->scratch), *hbase = static_cast<char *>(c->pinned);
-    dh = reinterpret_cast<double *>(dbase + o_h);
-    dt = reinterpret_cast<double *>(dbase + o_t);
-    dslots = reinterpret_cast<int *>(dbase + o_s);
-    dx = reinterpret_cast<double *>(dbase + o_x);
-    dc4 = reinterpret_cast<double *>(dbase + o_c4);
-    dc4l = reinterpret_cast<double *>(dbase + o_c4l);
-    dnit = reinterpret_cast<int *>(dbase + o_nit);
-    dnfev = reinterpret_cast<int *>(dbase + o_nfev);
-    dst = reinterpret_cast<int *>(dbase + o_st);
-    if (staged) {
-      std::memcpy(hbase + o_h, head, bs * 3 * D * sizeof(double));
-      std::memcpy(hbase + o_t, tail, bs * 3 * D * sizeof(double));
-      if (scene_ids) std::memcpy(hbase + o_s, slots.data(), bs * sizeof(int));
-      std::memcpy(hbase + o_x, x, bs * n * sizeof(double));
-      HIPCHK(c, hipMemcpyAsync(dbase + o_h, hbase + o_h, o_c4 - o_h, hipMemcpyHostToDevice, c->stream));
-    } else {
-      HIPCHK(c, hipMemcpyAsync(dx, x, bs * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(dh, head, bs * 3 * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(dt, tail, bs * 3 * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      if (scene_ids)
-        HIPCHK(c, hipMemcpyAsync(dslots, slots.data(), bs * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    }
   }
-  rc = neo_optimize_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? dslots : nullptr, B, M, D, dx, dh,
-                              dt, dc4, dc4l, dnit, dnfev, dst);
+  // the inputs are one contiguous range ending with x, the outputs one starting with it
+  HostStage st(c, kStagedUpTo);
+  const auto fh = st.in(head, bs * 3 * D), ft = st.in(tail, bs * 3 * D);
+  const auto fs = st.in(scene_ids ? slots.data() : nullptr, bs);
+  const auto fx = st.inout(x, bs * n);
+  const auto fc4 = st.out(costs4, bs * 4), fc4l = st.out(costs4_last, bs * 4);
+  const auto fnit = st.out(nit, bs), fnfev = st.out(nfev, bs), fst = st.out(status, bs);
+  rc = st.upload();
   if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (!staged) {
-    HIPCHK(c, hipMemcpyAsync(x, dx, bs * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(costs4, dc4, bs * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (costs4_last) HIPCHK(c, hipMemcpyAsync(costs4_last, dc4l, bs * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(nit, dnit, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(nfev, dnfev, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(status, dst, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return NEO_OK;
-  }
-  char *dbase = static_cast<char *>(c->scratch), *hbase = static_cast<char *>(c->pinned);
-  HIPCHK(c, hipMemcpyAsync(hbase + o_x, dbase + o_x, o_end - o_x, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::memcpy(x, hbase + o_x, bs * n * sizeof(double));
-  std::memcpy(costs4, hbase + o_c4, bs * 4 * sizeof(double));
-  if (costs4_last) std::memcpy(costs4_last, hbase + o_c4l, bs * 4 * sizeof(double));
-  std::memcpy(nit, hbase + o_nit, bs * sizeof(int));
-  std::memcpy(nfev, hbase + o_nfev, bs * sizeof(int));
-  std::memcpy(status, hbase + o_st, bs * sizeof(int));
-  return NEO_OK;
+  rc = neo_optimize_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fs) : nullptr, B, M, D, st.dev(fx),
+                              st.dev(fh), st.dev(ft), st.dev(fc4), st.dev(fc4l), st.dev(fnit), st.dev(fnfev), st.dev(fst));
+  if (rc) return rc;
+  return st.download();
 }
 
 int neo_eval_traj_batch(neo_ctx *c, int B, int M, int D, const double *x, const double *head, const double *tail,
@@ -1790,40 +1764,14 @@ int neo_eval_traj_batch(neo_ctx *c, int B, int M, int D, const double *x, const 
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
   const size_t n = (size_t)D * (M - 1) + M, bs = (size_t)B;
-  // scratch layout [x | head | tail | state | count]; small calls through the pinned mirror (one copy each way, as in
-  // neo_optimize_batch)
-  size_t o_x, o_h, o_t, o_s, o_c, o_end;
-  {
-    Carver lay(nullptr);
-    auto at = [&](size_t bytes) { lay.take<char>(0); const size_t o = lay.off; lay.off += bytes; return o; };
-    o_x = at(bs * n * sizeof(double));
-    o_h = at(bs * 3 * D * sizeof(double));
-    o_t = at(bs * 3 * D * sizeof(double));
-    o_s = at(bs * K * 3 * D * sizeof(double));
-    o_c = at(bs * sizeof(int));
-    o_end = lay.off;
-  }
-  const bool staged = o_end <= (size_t)256 * 1024;
-  rc = ensure_scratch(c, o_end + 256);
+  HostStage st(c, kStagedUpTo);
+  const auto fx = st.in(x, bs * n), fh = st.in(head, bs * 3 * D), ft = st.in(tail, bs * 3 * D);
+  const auto fs = st.out(state, bs * K * 3 * D);
+  const auto fcnt = st.out(count, bs);
+  rc = st.upload();
   if (rc) return rc;
-  if (staged) {
-    rc = ensure_pinned(c, o_end + 256);
-    if (rc) return rc;
-  }
-  char *dbase = static_cast<char *>(c->scratch), *hbase = static_cast<char *>(c->pinned);
-  double *dx = reinterpret_cast<double *>(dbase + o_x), *dh = reinterpret_cast<double *>(dbase + o_h);
-  double *dt = reinterpret_cast<double *>(dbase + o_t), *ds = reinterpret_cast<double *>(dbase + o_s);
-  int *dcnt = reinterpret_cast<int *>(dbase + o_c);
-  if (staged) {
-    std::memcpy(hbase + o_x, x, bs * n * sizeof(double));
-    std::memcpy(hbase + o_h, head, bs * 3 * D * sizeof(double));
-    std::memcpy(hbase + o_t, tail, bs * 3 * D * sizeof(double));
-    HIPCHK(c, hipMemcpyAsync(dbase + o_x, hbase + o_x, o_s - o_x, hipMemcpyHostToDevice, c->stream));
-  } else {
-    HIPCHK(c, hipMemcpyAsync(dx, x, bs * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dh, head, bs * 3 * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dt, tail, bs * 3 * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
+  double *dx = st.dev(fx), *dh = st.dev(fh), *dt = st.dev(ft), *ds = st.dev(fs);
+  int *dcnt = st.dev(fcnt);
   if (D == 2)
     hipLaunchKernelGGL((traj_state_kernel<2>), dim3(B), dim3(kWave), 0, c->stream, B, M, c->dev, dx, dh, dt, hz, K, ds,
                        dcnt);
@@ -1831,17 +1779,7 @@ int neo_eval_traj_batch(neo_ctx *c, int B, int M, int D, const double *x, const 
     hipLaunchKernelGGL((traj_state_kernel<3>), dim3(B), dim3(kWave), 0, c->stream, B, M, c->dev, dx, dh, dt, hz, K, ds,
                        dcnt);
   HIPCHK(c, hipGetLastError());
-  if (staged) {
-    HIPCHK(c, hipMemcpyAsync(hbase + o_s, dbase + o_s, o_end - o_s, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(state, hbase + o_s, bs * K * 3 * D * sizeof(double));
-    std::memcpy(count, hbase + o_c, bs * sizeof(int));
-    return NEO_OK;
-  }
-  HIPCHK(c, hipMemcpyAsync(state, ds, bs * K * 3 * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(count, dcnt, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return NEO_OK;
+  return st.download();
 }
 
 // ---- trajectory audit (ros_node/traj_planner_node.py:333-363; kernel: neo_audit.hpp)
@@ -1888,43 +1826,25 @@ int neo_audit_traj_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int
   int rc = audit_check(c, B, M, D, x, head, tail, hz, audit, count, flags);
   if (rc) return rc;
   if (B == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> whole_call(c->mu);  // scratch buffers stay ours until the copies back are done
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
   hipSetDevice(c->device);
   const size_t n = (size_t)D * (M - 1) + M, bs = (size_t)B;
   std::vector<int> slots;
-  if (scene_ids) {  // scene ids -> map-table slots, as neo_optimize_batch
-    slots.resize(bs);
-    int kind0 = -1;
-    for (size_t i = 0; i < bs; ++i) {
-      const int s = neo_scene_slot(c, scene_ids[i]);
-      if (s < 0) return fail(c, NEO_ERR_NO_MAP, "no ESDF for one of scene_ids");
-      const int k = c->maps.find(scene_ids[i])->second.kind;
-      if (kind0 < 0) kind0 = k;
-      if (k != kind0) return fail(c, NEO_ERR_INVALID, "scene_ids mix 2-D and 3-D maps");
-      slots[i] = s;
-    }
+  if (scene_ids) {
+    rc = scene_slots(c, scene_ids, bs, false, slots);
+    if (rc) return rc;
   }
-  rc = ensure_scratch(c, bs * (n + 6 * D + NEO_AUDIT_FIELDS) * sizeof(double) + 3 * bs * sizeof(int) + 7 * 256);
+  HostStage st(c, 0);
+  const auto fx = st.in(x, bs * n), fh = st.in(head, bs * 3 * D), ft = st.in(tail, bs * 3 * D);
+  const auto fs = st.in(scene_ids ? slots.data() : nullptr, bs);
+  const auto fa = st.out(audit, bs * NEO_AUDIT_FIELDS);
+  const auto fcnt = st.out(count, bs), ffl = st.out(flags, bs);
+  rc = st.upload();
   if (rc) return rc;
-  Carver cv(c->scratch);
-  double *dx = cv.take<double>(bs * n), *dh = cv.take<double>(bs * 3 * D), *dt = cv.take<double>(bs * 3 * D);
-  double *da = cv.take<double>(bs * NEO_AUDIT_FIELDS);
-  int *dslots = cv.take<int>(bs), *dcnt = cv.take<int>(bs), *dfl = cv.take<int>(bs);
-  HIPCHK(c, hipMemcpyAsync(dx, x, bs * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dh, head, bs * 3 * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dt, tail, bs * 3 * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (scene_ids) HIPCHK(c, hipMemcpyAsync(dslots, slots.data(), bs * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  rc = neo_audit_traj_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? dslots : nullptr, B, M, D, dx, dh, dt,
-                                hz, weights3, da, dcnt, dfl);
-  if (rc) {
-    hipStreamSynchronize(c->stream);  // (the slot copy in flight reads `slots`)
-    return rc;
-  }
-  HIPCHK(c, hipMemcpyAsync(audit, da, bs * NEO_AUDIT_FIELDS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(count, dcnt, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(flags, dfl, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return NEO_OK;
+  rc = neo_audit_traj_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fs) : nullptr, B, M, D, st.dev(fx),
+                                st.dev(fh), st.dev(ft), hz, weights3, st.dev(fa), st.dev(fcnt), st.dev(ffl));
+  if (rc) return rc;
+  return st.download();
 }
 
 // ---- geo warm start (traj_planner/astar_planner.py, geo_planner.py:19-101; kernels: neo_geo.hpp)
@@ -1945,18 +1865,6 @@ static int geo_scene_kind(neo_ctx *c, int scene_id) {
   auto it = c->maps.find(scene_id);
   if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "geo: no ESDF for this scene");
   if (it->second.kind != 0) return fail(c, NEO_ERR_UNSUPPORTED, "geo: the A* warm start needs a 2-D map");
-  return NEO_OK;
-}
-
-// host scene ids -> 2-D map-table slots
-static int geo_slots(neo_ctx *c, const int32_t *scene_ids, int B, std::vector<int> &slots) {
-  slots.resize((size_t)B);
-  for (int i = 0; i < B; ++i) {
-    auto it = c->maps.find(scene_ids[i]);
-    if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "geo: no ESDF for one of scene_ids");
-    if (it->second.kind != 0) return fail(c, NEO_ERR_UNSUPPORTED, "geo: one of scene_ids is a 3-D map");
-    slots[i] = it->second.slot;
-  }
   return NEO_OK;
 }
 
@@ -1981,42 +1889,26 @@ int neo_geo_search_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int
                          int32_t *path_len, double *path_cost, int32_t *expansions, int32_t *flags) {
   int rc = geo_check(c, B, start, target, max_expansions, path_cap, key_pts, path, path_len, path_cost, expansions, flags);
   if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> whole_call(c->mu);  // scratch buffers stay ours until the copies back are done
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
   hipSetDevice(c->device);
   rc = rebuild_tables(c);
   if (rc) return rc;
-  std::vector<int> slots;
-  if (scene_ids) {
-    rc = geo_slots(c, scene_ids, B, slots);
-    if (rc) return rc;
-  } else {
-    rc = geo_scene_kind(c, scene_id);
-    if (rc) return rc;
-  }
   const size_t bs = (size_t)B, pc = path ? (size_t)path_cap : 0;
-  rc = ensure_scratch(c, bs * (4 + 8 + 1 + 2 * pc) * sizeof(double) + 4 * bs * sizeof(int) + 10 * 256);
+  std::vector<int> slots;
+  rc = scene_ids ? scene_slots(c, scene_ids, bs, true, slots) : geo_scene_kind(c, scene_id);
   if (rc) return rc;
-  Carver cv(c->scratch);
-  double *ds = cv.take<double>(2 * bs), *dt = cv.take<double>(2 * bs), *dk = cv.take<double>(8 * bs);
-  double *dc = cv.take<double>(bs), *dp = path ? cv.take<double>(2 * bs * pc) : nullptr;
-  int *dslots = cv.take<int>(bs), *dl = cv.take<int>(bs), *de = cv.take<int>(bs), *df = cv.take<int>(bs);
-  HIPCHK(c, hipMemcpyAsync(ds, start, 2 * bs * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dt, target, 2 * bs * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (scene_ids) HIPCHK(c, hipMemcpyAsync(dslots, slots.data(), bs * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  rc = neo_geo_search_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? dslots : nullptr, B, ds, dt,
-                                max_expansions, path_cap, dk, dp, dl, dc, de, df);
-  if (rc) {
-    hipStreamSynchronize(c->stream);  // (the copies in flight read the caller's buffers)
-    return rc;
-  }
-  HIPCHK(c, hipMemcpyAsync(key_pts, dk, 8 * bs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(path_cost, dc, bs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(path_len, dl, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(expansions, de, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(flags, df, bs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (path) HIPCHK(c, hipMemcpyAsync(path, dp, 2 * bs * pc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return NEO_OK;
+  HostStage st(c, 0);
+  const auto fs = st.in(start, 2 * bs), ft = st.in(target, 2 * bs);
+  const auto fsl = st.in(scene_ids ? slots.data() : nullptr, bs);
+  const auto fk = st.out(key_pts, 8 * bs), fc = st.out(path_cost, bs), fp = st.out(path, 2 * bs * pc);
+  const auto fl = st.out(path_len, bs), fe = st.out(expansions, bs), ff = st.out(flags, bs);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_geo_search_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fsl) : nullptr, B, st.dev(fs),
+                                st.dev(ft), max_expansions, path_cap, st.dev(fk), path ? st.dev(fp) : nullptr, st.dev(fl),
+                                st.dev(fc), st.dev(fe), st.dev(ff));
+  if (rc) return rc;
+  return st.download();
 }
 
 int neo_geo_prune_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const double *paths,
@@ -2027,35 +1919,24 @@ int neo_geo_prune_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int 
   for (int i = 0; i < B; ++i)
     if (path_len[i] < 1 || path_len[i] > path_stride)
       return fail_locked(c, NEO_ERR_INVALID, "geo prune: path_len must be in [1, path_stride]");
-  std::lock_guard<std::recursive_mutex> whole_call(c->mu);
+  std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
   int rc = rebuild_tables(c);
   if (rc) return rc;
-  std::vector<int> slots;
-  if (scene_ids) {
-    rc = geo_slots(c, scene_ids, B, slots);
-    if (rc) return rc;
-  } else {
-    rc = geo_scene_kind(c, scene_id);
-    if (rc) return rc;
-  }
   const size_t bs = (size_t)B, ps = (size_t)path_stride;
-  rc = ensure_scratch(c, bs * (2 * ps + 8) * sizeof(double) + 2 * bs * sizeof(int) + 5 * 256);
+  std::vector<int> slots;
+  rc = scene_ids ? scene_slots(c, scene_ids, bs, true, slots) : geo_scene_kind(c, scene_id);
   if (rc) return rc;
-  Carver cv(c->scratch);
-  double *dp = cv.take<double>(2 * bs * ps), *dk = cv.take<double>(8 * bs);
-  int *dl = cv.take<int>(bs), *dslots = cv.take<int>(bs);
-  HIPCHK(c, hipMemcpyAsync(dp, paths, 2 * bs * ps * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dl, path_len, bs * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (scene_ids) HIPCHK(c, hipMemcpyAsync(dslots, slots.data(), bs * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  rc = geo_prune(c, scene_ids ? scene_ids[0] : scene_id, B, scene_ids ? dslots : nullptr, dp, dl, path_stride, dk);
-  if (rc) {
-    hipStreamSynchronize(c->stream);
-    return rc;
-  }
-  HIPCHK(c, hipMemcpyAsync(key_pts, dk, 8 * bs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return NEO_OK;
+  HostStage st(c, 0);
+  const auto fp = st.in(paths, 2 * bs * ps);
+  const auto fl = st.in(path_len, bs), fsl = st.in(scene_ids ? slots.data() : nullptr, bs);
+  const auto fk = st.out(key_pts, 8 * bs);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = geo_prune(c, scene_ids ? scene_ids[0] : scene_id, B, scene_ids ? st.dev(fsl) : nullptr, st.dev(fp), st.dev(fl),
+                 path_stride, st.dev(fk));
+  if (rc) return rc;
+  return st.download();
 }
 
 int neo_geo_workspace_budget(neo_ctx *c, size_t bytes) {
