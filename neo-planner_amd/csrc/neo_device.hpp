@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
+#include "../../include/neo_planner.h"
+
 namespace neo {
 
 constexpr int kWave = 64;
@@ -539,7 +541,7 @@ struct Lookup3D {
   __device__ __forceinline__ Raw load(const Addr &a) const {
     const E *vox = static_cast<const E *>(m.data);
     Raw q;
-    if (LAYOUT == 2 || (LAYOUT == 9 && m.layout == 2)) {
+    if (LAYOUT == 2 || (LAYOUT == 9 && m.layout == NEO_LAYOUT_CELL8)) {
       // cell-packed: the 8 corners [dz][dy][dx] of cell (ix, iy, iz) are contiguous and 16-byte aligned:
       // one lookup = one 32-byte (fp32) or 16-byte (fp16) read instead of four gathers
       const unsigned int cell = __umul24(__umul24((unsigned)a.i0[2], (unsigned)m.ny) + (unsigned)a.i0[1], (unsigned)m.nx) +
@@ -559,7 +561,7 @@ struct Lookup3D {
           q.c[w >> 1][w & 1][1] = __half2float(__ushort_as_half((unsigned short)(v[w] >> 16)));
         }
       }
-    } else if (LAYOUT == 3 || (LAYOUT == 9 && m.layout == 3)) {
+    } else if (LAYOUT == 3 || (LAYOUT == 9 && m.layout == NEO_LAYOUT_BRICK)) {
       // corner bricks: the cells are grouped in blocks of 2 x 2 x 2 (fp32) or 4 x 2 x 2 (fp16: x is the direction most
       // requests fly in), and all (2+1)^3 = 27 (or 5 x 3 x 3 = 45) corners of a block sit in ONE 128-byte line, [z][y][x]
       // inside the line.  A lookup is four x-pairs of that line -- one address register, four immediate offsets -- and
@@ -584,7 +586,7 @@ struct Lookup3D {
             load_pair<E>(vox + blk * 64u + in_line + so, q.c[dz][dy][0], q.c[dz][dy][1]);
           }
         }
-    } else if (LAYOUT == 0 || (LAYOUT == 9 && m.layout == 0)) {
+    } else if (LAYOUT == 0 || (LAYOUT == 9 && m.layout == NEO_LAYOUT_LINEAR)) {
       // 32-bit element index of corner (0,0,0); the other three x-pairs sit at +nx, +nx*ny, +nx*ny+nx
       const unsigned int base = __umul24(__umul24((unsigned)a.i0[2], (unsigned)m.ny) + (unsigned)a.i0[1], (unsigned)m.nx) +
                                 (unsigned)a.i0[0];
@@ -625,53 +627,6 @@ struct Lookup3D {
             q.c[dz][1][dx] = __half2float(__ushort_as_half((unsigned short)(u >> 16)));
           }
       }
-    }
-    return q;
-  }
-  // ---- the gathers of load() as LDS-DMA (yz-quad layout only): the 32 (fp32) / 16 (fp16) bytes of a lookup go from
-  // HBM / L2 straight into LDS -- `buffer_load_dwordx4 ... offen lds`, no destination registers -- so a lane can have as
-  // many lookups in flight as the wavefront has landing room, instead of as many as it has spare VGPRs.  One
-  // wave-instruction lands lane-linear: piece k of the wavefront's 64 lookups at land + k * 1024 + lane * 16.
-  static constexpr int kAsyncPieces = sizeof(E) == 4 ? 2 : 1;   // 16-byte pieces per lookup
-  static constexpr int kAsyncBytes = kAsyncPieces * 1024;       // landing bytes per wavefront and lookup round
-  typedef __attribute__((address_space(3))) void *LdsPtr;
-  __device__ __forceinline__ void load_async(const Addr &a, char *land /*wave-uniform LDS address*/) const {
-    static_assert(LAYOUT == 1, "LDS-DMA gathers are written for the yz-quad layout");
-    const unsigned int cell = __umul24(__umul24((unsigned)a.i0[2], (unsigned)m.ny) + (unsigned)a.i0[1], (unsigned)m.nx) +
-                              (unsigned)a.i0[0];
-    if constexpr (sizeof(E) == 4) {
-      // (the second half at its own register offset, hidden from the compiler: folded into the instruction's immediate
-      //  offset -- which it does with a constant in either offset operand -- the 16 would be added to the LDS address as
-      //  well as to the memory address and shift the landing by one lane)
-      const unsigned int off0 = cell * 16u;
-      unsigned int off1 = off0 + 16u;
-      asm volatile("" : "+v"(off1));
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsPtr)land, 16, (int)off0, 0, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsPtr)(land + 1024), 16, (int)off1, 0, 0, 0);
-    } else {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsPtr)land, 16, (int)(cell * 8u), 0, 0, 0);
-    }
-  }
-  // the lane's own lookup back out of the landing area (after the wavefront has waited for its LDS-DMA loads)
-  __device__ __forceinline__ Raw read_staged(const char *land) const {
-    typedef unsigned int U4 __attribute__((ext_vector_type(4)));
-    Raw q;
-    const U4 lo = *reinterpret_cast<const U4 *>(land + lane_id() * 16);
-    if constexpr (sizeof(E) == 4) {
-      const U4 hi = *reinterpret_cast<const U4 *>(land + 1024 + lane_id() * 16);
-      q.c[0][0][0] = __uint_as_float(lo[0]); q.c[0][1][0] = __uint_as_float(lo[1]);
-      q.c[1][0][0] = __uint_as_float(lo[2]); q.c[1][1][0] = __uint_as_float(lo[3]);
-      q.c[0][0][1] = __uint_as_float(hi[0]); q.c[0][1][1] = __uint_as_float(hi[1]);
-      q.c[1][0][1] = __uint_as_float(hi[2]); q.c[1][1][1] = __uint_as_float(hi[3]);
-    } else {
-#pragma unroll
-      for (int dx = 0; dx < 2; ++dx)
-#pragma unroll
-        for (int dz = 0; dz < 2; ++dz) {
-          const unsigned int u = lo[2 * dx + dz];
-          q.c[dz][0][dx] = __half2float(__ushort_as_half((unsigned short)(u & 0xffffu)));
-          q.c[dz][1][dx] = __half2float(__ushort_as_half((unsigned short)(u >> 16)));
-        }
     }
     return q;
   }

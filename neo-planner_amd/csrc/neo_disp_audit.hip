@@ -13,26 +13,13 @@ static int launch_audit(neo_ctx *c, const AuditArgs &a) {
   return NEO_OK;
 }
 
-template <typename E>
-static int launch_audit_3d(neo_ctx *c, int layout, const AuditArgs &a) {
-  switch (layout) {
-    case NEO_LAYOUT_LINEAR: return launch_audit<3, Map3D, Lookup3D<double, E, 0>>(c, a);
-    case NEO_LAYOUT_YZ4: return launch_audit<3, Map3D, Lookup3D<double, E, 1>>(c, a);
-    case NEO_LAYOUT_CELL8: return launch_audit<3, Map3D, Lookup3D<double, E, 2>>(c, a);
-    case NEO_LAYOUT_BRICK: return launch_audit<3, Map3D, Lookup3D<double, E, 3>>(c, a);
-    default: return fail(c, NEO_ERR_INVALID, "audit: unknown 3-D layout");
-  }
-}
-
 int dispatch_audit(neo_ctx *c, int kind, int elem, int layout, int D, const AuditArgs &a) {
   if (kind == 0) {  // the 2-D reference map: D = 2, or D = 3 looked up on its first two axes (as the sampled cost does)
     if (D == 2) return launch_audit<2, Map2D, Lookup2D<double>>(c, a);
     return launch_audit<3, Map2D, Lookup2D<double>>(c, a);
   }
   if (D != 3) return fail(c, NEO_ERR_INVALID, "audit: a 3-D map needs D = 3");
-  if (elem == NEO_F32) return launch_audit_3d<float>(c, layout, a);
-  if (elem == NEO_F16) return launch_audit_3d<__half>(c, layout, a);
-  return fail(c, NEO_ERR_INVALID, "audit: unsupported 3-D element type");
+  return visit_field<double>(c, elem, layout, [&](auto lk) { return launch_audit<3, Map3D, type_of<decltype(lk)>>(c, a); });
 }
 
 }  // namespace neo

@@ -55,17 +55,10 @@ int launch_opt_groups_2d(neo_ctx *c, bool f32, const OptArgs &a) {
   return f32 ? launch_group_2d<float>(c, a) : launch_group_2d<double>(c, a);
 }
 
+// (lane_group_launch, neo_abi.hip, sends no cell-packed field here)
 int launch_opt_groups(neo_ctx *c, int elem, int layout, const OptArgs &a) {
-  if (layout == NEO_LAYOUT_YZ4) {
-    if (elem == NEO_F32) return launch_group<float, Lookup3D<float, float, 1>>(c, a);
-    return launch_group<float, Lookup3D<float, __half, 1>>(c, a);
-  }
-  if (layout == NEO_LAYOUT_BRICK) {
-    if (elem == NEO_F32) return launch_group<float, Lookup3D<float, float, 3>>(c, a);
-    return launch_group<float, Lookup3D<float, __half, 3>>(c, a);
-  }
-  if (elem == NEO_F32) return launch_group<float, Lookup3D<float, float, 0>>(c, a);
-  return launch_group<float, Lookup3D<float, __half, 0>>(c, a);
+  return visit_field<float>(c, elem, layout, Elems<float, __half>{}, Layouts<NEO_LAYOUT_LINEAR, NEO_LAYOUT_YZ4, NEO_LAYOUT_BRICK>{},
+                            [&](auto lk) { return launch_group<float, type_of<decltype(lk)>>(c, a); });
 }
 
 }  // namespace neo

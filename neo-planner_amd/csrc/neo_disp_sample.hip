@@ -25,28 +25,19 @@ int launch_sample(neo_ctx *c, const MapT &map, const SampleArgs &a) {
   return launch_sample_io<D, Real, MapT, LookupT, double>(c, map, a);
 }
 
+template <typename Real>
+int sample_any(neo_ctx *c, const MapEntry &e, int D, const SampleArgs &a) {
+  if (e.kind == 0)
+    return D == 2 ? launch_sample<2, Real, Map2D, Lookup2D<Real>>(c, e.m2, a) : launch_sample<3, Real, Map2D, Lookup2D<Real>>(c, e.m2, a);
+  if (D != 3) return fail(c, NEO_ERR_INVALID, "a 3-D map needs D = 3");
+  return visit_field<Real>(c, e.elem, e.m3.layout,
+                           [&](auto lk) { return launch_sample<3, Real, Map3D, type_of<decltype(lk)>>(c, e.m3, a); });
+}
+
 int dispatch_sample(neo_ctx *c, const MapEntry &e, int D, const SampleArgs &a) {
   const bool f32 = c->params.sample_dtype == NEO_F32;
   if (a.io32 && !f32) return fail(c, NEO_ERR_INVALID, "fp32 coefficient / partials buffers need sample_dtype = NEO_F32");
-  if (e.kind == 0) {
-    if (D == 2)
-      return f32 ? launch_sample<2, float, Map2D, Lookup2D<float>>(c, e.m2, a)
-                 : launch_sample<2, double, Map2D, Lookup2D<double>>(c, e.m2, a);
-    return f32 ? launch_sample<3, float, Map2D, Lookup2D<float>>(c, e.m2, a)
-               : launch_sample<3, double, Map2D, Lookup2D<double>>(c, e.m2, a);
-  }
-  if (D != 3) return fail(c, NEO_ERR_INVALID, "a 3-D map needs D = 3");
-#define NEO_3D(LAY)                                                                                  \
-  if (e.elem == NEO_F32)                                                                             \
-    return f32 ? launch_sample<3, float, Map3D, Lookup3D<float, float, LAY>>(c, e.m3, a)             \
-               : launch_sample<3, double, Map3D, Lookup3D<double, float, LAY>>(c, e.m3, a);          \
-  return f32 ? launch_sample<3, float, Map3D, Lookup3D<float, __half, LAY>>(c, e.m3, a)              \
-             : launch_sample<3, double, Map3D, Lookup3D<double, __half, LAY>>(c, e.m3, a);
-  if (e.m3.layout == 0) { NEO_3D(0) }
-  if (e.m3.layout == 2) { NEO_3D(2) }
-  if (e.m3.layout == 3) { NEO_3D(3) }
-  NEO_3D(1)
-#undef NEO_3D
+  return f32 ? sample_any<float>(c, e, D, a) : sample_any<double>(c, e, D, a);
 }
 
 }  // namespace neo

@@ -218,6 +218,67 @@ inline int slots_for(int M, int D) {
   return ns <= 3 ? (ns < 1 ? 1 : ns) : 4;  // (3: cfg5's n = 161 -- a quarter fewer optimiser-vector instructions than 4 slots)
 }
 
+// ---- run-time values to template arguments: the one place where a field's (element type, layout) and a problem's
+// (FLAT slots, lane layout) become types.  Each visitor calls f with empty tag values; the unit's lambda reads the types
+// off them and names the kernel it owns.  Templates and inlined lambdas only: nothing is allocated, no std::function.
+template <class T>
+struct Type {
+  using type = T;
+};
+template <class Tag>
+using type_of = typename Tag::type;  // type_of<decltype(tag)>
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <typename... E>
+struct Elems {};
+template <int... LAY>
+struct Layouts {};
+template <typename E>
+constexpr int elem_code = std::is_same<E, float>::value ? NEO_F32 : NEO_F16;  // float | __half
+
+template <typename Real, typename E, class F, int... LAY>
+bool visit_layout(int layout, int &rc, F &f, Layouts<LAY...>) {
+  return ((layout == LAY && (rc = f(Type<Lookup3D<Real, E, LAY>>{}), true)) || ...);
+}
+// f(Type<Lookup3D<Real, E, LAY>>) for the stored element type and layout of a 3-D field, out of the ones the family has
+// kernels for: only those are instantiated.  Anything else -- nothing neo_esdf_upload_3d admits -- is NEO_ERR_INVALID.
+template <typename Real, class F, typename... E, int... LAY>
+int visit_field(neo_ctx *c, int elem, int layout, Elems<E...>, Layouts<LAY...> lays, F f) {
+  int rc = NEO_OK;
+  if (((elem == elem_code<E> && visit_layout<Real, E>(layout, rc, f, lays)) || ...)) return rc;
+  return fail(c, NEO_ERR_INVALID, "unknown 3-D field layout / element type");
+}
+// every field neo_esdf_upload_3d admits: fp32 or fp16 elements in any of the four layouts
+template <typename Real, class F>
+int visit_field(neo_ctx *c, int elem, int layout, F f) {
+  return visit_field<Real>(c, elem, layout, Elems<float, __half>{},
+                           Layouts<NEO_LAYOUT_LINEAR, NEO_LAYOUT_YZ4, NEO_LAYOUT_CELL8, NEO_LAYOUT_BRICK>{}, f);
+}
+
+// lane = (piece, dimension) whenever D * M fits the wavefront (cfg2: 63 lanes busy in the PIECE-layout phases instead of
+// 21, a third of the per-dimension state per lane); lane = piece otherwise.  flags bit 512 forces the latter (comparison
+// runs).
+inline bool lane_piece_dim(int D, int M, int flags) { return D * M <= kWave && !(flags & 512); }
+
+// f(Int<NS>, Type<LG>) for the FLAT slots and the lane layout of an M-piece problem: one or two slots on either lane
+// layout, three and four on WaveLanes (n > 128 means D * M > 64: lane = piece).  A family without kernels beyond MAX_NS
+// slots instantiates none and checks slots_for() first, with its own message.
+template <int D, int MAX_NS = 4, class F>
+int visit_slots(int M, int flags, F f) {
+  const bool pd = lane_piece_dim(D, M, flags);
+  switch (slots_for(M, D)) {
+    case 1: return pd ? f(Int<1>{}, Type<WaveLanesPD<D>>{}) : f(Int<1>{}, Type<WaveLanes>{});
+    case 2: return pd ? f(Int<2>{}, Type<WaveLanesPD<D>>{}) : f(Int<2>{}, Type<WaveLanes>{});
+    case 3:
+      if constexpr (MAX_NS >= 3) return f(Int<3>{}, Type<WaveLanes>{});
+      break;
+    default:
+      if constexpr (MAX_NS >= 4) return f(Int<4>{}, Type<WaveLanes>{});
+      break;
+  }
+  return NEO_ERR_INVALID;
+}
+
 // ---- per-family dispatch (neo_disp_*.hip)
 int dispatch_eval(neo_ctx *c, const MapEntry &e, int D, const EvalArgs &a);
 int dispatch_sample(neo_ctx *c, const MapEntry &e, int D, const SampleArgs &a);

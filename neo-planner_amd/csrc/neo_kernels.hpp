@@ -39,9 +39,6 @@
 #endif
 #include "neo_device.hpp"
 #include "neo_lbfgs.hpp"
-#ifdef NEO_STAMPS
-#define NEO_SM_STAMP(i) be.sm_stamp(i)
-#endif
 #include "neo_lbfgs_sm.hpp"
 
 namespace neo {
@@ -49,11 +46,7 @@ namespace neo {
 // the type of the optimiser's scalars and of the line-search state: fp32 where everything else is (Num = float) and the
 // run is the state machine (the straight-line form of the four-slot kernels keeps fp64 scalars)
 template <typename Num, int NS>
-#ifdef NEO_F64_SCALARS  // comparison builds: the fp64 scalars of rounds 1 - 4 everywhere
-using opt_scalar_t = double;
-#else
 using opt_scalar_t = std::conditional_t<sizeof(Num) == 4 && (NS <= NEO_SM_MAX_SLOTS), float, double>;
-#endif
 
 // doubles of LDS staging a wavefront needs: NS * 64 for the FLAT <-> PIECE exchange, 64 rows of [D][8] Reals for the
 // per-piece fold of the sampled partials (the two uses never overlap)
@@ -125,13 +118,6 @@ struct DevBackend {
   double *trace = nullptr;  // optional [trace_cap][4] of this trajectory: (f, step, samples, iteration) per evaluation
   double *trace_xg = nullptr;  // optional [trace_cap][2][n]: the evaluated point and its gradient
   int trace_cap = 0;
-#ifdef NEO_STAMPS  // timing experiments (tools/gpu_straggler.py): 100 MHz wall-clock ticks per phase
-  long long tk[4] = {0, 0, 0, 0};  // forward, sample, backward, evaluations
-  long long tl = 0, tl0 = 0;       // two-loop recursion (direction) time
-  __device__ __forceinline__ void sm_stamp(int i) {
-    if (i == 0) tl0 = wall_clock64(); else tl += wall_clock64() - tl0;
-  }
-#endif
 
   __device__ DevBackend(const DevParams &p, const MapT &mp) : prm(p), map(mp) {}
 
@@ -349,9 +335,6 @@ struct DevBackend {
   __device__ __forceinline__ int eval(const Vec &x, double &f, Vec &g, double *costs) {
     const int lane = lane_id();
     const int p = LG::piece();
-#ifdef NEO_STAMPS
-    const long long s0 = wall_clock64();
-#endif
     NEO_MARK("eval_begin");
     // Lane masks such as `piece < M` are loop invariant: hoisted out of the optimiser loop they are scalar register PAIRS
     // that live across everything, the allocator spills them to lanes of a vector register, and every use inside the
@@ -365,9 +348,6 @@ struct DevBackend {
     double energy, tsum;
     const int st = minco_forward<D, LG, Num, kPcr>(t, prm, energy, tsum);
     NEO_MARK("forward_done");
-#ifdef NEO_STAMPS
-    const long long s1 = wall_clock64();
-#endif
     if (st != 0) {
       f = 0.0;
 #pragma unroll
@@ -388,17 +368,7 @@ struct DevBackend {
       for (int k = 0; k < 6; ++k)
 #pragma unroll
         for (int d = 0; d < DL; ++d) cr[k][d] = (Real)t.c[k][d];
-#ifdef NEO_STAMPS
-      // timing experiment (flags bit 1024): a buffer descriptor with zero records -- the range check drops every gather
-      // (it returns 0 without touching memory) while the instruction stream stays: what the sample loop costs without
-      // its memory latency
-      MapT map_t = map;
-      if constexpr (sizeof(MapT) == sizeof(Map3D))
-        if (prm.dbg & 1024) map_t.bytes = 0;
-      LookupT lk(map_t);
-#else
       LookupT lk(map);
-#endif
       // lanes in proportion to the pieces' sample counts (xs is free between scatter_x and the gradient gather);
       // the assignment wants the sample count of piece l in lane l
       int ns_by_piece = t.ns;
@@ -448,9 +418,6 @@ struct DevBackend {
         for (int d = 0; d < DL; ++d) gC[k][d] = (Num)gCr[k][d];
       gT = (Num)gTr;
     }
-#ifdef NEO_STAMPS
-    const long long s2 = wall_clock64();
-#endif
     costs[0] = uniform(energy);
     costs[1] = uniform(tsum);
     costs[2] = uniform(cf);
@@ -474,13 +441,6 @@ struct DevBackend {
 #pragma unroll
     for (int k = 0; k < NS; ++k) g.v[k] = in_range(k, lg) ? xn[k * kWave + lg] : Num(0);
     NEO_MARK("gather_done");
-#ifdef NEO_STAMPS
-    const long long s3 = wall_clock64();
-    tk[0] += s1 - s0;
-    tk[1] += s2 - s1;
-    tk[2] += s3 - s2;
-    tk[3] += 1;
-#endif
     return 0;
   }
 };
@@ -730,9 +690,6 @@ __global__ __launch_bounds__(kWave, (WAVES == 2 ? (sizeof(Num) == 4 && NS <= 2 ?
   for (int k = 0; k < NS; ++k) xv.v[k] = (k * kWave + lane < n) ? x0[(size_t)b * n + k * kWave + lane] : 0.0;
   LbfgsOpts o{prm.ftol, prm.gtol, prm.maxls, prm.maxiter, prm.maxfun, NEO_LBFGS_M};
   LbfgsResult res;
-#ifdef NEO_STAMPS
-  const long long k0 = wall_clock64();
-#endif
   // n <= 128: the run as "evaluate, then advance" (neo_lbfgs_sm.hpp: the same arithmetic and decisions as
   // lbfgs_minimize) -- ONE inlined copy of the evaluation instead of two: 36 % less code and no spills in the cfg2
   // two-waves kernel.  Four FLAT slots (n > 128, cfg5): the compiler keeps the machine's vectors in private memory
@@ -779,15 +736,6 @@ __global__ __launch_bounds__(kWave, (WAVES == 2 ? (sizeof(Num) == 4 && NS <= 2 ?
   } else {
     lbfgs_minimize<BE>(be, xv, o, res);
   }
-#ifdef NEO_STAMPS
-  if (lane == 0 && nsamples) {  // the counter buffer is [B][8] in this build
-    long long *o8 = nsamples + (size_t)b * 8;
-    o8[1] = be.tk[3]; o8[2] = be.tk[0]; o8[3] = be.tk[1]; o8[4] = be.tk[2];
-    o8[5] = wall_clock64() - k0; o8[6] = k0; o8[7] = be.tl;  // (7: two-loop time; was the dispatch slot)
-    o8[0] = be.samples;
-  }
-  nsamples = nullptr;
-#endif
 #pragma unroll
   for (int k = 0; k < NS; ++k)
     if (k * kWave + lane < n) x[(size_t)b * n + k * kWave + lane] = xv.v[k];

@@ -16,9 +16,6 @@
 // every round is "evaluate, then advance" for all of them.
 #pragma once
 #include "neo_lbfgs.hpp"
-#ifndef NEO_SM_STAMP  // timing experiments only (NEO_STAMPS builds of the device kernels define it)
-#define NEO_SM_STAMP(i)
-#endif
 #ifndef NEO_MARK
 #define NEO_MARK(name)
 #endif
@@ -111,10 +108,8 @@ struct LbfgsMachine {
     while (next != DO_RETURN) {
       if (next == DO_START_ITER) {
         // ---- search direction
-        NEO_SM_STAMP(0);
         NEO_MARK("dir_begin");
         lbfgs_direction(be, g, d, tmp, tmp2, col, head, o.m, theta);
-        NEO_SM_STAMP(1);
         NEO_MARK("dir_end");
         // ---- line search set-up (lnsrlb)
         be.copy(t, x);

@@ -32,7 +32,8 @@ def _hipcc():
 
 
 def _flags():
-    # NEO_BUILD_DEFS="-DNEO_STAMPS ..." : experiment builds only (tools/); the product is built without
+    # NEO_BUILD_DEFS="-DNEO_X_OCC=2 ..." : experiment builds only (tools/); the product is built without.  The experiment
+    # switches of earlier rounds (phase stamps, the slim build, ...) are patches under tools/probe/, applied before such a build
     # -fno-slp-vectorize: packed fp32 operations (v_pk_*) want aligned register pairs; in these register-bound kernels
     # they cost moves and spills (8 v_mov per joint of the factor recurrence).  Measured on the MI355X with and without:
     # cfg2 all-fp32 943 k -> 995 k traj/s, cfg3 12.5 M -> 15.2 M, cfg4 888 k -> 945 k, cfg5 244 k -> 259 k; the

@@ -112,8 +112,8 @@ CASES = [
     case("f32x-M34", k3(3, "float", 2, WL, "float"), "f32x", 34),
     case("f32x-M41", k3(3, "float", 2, WL, "float"), "f32x", 41),
     case("f32x-M64", k3(4, "float", 2, WL, "float"), "f32x", 64),
-    # (NEO_FLAG_ONE_WAVE_PER_SIMD: the one-wave all-fp32 kernel is compiled only into experiment builds (NEO_X_ONE_WAVE);
-    #  the product's dispatch keeps the two-waves kernel -- this row pins that the flag changes nothing else)
+    # (NEO_FLAG_ONE_WAVE_PER_SIMD: the one-wave all-fp32 kernel is an experiment, tools/probe/x_one_wave.patch, and in no
+    #  product source; the product's dispatch keeps the two-waves kernel -- this row pins that the flag changes nothing else)
     case("f32x-M21-one-wave-flag", k3(2, "float", 2, PD3, "float"), "f32x", 21, waves=1),
     # ---- fp16 field (cfg5's store; M = 41 is cfg5's shape)
     case("f16-f64-M21", k3(2, "double", 1, PD3, elem="__half"), "f64", 21, store="f16"),

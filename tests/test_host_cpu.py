@@ -178,3 +178,12 @@ def test_trace_parity_cases_reach_the_kernels_they_name():
         ran = {re.sub(r"^void ", "", row["Name"].split("(")[0]).replace("neo::", "")
                for row in csv.DictReader(f) if "optimize_kernel<" in row["Name"]}
     assert ran == named, (sorted(ran - named), sorted(named - ran))
+
+
+def test_experiment_switch_patches_apply():
+    """the experiment switches live outside csrc/, as patches under tools/probe/: each still applies to the sources"""
+    import subprocess
+    for name in ("stamps", "slim_build", "x_one_wave", "f64_scalars", "lds_dma_gather"):
+        patch = os.path.join(REPO, "tools", "probe", name + ".patch")
+        r = subprocess.run(["git", "apply", "--check", patch], cwd=REPO, capture_output=True, text=True)
+        assert r.returncode == 0, (name, r.stderr)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Host-only refactors must leave the device code alone: disassembles every gfx950 code object of two builds of
 libneo_planner_hip.so (llvm-objdump -d on the entries of the library's offload bundles; no GPU needed) and compares
-the instructions symbol by symbol.
+the instructions symbol by symbol: mnemonics, operands and encodings.  The address a listing line carries is left out --
+where a kernel sits in its code object follows the order in which the unit instantiates its templates, and branch targets
+are printed relative to their symbol; so is the padding behind the last kernel of a code object.
 
     python tools/compare_device_code.py old.so [new.so]      (default new = the in-tree build)
 """
@@ -42,7 +44,10 @@ def kernels(lib):
                     assert cur not in syms, cur
                     syms[cur] = []
                 elif cur:
-                    syms[cur].append(line)
+                    syms[cur].append(re.sub(r"// [0-9A-F]{12}: ", "// ", line))
+    for lines in syms.values():  # (the zero padding objdump prints as "..." behind a code object's last kernel)
+        while lines and lines[-1].strip() in ("", "..."):
+            lines.pop()
     return syms
 
 

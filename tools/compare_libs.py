@@ -48,6 +48,7 @@ def child(out):
         o = bp.optimize(m2, bp.pack_x(w, ts), h, t)
         res[f"map2d_{dt}_x"] = o["x"]; res[f"map2d_{dt}_nfev"] = o["nfev"]
     host_forms(res, g3, g16, m2)
+    field_kinds(res)
     np.savez(out, **res)
 
 
@@ -117,6 +118,36 @@ def host_forms(res, g3, g16, m2):
     d = np.empty(5000)
     ctx.check(ctx.lib.neo_esdf_query(ctx.h, m2.scene_id, 5000, p(np.ascontiguousarray(pts2)), p(d), None))
     res["host_query2_nograd_d"] = d
+
+def field_kinds(res):
+    """the dispatch on a 3-D field's layout and element type: every (layout, store) through evaluation, ESDF lookup, audit
+    and the optimiser in each arithmetic mode and register allocation; lane groups and budgeted launches where they exist"""
+    import numpy as np
+    import neo_planner_amd as npa
+    from neo_planner_amd import _lib, synth
+    occ = synth.occupancy_3d(2, n=96, res=30.0 / 96, canopy=24)
+    h, t, w, ts = synth.replan_requests(13, 192, 5, D=3, length_range=(8.0, 14.0), **synth.VOLUME)
+    for layout in ("linear", "yz4", "cell8", "brick"):
+        for store in ("f32", "f16"):
+            ctx = _lib.Context(0)
+            g = npa.ESDF3D.from_occupancy(occ, 30.0 / 96, synth.DOMAIN_ORIGIN, store=store, layout=layout, ctx=ctx)
+            tag = f"kind_{layout}_{store}"
+            for dt in ("f64", "f32", "f32x"):
+                bp = npa.BatchPlanner(ctx=ctx, sample_dtype=dt)
+                x0 = bp.pack_x(w, ts)
+                e = bp.cost_grad(g, x0, h, t, want_coeffs=True)
+                res[f"{tag}_{dt}_eval_cost"] = e["cost"]; res[f"{tag}_{dt}_eval_grad"] = e["grad"]
+                res[f"{tag}_{dt}_sample_gC"] = bp.sampled_terms(g, e["coeffs"], ts)["grad_C"]
+                for wv in (1, 2):
+                    o = npa.BatchPlanner(ctx=ctx, sample_dtype=dt, waves_per_simd=wv).optimize(g, x0, h, t)
+                    res[f"{tag}_{dt}_w{wv}_x"] = o["x"]; res[f"{tag}_{dt}_w{wv}_nfev"] = o["nfev"]
+            res[f"{tag}_audit"] = np.column_stack([np.asarray(v, np.float64) for v in bp.audit(g, o["x"], h, t).values()])
+            if layout != "cell8":
+                res[f"{tag}_group_x"] = npa.BatchPlanner(ctx=ctx, sample_dtype="f32", lane_groups=True).optimize(g, x0, h, t)["x"]
+            if store == "f32" and layout in ("linear", "brick"):
+                for dt in ("f64", "f32", "f32x"):
+                    o = npa.BatchPlanner(ctx=ctx, sample_dtype=dt).optimize_budgeted(g, x0, h, t, 24)
+                    res[f"{tag}_{dt}_budget_x"] = o["x"]; res[f"{tag}_{dt}_budget_nfev"] = o["nfev"]
 
 
 def main():

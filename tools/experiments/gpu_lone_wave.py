@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Latency of the all-fp32 optimiser kernel when wavefronts have SIMDs to themselves: cfg2 batch 0 in launches of 4096 and of
 256 trajectories, default allocation (three wavefronts per SIMD, one sample a lane in flight) against NEO_FLAG_ONE_WAVE_PER_SIMD
-(experiment library built with -DNEO_X_ONE_WAVE: 512 registers, four samples in flight).  Prints ms per launch, the longest
+(experiment library: `git apply tools/probe/x_one_wave.patch`, built with -DNEO_X_ONE_WAVE: 512 registers, four samples in flight).  Prints ms per launch, the longest
 run's evaluations and microseconds per evaluation of that run; checks that both give the same bits."""
 import ctypes, os, sys, time
 os.environ.setdefault("OMP_NUM_THREADS", "1")

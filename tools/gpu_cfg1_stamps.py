@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Phase times of ONE plan() of the reference's shape (M = 3, D = 2, 300 x 300 nearest-cell map, fp64) -- a wavefront
-alone on the chip.  Needs a library built with NEO_BUILD_DEFS=-DNEO_STAMPS (NEO_PLANNER_LIB=...)."""
+alone on the chip.  Needs a library built with the phase stamps: `git apply tools/probe/stamps.patch`, then
+NEO_BUILD_DEFS=-DNEO_STAMPS (NEO_PLANNER_LIB=...)."""
 import ctypes, os, sys
 os.environ.setdefault("OMP_NUM_THREADS", "1")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

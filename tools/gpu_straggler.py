@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Where do the longest runs of optimize_kernel spend their time?  Needs a library built with
-NEO_BUILD_DEFS=-DNEO_STAMPS (the sample-counter buffer then carries 8 values per trajectory)."""
+"""Where do the longest runs of optimize_kernel spend their time?  Needs a library built with the phase stamps:
+`git apply tools/probe/stamps.patch`, then NEO_BUILD_DEFS=-DNEO_STAMPS (the sample-counter buffer then carries 8 values per
+trajectory)."""
 import ctypes, os, sys
 os.environ.setdefault("OMP_NUM_THREADS", "1")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,7 +1,8 @@
 #!/bin/bash
 # register / scratch footprint of the kernels of one translation unit:
 #   tools/probe/kstats.sh [unit.hip ...] [-Dflags]       default unit: neo_disp_opt3d_w2.hip (the two-waves optimiser)
-# -DNEO_SLIM_BUILD keeps only the cfg2 instantiation (linear fp32 field) of the optimiser units.
+# -DNEO_SLIM_BUILD keeps only the cfg2 instantiation (linear fp32 field) of the optimiser units; the switch is not in the
+# product sources: `git apply tools/probe/slim_build.patch` first.
 cd "$(dirname "$0")/../../neo-planner_amd/csrc" || exit 1
 mkdir -p /tmp/isa
 units=(); flags=()

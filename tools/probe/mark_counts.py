@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static instruction counts of optimize_kernel between the NEO_MARK position markers (build with -DNEO_MARKS -S):
+"""Static instruction counts of optimize_kernel between the NEO_MARK position markers (build with -DNEO_MARKS -S, after
+`git apply tools/probe/slim_build.patch`: NEO_SLIM_BUILD is not in the product sources):
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -I include --cuda-device-only -DNEO_MARKS \
           -DNEO_SLIM_BUILD -S neo-planner_amd/csrc/neo_disp_opt3d_x.hip -o /tmp/marks.s

@@ -7,7 +7,7 @@
 // Here
 //   * 64 * WPT lanes share the samples of one trajectory: 13 rounds become 5 (WPT = 2) or 3 (WPT = 4);
 //   * every lane puts the gathers of up to PF rounds in flight at once as LDS-DMA (`buffer_load_dwordx4 ... offen lds`,
-//     Lookup3D::load_async): the 32 bytes of a lookup land in LDS without a destination register, so the number in
+//     Lookup3D::load_async, tools/probe/lds_dma_gather.patch): the 32 bytes of a lookup land in LDS without a destination register, so the number in
 //     flight is set by the landing room (2 KB per wavefront and round), not by spare VGPRs -- the register-staged form
 //     spilled from two rounds on ("more samples in flight");
 //   * the per-piece sums go through LDS rows as in minco_sample, across the wavefronts of the workgroup (one barrier).
@@ -22,7 +22,8 @@
 // four 38.9 / 482, six 39.6 / 460, two wavefronts per trajectory 35.7-36.6 / 467-484, four 43.8 / 635.  The kernel is
 // bound by instruction issue, not by the latency of its gathers; the product's answer is fewer idle lane-rounds
 // (csrc/neo_sample_chunk.hpp).  Kept here, outside the library, as the experiment it was: a library built with
-// -DNEO_SAMPLE_EXPERIMENTS dispatches to it when NEO_SAMPLE_VARIANT is set.
+// -DNEO_SAMPLE_EXPERIMENTS dispatches to it when NEO_SAMPLE_VARIANT is set.  Lookup3D::load_async / read_staged are no
+// longer in csrc/neo_device.hpp: `git apply tools/probe/lds_dma_gather.patch` first.
 #pragma once
 #include "../../neo-planner_amd/csrc/neo_kernels.hpp"
 
