@@ -377,6 +377,84 @@ int neo_geo_prune_batch(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, in
 /* the byte budget the geo workspace is sized from (takes effect at the next reallocation) */
 int neo_geo_workspace_budget(neo_ctx *ctx, size_t bytes);
 
+/* ---- fleet replan loop (ros_node/traj_planner_node.py:390-578) ----------------
+ * What the reference's node does for one mission between two plans, for B missions in lock step.  2-D reference map,
+ * D = 2, fp64.  Fleet state, caller-owned DEVICE buffers indexed by MISSION:
+ *   cmd[B][cap][3][2]   the command arrays des_state_array (:518, :577): position, velocity, acceleration rows in the
+ *                       layout of neo_eval_traj_batch's state;
+ *   cmd_len[B]          des_state_length; cmd_index[B] des_state_index (the row being flown); future_index[B] (:531);
+ *   flags[B]            NEO_FLEET_FLAG_* below, OR-ed in by the kernels (the caller zeroes them once).
+ * Every call takes an optional DEVICE array `subset` of n_subset mission indices: only these are launched, NULL = all
+ * B.  Arrays are always indexed by mission, never by position; an index outside 0 .. B - 1 is skipped (the convention
+ * of neo_optimize_batch_budget_dev); a mission may appear in a subset once.  scene_id / scene_ids as in
+ * neo_optimize_batch (host form) / neo_optimize_batch_dev (_dev: a device array of map-table slots, one per mission).
+ * A mission's results depend on neither B, the subset nor the launch: no floating-point atomics, fixed summation order.
+ * Errors, before anything is launched, with a neo_last_error message: a NULL required buffer, B < 0, a bad subset size,
+ * cap <= 0, stride <= 0, step or ahead outside 0 .. 2^30, a rate or step length that is not finite and > 0, a 3-D map:
+ * NEO_ERR_INVALID; a scene without a map: NEO_ERR_NO_MAP. */
+#define NEO_FLEET_FLAG_TARGET_CAPPED 1  /* the lateral walk of the target ran into its bound: not the reference's target */
+#define NEO_FLEET_FLAG_CMD_FULL 2       /* a spliced trajectory did not fit cmd: its rows from `cap` on were dropped */
+#define NEO_FLEET_FLAG_BAD_SCENE 4      /* _dev: the mission's map-table slot is outside the table; its target is NaN */
+#define NEO_FLEET_FLAG_SPLICE_FAILED 8  /* the trajectory to splice could not be solved (exp(-tau) overflow): cmd untouched */
+#define NEO_FLEET_FLAG_ABANDONED 16     /* set by the host loop (neo_planner_amd.FleetReplanLoop): all targets of a tick failed */
+/* set_local_target (:450-488), one lane per mission.  cur_pos[B][2], goal[B][2]; jitter[B][2] is added to the first
+ * candidate (:469): zeros for the first target of a tick, the caller's N(0, 1) draws for the re-targeted ones -- the
+ * kernel draws nothing.  move_vel = 0.8 v_max (:87).
+ *   tail[B][3][2]     target position, velocity (move_vel towards the goal, :480-481), zero acceleration;
+ *   near_goal[B]      1 where |goal - cur_pos| < longitu_step_dis: the target is the goal with zero velocity (:456-459);
+ *   lateral_steps[B]  steps of the alternating, growing lateral walk (:474-477) out of has_collision -- the map's
+ *                     nearest-cell distance in the arithmetic of neo_esdf_query < 0.5, 10000 outside the map, which is
+ *                     what ends a walk.  The reference's loop has no bound; here a walk takes at most
+ *                     ceil(2 L / lateral_step_length) + 2 steps, L the map's diagonal extent (it cannot take that many:
+ *                     after k steps the candidate is ceil(k / 2) step lengths from the first one, and both must lie
+ *                     inside the map for the walk to go on), and never more than 2^20: NEO_FLEET_FLAG_TARGET_CAPPED.
+ * A target that falls on the goal has the reference's 0 / 0 velocity: NaN. */
+int neo_fleet_target_batch(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset,
+                           int n_subset, const double *cur_pos, const double *goal, const double *jitter,
+                           double longitu_step_dis, double lateral_step_length, double move_vel, double *tail,
+                           int32_t *near_goal, int32_t *lateral_steps, int32_t *flags);
+/* the same with DEVICE pointers, asynchronous on the context's stream.  (The host form above copies the output arrays
+ * up first, so the rows of missions outside the subset come back as they were.) */
+int neo_fleet_target_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset,
+                               int n_subset, const double *cur_pos, const double *goal, const double *jitter,
+                               double longitu_step_dis, double lateral_step_length, double move_vel, double *tail,
+                               int32_t *near_goal, int32_t *lateral_steps, int32_t *flags);
+/* perfect tracking for one replan period, then get_drone_state_ahead (:527-537), one lane per mission:
+ *   cmd_index = min(cmd_index + step, cmd_len - 1);  cur_pos[B][2] = position of row cmd_index;
+ *   future_index = min(ahead + cmd_index, cmd_len - 1);  head[B][3][2] = position and velocity of row future_index, zero
+ *   acceleration (the reference hands plan() a 2 x 2 state).
+ * step = commands per replan period, ahead = int(planning_time_ahead * cmd_hz), both computed by the caller.  A mission
+ * with cmd_len < 1 is left untouched.  Device pointers only: the point is the resident array. */
+int neo_fleet_advance_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                          const int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index, int step, int ahead,
+                          double *cur_pos, double *head);
+/* the splice of replan (:574-578), one wavefront per mission, for the launched missions with solved[b] != 0 (solved: a
+ * device array [B], NULL = all launched): the trajectory x[B][n], head[B][3][2], tail[B][3][2] of M pieces is solved as
+ * neo_eval_traj_batch solves it and its rows k < count = len(np.arange(0, sum(T), 1 / hz)) -- the rows of
+ * neo_eval_traj_batch at the same hz, bit for bit -- are written to cmd[b][future_index[b] + k]; cmd_len[b] =
+ * future_index[b] + count; rows before future_index[b] stay.  first != 0 splices at 0 and zeroes cmd_index and
+ * future_index (first_plan, :515-519).  Rows from `cap` on are dropped, cmd_len = cap, and NEO_FLEET_FLAG_CMD_FULL is
+ * raised: nothing is written past the buffer.  Device pointers only. */
+int neo_fleet_splice_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, const double *x,
+                         const double *head, const double *tail, const int32_t *solved, double hz, int first,
+                         double *cmd, int cap, int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index,
+                         int32_t *flags);
+/* get_weighted_metric (:333-363) over what was FLOWN, one wavefront per mission: the samples are rows 0, stride,
+ * 2 stride, ... < n_flown[b] of cmd[b] (stride = cmd_hz * metric_eva_interval: 6 at the reference's 60 Hz and 0.1 s;
+ * n_flown = the final cmd_index + 1, or cmd_len for a mission flown to its end; values outside 0 .. cap are clamped).
+ * The record is neo_audit_traj_batch's: audit[B][NEO_AUDIT_FIELDS], count[B] (samples), flags[B] (NEO_AUDIT_FLAG_*, not
+ * OR-ed: written), with d_k the nearest-cell lookup of the row's position; sample j has the time (j * stride) / cmd_hz,
+ * DURATION = n_flown / cmd_hz, and a row that is not finite gives the NaN record of NEO_AUDIT_FLAG_NONFINITE.
+ * NEO_AUDIT_FLAG_METRIC_FAIL is the reference's "planning is considered failed" (:359-361).  v_max, safe_dis and
+ * collision_cost_tol come from neo_params; weights3 as in neo_audit_traj_batch.  Same bits whatever the subset, its
+ * order and the launch.  The host form takes cmd, n_flown and the outputs as HOST arrays (a flight recorded elsewhere). */
+int neo_fleet_audit_batch(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset,
+                          int n_subset, const double *cmd, int cap, const int32_t *n_flown, int stride, double cmd_hz,
+                          const double *weights3, double *audit, int32_t *count, int32_t *flags);
+int neo_fleet_audit_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset,
+                              int n_subset, const double *cmd, int cap, const int32_t *n_flown, int stride,
+                              double cmd_hz, const double *weights3, double *audit, int32_t *count, int32_t *flags);
+
 /* ---- timing of the device work (bench.py) ----------------------------------
  * When enabled, every kernel launch of the named family is bracketed by HIP events on
  * the context stream; neo_profile_read returns launches and summed milliseconds. */

@@ -1847,6 +1847,208 @@ int neo_audit_traj_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int
   return st.download();
 }
 
+// ---- fleet replan loop (ros_node/traj_planner_node.py:390-578; kernels: neo_fleet.hpp)
+static int fleet_check(neo_ctx *c, int B, const int32_t *subset, int n_subset) {
+  if (!c) return NEO_ERR_INVALID;
+  if (B < 0) return fail_locked(c, NEO_ERR_INVALID, "fleet: B must be >= 0");
+  if (subset && (n_subset < 0 || n_subset > B)) return fail_locked(c, NEO_ERR_INVALID, "fleet: bad subset size");
+  return NEO_OK;
+}
+static bool fleet_positive(double v) { return std::isfinite(v) && v > 0.0; }
+
+// the 2-D maps of a fleet call (context locked): FleetArgs' table, slots and nmaps
+static int fleet_maps(neo_ctx *c, int scene_id, const int32_t *slots, FleetArgs &f) {
+  int rc = rebuild_tables(c);
+  if (rc) return rc;
+  CallMaps cm;
+  rc = resolve_call_maps(c, scene_id, slots != nullptr, cm);
+  if (rc) return rc;
+  if (cm.kind != 0) return fail(c, NEO_ERR_INVALID, "fleet: the 2-D reference map only (a 3-D map was given)");
+  f.table = cm.table;
+  f.slots = slots;
+  f.nmaps = cm.nmaps;
+  return NEO_OK;
+}
+
+static int fleet_target_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cur_pos,
+                              const double *goal, const double *jitter, double longitu, double lateral, double move_vel,
+                              const double *tail, const int32_t *near_goal, const int32_t *lateral_steps,
+                              const int32_t *flags) {
+  int rc = fleet_check(c, B, subset, n_subset);
+  if (rc) return rc;
+  if (!cur_pos || !goal || !jitter || !tail || !near_goal || !lateral_steps || !flags)
+    return fail_locked(c, NEO_ERR_INVALID, "fleet target: null buffer");
+  if (!fleet_positive(longitu) || !fleet_positive(lateral) || !std::isfinite(move_vel))
+    return fail_locked(c, NEO_ERR_INVALID, "fleet target: longitu_step_dis and lateral_step_length must be finite and > 0, "
+                                           "move_vel finite");
+  return NEO_OK;
+}
+
+int neo_fleet_target_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset,
+                               int n_subset, const double *cur_pos, const double *goal, const double *jitter,
+                               double longitu_step_dis, double lateral_step_length, double move_vel, double *tail,
+                               int32_t *near_goal, int32_t *lateral_steps, int32_t *flags) {
+  int rc = fleet_target_check(c, B, subset, n_subset, cur_pos, goal, jitter, longitu_step_dis, lateral_step_length,
+                              move_vel, tail, near_goal, lateral_steps, flags);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  FleetArgs f{B, subset, n_subset};
+  rc = fleet_maps(c, scene_id, scene_ids, f);
+  if (rc) return rc;
+  if (f.launched() == 0) return NEO_OK;
+  rc = fleet_target(c, f, {cur_pos, goal, jitter, longitu_step_dis, lateral_step_length, move_vel, tail, near_goal,
+                           lateral_steps, flags});
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+int neo_fleet_target_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset, int n_subset,
+                           const double *cur_pos, const double *goal, const double *jitter, double longitu_step_dis,
+                           double lateral_step_length, double move_vel, double *tail, int32_t *near_goal,
+                           int32_t *lateral_steps, int32_t *flags) {
+  int rc = fleet_target_check(c, B, subset, n_subset, cur_pos, goal, jitter, longitu_step_dis, lateral_step_length,
+                              move_vel, tail, near_goal, lateral_steps, flags);
+  if (rc) return rc;
+  if (B == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  const size_t bs = (size_t)B;
+  std::vector<int> slots;
+  if (scene_ids) {
+    rc = scene_slots(c, scene_ids, bs, false, slots);
+    if (rc) return rc;
+  }
+  // all arrays small: the pinned mirror.  The outputs go up too: missions outside the subset keep their rows
+  HostStage st(c, kStagedUpTo);
+  const auto fp = st.in(cur_pos, bs * 2), fg = st.in(goal, bs * 2), fj = st.in(jitter, bs * 2);
+  const auto fs = st.in(scene_ids ? slots.data() : nullptr, bs);
+  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
+  const auto ft = st.inout(tail, bs * 6);
+  const auto fn = st.inout(near_goal, bs), fl = st.inout(lateral_steps, bs), ff = st.inout(flags, bs);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_fleet_target_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fs) : nullptr, B,
+                                  subset ? st.dev(fsub) : nullptr, n_subset, st.dev(fp), st.dev(fg), st.dev(fj),
+                                  longitu_step_dis, lateral_step_length, move_vel, st.dev(ft), st.dev(fn), st.dev(fl),
+                                  st.dev(ff));
+  if (rc) return rc;
+  return st.download();
+}
+
+static int fleet_cmd_check(neo_ctx *c, const char *who, const double *cmd, int cap, const int32_t *cmd_len,
+                           const int32_t *cmd_index, const int32_t *future_index) {
+  if (!cmd || !cmd_len || !cmd_index || !future_index)
+    return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": null buffer").c_str());
+  if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": cap must be > 0").c_str());
+  return NEO_OK;
+}
+
+int neo_fleet_advance_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                          const int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index, int step, int ahead,
+                          double *cur_pos, double *head) {
+  int rc = fleet_check(c, B, subset, n_subset);
+  if (rc) return rc;
+  rc = fleet_cmd_check(c, "fleet advance", cmd, cap, cmd_len, cmd_index, future_index);
+  if (rc) return rc;
+  if (!cur_pos || !head) return fail_locked(c, NEO_ERR_INVALID, "fleet advance: null buffer");
+  if (step < 0 || step > (1 << 30) || ahead < 0 || ahead > (1 << 30))
+    return fail_locked(c, NEO_ERR_INVALID, "fleet advance: step and ahead must be in 0 .. 2^30");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const FleetArgs f{B, subset, n_subset};
+  if (f.launched() == 0) return NEO_OK;
+  rc = fleet_advance(c, f, {const_cast<double *>(cmd), cap, const_cast<int32_t *>(cmd_len), cmd_index, future_index}, step,
+                     ahead, cur_pos, head);
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+int neo_fleet_splice_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, const double *x, const double *head,
+                         const double *tail, const int32_t *solved, double hz, int first, double *cmd, int cap,
+                         int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index, int32_t *flags) {
+  int rc = fleet_check(c, B, subset, n_subset);
+  if (rc) return rc;
+  rc = check_shape(c, B, M, 2);
+  if (rc) return rc;
+  rc = fleet_cmd_check(c, "fleet splice", cmd, cap, cmd_len, cmd_index, future_index);
+  if (rc) return rc;
+  if (!x || !head || !tail || !flags) return fail_locked(c, NEO_ERR_INVALID, "fleet splice: null buffer");
+  if (!fleet_positive(hz)) return fail_locked(c, NEO_ERR_INVALID, "fleet splice: hz must be finite and > 0");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const FleetArgs f{B, subset, n_subset};
+  if (f.launched() == 0) return NEO_OK;
+  rc = fleet_splice(c, f, {cmd, cap, cmd_len, cmd_index, future_index}, {M, x, head, tail, solved, hz, first ? 1 : 0, flags});
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+static int fleet_audit_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                             const int32_t *n_flown, int stride, double cmd_hz, const double *audit, const int32_t *count,
+                             const int32_t *flags) {
+  int rc = fleet_check(c, B, subset, n_subset);
+  if (rc) return rc;
+  if (!cmd || !n_flown || !audit || !count || !flags) return fail_locked(c, NEO_ERR_INVALID, "fleet audit: null buffer");
+  if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, "fleet audit: cap must be > 0");
+  if (stride <= 0) return fail_locked(c, NEO_ERR_INVALID, "fleet audit: stride must be > 0");
+  if (!fleet_positive(cmd_hz)) return fail_locked(c, NEO_ERR_INVALID, "fleet audit: cmd_hz must be finite and > 0");
+  return NEO_OK;
+}
+
+int neo_fleet_audit_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset, int n_subset,
+                              const double *cmd, int cap, const int32_t *n_flown, int stride, double cmd_hz,
+                              const double *weights3, double *audit, int32_t *count, int32_t *flags) {
+  int rc = fleet_audit_check(c, B, subset, n_subset, cmd, cap, n_flown, stride, cmd_hz, audit, count, flags);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  FleetArgs f{B, subset, n_subset};
+  rc = fleet_maps(c, scene_id, scene_ids, f);
+  if (rc) return rc;
+  if (f.launched() == 0) return NEO_OK;
+  FleetAuditArgs aa{cmd, cap, n_flown, stride, cmd_hz, {1.0, 1.0, 100.0}, audit, count, flags};
+  if (weights3)
+    for (int k = 0; k < 3; ++k) aa.w[k] = weights3[k];
+  rc = fleet_audit(c, f, aa);
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+int neo_fleet_audit_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset, int n_subset,
+                          const double *cmd, int cap, const int32_t *n_flown, int stride, double cmd_hz,
+                          const double *weights3, double *audit, int32_t *count, int32_t *flags) {
+  int rc = fleet_audit_check(c, B, subset, n_subset, cmd, cap, n_flown, stride, cmd_hz, audit, count, flags);
+  if (rc) return rc;
+  if (B == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  const size_t bs = (size_t)B;
+  std::vector<int> slots;
+  if (scene_ids) {
+    rc = scene_slots(c, scene_ids, bs, false, slots);
+    if (rc) return rc;
+  }
+  HostStage st(c, 0);
+  const auto fc = st.in(cmd, bs * cap * 6);
+  const auto fnf = st.in(n_flown, bs);
+  const auto fs = st.in(scene_ids ? slots.data() : nullptr, bs);
+  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
+  const auto fa = st.inout(audit, bs * NEO_AUDIT_FIELDS);  // (missions outside the subset keep their records)
+  const auto fcnt = st.inout(count, bs), ffl = st.inout(flags, bs);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_fleet_audit_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fs) : nullptr, B,
+                                 subset ? st.dev(fsub) : nullptr, n_subset, st.dev(fc), cap, st.dev(fnf), stride, cmd_hz,
+                                 weights3, st.dev(fa), st.dev(fcnt), st.dev(ffl));
+  if (rc) return rc;
+  return st.download();
+}
+
 // ---- geo warm start (traj_planner/astar_planner.py, geo_planner.py:19-101; kernels: neo_geo.hpp)
 static int geo_check(neo_ctx *c, int B, const double *start, const double *target, int max_expansions, int path_cap,
                      const double *key_pts, const double *path, const int32_t *path_len, const double *path_cost,

@@ -1,0 +1,342 @@
+// neo_fleet.hpp -- the glue of a fleet of closed-loop missions (include/neo_planner.h, neo_fleet_*): what
+// ros_node/traj_planner_node.py does per mission between two plans, for B missions whose command arrays stay in HBM.
+//
+//   fleet_target_kernel    set_local_target       (:450-488)   one lane per mission
+//   fleet_advance_kernel   perfect tracking + get_drone_state_ahead (:527-537)   one lane per mission
+//   fleet_splice_kernel    the splice of replan   (:574-578, first_plan :515-519)   one wavefront per mission
+//   fleet_audit_kernel     get_weighted_metric    (:333-363) over the flown rows   one wavefront per mission
+//
+// Included by neo_disp_fleet.hip only.  2-D reference map, D = 2, fp64.  No floating-point atomics, fixed summation
+// order: a mission's results depend on neither the batch, the subset nor the launch.  All arrays are indexed by mission;
+// workgroup / lane i works on mission subset[i] (i without a subset), an index outside 0 .. B - 1 is skipped.  A mission
+// is owned by one lane (target, advance) or one wavefront (splice, audit) of a launch, so its flags word is updated with
+// a plain read-modify-write.
+#pragma once
+#include "neo_audit.hpp"
+
+namespace neo {
+
+constexpr int kFleetThreads = 256;  // target / advance: missions per workgroup
+constexpr int kFleetD = 2;
+constexpr int kFleetRow = 3 * kFleetD;  // doubles of a command row: position, velocity, acceleration
+// most lateral steps the target walk is ever given, whatever the map and the step (see fleet_walk_bound)
+constexpr int kFleetWalkMax = 1 << 20;
+
+__device__ __forceinline__ int fleet_mission(int i, int n, const int *__restrict__ subset, int B) {
+  if (i >= n) return -1;
+  const int b = subset ? subset[i] : i;
+  return (b >= 0 && b < B) ? b : -1;
+}
+
+// Bound of set_local_target's lateral walk (the reference's `while self.map.has_collision(...)` has none).  After k
+// steps the candidate sits at p_0 + (-1)^(k+1) ceil(k / 2) s along the first lateral direction (steps of s, 2 s, 3 s, ...
+// with alternating sign), s = lateral_step_length.  has_collision is only true INSIDE the map (outside the lookup
+// answers 10000), so a walk that is still going has p_0 and p_k inside: ceil(k / 2) s = |p_k - p_0| <= L, the map's
+// diagonal extent, i.e. k <= 2 L / s.  The candidate after floor(2 L / s) + 1 steps is therefore outside or free, and
+// ceil(2 L / s) + 2 steps are never all taken; NEO_FLEET_FLAG_TARGET_CAPPED marks the walk that did (rounding of the
+// bound itself at worst), or that ran into kFleetWalkMax with a tiny s.
+__device__ __forceinline__ int fleet_walk_bound(const Map2D &m, double s) {
+  const double ex = (double)m.W * m.res, ey = (double)m.H * m.res;
+  const double k = ceil(2.0 * sqrt(ex * ex + ey * ey) / s) + 2.0;
+  return k < (double)kFleetWalkMax ? (int)k : kFleetWalkMax;  // (a NaN bound compares false: the hard cap)
+}
+
+__global__ __launch_bounds__(kFleetThreads) void fleet_target_kernel(
+    int B, int n, const int *__restrict__ subset, const Map2D *__restrict__ maps, const int *__restrict__ scene_slot,
+    int nmaps, const double *__restrict__ cur_pos, const double *__restrict__ goal, const double *__restrict__ jitter,
+    double longitu, double lateral, double move_vel, double *__restrict__ tail, int *__restrict__ near_goal,
+    int *__restrict__ lateral_steps, int *__restrict__ flags) {
+#pragma clang fp contract(off)  // every operation rounded on its own, as the reference's NumPy expressions are
+  const int b = fleet_mission(blockIdx.x * kFleetThreads + threadIdx.x, n, subset, B);
+  if (b < 0) return;
+  double *tl = tail + (size_t)b * kFleetRow;
+  tl[4] = tl[5] = 0.0;  // the target's acceleration row
+  const int slot = scene_slot ? scene_slot[b] : 0;
+  if (slot < 0 || slot >= nmaps) {
+    tl[0] = tl[1] = tl[2] = tl[3] = __builtin_nan("");
+    near_goal[b] = 0;
+    lateral_steps[b] = 0;
+    flags[b] |= NEO_FLEET_FLAG_BAD_SCENE;
+    return;
+  }
+  const Map2D map = maps[slot];
+  const double cx = cur_pos[(size_t)b * 2], cy = cur_pos[(size_t)b * 2 + 1];
+  const double gx = goal[(size_t)b * 2], gy = goal[(size_t)b * 2 + 1];
+  const double dx = gx - cx, dy = gy - cy;
+  const double dist = sqrt(dx * dx + dy * dy);
+  if (dist < longitu) {  // :456-459
+    tl[0] = gx;
+    tl[1] = gy;
+    tl[2] = tl[3] = 0.0;
+    near_goal[b] = 1;
+    lateral_steps[b] = 0;
+    return;
+  }
+  const double ax = dx / dist, ay = dy / dist;  // :461
+  // lateral_dir = [[ay, -ax], [-ay, ax]] (:462-463)
+  double p[2] = {cx + longitu * ax + jitter[(size_t)b * 2], cy + longitu * ay + jitter[(size_t)b * 2 + 1]};  // :469-472
+  const Lookup2D<double> lk(map);
+  const int bound = fleet_walk_bound(map, lateral);
+  int steps = 0, capped = 0;
+  double shift = lateral, sign = 1.0;
+  for (;;) {  // :474-477
+    double g[2];
+    bool inside;
+    const double d = lk.fetch<2>(p, g, inside);
+    if (!(d < 0.5)) break;  // has_collision (map_server/esdf.py:50-51)
+    if (steps >= bound) {
+      capped = 1;
+      break;
+    }
+    p[0] = p[0] + shift * (sign * ay);
+    p[1] = p[1] + shift * (-(sign * ax));
+    sign = -sign;
+    shift = shift + lateral;
+    ++steps;
+  }
+  const double tx = gx - p[0], ty = gy - p[1];
+  const double tn = sqrt(tx * tx + ty * ty);  // 0 for a target on the goal: 0 / 0 = NaN, as in the reference (:480)
+  tl[0] = p[0];
+  tl[1] = p[1];
+  tl[2] = move_vel * (tx / tn);
+  tl[3] = move_vel * (ty / tn);
+  near_goal[b] = 0;
+  lateral_steps[b] = steps;
+  if (capped) flags[b] |= NEO_FLEET_FLAG_TARGET_CAPPED;
+}
+
+__global__ __launch_bounds__(kFleetThreads) void fleet_advance_kernel(
+    int B, int n, const int *__restrict__ subset, const double *__restrict__ cmd, int cap,
+    const int *__restrict__ cmd_len, int *__restrict__ cmd_index, int *__restrict__ future_index, int step, int ahead,
+    double *__restrict__ cur_pos, double *__restrict__ head) {
+  const int b = fleet_mission(blockIdx.x * kFleetThreads + threadIdx.x, n, subset, B);
+  if (b < 0) return;
+  int len = cmd_len[b];
+  len = len > cap ? cap : len;
+  if (len < 1) return;  // nothing planned yet: nothing to fly along
+  const int last = len - 1;
+  // (sums of non-negative ints below 2^30 each, checked by the caller's wrapper: no overflow)
+  int idx = cmd_index[b];
+  idx = idx < 0 ? 0 : idx;
+  idx = idx > last - step ? last : idx + step;  // min(idx + step, len - 1)
+  const int fut = idx > last - ahead ? last : idx + ahead;  // :531-532
+  cmd_index[b] = idx;
+  future_index[b] = fut;
+  const double *row = cmd + ((size_t)b * cap + idx) * kFleetRow;
+  cur_pos[(size_t)b * 2] = row[0];
+  cur_pos[(size_t)b * 2 + 1] = row[1];
+  const double *fr = cmd + ((size_t)b * cap + fut) * kFleetRow;
+  double *hd = head + (size_t)b * kFleetRow;
+  hd[0] = fr[0];
+  hd[1] = fr[1];
+  hd[2] = fr[2];
+  hd[3] = fr[3];
+  hd[4] = hd[5] = 0.0;  // the reference hands plan() a 2 x 2 state (:534-535)
+}
+
+// The solve and the rows are traj_state_kernel's (neo_abi.hip) through audit_sample_state, its expressions written out
+// again in neo_audit.hpp: compiled with the units' -ffp-contract=on and no pragma here, they round as its rows do.
+__global__ __launch_bounds__(kWave) void fleet_splice_kernel(
+    int B, int n_launch, const int *__restrict__ subset, int M, DevParams prm, const double *__restrict__ x,
+    const double *__restrict__ head, const double *__restrict__ tail, const int *__restrict__ solved, double hz, int first,
+    double *__restrict__ cmd, int cap, int *__restrict__ cmd_len, int *__restrict__ cmd_index,
+    int *__restrict__ future_index, int *__restrict__ flags) {
+  constexpr int D = kFleetD;
+  __shared__ double xs[kSlots * kWave];
+  __shared__ double cs[kWave * 6 * D];
+  __shared__ double tcum[kWave + 1];
+  const int b = fleet_mission(blockIdx.x, n_launch, subset, B);  // wave-uniform
+  if (b < 0) return;
+  if (solved && !solved[b]) return;
+  const int lane = lane_id();
+  struct NoMap {};
+  struct NoLookup {
+    __device__ explicit NoLookup(const NoMap &) {}
+  };
+  DevParams p = prm;
+  NoMap nm;
+  DevBackend<D, kSlots, double, NoMap, NoLookup> be(p, nm);
+  be.xs = xs;
+  be.hist = nullptr;
+  be.m = NEO_LBFGS_M;
+  be.coeff_out = nullptr;
+  load_boundary(be.t, head + (size_t)b * 3 * D, tail + (size_t)b * 3 * D, M);
+  const int n = be.t.n;
+  typename DevBackend<D, kSlots, double, NoMap, NoLookup>::Vec xv;
+#pragma unroll
+  for (int k = 0; k < kSlots; ++k) xv.v[k] = (k * kWave + lane < n) ? x[(size_t)b * n + k * kWave + lane] : 0.0;
+  be.scatter_x(xv);
+  double e, ts;
+  // no trajectory to splice (exp(-tau) overflow, or below a duration that is not finite): the array stays as it is
+  auto refuse = [&]() {
+    if (lane == 0) flags[b] |= NEO_FLEET_FLAG_SPLICE_FAILED;
+  };
+  if (minco_forward<D>(be.t, p, e, ts) != 0) return refuse();
+  if (lane < M) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+#pragma unroll
+      for (int d = 0; d < D; ++d) cs[(lane * 6 + k) * D + d] = be.t.c[k][d];
+  }
+  if (lane == 0) tcum[0] = 0.0;
+  for (int pce = 0; pce < M; ++pce) {
+    const double Tp = rdlane(be.t.T, pce);
+    if (lane == 0) tcum[pce + 1] = tcum[pce] + Tp;
+  }
+  __syncthreads();
+  const double total = tcum[M];
+  const double step = 1.0 / hz;
+  const double cnt_d = ceil(total / step);  // len(np.arange(0, total, 1/hz))
+  if (!(cnt_d >= 0.0 && cnt_d <= (double)(1 << 30))) return refuse();
+  const int cnt = (int)cnt_d;
+  int at = first ? 0 : future_index[b];
+  at = at < 0 ? 0 : (at > cap ? cap : at);
+  const int room = cap - at;
+  const int wr = cnt < room ? cnt : room;  // rows beyond the buffer are dropped
+  double *out0 = cmd + ((size_t)b * cap + at) * kFleetRow;
+  for (int k = lane; k < wr; k += kWave) {
+    double tt = (double)k * step;
+    if (tt > total) tt = total;
+    int pc = 0;
+    while (pc < M - 1 && tcum[pc + 1] < tt) ++pc;
+    double pos[D], vel[D], acc[D];
+    audit_sample_state<D>(cs, pc, tt - tcum[pc], pos, vel, acc);
+    double *out = out0 + (size_t)k * kFleetRow;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      out[0 * D + d] = pos[d];
+      out[1 * D + d] = vel[d];
+      out[2 * D + d] = acc[d];
+    }
+  }
+  if (lane == 0) {
+    cmd_len[b] = at + wr;
+    if (first) cmd_index[b] = future_index[b] = 0;
+    if (cnt > room) flags[b] |= NEO_FLEET_FLAG_CMD_FULL;
+  }
+}
+
+// audit_kernel's accumulation (neo_audit.hpp) over GIVEN rows: sample j is row j * stride of the mission's command
+// array, j < count = ceil(n_flown / stride).  Per round a lane loads the rows of its kAuditU samples, then has their
+// kAuditU map gathers in flight before the first is consumed.
+__global__ __launch_bounds__(kWave) void fleet_audit_kernel(
+    int B, int n_launch, const int *__restrict__ subset, DevParams prm, const Map2D *__restrict__ maps,
+    const int *__restrict__ scene_slot, int nmaps, const double *__restrict__ cmd, int cap,
+    const int *__restrict__ n_flown, int stride, double hz, double w0, double w1, double w2, double *__restrict__ audit,
+    int *__restrict__ count, int *__restrict__ flags) {
+#pragma clang fp contract(off)  // the metric's own arithmetic rounds every operation as the reference's NumPy does
+  constexpr int D = kFleetD;
+  const int b = fleet_mission(blockIdx.x, n_launch, subset, B);  // wave-uniform
+  if (b < 0) return;
+  const int lane = lane_id();
+  double *rec = audit + (size_t)b * NEO_AUDIT_FIELDS;
+  auto reject = [&]() {
+    if (lane < NEO_AUDIT_FIELDS) rec[lane] = __builtin_nan("");
+    if (lane == 0) {
+      count[b] = 0;
+      flags[b] = NEO_AUDIT_FLAG_NONFINITE;
+    }
+  };
+  const int slot = scene_slot ? scene_slot[b] : 0;
+  if (slot < 0 || slot >= nmaps) return reject();
+  const Map2D map = maps[slot];
+  int nf = n_flown[b];
+  nf = nf < 0 ? 0 : (nf > cap ? cap : nf);
+  const int cnt = (nf + stride - 1) / stride;  // len(range(0, nf, stride)); (cnt - 1) * stride < cap: row indices fit
+  const double *rows = cmd + (size_t)b * cap * kFleetRow;
+
+  const Lookup2D<double> lk(map);
+  const double vmax2 = prm.v_max * prm.v_max, safe = prm.safe_dis;
+  double path = 0.0, feas = 0.0, coll = 0.0, speed_max = 0.0, acc_max = 0.0, dmin = __builtin_inf();
+  int kmin = INT_MAX, kunsafe = -1, outside = 0, bad = 0;
+  double carry[D];  // position of the sample before this sub-round's lane 0 (lane 63 of the one before)
+#pragma unroll
+  for (int d = 0; d < D; ++d) carry[d] = 0.0;
+  for (int base = 0; base < cnt; base += kAuditU * kWave) {
+    double st[kAuditU][kFleetRow];
+    bool on[kAuditU];
+#pragma unroll
+    for (int u = 0; u < kAuditU; ++u) {
+      const int k = base + u * kWave + lane;
+      on[u] = k < cnt;
+      const double *r = rows + (size_t)(on[u] ? k : 0) * stride * kFleetRow;  // idle slots read row 0 (cap >= 1)
+#pragma unroll
+      for (int q = 0; q < kFleetRow; ++q) st[u][q] = r[q];
+    }
+    Lookup2D<double>::Addr ad[kAuditU];
+    Lookup2D<double>::Raw rw[kAuditU];
+#pragma unroll
+    for (int u = 0; u < kAuditU; ++u) {
+      const double pos[D] = {st[u][0], st[u][1]};
+      ad[u] = lk.prepare<D>(pos, on[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < kAuditU; ++u) rw[u] = lk.load(ad[u]);
+#pragma unroll
+    for (int u = 0; u < kAuditU; ++u) {
+      const int k = base + u * kWave + lane;
+      const double pos[D] = {st[u][0], st[u][1]}, vel[D] = {st[u][2], st[u][3]}, acc[D] = {st[u][4], st[u][5]};
+      double prev[D];
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        prev[d] = from_prev(pos[d], carry[d]);
+        carry[d] = rdlane(pos[d], kWave - 1);
+      }
+      double gdrop[D];
+      const double dk = lk.finish<D>(ad[u], rw[u], gdrop);
+      if (on[u]) {
+#pragma unroll
+        for (int q = 0; q < kFleetRow; ++q)
+          if (!__builtin_isfinite(st[u][q])) bad = 1;
+        const double v2 = audit_norm2<D>(vel), a2 = audit_norm2<D>(acc);
+        const double speed = sqrt(v2), accn = sqrt(a2);
+        speed_max = speed > speed_max ? speed : speed_max;
+        acc_max = accn > acc_max ? accn : acc_max;
+        const double vv = v2 - vmax2;  // :346-348
+        if (vv > 0.0) feas += vv * vv * vv;
+        if (k >= 1) {  // :341-343
+          double dp[D];
+#pragma unroll
+          for (int d = 0; d < D; ++d) dp[d] = pos[d] - prev[d];
+          path += sqrt(audit_norm2<D>(dp));
+        }
+        const double vd = safe - dk;  // :351-355
+        if (vd > 0.0) {
+          coll += vd * vd * vd;
+          if (kunsafe < 0) kunsafe = k;
+        }
+        if (dk < dmin) {
+          dmin = dk;
+          kmin = k;
+        }
+        if (!ad[u].inside) outside = 1;
+      }
+    }
+  }
+  if (wave_max_nonneg(bad)) return reject();
+  double s_path, s_feas, s_coll, s_unused;
+  wave_sum4(path, feas, coll, 0.0, s_path, s_feas, s_coll, s_unused);
+  const double vmx = wave_max_nonneg(speed_max), amx = wave_max_nonneg(acc_max);
+  wave_min_first(dmin, kmin);
+  const int ukey = wave_max_nonneg(kunsafe >= 0 ? INT_MAX - kunsafe : 0);  // largest key = earliest unsafe sample
+  const int outs = wave_max_nonneg(outside);
+  if (lane == 0) {
+    auto t_of = [&](int k) { return (double)(k * stride) / hz; };  // the time of command row k * stride
+    const double weighted = w0 * s_path + w1 * s_feas + w2 * s_coll;  // np.dot(raw_cost, metric_weights) (:357)
+    rec[NEO_AUDIT_PATH_LENGTH] = s_path;
+    rec[NEO_AUDIT_FEASIBILITY] = s_feas;
+    rec[NEO_AUDIT_COLLISION] = s_coll;
+    rec[NEO_AUDIT_WEIGHTED] = weighted;
+    rec[NEO_AUDIT_MIN_CLEARANCE] = dmin;
+    rec[NEO_AUDIT_T_MIN_CLEARANCE] = cnt > 0 ? t_of(kmin) : -1.0;
+    rec[NEO_AUDIT_MAX_SPEED] = vmx;
+    rec[NEO_AUDIT_MAX_ACC] = amx;
+    rec[NEO_AUDIT_T_FIRST_UNSAFE] = ukey > 0 ? t_of(INT_MAX - ukey) : -1.0;
+    rec[NEO_AUDIT_DURATION] = (double)nf / hz;
+    count[b] = cnt;
+    flags[b] = (ukey > 0 ? NEO_AUDIT_FLAG_UNSAFE : 0) | (weighted > 10.0 * prm.coll_tol ? NEO_AUDIT_FLAG_METRIC_FAIL : 0) |
+               (outs ? NEO_AUDIT_FLAG_OUTSIDE_MAP : 0);
+  }
+}
+
+}  // namespace neo

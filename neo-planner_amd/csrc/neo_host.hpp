@@ -196,6 +196,51 @@ struct AuditArgs {
   int *count, *flags;
 };
 
+// neo_fleet_*_dev: one launch of a fleet kernel each (neo_disp_fleet.hip, kernels in neo_fleet.hpp).  Every array is
+// indexed by mission; `subset` (device, n_subset indices) picks the missions launched, NULL = all B.
+struct FleetArgs {
+  int B;
+  const int *subset;
+  int n_subset;
+  // target / audit: the 2-D map table (or the one map), as in AuditArgs
+  const void *table = nullptr;
+  const int *slots = nullptr;
+  int nmaps = 1;
+  int launched() const { return subset ? n_subset : B; }
+};
+struct FleetTargetArgs {
+  const double *cur_pos, *goal, *jitter;
+  double longitu, lateral, move_vel;
+  double *tail;
+  int *near_goal, *lateral_steps, *flags;
+};
+struct FleetCmd {  // the resident command arrays
+  double *cmd;
+  int cap;
+  int *cmd_len, *cmd_index, *future_index;
+};
+struct FleetSpliceArgs {
+  int M;
+  const double *x, *head, *tail;
+  const int *solved;
+  double hz;
+  int first;
+  int *flags;
+};
+struct FleetAuditArgs {
+  const double *cmd;
+  int cap;
+  const int *n_flown;
+  int stride;
+  double hz, w[3];
+  double *audit;
+  int *count, *flags;
+};
+int fleet_target(neo_ctx *c, const FleetArgs &f, const FleetTargetArgs &a);
+int fleet_advance(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, int step, int ahead, double *cur_pos, double *head);
+int fleet_splice(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const FleetSpliceArgs &a);
+int fleet_audit(neo_ctx *c, const FleetArgs &f, const FleetAuditArgs &a);
+
 // neo_geo_search_batch_dev / neo_geo_prune_batch (neo_disp_geo.hip); the context is locked and its tables rebuilt
 struct GeoArgs {
   int B;

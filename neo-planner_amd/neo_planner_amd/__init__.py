@@ -10,7 +10,8 @@ from ._lib import Context, NeoError, default_context  # noqa: F401
 from .esdf import ESDF, ESDF3D  # noqa: F401
 from .planner import BatchPlanner, MinJerkPlanner, PlannerConfig  # noqa: F401
 from .geo import GeoPlanner  # noqa: F401
+from .fleet import FleetReplanLoop  # noqa: F401
 # the initializer network (torch) is imported on demand: `from neo_planner_amd import initializer`
 
 __all__ = ["Context", "NeoError", "default_context", "ESDF", "ESDF3D", "BatchPlanner", "MinJerkPlanner",
-           "PlannerConfig", "GeoPlanner"]
+           "PlannerConfig", "GeoPlanner", "FleetReplanLoop"]

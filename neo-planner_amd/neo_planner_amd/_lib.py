@@ -28,6 +28,9 @@ NEO_AUDIT_FLAG_UNSAFE, NEO_AUDIT_FLAG_METRIC_FAIL, NEO_AUDIT_FLAG_OUTSIDE_MAP, N
 # neo_geo_search_batch: flag bits
 NEO_GEO_FLAG_NO_PATH, NEO_GEO_FLAG_START_OUTSIDE, NEO_GEO_FLAG_CAPPED, NEO_GEO_FLAG_PATH_TRUNCATED = 1, 2, 4, 8
 NEO_GEO_FLAG_BAD_SCENE = 16
+# neo_fleet_*: flag bits of a mission
+NEO_FLEET_FLAG_TARGET_CAPPED, NEO_FLEET_FLAG_CMD_FULL, NEO_FLEET_FLAG_BAD_SCENE, NEO_FLEET_FLAG_SPLICE_FAILED = 1, 2, 4, 8
+NEO_FLEET_FLAG_ABANDONED = 16
 
 # every symbol include/neo_planner.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -44,7 +47,8 @@ EXPORTS = [
     "neo_sampled_terms_batch_f32", "neo_sampled_terms_batch_f32_dev", "neo_effort_order_dev",
     "neo_optimize_progress_counter", "neo_effort_order_scratch_bytes", "neo_audit_traj_batch",
     "neo_audit_traj_batch_dev", "neo_geo_search_batch", "neo_geo_search_batch_dev", "neo_geo_prune_batch",
-    "neo_geo_workspace_budget",
+    "neo_geo_workspace_budget", "neo_fleet_target_batch", "neo_fleet_target_batch_dev", "neo_fleet_advance_dev",
+    "neo_fleet_splice_dev", "neo_fleet_audit_batch", "neo_fleet_audit_batch_dev",
 ]
 
 
@@ -112,6 +116,12 @@ def load():
     L.neo_geo_search_batch_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i] + [c_p] * 6
     L.neo_geo_prune_batch.argtypes = [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p]
     L.neo_geo_workspace_budget.argtypes = [c_p, ctypes.c_size_t]
+    L.neo_fleet_target_batch.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_d, c_d, c_d] + [c_p] * 4
+    L.neo_fleet_target_batch_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_d, c_d, c_d] + [c_p] * 4
+    L.neo_fleet_advance_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p]
+    L.neo_fleet_splice_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_d, c_i, c_p, c_i] + [c_p] * 4
+    L.neo_fleet_audit_batch.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_d] + [c_p] * 4
+    L.neo_fleet_audit_batch_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_d] + [c_p] * 4
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]

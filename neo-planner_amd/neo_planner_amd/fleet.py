@@ -1,0 +1,293 @@
+"""
+Fleet replan loop: B closed-loop missions in lock step (ros_node/traj_planner_node.py:390-578, `ReplanLoop` for a fleet).
+
+Every tick is one round of batched launches over the missions still planning:
+
+  advance   perfect tracking for one replan period + get_drone_state_ahead (:527-537)   neo_fleet_advance_dev
+  target    set_local_target (:450-488)                                                  neo_fleet_target_batch_dev
+  plan      BatchPlanner.plan / geo_plan on the active missions (warm_start_plan / geo_traj_plan)
+  splice    the new commands into the old array at the look-ahead index (:574-578)       neo_fleet_splice_dev
+
+and the missions whose plan failed go round again with a jittered target, up to the reference's 11 targets a tick
+(:429-445).  At the end neo_fleet_audit_batch_dev takes the reference's flight metric (:333-363) over what was flown.
+The command arrays (cmd_hz rows a second and mission) stay in HBM from the first plan to the audit; the small vectors
+(look-ahead state, target, x, statuses) pass through the host, as BatchPlanner.plan takes host arrays.
+
+A mission's flight does not depend on which other missions share the fleet: the kernels work per mission, the target
+jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
+retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream_ids`).
+"""
+import ctypes
+import time
+
+import numpy as np
+
+from . import _lib
+
+MAX_TARGETS = 11        # :429-445: seed 0 .. 10 are planned, the mission is abandoned after the plan of target 10 fails
+
+
+def target_jitter(seed, mission_ids, tick, target):
+    """(len(mission_ids), 2) N(0, 1) draws of set_local_target's re-targeting (:469): zeros for the first target of a tick,
+    mission i's own stream SeedSequence(seed, i, tick, target) for the others"""
+    ids = np.asarray(mission_ids).reshape(-1)
+    if target == 0:
+        return np.zeros((ids.shape[0], 2))
+    return np.stack([np.random.default_rng([int(seed), int(i), int(tick), int(target)]).normal(0.0, 1.0, 2) for i in ids]) \
+        if ids.shape[0] else np.zeros((0, 2))
+
+
+def plan_seed(seed, tick, target):
+    """the seed BatchPlanner.plan gets for the plans of (tick, target): its retries then draw from
+    SeedSequence(plan_seed, mission id, attempt)"""
+    return int(np.random.SeedSequence([int(seed), int(tick), int(target)]).generate_state(1, np.uint64)[0] >> np.uint64(2))
+
+
+class FleetReplanLoop:
+    """`ReplanLoop` for B missions at once.  goals (B, 2); `map` one 2-D ESDF for all missions, or any of the maps plus
+    scene_ids (B,) of per-mission scene ids (as BatchPlanner.optimize).  mode "basic" (BatchPlanner.plan) or "geo"
+    (geo_plan: the A* warm start).  mission_ids (B,): the ids the random streams are keyed by (None: 0 .. B - 1) -- a
+    mission flown alone with its id flies as it does in the fleet.  max_cmd_seconds sizes the resident command arrays
+    (cap = max_cmd_seconds * cmd_hz rows a mission); a mission whose array fills up ends as not reached."""
+
+    def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
+                 longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
+                 scene_ids=None, mission_ids=None, metric_eva_interval=0.1):
+        if mode not in ("basic", "geo"):
+            raise ValueError("FleetReplanLoop: mode must be 'basic' or 'geo'")
+        self.bp, self.map, self.mode = batch_planner, map, mode
+        self.goals = _lib.as_f64(goals).reshape(-1, 2)
+        self.B = self.goals.shape[0]
+        self.cmd_hz = cmd_hz
+        self.replan_period, self.planning_time_ahead = replan_period, planning_time_ahead
+        self.longitu_step_dis, self.lateral_step_length = float(longitu_step_dis), float(lateral_step_length)
+        self.target_reach_threshold = target_reach_threshold
+        self.move_vel = 0.8 * float(batch_planner.cfg.v_max)                      # :87
+        self.cap = int(round(max_cmd_seconds * cmd_hz))
+        self.stride = int(round(cmd_hz * metric_eva_interval))                    # rows between two metric samples (:119)
+        self.seed = int(seed)
+        self.scene_ids = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32).reshape(-1)
+        self.mission_ids = np.arange(self.B) if mission_ids is None else np.asarray(mission_ids).reshape(-1)
+        if self.mission_ids.shape[0] != self.B or (self.scene_ids is not None and self.scene_ids.shape[0] != self.B):
+            raise ValueError("FleetReplanLoop: one mission id and one scene id per goal")
+        self.timings = []
+        self._dev = None
+
+    # ------------------------------------------------------------ device calls
+    def _subset(self, idx):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(self._device)
+
+    def _up(self, name, host):
+        """mission-indexed host array -> its resident device tensor"""
+        import torch
+        self._dev[name].copy_(torch.from_numpy(np.ascontiguousarray(host)))
+
+    def _sync(self):
+        import torch
+        torch.cuda.synchronize(self._device)     # (the context runs on its own stream: torch's copies first, then its launches)
+
+    def _target(self, sub):
+        c, d, p = self.bp.ctx, self._dev, self._p
+        c.check(c.lib.neo_fleet_target_batch_dev(c.h, self.map.scene_id, p(d["slots"]), self.B, p(sub), int(sub.numel()),
+                                                 p(d["cur_pos"]), p(d["goal"]), p(d["jitter"]), self.longitu_step_dis,
+                                                 self.lateral_step_length, self.move_vel, p(d["tail"]), p(d["near"]),
+                                                 p(d["steps"]), p(d["flags"])))
+
+    def _advance(self, sub):
+        c, d, p = self.bp.ctx, self._dev, self._p
+        step = int(round(self.replan_period * self.cmd_hz))
+        ahead = int(self.planning_time_ahead * self.cmd_hz)                        # :531
+        c.check(c.lib.neo_fleet_advance_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
+                                            p(d["cmd_index"]), p(d["future_index"]), step, ahead, p(d["cur_pos"]),
+                                            p(d["head"])))
+
+    def _splice(self, sub, M, first):
+        c, d, p = self.bp.ctx, self._dev, self._p
+        c.check(c.lib.neo_fleet_splice_dev(c.h, self.B, p(sub), int(sub.numel()), int(M), p(d["x"]), p(d["head"]),
+                                           p(d["tail"]), p(d["solved"]), float(self.cmd_hz), int(first), p(d["cmd"]),
+                                           self.cap, p(d["cmd_len"]), p(d["cmd_index"]), p(d["future_index"]),
+                                           p(d["flags"])))
+
+    def _audit(self):
+        c, d, p = self.bp.ctx, self._dev, self._p
+        c.check(c.lib.neo_fleet_audit_batch_dev(c.h, self.map.scene_id, p(d["slots"]), self.B, None, 0, p(d["cmd"]),
+                                                self.cap, p(d["n_flown"]), self.stride, float(self.cmd_hz), None,
+                                                p(d["audit"]), p(d["count"]), p(d["audit_flags"])))
+
+    def _alloc(self, n):
+        import torch
+        c = self.bp.ctx
+        self._device = dev = torch.device("cuda", c.device)
+        self._p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        B = self.B
+        f = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        i = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        self._dev = dict(cmd=f(B, self.cap, 3, 2), cmd_len=i(B), cmd_index=i(B), future_index=i(B), flags=i(B),
+                         cur_pos=f(B, 2), goal=f(B, 2), jitter=f(B, 2), head=f(B, 3, 2), tail=f(B, 3, 2), near=i(B),
+                         steps=i(B), x=f(B, n), solved=i(B), n_flown=i(B), audit=f(B, _lib.NEO_AUDIT_FIELDS), count=i(B),
+                         audit_flags=i(B), slots=None)
+        if self.scene_ids is not None:
+            slot_of = {int(s): int(c.lib.neo_scene_slot(c.h, int(s))) for s in np.unique(self.scene_ids)}
+            if min(slot_of.values()) < 0:
+                raise _lib.NeoError("FleetReplanLoop: a scene id without a map")
+            self._dev["slots"] = self._subset(np.array([slot_of[int(s)] for s in self.scene_ids]))
+        self._up("goal", self.goals)
+
+    # ------------------------------------------------------------ the loop
+    def run(self, start_pos, start_vel=None, max_replans=60):
+        """fly every mission from start_pos (B, 2) (start_vel (B, 2), None: at rest) towards its goal: the first plan and up to
+        `max_replans` replans, one replan period apart.  Returns a dict of (B,) arrays: success (the reference's
+        reached_target: the flight ended within target_reach_threshold of the goal, was not abandoned and is no
+        METRIC_FAIL), replans (plans that were spliced), failed_attempts, iter_num, opt_runs, n_cmd (rows of the command
+        array), n_flown, final_dist, flags (NEO_FLEET_FLAG_*), audit_flags (NEO_AUDIT_FLAG_*), count and the ten audit
+        fields by name."""
+        B = self.B
+        bp = self.bp
+        count = int(bp.cfg.init_wpts_num)
+        M, n = count + 1, 2 * count + count + 1
+        bp._sync()
+        self._alloc(n)
+        start_pos = _lib.as_f64(start_pos).reshape(B, 2)
+        head = np.zeros((B, 3, 2))
+        head[:, 0] = start_pos
+        if start_vel is not None:
+            head[:, 1] = _lib.as_f64(start_vel).reshape(B, 2)
+        cur_pos = start_pos.copy()
+        tail = np.zeros((B, 3, 2))
+        x = np.zeros((B, n))
+        replans = np.zeros(B, np.int32); failed = np.zeros(B, np.int32); opt_runs = np.zeros(B, np.int32)
+        iter_num = np.zeros(B, np.int64)
+        abandoned = np.zeros(B, bool); landed = np.zeros(B, bool)      # landed: near the goal and that plan spliced (:421-427)
+        active = np.arange(B)
+        self.timings = []
+        d = self._dev
+        planner = bp.geo_plan if self.mode == "geo" else bp.plan
+        for tick in range(max_replans + 1):
+            if active.size == 0:
+                break
+            tm = dict(tick=tick, active=int(active.size), fleet_s=0.0, plan_s=0.0, plans=0, plan_requests=0)
+            t_tick = time.perf_counter()
+            if tick > 0:
+                t0 = time.perf_counter()
+                self._sync()
+                self._advance(self._subset(active))
+                bp.ctx.synchronize()
+                cur_pos = d["cur_pos"].cpu().numpy()
+                head = d["head"].cpu().numpy()
+                tm["fleet_s"] += time.perf_counter() - t0
+            else:
+                self._up("cur_pos", cur_pos)
+                self._up("head", head)
+            pending = active
+            for r in range(MAX_TARGETS):
+                t0 = time.perf_counter()
+                jit = np.zeros((B, 2))
+                jit[pending] = target_jitter(self.seed, self.mission_ids[pending], tick, r)
+                self._up("jitter", jit)
+                sub = self._subset(pending)
+                self._sync()
+                self._target(sub)
+                bp.ctx.synchronize()
+                tail[pending] = d["tail"].cpu().numpy()[pending]
+                near = d["near"].cpu().numpy() != 0
+                tm["fleet_s"] += time.perf_counter() - t0
+                t0 = time.perf_counter()
+                out = planner(self.map, head[pending], tail[pending],
+                              scene_ids=None if self.scene_ids is None else self.scene_ids[pending],
+                              seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[pending])
+                tm["plan_s"] += time.perf_counter() - t0
+                tm["plans"] += 1
+                tm["plan_requests"] += int(pending.size)
+                ok = out["solved"]
+                iter_num[pending] += out["nit_total"]
+                opt_runs[pending] += out["attempts"]
+                t0 = time.perf_counter()
+                x[pending] = out["x"]
+                solved = np.zeros(B, np.int32)
+                solved[pending[ok]] = 1
+                self._up("x", x)
+                self._up("solved", solved)
+                self._sync()
+                self._splice(sub, M, first=(tick == 0))
+                bp.ctx.synchronize()
+                tm["fleet_s"] += time.perf_counter() - t0
+                replans[pending[ok]] += 1
+                failed[pending[~ok]] += 1
+                landed[pending[ok]] = near[pending[ok]]
+                pending = pending[~ok]
+                if pending.size == 0:
+                    break
+            abandoned[pending] = True
+            flags = d["flags"].cpu().numpy()
+            stuck = (flags & (_lib.NEO_FLEET_FLAG_CMD_FULL | _lib.NEO_FLEET_FLAG_SPLICE_FAILED)) != 0
+            active = active[~(abandoned | landed | stuck)[active]]
+            tm["tick_s"] = time.perf_counter() - t_tick
+            tm["host_s"] = tm["tick_s"] - tm["fleet_s"] - tm["plan_s"]
+            self.timings.append(tm)
+        return self._finish(replans, failed, iter_num, opt_runs, abandoned, landed)
+
+    def _finish(self, replans, failed, iter_num, opt_runs, abandoned, landed):
+        import torch
+        d = self._dev
+        cmd_len = d["cmd_len"].cpu().numpy()
+        cmd_index = d["cmd_index"].cpu().numpy()
+        # a mission that landed flies its array to the end; the others stopped at the row they were on
+        n_flown = np.where(landed, cmd_len, np.minimum(cmd_index + 1, cmd_len)).astype(np.int32)
+        self._up("n_flown", n_flown)
+        self._sync()
+        t0 = time.perf_counter()
+        self._audit()
+        self.bp.ctx.synchronize()
+        self.audit_s = time.perf_counter() - t0
+        last = torch.from_numpy(np.maximum(n_flown - 1, 0).astype(np.int64)).to(self._device)
+        end = d["cmd"][torch.arange(self.B, device=self._device), last, 0].cpu().numpy()
+        final_dist = np.where(n_flown > 0, np.linalg.norm(end - self.goals, axis=1), np.inf)
+        flags = d["flags"].cpu().numpy() | np.where(abandoned, _lib.NEO_FLEET_FLAG_ABANDONED, 0).astype(np.int32)
+        audit = d["audit"].cpu().numpy()
+        audit_flags = d["audit_flags"].cpu().numpy()
+        metric_fail = (audit_flags & (_lib.NEO_AUDIT_FLAG_METRIC_FAIL | _lib.NEO_AUDIT_FLAG_NONFINITE)) != 0
+        out = {name: audit[:, k] for k, name in enumerate(_lib.AUDIT_FIELDS)}
+        out.update(success=(final_dist < self.target_reach_threshold) & ~abandoned & ~metric_fail & (flags == 0),
+                   replans=replans, failed_attempts=failed, iter_num=iter_num, opt_runs=opt_runs, n_cmd=cmd_len,
+                   n_flown=n_flown, final_dist=final_dist, flags=flags, audit_flags=audit_flags,
+                   count=d["count"].cpu().numpy(), abandoned=abandoned, metric_fail=metric_fail)
+        return out
+
+    def commands(self, i):
+        """the command array of mission i (n_cmd, 3, 2) copied to the host"""
+        n = int(self._dev["cmd_len"][i].item())
+        return self._dev["cmd"][i, :n].cpu().numpy()
+
+
+def draw_missions(maps, per_map, seed=0, dist_range=(25.0, 30.0), safe_dis=0.7):
+    """`per_map` missions on each of the 2-D maps (ESDF objects with their host arrays): a start near the middle of the
+    map's low-x edge and goals `dist_range` metres from it, inside the map, start and goal cells at least `safe_dis` from
+    the nearest obstacle.  Returns start (B, 2), goals (B, 2), scene_ids (B,) -- the experiment of the reference's
+    bash scripts (one start, goals tens of metres away) for a fleet."""
+    rng = np.random.default_rng([int(seed), 0xF1EE7])
+    starts, goals, sids = [], [], []
+    for m in maps:
+        res, ox, oy = float(m.map_resolution), float(m.map_origin.x), float(m.map_origin.y)
+        H, W = m.esdf_map.shape
+
+        def clear(p):
+            row, col = ((p[:, 1] - oy) / res).astype(int), ((p[:, 0] - ox) / res).astype(int)
+            inside = (p[:, 0] >= ox) & (p[:, 1] >= oy) & (row < H) & (col < W)
+            return inside & (m.esdf_map[np.clip(row, 0, H - 1), np.clip(col, 0, W - 1)] >= safe_dis)
+
+        cand = np.stack([np.full(41, ox + 0.5), oy + 0.5 * H * res + 0.25 * ((np.arange(41) + 1) // 2) * (-1.0) ** np.arange(41)], 1)
+        ok = np.flatnonzero(clear(cand))
+        if ok.size == 0:
+            raise ValueError("draw_missions: no free start on a map")
+        start = cand[ok[0]]
+        got = np.zeros((0, 2))
+        while got.shape[0] < per_map:
+            r = rng.uniform(dist_range[0], dist_range[1], 4 * per_map)
+            th = rng.uniform(-0.5 * np.pi, 0.5 * np.pi, 4 * per_map)
+            g = start + r[:, None] * np.stack([np.cos(th), np.sin(th)], 1)
+            got = np.concatenate([got, g[clear(g)]])
+        starts.append(np.broadcast_to(start, (per_map, 2)))
+        goals.append(got[:per_map])
+        sids.append(np.full(per_map, m.scene_id, np.int32))
+    return np.concatenate(starts), np.concatenate(goals), np.concatenate(sids)

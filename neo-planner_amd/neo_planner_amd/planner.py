@@ -767,16 +767,27 @@ class BatchPlanner:
         ts[:, -1] *= 1.5
         return wp, ts
 
+    @staticmethod
+    def retry_noise(seed, stream_ids, attempt, D, count):
+        """the N(0, 0.5) waypoint jitter (:94) of `plan`'s re-seeded attempt `attempt` for the requests with the streams
+        `stream_ids`: request i draws (D, count) values from its OWN stream SeedSequence(seed, i, attempt)"""
+        return np.stack([np.random.default_rng([int(seed), int(i), int(attempt)]).normal(0.0, 0.5, (D, count))
+                         for i in stream_ids])
+
     def plan(self, map, head, tail, int_wpts=None, ts=None, waypoints=None, max_attempts=5, rng=None, scene_ids=None,
-             seed=None, return_launch_sizes=False):
+             seed=None, return_launch_sizes=False, stream_ids=None):
         """warm_start_plan (:186-203) for a batch: every request gets up to `max_attempts` plan_once runs.  An attempt that
         ends the way the reference raises on -- OverflowError statuses or `collision cost too large` (:235-237) -- is
         re-seeded like the reference's retries (straight line + N(0, 0.5), :94, :201) and optimised again; only the
         failed requests are launched again (compacted re-launches).  The jitter of request i at attempt a comes from its
         OWN stream, SeedSequence(seed, i, a): a retry does not depend on which other requests of the batch failed, as the
         reference's warm_start_plan of one request does not depend on other requests (`seed`: an int; None draws one from
-        `rng` or from the OS).  Returns the optimiser's dict plus `attempts` (B,) and `solved` (B,): a request with solved
-        False is one the reference answers with Exception("No solution for the given target")."""
+        `rng` or from the OS).  `stream_ids` (B,): the i of each request's streams in place of its position in the batch
+        (None: the position) -- a caller that plans a changing subset of longer-lived requests (FleetReplanLoop: missions)
+        passes their ids, so that a request's retries do not depend on who else is in the batch.  Returns the optimiser's
+        dict plus `attempts` (B,), `nit_total` (B,: L-BFGS iterations over all attempts that ran to an answer, what the
+        reference's planner.iter_num accumulates) and `solved` (B,): a request with solved False is one the reference
+        answers with Exception("No solution for the given target")."""
         if (int_wpts is None) != (ts is None):
             raise ValueError("BatchPlanner.plan: give both int_wpts and ts, or neither")
         head = _lib.as_f64(head); tail = _lib.as_f64(tail)
@@ -790,6 +801,14 @@ class BatchPlanner:
             raise _lib.NeoError("BatchPlanner.plan: requests %s name a scene without a map (NEO_TRAJ_BAD_SCENE)"
                                 % np.flatnonzero(out["status"] == _lib.NEO_TRAJ_BAD_SCENE)[:8].tolist())
         out["attempts"] = np.ones(B, dtype=np.int32)
+        if stream_ids is None:
+            stream_ids = np.arange(B)
+        stream_ids = np.asarray(stream_ids).reshape(-1)
+        if stream_ids.shape[0] != B:
+            raise ValueError("BatchPlanner.plan: stream_ids needs one id per request")
+        # (an attempt that overflowed raises before the reference counts it: expert_planner.py:226-232)
+        counted = lambda r: np.where(r["status"] >= _lib.NEO_TRAJ_NUMERIC_RANGE, 0, r["nit"]).astype(np.int64)
+        out["nit_total"] = counted(out)
         failed = lambda r: ((r["status"] > _lib.NEO_TRAJ_MAXITER) & (r["status"] != _lib.NEO_TRAJ_BAD_SCENE)) | r["collision"]
         todo = np.flatnonzero(failed(out))
         if seed is None:
@@ -798,7 +817,7 @@ class BatchPlanner:
         for attempt in range(1, max_attempts):
             if todo.size == 0:
                 break
-            noise = np.stack([np.random.default_rng([int(seed), int(i), attempt]).normal(0.0, 0.5, (D, count)) for i in todo])
+            noise = self.retry_noise(seed, stream_ids[todo], attempt, D, count)
             wp_n, ts_n = self.init_guess(head[todo], tail[todo], count)
             r = self.optimize(map, self.pack_x(wp_n + noise, ts_n), head[todo], tail[todo],
                               scene_ids=None if scene_ids is None else np.asarray(scene_ids)[todo])
@@ -806,6 +825,7 @@ class BatchPlanner:
             for k in ("x", "costs", "costs_last", "nit", "nfev", "status", "collision", "final_cost"):
                 out[k][todo] = r[k]
             out["attempts"][todo] += 1
+            out["nit_total"][todo] += counted(r)
             todo = todo[failed(r)]
         out["solved"] = ~failed(out)
         if return_launch_sizes:

@@ -1,0 +1,153 @@
+#!/usr/bin/env python3
+"""Times the fleet replan loop (neo_fleet_*, neo_fleet.hpp; neo_planner_amd.FleetReplanLoop).
+
+  kernels   the four fleet kernels at B = 4096 missions on scene 0 -- HIP events on the context's stream around 20
+            launches after 3 warm-up launches, on the state a fleet run left behind (real command arrays)
+  fleet     one whole run of 4096 missions (8 scenes x 512 goals drawn at 25 - 30 m) in mode basic or geo: wall time per
+            tick split into fleet kernels (with their small copies) / plan launches / host, missions per second, success
+            rate, plans and failed attempts per mission, median weighted metric
+
+Each step is one process: run them one after the other, every one under its own time limit, e.g.
+  timeout -k 10 300 python tools/gpu_fleet_time.py kernels --json profiles/fleet_kernels.json && \\
+  timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode basic --json profiles/fleet_basic.json && \\
+  timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode geo --json profiles/fleet_geo.json
+Prints one line per figure; --json PATH also writes them."""
+import argparse, ctypes, json, os, sys, time
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "neo-planner_amd"))
+import numpy as np, torch
+import neo_planner_amd as npa
+from neo_planner_amd import synth, _lib
+from neo_planner_amd.fleet import draw_missions
+
+ap = argparse.ArgumentParser()
+ap.add_argument("what", choices=["kernels", "fleet"])
+ap.add_argument("--mode", default="basic", choices=["basic", "geo"])
+ap.add_argument("--scenes", type=int, default=8)
+ap.add_argument("--per-scene", type=int, default=512)
+ap.add_argument("--batch", type=int, default=4096)
+ap.add_argument("--launches", type=int, default=20)
+ap.add_argument("--max-replans", type=int, default=60)
+ap.add_argument("--json", default=None)
+a = ap.parse_args()
+
+dev = torch.device("cuda", 0)
+ctx = _lib.default_context()
+
+
+def scene_map(s):
+    m = npa.ESDF(ctx=ctx)
+    m.occupancy_map_cb(synth.OccupancyGridMsg(synth.occupancy_2d(s)))
+    return m
+
+
+def dump(obj):
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(obj, f, indent=1)
+
+
+if a.what == "fleet":
+    maps = [scene_map(s) for s in range(a.scenes)]
+    start, goals, sids = draw_missions(maps, a.per_scene, seed=0)
+    bp = npa.BatchPlanner(ctx=ctx)
+    loop = npa.FleetReplanLoop(bp, maps[0], goals, mode=a.mode, scene_ids=sids, seed=0)
+    t0 = time.perf_counter()
+    out = loop.run(start, max_replans=a.max_replans)
+    wall = time.perf_counter() - t0
+    B = len(goals)
+    ticks = loop.timings
+    tot = {k: sum(t[k] for t in ticks) for k in ("tick_s", "fleet_s", "plan_s", "host_s")}
+    ok = out["success"]
+    res = dict(mode=a.mode, missions=B, scenes=a.scenes, wall_s=round(wall, 3), ticks=len(ticks),
+               missions_per_s=round(B / wall, 1), success_rate=float(ok.mean()),
+               plans_per_mission=float(out["replans"].mean()), failed_attempts_per_mission=float(out["failed_attempts"].mean()),
+               plan_launch_rounds=int(sum(t["plans"] for t in ticks)), plan_requests=int(sum(t["plan_requests"] for t in ticks)),
+               abandoned=int(out["abandoned"].sum()), metric_fail=int(out["metric_fail"].sum()),
+               cmd_full=int(((out["flags"] & _lib.NEO_FLEET_FLAG_CMD_FULL) != 0).sum()),
+               median_weighted_metric=float(np.nanmedian(out["weighted"])),
+               median_weighted_metric_successful=float(np.nanmedian(out["weighted"][ok])) if ok.any() else None,
+               min_clearance_successful=float(out["min_clearance"][ok].min()) if ok.any() else None,
+               mean_commands=float(out["n_cmd"].mean()), max_commands=int(out["n_cmd"].max()),
+               iterations_per_run=float(out["iter_num"].sum() / max(int(out["opt_runs"].sum()), 1)),
+               audit_ms=round(1e3 * loop.audit_s, 3),
+               per_tick_ms={k: round(1e3 * v / len(ticks), 3) for k, v in tot.items()},
+               share={k: round(v / tot["tick_s"], 4) for k, v in tot.items() if k != "tick_s"},
+               ticks_detail=[{k: (round(v, 5) if isinstance(v, float) else v) for k, v in t.items()} for t in ticks])
+    print(f"{a.mode}: {B} missions in {wall:.2f} s ({B / wall:.0f} missions/s), {len(ticks)} ticks; success "
+          f"{res['success_rate']:.3f}, plans a mission {res['plans_per_mission']:.2f}, failed attempts a mission "
+          f"{res['failed_attempts_per_mission']:.3f}, abandoned {res['abandoned']}, metric_fail {res['metric_fail']}, "
+          f"median weighted metric {res['median_weighted_metric']:.2f}", flush=True)
+    print(f"{a.mode}: per tick {res['per_tick_ms']['tick_s']:.1f} ms = fleet kernels and their copies "
+          f"{res['per_tick_ms']['fleet_s']:.1f} + plan launches {res['per_tick_ms']['plan_s']:.1f} + host "
+          f"{res['per_tick_ms']['host_s']:.1f}; final audit {res['audit_ms']:.2f} ms", flush=True)
+    dump(res)
+    sys.exit(0)
+
+# ---- kernels: B missions on scene 0, timed on the state a short fleet run leaves (arrays a few plans long)
+stream = torch.cuda.Stream()          # (not the null stream: its handle 0 would hand the context back its own stream)
+torch.cuda.set_stream(stream)
+ctx.set_stream(stream.cuda_stream)
+m = scene_map(0)
+B = a.batch
+start, goals, _ = draw_missions([m], B, seed=0)
+bp = npa.BatchPlanner(ctx=ctx)
+loop = npa.FleetReplanLoop(bp, m, goals, seed=0)
+ctx.check(ctx.lib.neo_profile_enable(ctx.h, 1))      # HIP events around the optimiser launches of the run's plans
+out = loop.run(start, max_replans=12)
+n_opt, opt_ms = ctypes.c_int64(0), ctypes.c_double(0.0)
+ctx.check(ctx.lib.neo_profile_read(ctx.h, _lib.NEO_KERNEL_OPTIMIZE, ctypes.byref(n_opt), ctypes.byref(opt_ms)))
+ctx.check(ctx.lib.neo_profile_enable(ctx.h, 0))
+opt_ms_tick = opt_ms.value / len(loop.timings)
+d = loop._dev
+p = lambda v: ctypes.c_void_p(v.data_ptr()) if v is not None else None
+plan_ms = [t["plan_s"] * 1e3 for t in loop.timings]
+n_cmd = d["cmd_len"].cpu().numpy()
+d["n_flown"].copy_(d["cmd_len"])
+M = int(bp.cfg.init_wpts_num) + 1
+d["solved"].fill_(1)
+lib, h = ctx.lib, ctx.h
+calls = {
+    "target": lambda: lib.neo_fleet_target_batch_dev(h, m.scene_id, None, B, None, 0, p(d["cur_pos"]), p(d["goal"]),
+                                                     p(d["jitter"]), 5.0, 1.0, loop.move_vel, p(d["tail"]), p(d["near"]),
+                                                     p(d["steps"]), p(d["flags"])),
+    # (step 0: the index stays, so that every launch reads the same rows)
+    "advance": lambda: lib.neo_fleet_advance_dev(h, B, None, 0, p(d["cmd"]), loop.cap, p(d["cmd_len"]), p(d["cmd_index"]),
+                                                 p(d["future_index"]), 0, 60, p(d["cur_pos"]), p(d["head"])),
+    "splice": lambda: lib.neo_fleet_splice_dev(h, B, None, 0, M, p(d["x"]), p(d["head"]), p(d["tail"]), p(d["solved"]), 60.0,
+                                               0, p(d["cmd"]), loop.cap, p(d["cmd_len"]), p(d["cmd_index"]),
+                                               p(d["future_index"]), p(d["flags"])),
+    "audit": lambda: lib.neo_fleet_audit_batch_dev(h, m.scene_id, None, B, None, 0, p(d["cmd"]), loop.cap, p(d["n_flown"]),
+                                                   loop.stride, 60.0, None, p(d["audit"]), p(d["count"]),
+                                                   p(d["audit_flags"])),
+}
+rows = []
+for name in ("advance", "target", "splice", "audit"):
+    for _ in range(3):
+        ctx.check(calls[name]())
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for _ in range(a.launches):
+        ctx.check(calls[name]())
+    e1.record(stream)
+    e1.synchronize()
+    us = 1e3 * e0.elapsed_time(e1) / a.launches
+    row = dict(kernel=name, batch=B, us_per_launch=round(us, 2))
+    if name == "splice":
+        cnt = d["cmd_len"].cpu().numpy() - d["future_index"].cpu().numpy()
+        row.update(rows_written_mean=float(cnt.mean()), gbytes_per_s=float(cnt.sum() * 48 / (us * 1e-6) / 1e9))
+    if name == "audit":
+        cnt = d["count"].cpu().numpy()
+        row.update(samples_mean=float(cnt.mean()), lookups_per_s=float(cnt.sum() / (us * 1e-6)), rows_mean=float(n_cmd.mean()))
+    if name == "target":
+        row.update(lateral_steps_mean=float(d["steps"].cpu().numpy().mean()))
+    rows.append(row)
+    print(f"{name:>8}: {us:8.1f} us per launch of {B} " + " ".join(f"{k}={v:.4g}" for k, v in row.items()
+                                                                     if k not in ("kernel", "batch", "us_per_launch")), flush=True)
+print(f"plan launches of the same run's ticks (B = {B}, host arrays in and out): median {np.median(plan_ms):.1f} ms, "
+      f"min {min(plan_ms):.1f} ms a tick", flush=True)
+print(f"optimiser kernels of those plans (HIP events): {opt_ms.value:.1f} ms in {n_opt.value} launches over {len(loop.timings)} "
+      f"ticks = {opt_ms_tick:.2f} ms a tick; a tenth of that is {100 * opt_ms_tick:.0f} us", flush=True)
+ctx.set_stream(None)
+dump(dict(kernels=rows, optimise_ms_per_tick=round(opt_ms_tick, 3), optimise_launches=int(n_opt.value), plan_ms_per_tick=[round(v, 3) for v in plan_ms], plan_ms_median=float(np.median(plan_ms))))
