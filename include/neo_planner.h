@@ -455,6 +455,72 @@ int neo_fleet_audit_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_i
                               int n_subset, const double *cmd, int cap, const int32_t *n_flown, int stride,
                               double cmd_hz, const double *weights3, double *audit, int32_t *count, int32_t *flags);
 
+/* ---- the `batch` planner mode on resident arrays (traj_planner/expert_planner.py:103-168) ----------------
+ * MinJerkPlanner.batch_plan optimises K laterally shifted initial guesses of one request and keeps the cheapest
+ * feasible one.  These two calls are what surrounds the optimiser launch for P requests at once, 2-D (D = 2), fp64:
+ *   candidates -> neo_optimize_batch_from_dev over the P * K packed rows -> select.
+ * Two kinds of arrays:
+ *   REQUEST-INDEXED [B]...   head, tail, slots, and everything select writes: indexed by request b;
+ *   PACKED [P * K]...        x0, head_k, tail_k, slots_k and the optimiser's results: row p * K + k holds candidate k
+ *                            of the request at position p of the launch (request-major).
+ * `subset` (n_subset request indices; a DEVICE array in the _dev forms, a host array in the host forms) names the
+ * requests launched, P = n_subset; NULL = all B, P = B, position p is request p.  An index outside 0 .. B - 1 in
+ * `subset` is skipped: candidates leaves its packed rows as they are, select writes nothing for it.  A request may
+ * appear in a subset once.  tau, lateral_offsets and weights4 are always HOST arrays (a few values, handed to the
+ * kernels by value).  A request's results depend on neither B, the subset nor the launch.
+ * Errors, before anything is launched, with a neo_last_error message: D != 2, K < 1, K > NEO_BATCH_MAX_CANDIDATES,
+ * M < 2, a shape neo_optimize_batch refuses, a NULL required buffer, B < 0, a bad subset size: NEO_ERR_INVALID. */
+#define NEO_BATCH_MAX_CANDIDATES 8
+/* batch_generate_init_variables (:103-140), one lane per packed row.  head / tail [B][3][2] request-indexed; slots [B]
+ * request-indexed map-table slots or NULL; tau[M] = map_T2tau of the shared durations init_T * [1.5, 1, ..., 1, 1.5];
+ * lateral_offsets[K] signed offsets along lateral_dir[0] = (f_y, -f_x), f the unit vector from start to target -- NULL:
+ * the reference's 0, +0.6, -0.6, +0.6, ... (its 0.6 * lateral_dir[(k - 1) % 2]; the distance does not grow).
+ *   x0[P * K][n]          n = 2 (M - 1) + M: the M - 1 waypoints of np.linspace(start + stride, target, M - 1,
+ *                         endpoint=False) by dimension, shifted by the candidate's offset, then tau -- every value with
+ *                         the bits NumPy computes (an offset of exactly 0 adds nothing: with start == target the
+ *                         direction is 0 / 0, candidates with an offset are NaN and candidate 0 is finite, as in the
+ *                         reference);
+ *   head_k, tail_k [P * K][3][2]   the request's head and tail, once per candidate;
+ *   slots_k[P * K]        slots[b] per candidate (0 without slots); NULL: not written.
+ * The host form copies x0, head_k, tail_k and slots_k up first, so rows of skipped indices come back as they were. */
+int neo_batch_candidates(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, int K,
+                         const double *head, const double *tail, const int32_t *slots, const double *tau,
+                         const double *lateral_offsets, double *x0, double *head_k, double *tail_k, int32_t *slots_k);
+/* the same with DEVICE pointers (tau and lateral_offsets stay host arrays), asynchronous on the context's stream */
+int neo_batch_candidates_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, int K,
+                             const double *head, const double *tail, const int32_t *slots, const double *tau,
+                             const double *lateral_offsets, double *x0, double *head_k, double *tail_k,
+                             int32_t *slots_k);
+/* the choice (:160-165), one wavefront per request, from the optimiser's PACKED results x_k [P * K][n], costs4_k,
+ * costs4_last_k [P * K][4], nit_k, nfev_k (or NULL), status_k [P * K] and weights4 (NULL: neo_params' weights).
+ * Candidate k is feasible when (status & 0xff) <= NEO_TRAJ_MAXITER and neither NEO_TRAJ_FLAG_COLLISION nor
+ * NEO_TRAJ_BAD_SCENE is set; its cost is (costs4_last * weights4).sum() in NumPy's order ((p0 + p1) + p2) + p3, +inf
+ * when it is not feasible.  REQUEST-INDEXED results:
+ *   chosen[B]        np.argmin of the costs (the first index of the minimum); -1 when no candidate is feasible or the
+ *                    minimum is NaN (the reference falls back to warm_start_plan then);
+ *   cand_cost[B][K]  the costs; solved[B] = chosen >= 0;
+ *   x[B][n], costs4[B][4], costs4_last[B][4], status[B], nit[B], nfev[B] (the last two or NULL)   the chosen
+ *                    candidate's results; a request with chosen = -1 leaves them untouched;
+ *   nit_total[B]     sum of nit over the candidates with (status & 0xff) < NEO_TRAJ_NUMERIC_RANGE, opt_runs[B] their
+ *                    number: what the reference adds to iter_num and opt_running_times (an overflowed run raises
+ *                    before it is counted).
+ *   fallback[P], n_fallback[1]   the requests with chosen = -1, compacted, in the order of their positions in the
+ *                    launch (ascending with an ascending subset or none); entries from n_fallback on are scratch.  No
+ *                    atomics decide a position: the list is the same from launch to launch.  A caller copies 4 bytes
+ *                    and the list, not B statuses.
+ * The host form copies the request-indexed arrays up first: what select does not write comes back as it was. */
+int neo_batch_select(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *x_k,
+                     const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
+                     const int32_t *status_k, const double *weights4, int32_t *chosen, double *cand_cost,
+                     int32_t *solved, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
+                     int32_t *status, int32_t *nit_total, int32_t *opt_runs, int32_t *fallback, int32_t *n_fallback);
+int neo_batch_select_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, int K,
+                         const double *x_k, const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k,
+                         const int32_t *nfev_k, const int32_t *status_k, const double *weights4, int32_t *chosen,
+                         double *cand_cost, int32_t *solved, double *x, double *costs4, double *costs4_last,
+                         int32_t *nit, int32_t *nfev, int32_t *status, int32_t *nit_total, int32_t *opt_runs,
+                         int32_t *fallback, int32_t *n_fallback);
+
 /* ---- timing of the device work (bench.py) ----------------------------------
  * When enabled, every kernel launch of the named family is bracketed by HIP events on
  * the context stream; neo_profile_read returns launches and summed milliseconds. */

@@ -2049,6 +2049,150 @@ int neo_fleet_audit_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, in
   return st.download();
 }
 
+// ---- the `batch` planner mode on resident arrays (traj_planner/expert_planner.py:103-168; kernels: neo_batch.hpp)
+static const double kBatchOffset = 0.6;  // :135
+static int batch_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M, int D, int K) {
+  int rc = fleet_check(c, B, subset, n_subset);
+  if (rc) return rc;
+  if (D != 2) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": D must be 2 (the reference's lateral candidates are 2-D)").c_str());
+  if (K < 1 || K > NEO_BATCH_MAX_CANDIDATES)
+    return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": K must be in 1 .. 8").c_str());
+  rc = check_shape(c, B, M, D);
+  if (rc) return rc;
+  if (M < 2) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": M must be >= 2 (at least one waypoint)").c_str());
+  if ((long long)(subset ? n_subset : B) * K > (long long)INT32_MAX)
+    return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": more than 2^31 - 1 candidate rows").c_str());
+  return NEO_OK;
+}
+// the reference's offsets 0, +0.6, -0.6, +0.6, ... (lateral_dir[(k - 1) % 2], :131-137)
+static void batch_default_offsets(int K, double *off) {
+  for (int k = 0; k < K; ++k) off[k] = k == 0 ? 0.0 : (k % 2 ? kBatchOffset : -kBatchOffset);
+}
+
+int neo_batch_candidates_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *head,
+                             const double *tail, const int32_t *slots, const double *tau, const double *lateral_offsets,
+                             double *x0, double *head_k, double *tail_k, int32_t *slots_k) {
+  int rc = batch_check(c, "batch candidates", B, subset, n_subset, M, D, K);
+  if (rc) return rc;
+  if (!head || !tail || !tau || !x0 || !head_k || !tail_k)
+    return fail_locked(c, NEO_ERR_INVALID, "batch candidates: null buffer");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const FleetArgs f{B, subset, n_subset};
+  if (f.launched() == 0) return NEO_OK;
+  double off[NEO_BATCH_MAX_CANDIDATES];
+  batch_default_offsets(K, off);
+  if (lateral_offsets)
+    for (int k = 0; k < K; ++k) off[k] = lateral_offsets[k];
+  rc = batch_candidates(c, f, {M, K, head, tail, slots, tau, off, x0, head_k, tail_k, slots_k});
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+int neo_batch_candidates(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *head,
+                         const double *tail, const int32_t *slots, const double *tau, const double *lateral_offsets,
+                         double *x0, double *head_k, double *tail_k, int32_t *slots_k) {
+  int rc = batch_check(c, "batch candidates", B, subset, n_subset, M, D, K);
+  if (rc) return rc;
+  if (!head || !tail || !tau || !x0 || !head_k || !tail_k)
+    return fail_locked(c, NEO_ERR_INVALID, "batch candidates: null buffer");
+  const size_t bs = (size_t)B, rows = (size_t)(subset ? n_subset : B) * K, n = (size_t)D * (M - 1) + M;
+  if (rows == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  // the packed outputs go up too: the rows of a skipped index come back as they were
+  HostStage st(c, kStagedUpTo);
+  const auto fh = st.in(head, bs * 6), ft = st.in(tail, bs * 6);
+  const auto fs = st.in(slots, slots ? bs : 0, 1);
+  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
+  const auto fx = st.inout(x0, rows * n), fhk = st.inout(head_k, rows * 6), ftk = st.inout(tail_k, rows * 6);
+  const auto fsk = st.inout(slots_k, slots_k ? rows : 0);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_batch_candidates_dev(c, B, subset ? st.dev(fsub) : nullptr, n_subset, M, D, K, st.dev(fh), st.dev(ft),
+                                slots ? st.dev(fs) : nullptr, tau, lateral_offsets, st.dev(fx), st.dev(fhk), st.dev(ftk),
+                                slots_k ? st.dev(fsk) : nullptr);
+  if (rc) return rc;
+  return st.download();
+}
+
+static int batch_select_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const void *x_k,
+                              const void *costs4_k, const void *last_k, const void *nit_k, const void *status_k,
+                              const void *chosen, const void *cand_cost, const void *solved, const void *x,
+                              const void *costs4, const void *costs4_last, const void *status, const void *nit_total,
+                              const void *opt_runs, const void *fallback, const void *n_fallback) {
+  int rc = batch_check(c, "batch select", B, subset, n_subset, M, D, K);
+  if (rc) return rc;
+  if (!x_k || !costs4_k || !last_k || !nit_k || !status_k || !chosen || !cand_cost || !solved || !x || !costs4 ||
+      !costs4_last || !status || !nit_total || !opt_runs || !fallback || !n_fallback)
+    return fail_locked(c, NEO_ERR_INVALID, "batch select: null buffer");
+  return NEO_OK;
+}
+
+int neo_batch_select_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *x_k,
+                         const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
+                         const int32_t *status_k, const double *weights4, int32_t *chosen, double *cand_cost,
+                         int32_t *solved, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
+                         int32_t *status, int32_t *nit_total, int32_t *opt_runs, int32_t *fallback, int32_t *n_fallback) {
+  int rc = batch_select_check(c, B, subset, n_subset, M, D, K, x_k, costs4_k, costs4_last_k, nit_k, status_k, chosen,
+                              cand_cost, solved, x, costs4, costs4_last, status, nit_total, opt_runs, fallback, n_fallback);
+  if (rc) return rc;
+  if (nfev && !nfev_k) return fail_locked(c, NEO_ERR_INVALID, "batch select: nfev without nfev_k");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const FleetArgs f{B, subset, n_subset};
+  if (f.launched() == 0) {
+    HIPCHK(c, hipMemsetAsync(n_fallback, 0, sizeof(int32_t), c->stream));
+    return NEO_OK;
+  }
+  rc = batch_select(c, f, {D * (M - 1) + M, K, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k,
+                           weights4 ? weights4 : c->params.weights, chosen, cand_cost, solved, x, costs4, costs4_last,
+                           nit, nfev, status, nit_total, opt_runs, fallback, n_fallback});
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+int neo_batch_select(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *x_k,
+                     const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
+                     const int32_t *status_k, const double *weights4, int32_t *chosen, double *cand_cost, int32_t *solved,
+                     double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev, int32_t *status,
+                     int32_t *nit_total, int32_t *opt_runs, int32_t *fallback, int32_t *n_fallback) {
+  int rc = batch_select_check(c, B, subset, n_subset, M, D, K, x_k, costs4_k, costs4_last_k, nit_k, status_k, chosen,
+                              cand_cost, solved, x, costs4, costs4_last, status, nit_total, opt_runs, fallback, n_fallback);
+  if (rc) return rc;
+  if (nfev && !nfev_k) return fail_locked(c, NEO_ERR_INVALID, "batch select: nfev without nfev_k");
+  const size_t bs = (size_t)B, P = (size_t)(subset ? n_subset : B), rows = P * K, n = (size_t)D * (M - 1) + M;
+  if (P == 0) {
+    *n_fallback = 0;
+    return NEO_OK;
+  }
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  // the request-indexed outputs go up too: requests outside the subset, and x of a request without a choice, stay
+  HostStage st(c, kStagedUpTo);
+  const auto fx = st.in(x_k, rows * n), fc = st.in(costs4_k, rows * 4), fl = st.in(costs4_last_k, rows * 4);
+  const auto fni = st.in(nit_k, rows), fnf = st.in(nfev_k, nfev_k ? rows : 0, 1), fst = st.in(status_k, rows);
+  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
+  const auto och = st.inout(chosen, bs);
+  const auto occ = st.inout(cand_cost, bs * K);
+  const auto oso = st.inout(solved, bs);
+  const auto ox = st.inout(x, bs * n), oc = st.inout(costs4, bs * 4), ol = st.inout(costs4_last, bs * 4);
+  const auto oni = st.inout(nit, nit ? bs : 0), onf = st.inout(nfev, nfev ? bs : 0), ost = st.inout(status, bs);
+  const auto ont = st.inout(nit_total, bs), oru = st.inout(opt_runs, bs);
+  // (the whole list comes back; its entries from n_fallback on are scratch)
+  const auto ofb = st.out(fallback, P), onb = st.out(n_fallback, 1);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_batch_select_dev(c, B, subset ? st.dev(fsub) : nullptr, n_subset, M, D, K, st.dev(fx), st.dev(fc), st.dev(fl),
+                            st.dev(fni), nfev_k ? st.dev(fnf) : nullptr, st.dev(fst), weights4, st.dev(och), st.dev(occ),
+                            st.dev(oso), st.dev(ox), st.dev(oc), st.dev(ol), nit ? st.dev(oni) : nullptr,
+                            nfev ? st.dev(onf) : nullptr, st.dev(ost), st.dev(ont), st.dev(oru), st.dev(ofb), st.dev(onb));
+  if (rc) return rc;
+  return st.download();
+}
+
 // ---- geo warm start (traj_planner/astar_planner.py, geo_planner.py:19-101; kernels: neo_geo.hpp)
 static int geo_check(neo_ctx *c, int B, const double *start, const double *target, int max_expansions, int path_cap,
                      const double *key_pts, const double *path, const int32_t *path_len, const double *path_cost,

@@ -241,6 +241,32 @@ int fleet_advance(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, int step, i
 int fleet_splice(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const FleetSpliceArgs &a);
 int fleet_audit(neo_ctx *c, const FleetArgs &f, const FleetAuditArgs &a);
 
+// neo_batch_*_dev: the `batch` planner mode on resident arrays (neo_disp_batch.hip, kernels in neo_batch.hpp).  P =
+// f.launched() requests; tau, off and w are HOST arrays (M, K and 4 values), handed to the kernels by value.
+struct BatchCandArgs {
+  int M, K;
+  const double *head, *tail;  // [B][3][2], by request
+  const int *slots;           // [B] by request, or NULL
+  const double *tau, *off;    // host
+  double *x0, *head_k, *tail_k;  // packed [P * K] rows
+  int *slots_k;                  // packed, or NULL
+};
+struct BatchSelectArgs {
+  int n, K;
+  const double *x_k, *costs4_k, *last_k;  // packed [P * K] rows: the optimiser's results
+  const int *nit_k, *nfev_k, *status_k;
+  const double *w;                        // host, 4 weights
+  int *chosen;                            // everything below by request
+  double *cand_cost;
+  int *solved;
+  double *x, *costs4, *costs4_last;
+  int *nit, *nfev, *status;               // nit, nfev: or NULL
+  int *nit_total, *opt_runs;
+  int *fallback, *n_fallback;             // [P] and [1]
+};
+int batch_candidates(neo_ctx *c, const FleetArgs &f, const BatchCandArgs &a);
+int batch_select(neo_ctx *c, const FleetArgs &f, const BatchSelectArgs &a);
+
 // neo_geo_search_batch_dev / neo_geo_prune_batch (neo_disp_geo.hip); the context is locked and its tables rebuilt
 struct GeoArgs {
   int B;

@@ -31,6 +31,7 @@ NEO_GEO_FLAG_BAD_SCENE = 16
 # neo_fleet_*: flag bits of a mission
 NEO_FLEET_FLAG_TARGET_CAPPED, NEO_FLEET_FLAG_CMD_FULL, NEO_FLEET_FLAG_BAD_SCENE, NEO_FLEET_FLAG_SPLICE_FAILED = 1, 2, 4, 8
 NEO_FLEET_FLAG_ABANDONED = 16
+NEO_BATCH_MAX_CANDIDATES = 8       # neo_batch_*: candidates a request
 
 # every symbol include/neo_planner.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -48,7 +49,8 @@ EXPORTS = [
     "neo_optimize_progress_counter", "neo_effort_order_scratch_bytes", "neo_audit_traj_batch",
     "neo_audit_traj_batch_dev", "neo_geo_search_batch", "neo_geo_search_batch_dev", "neo_geo_prune_batch",
     "neo_geo_workspace_budget", "neo_fleet_target_batch", "neo_fleet_target_batch_dev", "neo_fleet_advance_dev",
-    "neo_fleet_splice_dev", "neo_fleet_audit_batch", "neo_fleet_audit_batch_dev",
+    "neo_fleet_splice_dev", "neo_fleet_audit_batch", "neo_fleet_audit_batch_dev", "neo_batch_candidates",
+    "neo_batch_candidates_dev", "neo_batch_select", "neo_batch_select_dev",
 ]
 
 
@@ -122,6 +124,10 @@ def load():
     L.neo_fleet_splice_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_d, c_i, c_p, c_i] + [c_p] * 4
     L.neo_fleet_audit_batch.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_d] + [c_p] * 4
     L.neo_fleet_audit_batch_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_d] + [c_p] * 4
+    L.neo_batch_candidates.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 9
+    L.neo_batch_candidates_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 9
+    L.neo_batch_select.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 20
+    L.neo_batch_select_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 20
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]

@@ -5,13 +5,17 @@ Every tick is one round of batched launches over the missions still planning:
 
   advance   perfect tracking for one replan period + get_drone_state_ahead (:527-537)   neo_fleet_advance_dev
   target    set_local_target (:450-488)                                                  neo_fleet_target_batch_dev
-  plan      BatchPlanner.plan / geo_plan on the active missions (warm_start_plan / geo_traj_plan)
+  plan      BatchPlanner.plan / geo_plan on the active missions (warm_start_plan / geo_traj_plan), or, in mode
+            "batch", batch_plan_dev on the RESIDENT look-ahead states and targets (batch_plan: three lateral candidates)
   splice    the new commands into the old array at the look-ahead index (:574-578)       neo_fleet_splice_dev
 
 and the missions whose plan failed go round again with a jittered target, up to the reference's 11 targets a tick
 (:429-445).  At the end neo_fleet_audit_batch_dev takes the reference's flight metric (:333-363) over what was flown.
 The command arrays (cmd_hz rows a second and mission) stay in HBM from the first plan to the audit; the small vectors
-(look-ahead state, target, x, statuses) pass through the host, as BatchPlanner.plan takes host arrays.
+(look-ahead state, target, x, statuses) pass through the host, as BatchPlanner.plan takes host arrays.  Mode "batch"
+is the exception: candidates, the optimiser launch over missions x 3, the choice and the splice work on the resident
+arrays; per target round only `near`, `solved`, the two counters and the list of the missions without a feasible
+candidate come to the host, and only those missions take the host `plan` (their rows of x / solved are uploaded).
 
 A mission's flight does not depend on which other missions share the fleet: the kernels work per mission, the target
 jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
@@ -45,16 +49,17 @@ def plan_seed(seed, tick, target):
 
 class FleetReplanLoop:
     """`ReplanLoop` for B missions at once.  goals (B, 2); `map` one 2-D ESDF for all missions, or any of the maps plus
-    scene_ids (B,) of per-mission scene ids (as BatchPlanner.optimize).  mode "basic" (BatchPlanner.plan) or "geo"
-    (geo_plan: the A* warm start).  mission_ids (B,): the ids the random streams are keyed by (None: 0 .. B - 1) -- a
-    mission flown alone with its id flies as it does in the fleet.  max_cmd_seconds sizes the resident command arrays
+    scene_ids (B,) of per-mission scene ids (as BatchPlanner.optimize).  mode "basic" (BatchPlanner.plan), "geo"
+    (geo_plan: the A* warm start) or "batch" (batch_plan: the cheapest feasible of three lateral candidates, on the
+    device).  mission_ids (B,): the ids the random streams are keyed by (None: 0 .. B - 1) -- a mission flown alone with
+    its id flies as it does in the fleet.  max_cmd_seconds sizes the resident command arrays
     (cap = max_cmd_seconds * cmd_hz rows a mission); a mission whose array fills up ends as not reached."""
 
     def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
                  longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
                  scene_ids=None, mission_ids=None, metric_eva_interval=0.1):
-        if mode not in ("basic", "geo"):
-            raise ValueError("FleetReplanLoop: mode must be 'basic' or 'geo'")
+        if mode not in ("basic", "geo", "batch"):
+            raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo' or 'batch'")
         self.bp, self.map, self.mode = batch_planner, map, mode
         self.goals = _lib.as_f64(goals).reshape(-1, 2)
         self.B = self.goals.shape[0]
@@ -72,6 +77,8 @@ class FleetReplanLoop:
             raise ValueError("FleetReplanLoop: one mission id and one scene id per goal")
         self.timings = []
         self._dev = None
+        self._batch = None      # mode "batch": BatchPlanner.batch_buffers, made at the first plan
+        self.uncounted_candidates = np.zeros(self.B, np.int64)   # mode "batch": per mission, candidate runs left out of opt_runs
 
     # ------------------------------------------------------------ device calls
     def _subset(self, idx):
@@ -134,6 +141,37 @@ class FleetReplanLoop:
             self._dev["slots"] = self._subset(np.array([slot_of[int(s)] for s in self.scene_ids]))
         self._up("goal", self.goals)
 
+    def _plan_batch(self, sub, pending, tick, r):
+        """mode "batch": one target round's plans for the missions `pending` (ascending; `sub` the same on the device) on the
+        resident head / tail -- select writes the resident x and solved -- then the host `plan` for the missions without
+        a feasible candidate.  Returns (ok over pending, nit_total, attempts) as the host planners' dicts have them."""
+        import torch
+        bp, d = self.bp, self._dev
+        if self._batch is None:
+            self._batch = bp.batch_buffers(self.B, 3, self._device)
+            self._sync()
+        bufs = bp.batch_plan_dev(self.map, d["head"], d["tail"], self._batch, slots=d["slots"], subset=sub, x=d["x"],
+                                 solved=d["solved"])
+        fb = bp.batch_fallback(bufs)
+        nit = bufs["nit_total"].cpu().numpy()[pending].astype(np.int64)
+        runs = bufs["opt_runs"].cpu().numpy()[pending].copy()
+        self.uncounted_candidates[pending] += 3 - runs      # candidate runs that overflowed: the reference counts none of them
+        if fb.size:
+            idx = torch.from_numpy(fb).to(self._device)
+            head, tail = d["head"][idx].cpu().numpy(), d["tail"][idx].cpu().numpy()
+            count = int(bp.cfg.init_wpts_num)
+            res = bp.plan(self.map, head, tail, int_wpts=bp.batch_init_guess(head, tail, K=1)[0][:, 0],
+                          ts=np.tile(bp._batch_ts_tau(count)[0], (fb.size, 1)),
+                          scene_ids=None if self.scene_ids is None else self.scene_ids[fb],
+                          seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[fb])
+            d["x"][idx] = torch.from_numpy(np.ascontiguousarray(res["x"])).to(self._device)
+            d["solved"][idx] = torch.from_numpy(res["solved"].astype(np.int32)).to(self._device)
+            at = np.searchsorted(pending, fb)
+            nit[at] += res["nit_total"]
+            runs[at] += res["attempts"]
+        ok = d["solved"].cpu().numpy()[pending] != 0
+        return ok, nit, runs
+
     # ------------------------------------------------------------ the loop
     def run(self, start_pos, start_vel=None, max_replans=60):
         """fly every mission from start_pos (B, 2) (start_vel (B, 2), None: at rest) towards its goal: the first plan and up to
@@ -161,6 +199,7 @@ class FleetReplanLoop:
         abandoned = np.zeros(B, bool); landed = np.zeros(B, bool)      # landed: near the goal and that plan spliced (:421-427)
         active = np.arange(B)
         self.timings = []
+        self.uncounted_candidates[:] = 0
         d = self._dev
         planner = bp.geo_plan if self.mode == "geo" else bp.plan
         for tick in range(max_replans + 1):
@@ -173,8 +212,9 @@ class FleetReplanLoop:
                 self._sync()
                 self._advance(self._subset(active))
                 bp.ctx.synchronize()
-                cur_pos = d["cur_pos"].cpu().numpy()
-                head = d["head"].cpu().numpy()
+                if self.mode != "batch":             # (batch plans on the resident look-ahead states)
+                    cur_pos = d["cur_pos"].cpu().numpy()
+                    head = d["head"].cpu().numpy()
                 tm["fleet_s"] += time.perf_counter() - t0
             else:
                 self._up("cur_pos", cur_pos)
@@ -189,25 +229,30 @@ class FleetReplanLoop:
                 self._sync()
                 self._target(sub)
                 bp.ctx.synchronize()
-                tail[pending] = d["tail"].cpu().numpy()[pending]
+                if self.mode != "batch":
+                    tail[pending] = d["tail"].cpu().numpy()[pending]
                 near = d["near"].cpu().numpy() != 0
                 tm["fleet_s"] += time.perf_counter() - t0
                 t0 = time.perf_counter()
-                out = planner(self.map, head[pending], tail[pending],
-                              scene_ids=None if self.scene_ids is None else self.scene_ids[pending],
-                              seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[pending])
+                if self.mode == "batch":
+                    ok, nit_total, attempts = self._plan_batch(sub, pending, tick, r)
+                else:
+                    out = planner(self.map, head[pending], tail[pending],
+                                  scene_ids=None if self.scene_ids is None else self.scene_ids[pending],
+                                  seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[pending])
+                    ok, nit_total, attempts = out["solved"], out["nit_total"], out["attempts"]
                 tm["plan_s"] += time.perf_counter() - t0
                 tm["plans"] += 1
                 tm["plan_requests"] += int(pending.size)
-                ok = out["solved"]
-                iter_num[pending] += out["nit_total"]
-                opt_runs[pending] += out["attempts"]
+                iter_num[pending] += nit_total
+                opt_runs[pending] += attempts
                 t0 = time.perf_counter()
-                x[pending] = out["x"]
-                solved = np.zeros(B, np.int32)
-                solved[pending[ok]] = 1
-                self._up("x", x)
-                self._up("solved", solved)
+                if self.mode != "batch":
+                    x[pending] = out["x"]
+                    solved = np.zeros(B, np.int32)
+                    solved[pending[ok]] = 1
+                    self._up("x", x)
+                    self._up("solved", solved)
                 self._sync()
                 self._splice(sub, M, first=(tick == 0))
                 bp.ctx.synchronize()

@@ -832,6 +832,186 @@ class BatchPlanner:
             out["launch_sizes"] = launches
         return out
 
+    # ------------------------------------------------------------ the reference's `batch` mode (:103-168) for B requests
+    def _batch_offsets(self, K, lateral_offsets):
+        """the signed lateral offsets of K candidates: the reference's 0, +0.6, -0.6, +0.6, ... (0.6 * lateral_dir[(k - 1) % 2],
+        :131-137 -- the distance does not grow) unless `lateral_offsets` (K values) is given"""
+        if lateral_offsets is not None:
+            off = _lib.as_f64(lateral_offsets).reshape(-1)
+            if K is not None and off.shape[0] != int(K):
+                raise ValueError("BatchPlanner.batch_plan: lateral_offsets needs one offset per candidate")
+        else:
+            K = 3 if K is None else int(K)         # the reference's batch_num
+            off = np.array([0.0 if k == 0 else (0.6 if k % 2 else -0.6) for k in range(max(K, 0))])
+        if not 1 <= off.shape[0] <= _lib.NEO_BATCH_MAX_CANDIDATES:
+            raise ValueError("BatchPlanner.batch_plan: K must be in 1 .. %d" % _lib.NEO_BATCH_MAX_CANDIDATES)
+        return off
+
+    def _batch_ts_tau(self, count):
+        """the shared durations init_T * [1.5, 1, ..., 1, 1.5] and their tau, element by element through math.log as
+        MinJerkPlanner.map_T2tau computes it (:468-475)"""
+        ts = float(self.cfg.init_T) * np.ones((count + 1,))
+        ts[0] *= 1.5
+        ts[-1] *= 1.5
+        tau = np.array([-math.log((self.cfg.T_max - self.cfg.T_min) / (t - self.cfg.T_min) - 1) for t in ts])
+        return ts, tau
+
+    def batch_init_guess(self, head, tail, K=None, lateral_offsets=None):
+        """batch_generate_init_variables (:103-140) for B 2-D requests, in NumPy: int_wpts (B, K, D, count) -- candidate k
+        is the straight line shifted by lateral_offsets[k] along lateral_dir[0] -- and the shared ts (M,).  Request by
+        request the values are MinJerkPlanner.batch_generate_init_variables', bit for bit (what neo_batch_candidates
+        computes on the device).  start == target: candidate 0 finite, the shifted ones NaN, as in the reference."""
+        head = _lib.as_f64(head); tail = _lib.as_f64(tail)
+        B, D = head.shape[0], head.shape[2]
+        if D != 2:
+            raise ValueError("BatchPlanner.batch_init_guess: the reference's lateral candidates are 2-D (D = 2)")
+        off = self._batch_offsets(K, lateral_offsets)
+        count = int(self.cfg.init_wpts_num)
+        out = np.zeros((B, off.shape[0], D, count))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for b in range(B):
+                start, target = head[b, 0], tail[b, 0]
+                forward = (target - start) / np.linalg.norm(target - start)
+                side = np.array([forward[1], -forward[0]])           # lateral_dir[0]; lateral_dir[1] is its exact negative
+                stride = (target - start) / (count + 1)
+                c0 = np.linspace(start + stride, target, count, endpoint=False)
+                for k, o in enumerate(off):
+                    out[b, k] = (c0 + o * side if o != 0.0 else c0).T
+        return out, self._batch_ts_tau(count)[0]
+
+    def batch_buffers(self, B, K, device):
+        """the resident arrays of `batch_plan_dev` for up to B requests of K candidates: the packed work arrays of the
+        B * K optimiser runs and the request-indexed results (torch tensors, zeroed)"""
+        import torch
+        count = int(self.cfg.init_wpts_num)
+        n, R = 2 * count + count + 1, B * K
+        f = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
+        i = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
+        return dict(B=B, K=K, x_k=f(R, n), head_k=f(R, 3, 2), tail_k=f(R, 3, 2), slots_k=i(R), costs_k=f(R, 4), last_k=f(R, 4),
+                    nit_k=i(R), nfev_k=i(R), status_k=i(R), chosen=i(B), candidate_cost=f(B, K), solved=i(B), x=f(B, n),
+                    costs=f(B, 4), costs_last=f(B, 4), nit=i(B), nfev=i(B), status=i(B), nit_total=i(B), opt_runs=i(B),
+                    fallback=i(max(B, 1)), n_fallback=i(1))
+
+    def batch_plan_dev(self, map, head, tail, bufs=None, K=None, lateral_offsets=None, slots=None, subset=None, x=None,
+                       solved=None):
+        """the main path of `batch_plan` on RESIDENT torch tensors, asynchronous on the context's stream (as optimize_dev is
+        to optimize): head / tail (B, 3, 2) float64 by request; `slots` (B,) int32 map-table slots by request or None;
+        `subset` an int32 tensor of the request indices to plan (None: all B).  Three launches -- neo_batch_candidates_dev,
+        neo_optimize_batch_from_dev over the P * K packed rows, neo_batch_select_dev -- and nothing passes through the
+        host.  Results by request in `bufs` (batch_buffers; made when None): chosen, candidate_cost, solved, x, costs,
+        costs_last, nit, nfev, status (with the collision flag), nit_total, opt_runs; `x` / `solved`: the caller's own
+        resident arrays to write instead of the ones in bufs (FleetReplanLoop's).  The requests without a feasible candidate
+        -- chosen -1, x untouched -- are listed in bufs["fallback"][:bufs["n_fallback"]]: `batch_fallback` fetches the list;
+        they are the caller's to retry (`batch_plan` does).  Returns bufs."""
+        self._sync()
+        c = self.ctx
+        B, D = head.shape[0], head.shape[2]
+        if D != 2:
+            raise ValueError("BatchPlanner.batch_plan_dev: the reference's lateral candidates are 2-D (D = 2)")
+        off = self._batch_offsets(K, lateral_offsets)
+        K = off.shape[0]
+        if bufs is None:
+            bufs = self.batch_buffers(B, K, head.device)
+        if bufs["B"] < B or bufs["K"] != K:
+            raise ValueError("BatchPlanner.batch_plan_dev: bufs were made for another B or K")
+        count = int(self.cfg.init_wpts_num)
+        M = count + 1
+        _, tau = self._batch_ts_tau(count)
+        P = B if subset is None else int(subset.numel())
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        d = bufs
+        c.check(c.lib.neo_batch_candidates_dev(c.h, B, p(subset), P, M, D, K, p(head), p(tail), p(slots), _lib.ptr(tau),
+                                               _lib.ptr(off), p(d["x_k"]), p(d["head_k"]), p(d["tail_k"]),
+                                               p(d["slots_k"]) if slots is not None else None))
+        if P > 0:
+            c.check(c.lib.neo_optimize_dispatch_order_host(c.h, None, 0))
+            c.check(c.lib.neo_optimize_progress_counter(c.h, None))
+            c.check(c.lib.neo_optimize_batch_from_dev(c.h, map.scene_id, p(d["slots_k"]) if slots is not None else None,
+                                                      P * K, M, D, p(d["x_k"]), p(d["x_k"]), p(d["head_k"]), p(d["tail_k"]),
+                                                      p(d["costs_k"]), p(d["last_k"]), p(d["nit_k"]), p(d["nfev_k"]),
+                                                      p(d["status_k"])))
+        w = _lib.as_f64(self.cfg.weights).reshape(4)
+        c.check(c.lib.neo_batch_select_dev(c.h, B, p(subset), P, M, D, K, p(d["x_k"]), p(d["costs_k"]), p(d["last_k"]),
+                                           p(d["nit_k"]), p(d["nfev_k"]), p(d["status_k"]), _lib.ptr(w), p(d["chosen"]),
+                                           p(d["candidate_cost"]), p(solved if solved is not None else d["solved"]),
+                                           p(x if x is not None else d["x"]), p(d["costs"]), p(d["costs_last"]), p(d["nit"]),
+                                           p(d["nfev"]), p(d["status"]), p(d["nit_total"]), p(d["opt_runs"]),
+                                           p(d["fallback"]), p(d["n_fallback"])))
+        return bufs
+
+    def batch_fallback(self, bufs):
+        """waits for the context's stream, then copies the number of fallback requests (4 bytes) and the list itself"""
+        self.ctx.synchronize()
+        nf = int(bufs["n_fallback"].item())
+        return bufs["fallback"][:nf].cpu().numpy().astype(np.int64) if nf else np.zeros(0, np.int64)
+
+    def batch_plan(self, map, head, tail, K=None, lateral_offsets=None, scene_ids=None, seed=None, stream_ids=None,
+                   max_attempts=5):
+        """MinJerkPlanner.batch_plan (:142-168) for B 2-D requests head / tail (B, 3, 2): K laterally shifted initial
+        guesses a request (`batch_init_guess`), ONE optimiser launch of B * K trajectories, and the cheapest feasible
+        candidate of each request kept -- candidates, launch and choice on the device (`batch_plan_dev`).  Only the
+        requests WITHOUT a feasible candidate come back to the host: they take `plan(int_wpts=candidate 0, ts=...)`, the
+        reference's warm_start_plan(cands[0], ts) (:166-168), with plan's per-request random streams (`seed`,
+        `stream_ids`, `max_attempts` as there).  scene_ids as in `optimize`.  Returns the optimiser's dict for the kept
+        trajectory (x, costs, costs_last, nit, nfev, status, collision) plus chosen (B,: the candidate kept, -1: the
+        result comes from the fallback), candidate_cost (B, K: +inf for a candidate that is not feasible), final_cost
+        (B,: the reference's (costs_last * weights).sum(), :233-234, summed by NumPy on the host -- `optimize`'s
+        final_cost is taken from `costs`, the costs at x, instead), nit_total and attempts (B,: what the reference adds
+        to iter_num and opt_running_times over the candidates, an overflowed run not counted, plus the fallback's
+        nit_total and attempts) and solved (B,).  A scene without a map among the requests raises NeoError, as in `plan`."""
+        import torch
+        head = _lib.as_f64(head); tail = _lib.as_f64(tail)
+        if head.ndim != 3 or head.shape[2] != 2 or head.shape != tail.shape:
+            raise ValueError("BatchPlanner.batch_plan: head and tail (B, 3, 2): the reference's lateral candidates are 2-D")
+        B = head.shape[0]
+        off = self._batch_offsets(K, lateral_offsets)
+        K = off.shape[0]
+        stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
+        if stream_ids.shape[0] != B:
+            raise ValueError("BatchPlanner.batch_plan: stream_ids needs one id per request")
+        sid = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32).reshape(-1)
+        if sid is not None and sid.shape[0] != B:
+            raise ValueError("BatchPlanner.batch_plan: scene_ids needs one id per request")
+        count = int(self.cfg.init_wpts_num)
+        n = 2 * count + count + 1
+        w = np.asarray(self.cfg.weights, dtype=np.float64)
+        if B == 0:
+            z = lambda *shape, dt=np.float64: np.zeros(shape, dtype=dt)
+            return dict(x=z(0, n), costs=z(0, 4), costs_last=z(0, 4), nit=z(0, dt=np.int32), nfev=z(0, dt=np.int32),
+                        status=z(0, dt=np.int32), collision=z(0, dt=bool), chosen=z(0, dt=np.int32), candidate_cost=z(0, K),
+                        final_cost=z(0), nit_total=z(0, dt=np.int64), attempts=z(0, dt=np.int32), solved=z(0, dt=bool))
+        c = self.ctx
+        dev = torch.device("cuda", c.device)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        slots = None
+        if sid is not None:
+            slot_of = {int(s): int(c.lib.neo_scene_slot(c.h, int(s))) for s in np.unique(sid)}
+            if min(slot_of.values()) < 0:
+                raise _lib.NeoError("BatchPlanner.batch_plan: requests name a scene without a map")
+            slots = t(np.array([slot_of[int(s)] for s in sid], dtype=np.int32))
+        d_head, d_tail = t(head), t(tail)
+        bufs = self.batch_buffers(B, K, dev)
+        torch.cuda.synchronize(dev)        # (the context has its own stream: the buffers above are ready before it starts)
+        self.batch_plan_dev(map, d_head, d_tail, bufs, lateral_offsets=off, slots=slots)
+        fb = self.batch_fallback(bufs)
+        h = {k: bufs[k].cpu().numpy() for k in ("x", "costs", "costs_last", "nit", "nfev", "status", "chosen",
+                                                "candidate_cost", "solved", "nit_total", "opt_runs")}
+        st = h["status"]
+        out = dict(x=h["x"], costs=h["costs"], costs_last=h["costs_last"], nit=h["nit"], nfev=h["nfev"], status=st & 0xff,
+                   collision=(st & _lib.NEO_TRAJ_FLAG_COLLISION) != 0, chosen=h["chosen"], candidate_cost=h["candidate_cost"],
+                   nit_total=h["nit_total"].astype(np.int64), attempts=h["opt_runs"].copy(), solved=h["solved"] != 0)
+        if fb.size:
+            cand0 = self.batch_init_guess(head[fb], tail[fb], K=1)[0][:, 0]
+            ts = np.tile(self._batch_ts_tau(count)[0], (fb.size, 1))
+            r = self.plan(map, head[fb], tail[fb], int_wpts=cand0, ts=ts, max_attempts=max_attempts, seed=seed,
+                          stream_ids=stream_ids[fb], scene_ids=None if sid is None else sid[fb])
+            for k in ("x", "costs", "costs_last", "nit", "nfev", "status", "collision", "solved"):
+                out[k][fb] = r[k]
+            out["attempts"][fb] += r["attempts"]
+            out["nit_total"][fb] += r["nit_total"]
+        out["final_cost"] = (out["costs_last"] * w).sum(axis=1)
+        return out
+
     def expected_effort_order(self, head, tail, ts):
         """permutation that starts the runs expected to be long first.  Proxy: time slack of the initial
         guess, sum(ts) * v_max / distance -- a guess that is far too slow needs many iterations to shed

@@ -2,15 +2,17 @@
 """Times the fleet replan loop (neo_fleet_*, neo_fleet.hpp; neo_planner_amd.FleetReplanLoop).
 
   kernels   the four fleet kernels at B = 4096 missions on scene 0 -- HIP events on the context's stream around 20
-            launches after 3 warm-up launches, on the state a fleet run left behind (real command arrays)
-  fleet     one whole run of 4096 missions (8 scenes x 512 goals drawn at 25 - 30 m) in mode basic or geo: wall time per
+            launches after 3 warm-up launches, on the state a fleet run left behind (real command arrays) -- and the
+            two kernels of the batch mode (neo_batch.hpp) at 4096 requests x 3 candidates on the same state
+  fleet     one whole run of 4096 missions (8 scenes x 512 goals drawn at 25 - 30 m) in mode basic, geo or batch: wall time per
             tick split into fleet kernels (with their small copies) / plan launches / host, missions per second, success
             rate, plans and failed attempts per mission, median weighted metric
 
 Each step is one process: run them one after the other, every one under its own time limit, e.g.
   timeout -k 10 300 python tools/gpu_fleet_time.py kernels --json profiles/fleet_kernels.json && \\
   timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode basic --json profiles/fleet_basic.json && \\
-  timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode geo --json profiles/fleet_geo.json
+  timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode geo --json profiles/fleet_geo.json && \\
+  timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode batch --json profiles/fleet_batch.json
 Prints one line per figure; --json PATH also writes them."""
 import argparse, ctypes, json, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,7 +24,7 @@ from neo_planner_amd.fleet import draw_missions
 
 ap = argparse.ArgumentParser()
 ap.add_argument("what", choices=["kernels", "fleet"])
-ap.add_argument("--mode", default="basic", choices=["basic", "geo"])
+ap.add_argument("--mode", default="basic", choices=["basic", "geo", "batch"])
 ap.add_argument("--scenes", type=int, default=8)
 ap.add_argument("--per-scene", type=int, default=512)
 ap.add_argument("--batch", type=int, default=4096)
@@ -122,8 +124,24 @@ calls = {
                                                    loop.stride, 60.0, None, p(d["audit"]), p(d["count"]),
                                                    p(d["audit_flags"])),
 }
+# the batch mode's kernels on the run's last look-ahead states and targets: 4096 requests x 3 candidates; select on the
+# results of one optimiser launch over the 12 288 candidates (not timed here)
+bufs = bp.batch_buffers(B, 3, dev)
+_, tau = bp._batch_ts_tau(M - 1)
+w4 = _lib.as_f64(bp.cfg.weights)
+calls["batch_candidates"] = lambda: lib.neo_batch_candidates_dev(h, B, None, 0, M, 2, 3, p(d["head"]), p(d["tail"]), None,
+                                                                 _lib.ptr(tau), None, p(bufs["x_k"]), p(bufs["head_k"]),
+                                                                 p(bufs["tail_k"]), None)
+calls["batch_select"] = lambda: lib.neo_batch_select_dev(
+    h, B, None, 0, M, 2, 3, p(bufs["x_k"]), p(bufs["costs_k"]), p(bufs["last_k"]), p(bufs["nit_k"]), p(bufs["nfev_k"]),
+    p(bufs["status_k"]), _lib.ptr(w4), p(bufs["chosen"]), p(bufs["candidate_cost"]), p(bufs["solved"]), p(bufs["x"]),
+    p(bufs["costs"]), p(bufs["costs_last"]), p(bufs["nit"]), p(bufs["nfev"]), p(bufs["status"]), p(bufs["nit_total"]),
+    p(bufs["opt_runs"]), p(bufs["fallback"]), p(bufs["n_fallback"]))
+stream.synchronize()
+bp.batch_plan_dev(m, d["head"], d["tail"], bufs)
+ctx.synchronize()
 rows = []
-for name in ("advance", "target", "splice", "audit"):
+for name in ("advance", "target", "splice", "audit", "batch_candidates", "batch_select"):
     for _ in range(3):
         ctx.check(calls[name]())
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -142,6 +160,10 @@ for name in ("advance", "target", "splice", "audit"):
         row.update(samples_mean=float(cnt.mean()), lookups_per_s=float(cnt.sum() / (us * 1e-6)), rows_mean=float(n_cmd.mean()))
     if name == "target":
         row.update(lateral_steps_mean=float(d["steps"].cpu().numpy().mean()))
+    if name == "batch_candidates":
+        row.update(candidates=3 * B)
+    if name == "batch_select":       # (select and its compaction launch)
+        row.update(candidates=3 * B, fallback=int(bufs["n_fallback"].item()), launches_per_call=2)
     rows.append(row)
     print(f"{name:>8}: {us:8.1f} us per launch of {B} " + " ".join(f"{k}={v:.4g}" for k, v in row.items()
                                                                      if k not in ("kernel", "batch", "us_per_launch")), flush=True)
