@@ -282,6 +282,23 @@ int geo_prune(neo_ctx *c, int scene_id, int B, const int *slots, const double *p
 void geo_release(neo_ctx *c);             // frees every geo buffer (neo_ctx_destroy)
 void geo_forget(neo_ctx *c, int scene_id);  // frees the scene's mask (map drop)
 
+// the map kernels' launches (neo_disp_esdf.hip, kernels in neo_esdf.hpp), on the context's stream.  Every pointer is a
+// device array the caller owns -- the C ABI carves the work arrays from the context's scratch -- and nothing is
+// allocated; the arguments are the ones neo_esdf_* checked.
+struct Edt2DWork {  // work arrays of a W x H build: v and z are the sweeps' stacks (maps beyond 512 x 512 only)
+  const int8_t *occ;
+  int *g, *v;        // [W * H] each
+  double *z;         // [H * (W + 1)]
+  double *dist, *gx, *gy;  // [W * H] each: the results, as the reference's arrays
+};
+void esdf_build_2d(neo_ctx *c, const Edt2DWork &w, int W, int H, double res, double4 *rec);  // EDT, gradient, records
+void esdf_pack_2d(neo_ctx *c, const double *dist, const double *gx, const double *gy, size_t ncell, double4 *rec);
+void esdf_pack_3d(neo_ctx *c, const void *src, int src_dtype, int nx, int ny, int nz, int store_dtype, int layout, int nbx,
+                  int nby, int nbz, void *dst);  // nbx, nby, nbz: bricks per axis (NEO_LAYOUT_BRICK only)
+// x, y and z pass of the exact 3-D EDT: occupancy -> gx (row distances) -> sq (squared plane distances) -> dist
+void esdf_edt_3d(neo_ctx *c, const uint8_t *occ, int nx, int ny, int nz, double res, uint16_t *gx, uint32_t *sq, float *dist);
+void esdf_query(neo_ctx *c, const MapEntry &e, int n, const double *pts, double *dist, double *grad);
+
 // FLAT slots of the optimiser vectors: n <= 64, 128, 192 or 256 variables
 inline int slots_for(int M, int D) {
   const int n = D * (M - 1) + M;
@@ -350,7 +367,8 @@ int visit_slots(int M, int flags, F f) {
   return NEO_ERR_INVALID;
 }
 
-// ---- per-family dispatch (neo_disp_*.hip)
+// ---- per-family dispatch (neo_disp_*.hip; the fleet, batch, geo and map units' entry points are declared with their
+// argument packs above)
 int dispatch_eval(neo_ctx *c, const MapEntry &e, int D, const EvalArgs &a);
 int dispatch_sample(neo_ctx *c, const MapEntry &e, int D, const SampleArgs &a);
 int dispatch_audit(neo_ctx *c, int kind, int elem, int layout, int D, const AuditArgs &a);  // neo_disp_audit.hip

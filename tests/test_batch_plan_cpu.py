@@ -85,6 +85,7 @@ def test_header_declares_and_library_exports_the_batch_entry_points():
     assert re.search(r"^#define NEO_BATCH_MAX_CANDIDATES 8\b", header, re.M) and _lib.NEO_BATCH_MAX_CANDIDATES == 8
     assert re.search(r"^#define NEO_ABI_VERSION 1\b", header, re.M)
     assert "neo_disp_batch.hip" in build.SOURCES and build.UNIT_HEADERS["neo_disp_batch.hip"] == ["neo_batch.hpp"]
+    assert "neo_disp_esdf.hip" in build.SOURCES and build.UNIT_HEADERS["neo_disp_esdf.hip"] == ["neo_esdf.hpp"]
     build.build()
     lib = _lib.load()
     for name in ENTRY_POINTS:

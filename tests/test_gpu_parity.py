@@ -58,7 +58,7 @@ def test_esdf_build_and_lookup_bit_exact(path):
                                         ((600, 40), 5), ((3, 520), 6), ((37, 700), 7)])
 def test_esdf_build_matches_scipy_on_odd_shapes(shape, seed):
     """maps up to 512 x 512 take the exhaustive per-cell kernels, larger ones the lower-envelope sweeps
-    (neo_abi.hip: edt2_*_bf / edt_columns + edt_rows): both paths, both with and without obstacles"""
+    (neo_esdf.hpp: edt2_*_bf / edt_columns + edt_rows): both paths, both with and without obstacles"""
     rng = np.random.default_rng(seed)
     occ = np.where(rng.random(shape) < 0.03, 100, 0).astype(np.int8)
     if seed in (4, 6):
@@ -77,7 +77,9 @@ def test_esdf_build_matches_scipy_on_odd_shapes(shape, seed):
                                         # long lines: the narrower LDS tiles of the y / z passes (16, 8 and 2 columns)
                                         ((6, 600, 70), 3), ((700, 6, 40), 4), ((4, 3000, 10), 5), ((2, 2, 2), 6),
                                         # z lines whose tile would pass 64 KB only together with the kernel's static LDS
-                                        ((680, 5, 20), 7), ((1360, 3, 9), 8)])
+                                        ((680, 5, 20), 7), ((1360, 3, 9), 8),
+                                        # lines past the packed keys' 836 voxels: the general form's 8-column tile, z and y pass
+                                        ((900, 3, 9), 9), ((4, 900, 10), 10)])
 def test_esdf_build_3d_is_the_exact_edt(shape, seed):
     """device-side 3-D EDT against scipy.ndimage.distance_transform_edt: equal after the same fp32 rounding"""
     from scipy import ndimage
@@ -103,7 +105,10 @@ def test_esdf_build_3d_packed_key_and_general_line_passes_agree():
     for shape, dens in (((48, 48, 48), 0.01), ((33, 300, 64), 0.002), ((300, 20, 40), 0.002), ((9, 40, 600), 0.001),
                         ((12, 40, 1028), 0.001), ((21, 33, 47), 0.02),
                         # x rows at the edges of the 8 / 16 voxels-a-lane forms: one load a lane, all 64 lanes, one past
-                        ((5, 6, 4), 0.05), ((6, 9, 512), 0.002), ((6, 9, 516), 0.002), ((5, 7, 1024), 0.001)):
+                        ((5, 6, 4), 0.05), ((6, 9, 512), 0.002), ((6, 9, 516), 0.002), ((5, 7, 1024), 0.001),
+                        # z lines at the edges of the tile choices: the last 16-column general tile (63456 of 63488 bytes) and
+                        # the first 8-column one; the longest line the packed keys admit and the first they do not
+                        ((661, 4, 8), 0.01), ((662, 4, 8), 0.01), ((836, 3, 4), 0.01), ((837, 3, 4), 0.01)):
         occ = (rng.random(shape) < dens).astype(np.uint8)
         occ[0] = 1
         occ[:, shape[1] // 2:, :] &= (rng.random((shape[0], shape[1] - shape[1] // 2, shape[2])) < 0.5)  # rows with nothing occupied
@@ -139,6 +144,35 @@ def test_esdf_build_3d_full_scene_matches_scipy():
     want = (ndimage.distance_transform_edt(1 - occ) * (30.0 / 160)).astype(np.float32)
     g3 = npa.ESDF3D.from_occupancy(occ, 30.0 / 160, synth.DOMAIN_ORIGIN, want_dist=True)
     assert np.array_equal(g3.dist, want)
+
+
+@pytest.mark.parametrize("shape,seed", [((5, 6, 7), 0), ((9, 4, 3), 1)])
+def test_esdf_upload_3d_pack_matrix(shape, seed):
+    """neo_esdf_upload_3d packs a float64 or float32 volume into fp32 or fp16 elements in any of the four layouts: all 16
+    combinations, looked up against the oracle on the volume rounded to the stored type (the device converts through fp32
+    and rounds to nearest even, as NumPy does), at the 1e-12 of the other 3-D lookup tests"""
+    from scipy import ndimage
+    rng = np.random.default_rng(seed)
+    occ = (rng.random(shape) < 0.05).astype(np.uint8)
+    occ[0, 0, 0] = 1
+    res = 0.1
+    vol = (ndimage.distance_transform_edt(1 - occ) * res).astype(np.float32)
+    nz, ny, nx = shape
+    hi = np.array([(nx - 1) * res, (ny - 1) * res, (nz - 1) * res])
+    pts = rng.uniform(0.0, 1.0, (200, 3)) * hi                    # strictly inside [0, (n - 1) * res) on every axis
+    assert np.all(pts < hi)
+    want = {}
+    for store, stored in (("f32", vol), ("f16", vol.astype(np.float16).astype(np.float32))):
+        o3 = onp.Grid3DESDF(stored, res, (0.0, 0.0, 0.0))
+        want[store] = np.array([o3.lookup(p)[0] for p in pts])
+    for src in (vol.astype(np.float64), vol):
+        for store in ("f32", "f16"):
+            for layout in ("linear", "yz4", "cell8", "brick"):
+                g3 = npa.ESDF3D(src, res, (0.0, 0.0, 0.0), store=store, layout=layout)
+                dis, _ = g3.query(pts)
+                err = np.max(np.abs(dis - want[store]))
+                print(f"pack matrix {shape} {src.dtype} -> {store} {layout}: max |dis - oracle| = {err:.3e}")
+                assert err <= 1e-12, (src.dtype, store, layout)
 
 
 def test_trilinear_lookup_matches_oracle_and_ties_back_to_2d():
