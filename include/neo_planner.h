@@ -521,6 +521,73 @@ int neo_batch_select_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subse
                          int32_t *nit, int32_t *nfev, int32_t *status, int32_t *nit_total, int32_t *opt_runs,
                          int32_t *fallback, int32_t *n_fallback);
 
+/* ---- BatchPlanner.plan's retry chain on resident arrays (traj_planner/expert_planner.py:186-203) --------
+ * warm_start_plan gives a request up to five plan_once runs: an attempt that ends the way the reference raises on is
+ * re-seeded (straight line + N(0, 0.5) jitter, :94, :201) and optimised again.  These two calls are what surrounds the
+ * optimiser launch of ONE attempt for P requests at once, D = 2 or 3, fp64:
+ *   guess -> neo_optimize_batch_from_dev over the P packed rows -> merge,
+ * and merge's list of failed requests is the next attempt's `subset`.  Between two attempts a host reads the count
+ * (4 bytes) and the list, and draws the jitter of those requests; everything else stays on the device.
+ * Two kinds of arrays, as in the neo_batch_* block:
+ *   REQUEST-INDEXED [B]...   head, tail, slots, x_init and everything merge writes: indexed by request b;
+ *   PACKED [P]...            x0, head_k, tail_k, slots_k, noise and the optimiser's results: row p belongs to the
+ *                            request at position p of the launch.
+ * `subset` (n_subset request indices; a DEVICE array in the _dev forms, a host array in the host forms) names the
+ * requests launched, P = n_subset; NULL = all B, P = B, position p is request p.  An index outside 0 .. B - 1 in
+ * `subset` is skipped: guess leaves its packed rows as they are, merge writes nothing for it.  A request may appear
+ * in a subset once.  frac and tau are always HOST arrays (a few values, handed to the kernel by value).  A request's
+ * results depend on neither B, the subset nor the launch.
+ * Errors, before anything is launched, with a neo_last_error message: M < 2, a shape neo_optimize_batch refuses
+ * (D outside {2, 3} among them), a NULL required buffer, B < 0, a bad subset size: NEO_ERR_INVALID. */
+/* generate_init_variables (:82-101), one lane per launched request.  head / tail [B][3][D] request-indexed; slots [B]
+ * request-indexed map-table slots or NULL; frac[M - 1] = (k + 1) / M, the waypoints' places along the line;
+ * tau[M] = map_T2tau of the durations init_T * [1.5, 1, ..., 1, 1.5].
+ *   x0[P][n]           n = D (M - 1) + M: waypoint k of dimension d is start + (target - start) * frac[k], then
+ *                      + noise[p][d][k] when noise (PACKED [P][D][M - 1], the re-seeded attempts' jitter) is given --
+ *                      every operation rounded on its own, no fused multiply-add: the bits of NumPy's
+ *                      start + (target - start) * f (+ noise) -- by dimension, then tau.
+ *                      With x_init ([B][n] request-indexed, or NULL) the row is x_init[b] copied instead: a caller's
+ *                      own start points (a warm start); frac, tau and noise are not read then;
+ *   head_k, tail_k [P][3][D]   the request's head and tail;
+ *   slots_k[P]         slots[b] (0 without slots); NULL: not written.
+ * The host form copies x0, head_k, tail_k and slots_k up first, so rows of skipped indices come back as they were. */
+int neo_plan_guess(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, const double *head,
+                   const double *tail, const int32_t *slots, const double *x_init, const double *noise,
+                   const double *frac, const double *tau, double *x0, double *head_k, double *tail_k, int32_t *slots_k);
+/* the same with DEVICE pointers (frac and tau stay host arrays), asynchronous on the context's stream */
+int neo_plan_guess_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, const double *head,
+                       const double *tail, const int32_t *slots, const double *x_init, const double *noise,
+                       const double *frac, const double *tau, double *x0, double *head_k, double *tail_k,
+                       int32_t *slots_k);
+/* one attempt's bookkeeping, one wavefront per launched request, from the optimiser's PACKED results x_k [P][n],
+ * costs4_k, costs4_last_k [P][4], nit_k, nfev_k, status_k [P].  REQUEST-INDEXED results, written for every launched
+ * request (requests not launched keep theirs):
+ *   x[B][n], costs4[B][4], costs4_last[B][4], nit[B], nfev[B], status[B]   the attempt's results (status with its
+ *                    NEO_TRAJ_FLAG_COLLISION bit);
+ *   attempts[B]      += 1;
+ *   nit_total[B]     (64-bit) += nit unless (status & 0xff) >= NEO_TRAJ_NUMERIC_RANGE: what the reference adds to
+ *                    iter_num (an overflowed run raises before it is counted);
+ *                    reset != 0 starts a chain instead: attempts = 1, nit_total = the counted nit;
+ *   solved[B]        0 when the attempt FAILED -- ((status & 0xff) > NEO_TRAJ_MAXITER and != NEO_TRAJ_BAD_SCENE) or
+ *                    NEO_TRAJ_FLAG_COLLISION -- 1 otherwise;
+ *   failed[P], n_failed[1]   the failed requests, compacted, in the order of their positions in the launch (ascending
+ *                    with an ascending subset or none); entries from n_failed on are scratch.  No atomics decide a
+ *                    position.  It must not be the array `subset` points to: two attempts in a row alternate
+ *                    between two lists;
+ *   bad_scene[1]     1 when a launched request ended with NEO_TRAJ_BAD_SCENE (a map-table slot without a map: no
+ *                    planning failure, retrying cannot help -- the caller's error to raise), 0 otherwise.
+ * The host form copies the request-indexed arrays up first: what merge does not write comes back as it was. */
+int neo_plan_merge(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, int reset, const double *x_k,
+                   const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
+                   const int32_t *status_k, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
+                   int32_t *status, int32_t *attempts, int64_t *nit_total, int32_t *solved, int32_t *failed,
+                   int32_t *n_failed, int32_t *bad_scene);
+int neo_plan_merge_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, int reset,
+                       const double *x_k, const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k,
+                       const int32_t *nfev_k, const int32_t *status_k, double *x, double *costs4, double *costs4_last,
+                       int32_t *nit, int32_t *nfev, int32_t *status, int32_t *attempts, int64_t *nit_total,
+                       int32_t *solved, int32_t *failed, int32_t *n_failed, int32_t *bad_scene);
+
 /* ---- timing of the device work (bench.py) ----------------------------------
  * When enabled, every kernel launch of the named family is bracketed by HIP events on
  * the context stream; neo_profile_read returns launches and summed milliseconds. */

@@ -1428,6 +1428,145 @@ int neo_batch_select(neo_ctx *c, int B, const int32_t *subset, int n_subset, int
   return st.download();
 }
 
+// ---- BatchPlanner.plan's retry chain on resident arrays (traj_planner/expert_planner.py:186-203; kernels: neo_plan.hpp)
+static int plan_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M, int D) {
+  int rc = fleet_check(c, B, subset, n_subset);
+  if (rc) return rc;
+  rc = check_shape(c, B, M, D);
+  if (rc) return rc;
+  if (M < 2) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": M must be >= 2 (at least one waypoint)").c_str());
+  return NEO_OK;
+}
+
+static int plan_guess_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const void *head,
+                            const void *tail, const void *x_init, const void *frac, const void *tau, const void *x0,
+                            const void *head_k, const void *tail_k) {
+  int rc = plan_check(c, "plan guess", B, subset, n_subset, M, D);
+  if (rc) return rc;
+  if (!head || !tail || !x0 || !head_k || !tail_k) return fail_locked(c, NEO_ERR_INVALID, "plan guess: null buffer");
+  if (!x_init && (!frac || !tau)) return fail_locked(c, NEO_ERR_INVALID, "plan guess: frac and tau are needed without x_init");
+  return NEO_OK;
+}
+
+int neo_plan_guess_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const double *head,
+                       const double *tail, const int32_t *slots, const double *x_init, const double *noise,
+                       const double *frac, const double *tau, double *x0, double *head_k, double *tail_k,
+                       int32_t *slots_k) {
+  int rc = plan_guess_check(c, B, subset, n_subset, M, D, head, tail, x_init, frac, tau, x0, head_k, tail_k);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const FleetArgs f{B, subset, n_subset};
+  if (f.launched() == 0) return NEO_OK;
+  rc = plan_guess(c, f, D, {M, head, tail, slots, x_init, noise, frac, tau, x0, head_k, tail_k, slots_k});
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+int neo_plan_guess(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const double *head,
+                   const double *tail, const int32_t *slots, const double *x_init, const double *noise, const double *frac,
+                   const double *tau, double *x0, double *head_k, double *tail_k, int32_t *slots_k) {
+  int rc = plan_guess_check(c, B, subset, n_subset, M, D, head, tail, x_init, frac, tau, x0, head_k, tail_k);
+  if (rc) return rc;
+  const size_t bs = (size_t)B, P = (size_t)(subset ? n_subset : B), n = (size_t)D * (M - 1) + M, hd = (size_t)3 * D;
+  if (P == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  // the packed outputs go up too: the rows of a skipped index come back as they were
+  HostStage st(c, kStagedUpTo);
+  const auto fh = st.in(head, bs * hd), ft = st.in(tail, bs * hd);
+  const auto fs = st.in(slots, slots ? bs : 0, 1);
+  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
+  const auto fxi = st.in(x_init, x_init ? bs * n : 0, 1);
+  const auto fno = st.in(noise, noise ? P * (size_t)D * (M - 1) : 0, 1);
+  const auto fx = st.inout(x0, P * n), fhk = st.inout(head_k, P * hd), ftk = st.inout(tail_k, P * hd);
+  const auto fsk = st.inout(slots_k, slots_k ? P : 0);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_plan_guess_dev(c, B, subset ? st.dev(fsub) : nullptr, n_subset, M, D, st.dev(fh), st.dev(ft),
+                          slots ? st.dev(fs) : nullptr, x_init ? st.dev(fxi) : nullptr, noise ? st.dev(fno) : nullptr, frac,
+                          tau, st.dev(fx), st.dev(fhk), st.dev(ftk), slots_k ? st.dev(fsk) : nullptr);
+  if (rc) return rc;
+  return st.download();
+}
+
+static int plan_merge_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const void *x_k,
+                            const void *costs4_k, const void *last_k, const void *nit_k, const void *nfev_k,
+                            const void *status_k, const void *x, const void *costs4, const void *costs4_last,
+                            const void *nit, const void *nfev, const void *status, const void *attempts,
+                            const void *nit_total, const void *solved, const void *failed, const void *n_failed,
+                            const void *bad_scene) {
+  int rc = plan_check(c, "plan merge", B, subset, n_subset, M, D);
+  if (rc) return rc;
+  if (!x_k || !costs4_k || !last_k || !nit_k || !nfev_k || !status_k || !x || !costs4 || !costs4_last || !nit || !nfev ||
+      !status || !attempts || !nit_total || !solved || !failed || !n_failed || !bad_scene)
+    return fail_locked(c, NEO_ERR_INVALID, "plan merge: null buffer");
+  return NEO_OK;
+}
+
+int neo_plan_merge_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int reset, const double *x_k,
+                       const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
+                       const int32_t *status_k, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
+                       int32_t *status, int32_t *attempts, int64_t *nit_total, int32_t *solved, int32_t *failed,
+                       int32_t *n_failed, int32_t *bad_scene) {
+  int rc = plan_merge_check(c, B, subset, n_subset, M, D, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4,
+                            costs4_last, nit, nfev, status, attempts, nit_total, solved, failed, n_failed, bad_scene);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const FleetArgs f{B, subset, n_subset};
+  HIPCHK(c, hipMemsetAsync(bad_scene, 0, sizeof(int32_t), c->stream));
+  if (f.launched() == 0) {
+    HIPCHK(c, hipMemsetAsync(n_failed, 0, sizeof(int32_t), c->stream));
+    return NEO_OK;
+  }
+  static_assert(sizeof(long long) == sizeof(int64_t), "nit_total is a 64-bit integer on both sides");
+  rc = plan_merge(c, f, {D * (M - 1) + M, reset ? 1 : 0, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4,
+                         costs4_last, nit, nfev, status, attempts, reinterpret_cast<long long *>(nit_total), solved, failed,
+                         n_failed, bad_scene});
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+int neo_plan_merge(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int reset, const double *x_k,
+                   const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
+                   const int32_t *status_k, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
+                   int32_t *status, int32_t *attempts, int64_t *nit_total, int32_t *solved, int32_t *failed,
+                   int32_t *n_failed, int32_t *bad_scene) {
+  int rc = plan_merge_check(c, B, subset, n_subset, M, D, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4,
+                            costs4_last, nit, nfev, status, attempts, nit_total, solved, failed, n_failed, bad_scene);
+  if (rc) return rc;
+  const size_t bs = (size_t)B, P = (size_t)(subset ? n_subset : B), n = (size_t)D * (M - 1) + M;
+  if (P == 0) {
+    *n_failed = 0;
+    *bad_scene = 0;
+    return NEO_OK;
+  }
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  // the request-indexed arrays go up too: requests outside the subset stay, attempts and nit_total accumulate
+  HostStage st(c, kStagedUpTo);
+  const auto fx = st.in(x_k, P * n), fc = st.in(costs4_k, P * 4), fl = st.in(costs4_last_k, P * 4);
+  const auto fni = st.in(nit_k, P), fnf = st.in(nfev_k, P), fst = st.in(status_k, P);
+  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
+  const auto ox = st.inout(x, bs * n), oc = st.inout(costs4, bs * 4), ol = st.inout(costs4_last, bs * 4);
+  const auto oni = st.inout(nit, bs), onf = st.inout(nfev, bs), ost = st.inout(status, bs);
+  const auto oat = st.inout(attempts, bs);
+  const auto ont = st.inout(nit_total, bs);
+  const auto oso = st.inout(solved, bs);
+  // (the whole list comes back; its entries from n_failed on are scratch)
+  const auto ofl = st.out(failed, P), onl = st.out(n_failed, 1), obs = st.out(bad_scene, 1);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_plan_merge_dev(c, B, subset ? st.dev(fsub) : nullptr, n_subset, M, D, reset, st.dev(fx), st.dev(fc), st.dev(fl),
+                          st.dev(fni), st.dev(fnf), st.dev(fst), st.dev(ox), st.dev(oc), st.dev(ol), st.dev(oni), st.dev(onf),
+                          st.dev(ost), st.dev(oat), st.dev(ont), st.dev(oso), st.dev(ofl), st.dev(onl), st.dev(obs));
+  if (rc) return rc;
+  return st.download();
+}
+
 // ---- geo warm start (traj_planner/astar_planner.py, geo_planner.py:19-101; kernels: neo_geo.hpp)
 static int geo_check(neo_ctx *c, int B, const double *start, const double *target, int max_expansions, int path_cap,
                      const double *key_pts, const double *path, const int32_t *path_len, const double *path_cost,

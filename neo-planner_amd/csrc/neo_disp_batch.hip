@@ -26,7 +26,11 @@ int batch_select(neo_ctx *c, const FleetArgs &f, const BatchSelectArgs &a) {
   hipLaunchKernelGGL(batch_select_kernel, dim3(P), dim3(kWave), 0, c->stream, f.B, P, f.subset, a.n, a.K, a.x_k, a.costs4_k,
                      a.last_k, a.nit_k, a.nfev_k, a.status_k, w, a.chosen, a.cand_cost, a.solved, a.x, a.costs4,
                      a.costs4_last, a.nit, a.nfev, a.status, a.nit_total, a.opt_runs, a.fallback);
-  hipLaunchKernelGGL(batch_compact_kernel, dim3(1), dim3(kCompactThreads), 0, c->stream, P, a.fallback, a.n_fallback);
+  return batch_compact(c, P, a.fallback, a.n_fallback);
+}
+
+int batch_compact(neo_ctx *c, int P, int *pending, int *n_pending) {
+  hipLaunchKernelGGL(batch_compact_kernel, dim3(1), dim3(kCompactThreads), 0, c->stream, P, pending, n_pending);
   return NEO_OK;
 }
 

@@ -266,6 +266,33 @@ struct BatchSelectArgs {
 };
 int batch_candidates(neo_ctx *c, const FleetArgs &f, const BatchCandArgs &a);
 int batch_select(neo_ctx *c, const FleetArgs &f, const BatchSelectArgs &a);
+// pending[P] (request indices, or -1) packed in place in position order, *n_pending their number: one launch
+int batch_compact(neo_ctx *c, int P, int *pending, int *n_pending);
+
+// neo_plan_*_dev: BatchPlanner.plan's retry chain on resident arrays (neo_disp_plan.hip, kernels in neo_plan.hpp).
+// P = f.launched() requests; frac and tau are HOST arrays (M - 1 and M values), handed to the kernel by value.
+struct PlanGuessArgs {
+  int M;
+  const double *head, *tail;     // [B][3][D], by request
+  const int *slots;              // [B] by request, or NULL
+  const double *x_init;          // [B][n] by request, or NULL: the caller's start points instead of the straight line
+  const double *noise;           // packed [P][D][M - 1], or NULL
+  const double *frac, *tau;      // host (not read with x_init)
+  double *x0, *head_k, *tail_k;  // packed [P] rows
+  int *slots_k;                  // packed, or NULL
+};
+struct PlanMergeArgs {
+  int n, reset;
+  const double *x_k, *costs4_k, *last_k;  // packed [P] rows: the optimiser's results
+  const int *nit_k, *nfev_k, *status_k;
+  double *x, *costs4, *costs4_last;       // everything below by request
+  int *nit, *nfev, *status, *attempts;
+  long long *nit_total;
+  int *solved;
+  int *failed, *n_failed, *bad_scene;     // [P], [1] and [1]
+};
+int plan_guess(neo_ctx *c, const FleetArgs &f, int D, const PlanGuessArgs &a);
+int plan_merge(neo_ctx *c, const FleetArgs &f, const PlanMergeArgs &a);
 
 // neo_geo_search_batch_dev / neo_geo_prune_batch (neo_disp_geo.hip); the context is locked and its tables rebuilt
 struct GeoArgs {

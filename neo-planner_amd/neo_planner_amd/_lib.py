@@ -50,7 +50,8 @@ EXPORTS = [
     "neo_audit_traj_batch_dev", "neo_geo_search_batch", "neo_geo_search_batch_dev", "neo_geo_prune_batch",
     "neo_geo_workspace_budget", "neo_fleet_target_batch", "neo_fleet_target_batch_dev", "neo_fleet_advance_dev",
     "neo_fleet_splice_dev", "neo_fleet_audit_batch", "neo_fleet_audit_batch_dev", "neo_batch_candidates",
-    "neo_batch_candidates_dev", "neo_batch_select", "neo_batch_select_dev",
+    "neo_batch_candidates_dev", "neo_batch_select", "neo_batch_select_dev", "neo_plan_guess", "neo_plan_guess_dev",
+    "neo_plan_merge", "neo_plan_merge_dev",
 ]
 
 
@@ -128,6 +129,10 @@ def load():
     L.neo_batch_candidates_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 9
     L.neo_batch_select.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 20
     L.neo_batch_select_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 20
+    L.neo_plan_guess.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i] + [c_p] * 11
+    L.neo_plan_guess_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i] + [c_p] * 11
+    L.neo_plan_merge.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 18
+    L.neo_plan_merge_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 18
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]

@@ -16,6 +16,9 @@ The command arrays (cmd_hz rows a second and mission) stay in HBM from the first
 is the exception: candidates, the optimiser launch over missions x 3, the choice and the splice work on the resident
 arrays; per target round only `near`, `solved`, the two counters and the list of the missions without a feasible
 candidate come to the host, and only those missions take the host `plan` (their rows of x / solved are uploaded).
+With resident=True the plans are BatchPlanner.plan_dev's, bit for bit the same: mode "basic" plans on the resident
+look-ahead states and targets and fetches `solved` and the two counters of the pending missions only; mode "batch" sends
+its list of missions without a feasible candidate through plan_dev as well.
 
 A mission's flight does not depend on which other missions share the fleet: the kernels work per mission, the target
 jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
@@ -53,13 +56,18 @@ class FleetReplanLoop:
     (geo_plan: the A* warm start) or "batch" (batch_plan: the cheapest feasible of three lateral candidates, on the
     device).  mission_ids (B,): the ids the random streams are keyed by (None: 0 .. B - 1) -- a mission flown alone with
     its id flies as it does in the fleet.  max_cmd_seconds sizes the resident command arrays
-    (cap = max_cmd_seconds * cmd_hz rows a mission); a mission whose array fills up ends as not reached."""
+    (cap = max_cmd_seconds * cmd_hz rows a mission); a mission whose array fills up ends as not reached.
+    resident=True (modes "basic" and "batch"): the plans run through BatchPlanner.plan_dev on the resident arrays --
+    the same flights; head, tail and x no longer pass through the host."""
 
     def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
                  longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
-                 scene_ids=None, mission_ids=None, metric_eva_interval=0.1):
+                 scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False):
         if mode not in ("basic", "geo", "batch"):
             raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo' or 'batch'")
+        if resident and mode == "geo":
+            raise ValueError("FleetReplanLoop: resident=True needs mode 'basic' or 'batch' (geo_plan has no resident form)")
+        self.resident = bool(resident)
         self.bp, self.map, self.mode = batch_planner, map, mode
         self.goals = _lib.as_f64(goals).reshape(-1, 2)
         self.B = self.goals.shape[0]
@@ -78,6 +86,7 @@ class FleetReplanLoop:
         self.timings = []
         self._dev = None
         self._batch = None      # mode "batch": BatchPlanner.batch_buffers, made at the first plan
+        self._plan = None       # resident=True: BatchPlanner.plan_buffers, made at the first plan
         self.uncounted_candidates = np.zeros(self.B, np.int64)   # mode "batch": per mission, candidate runs left out of opt_runs
 
     # ------------------------------------------------------------ device calls
@@ -141,6 +150,23 @@ class FleetReplanLoop:
             self._dev["slots"] = self._subset(np.array([slot_of[int(s)] for s in self.scene_ids]))
         self._up("goal", self.goals)
 
+    def _plan_bufs(self):
+        if self._plan is None:
+            self._plan = self.bp.plan_buffers(self.B, self._device, D=2)
+            self._sync()
+        return self._plan
+
+    def _plan_resident(self, sub, pending, tick, r):
+        """resident=True, mode "basic": one target round's plans for the missions `pending` (`sub` the same on the device)
+        on the resident head / tail -- plan_dev writes the resident x and solved.  Returns (ok over pending, nit_total,
+        attempts) as the host planner's dict has them."""
+        bufs = self.bp.plan_dev(self.map, self._dev["head"], self._dev["tail"], bufs=self._plan_bufs(), slots=self._dev["slots"],
+                                subset=sub, x=self._dev["x"], solved=self._dev["solved"], seed=plan_seed(self.seed, tick, r),
+                                stream_ids=self.mission_ids)
+        idx = sub.long()
+        return (self._dev["solved"][idx].cpu().numpy() != 0, bufs["nit_total"][idx].cpu().numpy(),
+                bufs["attempts"][idx].cpu().numpy())
+
     def _plan_batch(self, sub, pending, tick, r):
         """mode "batch": one target round's plans for the missions `pending` (ascending; `sub` the same on the device) on the
         resident head / tail -- select writes the resident x and solved -- then the host `plan` for the missions without
@@ -156,7 +182,22 @@ class FleetReplanLoop:
         nit = bufs["nit_total"].cpu().numpy()[pending].astype(np.int64)
         runs = bufs["opt_runs"].cpu().numpy()[pending].copy()
         self.uncounted_candidates[pending] += 3 - runs      # candidate runs that overflowed: the reference counts none of them
-        if fb.size:
+        if fb.size and self.resident:
+            # candidate 0 (linspace's bits, with pack_x's tau) of the listed missions straight into plan_dev's packed rows
+            c, p, pb = bp.ctx, self._p, self._plan_bufs()
+            count = int(bp.cfg.init_wpts_num)
+            fb_dev = bufs["fallback"][:fb.size]
+            c.check(c.lib.neo_batch_candidates_dev(c.h, self.B, p(fb_dev), int(fb.size), count + 1, 2, 1, p(d["head"]),
+                                                   p(d["tail"]), p(d["slots"]), _lib.ptr(bp._plan_frac_tau(count)[1]), None,
+                                                   p(pb["x_k"]), p(pb["head_k"]), p(pb["tail_k"]),
+                                                   p(pb["slots_k"]) if d["slots"] is not None else None))
+            bp.plan_dev(self.map, d["head"], d["tail"], bufs=pb, slots=d["slots"], subset=fb_dev, x=d["x"], solved=d["solved"],
+                        seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids, _guessed=True)
+            idx = fb_dev.long()
+            at = np.searchsorted(pending, fb)
+            nit[at] += pb["nit_total"][idx].cpu().numpy()
+            runs[at] += pb["attempts"][idx].cpu().numpy()
+        elif fb.size:
             idx = torch.from_numpy(fb).to(self._device)
             head, tail = d["head"][idx].cpu().numpy(), d["tail"][idx].cpu().numpy()
             count = int(bp.cfg.init_wpts_num)
@@ -212,7 +253,7 @@ class FleetReplanLoop:
                 self._sync()
                 self._advance(self._subset(active))
                 bp.ctx.synchronize()
-                if self.mode != "batch":             # (batch plans on the resident look-ahead states)
+                if self.mode != "batch" and not self.resident:      # (batch and resident plans use the resident states)
                     cur_pos = d["cur_pos"].cpu().numpy()
                     head = d["head"].cpu().numpy()
                 tm["fleet_s"] += time.perf_counter() - t0
@@ -229,13 +270,15 @@ class FleetReplanLoop:
                 self._sync()
                 self._target(sub)
                 bp.ctx.synchronize()
-                if self.mode != "batch":
+                if self.mode != "batch" and not self.resident:
                     tail[pending] = d["tail"].cpu().numpy()[pending]
                 near = d["near"].cpu().numpy() != 0
                 tm["fleet_s"] += time.perf_counter() - t0
                 t0 = time.perf_counter()
                 if self.mode == "batch":
                     ok, nit_total, attempts = self._plan_batch(sub, pending, tick, r)
+                elif self.resident:
+                    ok, nit_total, attempts = self._plan_resident(sub, pending, tick, r)
                 else:
                     out = planner(self.map, head[pending], tail[pending],
                                   scene_ids=None if self.scene_ids is None else self.scene_ids[pending],
@@ -247,7 +290,7 @@ class FleetReplanLoop:
                 iter_num[pending] += nit_total
                 opt_runs[pending] += attempts
                 t0 = time.perf_counter()
-                if self.mode != "batch":
+                if self.mode != "batch" and not self.resident:
                     x[pending] = out["x"]
                     solved = np.zeros(B, np.int32)
                     solved[pending[ok]] = 1

@@ -832,6 +832,131 @@ class BatchPlanner:
             out["launch_sizes"] = launches
         return out
 
+    # ------------------------------------------------------------ `plan` on resident arrays
+    def _plan_frac_tau(self, count):
+        """what neo_plan_guess takes from the host: init_guess's fractions f[k] = k / (count + 1) and the tau of its
+        durations -- through pack_x's own expression (np.log: math.log may differ in the last bit)"""
+        frac = np.arange(1, count + 1) / (count + 1)
+        ts = np.full((1, count + 1), float(self.cfg.init_T))
+        ts[:, 0] *= 1.5
+        ts[:, -1] *= 1.5
+        return frac, np.ascontiguousarray(self.pack_x(np.zeros((1, 1, count)), ts)[0, count:])
+
+    def plan_buffers(self, B, device, D=2, waypoints=None):
+        """the resident arrays of `plan_dev` for up to B requests of dimension D with `waypoints` waypoints (None: the
+        config's init_wpts_num): the packed work arrays of an attempt's launch, the two launch lists, and the
+        request-indexed results (torch tensors, zeroed)"""
+        import torch
+        count = int(waypoints if waypoints is not None else self.cfg.init_wpts_num)
+        M, n = count + 1, D * count + count + 1
+        f = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
+        i = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
+        R = max(B, 1)
+        bufs = dict(B=B, D=D, M=M, x_k=f(R, n), head_k=f(R, 3, D), tail_k=f(R, 3, D), slots_k=i(R), noise=f(R, D, count),
+                    costs_k=f(R, 4), last_k=f(R, 4), nit_k=i(R), nfev_k=i(R), status_k=i(R), todo=i(2, R), counts=i(2),
+                    x=f(B, n), costs=f(B, 4), costs_last=f(B, 4), nit=i(B), nfev=i(B), status=i(B), attempts=i(B),
+                    nit_total=torch.zeros(B, dtype=torch.int64, device=device), solved=i(B), launch_sizes=[])
+        if B > 1024:        # (launches this large are dispatched longest-expected first, as `optimize` does)
+            nbytes = int(_lib.load().neo_effort_order_scratch_bytes(B))
+            bufs.update(order=i(B), order_scratch=f(nbytes // 8 + 1))
+        return bufs
+
+    def plan_dev(self, map, head, tail, bufs=None, x0=None, slots=None, subset=None, x=None, solved=None, max_attempts=5,
+                 seed=None, rng=None, stream_ids=None, waypoints=None, _guessed=False):
+        """`plan` on RESIDENT torch tensors, every returned array bit for bit `plan`'s: head / tail (B, 3, D) float64 by
+        request; `x0` (B, n) an optional first guess by request (plan's int_wpts / ts, packed: a warm start) -- without,
+        attempt 0 starts from the straight line; `slots` (B,) int32 map-table slots by request or None; `subset` an
+        int32 tensor of the request indices to plan (None: all B; each at most once).  Every attempt is neo_plan_guess_dev,
+        neo_effort_order_dev for more than 1024 rows, neo_optimize_batch_from_dev over the packed rows and
+        neo_plan_merge_dev; between two attempts the host reads two words and the list of the failed requests, draws
+        `retry_noise` for those -- from the streams SeedSequence(seed, stream_ids[request], attempt), `stream_ids` a HOST
+        array by request (None: the index) -- and uploads it.  seed / rng / max_attempts / waypoints as in `plan`.
+        Results by request in `bufs` (plan_buffers; made when None): x, costs, costs_last, nit, nfev, status (with the
+        collision flag), attempts, nit_total (int64), solved (int32) and launch_sizes (a host list); `x` / `solved`: the
+        caller's own resident arrays to write instead of the ones in bufs (FleetReplanLoop's).  Requests outside the
+        subset keep what they had.  The chain has ended when the call returns (the context's stream is waited for).  A
+        request that names a map-table slot without a map raises NeoError, as in `plan`.  Returns bufs."""
+        import torch
+        if head.ndim != 3 or head.shape[1] != 3 or tuple(tail.shape) != tuple(head.shape):
+            raise ValueError("BatchPlanner.plan_dev: head and tail (B, 3, D)")
+        B, D = head.shape[0], head.shape[2]
+        count = int(waypoints if waypoints is not None else self.cfg.init_wpts_num)
+        if x0 is not None:
+            n0 = x0.shape[1]
+            count = (n0 + D) // (D + 1) - 1
+            if x0.shape[0] != B or count < 1 or D * count + count + 1 != n0 or (waypoints is not None and int(waypoints) != count):
+                raise ValueError("BatchPlanner.plan_dev: x0 (B, D * waypoints + waypoints + 1)")
+        M = count + 1
+        if max_attempts < 1:
+            raise ValueError("BatchPlanner.plan_dev: max_attempts must be >= 1")
+        stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
+        if stream_ids.shape[0] != B:
+            raise ValueError("BatchPlanner.plan_dev: stream_ids needs one id per request")
+        if bufs is not None and (bufs["B"] < B or bufs["D"] != D or bufs["M"] != M):
+            raise ValueError("BatchPlanner.plan_dev: bufs were made for another B, D or number of waypoints")
+        self._sync()
+        c = self.ctx
+        dev = head.device
+        if bufs is None:
+            bufs = self.plan_buffers(B, dev, D=D, waypoints=count)
+            torch.cuda.synchronize(dev)     # (the context has its own stream: the buffers are ready before it starts)
+        d = bufs
+        if seed is None:
+            seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
+        frac, tau = self._plan_frac_tau(count)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        slots_k = p(d["slots_k"]) if slots is not None else None
+        out_x, out_solved = (x if x is not None else d["x"]), (solved if solved is not None else d["solved"])
+        n_failed, bad = p(d["counts"][0:]), p(d["counts"][1:])
+        sub, P = p(subset), (B if subset is None else int(subset.numel()))
+        launches = []
+        bad_scene = None
+        c.check(c.lib.neo_optimize_progress_counter(c.h, None))
+        try:
+            for attempt in range(max_attempts):
+                if attempt > 0:
+                    c.synchronize()
+                    nf, bad_scene = d["counts"].tolist()
+                    if bad_scene or nf == 0:
+                        break
+                    todo = d["todo"][(attempt - 1) % 2]
+                    ids = todo[:nf].cpu().numpy()
+                    noise = self.retry_noise(seed, stream_ids[ids], attempt, D, count)
+                    d["noise"][:nf].copy_(torch.from_numpy(np.ascontiguousarray(noise)))
+                    torch.cuda.synchronize(dev)
+                    sub, P = p(todo), nf
+                if not (attempt == 0 and _guessed):
+                    c.check(c.lib.neo_plan_guess_dev(c.h, B, sub, P, M, D, p(head), p(tail), p(slots),
+                                                     p(x0) if attempt == 0 else None, p(d["noise"]) if attempt > 0 else None,
+                                                     _lib.ptr(frac), _lib.ptr(tau), p(d["x_k"]), p(d["head_k"]), p(d["tail_k"]),
+                                                     slots_k))
+                if P > 0:
+                    if P > 1024:
+                        c.check(c.lib.neo_effort_order_dev(c.h, P, M, D, p(d["x_k"]), p(d["head_k"]), p(d["tail_k"]),
+                                                           p(d["order_scratch"]), p(d["order"])))
+                        c.check(c.lib.neo_optimize_dispatch_order(c.h, p(d["order"]), P))
+                    else:
+                        c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))
+                    c.check(c.lib.neo_optimize_batch_from_dev(c.h, map.scene_id, slots_k, P, M, D, p(d["x_k"]), p(d["x_k"]),
+                                                              p(d["head_k"]), p(d["tail_k"]), p(d["costs_k"]), p(d["last_k"]),
+                                                              p(d["nit_k"]), p(d["nfev_k"]), p(d["status_k"])))
+                c.check(c.lib.neo_plan_merge_dev(c.h, B, sub, P, M, D, int(attempt == 0), p(d["x_k"]), p(d["costs_k"]),
+                                                 p(d["last_k"]), p(d["nit_k"]), p(d["nfev_k"]), p(d["status_k"]), p(out_x),
+                                                 p(d["costs"]), p(d["costs_last"]), p(d["nit"]), p(d["nfev"]), p(d["status"]),
+                                                 p(d["attempts"]), p(d["nit_total"]), p(out_solved), p(d["todo"][attempt % 2]),
+                                                 n_failed, bad))
+                launches.append(P)
+                bad_scene = None
+            c.synchronize()
+        finally:
+            c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))     # (the order is in bufs: no launch after this reads it)
+        if bad_scene is None:       # (the last attempt's word has not been read yet)
+            bad_scene = int(d["counts"][1].item())
+        if bad_scene:
+            raise _lib.NeoError("BatchPlanner.plan_dev: a request names a scene without a map (NEO_TRAJ_BAD_SCENE)")
+        d["launch_sizes"] = launches
+        return bufs
+
     # ------------------------------------------------------------ the reference's `batch` mode (:103-168) for B requests
     def _batch_offsets(self, K, lateral_offsets):
         """the signed lateral offsets of K candidates: the reference's 0, +0.6, -0.6, +0.6, ... (0.6 * lateral_dir[(k - 1) % 2],

@@ -3,16 +3,20 @@
 
   kernels   the four fleet kernels at B = 4096 missions on scene 0 -- HIP events on the context's stream around 20
             launches after 3 warm-up launches, on the state a fleet run left behind (real command arrays) -- and the
-            two kernels of the batch mode (neo_batch.hpp) at 4096 requests x 3 candidates on the same state
+            two kernels of the batch mode (neo_batch.hpp) at 4096 requests x 3 candidates on the same state, and the
+            two kernels of the resident plan (neo_plan.hpp: guess with jitter, merge with its compaction launch) at 4096
+            requests
   fleet     one whole run of 4096 missions (8 scenes x 512 goals drawn at 25 - 30 m) in mode basic, geo or batch: wall time per
             tick split into fleet kernels (with their small copies) / plan launches / host, missions per second, success
-            rate, plans and failed attempts per mission, median weighted metric
+            rate, plans and failed attempts per mission, median weighted metric; --resident plans through
+            BatchPlanner.plan_dev on the resident arrays (modes basic and batch; the same flights)
 
 Each step is one process: run them one after the other, every one under its own time limit, e.g.
   timeout -k 10 300 python tools/gpu_fleet_time.py kernels --json profiles/fleet_kernels.json && \\
   timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode basic --json profiles/fleet_basic.json && \\
   timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode geo --json profiles/fleet_geo.json && \\
-  timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode batch --json profiles/fleet_batch.json
+  timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode batch --json profiles/fleet_batch.json && \\
+  timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode basic --resident --json profiles/fleet_basic_resident.json
 Prints one line per figure; --json PATH also writes them."""
 import argparse, ctypes, json, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,6 +34,7 @@ ap.add_argument("--per-scene", type=int, default=512)
 ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--launches", type=int, default=20)
 ap.add_argument("--max-replans", type=int, default=60)
+ap.add_argument("--resident", action="store_true")
 ap.add_argument("--json", default=None)
 a = ap.parse_args()
 
@@ -54,7 +59,7 @@ if a.what == "fleet":
     maps = [scene_map(s) for s in range(a.scenes)]
     start, goals, sids = draw_missions(maps, a.per_scene, seed=0)
     bp = npa.BatchPlanner(ctx=ctx)
-    loop = npa.FleetReplanLoop(bp, maps[0], goals, mode=a.mode, scene_ids=sids, seed=0)
+    loop = npa.FleetReplanLoop(bp, maps[0], goals, mode=a.mode, scene_ids=sids, seed=0, resident=a.resident)
     t0 = time.perf_counter()
     out = loop.run(start, max_replans=a.max_replans)
     wall = time.perf_counter() - t0
@@ -62,7 +67,7 @@ if a.what == "fleet":
     ticks = loop.timings
     tot = {k: sum(t[k] for t in ticks) for k in ("tick_s", "fleet_s", "plan_s", "host_s")}
     ok = out["success"]
-    res = dict(mode=a.mode, missions=B, scenes=a.scenes, wall_s=round(wall, 3), ticks=len(ticks),
+    res = dict(mode=a.mode, resident=bool(a.resident), missions=B, scenes=a.scenes, wall_s=round(wall, 3), ticks=len(ticks),
                missions_per_s=round(B / wall, 1), success_rate=float(ok.mean()),
                plans_per_mission=float(out["replans"].mean()), failed_attempts_per_mission=float(out["failed_attempts"].mean()),
                plan_launch_rounds=int(sum(t["plans"] for t in ticks)), plan_requests=int(sum(t["plan_requests"] for t in ticks)),
@@ -137,11 +142,24 @@ calls["batch_select"] = lambda: lib.neo_batch_select_dev(
     p(bufs["status_k"]), _lib.ptr(w4), p(bufs["chosen"]), p(bufs["candidate_cost"]), p(bufs["solved"]), p(bufs["x"]),
     p(bufs["costs"]), p(bufs["costs_last"]), p(bufs["nit"]), p(bufs["nfev"]), p(bufs["status"]), p(bufs["nit_total"]),
     p(bufs["opt_runs"]), p(bufs["fallback"]), p(bufs["n_fallback"]))
+# the resident plan's kernels on the same states: the guess of a re-seeded attempt (with jitter) for 4096 requests, and the
+# merge of one optimiser launch's results (not timed here) with its compaction launch
+pb = bp.plan_buffers(B, dev)
+frac, ptau = bp._plan_frac_tau(M - 1)
+pb["noise"].copy_(torch.from_numpy(np.random.default_rng(0).normal(0.0, 0.5, tuple(pb["noise"].shape))))
+calls["plan_guess"] = lambda: lib.neo_plan_guess_dev(h, B, None, 0, M, 2, p(d["head"]), p(d["tail"]), None, None, p(pb["noise"]),
+                                                     _lib.ptr(frac), _lib.ptr(ptau), p(pb["x_k"]), p(pb["head_k"]),
+                                                     p(pb["tail_k"]), None)
+calls["plan_merge"] = lambda: lib.neo_plan_merge_dev(
+    h, B, None, 0, M, 2, 0, p(pb["x_k"]), p(pb["costs_k"]), p(pb["last_k"]), p(pb["nit_k"]), p(pb["nfev_k"]), p(pb["status_k"]),
+    p(pb["x"]), p(pb["costs"]), p(pb["costs_last"]), p(pb["nit"]), p(pb["nfev"]), p(pb["status"]), p(pb["attempts"]),
+    p(pb["nit_total"]), p(pb["solved"]), p(pb["todo"][0]), p(pb["counts"][0:]), p(pb["counts"][1:]))
 stream.synchronize()
 bp.batch_plan_dev(m, d["head"], d["tail"], bufs)
+bp.plan_dev(m, d["head"], d["tail"], pb, max_attempts=1, seed=0)       # (leaves one launch's packed results in pb)
 ctx.synchronize()
 rows = []
-for name in ("advance", "target", "splice", "audit", "batch_candidates", "batch_select"):
+for name in ("advance", "target", "splice", "audit", "batch_candidates", "batch_select", "plan_guess", "plan_merge"):
     for _ in range(3):
         ctx.check(calls[name]())
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -164,6 +182,8 @@ for name in ("advance", "target", "splice", "audit", "batch_candidates", "batch_
         row.update(candidates=3 * B)
     if name == "batch_select":       # (select and its compaction launch)
         row.update(candidates=3 * B, fallback=int(bufs["n_fallback"].item()), launches_per_call=2)
+    if name == "plan_merge":         # (merge and its compaction launch; the memset of the bad-scene word)
+        row.update(failed=int(pb["counts"][0].item()), launches_per_call=2)
     rows.append(row)
     print(f"{name:>8}: {us:8.1f} us per launch of {B} " + " ".join(f"{k}={v:.4g}" for k, v in row.items()
                                                                      if k not in ("kernel", "batch", "us_per_launch")), flush=True)
