@@ -175,12 +175,14 @@ NEO_HD void lbfgs_minimize(Backend &be, typename Backend::Vec &x, const LbfgsOpt
     iter++;
     nit++;
     for (int k = 0; k < 4; ++k) cur[k] = costs[k];
+    // the caps first: SciPy's driver tests them on NEW_X, before it hands the point back to setulb for the
+    // convergence tests -- an iteration that both reaches a cap and converges ends as STOP (TERM_MAXITER)
+    if (nit >= o.maxiter || nfev > o.maxfun) return finish(TERM_MAXITER);
     if (be.amax(g) <= o.gtol) return finish(TERM_CONVERGED_GRAD);
     {
       const double ddum = fmax(fmax(fabs(fold), fabs(f)), 1.0);
       if ((fold - f) <= o.ftol * ddum) return finish(TERM_CONVERGED_F);
     }
-    if (nit >= o.maxiter || nfev > o.maxfun) return finish(TERM_MAXITER);
 
     // ---- update the limited-memory pairs (mainlb + matupd)
     be.lincomb(r, g, -1.0, r);  // r = g - g_old = y

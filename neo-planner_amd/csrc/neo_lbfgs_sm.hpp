@@ -176,12 +176,14 @@ struct LbfgsMachine {
         iter++;
         nit++;
         for (int k = 0; k < 4; ++k) cur()[k] = costs()[k];
+        // the caps first: SciPy's driver tests them on NEW_X, before it hands the point back to setulb for the
+        // convergence tests -- an iteration that both reaches a cap and converges ends as STOP (TERM_MAXITER)
+        if (nit >= o.maxiter || nfev > o.maxfun) return finish(TERM_MAXITER);
         if (be.amax(g) <= o.gtol) return finish(TERM_CONVERGED_GRAD);
         {
           const S ddum = fmax(fmax(fabs(fold), fabs(f)), S(1));
           if ((fold - f) <= (S)o.ftol * ddum) return finish(TERM_CONVERGED_F);
         }
-        if (nit >= o.maxiter || nfev > o.maxfun) return finish(TERM_MAXITER);
         // ---- update the limited-memory pairs (mainlb + matupd)
         be.lincomb(r, g, -1.0, r);  // r = g - g_old = y
         S dr, ddum;

@@ -46,10 +46,14 @@ class PlannerConfig:
 
 
 def _push_params(ctx, p, sample_dtype, stale_T=True, flags=0):
+    """the optimiser options ftol / gtol / maxls / maxiter / maxfun are read from `p` where it has them; without them
+    the reference's (expert_planner.py:213-225)"""
     ctx.set_params(v_max=float(p.v_max), T_min=float(p.T_min), T_max=float(p.T_max), safe_dis=float(p.safe_dis),
                    delta_t=float(p.delta_t), weights=[float(w) for w in p.weights],
-                   collision_cost_tol=float(p.collision_cost_tol), ftol=1e-4, gtol=1e-4, maxls=20,
-                   maxiter=15000, maxfun=15000, bugcompat_stale_T=int(bool(stale_T)),
+                   collision_cost_tol=float(p.collision_cost_tol), ftol=float(getattr(p, "ftol", 1e-4)),
+                   gtol=float(getattr(p, "gtol", 1e-4)), maxls=int(getattr(p, "maxls", 20)),
+                   maxiter=int(getattr(p, "maxiter", 15000)), maxfun=int(getattr(p, "maxfun", 15000)),
+                   bugcompat_stale_T=int(bool(stale_T)),
                    sample_dtype={"f64": _lib.NEO_F64, "f32": _lib.NEO_F32}[sample_dtype], flags=int(flags))
 
 

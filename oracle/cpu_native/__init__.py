@@ -89,8 +89,10 @@ def make_params(cfg=None, stale_T=True, sample_f32=False, coeff_eps=0.0, grad_ep
     for k in range(4):
         p.w[k] = float(cfg.weights[k])
     p.coll_tol = float(cfg.collision_cost_tol)
-    p.ftol = p.gtol = 1e-4                              # tol=1e-4 (expert_planner.py:218)
-    p.maxls, p.maxiter, p.maxfun = 20, 15000, 15000     # (:221-224)
+    # tol=1e-4 (expert_planner.py:218) and maxls / maxiter / maxfun (:221-224), unless cfg carries its own
+    p.ftol, p.gtol = float(getattr(cfg, "ftol", 1e-4)), float(getattr(cfg, "gtol", 1e-4))
+    p.maxls, p.maxiter, p.maxfun = (int(getattr(cfg, "maxls", 20)), int(getattr(cfg, "maxiter", 15000)),
+                                    int(getattr(cfg, "maxfun", 15000)))
     p.stale_T = int(bool(stale_T))
     p.sample_f32 = int(bool(sample_f32))
     p.coeff_eps = float(coeff_eps)

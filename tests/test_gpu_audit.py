@@ -132,7 +132,39 @@ def test_audit_equals_the_metric_of_eval_rows_and_point_queries_3d(store, layout
 def test_audit_against_the_oracle_and_the_reference_formula(map2d, cfg2_2d):
     """get_full_state_cmd(10) and GridESDF.get_edt_dis of the NumPy oracle through traj_planner_node.py:333-363"""
     from oracle import minco_np as onp
-    bp, head, tail, x0, xo = cfg2_2d
+    _check_against_the_oracle(map2d, cfg2_2d, onp.PlannerParams())
+
+
+@pytest.fixture(scope="module", params=["A", "B"])
+def set_2d(request, map2d):
+    """64 requests at a parameter set of tests/param_sets.py: a non-default v_max, safe_dis and collision_cost_tol in the
+    metric, T_min / T_max in neo_eval_traj_batch's tau -> T map"""
+    import param_sets as ps
+    name = request.param
+    bp = npa.BatchPlanner(config=ps.planner_config(name))
+    head, tail, wp, _ = synth.replan_requests(1, 64, 20, D=2)
+    ts = ps.durations(np.random.default_rng(7), name, (64, 21), *ps.RUN_DUR[name])
+    x0 = bp.pack_x(wp, ts)
+    xo = bp.optimize(map2d, x0, head, tail)["x"]
+    return name, (bp, head, tail, x0, xo)
+
+
+def test_audit_equals_the_metric_of_eval_rows_and_point_queries_at_the_sets(map2d, set_2d):
+    _, (bp, head, tail, x0, xo) = set_2d
+    raw = _check_self_consistent(bp, map2d, x0, head, tail, 10.0)
+    opt = _check_self_consistent(bp, map2d, xo, head, tail, 10.0)
+    assert raw["unsafe"].any() and raw["unsafe"].sum() >= opt["unsafe"].sum()
+
+
+def test_audit_against_the_oracle_and_the_reference_formula_at_the_sets(map2d, set_2d):
+    import param_sets as ps
+    name, run = set_2d
+    _check_against_the_oracle(map2d, run, ps.oracle_params(name))
+
+
+def _check_against_the_oracle(map2d, run, oracle_params):
+    from oracle import minco_np as onp
+    bp, head, tail, x0, xo = run
     occ = synth.occupancy_2d(1)
     grid = onp.GridESDF(occ, synth.RES, occ.shape[1], occ.shape[0], (synth.DOMAIN_ORIGIN[0], synth.DOMAIN_ORIGIN[1]))
     B, M, D = 48, 21, 2
@@ -147,7 +179,7 @@ def test_audit_against_the_oracle_and_the_reference_formula(map2d, cfg2_2d):
         if np.any(-x[b, D * (M - 1):] > 709.782712893384):   # math.exp(-tau) overflows: the reference raises (:481)
             assert out["flags"][b] == _lib.NEO_AUDIT_FLAG_NONFINITE and out["count"][b] == 0
             continue
-        pl = onp.OraclePlanner(onp.PlannerParams())
+        pl = onp.OraclePlanner(oracle_params)
         pl.read_planning_conditions(grid, hd[b], tl[b], wp[b], ts[b])
         st = pl.get_full_state_cmd(10)
         # the reference formula, verbatim in structure (traj_planner_node.py:333-363)

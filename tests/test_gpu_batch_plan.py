@@ -225,6 +225,42 @@ def test_select_equals_the_numpy_restatement_on_synthetic_results(K, shuffled):
     compare({k: v.cpu().numpy() for k, v in d.items()}, d_fb.cpu().numpy(), int(d_nfb.item()))
 
 
+def test_select_without_weights_uses_the_contexts_weights_at_set_b():
+    """weights4 == NULL: the context's weights -- at parameter set B (tests/param_sets.py: [2, 0.25, 40, 300]) the candidate
+    costs and the choice are the restatement's with the set's weights, and differ from the default weights' choice"""
+    import param_sets as ps
+    ctx = _lib.default_context()
+    rng = np.random.default_rng(77)
+    B, K, n, M = 16, 3, 7, 3
+    sub = rng.permutation(B).astype(np.int32)
+    R = B * K
+    xk = rng.normal(0, 1, (R, n)); ck = rng.random((R, 4))
+    lk = rng.random((R, 4)) * np.array([1.0, 1.0, 1e-1, 1e-3])      # (a collision term that decides at 10000, not at 300)
+    nit = rng.integers(0, 200, R).astype(np.int32); nfev = rng.integers(0, 400, R).astype(np.int32)
+    st = rng.choice([0, 1, 2, 3, 4, 0x100], R, p=[.4, .2, .1, .1, .1, .1]).astype(np.int32)
+    names = ("chosen", "cand_cost", "solved", "x", "costs4", "costs4_last", "nit", "nfev", "status", "nit_total", "opt_runs")
+    init = dict(chosen=np.full(B, -9, np.int32), cand_cost=np.full((B, K), SENTINEL), solved=np.full(B, -9, np.int32),
+                x=np.full((B, n), SENTINEL), costs4=np.full((B, 4), SENTINEL), costs4_last=np.full((B, 4), SENTINEL),
+                nit=np.full(B, -9, np.int32), nfev=np.full(B, -9, np.int32), status=np.full(B, -9, np.int32),
+                nit_total=np.full(B, -9, np.int32), opt_runs=np.full(B, -9, np.int32))
+    chosen = {}
+    for name in ("B", None):
+        bp = npa.BatchPlanner(config=ps.planner_config(name))
+        bp._sync()
+        w = np.asarray(bp.cfg.weights, dtype=np.float64)
+        ref, ref_fb = _select_restated(B, sub, K, n, xk, ck, lk, nit, nfev, st, w, init)
+        h = {k: v.copy() for k, v in init.items()}
+        fb = np.full(B, -3, np.int32); nfb = np.full(1, -3, np.int32)
+        ctx.check(ctx.lib.neo_batch_select(ctx.h, B, _lib.ptr(sub), B, M, 2, K, _lib.ptr(xk), _lib.ptr(ck), _lib.ptr(lk),
+                                           _lib.ptr(nit), _lib.ptr(nfev), _lib.ptr(st), None,
+                                           *[_lib.ptr(h[k]) for k in names], _lib.ptr(fb), _lib.ptr(nfb)))
+        for k in names:
+            assert np.array_equal(h[k], ref[k], equal_nan=True), (name, k)
+        assert int(nfb[0]) == len(ref_fb) and np.array_equal(fb[:len(ref_fb)], ref_fb)
+        chosen[name] = h["chosen"].copy()
+    assert (chosen["B"] >= 0).sum() >= B // 2 and not np.array_equal(chosen["B"], chosen[None])
+
+
 # ------------------------------------------------------------------ 3. batch_plan on R
 class _Recording(npa.MinJerkPlanner):
     """MinJerkPlanner that keeps the tau the optimiser returned for every candidate (batch_plan keeps int_wpts and ts only)"""

@@ -378,8 +378,18 @@ def _audit_restated(m, rows, n_flown, stride, hz, cfg, weights=(1.0, 1.0, 100.0)
 
 
 def test_audit_of_flown_rows_equals_the_reference_metric(maps, flight3):
+    _check_audit_of_flown_rows(maps, flight3, npa.BatchPlanner())
+
+
+def test_audit_of_flown_rows_equals_the_reference_metric_at_set_a(maps, flight3):
+    """the same comparison with the context at parameter set A (tests/param_sets.py): v_max 2.5, safe_dis 1.1 and
+    collision_cost_tol 40 in the metric and its METRIC_FAIL threshold"""
+    import param_sets as ps
+    _check_audit_of_flown_rows(maps, flight3, npa.BatchPlanner(config=ps.planner_config("A")))
+
+
+def _check_audit_of_flown_rows(maps, flight3, bp):
     torch, dev = _torch()
-    bp = npa.BatchPlanner()
     ctx = bp.ctx
     bp._sync()
     m, _ = maps[3]
@@ -389,12 +399,12 @@ def test_audit_of_flown_rows_equals_the_reference_metric(maps, flight3):
     assert 1000 < len(flown) <= cap
     rng = np.random.default_rng(3)
     cases = [(flown, len(flown)), (flown, len(flown) - 1), (flown, 1207), (flown, 1), (flown, 0), (flown, 7)]
-    # synthetic flights: straight lines at 1.3 and 0.7 m/s through the forest and out of the map
+    # synthetic flights: straight lines at 1.3 and 0.7 times v_max through the forest and out of the map
     for k in range(10):
         a = np.array([rng.uniform(0.5, 5.0), rng.uniform(-14.0, 14.0)])
         b = np.array([rng.uniform(31.0, 40.0), rng.uniform(-20.0, 20.0)])
         n = int(rng.integers(600, cap))
-        speed = 1.3 if k % 2 == 0 else 0.7
+        speed = (1.3 if k % 2 == 0 else 0.7) * bp.cfg.v_max
         u = (b - a) / np.linalg.norm(b - a)
         rows = np.zeros((n, 3, 2))
         rows[:, 0] = a + (np.arange(n) / hz * speed)[:, None] * u + 0.3 * np.sin(np.arange(n) / 40.0)[:, None] * u[::-1]

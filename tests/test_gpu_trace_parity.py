@@ -24,8 +24,9 @@ Boundary states: the 3-D requests have non-zero head and tail velocity and accel
 leave three of those rows at zero), so every row of the boundary state enters every evaluation.
 
 Counted exceptions, as in test_gpu_replay.py:
-  * the all-fp32 mode forms T in fp32: an evaluation whose T / delta_t lies within fp32 rounding of an integer may use one
-    sample more or fewer than the oracle -- identified by the recorded sample count, each within 1e-5 of a boundary, rare;
+  * the all-fp32 mode forms T in fp32: an evaluation whose q = T / delta_t lies within fp32 rounding of an integer may use
+    one sample more or fewer than the oracle -- identified by the recorded sample count, each within 2e-7 * max(q, 50) of a
+    boundary (1e-5 at the default parameters, where q <= 50), rare;
   * gradient cell-face events of the fp32 modes: a sample whose fp32 position lies on the other side of a voxel face than
     the oracle's reads the neighbouring cell's gradient (the trilinear interpolant is continuous, its gradient is not);
   * on the 2-D NEAREST map the VALUE jumps at cell faces too (tests/helpers.py reference_jump): an fp32 sample position
@@ -46,6 +47,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import param_sets as ps
 from test_gpu_replay import TOL
 
 pytestmark = pytest.mark.gpu
@@ -76,12 +78,14 @@ def k2(D, NS, real, waves, lg, num="double"):
 PD3, PD2, WL = "WaveLanesPD<3>", "WaveLanesPD<2>", "WaveLanes"
 
 
-def case(name, inst, mode, M, waves=None, flags=0, stale_T=True, map="3d", store="f32", D=3, scenes=1, order=None):
-    """inst: the optimize_kernel<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET> that dispatch_opt's choice of
+def case(name, inst, mode, M, waves=None, flags=0, stale_T=True, map="3d", store="f32", D=3, scenes=1, order=None, cfg=None):
+    """cfg: None (the default parameters) or the name of a parameter set of tests/param_sets.py -- the run's parameters and
+    the range its start durations are drawn from.
+    inst: the optimize_kernel<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET> that dispatch_opt's choice of
     launch_opt<D, Real, MapT, LookupT, WAVES, Num> launches for this shape (NS = ceil(n / 64), capped at 4; LG =
     WaveLanesPD<D> where D * M <= 64 and flags bit 512 is clear, else WaveLanes)"""
     return pytest.param(dict(name=name, inst=inst, mode=mode, M=M, waves=waves, flags=flags, stale_T=stale_T, map=map,
-                             store=store, D=D, scenes=scenes, order=order), id=name)
+                             store=store, D=D, scenes=scenes, order=order, cfg=cfg), id=name)
 
 
 CASES = [
@@ -145,6 +149,22 @@ CASES = [
     case("scenes2-f32x-M21", k3(2, "float", 2, PD3, "float"), "f32x", 21, scenes=2),
     case("reversed-f64-M21", k3(2, "double", 1, PD3), "f64", 21, order="reversed"),
     case("reversed-f32x-M21", k3(2, "float", 2, PD3, "float"), "f32x", 21, order="reversed"),
+    # ---- away from the default parameters (tests/param_sets.py): one row per dispatch unit and set.  A: inexact 1 / delta_t,
+    #      T_min no multiple of delta_t; B: up to 238 samples per piece (M <= 21); C: T_min = 4 delta_t, a zero weight
+    case("A-f64-w1-M21", k3(2, "double", 1, PD3), "f64", 21, cfg="A"),
+    case("B-f64-w1-M3", k3(1, "double", 1, PD3), "f64", 3, cfg="B"),
+    case("C-f64-w1-M41", k3(3, "double", 1, WL), "f64", 41, cfg="C"),
+    case("B-f64-w2-M21", k3(2, "double", 2, PD3), "f64", 21, waves=2, cfg="B"),
+    case("B-f32-w1-M21", k3(2, "float", 1, PD3), "f32", 21, cfg="B"),
+    case("A-f32-w1-M64", k3(4, "float", 1, WL), "f32", 64, cfg="A"),
+    case("A-f32-w2-M41", k3(3, "float", 2, WL), "f32", 41, waves=2, cfg="A"),
+    case("B-f32x-M3", k3(1, "float", 2, PD3, "float"), "f32x", 3, cfg="B"),
+    case("A-f32x-M21", k3(2, "float", 2, PD3, "float"), "f32x", 21, cfg="A"),
+    case("C-f32x-M34", k3(3, "float", 2, WL, "float"), "f32x", 34, cfg="C"),
+    case("B-f16-f32x-M21", k3(2, "float", 2, PD3, "float", elem="__half"), "f32x", 21, store="f16", cfg="B"),
+    case("A-2d-f64-w1-M21", k2(2, 1, "double", 1, PD2), "f64", 21, map="2d", D=2, cfg="A"),
+    case("B-2d-f32-w1-M3", k2(2, 1, "float", 1, PD2), "f32", 3, map="2d", D=2, cfg="B"),
+    case("B-2d-f32x-M21", k2(2, 1, "float", 2, PD2, "float"), "f32x", 21, map="2d", D=2, cfg="B"),
 ]
 
 
@@ -224,7 +244,12 @@ def _traced_run(world, c):
     else:
         lo, hi = np.array([1.0, -5.0, 1.0]), np.array([11.5, 5.0, 10.0])
     head, tail, wp, ts = _requests(rng, M, D, lo, hi)
-    bp = npa.BatchPlanner(ctx=ctx, sample_dtype=mode, stale_T=c["stale_T"], waves_per_simd=c["waves"])
+    config = None
+    if c["cfg"] is not None:
+        # (the default rows' 0.8 .. 2.5 s are no valid durations at every set: the set's own range, drawn after the rest)
+        ts = ps.durations(rng, c["cfg"], (B, M), *ps.RUN_DUR[c["cfg"]])
+        config = ps.planner_config(c["cfg"])
+    bp = npa.BatchPlanner(config=config, ctx=ctx, sample_dtype=mode, stale_T=c["stale_T"], waves_per_simd=c["waves"])
     bp.flags |= c["flags"]
     bp._sync()
     x0 = bp.pack_x(wp, ts)
@@ -320,7 +345,8 @@ def _check_run(args):
     near = []
     for k in np.flatnonzero(ok & ~same_ns):
         q = T[k] / cfg.delta_t
-        near.append(float(np.abs(q - np.round(q)).min()))
+        e = np.abs(q - np.round(q))
+        near.append((float(e.min()), float(q[np.argmin(e)])))
     out["ns_diff"], out["near_edge"] = len(near), near
     out["iter_monotone"] = bool(np.all(np.diff(it_d) >= 0))
     # ---- end of the run
@@ -359,7 +385,7 @@ def test_every_evaluation_of_every_kernel_is_an_oracle_evaluation(world, c):
     last_rel = [o["last_rel"] for o in runs if o["last_rel"] is not None]
     final_rel = [o["final_rel"] for o in runs if o["final_rel"] is not None]
     q = lambda a: [float(np.quantile(a, p)) for p in (0.5, 0.9, 0.99, 0.999, 1.0)] if len(a) else []
-    report = dict(case=c["name"], inst=c["inst"], mode=mode, M=M, D=D, evaluations=n_eval,
+    report = dict(case=c["name"], inst=c["inst"], mode=mode, M=M, D=D, params=c["cfg"] or "default", evaluations=n_eval,
                   nfev=[int(o["E"]) for o in runs], status=[o["status"] for o in runs],
                   value_rel_err_quantiles_50_90_99_999_max=q(rel_f), grad_err_over_run_scale_quantiles=q(rel_g),
                   grad_err_over_own_max_quantiles=q(rel_g_own),
@@ -398,7 +424,10 @@ def test_every_evaluation_of_every_kernel_is_an_oracle_evaluation(world, c):
     # sample counts: the oracle's int(T / delta_t) at every evaluation (the all-fp32 mode: counted boundary cases)
     # (the share: test_gpu_replay bounds it at 1e-3 on cfg2's requests; the random boundary states here drive some durations
     #  onto T_min = 5 delta_t, where T / delta_t is an integer at every evaluation of the line search: 1 %)
-    assert ns_diff <= 1e-2 * n_eval and all(e <= 1e-5 for e in near_edge), (name, ns_diff, near_edge)
+    # (the boundary test: an fp32 T * (1 / delta_t) carries a RELATIVE error, so the distance of q = T / delta_t to an integer
+    #  is held to 2e-7 * max(q, 50) -- 1e-5 for every q the default parameters can give, q <= 50, and in proportion beyond:
+    #  set B reaches q = 238)
+    assert ns_diff <= 1e-2 * n_eval and all(e <= 2e-7 * max(q_, 50.0) for e, q_ in near_edge), (name, ns_diff, near_edge)
     if mode != "f32x":
         assert ns_diff == 0, (name, ns_diff)
     # ---- end of every run
