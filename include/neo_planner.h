@@ -588,6 +588,40 @@ int neo_plan_merge_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset,
                        int32_t *nit, int32_t *nfev, int32_t *status, int32_t *attempts, int64_t *nit_total,
                        int32_t *solved, int32_t *failed, int32_t *n_failed, int32_t *bad_scene);
 
+/* ---- batched depth camera ---------------------------------------------------
+ * B pinhole depth images of box scenes in one call: neo_planner_amd/initializer.py raycast_depth, the sensor in front
+ * of the initializer network (traj_planner/record_planner.py:16-18 scales the image to uint8 by its maximum), for B
+ * requests that each see their own scene from their own pose.
+ *   boxes[NB][6]             doubles, lo xyz then hi xyz, the boxes of all scenes back to back
+ *   box_begin[n_scenes + 1]  scene s owns the boxes box_begin[s] .. box_begin[s + 1]; at most NEO_DEPTH_MAX_BOXES each
+ *   scene_index[B]           the scene of each request, or NULL: every request sees scene 0
+ *   pose[B][5]               eye x y z, cos(yaw), sin(yaw): the caller takes the cosine and sine (the device calls no
+ *                            trigonometric function)
+ *   focal_px                 (width / 2) / tan(hfov / 2), in pixels; max_range in metres
+ *   depth_m[B][height][width]   float32 metres along the optical axis, clipped to [0, max_range]
+ *   depth_u8[B][height][width]  (uint8)(depth / max(depth_max, 1e-9f) * 255.0f), the network's input; may be NULL
+ *   depth_max[B]                float32 maximum of each image; may be NULL
+ * Camera frame: x forward, y left, z up; the ground is the plane z = 0.  Every ray is computed in fp32 with each
+ * product rounded on its own (tests/depth_oracle_np.py restates it in NumPy, bit for bit), the pixel coordinates and
+ * the boxes' corners relative to the eye in fp64 rounded once.  An image's bytes depend on its own pose, its scene's
+ * boxes and the camera only: not on B, its place in the batch, the packing of the scenes or the launch.
+ * NEO_ERR_INVALID before anything is copied or launched: B < 1, width or height outside 1..4096, focal_px or max_range
+ * not finite or <= 0, n_scenes < 1, a NULL boxes / box_begin / pose / depth_m; host form also: box_begin not
+ * non-decreasing from 0, a scene with more than NEO_DEPTH_MAX_BOXES boxes, a scene_index outside 0 .. n_scenes - 1.
+ * The _dev form cannot read its index arrays: a request whose scene index (or box range) is out of range gets depth_m
+ * NaN, depth_u8 0 and depth_max NaN, and reads no box. */
+#define NEO_DEPTH_MAX_BOXES 1024
+int neo_depth_render_batch(neo_ctx *ctx, int width, int height, double focal_px, double max_range, const double *boxes,
+                           const int32_t *box_begin, int n_scenes, const int32_t *scene_index, int B, const double *pose,
+                           float *depth_m, uint8_t *depth_u8, float *depth_max);
+int neo_depth_render_batch_dev(neo_ctx *ctx, int width, int height, double focal_px, double max_range,
+                               const double *boxes, const int32_t *box_begin, int n_scenes, const int32_t *scene_index,
+                               int B, const double *pose, float *depth_m, uint8_t *depth_u8, float *depth_max);
+/* diagnostics: optional DEVICE counter (64-bit, the caller zeroes it) to which the next render passes add, per tile, the
+ * boxes left after culling times the tile's pixels: box tests per ray = counter / (B * height * width).  NULL switches it
+ * off. */
+int neo_depth_box_test_counter(neo_ctx *ctx, uint64_t *dev_count);
+
 /* ---- timing of the device work (bench.py) ----------------------------------
  * When enabled, every kernel launch of the named family is bracketed by HIP events on
  * the context stream; neo_profile_read returns launches and summed milliseconds. */

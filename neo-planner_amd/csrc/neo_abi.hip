@@ -452,6 +452,7 @@ int neo_ctx_destroy(neo_ctx *c) {
   if (c->stream != c->home_stream) hipStreamSynchronize(c->home_stream);
   drain_profile(c);
   geo_release(c);
+  depth_release(c);
   for (auto &kv : c->maps)
     if (kv.second.data) hipFree(kv.second.data);
   if (c->order_buf) hipFree(c->order_buf);
@@ -1080,6 +1081,75 @@ int neo_audit_traj_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int
                                 st.dev(fh), st.dev(ft), hz, weights3, st.dev(fa), st.dev(fcnt), st.dev(ffl));
   if (rc) return rc;
   return st.download();
+}
+
+// ---- batched depth camera (neo_planner_amd/initializer.py raycast_depth for B requests; kernels: neo_depth.hpp)
+// the argument checks both forms make before anything is copied or launched (context unlocked)
+static int depth_check(neo_ctx *c, int width, int height, double focal_px, double max_range, const double *boxes,
+                       const int32_t *box_begin, int n_scenes, int B, const double *pose, const float *depth_m) {
+  if (!c) return NEO_ERR_INVALID;
+  if (B < 1) return fail_locked(c, NEO_ERR_INVALID, "depth: B must be >= 1");
+  if (width < 1 || width > 4096 || height < 1 || height > 4096)
+    return fail_locked(c, NEO_ERR_INVALID, "depth: width and height must be in 1..4096");
+  if (!std::isfinite(focal_px) || !(focal_px > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "depth: focal_px must be finite and > 0");
+  if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "depth: max_range must be finite and > 0");
+  if (n_scenes < 1) return fail_locked(c, NEO_ERR_INVALID, "depth: n_scenes must be >= 1");
+  if (!boxes || !box_begin || !pose || !depth_m) return fail_locked(c, NEO_ERR_INVALID, "depth: null buffer");
+  return NEO_OK;
+}
+
+int neo_depth_render_batch_dev(neo_ctx *c, int width, int height, double focal_px, double max_range, const double *boxes,
+                               const int32_t *box_begin, int n_scenes, const int32_t *scene_index, int B,
+                               const double *pose, float *depth_m, uint8_t *depth_u8, float *depth_max) {
+  int rc = depth_check(c, width, height, focal_px, max_range, boxes, box_begin, n_scenes, B, pose, depth_m);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  return depth_render(c, DepthCall{width, height, focal_px, max_range, boxes, box_begin, n_scenes, scene_index, B, pose,
+                                   depth_m, depth_u8, depth_max});
+}
+
+int neo_depth_render_batch(neo_ctx *c, int width, int height, double focal_px, double max_range, const double *boxes,
+                           const int32_t *box_begin, int n_scenes, const int32_t *scene_index, int B, const double *pose,
+                           float *depth_m, uint8_t *depth_u8, float *depth_max) {
+  int rc = depth_check(c, width, height, focal_px, max_range, boxes, box_begin, n_scenes, B, pose, depth_m);
+  if (rc) return rc;
+  // what the device form cannot read on the host
+  if (box_begin[0] != 0) return fail_locked(c, NEO_ERR_INVALID, "depth: box_begin must start at 0");
+  for (int s = 0; s < n_scenes; ++s) {
+    if (box_begin[s + 1] < box_begin[s]) return fail_locked(c, NEO_ERR_INVALID, "depth: box_begin must be non-decreasing");
+    if (box_begin[s + 1] - box_begin[s] > NEO_DEPTH_MAX_BOXES)
+      return fail_locked(c, NEO_ERR_INVALID, "depth: a scene has more than NEO_DEPTH_MAX_BOXES boxes");
+  }
+  if (scene_index)
+    for (int b = 0; b < B; ++b)
+      if (scene_index[b] < 0 || scene_index[b] >= n_scenes)
+        return fail_locked(c, NEO_ERR_INVALID, "depth: a scene_index is outside 0 .. n_scenes - 1");
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  const size_t bs = (size_t)B, hw = (size_t)width * height, nbox = (size_t)box_begin[n_scenes];
+  HostStage st(c, 0);
+  const auto fb = st.in(nbox ? boxes : nullptr, nbox * 6, 6);  // (without any box: a valid pointer nothing is read from)
+  const auto fbb = st.in(box_begin, (size_t)n_scenes + 1);
+  const auto fsi = st.in(scene_index, bs);
+  const auto fp = st.in(pose, bs * 5);
+  const auto fm = st.out(depth_m, bs * hw);
+  const auto fu = st.out(depth_u8, depth_u8 ? bs * hw : 0);
+  const auto fx = st.out(depth_max, bs);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_depth_render_batch_dev(c, width, height, focal_px, max_range, st.dev(fb), st.dev(fbb), n_scenes,
+                                  scene_index ? st.dev(fsi) : nullptr, B, st.dev(fp), st.dev(fm),
+                                  depth_u8 ? st.dev(fu) : nullptr, st.dev(fx));
+  if (rc) return rc;
+  return st.download();
+}
+
+int neo_depth_box_test_counter(neo_ctx *c, uint64_t *dev_count) {
+  if (!c) return NEO_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  c->depth.box_tests = reinterpret_cast<unsigned long long *>(dev_count);
+  return NEO_OK;
 }
 
 // ---- fleet replan loop (ros_node/traj_planner_node.py:390-578; kernels: neo_fleet.hpp)

@@ -46,6 +46,15 @@ struct GeoState {
   std::vector<char> table_host;  // what `table` holds
 };
 
+// the depth camera's device state (neo_disp_depth.hip): the pixel tables of a call, and the images' maxima when the
+// caller keeps none
+struct DepthState {
+  float *uv = nullptr;          // u (padded) then v of the call in flight
+  unsigned *max_bits = nullptr;
+  size_t max_cap = 0;           // images `max_bits` has room for
+  unsigned long long *box_tests = nullptr;  // optional device counter (neo_depth_box_test_counter)
+};
+
 struct ProfileSlot {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
   int64_t launches = 0;
@@ -94,6 +103,7 @@ struct neo_ctx {
   int edt_flags = 0;                    // NEO_EDT_* (neo_esdf_build_config)
   unsigned long long map_serial = 0;    // MapEntry::version source
   neo::GeoState geo;
+  neo::DepthState depth;
 };
 
 namespace neo {
@@ -308,6 +318,24 @@ int geo_prune(neo_ctx *c, int scene_id, int B, const int *slots, const double *p
               double *key_pts);
 void geo_release(neo_ctx *c);             // frees every geo buffer (neo_ctx_destroy)
 void geo_forget(neo_ctx *c, int scene_id);  // frees the scene's mask (map drop)
+
+// neo_depth_render_batch_dev (neo_disp_depth.hip, kernels in neo_depth.hpp): the tables, the render pass and, with
+// depth_u8, the normalise pass, on the context's stream; every pointer is a device array, the arguments are checked
+struct DepthCall {
+  int W, H;
+  double focal, max_range;
+  const double *boxes;
+  const int *box_begin;
+  int n_scenes;
+  const int *scene_index;  // or NULL
+  int B;
+  const double *pose;
+  float *depth_m;
+  unsigned char *depth_u8;  // or NULL
+  float *depth_max;         // or NULL
+};
+int depth_render(neo_ctx *c, const DepthCall &a);
+void depth_release(neo_ctx *c);  // frees the camera's buffers (neo_ctx_destroy)
 
 // the map kernels' launches (neo_disp_esdf.hip, kernels in neo_esdf.hpp), on the context's stream.  Every pointer is a
 // device array the caller owns -- the C ABI carves the work arrays from the context's scratch -- and nothing is

@@ -11,7 +11,8 @@ from .esdf import ESDF, ESDF3D  # noqa: F401
 from .planner import BatchPlanner, MinJerkPlanner, PlannerConfig  # noqa: F401
 from .geo import GeoPlanner  # noqa: F401
 from .fleet import FleetReplanLoop  # noqa: F401
+from .depth import DepthCamera  # noqa: F401
 # the initializer network (torch) is imported on demand: `from neo_planner_amd import initializer`
 
 __all__ = ["Context", "NeoError", "default_context", "ESDF", "ESDF3D", "BatchPlanner", "MinJerkPlanner",
-           "PlannerConfig", "GeoPlanner", "FleetReplanLoop"]
+           "PlannerConfig", "GeoPlanner", "FleetReplanLoop", "DepthCamera"]

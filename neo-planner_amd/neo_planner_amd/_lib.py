@@ -32,6 +32,7 @@ NEO_GEO_FLAG_BAD_SCENE = 16
 NEO_FLEET_FLAG_TARGET_CAPPED, NEO_FLEET_FLAG_CMD_FULL, NEO_FLEET_FLAG_BAD_SCENE, NEO_FLEET_FLAG_SPLICE_FAILED = 1, 2, 4, 8
 NEO_FLEET_FLAG_ABANDONED = 16
 NEO_BATCH_MAX_CANDIDATES = 8       # neo_batch_*: candidates a request
+NEO_DEPTH_MAX_BOXES = 1024         # neo_depth_*: boxes a scene
 
 # every symbol include/neo_planner.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -51,7 +52,8 @@ EXPORTS = [
     "neo_geo_workspace_budget", "neo_fleet_target_batch", "neo_fleet_target_batch_dev", "neo_fleet_advance_dev",
     "neo_fleet_splice_dev", "neo_fleet_audit_batch", "neo_fleet_audit_batch_dev", "neo_batch_candidates",
     "neo_batch_candidates_dev", "neo_batch_select", "neo_batch_select_dev", "neo_plan_guess", "neo_plan_guess_dev",
-    "neo_plan_merge", "neo_plan_merge_dev",
+    "neo_plan_merge", "neo_plan_merge_dev", "neo_depth_render_batch", "neo_depth_render_batch_dev",
+    "neo_depth_box_test_counter",
 ]
 
 
@@ -133,6 +135,9 @@ def load():
     L.neo_plan_guess_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i] + [c_p] * 11
     L.neo_plan_merge.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 18
     L.neo_plan_merge_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 18
+    L.neo_depth_render_batch.argtypes = [c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_i, c_p, c_i] + [c_p] * 4
+    L.neo_depth_render_batch_dev.argtypes = [c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_i, c_p, c_i] + [c_p] * 4
+    L.neo_depth_box_test_counter.argtypes = [c_p, c_p]
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]

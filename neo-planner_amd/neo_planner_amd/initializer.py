@@ -104,6 +104,36 @@ def form_nn_input(depth_img, drone_state, des_pos_z, plan_init_state, target_sta
     return depth_norm, motion
 
 
+def form_nn_input_batch(drone_pos, drone_vel, local_vel, yaw, des_pos_z, start, target):
+    """form_nn_input's motion vector for B requests whose attitude is Quat.from_yaw(yaw): drone_pos, drone_vel,
+    local_vel (B, 3), yaw (B,), start (B, 2, 2) = the plan's initial position and velocity (x, y), target (B, 2, 2) =
+    the target's.  Returns motion (B, 24), R (B, 3, 3) body -> world, global_pos (B, 3) -- what
+    BatchInitializer.warm_start takes."""
+    pos = np.asarray(drone_pos, dtype=np.float64).reshape(-1, 3)
+    vel = np.asarray(drone_vel, dtype=np.float64).reshape(-1, 3)
+    lv = np.asarray(local_vel, dtype=np.float64).reshape(-1, 3)
+    yaw = np.asarray(yaw, dtype=np.float64).reshape(-1)
+    start = np.asarray(start, dtype=np.float64)
+    target = np.asarray(target, dtype=np.float64)
+    B = pos.shape[0]
+    w, z = np.cos(yaw / 2), np.sin(yaw / 2)
+    nrm = np.sqrt(w * w + z * z)                                        # (Quat normalises)
+    w, z = w / nrm, z / nrm
+    R = np.zeros((B, 3, 3))
+    R[:, 0, 0] = R[:, 1, 1] = 1 - 2 * (z * z)
+    R[:, 0, 1] = -2 * z * w
+    R[:, 1, 0] = 2 * z * w
+    R[:, 2, 2] = 1.0
+
+    def body(p_xy, z_value, origin):
+        v3 = np.concatenate([p_xy, np.full((B, 1), float(z_value))], axis=1) - origin
+        return np.einsum("bji,bj->bi", R, v3)                           # R^T v: the inverse rotation
+
+    motion = np.concatenate([lv, R.reshape(B, 9), body(start[:, 0], des_pos_z, pos), body(start[:, 1], 0.0, vel),
+                             body(target[:, 0], des_pos_z, pos), body(target[:, 1], 0.0, vel)], axis=1)
+    return motion, R, pos.copy()
+
+
 # --------------------------------------------------------------------------- network
 CONV_IMPL = "gemm"      # "gemm": im2col + one GEMM per convolution (matrix cores); "miopen": nn.Conv2d as is
 
@@ -346,6 +376,16 @@ class BatchInitializer:
         return self.net.image_features(img.reshape(1, 1, *img.shape[-2:]))
 
     @torch.no_grad()
+    def image_features(self, depth_u8, chunk=64):
+        """features (B, 24) of B images (B, H, W), a device tensor or an array (DepthCamera's depth_u8): one feature per
+        request for `warm_start`.  The backbone runs `chunk` images at a time."""
+        img = torch.as_tensor(depth_u8) if not torch.is_tensor(depth_u8) else depth_u8
+        img = img.reshape(-1, 1, *img.shape[-2:])
+        out = [self.net.image_features(img[b0:b0 + chunk].to(self.device, dtype=torch.float32))
+               for b0 in range(0, img.shape[0], max(1, int(chunk)))]
+        return torch.cat(out, dim=0)
+
+    @torch.no_grad()
     def warm_start(self, scene_feature, motion, attitude_R, global_pos, clamp_ts=True):
         """motion [B,24], attitude_R [B,3,3] (body->world), global_pos [B,3]  ->
         int_wpts [B,2,2] (world, z dropped), ts [B,3].  An untrained or extrapolating network can
@@ -362,3 +402,50 @@ class BatchInitializer:
             eps = 1e-3 * (self.T_max - self.T_min)
             ts = ts.clamp(self.T_min + eps, self.T_max - eps)
         return world[:, :, :2].transpose(1, 2).contiguous(), ts.contiguous()
+
+
+class BatchNeoPlanner:
+    """NeoPlanner.enhanced_traj_plan (neo_planner.py:10-51) for B requests: every request's own depth image from the
+    batched camera (depth.DepthCamera), the motion vectors, the initializer network, and the warm starts into
+    BatchPlanner.plan.  batch_planner: a BatchPlanner; initializer: a BatchInitializer; camera: a DepthCamera of the
+    network's image size."""
+
+    def __init__(self, batch_planner, initializer, camera, des_pos_z=2.0):
+        net = initializer.net
+        if (camera.height, camera.width) != (net.img_height, net.img_width):
+            raise ValueError("BatchNeoPlanner: the camera renders %d x %d, the network takes %d x %d"
+                             % (camera.height, camera.width, net.img_height, net.img_width))
+        self.bp, self.init, self.camera, self.des_pos_z = batch_planner, initializer, camera, float(des_pos_z)
+        self.chunk = 64          # images per render launch and backbone pass
+
+    def warm_start(self, scenes, drone_pos, drone_vel, local_vel, yaw, head, tail, scene_index=None):
+        """scenes: the camera's scenes (DepthCamera.pack_scenes), scene_index (B,) the scene each request sees (None:
+        scene 0); the camera sits at drone_pos (B, 3) looking along yaw (B,); head, tail (B, >= 2, 2): the plan's initial
+        and target position and velocity.  Returns int_wpts (B, 2, 2) and ts (B, 3) as float64 arrays and the images
+        depth_u8 (B, H, W) (a device tensor when the initializer runs on the GPU)."""
+        head = np.asarray(head, dtype=np.float64)
+        tail = np.asarray(tail, dtype=np.float64)
+        motion, R, pos = form_nn_input_batch(drone_pos, drone_vel, local_vel, yaw, self.des_pos_z, head[:, :2], tail[:, :2])
+        cam = self.camera
+        if self.init.device.type == "cuda":
+            dev = self.init.device
+            boxes, begin = cam.pack_scenes(scenes)
+            if boxes.shape[0] == 0:
+                boxes = np.zeros((1, 6))
+            sidx = None if scene_index is None else torch.as_tensor(np.ascontiguousarray(scene_index, dtype=np.int32), device=dev)
+            depth_u8 = cam.render_dev(torch.as_tensor(boxes, device=dev), torch.as_tensor(begin, device=dev),
+                                      torch.as_tensor(cam.poses(pos, yaw), device=dev), sidx, chunk=self.chunk,
+                                      want_m=False)["depth_u8"]
+        else:
+            depth_u8 = cam.render(scenes, pos, yaw, scene_index)["depth_u8"]
+        feat = self.init.image_features(depth_u8, chunk=self.chunk)
+        wp, ts = self.init.warm_start(feat, motion, R, pos)
+        return wp.cpu().numpy(), ts.cpu().numpy(), depth_u8
+
+    def plan(self, map, scenes, drone_pos, drone_vel, local_vel, yaw, head, tail, scene_index=None, **plan_kw):
+        """render -> motion -> network -> BatchPlanner.plan(map, head, tail, int_wpts=, ts=, **plan_kw).  Returns plan's
+        dict plus the network's warm start `int_wpts0`, `ts0` and the images `depth_u8`."""
+        wp, ts, depth_u8 = self.warm_start(scenes, drone_pos, drone_vel, local_vel, yaw, head, tail, scene_index)
+        out = self.bp.plan(map, head, tail, int_wpts=wp, ts=ts, **plan_kw)
+        out["int_wpts0"], out["ts0"], out["depth_u8"] = wp, ts, depth_u8
+        return out
