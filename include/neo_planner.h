@@ -159,6 +159,22 @@ int neo_esdf_upload_2d(neo_ctx *ctx, int scene_id, const double *dist, const dou
 int neo_esdf_build_2d(neo_ctx *ctx, int scene_id, const int8_t *occupancy, int width, int height,
                       double resolution, double origin_x, double origin_y, double *out_dist,
                       double *out_grad_x, double *out_grad_y);
+/* neo_esdf_build_2d for n maps of one size whose occupancy is already on the device (onboard maps: one per mission):
+ * scene_ids[n] and origins[n][2] are HOST arrays, occupancy[n][height][width] a DEVICE array, the maps back to back.
+ * The same kernels with the maps in the grid -- the column sweep, then the exhaustive row pass up to 512 x 512 and the
+ * row sweep beyond; all forms give the same integers -- and so the same records, bit for bit, as n neo_esdf_build_2d
+ * calls; they are written straight into each scene's record buffer and nothing is copied back.  A scene that already holds a 2-D map of this width and height is rewritten in place:
+ * with an unchanged origin and resolution its descriptor, the map table, every neo_scene_slot value and a caller's
+ * resident slot arrays stay valid (its version is bumped as by neo_esdf_build_2d); any other scene gets a new buffer
+ * and the table is rebuilt at its next use.  The call waits for the device once before the first record is overwritten
+ * (when any map is rewritten) and for the context's stream once at the end: per call, not per map.
+ * Device memory: 12 bytes a cell and map of scratch (beyond 512 x 512: 24 bytes and 8 a row), carved once from the
+ * context's scratch for as many maps as fit 1 GiB -- 993 maps of 300 x 300 -- and reused by the passes of a larger batch.
+ * NEO_ERR_INVALID: n < 0, a NULL buffer with n > 0, width or height < 1, more than 2^28 cells, a resolution that is not
+ * finite and > 0, a scene id listed twice.  A call that fails on the device leaves the scenes it was rewriting without
+ * a map. */
+int neo_esdf_build_2d_batch_dev(neo_ctx *ctx, const int32_t *scene_ids, int n, const int8_t *occupancy, int width,
+                                int height, double resolution, const double *origins);
 /* 3-D distance field for NEO_INTERP_TRILINEAR_3D.  dist is [nz][ny][nx] of src_dtype
  * (host pointer, or device pointer when src_is_device != 0); it is stored on the device
  * as store_dtype in `layout`. */
@@ -428,6 +444,15 @@ int neo_fleet_target_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_
 int neo_fleet_advance_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
                           const int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index, int step, int ahead,
                           double *cur_pos, double *head);
+/* the camera pose a mission senses from (onboard maps), one lane per mission: pose[B][5] = cur_pos x, y, eye_z, c, s
+ * as neo_depth_render_batch takes it.  (c, s) is the unit vector of the last step of the command array, position of
+ * row cmd_index minus that of the row before it (:685-687 without the arctan2 round trip); where there is no such step
+ * (cmd_index < 1, nothing planned yet) or it has no length, the unit vector from cur_pos to goal; (1, 0) on the goal.
+ * Two squares, their sum, one square root and two divisions, each rounded on its own, so NumPy gives the same bits.
+ * Device pointers only. */
+int neo_fleet_pose_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                       const int32_t *cmd_len, const int32_t *cmd_index, const double *cur_pos, const double *goal,
+                       double eye_z, double *pose);
 /* the splice of replan (:574-578), one wavefront per mission, for the launched missions with solved[b] != 0 (solved: a
  * device array [B], NULL = all launched): the trajectory x[B][n], head[B][3][2], tail[B][3][2] of M pieces is solved as
  * neo_eval_traj_batch solves it and its rows k < count = len(np.arange(0, sum(T), 1 / hz)) -- the rows of
@@ -621,6 +646,60 @@ int neo_depth_render_batch_dev(neo_ctx *ctx, int width, int height, double focal
  * boxes left after culling times the tile's pixels: box tests per ray = counter / (B * height * width).  NULL switches it
  * off. */
 int neo_depth_box_test_counter(neo_ctx *ctx, uint64_t *dev_count);
+
+/* ---- onboard mapping (launch/map_server_onboard.launch) ---------------------------------
+ * The depth images of B missions into B 2-D occupancy grids of their own: what octomap_server (0.1 m leaves,
+ * sensor_model/max_range 6.0, projected_map of the band occupancy_min_z .. occupancy_max_z) gives ESDF.occupancy_map_cb
+ * on the vehicle, as a fixed model: octomap's scan insertion (within a scan a hit wins over a miss, clamped log-odds,
+ * occupied from probability 0.5) projected to 2-D.  tests/onboard_oracle_np.py is the model in NumPy; the kernel equals
+ * it bit for bit.  Per mission and scan, with the ray directions of neo_depth_render_batch widened to fp64 --
+ * dx_j = c + u_j s, dy_j = s - u_j c, dz_i = -v_i, each fp32 product and sum rounded on its own -- and every further
+ * operation fp64, rounded on its own:
+ *   cell of a point  fx = (px - ox) / res, fy = (py - oy) / res; outside the grid, and ignored, unless 0 <= fx < grid_w
+ *                    and 0 <= fy < grid_h; else cell (int)fy * grid_w + (int)fx (map_server/esdf.py:61-62);
+ *   hit              pixel (i, j) of depth d when d < sensor_range and z_lo <= ez + d dz_i <= z_hi: the cell of
+ *                    (ex + d dx_j, ey + d dy_j).  A NaN depth marks nothing;
+ *   passed           for the samples t_n = n (res / 2), n < ceil(sensor_range / (res / 2)), with t_n < min(d, sensor_range)
+ *                    and z_lo <= ez + t_n dz_i <= z_hi: the cell of (ex + t_n dx_j, ey + t_n dy_j);
+ *   update           the scan's marks are the union over its pixels, then every marked cell is updated once, from L0 = 0
+ *                    if it was never updated: a hit cell to min(L0 + hit, hi), a cell passed but not hit to
+ *                    max(L0 + miss, lo).  Unmarked cells keep their state.
+ * Log-odds are integers in units of 0.05 (octomap's 0.7 / 0.4 / 0.12 / 0.97 are hit 17, miss -8, lo -40, hi 70),
+ * stored as int8 with -128 = never updated.
+ *   subset[n_subset]   DEVICE (host form: host) mission indices, NULL = all B; n = n_subset or B missions are launched
+ *   depth_m[n][height][width], pose[n][5]   the image and the pose (neo_depth_render_batch's) of each LAUNCHED mission,
+ *                      by position in the subset -- a caller renders only the missions that sense.  (c, s) must be a
+ *                      unit vector to fp32 rounding: marks further from the eye than a unit heading reaches are dropped
+ *   width, height, focal_px, max_range   the camera of neo_depth_render_batch; max_range < sensor_range is an error (a
+ *                      depth clipped below sensor_range would read as a hit)
+ *   origins[B][2]      the grids' origins, by mission; grid_w, grid_h, res are shared
+ *   logodds[B][grid_h][grid_w]    int8, in and out, by mission (all -128 before the first scan)
+ *   occupancy[B][grid_h][grid_w]  int8 as nav_msgs/OccupancyGrid.data: 100 where L >= 0, 0 where updated and L < 0,
+ *                      -1 never updated.  Only the cells a scan marks are written: hand in the previous call's array
+ *                      (all -1 before the first scan)
+ *   changed[B]         1 where the set of cells with value 100 changed in this scan, else 0 (launched missions only)
+ * A mission outside the subset keeps every byte.  Results do not depend on the order of pixels, launches or missions.
+ * A mission may appear in a subset once: two workgroups on one mission would update its grids unordered (the host
+ * form rejects a repeated entry, the _dev form cannot see it).
+ * One workgroup per mission holds two bits a cell of the window a scan can touch in LDS: (2 h + 1)^2 cells around the
+ * eye's cell, h = ceil(sensor_range sqrt(1 + u_max^2) (1 + 1e-6) / res) + 1 with u_max the outermost column's |u| (a
+ * point lies d along the axis and d u across it) -- 169^2 cells for the 87 degree camera at the defaults.
+ * NEO_ERR_INVALID before anything is copied or launched, with a message: B outside 1 .. 2^20, a bad subset size, width
+ * or height outside 1..4096, focal_px, res or sensor_range not finite or <= 0, max_range < sensor_range, a band that is
+ * not finite or has z_lo > z_hi, grid_w or grid_h < 1 or more than 2^30 cells, log-odds outside -127 <= lo <= hi <= 127,
+ * 0 <= hit <= 127, -127 <= miss <= 0, a NULL buffer, a window that does not fit the 64 KB of LDS of a workgroup; host
+ * form also: a subset entry outside 0 .. B - 1 (the _dev form skips it) or listed twice. */
+int neo_onboard_integrate_batch(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const float *depth_m,
+                                const double *pose, int width, int height, double focal_px, double max_range, int grid_w,
+                                int grid_h, double res, const double *origins, double sensor_range, double z_lo,
+                                double z_hi, int hit, int miss, int lo, int hi, int8_t *logodds, int8_t *occupancy,
+                                int32_t *changed);
+/* the same with DEVICE pointers, asynchronous on the context's stream */
+int neo_onboard_integrate_batch_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const float *depth_m,
+                                    const double *pose, int width, int height, double focal_px, double max_range,
+                                    int grid_w, int grid_h, double res, const double *origins, double sensor_range,
+                                    double z_lo, double z_hi, int hit, int miss, int lo, int hi, int8_t *logodds,
+                                    int8_t *occupancy, int32_t *changed);
 
 /* ---- timing of the device work (bench.py) ----------------------------------
  * When enabled, every kernel launch of the named family is bracketed by HIP events on

@@ -610,6 +610,119 @@ int neo_esdf_build_2d(neo_ctx *c, int scene_id, const int8_t *occ, int W, int H,
   return NEO_OK;
 }
 
+// Scratch of neo_esdf_build_2d_batch_dev, carved once for a pass of `chunk` maps: per map g (4 bytes a cell) and dist
+// (8), beyond 512 x 512 also the sweeps' v (4) and z (8 (W + 1) H); plus the chunk's record pointers.  A pass takes as
+// many maps as fit kBatchBuildScratch (and grid.y / grid.z): 12 bytes a cell -- 1.08 MB for 300 x 300, 993 maps a pass.
+static const size_t kBatchBuildScratch = (size_t)1 << 30;
+static size_t batch_build_bytes_per_map(int W, int H, bool sweeps) {
+  const size_t ncell = (size_t)W * H;
+  size_t per = ncell * (sizeof(int) + sizeof(double)) + 512;
+  if (sweeps) per += ncell * sizeof(int) + (size_t)H * (W + 1) * sizeof(double) + 512;
+  return per;
+}
+
+int neo_esdf_build_2d_batch_dev(neo_ctx *c, const int32_t *scene_ids, int n, const int8_t *occ, int W, int H, double res,
+                                const double *origins) {
+  if (!c) return NEO_ERR_INVALID;
+  if (n < 0 || W < 1 || H < 1 || !(res > 0.0) || !std::isfinite(res))
+    return fail_locked(c, NEO_ERR_INVALID, "batch build: n >= 0, width and height >= 1, resolution finite and > 0");
+  if (n == 0) return NEO_OK;
+  if (!scene_ids || !occ || !origins) return fail_locked(c, NEO_ERR_INVALID, "batch build: null buffer");
+  if ((size_t)W * H > (size_t)1 << 28) return fail_locked(c, NEO_ERR_INVALID, "batch build: more than 2^28 cells a map");
+  {
+    std::vector<int32_t> ids(scene_ids, scene_ids + n);
+    std::sort(ids.begin(), ids.end());
+    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end())
+      return fail_locked(c, NEO_ERR_INVALID, "batch build: a scene id is listed twice");
+  }
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const size_t ncell = (size_t)W * H;
+  const bool sweeps = W > 512 || H > 512;
+  const size_t per = batch_build_bytes_per_map(W, H, sweeps);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, kBatchBuildScratch / per, (size_t)65535}));
+  int rc = ensure_scratch(c, (size_t)chunk * (per + sizeof(void *)) + 4096);
+  if (rc) return rc;
+  // the record buffer of every scene: its own where it already holds a 2-D map of this size (rewritten in place, the
+  // descriptor -- and with it the map table and every slot -- usually unchanged), a new one otherwise
+  std::vector<double4 *> recs((size_t)n);
+  std::vector<char> fresh((size_t)n, 0);
+  bool any_reuse = false;
+  for (int k = 0; k < n; ++k) {
+    auto it = c->maps.find(scene_ids[k]);
+    if (it != c->maps.end() && it->second.kind == 0 && it->second.data && it->second.m2.W == W && it->second.m2.H == H) {
+      recs[k] = static_cast<double4 *>(it->second.data);
+      any_reuse = true;
+    }
+  }
+  // nothing on the device may still read a buffer that is rewritten: one wait for the whole call
+  if (any_reuse) HIPCHK(c, hipDeviceSynchronize());
+  bool launched = false;
+  auto undo = [&]() {  // a failed call leaves no half-written map behind: the scenes it rewrote have none any more
+    hipStreamSynchronize(c->stream);
+    for (int k = 0; k < n; ++k) {
+      if (fresh[k]) hipFree(recs[k]);
+      else if (recs[k] && launched) drop_locked(c, scene_ids[k]);
+    }
+  };
+  for (int k = 0; k < n; ++k) {
+    if (recs[k]) continue;
+    void *p = nullptr;
+    const hipError_t e = hipMalloc(&p, ncell * sizeof(double4));
+    if (e != hipSuccess) {
+      undo();
+      return fail(c, NEO_ERR_HIP, std::string("batch build: hipMalloc of a record buffer: ") + hipGetErrorString(e));
+    }
+    recs[k] = static_cast<double4 *>(p);
+    fresh[k] = 1;
+  }
+  {
+    ProfScope ps(c, NEO_KERNEL_ESDF_BUILD);
+    for (int k0 = 0; k0 < n; k0 += chunk) {
+      const int nm = std::min(chunk, n - k0);
+      Carver cv(c->scratch);  // (the passes follow one another on the stream: one carving serves them all)
+      double4 **d_recs = cv.take<double4 *>((size_t)chunk);
+      Edt2DWork w{};
+      w.occ = occ + (size_t)k0 * ncell;
+      w.g = cv.take<int>((size_t)chunk * ncell);
+      w.dist = cv.take<double>((size_t)chunk * ncell);
+      if (sweeps) {
+        w.v = cv.take<int>((size_t)chunk * ncell);
+        w.z = cv.take<double>((size_t)chunk * H * (W + 1));
+      }
+      const hipError_t e = hipMemcpyAsync(d_recs, recs.data() + k0, (size_t)nm * sizeof(double4 *), hipMemcpyHostToDevice, c->stream);
+      if (e != hipSuccess) {
+        undo();
+        return fail(c, NEO_ERR_HIP, std::string("batch build: ") + hipGetErrorString(e));
+      }
+      launched = true;
+      esdf_build_2d_batch(c, w, nm, W, H, res, d_recs);
+    }
+  }
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (also: `recs` outlives the copies that read it)
+  if (e != hipSuccess) {
+    undo();
+    return fail(c, NEO_ERR_HIP, std::string("batch build: ") + hipGetErrorString(e));
+  }
+  for (int k = 0; k < n; ++k) {
+    const double ox = origins[(size_t)k * 2], oy = origins[(size_t)k * 2 + 1];
+    if (fresh[k]) {
+      drop_locked(c, scene_ids[k]);  // (a map of another kind or size)
+      DevBuf rec;
+      rec.p = recs[k];
+      adopt_map_2d(c, scene_ids[k], rec, W, H, res, ox, oy);
+      continue;
+    }
+    MapEntry &en = c->maps.find(scene_ids[k])->second;
+    const Map2D m{static_cast<const double4 *>(en.data), W, H, res, ox, oy};
+    if (memcmp(&m, &en.m2, sizeof(m)) != 0) c->table_dirty = true;
+    en.m2 = m;
+    en.version = ++c->map_serial;  // new contents: the geo mask is stale
+  }
+  return NEO_OK;
+}
+
 int neo_esdf_upload_3d(neo_ctx *c, int scene_id, const void *dist, int src_dtype, int src_is_device, int nx, int ny,
                        int nz, double res, const double origin[3], int store_dtype, int layout) {
   if (!c || !dist || !origin || nx < 2 || ny < 2 || nz < 2 || !(res > 0.0)) return NEO_ERR_INVALID;
@@ -1152,6 +1265,100 @@ int neo_depth_box_test_counter(neo_ctx *c, uint64_t *dev_count) {
   return NEO_OK;
 }
 
+// ---- onboard mapping (launch/map_server_onboard.launch: octomap_server's scan insertion projected to 2-D; kernel:
+// neo_onboard.hpp).  The checks both forms make before anything is copied or launched (context unlocked); N and half
+// are the samples a ray and the window's reach in cells.
+static int onboard_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const float *depth_m, const double *pose,
+                         int width, int height, double focal_px, double max_range, int grid_w, int grid_h, double res,
+                         const double *origins, double sensor_range, double z_lo, double z_hi, int l_hit, int l_miss,
+                         int l_lo, int l_hi, const int8_t *logodds, const int8_t *occupancy, const int32_t *changed, int &N,
+                         int &half) {
+  if (!c) return NEO_ERR_INVALID;
+  if (B < 1 || B > (1 << 20)) return fail_locked(c, NEO_ERR_INVALID, "onboard: B must be in 1 .. 2^20");
+  if (subset && (n_subset < 0 || n_subset > B)) return fail_locked(c, NEO_ERR_INVALID, "onboard: bad subset size");
+  if (width < 1 || width > 4096 || height < 1 || height > 4096)
+    return fail_locked(c, NEO_ERR_INVALID, "onboard: width and height must be in 1..4096");
+  if (!std::isfinite(focal_px) || !(focal_px > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "onboard: focal_px must be finite and > 0");
+  if (!std::isfinite(res) || !(res > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "onboard: resolution must be finite and > 0");
+  if (!std::isfinite(sensor_range) || !(sensor_range > 0.0))
+    return fail_locked(c, NEO_ERR_INVALID, "onboard: sensor_range must be finite and > 0");
+  if (!(max_range >= sensor_range))
+    return fail_locked(c, NEO_ERR_INVALID, "onboard: the camera's max_range must reach sensor_range (a depth clipped below "
+                                           "it would read as a hit)");
+  if (!std::isfinite(z_lo) || !std::isfinite(z_hi) || !(z_lo <= z_hi))
+    return fail_locked(c, NEO_ERR_INVALID, "onboard: the band needs finite z_lo <= z_hi");
+  if (grid_w < 1 || grid_h < 1 || (size_t)grid_w * grid_h > (size_t)1 << 30)
+    return fail_locked(c, NEO_ERR_INVALID, "onboard: grid width and height >= 1, at most 2^30 cells");
+  if (l_lo < -127 || l_hi > 127 || l_lo > l_hi || l_hit < 0 || l_hit > 127 || l_miss > 0 || l_miss < -127)
+    return fail_locked(c, NEO_ERR_INVALID, "onboard: log-odds need -127 <= lo <= hi <= 127, 0 <= hit <= 127, -127 <= miss <= 0");
+  if (!depth_m || !pose || !origins || !logodds || !occupancy || !changed)
+    return fail_locked(c, NEO_ERR_INVALID, "onboard: null buffer");
+  const double nd = std::ceil(sensor_range / (res / 2.0));
+  half = onboard_window_half(width, focal_px, sensor_range, res);
+  if (!(nd <= 32767.0) || half > 4096 || onboard_lds_need(half, (int)nd, height) > onboard_lds_limit())
+    return fail_locked(c, NEO_ERR_INVALID, "onboard: the window a scan can touch (sensor_range against the resolution and "
+                                           "the camera's field of view) does not fit the 64 KB of LDS a workgroup has");
+  N = (int)nd;
+  return NEO_OK;
+}
+
+int neo_onboard_integrate_batch_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const float *depth_m,
+                                    const double *pose, int width, int height, double focal_px, double max_range, int grid_w,
+                                    int grid_h, double res, const double *origins, double sensor_range, double z_lo,
+                                    double z_hi, int l_hit, int l_miss, int l_lo, int l_hi, int8_t *logodds,
+                                    int8_t *occupancy, int32_t *changed) {
+  int N = 0, half = 0;
+  int rc = onboard_check(c, B, subset, n_subset, depth_m, pose, width, height, focal_px, max_range, grid_w, grid_h, res,
+                         origins, sensor_range, z_lo, z_hi, l_hit, l_miss, l_lo, l_hi, logodds, occupancy, changed, N, half);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const int n_launch = subset ? n_subset : B;
+  if (n_launch == 0) return NEO_OK;
+  return onboard_integrate(c, OnboardCall{B, n_launch, subset, depth_m, pose, width, height, focal_px, grid_w, grid_h, res,
+                                          origins, sensor_range, z_lo, z_hi, l_hit, l_miss, l_lo, l_hi, N, half, logodds,
+                                          occupancy, changed});
+}
+
+int neo_onboard_integrate_batch(neo_ctx *c, int B, const int32_t *subset, int n_subset, const float *depth_m,
+                                const double *pose, int width, int height, double focal_px, double max_range, int grid_w,
+                                int grid_h, double res, const double *origins, double sensor_range, double z_lo, double z_hi,
+                                int l_hit, int l_miss, int l_lo, int l_hi, int8_t *logodds, int8_t *occupancy,
+                                int32_t *changed) {
+  int N = 0, half = 0;
+  int rc = onboard_check(c, B, subset, n_subset, depth_m, pose, width, height, focal_px, max_range, grid_w, grid_h, res,
+                         origins, sensor_range, z_lo, z_hi, l_hit, l_miss, l_lo, l_hi, logodds, occupancy, changed, N, half);
+  if (rc) return rc;
+  if (subset) {
+    std::vector<char> seen((size_t)B, 0);
+    for (int i = 0; i < n_subset; ++i) {
+      if (subset[i] < 0 || subset[i] >= B) return fail_locked(c, NEO_ERR_INVALID, "onboard: a subset entry is outside 0 .. B - 1");
+      if (seen[subset[i]]) return fail_locked(c, NEO_ERR_INVALID, "onboard: a mission is listed twice in the subset");
+      seen[subset[i]] = 1;
+    }
+  }
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  const size_t bs = (size_t)B, nl = subset ? (size_t)n_subset : bs, hw = (size_t)width * height;
+  const size_t ncell = (size_t)grid_w * grid_h;
+  if (nl == 0) return NEO_OK;
+  HostStage st(c, 0);
+  const auto fsub = st.in(subset, subset ? nl : 0, 1);
+  const auto fd = st.in(depth_m, nl * hw);
+  const auto fp = st.in(pose, nl * 5);
+  const auto fo = st.in(origins, bs * 2);
+  const auto fl = st.inout(logodds, bs * ncell);    // (missions outside the subset keep their grids)
+  const auto fc = st.inout(occupancy, bs * ncell);
+  const auto fg = st.inout(changed, bs);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_onboard_integrate_batch_dev(c, B, subset ? st.dev(fsub) : nullptr, n_subset, st.dev(fd), st.dev(fp), width, height,
+                                       focal_px, max_range, grid_w, grid_h, res, st.dev(fo), sensor_range, z_lo, z_hi, l_hit,
+                                       l_miss, l_lo, l_hi, st.dev(fl), st.dev(fc), st.dev(fg));
+  if (rc) return rc;
+  return st.download();
+}
+
 // ---- fleet replan loop (ros_node/traj_planner_node.py:390-578; kernels: neo_fleet.hpp)
 static int fleet_check(neo_ctx *c, int B, const int32_t *subset, int n_subset) {
   if (!c) return NEO_ERR_INVALID;
@@ -1266,6 +1473,25 @@ int neo_fleet_advance_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset
   if (f.launched() == 0) return NEO_OK;
   rc = fleet_advance(c, f, {const_cast<double *>(cmd), cap, const_cast<int32_t *>(cmd_len), cmd_index, future_index}, step,
                      ahead, cur_pos, head);
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+int neo_fleet_pose_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                       const int32_t *cmd_len, const int32_t *cmd_index, const double *cur_pos, const double *goal,
+                       double eye_z, double *pose) {
+  int rc = fleet_check(c, B, subset, n_subset);
+  if (rc) return rc;
+  if (!cmd || !cmd_len || !cmd_index || !cur_pos || !goal || !pose) return fail_locked(c, NEO_ERR_INVALID, "fleet pose: null buffer");
+  if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, "fleet pose: cap must be > 0");
+  if (!std::isfinite(eye_z)) return fail_locked(c, NEO_ERR_INVALID, "fleet pose: eye_z must be finite");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const FleetArgs f{B, subset, n_subset};
+  if (f.launched() == 0) return NEO_OK;
+  rc = fleet_pose(c, f, {const_cast<double *>(cmd), cap, const_cast<int32_t *>(cmd_len), const_cast<int32_t *>(cmd_index), nullptr},
+                  cur_pos, goal, eye_z, pose);
   if (rc) return rc;
   HIPCHK(c, hipGetLastError());
   return NEO_OK;

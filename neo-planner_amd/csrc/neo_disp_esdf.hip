@@ -17,7 +17,25 @@ void esdf_build_2d(neo_ctx *c, const Edt2DWork &w, int W, int H, double res, dou
     hipLaunchKernelGGL(edt_rows_kernel, dim3((H + 63) / 64), dim3(64), 0, c->stream, w.g, W, H, res, w.v, w.z, w.dist);
   }
   hipLaunchKernelGGL(gradient_pack_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, w.dist, W, H,
-                     rec, w.gx, w.gy);
+                     rec, nullptr, w.gx, w.gy);
+}
+
+// the same launches with the maps of a batch in the grid (at most 65535 a call: grid.y / grid.z)
+void esdf_build_2d_batch(neo_ctx *c, const Edt2DWork &w, int nmap, int W, int H, double res, double4 *const *recs) {
+  const size_t ncell = (size_t)W * H;
+  const unsigned nm = (unsigned)nmap;
+  // The column pass is always the sweep, one lane per column: a batch has the columns of all its maps to fill the machine
+  // with, and the exhaustive column kernel was two thirds of a batch's time (4096 maps of 300 x 300: 88.4 ms with it,
+  // 27.5 ms with the sweep; the row sweep as well: 32.3 ms -- `tools/gpu_onboard_time.py rebuild`).  Both give the same integers.  Rows: exhaustive up to
+  // 512 x 512, the sweep beyond, as for one map.
+  hipLaunchKernelGGL(edt_columns_kernel, dim3((W + 63) / 64, nm), dim3(64), 0, c->stream, w.occ, W, H, w.g);
+  if (W <= 512 && H <= 512) {
+    hipLaunchKernelGGL(edt2_rows_bf_kernel, dim3((W + 63) / 64, H, nm), dim3(64), 0, c->stream, w.g, W, H, res, w.dist);
+  } else {
+    hipLaunchKernelGGL(edt_rows_kernel, dim3((H + 63) / 64, nm), dim3(64), 0, c->stream, w.g, W, H, res, w.v, w.z, w.dist);
+  }
+  hipLaunchKernelGGL(gradient_pack_kernel, dim3((unsigned)((ncell + 255) / 256), nm), dim3(256), 0, c->stream, w.dist, W, H,
+                     nullptr, recs, nullptr, nullptr);
 }
 
 void esdf_pack_2d(neo_ctx *c, const double *dist, const double *gx, const double *gy, size_t ncell, double4 *rec) {

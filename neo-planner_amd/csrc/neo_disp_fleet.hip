@@ -23,6 +23,14 @@ int fleet_advance(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, int step, i
   return NEO_OK;
 }
 
+int fleet_pose(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const double *cur_pos, const double *goal, double eye_z,
+               double *pose) {
+  const int n = f.launched();
+  hipLaunchKernelGGL(fleet_pose_kernel, lanes_grid(n), dim3(kFleetThreads), 0, c->stream, f.B, n, f.subset, m.cmd, m.cap,
+                     m.cmd_len, m.cmd_index, cur_pos, goal, eye_z, pose);
+  return NEO_OK;
+}
+
 int fleet_splice(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const FleetSpliceArgs &a) {
   const int n = f.launched();
   hipLaunchKernelGGL(fleet_splice_kernel, dim3(n), dim3(kWave), 0, c->stream, f.B, n, f.subset, a.M, c->dev, a.x, a.head,

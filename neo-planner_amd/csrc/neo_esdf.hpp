@@ -15,11 +15,16 @@ namespace neo {
 // exact Euclidean distance transform of the free cells to the nearest occupied cell, two
 // separable passes over integer squared distances (Felzenszwalb & Huttenlocher lower envelope),
 // then sqrt * resolution and numpy.gradient with unit spacing.
+// Every 2-D kernel takes a map dimension in its grid (blockIdx.y of the sweeps and of gradient_pack, blockIdx.z of the
+// exhaustive form): map k's occupancy and work arrays lie k maps further on (neo_esdf_build_2d_batch_dev); a launch for
+// one map has one block there.
 constexpr int kEdtInf = 1 << 28;
 
 __global__ void edt_columns_kernel(const int8_t *__restrict__ occ, int W, int H, int *__restrict__ g) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   if (x >= W) return;
+  occ += (size_t)blockIdx.y * W * H;
+  g += (size_t)blockIdx.y * W * H;
   int d = kEdtInf;
   for (int y = 0; y < H; ++y) {
     d = (occ[(size_t)y * W + x] == 100) ? 0 : (d >= kEdtInf ? kEdtInf : d + 1);
@@ -38,9 +43,10 @@ __global__ void edt_rows_kernel(const int *__restrict__ g, int W, int H, double 
                                 double *__restrict__ zbuf, double *__restrict__ dist) {
   const int y = blockIdx.x * blockDim.x + threadIdx.x;
   if (y >= H) return;
-  const int *f = g + (size_t)y * W;
-  int *v = vbuf + (size_t)y * W;
-  double *z = zbuf + (size_t)y * (W + 1);
+  const size_t map0 = (size_t)blockIdx.y * W * H;
+  const int *f = g + map0 + (size_t)y * W;
+  int *v = vbuf + map0 + (size_t)y * W;
+  double *z = zbuf + (size_t)blockIdx.y * H * (W + 1) + (size_t)y * (W + 1);
   int k = -1;
   for (int q = 0; q < W; ++q) {
     if (f[q] >= kEdtInf) continue;
@@ -61,7 +67,7 @@ __global__ void edt_rows_kernel(const int *__restrict__ g, int W, int H, double 
     z[k] = (k == 0) ? -1.0e300 : s;
     z[k + 1] = 1.0e300;
   }
-  double *out = dist + (size_t)y * W;
+  double *out = dist + map0 + (size_t)y * W;
   if (k < 0) {
     // no occupied cell in the whole map: scipy.ndimage.distance_transform_edt then measures to a
     // virtual background cell at (row -1, column 0); the reference inherits that (esdf.py:29)
@@ -87,6 +93,8 @@ __global__ void edt_rows_kernel(const int *__restrict__ g, int W, int H, double 
 __global__ void edt2_columns_bf_kernel(const int8_t *__restrict__ occ, int W, int H, int *__restrict__ g) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= W) return;
+  occ += (size_t)blockIdx.z * W * H;
+  g += (size_t)blockIdx.z * W * H;
   int d = kEdtInf;
   for (int q = 0; q < H; ++q) {
     const int dq = q > y ? q - y : y - q;
@@ -97,7 +105,8 @@ __global__ void edt2_columns_bf_kernel(const int8_t *__restrict__ occ, int W, in
 __global__ void edt2_rows_bf_kernel(const int *__restrict__ g, int W, int H, double res, double *__restrict__ dist) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= W) return;
-  const int *f = g + (size_t)y * W;
+  const size_t map0 = (size_t)blockIdx.z * W * H;
+  const int *f = g + map0 + (size_t)y * W;
   long long best = -1;
   for (int p = 0; p < W; ++p) {
     const int fp = f[p];
@@ -108,7 +117,7 @@ __global__ void edt2_rows_bf_kernel(const int *__restrict__ g, int W, int H, dou
   }
   // no occupied cell in the whole map: SciPy's virtual background cell at (row -1, column 0), see edt_rows_kernel
   if (best < 0) best = (long long)(y + 1) * (y + 1) + (long long)x * x;
-  dist[(size_t)y * W + x] = sqrt((double)best) * res;
+  dist[map0 + (size_t)y * W + x] = sqrt((double)best) * res;
 }
 
 // ---- 3-D exact EDT (north-star scenes): three separable passes over integers, so the result equals
@@ -513,11 +522,15 @@ __global__ __launch_bounds__(kEdtThreads) void edt3_line_keys_kernel(const SrcT 
 #undef NEO_EDT_K
 #undef NEO_EDT_NEGP
 
-// numpy.gradient, unit spacing: central differences inside, one-sided at the borders
+// numpy.gradient, unit spacing: central differences inside, one-sided at the borders.  `recs` (or NULL): the record
+// buffer of each map of a batch, in place of `rec`
 __global__ void gradient_pack_kernel(const double *__restrict__ dist, int W, int H, double4 *__restrict__ rec,
-                                     double *__restrict__ gx_out, double *__restrict__ gy_out) {
+                                     double4 *const *__restrict__ recs, double *__restrict__ gx_out,
+                                     double *__restrict__ gy_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= W * H) return;
+  dist += (size_t)blockIdx.y * W * H;
+  if (recs) rec = recs[blockIdx.y];
   const int y = i / W, x = i - y * W;
   double gx, gy;
   if (W == 1) gx = 0.0;

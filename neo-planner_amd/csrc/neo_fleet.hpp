@@ -3,6 +3,7 @@
 //
 //   fleet_target_kernel    set_local_target       (:450-488)   one lane per mission
 //   fleet_advance_kernel   perfect tracking + get_drone_state_ahead (:527-537)   one lane per mission
+//   fleet_pose_kernel      the camera pose a mission senses from (:685-687)          one lane per mission
 //   fleet_splice_kernel    the splice of replan   (:574-578, first_plan :515-519)   one wavefront per mission
 //   fleet_audit_kernel     get_weighted_metric    (:333-363) over the flown rows   one wavefront per mission
 //
@@ -103,6 +104,47 @@ __global__ __launch_bounds__(kFleetThreads) void fleet_target_kernel(
   near_goal[b] = 0;
   lateral_steps[b] = steps;
   if (capped) flags[b] |= NEO_FLEET_FLAG_TARGET_CAPPED;
+}
+
+// The camera pose a mission senses from (onboard maps): the eye is where the mission is, at height eye_z; the heading is
+// the unit vector of the last step of its command array, row cmd_index minus the row before it -- :685-687 without the
+// arctan2 round trip -- or, where there is no such step or it has no length, of the way to the goal; (1, 0) on the goal.
+// Squares, one sum, sqrt and divisions, each rounded on its own: NumPy reproduces the bits.
+__device__ __forceinline__ bool fleet_unit(double dx, double dy, double &c, double &s) {
+#pragma clang fp contract(off)
+  const double xx = dx * dx, yy = dy * dy;
+  const double n = sqrt(xx + yy);
+  if (!(n > 0.0 && n < __builtin_inf())) return false;
+  c = dx / n;
+  s = dy / n;
+  return true;
+}
+
+__global__ __launch_bounds__(kFleetThreads) void fleet_pose_kernel(
+    int B, int n, const int *__restrict__ subset, const double *__restrict__ cmd, int cap,
+    const int *__restrict__ cmd_len, const int *__restrict__ cmd_index, const double *__restrict__ cur_pos,
+    const double *__restrict__ goal, double eye_z, double *__restrict__ pose) {
+#pragma clang fp contract(off)
+  const int b = fleet_mission(blockIdx.x * kFleetThreads + threadIdx.x, n, subset, B);
+  if (b < 0) return;
+  const double px = cur_pos[(size_t)b * 2], py = cur_pos[(size_t)b * 2 + 1];
+  int len = cmd_len[b];
+  len = len > cap ? cap : len;
+  const int k = cmd_index[b];
+  double c = 1.0, s = 0.0;
+  bool have = false;
+  if (k >= 1 && k < len) {
+    const double *r1 = cmd + ((size_t)b * cap + k) * kFleetRow, *r0 = r1 - kFleetRow;
+    have = fleet_unit(r1[0] - r0[0], r1[1] - r0[1], c, s);
+  }
+  if (!have) have = fleet_unit(goal[(size_t)b * 2] - px, goal[(size_t)b * 2 + 1] - py, c, s);
+  if (!have) c = 1.0, s = 0.0;
+  double *o = pose + (size_t)b * 5;
+  o[0] = px;
+  o[1] = py;
+  o[2] = eye_z;
+  o[3] = c;
+  o[4] = s;
 }
 
 __global__ __launch_bounds__(kFleetThreads) void fleet_advance_kernel(

@@ -250,6 +250,9 @@ int fleet_target(neo_ctx *c, const FleetArgs &f, const FleetTargetArgs &a);
 int fleet_advance(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, int step, int ahead, double *cur_pos, double *head);
 int fleet_splice(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const FleetSpliceArgs &a);
 int fleet_audit(neo_ctx *c, const FleetArgs &f, const FleetAuditArgs &a);
+// the missions' camera poses (eye x y z, cos, sin) from where they are on their command arrays
+int fleet_pose(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const double *cur_pos, const double *goal, double eye_z,
+               double *pose);
 
 // neo_batch_*_dev: the `batch` planner mode on resident arrays (neo_disp_batch.hip, kernels in neo_batch.hpp).  P =
 // f.launched() requests; tau, off and w are HOST arrays (M, K and 4 values), handed to the kernels by value.
@@ -337,6 +340,29 @@ struct DepthCall {
 int depth_render(neo_ctx *c, const DepthCall &a);
 void depth_release(neo_ctx *c);  // frees the camera's buffers (neo_ctx_destroy)
 
+// neo_onboard_integrate_batch_dev (neo_disp_onboard.hip, kernel in neo_onboard.hpp): one launch on the context's
+// stream; every pointer is a device array, the arguments are checked, N and half sized by the caller
+struct OnboardCall {
+  int B, n_launch;
+  const int *subset;  // or NULL
+  const float *depth_m;
+  const double *pose;
+  int W, H;
+  double focal;
+  int grid_w, grid_h;
+  double res;
+  const double *origins;
+  double range, z_lo, z_hi;
+  int l_hit, l_miss, l_lo, l_hi;
+  int N, half;
+  int8_t *logodds, *occupancy;
+  int *changed;
+};
+int onboard_window_half(int width, double focal, double range, double res);  // cells from the eye's cell to the window's edge
+size_t onboard_lds_need(int half, int N, int height);                         // LDS bytes of a launch
+size_t onboard_lds_limit();
+int onboard_integrate(neo_ctx *c, const OnboardCall &k);
+
 // the map kernels' launches (neo_disp_esdf.hip, kernels in neo_esdf.hpp), on the context's stream.  Every pointer is a
 // device array the caller owns -- the C ABI carves the work arrays from the context's scratch -- and nothing is
 // allocated; the arguments are the ones neo_esdf_* checked.
@@ -347,6 +373,9 @@ struct Edt2DWork {  // work arrays of a W x H build: v and z are the sweeps' sta
   double *dist, *gx, *gy;  // [W * H] each: the results, as the reference's arrays
 };
 void esdf_build_2d(neo_ctx *c, const Edt2DWork &w, int W, int H, double res, double4 *rec);  // EDT, gradient, records
+// the same kernels for `nmap` maps of one size in one set of launches: occ and the work arrays hold the maps back to
+// back (z: H * (W + 1) a map), recs[nmap] (device) names each map's record buffer; gx and gy are not kept
+void esdf_build_2d_batch(neo_ctx *c, const Edt2DWork &w, int nmap, int W, int H, double res, double4 *const *recs);
 void esdf_pack_2d(neo_ctx *c, const double *dist, const double *gx, const double *gy, size_t ncell, double4 *rec);
 void esdf_pack_3d(neo_ctx *c, const void *src, int src_dtype, int nx, int ny, int nz, int store_dtype, int layout, int nbx,
                   int nby, int nbz, void *dst);  // nbx, nby, nbz: bricks per axis (NEO_LAYOUT_BRICK only)

@@ -12,7 +12,8 @@ from .planner import BatchPlanner, MinJerkPlanner, PlannerConfig  # noqa: F401
 from .geo import GeoPlanner  # noqa: F401
 from .fleet import FleetReplanLoop  # noqa: F401
 from .depth import DepthCamera  # noqa: F401
+from .onboard import OnboardMapper  # noqa: F401
 # the initializer network (torch) is imported on demand: `from neo_planner_amd import initializer`
 
 __all__ = ["Context", "NeoError", "default_context", "ESDF", "ESDF3D", "BatchPlanner", "MinJerkPlanner",
-           "PlannerConfig", "GeoPlanner", "FleetReplanLoop", "DepthCamera"]
+           "PlannerConfig", "GeoPlanner", "FleetReplanLoop", "DepthCamera", "OnboardMapper"]

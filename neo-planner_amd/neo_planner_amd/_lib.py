@@ -53,7 +53,8 @@ EXPORTS = [
     "neo_fleet_splice_dev", "neo_fleet_audit_batch", "neo_fleet_audit_batch_dev", "neo_batch_candidates",
     "neo_batch_candidates_dev", "neo_batch_select", "neo_batch_select_dev", "neo_plan_guess", "neo_plan_guess_dev",
     "neo_plan_merge", "neo_plan_merge_dev", "neo_depth_render_batch", "neo_depth_render_batch_dev",
-    "neo_depth_box_test_counter",
+    "neo_depth_box_test_counter", "neo_onboard_integrate_batch", "neo_onboard_integrate_batch_dev",
+    "neo_esdf_build_2d_batch_dev", "neo_fleet_pose_dev",
 ]
 
 
@@ -138,6 +139,11 @@ def load():
     L.neo_depth_render_batch.argtypes = [c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_i, c_p, c_i] + [c_p] * 4
     L.neo_depth_render_batch_dev.argtypes = [c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_i, c_p, c_i] + [c_p] * 4
     L.neo_depth_box_test_counter.argtypes = [c_p, c_p]
+    _onboard = [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_d, c_d, c_i, c_i, c_d, c_p, c_d, c_d, c_d, c_i, c_i, c_i, c_i, c_p, c_p, c_p]
+    L.neo_onboard_integrate_batch.argtypes = list(_onboard)
+    L.neo_onboard_integrate_batch_dev.argtypes = list(_onboard)
+    L.neo_esdf_build_2d_batch_dev.argtypes = [c_p, c_p, c_i, c_p, c_i, c_i, c_d, c_p]
+    L.neo_fleet_pose_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_d, c_p]
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]

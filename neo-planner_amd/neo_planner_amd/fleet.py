@@ -20,6 +20,12 @@ With resident=True the plans are BatchPlanner.plan_dev's, bit for bit the same: 
 look-ahead states and targets and fetches `solved` and the two counters of the pending missions only; mode "batch" sends
 its list of missions without a feasible candidate through plan_dev as well.
 
+With onboard=OnboardMapper the missions fly on what they have seen: before the targets of every tick (tick 0 included)
+the active missions sense from where they are -- the eye at (cur_pos, des_pos_z), heading along the last step of the
+command array (neo_fleet_pose_dev), mapper.update renders, integrates and rebuilds -- and the targets and the plans use
+each mission's onboard scene.  The final audit is taken on the true maps: the flight metric is measured against the
+world, not the belief.
+
 A mission's flight does not depend on which other missions share the fleet: the kernels work per mission, the target
 jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
 retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream_ids`).
@@ -58,16 +64,28 @@ class FleetReplanLoop:
     its id flies as it does in the fleet.  max_cmd_seconds sizes the resident command arrays
     (cap = max_cmd_seconds * cmd_hz rows a mission); a mission whose array fills up ends as not reached.
     resident=True (modes "basic" and "batch"): the plans run through BatchPlanner.plan_dev on the resident arrays --
-    the same flights; head, tail and x no longer pass through the host."""
+    the same flights; head, tail and x no longer pass through the host.
+    onboard: an OnboardMapper for the same B missions -- targets and plans then use each mission's onboard scene, `map` /
+    scene_ids only the final audit; scenes = (boxes (NB, 6), box_begin (S + 1,)) as DepthCamera.pack_scenes returns them
+    and scene_index (B,) (None: scene 0) say what each mission's camera sees; des_pos_z is the eye's height.  run() starts
+    from onboard.reset(): every flight begins knowing nothing, whatever the mapper saw before.
+    record_poses adds `poses` (ticks, B, 5) and `sensed` (ticks, B) to the result."""
 
     def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
                  longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
-                 scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False):
+                 scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False, onboard=None, scenes=None,
+                 scene_index=None, des_pos_z=2.0, record_poses=False):
         if mode not in ("basic", "geo", "batch"):
             raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo' or 'batch'")
         if resident and mode == "geo":
             raise ValueError("FleetReplanLoop: resident=True needs mode 'basic' or 'batch' (geo_plan has no resident form)")
+        if onboard is not None and mode == "geo":
+            raise ValueError("FleetReplanLoop: onboard maps need mode 'basic' or 'batch' (geo on onboard maps is not built)")
+        if onboard is not None and scenes is None:
+            raise ValueError("FleetReplanLoop: onboard needs scenes=(boxes, box_begin), what the cameras see")
         self.resident = bool(resident)
+        self.onboard, self.scenes, self.des_pos_z, self.record_poses = onboard, scenes, float(des_pos_z), bool(record_poses)
+        self.scene_index = None if scene_index is None else np.ascontiguousarray(scene_index, dtype=np.int32).reshape(-1)
         self.bp, self.map, self.mode = batch_planner, map, mode
         self.goals = _lib.as_f64(goals).reshape(-1, 2)
         self.B = self.goals.shape[0]
@@ -83,6 +101,11 @@ class FleetReplanLoop:
         self.mission_ids = np.arange(self.B) if mission_ids is None else np.asarray(mission_ids).reshape(-1)
         if self.mission_ids.shape[0] != self.B or (self.scene_ids is not None and self.scene_ids.shape[0] != self.B):
             raise ValueError("FleetReplanLoop: one mission id and one scene id per goal")
+        if onboard is not None and (onboard.B != self.B or (self.scene_index is not None and self.scene_index.shape[0] != self.B)):
+            raise ValueError("FleetReplanLoop: the onboard mapper and scene_index must have one entry per goal")
+        # what targets and plans see: the missions' onboard scenes, or the given map(s)
+        self.plan_map = map if onboard is None else onboard
+        self.plan_scene_ids = self.scene_ids if onboard is None else onboard.scene_ids
         self.timings = []
         self._dev = None
         self._batch = None      # mode "batch": BatchPlanner.batch_buffers, made at the first plan
@@ -105,10 +128,29 @@ class FleetReplanLoop:
 
     def _target(self, sub):
         c, d, p = self.bp.ctx, self._dev, self._p
-        c.check(c.lib.neo_fleet_target_batch_dev(c.h, self.map.scene_id, p(d["slots"]), self.B, p(sub), int(sub.numel()),
+        c.check(c.lib.neo_fleet_target_batch_dev(c.h, self.plan_map.scene_id, p(d["plan_slots"]), self.B, p(sub), int(sub.numel()),
                                                  p(d["cur_pos"]), p(d["goal"]), p(d["jitter"]), self.longitu_step_dis,
                                                  self.lateral_step_length, self.move_vel, p(d["tail"]), p(d["near"]),
                                                  p(d["steps"]), p(d["flags"])))
+
+    def _sense(self, active, tm):
+        """the active missions' poses from where they are, then mapper.update on what their cameras see"""
+        c, d, p = self.bp.ctx, self._dev, self._p
+        t0 = time.perf_counter()
+        sub = self._subset(active)
+        self._sync()
+        c.check(c.lib.neo_fleet_pose_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
+                                         p(d["cmd_index"]), p(d["cur_pos"]), p(d["goal"]), self.des_pos_z, p(d["pose"])))
+        c.synchronize()
+        rebuilt = self.onboard.update(d["boxes"], d["box_begin"], d["pose"], d["scene_index"], subset=active)
+        tm["sense_s"] = time.perf_counter() - t0
+        tm["rebuilt"] = int(len(rebuilt))
+        tm.update({k: self.onboard.last[k] for k in ("render_s", "integrate_s", "rebuild_s")})
+        if self.record_poses:
+            self._poses.append(d["pose"].cpu().numpy())
+            sensed = np.zeros(self.B, bool)
+            sensed[active] = True
+            self._sensed.append(sensed)
 
     def _advance(self, sub):
         c, d, p = self.bp.ctx, self._dev, self._p
@@ -142,12 +184,23 @@ class FleetReplanLoop:
         self._dev = dict(cmd=f(B, self.cap, 3, 2), cmd_len=i(B), cmd_index=i(B), future_index=i(B), flags=i(B),
                          cur_pos=f(B, 2), goal=f(B, 2), jitter=f(B, 2), head=f(B, 3, 2), tail=f(B, 3, 2), near=i(B),
                          steps=i(B), x=f(B, n), solved=i(B), n_flown=i(B), audit=f(B, _lib.NEO_AUDIT_FIELDS), count=i(B),
-                         audit_flags=i(B), slots=None)
+                         audit_flags=i(B), slots=None, plan_slots=None)
         if self.scene_ids is not None:
             slot_of = {int(s): int(c.lib.neo_scene_slot(c.h, int(s))) for s in np.unique(self.scene_ids)}
             if min(slot_of.values()) < 0:
                 raise _lib.NeoError("FleetReplanLoop: a scene id without a map")
             self._dev["slots"] = self._subset(np.array([slot_of[int(s)] for s in self.scene_ids]))
+        self._dev["plan_slots"] = self._dev["slots"]
+        if self.onboard is not None:
+            self.onboard.reset()      # all unknown, and the slots as the map table numbers them now
+            boxes, box_begin = self.scenes
+            self._dev.update(plan_slots=self.onboard.slots, pose=f(B, 5),
+                             boxes=torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 6)).to(dev),
+                             box_begin=torch.from_numpy(np.ascontiguousarray(box_begin, dtype=np.int32)).to(dev),
+                             scene_index=None if self.scene_index is None else torch.from_numpy(self.scene_index).to(dev))
+            if self._dev["boxes"].shape[0] == 0:      # (a scene list without any box still hands over a valid pointer)
+                self._dev["boxes"] = f(1, 6)
+        self._poses, self._sensed = [], []
         self._up("goal", self.goals)
 
     def _plan_bufs(self):
@@ -160,7 +213,7 @@ class FleetReplanLoop:
         """resident=True, mode "basic": one target round's plans for the missions `pending` (`sub` the same on the device)
         on the resident head / tail -- plan_dev writes the resident x and solved.  Returns (ok over pending, nit_total,
         attempts) as the host planner's dict has them."""
-        bufs = self.bp.plan_dev(self.map, self._dev["head"], self._dev["tail"], bufs=self._plan_bufs(), slots=self._dev["slots"],
+        bufs = self.bp.plan_dev(self.plan_map, self._dev["head"], self._dev["tail"], bufs=self._plan_bufs(), slots=self._dev["plan_slots"],
                                 subset=sub, x=self._dev["x"], solved=self._dev["solved"], seed=plan_seed(self.seed, tick, r),
                                 stream_ids=self.mission_ids)
         idx = sub.long()
@@ -176,7 +229,7 @@ class FleetReplanLoop:
         if self._batch is None:
             self._batch = bp.batch_buffers(self.B, 3, self._device)
             self._sync()
-        bufs = bp.batch_plan_dev(self.map, d["head"], d["tail"], self._batch, slots=d["slots"], subset=sub, x=d["x"],
+        bufs = bp.batch_plan_dev(self.plan_map, d["head"], d["tail"], self._batch, slots=d["plan_slots"], subset=sub, x=d["x"],
                                  solved=d["solved"])
         fb = bp.batch_fallback(bufs)
         nit = bufs["nit_total"].cpu().numpy()[pending].astype(np.int64)
@@ -188,10 +241,10 @@ class FleetReplanLoop:
             count = int(bp.cfg.init_wpts_num)
             fb_dev = bufs["fallback"][:fb.size]
             c.check(c.lib.neo_batch_candidates_dev(c.h, self.B, p(fb_dev), int(fb.size), count + 1, 2, 1, p(d["head"]),
-                                                   p(d["tail"]), p(d["slots"]), _lib.ptr(bp._plan_frac_tau(count)[1]), None,
+                                                   p(d["tail"]), p(d["plan_slots"]), _lib.ptr(bp._plan_frac_tau(count)[1]), None,
                                                    p(pb["x_k"]), p(pb["head_k"]), p(pb["tail_k"]),
-                                                   p(pb["slots_k"]) if d["slots"] is not None else None))
-            bp.plan_dev(self.map, d["head"], d["tail"], bufs=pb, slots=d["slots"], subset=fb_dev, x=d["x"], solved=d["solved"],
+                                                   p(pb["slots_k"]) if d["plan_slots"] is not None else None))
+            bp.plan_dev(self.plan_map, d["head"], d["tail"], bufs=pb, slots=d["plan_slots"], subset=fb_dev, x=d["x"], solved=d["solved"],
                         seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids, _guessed=True)
             idx = fb_dev.long()
             at = np.searchsorted(pending, fb)
@@ -201,9 +254,9 @@ class FleetReplanLoop:
             idx = torch.from_numpy(fb).to(self._device)
             head, tail = d["head"][idx].cpu().numpy(), d["tail"][idx].cpu().numpy()
             count = int(bp.cfg.init_wpts_num)
-            res = bp.plan(self.map, head, tail, int_wpts=bp.batch_init_guess(head, tail, K=1)[0][:, 0],
+            res = bp.plan(self.plan_map, head, tail, int_wpts=bp.batch_init_guess(head, tail, K=1)[0][:, 0],
                           ts=np.tile(bp._batch_ts_tau(count)[0], (fb.size, 1)),
-                          scene_ids=None if self.scene_ids is None else self.scene_ids[fb],
+                          scene_ids=None if self.plan_scene_ids is None else self.plan_scene_ids[fb],
                           seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[fb])
             d["x"][idx] = torch.from_numpy(np.ascontiguousarray(res["x"])).to(self._device)
             d["solved"][idx] = torch.from_numpy(res["solved"].astype(np.int32)).to(self._device)
@@ -260,6 +313,8 @@ class FleetReplanLoop:
             else:
                 self._up("cur_pos", cur_pos)
                 self._up("head", head)
+            if self.onboard is not None:
+                self._sense(active, tm)
             pending = active
             for r in range(MAX_TARGETS):
                 t0 = time.perf_counter()
@@ -280,8 +335,8 @@ class FleetReplanLoop:
                 elif self.resident:
                     ok, nit_total, attempts = self._plan_resident(sub, pending, tick, r)
                 else:
-                    out = planner(self.map, head[pending], tail[pending],
-                                  scene_ids=None if self.scene_ids is None else self.scene_ids[pending],
+                    out = planner(self.plan_map, head[pending], tail[pending],
+                                  scene_ids=None if self.plan_scene_ids is None else self.plan_scene_ids[pending],
                                   seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[pending])
                     ok, nit_total, attempts = out["solved"], out["nit_total"], out["attempts"]
                 tm["plan_s"] += time.perf_counter() - t0
@@ -311,7 +366,7 @@ class FleetReplanLoop:
             stuck = (flags & (_lib.NEO_FLEET_FLAG_CMD_FULL | _lib.NEO_FLEET_FLAG_SPLICE_FAILED)) != 0
             active = active[~(abandoned | landed | stuck)[active]]
             tm["tick_s"] = time.perf_counter() - t_tick
-            tm["host_s"] = tm["tick_s"] - tm["fleet_s"] - tm["plan_s"]
+            tm["host_s"] = tm["tick_s"] - tm["fleet_s"] - tm["plan_s"] - tm.get("sense_s", 0.0)
             self.timings.append(tm)
         return self._finish(replans, failed, iter_num, opt_runs, abandoned, landed)
 
@@ -340,6 +395,9 @@ class FleetReplanLoop:
                    replans=replans, failed_attempts=failed, iter_num=iter_num, opt_runs=opt_runs, n_cmd=cmd_len,
                    n_flown=n_flown, final_dist=final_dist, flags=flags, audit_flags=audit_flags,
                    count=d["count"].cpu().numpy(), abandoned=abandoned, metric_fail=metric_fail)
+        if self.record_poses and self.onboard is not None:
+            out.update(poses=np.stack(self._poses) if self._poses else np.zeros((0, self.B, 5)),
+                       sensed=np.stack(self._sensed) if self._sensed else np.zeros((0, self.B), bool))
         return out
 
     def commands(self, i):
