@@ -480,6 +480,51 @@ int neo_fleet_audit_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_i
                               int n_subset, const double *cmd, int cap, const int32_t *n_flown, int stride,
                               double cmd_hz, const double *weights3, double *audit, int32_t *count, int32_t *flags);
 
+/* ---- fleet record mode (traj_planner/record_planner.py:13-72, :152-185) ----------------
+ * What the reference's `record` planner saves of every successful plan, for the missions of a fleet: one row of a
+ * RESIDENT dataset of `capacity` rows, caller-owned DEVICE buffers:
+ *   motion[capacity][24]            form_nn_input's vector (:13-58), see below;
+ *   wpts_local[capacity][3 (M - 1)] form_nn_output (:61-72): the waypoints in the body frame, waypoint-major (x, y, z);
+ *   tau[capacity][M]                the last M entries of the plan's x -- the durations are
+ *                                   ts = (T_max - T_min) / (1 + exp(-tau)) + T_min (expert_planner.py:477-483), which the
+ *                                   HOST derives: the device's exp is not libm's;
+ *   pose_rows[capacity][5]          the sensed pose (eye x, y, z, c, s) the row was formed with;
+ *   meta[capacity][3]               int32: mission id, tick, target round;
+ *   images[capacity][H][W]          the mission's uint8 depth image (neo_depth_render_batch's depth_u8);
+ *   n_rows[1], dropped[1]           int32 device words: rows filled so far, and rows that found no place.  The caller
+ *                                   zeroes them once and reads them when it wants to know.
+ * Fleet state as in the section above (device arrays indexed by MISSION, `subset` of n_subset mission indices or NULL
+ * = all B, an index outside 0 .. B - 1 is skipped, a mission may appear once).  fp64, every operation rounded on its
+ * own, so NumPy gives the same bits; no atomics: a mission's row depends on neither B, the subset nor its position,
+ * and its row NUMBER only on the launched missions before it.  Nothing is written outside rows 0 .. capacity - 1 of
+ * any dataset array.  Device pointers only, asynchronous on the context's stream.
+ * NEO_ERR_INVALID before any launch, with a neo_last_error message: B < 1, a bad subset size, M outside 2 .. 64,
+ * capacity < 1, cap <= 0, width or height outside 1 .. 4096, a NULL required buffer. */
+/* drone_state.global_vel at the time of a tick's plans, one lane per mission: cur_vel[B][2] = the velocity of row
+ * cmd_index[b] of cmd[b] (clamped into 0 .. cmd_len - 1) for a mission with cmd_len >= 1, else head[b][1] -- before
+ * the first plan drone_state is plan_init_state (ros_node/traj_planner_node.py first_plan).  Call it once a tick before
+ * any plan: the splice of a later target round may overwrite row cmd_index. */
+int neo_record_state_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                         const int32_t *cmd_len, const int32_t *cmd_index, const double *head, double *cur_vel);
+/* One target round's rows, two launches.  Rank (one workgroup, ballot and prefix counts): the launched mission at
+ * position k with solved[b] != 0 (solved NULL: every launched mission) gets row_of[k] = *n_rows + its rank among
+ * them; the others -1; a row at or beyond `capacity` is -1 too and counted in *dropped; *n_rows advances by the rows
+ * given.  row_of is a device array of at least the launched missions, written for every position.  Commit (one
+ * workgroup of 256 lanes per launched mission, returns at once on row -1) writes the row from x[B][3 M - 2],
+ * head[B][3][2], tail[B][3][2], pose[B][5] (neo_fleet_pose_dev), cur_vel[B][2] and staging[B][H][W], the tick's images
+ * by mission.  With R = [[c, -s, 0], [s, c, 0], [0, 0, 1]] of the pose, R^T v = (c vx + s vy, -s vx + c vy, vz) and
+ * p = (px, py, pz) the eye, the 24 values of motion are: R^T (cur_vel, 0); R row-major; R^T ((head pos, pz) - p);
+ * R^T ((head vel, 0) - (cur_vel, 0)); the same two for tail.  Waypoint i is R^T ((q_x[i], q_y[i], pz) - p), q the
+ * first 2 (M - 1) entries of x[b], row-major by dimension.  meta = (mission_ids[b], or b with mission_ids NULL; tick;
+ * round).  The image is copied with 16-byte loads and stores over the aligned middle of the destination row and bytes
+ * at both ends: H * W need not be a multiple of 16. */
+int neo_record_commit_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, const double *x,
+                          const double *head, const double *tail, const int32_t *solved, const double *pose,
+                          const double *cur_vel, const uint8_t *staging, int width, int height,
+                          const int32_t *mission_ids, int tick, int round, int capacity, double *motion,
+                          double *wpts_local, double *tau, double *pose_rows, int32_t *meta, uint8_t *images,
+                          int32_t *row_of, int32_t *n_rows, int32_t *dropped);
+
 /* ---- the `batch` planner mode on resident arrays (traj_planner/expert_planner.py:103-168) ----------------
  * MinJerkPlanner.batch_plan optimises K laterally shifted initial guesses of one request and keeps the cheapest
  * feasible one.  These two calls are what surrounds the optimiser launch for P requests at once, 2-D (D = 2), fp64:

@@ -1580,6 +1580,56 @@ int neo_fleet_audit_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, in
   return st.download();
 }
 
+// ---- the fleet's record mode (traj_planner/record_planner.py:13-72; kernels: neo_record.hpp)
+static int record_check(neo_ctx *c, int B, const int32_t *subset, int n_subset) {
+  if (!c) return NEO_ERR_INVALID;
+  if (B < 1) return fail_locked(c, NEO_ERR_INVALID, "record: B must be >= 1");
+  if (subset && (n_subset < 0 || n_subset > B)) return fail_locked(c, NEO_ERR_INVALID, "record: bad subset size");
+  return NEO_OK;
+}
+
+int neo_record_state_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                         const int32_t *cmd_len, const int32_t *cmd_index, const double *head, double *cur_vel) {
+  int rc = record_check(c, B, subset, n_subset);
+  if (rc) return rc;
+  if (!cmd || !cmd_len || !cmd_index || !head || !cur_vel) return fail_locked(c, NEO_ERR_INVALID, "record state: null buffer");
+  if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, "record state: cap must be > 0");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const FleetArgs f{B, subset, n_subset};
+  if (f.launched() == 0) return NEO_OK;
+  rc = record_state(c, f, cmd, cap, cmd_len, cmd_index, head, cur_vel);
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+int neo_record_commit_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, const double *x, const double *head,
+                          const double *tail, const int32_t *solved, const double *pose, const double *cur_vel,
+                          const uint8_t *staging, int width, int height, const int32_t *mission_ids, int tick, int round,
+                          int capacity, double *motion, double *wpts_local, double *tau, double *pose_rows, int32_t *meta,
+                          uint8_t *images, int32_t *row_of, int32_t *n_rows, int32_t *dropped) {
+  int rc = record_check(c, B, subset, n_subset);
+  if (rc) return rc;
+  if (M < 2 || M > NEO_MAX_PIECES) return fail_locked(c, NEO_ERR_INVALID, "record commit: M must be in 2 .. 64");
+  if (capacity < 1) return fail_locked(c, NEO_ERR_INVALID, "record commit: capacity must be >= 1");
+  if (width < 1 || width > 4096 || height < 1 || height > 4096)
+    return fail_locked(c, NEO_ERR_INVALID, "record commit: width and height must be in 1 .. 4096");
+  if (!x || !head || !tail || !pose || !cur_vel || !staging || !motion || !wpts_local || !tau || !pose_rows || !meta ||
+      !images || !row_of || !n_rows || !dropped)
+    return fail_locked(c, NEO_ERR_INVALID, "record commit: null buffer");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const FleetArgs f{B, subset, n_subset};
+  if (f.launched() == 0) return NEO_OK;
+  rc = record_commit(c, f, RecordCommitArgs{M, x, head, tail, solved, pose, cur_vel, staging, width, height, mission_ids,
+                                            tick, round, capacity, motion, wpts_local, tau, pose_rows, meta, images, row_of,
+                                            n_rows, dropped});
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
 // ---- the `batch` planner mode on resident arrays (traj_planner/expert_planner.py:103-168; kernels: neo_batch.hpp)
 static const double kBatchOffset = 0.6;  // :135
 static int batch_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M, int D, int K) {

@@ -254,6 +254,26 @@ int fleet_audit(neo_ctx *c, const FleetArgs &f, const FleetAuditArgs &a);
 int fleet_pose(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const double *cur_pos, const double *goal, double eye_z,
                double *pose);
 
+// neo_record_*_dev: the fleet's `record` mode (neo_disp_record.hip, kernels in neo_record.hpp).  Every pointer is a
+// device array; the arguments were checked by the C ABI.
+struct RecordCommitArgs {
+  int M;
+  const double *x, *head, *tail;  // [B][n], [B][3][2], [B][3][2] by mission
+  const int *solved;              // [B], or NULL: every launched mission
+  const double *pose, *cur_vel;   // [B][5], [B][2]
+  const unsigned char *staging;   // [B][H][W]
+  int W, H;
+  const int *mission_ids;         // [B], or NULL: the mission's index
+  int tick, round, capacity;
+  double *motion, *wpts_local, *tau, *pose_rows;  // the dataset, `capacity` rows each
+  int *meta;
+  unsigned char *images;
+  int *row_of, *n_rows, *dropped;  // [launched], [1], [1]
+};
+int record_state(neo_ctx *c, const FleetArgs &f, const double *cmd, int cap, const int *cmd_len, const int *cmd_index,
+                 const double *head, double *cur_vel);
+int record_commit(neo_ctx *c, const FleetArgs &f, const RecordCommitArgs &a);  // rank, then commit
+
 // neo_batch_*_dev: the `batch` planner mode on resident arrays (neo_disp_batch.hip, kernels in neo_batch.hpp).  P =
 // f.launched() requests; tau, off and w are HOST arrays (M, K and 4 values), handed to the kernels by value.
 struct BatchCandArgs {

@@ -13,7 +13,10 @@ from .geo import GeoPlanner  # noqa: F401
 from .fleet import FleetReplanLoop  # noqa: F401
 from .depth import DepthCamera  # noqa: F401
 from .onboard import OnboardMapper  # noqa: F401
+from .record import DemoRecorder  # noqa: F401
+from .training import train_initializer  # noqa: F401  (torch and the network are imported when it is called)
 # the initializer network (torch) is imported on demand: `from neo_planner_amd import initializer`
 
 __all__ = ["Context", "NeoError", "default_context", "ESDF", "ESDF3D", "BatchPlanner", "MinJerkPlanner",
-           "PlannerConfig", "GeoPlanner", "FleetReplanLoop", "DepthCamera", "OnboardMapper"]
+           "PlannerConfig", "GeoPlanner", "FleetReplanLoop", "DepthCamera", "OnboardMapper", "DemoRecorder",
+           "train_initializer"]

@@ -54,7 +54,7 @@ EXPORTS = [
     "neo_batch_candidates_dev", "neo_batch_select", "neo_batch_select_dev", "neo_plan_guess", "neo_plan_guess_dev",
     "neo_plan_merge", "neo_plan_merge_dev", "neo_depth_render_batch", "neo_depth_render_batch_dev",
     "neo_depth_box_test_counter", "neo_onboard_integrate_batch", "neo_onboard_integrate_batch_dev",
-    "neo_esdf_build_2d_batch_dev", "neo_fleet_pose_dev",
+    "neo_esdf_build_2d_batch_dev", "neo_fleet_pose_dev", "neo_record_state_dev", "neo_record_commit_dev",
 ]
 
 
@@ -144,6 +144,8 @@ def load():
     L.neo_onboard_integrate_batch_dev.argtypes = list(_onboard)
     L.neo_esdf_build_2d_batch_dev.argtypes = [c_p, c_p, c_i, c_p, c_i, c_i, c_d, c_p]
     L.neo_fleet_pose_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_d, c_p]
+    L.neo_record_state_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p]
+    L.neo_record_commit_dev.argtypes = [c_p, c_i, c_p, c_i, c_i] + [c_p] * 7 + [c_i, c_i, c_p, c_i, c_i, c_i] + [c_p] * 9
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]

@@ -26,6 +26,13 @@ command array (neo_fleet_pose_dev), mapper.update renders, integrates and rebuil
 each mission's onboard scene.  The final audit is taken on the true maps: the flight metric is measured against the
 world, not the belief.
 
+With record=DemoRecorder the fleet keeps what its expert did (the reference's `selected_planner:=record`,
+traj_planner/record_planner.py): once a tick, after the advance and before the targets, the active missions' poses
+(neo_fleet_pose_dev), their velocities now (neo_record_state_dev) and their depth images go into the recorder's
+per-mission buffers, and every target round, just before the splice, one neo_record_commit_dev appends a row for each
+mission whose plan solved.  The flights are the same with and without it, and no host read is added: the rows and
+their counters stay on the device until the recorder is asked.
+
 A mission's flight does not depend on which other missions share the fleet: the kernels work per mission, the target
 jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
 retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream_ids`).
@@ -69,22 +76,28 @@ class FleetReplanLoop:
     scene_ids only the final audit; scenes = (boxes (NB, 6), box_begin (S + 1,)) as DepthCamera.pack_scenes returns them
     and scene_index (B,) (None: scene 0) say what each mission's camera sees; des_pos_z is the eye's height.  run() starts
     from onboard.reset(): every flight begins knowing nothing, whatever the mapper saw before.
-    record_poses adds `poses` (ticks, B, 5) and `sensed` (ticks, B) to the result."""
+    record_poses adds `poses` (ticks, B, 5) and `sensed` (ticks, B) to the result.
+    record: a DemoRecorder (record.py) -- every spliced plan becomes a row of its dataset, in the order (tick, target
+    round, ascending mission); works with every mode, resident or not, with or without onboard, and needs scenes /
+    scene_index as onboard does (the recorder's camera looks at the same scenes).  run() appends to what the recorder
+    holds: recorder.reset() starts over.  With onboard set as well the images are rendered twice a tick, once by the
+    mapper (float32 metres) and once for the recorder (uint8), from the same poses."""
 
     def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
                  longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
                  scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False, onboard=None, scenes=None,
-                 scene_index=None, des_pos_z=2.0, record_poses=False):
+                 scene_index=None, des_pos_z=2.0, record_poses=False, record=None):
         if mode not in ("basic", "geo", "batch"):
             raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo' or 'batch'")
         if resident and mode == "geo":
             raise ValueError("FleetReplanLoop: resident=True needs mode 'basic' or 'batch' (geo_plan has no resident form)")
         if onboard is not None and mode == "geo":
             raise ValueError("FleetReplanLoop: onboard maps need mode 'basic' or 'batch' (geo on onboard maps is not built)")
-        if onboard is not None and scenes is None:
-            raise ValueError("FleetReplanLoop: onboard needs scenes=(boxes, box_begin), what the cameras see")
+        if (onboard is not None or record is not None) and scenes is None:
+            raise ValueError("FleetReplanLoop: onboard and record need scenes=(boxes, box_begin), what the cameras see")
         self.resident = bool(resident)
         self.onboard, self.scenes, self.des_pos_z, self.record_poses = onboard, scenes, float(des_pos_z), bool(record_poses)
+        self.record = record
         self.scene_index = None if scene_index is None else np.ascontiguousarray(scene_index, dtype=np.int32).reshape(-1)
         self.bp, self.map, self.mode = batch_planner, map, mode
         self.goals = _lib.as_f64(goals).reshape(-1, 2)
@@ -101,8 +114,14 @@ class FleetReplanLoop:
         self.mission_ids = np.arange(self.B) if mission_ids is None else np.asarray(mission_ids).reshape(-1)
         if self.mission_ids.shape[0] != self.B or (self.scene_ids is not None and self.scene_ids.shape[0] != self.B):
             raise ValueError("FleetReplanLoop: one mission id and one scene id per goal")
-        if onboard is not None and (onboard.B != self.B or (self.scene_index is not None and self.scene_index.shape[0] != self.B)):
-            raise ValueError("FleetReplanLoop: the onboard mapper and scene_index must have one entry per goal")
+        if onboard is not None and onboard.B != self.B:
+            raise ValueError("FleetReplanLoop: the onboard mapper must have one entry per goal")
+        if (onboard is not None or record is not None) and self.scene_index is not None and self.scene_index.shape[0] != self.B:
+            raise ValueError("FleetReplanLoop: scene_index must have one entry per goal")
+        if record is not None and record.M != int(batch_planner.cfg.init_wpts_num) + 1:
+            raise ValueError("FleetReplanLoop: the recorder's M must be the planner's init_wpts_num + 1")
+        if record is not None and record.ctx is not batch_planner.ctx:
+            raise ValueError("FleetReplanLoop: the recorder and the planner must share one context")
         # what targets and plans see: the missions' onboard scenes, or the given map(s)
         self.plan_map = map if onboard is None else onboard
         self.plan_scene_ids = self.scene_ids if onboard is None else onboard.scene_ids
@@ -152,6 +171,31 @@ class FleetReplanLoop:
             sensed[active] = True
             self._sensed.append(sensed)
 
+    def _record_tick(self, active, tm):
+        """record: the active missions' poses (the ones _sense took, with onboard), their velocities now and their depth
+        images into the recorder's per-mission buffers"""
+        c, d, p, rec = self.bp.ctx, self._dev, self._p, self.record
+        t0 = time.perf_counter()
+        sub = self._subset(active)
+        self._sync()
+        if self.onboard is None:
+            c.check(c.lib.neo_fleet_pose_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
+                                             p(d["cmd_index"]), p(d["cur_pos"]), p(d["goal"]), self.des_pos_z, p(d["pose"])))
+        c.check(c.lib.neo_record_state_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
+                                           p(d["cmd_index"]), p(d["head"]), p(rec.cur_vel)))
+        c.synchronize()
+        whole = active.size == self.B
+        idx64 = None if whole else sub.long()
+        pose_k = d["pose"] if whole else d["pose"].index_select(0, idx64).contiguous()
+        sidx = d["scene_index"]
+        sidx_k = sidx if (sidx is None or whole) else sidx.index_select(0, idx64).contiguous()
+        img = rec.camera.render_dev(d["boxes"], d["box_begin"], pose_k, sidx_k, chunk=rec.chunk, want_m=False)["depth_u8"]
+        if whole:
+            rec.staging.copy_(img)
+        else:
+            rec.staging.index_copy_(0, idx64, img)
+        tm["record_s"] = time.perf_counter() - t0
+
     def _advance(self, sub):
         c, d, p = self.bp.ctx, self._dev, self._p
         step = int(round(self.replan_period * self.cmd_hz))
@@ -193,13 +237,19 @@ class FleetReplanLoop:
         self._dev["plan_slots"] = self._dev["slots"]
         if self.onboard is not None:
             self.onboard.reset()      # all unknown, and the slots as the map table numbers them now
+            self._dev.update(plan_slots=self.onboard.slots)
+        if self.onboard is not None or self.record is not None:      # what the cameras see, and where they look from
             boxes, box_begin = self.scenes
-            self._dev.update(plan_slots=self.onboard.slots, pose=f(B, 5),
+            self._dev.update(pose=f(B, 5),
                              boxes=torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 6)).to(dev),
                              box_begin=torch.from_numpy(np.ascontiguousarray(box_begin, dtype=np.int32)).to(dev),
                              scene_index=None if self.scene_index is None else torch.from_numpy(self.scene_index).to(dev))
             if self._dev["boxes"].shape[0] == 0:      # (a scene list without any box still hands over a valid pointer)
                 self._dev["boxes"] = f(1, 6)
+        if self.record is not None:
+            self.record.bind(B)
+            self.record.T_min, self.record.T_max = float(self.bp.cfg.T_min), float(self.bp.cfg.T_max)   # what rows() maps tau with
+            self._dev["mission_ids"] = self._subset(self.mission_ids)
         self._poses, self._sensed = [], []
         self._up("goal", self.goals)
 
@@ -315,6 +365,8 @@ class FleetReplanLoop:
                 self._up("head", head)
             if self.onboard is not None:
                 self._sense(active, tm)
+            if self.record is not None:
+                self._record_tick(active, tm)
             pending = active
             for r in range(MAX_TARGETS):
                 t0 = time.perf_counter()
@@ -352,6 +404,8 @@ class FleetReplanLoop:
                     self._up("x", x)
                     self._up("solved", solved)
                 self._sync()
+                if self.record is not None:      # the round's rows, from the plans about to be spliced
+                    self.record.commit(B, sub, d["x"], d["head"], d["tail"], d["solved"], d["pose"], d["mission_ids"], tick, r)
                 self._splice(sub, M, first=(tick == 0))
                 bp.ctx.synchronize()
                 tm["fleet_s"] += time.perf_counter() - t0
@@ -366,7 +420,7 @@ class FleetReplanLoop:
             stuck = (flags & (_lib.NEO_FLEET_FLAG_CMD_FULL | _lib.NEO_FLEET_FLAG_SPLICE_FAILED)) != 0
             active = active[~(abandoned | landed | stuck)[active]]
             tm["tick_s"] = time.perf_counter() - t_tick
-            tm["host_s"] = tm["tick_s"] - tm["fleet_s"] - tm["plan_s"] - tm.get("sense_s", 0.0)
+            tm["host_s"] = tm["tick_s"] - tm["fleet_s"] - tm["plan_s"] - tm.get("sense_s", 0.0) - tm.get("record_s", 0.0)
             self.timings.append(tm)
         return self._finish(replans, failed, iter_num, opt_runs, abandoned, landed)
 
