@@ -189,9 +189,16 @@ class HostStage {
   template <typename T>
   Ref<T> out(T *host, size_t count, size_t reserve = 0) { return {add(2, nullptr, host, count * sizeof(T), reserve * sizeof(T))}; }
 
+  // an array the caller may leave out (a subset, slots, ...): staged like in() / inout() when it is given; dev() of
+  // the field is NULL when it is not, which is what the `_dev` form takes for "none"
+  template <typename T>
+  Ref<T> in_optional(const T *host, size_t count) { return {add(0, host, nullptr, host ? count * sizeof(T) : 0, sizeof(T), !host)}; }
+  template <typename T>
+  Ref<T> inout_optional(T *host, size_t count) { return {add(1, host, host, host ? count * sizeof(T) : 0, 0, !host)}; }
+
   // the field's device array: valid from upload() on (growing the scratch moves it), NULL before
   template <typename T>
-  T *dev(Ref<T> r) const { return dbase_ ? reinterpret_cast<T *>(dbase_ + f_[r.i].off) : nullptr; }
+  T *dev(Ref<T> r) const { return dbase_ && !f_[r.i].absent ? reinterpret_cast<T *>(dbase_ + f_[r.i].off) : nullptr; }
 
   int upload() {
     if (!ordered_) return fail(c_, NEO_ERR_INVALID, "internal: staged fields declared out of order");
@@ -234,15 +241,16 @@ class HostStage {
     size_t off, bytes;
     const void *src;  // host array copied up, or NULL
     void *dst;        // host array copied back, or NULL
+    bool absent;      // an optional field the caller left out
   };
-  int add(int role, const void *src, void *dst, size_t bytes, size_t reserve) {
+  int add(int role, const void *src, void *dst, size_t bytes, size_t reserve, bool absent = false) {
     ordered_ = ordered_ && role >= role_;
     role_ = role;
     const size_t off = (end_ + 255) & ~size_t(255);
     if (role >= 1) out_begin_ = std::min(out_begin_, off);
     if (role == 2) in_end_ = std::min(in_end_, off);
     end_ = off + std::max(bytes, reserve);
-    f_.push_back({off, bytes, src, dst});
+    f_.push_back({off, bytes, src, dst, absent});
     return (int)f_.size() - 1;
   }
   neo_ctx *c_;
@@ -332,6 +340,52 @@ int fail_locked(neo_ctx *c, int code, const char *msg) {
   std::lock_guard<std::recursive_mutex> g(c->mu);
   return fail(c, code, msg);
 }
+
+// the end of a `_dev` entry point: the launcher's return code, then the launch's own error
+int launched(neo_ctx *c, int rc) {
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return NEO_OK;
+}
+
+// the (B, subset, n_subset) of the entry points that take a launch list (context unlocked): B_min <= B, B <= B_max
+// where there is a bound (a power of two), at most B entries
+int list_check(neo_ctx *c, const char *who, int B, int B_min, int B_max, const int32_t *subset, int n_subset) {
+  if (!c) return NEO_ERR_INVALID;
+  if (B < B_min || B > B_max) {
+    std::string msg = std::string(who) + ": B must be ";
+    if (B_max == INT32_MAX) {
+      msg += ">= " + std::to_string(B_min);
+    } else {
+      int k = 0;
+      while ((1 << k) < B_max) ++k;
+      msg += "in " + std::to_string(B_min) + " .. 2^" + std::to_string(k);
+    }
+    return fail_locked(c, NEO_ERR_INVALID, msg.c_str());
+  }
+  if (subset && (n_subset < 0 || n_subset > B))
+    return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": bad subset size").c_str());
+  return NEO_OK;
+}
+
+// the six result arrays of an optimiser launch through a stage: the packed rows go up, the request-indexed ones go up
+// and come back (rows outside the launch stay); an array the caller left out stays out
+struct RowRefs {
+  HostStage::Ref<double> x, costs4, costs4_last;
+  HostStage::Ref<int32_t> nit, nfev, status;
+};
+RowRefs stage_rows_in(HostStage &st, const RunRowsIn &r, size_t rows, size_t n) {
+  return {st.in(r.x, rows * n), st.in(r.costs4, rows * 4), st.in(r.costs4_last, rows * 4), st.in(r.nit, rows),
+          st.in_optional(r.nfev, rows), st.in(r.status, rows)};
+}
+RowRefs stage_rows_inout(HostStage &st, const RunRows &r, size_t rows, size_t n) {
+  return {st.inout(r.x, rows * n), st.inout(r.costs4, rows * 4), st.inout(r.costs4_last, rows * 4),
+          st.inout_optional(r.nit, rows), st.inout_optional(r.nfev, rows), st.inout(r.status, rows)};
+}
+RunRows staged_rows(const HostStage &st, const RowRefs &f) {
+  return {st.dev(f.x), st.dev(f.costs4), st.dev(f.costs4_last), st.dev(f.nit), st.dev(f.nfev), st.dev(f.status)};
+}
+RunRowsIn as_const(const RunRows &r) { return {r.x, r.costs4, r.costs4_last, r.nit, r.nfev, r.status}; }
 
 // dispatch_opt sends this launch to the lane-group kernel (several small trajectories per wavefront, opt-in):
 // on the reference's own map small planar problems (M = 3 -> n = 7), on 3-D fields small problems in fp32 sampling
@@ -852,10 +906,7 @@ int neo_cost_grad_batch_dev(neo_ctx *c, int scene_id, int B, int M, int D, const
   if (B == 0) return NEO_OK;
   ProfScope ps(c, NEO_KERNEL_EVAL);
   const EvalArgs ea{B, M, x, head, tail, cost, costs4, grad, coeffs, status};
-  rc = dispatch_eval(c, it->second, D, ea);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  return launched(c, dispatch_eval(c, it->second, D, ea));
 }
 
 int neo_cost_grad_batch(neo_ctx *c, int scene_id, int B, int M, int D, const double *x, const double *head,
@@ -897,10 +948,7 @@ static int sampled_terms_dev(neo_ctx *c, int scene_id, int B, int M, int D, cons
   ProfScope ps(c, NEO_KERNEL_ESDF_SAMPLE);
   SampleArgs sa{B, M, coeffs, ts, costs2, grad_C, grad_T};
   sa.io32 = io32;
-  rc = dispatch_sample(c, it->second, D, sa);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  return launched(c, dispatch_sample(c, it->second, D, sa));
 }
 
 int neo_sampled_terms_batch_dev(neo_ctx *c, int scene_id, int B, int M, int D, const double *coeffs,
@@ -1016,10 +1064,7 @@ int neo_optimize_batch_from_dev(neo_ctx *c, int scene_id, const int32_t *scene_i
     return fail(c, NEO_ERR_INVALID, "lane-group launch (NEO_FLAG_LANE_GROUPS): neo_optimize_trace, neo_optimize_trace_xg "
                                     "and neo_optimize_progress_counter are not supported");
   ProfScope ps(c, NEO_KERNEL_OPTIMIZE);
-  rc = dispatch_opt(c, kind, elem, layout, D, oa);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  return launched(c, dispatch_opt(c, kind, elem, layout, D, oa));
 }
 
 size_t neo_optimize_state_bytes(int M, int D) {
@@ -1059,10 +1104,7 @@ int neo_optimize_batch_budget_dev(neo_ctx *c, int scene_id, int B, int M, int D,
   oa.subset = subset;
   oa.n_subset = subset ? n_subset : 0;
   oa.traj_total = B;
-  rc = launch_opt_3d_budget(c, it->second.elem, it->second.m3.layout, oa);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  return launched(c, launch_opt_3d_budget(c, it->second.elem, it->second.m3.layout, oa));
 }
 
 int neo_scene_slot(neo_ctx *c, int scene_id) {
@@ -1160,13 +1202,10 @@ int neo_audit_traj_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids,
   if (rc) return rc;
   if (cm.kind == 1 && D != 3) return fail(c, NEO_ERR_INVALID, "audit: a 3-D map needs D = 3");
   if (B == 0) return NEO_OK;
-  AuditArgs aa{B, M, cm.table, scene_ids, cm.nmaps, x, head, tail, hz, {1.0, 1.0, 100.0}, audit, count, flags};
+  AuditArgs aa{B, M, {cm.table, scene_ids, cm.nmaps}, x, head, tail, hz, {1.0, 1.0, 100.0}, audit, count, flags};
   if (weights3)
     for (int k = 0; k < 3; ++k) aa.w[k] = weights3[k];
-  rc = dispatch_audit(c, cm.kind, cm.elem, cm.layout, D, aa);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  return launched(c, dispatch_audit(c, cm.kind, cm.elem, cm.layout, D, aa));
 }
 
 int neo_audit_traj_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, int M, int D, const double *x,
@@ -1273,9 +1312,8 @@ static int onboard_check(neo_ctx *c, int B, const int32_t *subset, int n_subset,
                          const double *origins, double sensor_range, double z_lo, double z_hi, int l_hit, int l_miss,
                          int l_lo, int l_hi, const int8_t *logodds, const int8_t *occupancy, const int32_t *changed, int &N,
                          int &half) {
-  if (!c) return NEO_ERR_INVALID;
-  if (B < 1 || B > (1 << 20)) return fail_locked(c, NEO_ERR_INVALID, "onboard: B must be in 1 .. 2^20");
-  if (subset && (n_subset < 0 || n_subset > B)) return fail_locked(c, NEO_ERR_INVALID, "onboard: bad subset size");
+  int rc = list_check(c, "onboard", B, 1, 1 << 20, subset, n_subset);
+  if (rc) return rc;
   if (width < 1 || width > 4096 || height < 1 || height > 4096)
     return fail_locked(c, NEO_ERR_INVALID, "onboard: width and height must be in 1..4096");
   if (!std::isfinite(focal_px) || !(focal_px > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "onboard: focal_px must be finite and > 0");
@@ -1313,9 +1351,9 @@ int neo_onboard_integrate_batch_dev(neo_ctx *c, int B, const int32_t *subset, in
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const int n_launch = subset ? n_subset : B;
-  if (n_launch == 0) return NEO_OK;
-  return onboard_integrate(c, OnboardCall{B, n_launch, subset, depth_m, pose, width, height, focal_px, grid_w, grid_h, res,
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return onboard_integrate(c, OnboardCall{list, depth_m, pose, width, height, focal_px, grid_w, grid_h, res,
                                           origins, sensor_range, z_lo, z_hi, l_hit, l_miss, l_lo, l_hi, N, half, logodds,
                                           occupancy, changed});
 }
@@ -1339,11 +1377,11 @@ int neo_onboard_integrate_batch(neo_ctx *c, int B, const int32_t *subset, int n_
   }
   std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
   hipSetDevice(c->device);
-  const size_t bs = (size_t)B, nl = subset ? (size_t)n_subset : bs, hw = (size_t)width * height;
+  const size_t bs = (size_t)B, nl = (size_t)launch_list(B, subset, n_subset).n, hw = (size_t)width * height;
   const size_t ncell = (size_t)grid_w * grid_h;
   if (nl == 0) return NEO_OK;
   HostStage st(c, 0);
-  const auto fsub = st.in(subset, subset ? nl : 0, 1);
+  const auto fsub = st.in_optional(subset, nl);
   const auto fd = st.in(depth_m, nl * hw);
   const auto fp = st.in(pose, nl * 5);
   const auto fo = st.in(origins, bs * 2);
@@ -1352,7 +1390,7 @@ int neo_onboard_integrate_batch(neo_ctx *c, int B, const int32_t *subset, int n_
   const auto fg = st.inout(changed, bs);
   rc = st.upload();
   if (rc) return rc;
-  rc = neo_onboard_integrate_batch_dev(c, B, subset ? st.dev(fsub) : nullptr, n_subset, st.dev(fd), st.dev(fp), width, height,
+  rc = neo_onboard_integrate_batch_dev(c, B, st.dev(fsub), n_subset, st.dev(fd), st.dev(fp), width, height,
                                        focal_px, max_range, grid_w, grid_h, res, st.dev(fo), sensor_range, z_lo, z_hi, l_hit,
                                        l_miss, l_lo, l_hi, st.dev(fl), st.dev(fc), st.dev(fg));
   if (rc) return rc;
@@ -1360,25 +1398,17 @@ int neo_onboard_integrate_batch(neo_ctx *c, int B, const int32_t *subset, int n_
 }
 
 // ---- fleet replan loop (ros_node/traj_planner_node.py:390-578; kernels: neo_fleet.hpp)
-static int fleet_check(neo_ctx *c, int B, const int32_t *subset, int n_subset) {
-  if (!c) return NEO_ERR_INVALID;
-  if (B < 0) return fail_locked(c, NEO_ERR_INVALID, "fleet: B must be >= 0");
-  if (subset && (n_subset < 0 || n_subset > B)) return fail_locked(c, NEO_ERR_INVALID, "fleet: bad subset size");
-  return NEO_OK;
-}
 static bool fleet_positive(double v) { return std::isfinite(v) && v > 0.0; }
 
-// the 2-D maps of a fleet call (context locked): FleetArgs' table, slots and nmaps
-static int fleet_maps(neo_ctx *c, int scene_id, const int32_t *slots, FleetArgs &f) {
+// the 2-D maps of a fleet call (context locked)
+static int fleet_maps(neo_ctx *c, int scene_id, const int32_t *slots, MapRef &m) {
   int rc = rebuild_tables(c);
   if (rc) return rc;
   CallMaps cm;
   rc = resolve_call_maps(c, scene_id, slots != nullptr, cm);
   if (rc) return rc;
   if (cm.kind != 0) return fail(c, NEO_ERR_INVALID, "fleet: the 2-D reference map only (a 3-D map was given)");
-  f.table = cm.table;
-  f.slots = slots;
-  f.nmaps = cm.nmaps;
+  m = {cm.table, slots, cm.nmaps};
   return NEO_OK;
 }
 
@@ -1386,7 +1416,7 @@ static int fleet_target_check(neo_ctx *c, int B, const int32_t *subset, int n_su
                               const double *goal, const double *jitter, double longitu, double lateral, double move_vel,
                               const double *tail, const int32_t *near_goal, const int32_t *lateral_steps,
                               const int32_t *flags) {
-  int rc = fleet_check(c, B, subset, n_subset);
+  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
   if (rc) return rc;
   if (!cur_pos || !goal || !jitter || !tail || !near_goal || !lateral_steps || !flags)
     return fail_locked(c, NEO_ERR_INVALID, "fleet target: null buffer");
@@ -1405,15 +1435,13 @@ int neo_fleet_target_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_id
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  FleetArgs f{B, subset, n_subset};
-  rc = fleet_maps(c, scene_id, scene_ids, f);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  MapRef maps;
+  rc = fleet_maps(c, scene_id, scene_ids, maps);
   if (rc) return rc;
-  if (f.launched() == 0) return NEO_OK;
-  rc = fleet_target(c, f, {cur_pos, goal, jitter, longitu_step_dis, lateral_step_length, move_vel, tail, near_goal,
-                           lateral_steps, flags});
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  if (list.n == 0) return NEO_OK;
+  return launched(c, fleet_target(c, list, maps, {cur_pos, goal, jitter, longitu_step_dis, lateral_step_length, move_vel,
+                                                  tail, near_goal, lateral_steps, flags}));
 }
 
 int neo_fleet_target_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset, int n_subset,
@@ -1436,14 +1464,13 @@ int neo_fleet_target_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, i
   HostStage st(c, kStagedUpTo);
   const auto fp = st.in(cur_pos, bs * 2), fg = st.in(goal, bs * 2), fj = st.in(jitter, bs * 2);
   const auto fs = st.in(scene_ids ? slots.data() : nullptr, bs);
-  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
+  const auto fsub = st.in_optional(subset, (size_t)n_subset);
   const auto ft = st.inout(tail, bs * 6);
   const auto fn = st.inout(near_goal, bs), fl = st.inout(lateral_steps, bs), ff = st.inout(flags, bs);
   rc = st.upload();
   if (rc) return rc;
   rc = neo_fleet_target_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fs) : nullptr, B,
-                                  subset ? st.dev(fsub) : nullptr, n_subset, st.dev(fp), st.dev(fg), st.dev(fj),
-                                  longitu_step_dis, lateral_step_length, move_vel, st.dev(ft), st.dev(fn), st.dev(fl),
+                                  st.dev(fsub), n_subset, st.dev(fp), st.dev(fg), st.dev(fj), longitu_step_dis, lateral_step_length, move_vel, st.dev(ft), st.dev(fn), st.dev(fl),
                                   st.dev(ff));
   if (rc) return rc;
   return st.download();
@@ -1460,7 +1487,7 @@ static int fleet_cmd_check(neo_ctx *c, const char *who, const double *cmd, int c
 int neo_fleet_advance_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
                           const int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index, int step, int ahead,
                           double *cur_pos, double *head) {
-  int rc = fleet_check(c, B, subset, n_subset);
+  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
   if (rc) return rc;
   rc = fleet_cmd_check(c, "fleet advance", cmd, cap, cmd_len, cmd_index, future_index);
   if (rc) return rc;
@@ -1469,38 +1496,32 @@ int neo_fleet_advance_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset
     return fail_locked(c, NEO_ERR_INVALID, "fleet advance: step and ahead must be in 0 .. 2^30");
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const FleetArgs f{B, subset, n_subset};
-  if (f.launched() == 0) return NEO_OK;
-  rc = fleet_advance(c, f, {const_cast<double *>(cmd), cap, const_cast<int32_t *>(cmd_len), cmd_index, future_index}, step,
-                     ahead, cur_pos, head);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, fleet_advance(c, list, {const_cast<double *>(cmd), cap, const_cast<int32_t *>(cmd_len), cmd_index,
+                                             future_index}, step, ahead, cur_pos, head));
 }
 
 int neo_fleet_pose_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
                        const int32_t *cmd_len, const int32_t *cmd_index, const double *cur_pos, const double *goal,
                        double eye_z, double *pose) {
-  int rc = fleet_check(c, B, subset, n_subset);
+  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
   if (rc) return rc;
   if (!cmd || !cmd_len || !cmd_index || !cur_pos || !goal || !pose) return fail_locked(c, NEO_ERR_INVALID, "fleet pose: null buffer");
   if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, "fleet pose: cap must be > 0");
   if (!std::isfinite(eye_z)) return fail_locked(c, NEO_ERR_INVALID, "fleet pose: eye_z must be finite");
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const FleetArgs f{B, subset, n_subset};
-  if (f.launched() == 0) return NEO_OK;
-  rc = fleet_pose(c, f, {const_cast<double *>(cmd), cap, const_cast<int32_t *>(cmd_len), const_cast<int32_t *>(cmd_index), nullptr},
-                  cur_pos, goal, eye_z, pose);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, fleet_pose(c, list, {const_cast<double *>(cmd), cap, const_cast<int32_t *>(cmd_len),
+                                          const_cast<int32_t *>(cmd_index), nullptr}, cur_pos, goal, eye_z, pose));
 }
 
 int neo_fleet_splice_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, const double *x, const double *head,
                          const double *tail, const int32_t *solved, double hz, int first, double *cmd, int cap,
                          int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index, int32_t *flags) {
-  int rc = fleet_check(c, B, subset, n_subset);
+  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
   if (rc) return rc;
   rc = check_shape(c, B, M, 2);
   if (rc) return rc;
@@ -1510,18 +1531,16 @@ int neo_fleet_splice_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset,
   if (!fleet_positive(hz)) return fail_locked(c, NEO_ERR_INVALID, "fleet splice: hz must be finite and > 0");
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const FleetArgs f{B, subset, n_subset};
-  if (f.launched() == 0) return NEO_OK;
-  rc = fleet_splice(c, f, {cmd, cap, cmd_len, cmd_index, future_index}, {M, x, head, tail, solved, hz, first ? 1 : 0, flags});
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, fleet_splice(c, list, {cmd, cap, cmd_len, cmd_index, future_index},
+                                  {M, x, head, tail, solved, hz, first ? 1 : 0, flags}));
 }
 
 static int fleet_audit_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
                              const int32_t *n_flown, int stride, double cmd_hz, const double *audit, const int32_t *count,
                              const int32_t *flags) {
-  int rc = fleet_check(c, B, subset, n_subset);
+  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
   if (rc) return rc;
   if (!cmd || !n_flown || !audit || !count || !flags) return fail_locked(c, NEO_ERR_INVALID, "fleet audit: null buffer");
   if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, "fleet audit: cap must be > 0");
@@ -1537,17 +1556,15 @@ int neo_fleet_audit_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  FleetArgs f{B, subset, n_subset};
-  rc = fleet_maps(c, scene_id, scene_ids, f);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  MapRef maps;
+  rc = fleet_maps(c, scene_id, scene_ids, maps);
   if (rc) return rc;
-  if (f.launched() == 0) return NEO_OK;
+  if (list.n == 0) return NEO_OK;
   FleetAuditArgs aa{cmd, cap, n_flown, stride, cmd_hz, {1.0, 1.0, 100.0}, audit, count, flags};
   if (weights3)
     for (int k = 0; k < 3; ++k) aa.w[k] = weights3[k];
-  rc = fleet_audit(c, f, aa);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  return launched(c, fleet_audit(c, list, maps, aa));
 }
 
 int neo_fleet_audit_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset, int n_subset,
@@ -1568,40 +1585,30 @@ int neo_fleet_audit_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, in
   const auto fc = st.in(cmd, bs * cap * 6);
   const auto fnf = st.in(n_flown, bs);
   const auto fs = st.in(scene_ids ? slots.data() : nullptr, bs);
-  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
+  const auto fsub = st.in_optional(subset, (size_t)n_subset);
   const auto fa = st.inout(audit, bs * NEO_AUDIT_FIELDS);  // (missions outside the subset keep their records)
   const auto fcnt = st.inout(count, bs), ffl = st.inout(flags, bs);
   rc = st.upload();
   if (rc) return rc;
   rc = neo_fleet_audit_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fs) : nullptr, B,
-                                 subset ? st.dev(fsub) : nullptr, n_subset, st.dev(fc), cap, st.dev(fnf), stride, cmd_hz,
+                                 st.dev(fsub), n_subset, st.dev(fc), cap, st.dev(fnf), stride, cmd_hz,
                                  weights3, st.dev(fa), st.dev(fcnt), st.dev(ffl));
   if (rc) return rc;
   return st.download();
 }
 
 // ---- the fleet's record mode (traj_planner/record_planner.py:13-72; kernels: neo_record.hpp)
-static int record_check(neo_ctx *c, int B, const int32_t *subset, int n_subset) {
-  if (!c) return NEO_ERR_INVALID;
-  if (B < 1) return fail_locked(c, NEO_ERR_INVALID, "record: B must be >= 1");
-  if (subset && (n_subset < 0 || n_subset > B)) return fail_locked(c, NEO_ERR_INVALID, "record: bad subset size");
-  return NEO_OK;
-}
-
 int neo_record_state_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
                          const int32_t *cmd_len, const int32_t *cmd_index, const double *head, double *cur_vel) {
-  int rc = record_check(c, B, subset, n_subset);
+  int rc = list_check(c, "record", B, 1, INT32_MAX, subset, n_subset);
   if (rc) return rc;
   if (!cmd || !cmd_len || !cmd_index || !head || !cur_vel) return fail_locked(c, NEO_ERR_INVALID, "record state: null buffer");
   if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, "record state: cap must be > 0");
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const FleetArgs f{B, subset, n_subset};
-  if (f.launched() == 0) return NEO_OK;
-  rc = record_state(c, f, cmd, cap, cmd_len, cmd_index, head, cur_vel);
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, record_state(c, list, cmd, cap, cmd_len, cmd_index, head, cur_vel));
 }
 
 int neo_record_commit_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, const double *x, const double *head,
@@ -1609,7 +1616,7 @@ int neo_record_commit_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset
                           const uint8_t *staging, int width, int height, const int32_t *mission_ids, int tick, int round,
                           int capacity, double *motion, double *wpts_local, double *tau, double *pose_rows, int32_t *meta,
                           uint8_t *images, int32_t *row_of, int32_t *n_rows, int32_t *dropped) {
-  int rc = record_check(c, B, subset, n_subset);
+  int rc = list_check(c, "record", B, 1, INT32_MAX, subset, n_subset);
   if (rc) return rc;
   if (M < 2 || M > NEO_MAX_PIECES) return fail_locked(c, NEO_ERR_INVALID, "record commit: M must be in 2 .. 64");
   if (capacity < 1) return fail_locked(c, NEO_ERR_INVALID, "record commit: capacity must be >= 1");
@@ -1620,20 +1627,17 @@ int neo_record_commit_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset
     return fail_locked(c, NEO_ERR_INVALID, "record commit: null buffer");
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const FleetArgs f{B, subset, n_subset};
-  if (f.launched() == 0) return NEO_OK;
-  rc = record_commit(c, f, RecordCommitArgs{M, x, head, tail, solved, pose, cur_vel, staging, width, height, mission_ids,
-                                            tick, round, capacity, motion, wpts_local, tau, pose_rows, meta, images, row_of,
-                                            n_rows, dropped});
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, record_commit(c, list, RecordCommitArgs{M, x, head, tail, solved, pose, cur_vel, staging, width, height,
+                                                             mission_ids, tick, round, capacity, motion, wpts_local, tau,
+                                                             pose_rows, meta, images, row_of, n_rows, dropped}));
 }
 
 // ---- the `batch` planner mode on resident arrays (traj_planner/expert_planner.py:103-168; kernels: neo_batch.hpp)
 static const double kBatchOffset = 0.6;  // :135
 static int batch_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M, int D, int K) {
-  int rc = fleet_check(c, B, subset, n_subset);
+  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
   if (rc) return rc;
   if (D != 2) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": D must be 2 (the reference's lateral candidates are 2-D)").c_str());
   if (K < 1 || K > NEO_BATCH_MAX_CANDIDATES)
@@ -1641,7 +1645,7 @@ static int batch_check(neo_ctx *c, const char *who, int B, const int32_t *subset
   rc = check_shape(c, B, M, D);
   if (rc) return rc;
   if (M < 2) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": M must be >= 2 (at least one waypoint)").c_str());
-  if ((long long)(subset ? n_subset : B) * K > (long long)INT32_MAX)
+  if ((long long)launch_list(B, subset, n_subset).n * K > (long long)INT32_MAX)
     return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": more than 2^31 - 1 candidate rows").c_str());
   return NEO_OK;
 }
@@ -1659,16 +1663,13 @@ int neo_batch_candidates_dev(neo_ctx *c, int B, const int32_t *subset, int n_sub
     return fail_locked(c, NEO_ERR_INVALID, "batch candidates: null buffer");
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const FleetArgs f{B, subset, n_subset};
-  if (f.launched() == 0) return NEO_OK;
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
   double off[NEO_BATCH_MAX_CANDIDATES];
   batch_default_offsets(K, off);
   if (lateral_offsets)
     for (int k = 0; k < K; ++k) off[k] = lateral_offsets[k];
-  rc = batch_candidates(c, f, {M, K, head, tail, slots, tau, off, x0, head_k, tail_k, slots_k});
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  return launched(c, batch_candidates(c, list, {M, K, head, tail, slots, tau, off, x0, head_k, tail_k, slots_k}));
 }
 
 int neo_batch_candidates(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *head,
@@ -1678,36 +1679,33 @@ int neo_batch_candidates(neo_ctx *c, int B, const int32_t *subset, int n_subset,
   if (rc) return rc;
   if (!head || !tail || !tau || !x0 || !head_k || !tail_k)
     return fail_locked(c, NEO_ERR_INVALID, "batch candidates: null buffer");
-  const size_t bs = (size_t)B, rows = (size_t)(subset ? n_subset : B) * K, n = (size_t)D * (M - 1) + M;
+  const size_t bs = (size_t)B, rows = (size_t)launch_list(B, subset, n_subset).n * K, n = (size_t)D * (M - 1) + M;
   if (rows == 0) return NEO_OK;
   std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
   hipSetDevice(c->device);
   // the packed outputs go up too: the rows of a skipped index come back as they were
   HostStage st(c, kStagedUpTo);
   const auto fh = st.in(head, bs * 6), ft = st.in(tail, bs * 6);
-  const auto fs = st.in(slots, slots ? bs : 0, 1);
-  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
+  const auto fs = st.in_optional(slots, bs), fsub = st.in_optional(subset, (size_t)n_subset);
   const auto fx = st.inout(x0, rows * n), fhk = st.inout(head_k, rows * 6), ftk = st.inout(tail_k, rows * 6);
-  const auto fsk = st.inout(slots_k, slots_k ? rows : 0);
+  const auto fsk = st.inout_optional(slots_k, rows);
   rc = st.upload();
   if (rc) return rc;
-  rc = neo_batch_candidates_dev(c, B, subset ? st.dev(fsub) : nullptr, n_subset, M, D, K, st.dev(fh), st.dev(ft),
-                                slots ? st.dev(fs) : nullptr, tau, lateral_offsets, st.dev(fx), st.dev(fhk), st.dev(ftk),
-                                slots_k ? st.dev(fsk) : nullptr);
+  rc = neo_batch_candidates_dev(c, B, st.dev(fsub), n_subset, M, D, K, st.dev(fh), st.dev(ft), st.dev(fs), tau,
+                                lateral_offsets, st.dev(fx), st.dev(fhk), st.dev(ftk), st.dev(fsk));
   if (rc) return rc;
   return st.download();
 }
 
-static int batch_select_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const void *x_k,
-                              const void *costs4_k, const void *last_k, const void *nit_k, const void *status_k,
-                              const void *chosen, const void *cand_cost, const void *solved, const void *x,
-                              const void *costs4, const void *costs4_last, const void *status, const void *nit_total,
-                              const void *opt_runs, const void *fallback, const void *n_fallback) {
-  int rc = batch_check(c, "batch select", B, subset, n_subset, M, D, K);
+static int batch_select_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const BatchSelectArgs &a) {
+  int rc = batch_check(c, "batch select", B, subset, n_subset, M, D, a.K);
   if (rc) return rc;
-  if (!x_k || !costs4_k || !last_k || !nit_k || !status_k || !chosen || !cand_cost || !solved || !x || !costs4 ||
-      !costs4_last || !status || !nit_total || !opt_runs || !fallback || !n_fallback)
+  const RunRowsIn &k = a.packed;
+  const RunRows &o = a.out;
+  if (!k.x || !k.costs4 || !k.costs4_last || !k.nit || !k.status || !a.chosen || !a.cand_cost || !a.solved || !o.x ||
+      !o.costs4 || !o.costs4_last || !o.status || !a.nit_total || !a.opt_runs || !a.fallback || !a.n_fallback)
     return fail_locked(c, NEO_ERR_INVALID, "batch select: null buffer");
+  if (o.nfev && !k.nfev) return fail_locked(c, NEO_ERR_INVALID, "batch select: nfev without nfev_k");
   return NEO_OK;
 }
 
@@ -1716,23 +1714,19 @@ int neo_batch_select_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset,
                          const int32_t *status_k, const double *weights4, int32_t *chosen, double *cand_cost,
                          int32_t *solved, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
                          int32_t *status, int32_t *nit_total, int32_t *opt_runs, int32_t *fallback, int32_t *n_fallback) {
-  int rc = batch_select_check(c, B, subset, n_subset, M, D, K, x_k, costs4_k, costs4_last_k, nit_k, status_k, chosen,
-                              cand_cost, solved, x, costs4, costs4_last, status, nit_total, opt_runs, fallback, n_fallback);
+  BatchSelectArgs a{D * (M - 1) + M, K, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k}, weights4, chosen, cand_cost,
+                    solved, {x, costs4, costs4_last, nit, nfev, status}, nit_total, opt_runs, fallback, n_fallback};
+  int rc = batch_select_check(c, B, subset, n_subset, M, D, a);
   if (rc) return rc;
-  if (nfev && !nfev_k) return fail_locked(c, NEO_ERR_INVALID, "batch select: nfev without nfev_k");
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const FleetArgs f{B, subset, n_subset};
-  if (f.launched() == 0) {
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) {
     HIPCHK(c, hipMemsetAsync(n_fallback, 0, sizeof(int32_t), c->stream));
     return NEO_OK;
   }
-  rc = batch_select(c, f, {D * (M - 1) + M, K, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k,
-                           weights4 ? weights4 : c->params.weights, chosen, cand_cost, solved, x, costs4, costs4_last,
-                           nit, nfev, status, nit_total, opt_runs, fallback, n_fallback});
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  if (!a.w) a.w = c->params.weights;
+  return launched(c, batch_select(c, list, a));
 }
 
 int neo_batch_select(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *x_k,
@@ -1740,11 +1734,12 @@ int neo_batch_select(neo_ctx *c, int B, const int32_t *subset, int n_subset, int
                      const int32_t *status_k, const double *weights4, int32_t *chosen, double *cand_cost, int32_t *solved,
                      double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev, int32_t *status,
                      int32_t *nit_total, int32_t *opt_runs, int32_t *fallback, int32_t *n_fallback) {
-  int rc = batch_select_check(c, B, subset, n_subset, M, D, K, x_k, costs4_k, costs4_last_k, nit_k, status_k, chosen,
-                              cand_cost, solved, x, costs4, costs4_last, status, nit_total, opt_runs, fallback, n_fallback);
+  const BatchSelectArgs a{D * (M - 1) + M, K, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k}, weights4, chosen,
+                          cand_cost, solved, {x, costs4, costs4_last, nit, nfev, status}, nit_total, opt_runs, fallback,
+                          n_fallback};
+  int rc = batch_select_check(c, B, subset, n_subset, M, D, a);
   if (rc) return rc;
-  if (nfev && !nfev_k) return fail_locked(c, NEO_ERR_INVALID, "batch select: nfev without nfev_k");
-  const size_t bs = (size_t)B, P = (size_t)(subset ? n_subset : B), rows = P * K, n = (size_t)D * (M - 1) + M;
+  const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n;
   if (P == 0) {
     *n_fallback = 0;
     return NEO_OK;
@@ -1753,30 +1748,29 @@ int neo_batch_select(neo_ctx *c, int B, const int32_t *subset, int n_subset, int
   hipSetDevice(c->device);
   // the request-indexed outputs go up too: requests outside the subset, and x of a request without a choice, stay
   HostStage st(c, kStagedUpTo);
-  const auto fx = st.in(x_k, rows * n), fc = st.in(costs4_k, rows * 4), fl = st.in(costs4_last_k, rows * 4);
-  const auto fni = st.in(nit_k, rows), fnf = st.in(nfev_k, nfev_k ? rows : 0, 1), fst = st.in(status_k, rows);
-  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
+  const RowRefs fk = stage_rows_in(st, a.packed, P * K, (size_t)a.n);
+  const auto fsub = st.in_optional(subset, (size_t)n_subset);
   const auto och = st.inout(chosen, bs);
   const auto occ = st.inout(cand_cost, bs * K);
   const auto oso = st.inout(solved, bs);
-  const auto ox = st.inout(x, bs * n), oc = st.inout(costs4, bs * 4), ol = st.inout(costs4_last, bs * 4);
-  const auto oni = st.inout(nit, nit ? bs : 0), onf = st.inout(nfev, nfev ? bs : 0), ost = st.inout(status, bs);
+  const RowRefs fo = stage_rows_inout(st, a.out, bs, (size_t)a.n);
   const auto ont = st.inout(nit_total, bs), oru = st.inout(opt_runs, bs);
   // (the whole list comes back; its entries from n_fallback on are scratch)
   const auto ofb = st.out(fallback, P), onb = st.out(n_fallback, 1);
   rc = st.upload();
   if (rc) return rc;
-  rc = neo_batch_select_dev(c, B, subset ? st.dev(fsub) : nullptr, n_subset, M, D, K, st.dev(fx), st.dev(fc), st.dev(fl),
-                            st.dev(fni), nfev_k ? st.dev(fnf) : nullptr, st.dev(fst), weights4, st.dev(och), st.dev(occ),
-                            st.dev(oso), st.dev(ox), st.dev(oc), st.dev(ol), nit ? st.dev(oni) : nullptr,
-                            nfev ? st.dev(onf) : nullptr, st.dev(ost), st.dev(ont), st.dev(oru), st.dev(ofb), st.dev(onb));
+  const RunRowsIn k = as_const(staged_rows(st, fk));
+  const RunRows o = staged_rows(st, fo);
+  rc = neo_batch_select_dev(c, B, st.dev(fsub), n_subset, M, D, K, k.x, k.costs4, k.costs4_last, k.nit, k.nfev, k.status,
+                            weights4, st.dev(och), st.dev(occ), st.dev(oso), o.x, o.costs4, o.costs4_last, o.nit, o.nfev,
+                            o.status, st.dev(ont), st.dev(oru), st.dev(ofb), st.dev(onb));
   if (rc) return rc;
   return st.download();
 }
 
 // ---- BatchPlanner.plan's retry chain on resident arrays (traj_planner/expert_planner.py:186-203; kernels: neo_plan.hpp)
 static int plan_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M, int D) {
-  int rc = fleet_check(c, B, subset, n_subset);
+  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
   if (rc) return rc;
   rc = check_shape(c, B, M, D);
   if (rc) return rc;
@@ -1802,12 +1796,9 @@ int neo_plan_guess_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, i
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const FleetArgs f{B, subset, n_subset};
-  if (f.launched() == 0) return NEO_OK;
-  rc = plan_guess(c, f, D, {M, head, tail, slots, x_init, noise, frac, tau, x0, head_k, tail_k, slots_k});
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, plan_guess(c, list, D, {M, head, tail, slots, x_init, noise, frac, tau, x0, head_k, tail_k, slots_k}));
 }
 
 int neo_plan_guess(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const double *head,
@@ -1815,65 +1806,57 @@ int neo_plan_guess(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M
                    const double *tau, double *x0, double *head_k, double *tail_k, int32_t *slots_k) {
   int rc = plan_guess_check(c, B, subset, n_subset, M, D, head, tail, x_init, frac, tau, x0, head_k, tail_k);
   if (rc) return rc;
-  const size_t bs = (size_t)B, P = (size_t)(subset ? n_subset : B), n = (size_t)D * (M - 1) + M, hd = (size_t)3 * D;
+  const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n, n = (size_t)D * (M - 1) + M, hd = (size_t)3 * D;
   if (P == 0) return NEO_OK;
   std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
   hipSetDevice(c->device);
   // the packed outputs go up too: the rows of a skipped index come back as they were
   HostStage st(c, kStagedUpTo);
   const auto fh = st.in(head, bs * hd), ft = st.in(tail, bs * hd);
-  const auto fs = st.in(slots, slots ? bs : 0, 1);
-  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
-  const auto fxi = st.in(x_init, x_init ? bs * n : 0, 1);
-  const auto fno = st.in(noise, noise ? P * (size_t)D * (M - 1) : 0, 1);
+  const auto fs = st.in_optional(slots, bs), fsub = st.in_optional(subset, (size_t)n_subset);
+  const auto fxi = st.in_optional(x_init, bs * n), fno = st.in_optional(noise, P * (size_t)D * (M - 1));
   const auto fx = st.inout(x0, P * n), fhk = st.inout(head_k, P * hd), ftk = st.inout(tail_k, P * hd);
-  const auto fsk = st.inout(slots_k, slots_k ? P : 0);
+  const auto fsk = st.inout_optional(slots_k, P);
   rc = st.upload();
   if (rc) return rc;
-  rc = neo_plan_guess_dev(c, B, subset ? st.dev(fsub) : nullptr, n_subset, M, D, st.dev(fh), st.dev(ft),
-                          slots ? st.dev(fs) : nullptr, x_init ? st.dev(fxi) : nullptr, noise ? st.dev(fno) : nullptr, frac,
-                          tau, st.dev(fx), st.dev(fhk), st.dev(ftk), slots_k ? st.dev(fsk) : nullptr);
+  rc = neo_plan_guess_dev(c, B, st.dev(fsub), n_subset, M, D, st.dev(fh), st.dev(ft), st.dev(fs), st.dev(fxi), st.dev(fno),
+                          frac, tau, st.dev(fx), st.dev(fhk), st.dev(ftk), st.dev(fsk));
   if (rc) return rc;
   return st.download();
 }
 
-static int plan_merge_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const void *x_k,
-                            const void *costs4_k, const void *last_k, const void *nit_k, const void *nfev_k,
-                            const void *status_k, const void *x, const void *costs4, const void *costs4_last,
-                            const void *nit, const void *nfev, const void *status, const void *attempts,
-                            const void *nit_total, const void *solved, const void *failed, const void *n_failed,
-                            const void *bad_scene) {
+static int plan_merge_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const PlanMergeArgs &a) {
   int rc = plan_check(c, "plan merge", B, subset, n_subset, M, D);
   if (rc) return rc;
-  if (!x_k || !costs4_k || !last_k || !nit_k || !nfev_k || !status_k || !x || !costs4 || !costs4_last || !nit || !nfev ||
-      !status || !attempts || !nit_total || !solved || !failed || !n_failed || !bad_scene)
+  const RunRowsIn &k = a.packed;
+  const RunRows &o = a.out;
+  if (!k.x || !k.costs4 || !k.costs4_last || !k.nit || !k.nfev || !k.status || !o.x || !o.costs4 || !o.costs4_last ||
+      !o.nit || !o.nfev || !o.status || !a.attempts || !a.nit_total || !a.solved || !a.failed || !a.n_failed || !a.bad_scene)
     return fail_locked(c, NEO_ERR_INVALID, "plan merge: null buffer");
   return NEO_OK;
 }
+
+static_assert(sizeof(long long) == sizeof(int64_t), "nit_total is a 64-bit integer on both sides");
 
 int neo_plan_merge_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int reset, const double *x_k,
                        const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
                        const int32_t *status_k, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
                        int32_t *status, int32_t *attempts, int64_t *nit_total, int32_t *solved, int32_t *failed,
                        int32_t *n_failed, int32_t *bad_scene) {
-  int rc = plan_merge_check(c, B, subset, n_subset, M, D, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4,
-                            costs4_last, nit, nfev, status, attempts, nit_total, solved, failed, n_failed, bad_scene);
+  const PlanMergeArgs a{D * (M - 1) + M, reset ? 1 : 0, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k},
+                        {x, costs4, costs4_last, nit, nfev, status}, attempts, reinterpret_cast<long long *>(nit_total), solved,
+                        failed, n_failed, bad_scene};
+  int rc = plan_merge_check(c, B, subset, n_subset, M, D, a);
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const FleetArgs f{B, subset, n_subset};
+  const LaunchList list = launch_list(B, subset, n_subset);
   HIPCHK(c, hipMemsetAsync(bad_scene, 0, sizeof(int32_t), c->stream));
-  if (f.launched() == 0) {
+  if (list.n == 0) {
     HIPCHK(c, hipMemsetAsync(n_failed, 0, sizeof(int32_t), c->stream));
     return NEO_OK;
   }
-  static_assert(sizeof(long long) == sizeof(int64_t), "nit_total is a 64-bit integer on both sides");
-  rc = plan_merge(c, f, {D * (M - 1) + M, reset ? 1 : 0, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4,
-                         costs4_last, nit, nfev, status, attempts, reinterpret_cast<long long *>(nit_total), solved, failed,
-                         n_failed, bad_scene});
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
+  return launched(c, plan_merge(c, list, a));
 }
 
 int neo_plan_merge(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int reset, const double *x_k,
@@ -1881,10 +1864,12 @@ int neo_plan_merge(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M
                    const int32_t *status_k, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
                    int32_t *status, int32_t *attempts, int64_t *nit_total, int32_t *solved, int32_t *failed,
                    int32_t *n_failed, int32_t *bad_scene) {
-  int rc = plan_merge_check(c, B, subset, n_subset, M, D, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4,
-                            costs4_last, nit, nfev, status, attempts, nit_total, solved, failed, n_failed, bad_scene);
+  const PlanMergeArgs a{D * (M - 1) + M, reset ? 1 : 0, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k},
+                        {x, costs4, costs4_last, nit, nfev, status}, attempts, reinterpret_cast<long long *>(nit_total), solved,
+                        failed, n_failed, bad_scene};
+  int rc = plan_merge_check(c, B, subset, n_subset, M, D, a);
   if (rc) return rc;
-  const size_t bs = (size_t)B, P = (size_t)(subset ? n_subset : B), n = (size_t)D * (M - 1) + M;
+  const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n;
   if (P == 0) {
     *n_failed = 0;
     *bad_scene = 0;
@@ -1894,11 +1879,9 @@ int neo_plan_merge(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M
   hipSetDevice(c->device);
   // the request-indexed arrays go up too: requests outside the subset stay, attempts and nit_total accumulate
   HostStage st(c, kStagedUpTo);
-  const auto fx = st.in(x_k, P * n), fc = st.in(costs4_k, P * 4), fl = st.in(costs4_last_k, P * 4);
-  const auto fni = st.in(nit_k, P), fnf = st.in(nfev_k, P), fst = st.in(status_k, P);
-  const auto fsub = st.in(subset, subset ? (size_t)n_subset : 0, 1);
-  const auto ox = st.inout(x, bs * n), oc = st.inout(costs4, bs * 4), ol = st.inout(costs4_last, bs * 4);
-  const auto oni = st.inout(nit, bs), onf = st.inout(nfev, bs), ost = st.inout(status, bs);
+  const RowRefs fk = stage_rows_in(st, a.packed, P, (size_t)a.n);
+  const auto fsub = st.in_optional(subset, (size_t)n_subset);
+  const RowRefs fo = stage_rows_inout(st, a.out, bs, (size_t)a.n);
   const auto oat = st.inout(attempts, bs);
   const auto ont = st.inout(nit_total, bs);
   const auto oso = st.inout(solved, bs);
@@ -1906,9 +1889,11 @@ int neo_plan_merge(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M
   const auto ofl = st.out(failed, P), onl = st.out(n_failed, 1), obs = st.out(bad_scene, 1);
   rc = st.upload();
   if (rc) return rc;
-  rc = neo_plan_merge_dev(c, B, subset ? st.dev(fsub) : nullptr, n_subset, M, D, reset, st.dev(fx), st.dev(fc), st.dev(fl),
-                          st.dev(fni), st.dev(fnf), st.dev(fst), st.dev(ox), st.dev(oc), st.dev(ol), st.dev(oni), st.dev(onf),
-                          st.dev(ost), st.dev(oat), st.dev(ont), st.dev(oso), st.dev(ofl), st.dev(onl), st.dev(obs));
+  const RunRowsIn k = as_const(staged_rows(st, fk));
+  const RunRows o = staged_rows(st, fo);
+  rc = neo_plan_merge_dev(c, B, st.dev(fsub), n_subset, M, D, reset, k.x, k.costs4, k.costs4_last, k.nit, k.nfev, k.status, o.x,
+                          o.costs4, o.costs4_last, o.nit, o.nfev, o.status, st.dev(oat), st.dev(ont), st.dev(oso), st.dev(ofl),
+                          st.dev(onl), st.dev(obs));
   if (rc) return rc;
   return st.download();
 }

@@ -8,11 +8,11 @@
 //   batch_compact_kernel      the requests without a feasible candidate as a compacted list   one workgroup
 //
 // Included by neo_disp_batch.hip only.  D = 2, fp64.  Request-indexed arrays (head, tail, slots and everything select
-// writes) are indexed by request b; packed arrays by row p * K + k, p the request's position in the launch: lane /
-// workgroup p works on request subset[p] (p without a subset), an index outside 0 .. B - 1 is skipped and its packed
-// rows stay as they are.  No atomics: the order of the compacted list follows from the positions alone.
+// writes) are indexed by request b; packed arrays by row p * K + k, p the request's position in the launch list
+// (neo_launch_list.hpp).  No atomics: the order of the compacted list follows from the positions alone.
 #pragma once
 #include "neo_device.hpp"
+#include "neo_launch_list.hpp"
 
 namespace neo {
 
@@ -33,12 +33,6 @@ struct BatchWeights {
   double v[4];
 };
 
-__device__ __forceinline__ int batch_request(int p, int P, const int *__restrict__ subset, int B) {
-  if (p >= P) return -1;
-  const int b = subset ? subset[p] : p;
-  return (b >= 0 && b < B) ? b : -1;
-}
-
 // The waypoints are NumPy's, operation by operation (every one rounded on its own):
 //   stride = (target - start) / (count + 1)
 //   np.linspace(start + stride, target, count, endpoint=False): first = start + stride, delta = target - first,
@@ -53,24 +47,18 @@ __device__ __forceinline__ int batch_request(int p, int P, const int *__restrict
 //     lateral_dir[0].  An offset of exactly 0 adds nothing (candidate 0 stays finite where start == target makes the
 //     direction 0 / 0 = NaN, as in the reference).
 __global__ __launch_bounds__(kBatchThreads) void batch_candidates_kernel(
-    int B, int P, const int *__restrict__ subset, int M, int K, const double *__restrict__ head,
-    const double *__restrict__ tail, const int *__restrict__ slots, BatchTau tau, BatchOffsets off,
-    double *__restrict__ x0, double *__restrict__ head_k, double *__restrict__ tail_k, int *__restrict__ slots_k) {
+    LaunchList list, int M, int K, const double *__restrict__ head, const double *__restrict__ tail,
+    const int *__restrict__ slots, BatchTau tau, BatchOffsets off, double *__restrict__ x0, double *__restrict__ head_k,
+    double *__restrict__ tail_k, int *__restrict__ slots_k) {
 #pragma clang fp contract(off)
   constexpr int D = kBatchD;
   const int row = blockIdx.x * kBatchThreads + threadIdx.x;
   const int p = row / K, k = row - p * K;
-  const int b = batch_request(p, P, subset, B);  // (row >= P * K gives p >= P)
+  const int b = list.request(p);  // (a row beyond the last position's gives p >= list.n)
   if (b < 0) return;
   const int count = M - 1, n = D * count + M;
   const double *hd = head + (size_t)b * 3 * D, *tl = tail + (size_t)b * 3 * D;
-  double *hk = head_k + (size_t)row * 3 * D, *tk = tail_k + (size_t)row * 3 * D;
-#pragma unroll
-  for (int q = 0; q < 3 * D; ++q) {
-    hk[q] = hd[q];
-    tk[q] = tl[q];
-  }
-  if (slots_k) slots_k[row] = slots ? slots[b] : 0;
+  pack_boundary<D>(head, tail, slots, b, head_k, tail_k, slots_k, (size_t)row);
   double first[D], delta[D], step[D], lat[D];
   const double dx = tl[0] - hd[0], dy = tl[1] - hd[1];
   const double dd[D] = {dx, dy};
@@ -119,18 +107,15 @@ __global__ __launch_bounds__(kBatchThreads) void batch_candidates_kernel(
 // (np.min(cost) < np.inf is false then, and the reference falls back).
 // `pending[p]` gets the request's index when chosen is -1, -1 otherwise: batch_compact_kernel packs it afterwards.
 __global__ __launch_bounds__(kWave) void batch_select_kernel(
-    int B, int P, const int *__restrict__ subset, int n, int K, const double *__restrict__ x_k,
-    const double *__restrict__ costs4_k, const double *__restrict__ last_k, const int *__restrict__ nit_k,
-    const int *__restrict__ nfev_k, const int *__restrict__ status_k, BatchWeights w, int *__restrict__ chosen,
-    double *__restrict__ cand_cost, int *__restrict__ solved, double *__restrict__ x, double *__restrict__ costs4,
-    double *__restrict__ costs4_last, int *__restrict__ nit, int *__restrict__ nfev, int *__restrict__ status,
-    int *__restrict__ nit_total, int *__restrict__ opt_runs, int *__restrict__ pending) {
+    LaunchList list, int n, int K, RunRowsIn packed, BatchWeights w, int *__restrict__ chosen,
+    double *__restrict__ cand_cost, int *__restrict__ solved, RunRows out, int *__restrict__ nit_total,
+    int *__restrict__ opt_runs, int *__restrict__ pending) {
 #pragma clang fp contract(off)
   const int p = blockIdx.x;
   const int lane = lane_id();
-  const int b = batch_request(p, P, subset, B);  // wave-uniform
+  const int b = list.request(p);  // wave-uniform
   if (b < 0) {
-    if (lane == 0 && p < P) pending[p] = -1;
+    if (lane == 0 && p < list.size()) pending[p] = -1;
     return;
   }
   // every lane walks the K <= 8 candidates: the same loads and the same result in all of them
@@ -139,12 +124,12 @@ __global__ __launch_bounds__(kWave) void batch_select_kernel(
   bool nan = false;
   for (int k = 0; k < K; ++k) {
     const size_t row = (size_t)p * K + k;
-    const int st = status_k[row];
+    const int st = packed.status[row];
     const int code = st & 0xff;
     const bool feasible = code <= NEO_TRAJ_MAXITER && !(st & NEO_TRAJ_FLAG_COLLISION);  // (BAD_SCENE is > MAXITER)
     double cost = __builtin_inf();
     if (feasible) {
-      const double *c = last_k + row * 4;
+      const double *c = packed.costs4_last + row * 4;
       const double p0 = c[0] * w.v[0], p1 = c[1] * w.v[1], p2 = c[2] * w.v[2], p3 = c[3] * w.v[3];
       const double s01 = p0 + p1;
       const double s012 = s01 + p2;
@@ -157,7 +142,7 @@ __global__ __launch_bounds__(kWave) void batch_select_kernel(
       pick = k;
     }
     if (code < NEO_TRAJ_NUMERIC_RANGE) {  // an overflowed run raises before the reference counts it
-      its += nit_k[row];
+      its += packed.nit[row];
       ++runs;
     }
   }
@@ -170,49 +155,26 @@ __global__ __launch_bounds__(kWave) void batch_select_kernel(
     pending[p] = pick >= 0 ? -1 : b;
   }
   if (pick < 0) return;  // x[b] and the other results of the request stay untouched
-  const size_t row = (size_t)p * K + pick;
-  for (int i = lane; i < n; i += kWave) x[(size_t)b * n + i] = x_k[row * n + i];
-  if (lane < 4) {
-    costs4[(size_t)b * 4 + lane] = costs4_k[row * 4 + lane];
-    costs4_last[(size_t)b * 4 + lane] = last_k[row * 4 + lane];
-  }
-  if (lane == 0) {
-    status[b] = status_k[row];
-    if (nit) nit[b] = nit_k[row];
-    if (nfev) nfev[b] = nfev_k[row];
-  }
+  scatter_run_row(lane, n, packed, (size_t)p * K + pick, out, b);
 }
 
 // pending[P] (a request index, or -1) -> its entries >= 0 packed to the front in the order of their positions, and
-// their number.  ONE workgroup walks the array in chunks of kCompactThreads: a chunk is read whole, then written at or
-// before the places it was read from, so the packing is done in place and no position depends on scheduling.  With an
-// ascending subset (or none) the list is ascending.
+// their number.  ONE workgroup walks the array in chunks of kCompactThreads with ordered_rank (neo_launch_list.hpp): a
+// chunk is read whole, then written at or before the places it was read from, so the packing is done in place and no
+// position depends on scheduling.  With an ascending subset (or none) the list is ascending.
 __global__ __launch_bounds__(kCompactThreads) void batch_compact_kernel(int P, int *__restrict__ pending,
                                                                         int *__restrict__ n_pending) {
-  constexpr int kWaves = kCompactThreads / kWave;
-  __shared__ int wave_cnt[kWaves];
-  __shared__ int base_s;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  if (tid == 0) base_s = 0;
+  __shared__ RankLds<kCompactThreads> ranks;
+  const int tid = threadIdx.x;
+  if (tid == 0) ranks.base = 0;
   __syncthreads();
   for (int at = 0; at < P; at += kCompactThreads) {
     const int i = at + tid;
-    const int v = i < P ? pending[i] : -1;
-    const unsigned long long m = __ballot(v >= 0);
-    if (lane == 0) wave_cnt[wv] = __popcll(m);
-    __syncthreads();  // every read of this chunk is done, the counts are visible
-    int before = base_s;
-    for (int q = 0; q < wv; ++q) before += wave_cnt[q];
-    if (v >= 0) pending[before + __popcll(m & ((1ull << lane) - 1ull))] = v;
-    __syncthreads();
-    if (tid == 0) {
-      int total = 0;
-      for (int q = 0; q < kWaves; ++q) total += wave_cnt[q];
-      base_s += total;
-    }
-    __syncthreads();
+    const int v = i < P ? pending[i] : -1;      // the chunk is read whole ...
+    const int rank = ordered_rank(v >= 0, ranks);
+    if (v >= 0) pending[rank] = v;              // ... before any of it is written: rank <= i
   }
-  if (tid == 0) *n_pending = base_s;
+  if (tid == 0) *n_pending = ranks.base;
 }
 
 }  // namespace neo

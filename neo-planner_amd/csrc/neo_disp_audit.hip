@@ -8,8 +8,8 @@ namespace neo {
 template <int D, class MapT, class LookupT>
 static int launch_audit(neo_ctx *c, const AuditArgs &a) {
   hipLaunchKernelGGL((audit_kernel<D, MapT, LookupT>), dim3(a.B), dim3(kWave), 0, c->stream, a.B, a.M, c->dev,
-                     static_cast<const MapT *>(a.table), a.slots, a.nmaps, a.x, a.head, a.tail, a.hz, a.w[0], a.w[1],
-                     a.w[2], a.audit, a.count, a.flags);
+                     static_cast<const MapT *>(a.maps.table), a.maps.slots, a.maps.nmaps, a.x, a.head, a.tail, a.hz, a.w[0],
+                     a.w[1], a.w[2], a.audit, a.count, a.flags);
   return NEO_OK;
 }
 

@@ -6,27 +6,24 @@
 
 namespace neo {
 
-int batch_candidates(neo_ctx *c, const FleetArgs &f, const BatchCandArgs &a) {
-  const int P = f.launched();
+int batch_candidates(neo_ctx *c, const LaunchList &l, const BatchCandArgs &a) {
   BatchTau tau{};
   BatchOffsets off{};
   for (int i = 0; i < a.M; ++i) tau.v[i] = a.tau[i];
   for (int k = 0; k < a.K; ++k) off.v[k] = a.off[k];
-  const long long rows = (long long)P * a.K;
+  const long long rows = (long long)l.n * a.K;
   hipLaunchKernelGGL(batch_candidates_kernel, dim3((unsigned)((rows + kBatchThreads - 1) / kBatchThreads)),
-                     dim3(kBatchThreads), 0, c->stream, f.B, P, f.subset, a.M, a.K, a.head, a.tail, a.slots, tau, off, a.x0,
-                     a.head_k, a.tail_k, a.slots_k);
+                     dim3(kBatchThreads), 0, c->stream, l, a.M, a.K, a.head, a.tail, a.slots, tau, off, a.x0, a.head_k, a.tail_k,
+                     a.slots_k);
   return NEO_OK;
 }
 
-int batch_select(neo_ctx *c, const FleetArgs &f, const BatchSelectArgs &a) {
-  const int P = f.launched();
+int batch_select(neo_ctx *c, const LaunchList &l, const BatchSelectArgs &a) {
   BatchWeights w{};
   for (int i = 0; i < 4; ++i) w.v[i] = a.w[i];
-  hipLaunchKernelGGL(batch_select_kernel, dim3(P), dim3(kWave), 0, c->stream, f.B, P, f.subset, a.n, a.K, a.x_k, a.costs4_k,
-                     a.last_k, a.nit_k, a.nfev_k, a.status_k, w, a.chosen, a.cand_cost, a.solved, a.x, a.costs4,
-                     a.costs4_last, a.nit, a.nfev, a.status, a.nit_total, a.opt_runs, a.fallback);
-  return batch_compact(c, P, a.fallback, a.n_fallback);
+  hipLaunchKernelGGL(batch_select_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.n, a.K, a.packed, w, a.chosen,
+                     a.cand_cost, a.solved, a.out, a.nit_total, a.opt_runs, a.fallback);
+  return batch_compact(c, l.n, a.fallback, a.n_fallback);
 }
 
 int batch_compact(neo_ctx *c, int P, int *pending, int *n_pending) {

@@ -8,40 +8,35 @@ namespace neo {
 
 static dim3 lanes_grid(int n) { return dim3((n + kFleetThreads - 1) / kFleetThreads); }
 
-int fleet_target(neo_ctx *c, const FleetArgs &f, const FleetTargetArgs &a) {
-  const int n = f.launched();
-  hipLaunchKernelGGL(fleet_target_kernel, lanes_grid(n), dim3(kFleetThreads), 0, c->stream, f.B, n, f.subset,
-                     static_cast<const Map2D *>(f.table), f.slots, f.nmaps, a.cur_pos, a.goal, a.jitter, a.longitu,
+int fleet_target(neo_ctx *c, const LaunchList &l, const MapRef &m, const FleetTargetArgs &a) {
+  hipLaunchKernelGGL(fleet_target_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l,
+                     static_cast<const Map2D *>(m.table), m.slots, m.nmaps, a.cur_pos, a.goal, a.jitter, a.longitu,
                      a.lateral, a.move_vel, a.tail, a.near_goal, a.lateral_steps, a.flags);
   return NEO_OK;
 }
 
-int fleet_advance(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, int step, int ahead, double *cur_pos, double *head) {
-  const int n = f.launched();
-  hipLaunchKernelGGL(fleet_advance_kernel, lanes_grid(n), dim3(kFleetThreads), 0, c->stream, f.B, n, f.subset, m.cmd,
-                     m.cap, m.cmd_len, m.cmd_index, m.future_index, step, ahead, cur_pos, head);
+int fleet_advance(neo_ctx *c, const LaunchList &l, const FleetCmd &m, int step, int ahead, double *cur_pos, double *head) {
+  hipLaunchKernelGGL(fleet_advance_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l, m.cmd, m.cap, m.cmd_len,
+                     m.cmd_index, m.future_index, step, ahead, cur_pos, head);
   return NEO_OK;
 }
 
-int fleet_pose(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const double *cur_pos, const double *goal, double eye_z,
+int fleet_pose(neo_ctx *c, const LaunchList &l, const FleetCmd &m, const double *cur_pos, const double *goal, double eye_z,
                double *pose) {
-  const int n = f.launched();
-  hipLaunchKernelGGL(fleet_pose_kernel, lanes_grid(n), dim3(kFleetThreads), 0, c->stream, f.B, n, f.subset, m.cmd, m.cap,
-                     m.cmd_len, m.cmd_index, cur_pos, goal, eye_z, pose);
+  hipLaunchKernelGGL(fleet_pose_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l, m.cmd, m.cap, m.cmd_len,
+                     m.cmd_index, cur_pos, goal, eye_z, pose);
   return NEO_OK;
 }
 
-int fleet_splice(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const FleetSpliceArgs &a) {
-  const int n = f.launched();
-  hipLaunchKernelGGL(fleet_splice_kernel, dim3(n), dim3(kWave), 0, c->stream, f.B, n, f.subset, a.M, c->dev, a.x, a.head,
-                     a.tail, a.solved, a.hz, a.first, m.cmd, m.cap, m.cmd_len, m.cmd_index, m.future_index, a.flags);
+int fleet_splice(neo_ctx *c, const LaunchList &l, const FleetCmd &m, const FleetSpliceArgs &a) {
+  hipLaunchKernelGGL(fleet_splice_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.M, c->dev, a.x, a.head, a.tail,
+                     a.solved, a.hz, a.first, m.cmd, m.cap, m.cmd_len, m.cmd_index, m.future_index, a.flags);
   return NEO_OK;
 }
 
-int fleet_audit(neo_ctx *c, const FleetArgs &f, const FleetAuditArgs &a) {
-  const int n = f.launched();
-  hipLaunchKernelGGL(fleet_audit_kernel, dim3(n), dim3(kWave), 0, c->stream, f.B, n, f.subset, c->dev,
-                     static_cast<const Map2D *>(f.table), f.slots, f.nmaps, a.cmd, a.cap, a.n_flown, a.stride, a.hz, a.w[0],
+int fleet_audit(neo_ctx *c, const LaunchList &l, const MapRef &m, const FleetAuditArgs &a) {
+  hipLaunchKernelGGL(fleet_audit_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, c->dev,
+                     static_cast<const Map2D *>(m.table), m.slots, m.nmaps, a.cmd, a.cap, a.n_flown, a.stride, a.hz, a.w[0],
                      a.w[1], a.w[2], a.audit, a.count, a.flags);
   return NEO_OK;
 }

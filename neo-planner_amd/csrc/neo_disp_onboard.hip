@@ -23,7 +23,7 @@ size_t onboard_lds_limit() { return kOnboardLds; }
 
 int onboard_integrate(neo_ctx *c, const OnboardCall &k) {
   OnboardArgs a{};
-  a.B = k.B, a.n_launch = k.n_launch, a.subset = k.subset;
+  a.list = k.list;
   a.depth_m = k.depth_m, a.pose = k.pose;
   a.W = k.W, a.H = k.H, a.focal = k.focal;
   a.grid_w = k.grid_w, a.grid_h = k.grid_h, a.res = k.res, a.origins = k.origins;
@@ -33,7 +33,7 @@ int onboard_integrate(neo_ctx *c, const OnboardCall &k) {
   a.logodds = k.logodds, a.occupancy = k.occupancy, a.changed = k.changed;
   const size_t lds = onboard_lds_bytes(k.half, k.N, k.H);
   // one workgroup a launched mission (the C ABI admits at most 2^20 missions a call)
-  hipLaunchKernelGGL(onboard_integrate_kernel, dim3(k.n_launch), dim3(kOnboardThreads), lds, c->stream, a);
+  hipLaunchKernelGGL(onboard_integrate_kernel, dim3(k.list.n), dim3(kOnboardThreads), lds, c->stream, a);
   HIPCHK(c, hipGetLastError());
   return NEO_OK;
 }

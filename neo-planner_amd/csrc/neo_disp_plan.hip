@@ -6,30 +6,27 @@
 
 namespace neo {
 
-int plan_guess(neo_ctx *c, const FleetArgs &f, int D, const PlanGuessArgs &a) {
-  const int P = f.launched();
+int plan_guess(neo_ctx *c, const LaunchList &l, int D, const PlanGuessArgs &a) {
   PlanFrac frac{};
   PlanTau tau{};
   if (!a.x_init) {
     for (int k = 0; k < a.M - 1; ++k) frac.v[k] = a.frac[k];
     for (int i = 0; i < a.M; ++i) tau.v[i] = a.tau[i];
   }
-  const dim3 grid((unsigned)((P + kPlanThreads - 1) / kPlanThreads)), block(kPlanThreads);
+  const dim3 grid((unsigned)((l.n + kPlanThreads - 1) / kPlanThreads)), block(kPlanThreads);
   if (D == 2)
-    hipLaunchKernelGGL(plan_guess_kernel<2>, grid, block, 0, c->stream, f.B, P, f.subset, a.M, a.head, a.tail, a.slots,
-                       a.x_init, a.noise, frac, tau, a.x0, a.head_k, a.tail_k, a.slots_k);
+    hipLaunchKernelGGL(plan_guess_kernel<2>, grid, block, 0, c->stream, l, a.M, a.head, a.tail, a.slots, a.x_init,
+                       a.noise, frac, tau, a.x0, a.head_k, a.tail_k, a.slots_k);
   else
-    hipLaunchKernelGGL(plan_guess_kernel<3>, grid, block, 0, c->stream, f.B, P, f.subset, a.M, a.head, a.tail, a.slots,
-                       a.x_init, a.noise, frac, tau, a.x0, a.head_k, a.tail_k, a.slots_k);
+    hipLaunchKernelGGL(plan_guess_kernel<3>, grid, block, 0, c->stream, l, a.M, a.head, a.tail, a.slots, a.x_init,
+                       a.noise, frac, tau, a.x0, a.head_k, a.tail_k, a.slots_k);
   return NEO_OK;
 }
 
-int plan_merge(neo_ctx *c, const FleetArgs &f, const PlanMergeArgs &a) {
-  const int P = f.launched();
-  hipLaunchKernelGGL(plan_merge_kernel, dim3(P), dim3(kWave), 0, c->stream, f.B, P, f.subset, a.n, a.reset, a.x_k,
-                     a.costs4_k, a.last_k, a.nit_k, a.nfev_k, a.status_k, a.x, a.costs4, a.costs4_last, a.nit, a.nfev,
-                     a.status, a.attempts, a.nit_total, a.solved, a.failed, a.bad_scene);
-  return batch_compact(c, P, a.failed, a.n_failed);
+int plan_merge(neo_ctx *c, const LaunchList &l, const PlanMergeArgs &a) {
+  hipLaunchKernelGGL(plan_merge_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.n, a.reset, a.packed, a.out, a.attempts,
+                     a.nit_total, a.solved, a.failed, a.bad_scene);
+  return batch_compact(c, l.n, a.failed, a.n_failed);
 }
 
 }  // namespace neo

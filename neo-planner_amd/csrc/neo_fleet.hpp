@@ -9,11 +9,12 @@
 //
 // Included by neo_disp_fleet.hip only.  2-D reference map, D = 2, fp64.  No floating-point atomics, fixed summation
 // order: a mission's results depend on neither the batch, the subset nor the launch.  All arrays are indexed by mission;
-// workgroup / lane i works on mission subset[i] (i without a subset), an index outside 0 .. B - 1 is skipped.  A mission
-// is owned by one lane (target, advance) or one wavefront (splice, audit) of a launch, so its flags word is updated with
-// a plain read-modify-write.
+// workgroup / lane i works on the mission at position i of the launch list (neo_launch_list.hpp).  A mission is owned
+// by one lane (target, advance) or one wavefront (splice, audit) of a launch, so its flags word is updated with a plain
+// read-modify-write.
 #pragma once
 #include "neo_audit.hpp"
+#include "neo_launch_list.hpp"
 
 namespace neo {
 
@@ -22,12 +23,6 @@ constexpr int kFleetD = 2;
 constexpr int kFleetRow = 3 * kFleetD;  // doubles of a command row: position, velocity, acceleration
 // most lateral steps the target walk is ever given, whatever the map and the step (see fleet_walk_bound)
 constexpr int kFleetWalkMax = 1 << 20;
-
-__device__ __forceinline__ int fleet_mission(int i, int n, const int *__restrict__ subset, int B) {
-  if (i >= n) return -1;
-  const int b = subset ? subset[i] : i;
-  return (b >= 0 && b < B) ? b : -1;
-}
 
 // Bound of set_local_target's lateral walk (the reference's `while self.map.has_collision(...)` has none).  After k
 // steps the candidate sits at p_0 + (-1)^(k+1) ceil(k / 2) s along the first lateral direction (steps of s, 2 s, 3 s, ...
@@ -43,12 +38,12 @@ __device__ __forceinline__ int fleet_walk_bound(const Map2D &m, double s) {
 }
 
 __global__ __launch_bounds__(kFleetThreads) void fleet_target_kernel(
-    int B, int n, const int *__restrict__ subset, const Map2D *__restrict__ maps, const int *__restrict__ scene_slot,
-    int nmaps, const double *__restrict__ cur_pos, const double *__restrict__ goal, const double *__restrict__ jitter,
+    LaunchList list, const Map2D *__restrict__ maps, const int *__restrict__ scene_slot, int nmaps,
+    const double *__restrict__ cur_pos, const double *__restrict__ goal, const double *__restrict__ jitter,
     double longitu, double lateral, double move_vel, double *__restrict__ tail, int *__restrict__ near_goal,
     int *__restrict__ lateral_steps, int *__restrict__ flags) {
 #pragma clang fp contract(off)  // every operation rounded on its own, as the reference's NumPy expressions are
-  const int b = fleet_mission(blockIdx.x * kFleetThreads + threadIdx.x, n, subset, B);
+  const int b = list.request(blockIdx.x * kFleetThreads + threadIdx.x);
   if (b < 0) return;
   double *tl = tail + (size_t)b * kFleetRow;
   tl[4] = tl[5] = 0.0;  // the target's acceleration row
@@ -121,11 +116,11 @@ __device__ __forceinline__ bool fleet_unit(double dx, double dy, double &c, doub
 }
 
 __global__ __launch_bounds__(kFleetThreads) void fleet_pose_kernel(
-    int B, int n, const int *__restrict__ subset, const double *__restrict__ cmd, int cap,
-    const int *__restrict__ cmd_len, const int *__restrict__ cmd_index, const double *__restrict__ cur_pos,
+    LaunchList list, const double *__restrict__ cmd, int cap, const int *__restrict__ cmd_len,
+    const int *__restrict__ cmd_index, const double *__restrict__ cur_pos,
     const double *__restrict__ goal, double eye_z, double *__restrict__ pose) {
 #pragma clang fp contract(off)
-  const int b = fleet_mission(blockIdx.x * kFleetThreads + threadIdx.x, n, subset, B);
+  const int b = list.request(blockIdx.x * kFleetThreads + threadIdx.x);
   if (b < 0) return;
   const double px = cur_pos[(size_t)b * 2], py = cur_pos[(size_t)b * 2 + 1];
   int len = cmd_len[b];
@@ -148,10 +143,10 @@ __global__ __launch_bounds__(kFleetThreads) void fleet_pose_kernel(
 }
 
 __global__ __launch_bounds__(kFleetThreads) void fleet_advance_kernel(
-    int B, int n, const int *__restrict__ subset, const double *__restrict__ cmd, int cap,
-    const int *__restrict__ cmd_len, int *__restrict__ cmd_index, int *__restrict__ future_index, int step, int ahead,
-    double *__restrict__ cur_pos, double *__restrict__ head) {
-  const int b = fleet_mission(blockIdx.x * kFleetThreads + threadIdx.x, n, subset, B);
+    LaunchList list, const double *__restrict__ cmd, int cap, const int *__restrict__ cmd_len,
+    int *__restrict__ cmd_index, int *__restrict__ future_index, int step, int ahead, double *__restrict__ cur_pos,
+    double *__restrict__ head) {
+  const int b = list.request(blockIdx.x * kFleetThreads + threadIdx.x);
   if (b < 0) return;
   int len = cmd_len[b];
   len = len > cap ? cap : len;
@@ -179,7 +174,7 @@ __global__ __launch_bounds__(kFleetThreads) void fleet_advance_kernel(
 // The solve and the rows are traj_state_kernel's (neo_abi.hip) through audit_sample_state, its expressions written out
 // again in neo_audit.hpp: compiled with the units' -ffp-contract=on and no pragma here, they round as its rows do.
 __global__ __launch_bounds__(kWave) void fleet_splice_kernel(
-    int B, int n_launch, const int *__restrict__ subset, int M, DevParams prm, const double *__restrict__ x,
+    LaunchList list, int M, DevParams prm, const double *__restrict__ x,
     const double *__restrict__ head, const double *__restrict__ tail, const int *__restrict__ solved, double hz, int first,
     double *__restrict__ cmd, int cap, int *__restrict__ cmd_len, int *__restrict__ cmd_index,
     int *__restrict__ future_index, int *__restrict__ flags) {
@@ -187,7 +182,7 @@ __global__ __launch_bounds__(kWave) void fleet_splice_kernel(
   __shared__ double xs[kSlots * kWave];
   __shared__ double cs[kWave * 6 * D];
   __shared__ double tcum[kWave + 1];
-  const int b = fleet_mission(blockIdx.x, n_launch, subset, B);  // wave-uniform
+  const int b = list.request(blockIdx.x);  // wave-uniform
   if (b < 0) return;
   if (solved && !solved[b]) return;
   const int lane = lane_id();
@@ -262,13 +257,13 @@ __global__ __launch_bounds__(kWave) void fleet_splice_kernel(
 // array, j < count = ceil(n_flown / stride).  Per round a lane loads the rows of its kAuditU samples, then has their
 // kAuditU map gathers in flight before the first is consumed.
 __global__ __launch_bounds__(kWave) void fleet_audit_kernel(
-    int B, int n_launch, const int *__restrict__ subset, DevParams prm, const Map2D *__restrict__ maps,
+    LaunchList list, DevParams prm, const Map2D *__restrict__ maps,
     const int *__restrict__ scene_slot, int nmaps, const double *__restrict__ cmd, int cap,
     const int *__restrict__ n_flown, int stride, double hz, double w0, double w1, double w2, double *__restrict__ audit,
     int *__restrict__ count, int *__restrict__ flags) {
 #pragma clang fp contract(off)  // the metric's own arithmetic rounds every operation as the reference's NumPy does
   constexpr int D = kFleetD;
-  const int b = fleet_mission(blockIdx.x, n_launch, subset, B);  // wave-uniform
+  const int b = list.request(blockIdx.x);  // wave-uniform
   if (b < 0) return;
   const int lane = lane_id();
   double *rec = audit + (size_t)b * NEO_AUDIT_FIELDS;

@@ -16,6 +16,7 @@
 
 #include "../../include/neo_planner.h"
 #include "neo_device.hpp"
+#include "neo_launch_list.hpp"
 
 namespace neo {
 struct MapEntry {
@@ -197,9 +198,7 @@ struct SampleArgs {
 // neo_audit_traj_batch_dev: one audit_kernel launch (neo_disp_audit.hip)
 struct AuditArgs {
   int B, M;
-  const void *table;  // map table (or the one map) of the call's kind
-  const int *slots;   // device array [B] of map-table slots, or NULL (all trajectories use table[0])
-  int nmaps;          // entries of `table` (slots are checked against it on the device)
+  MapRef maps;  // of the call's kind
   const double *x, *head, *tail;
   double hz, w[3];
   double *audit;
@@ -207,17 +206,7 @@ struct AuditArgs {
 };
 
 // neo_fleet_*_dev: one launch of a fleet kernel each (neo_disp_fleet.hip, kernels in neo_fleet.hpp).  Every array is
-// indexed by mission; `subset` (device, n_subset indices) picks the missions launched, NULL = all B.
-struct FleetArgs {
-  int B;
-  const int *subset;
-  int n_subset;
-  // target / audit: the 2-D map table (or the one map), as in AuditArgs
-  const void *table = nullptr;
-  const int *slots = nullptr;
-  int nmaps = 1;
-  int launched() const { return subset ? n_subset : B; }
-};
+// indexed by mission; the LaunchList picks the missions launched, the MapRef (target, audit) is the 2-D map table.
 struct FleetTargetArgs {
   const double *cur_pos, *goal, *jitter;
   double longitu, lateral, move_vel;
@@ -246,12 +235,12 @@ struct FleetAuditArgs {
   double *audit;
   int *count, *flags;
 };
-int fleet_target(neo_ctx *c, const FleetArgs &f, const FleetTargetArgs &a);
-int fleet_advance(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, int step, int ahead, double *cur_pos, double *head);
-int fleet_splice(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const FleetSpliceArgs &a);
-int fleet_audit(neo_ctx *c, const FleetArgs &f, const FleetAuditArgs &a);
+int fleet_target(neo_ctx *c, const LaunchList &l, const MapRef &m, const FleetTargetArgs &a);
+int fleet_advance(neo_ctx *c, const LaunchList &l, const FleetCmd &m, int step, int ahead, double *cur_pos, double *head);
+int fleet_splice(neo_ctx *c, const LaunchList &l, const FleetCmd &m, const FleetSpliceArgs &a);
+int fleet_audit(neo_ctx *c, const LaunchList &l, const MapRef &m, const FleetAuditArgs &a);
 // the missions' camera poses (eye x y z, cos, sin) from where they are on their command arrays
-int fleet_pose(neo_ctx *c, const FleetArgs &f, const FleetCmd &m, const double *cur_pos, const double *goal, double eye_z,
+int fleet_pose(neo_ctx *c, const LaunchList &l, const FleetCmd &m, const double *cur_pos, const double *goal, double eye_z,
                double *pose);
 
 // neo_record_*_dev: the fleet's `record` mode (neo_disp_record.hip, kernels in neo_record.hpp).  Every pointer is a
@@ -270,12 +259,12 @@ struct RecordCommitArgs {
   unsigned char *images;
   int *row_of, *n_rows, *dropped;  // [launched], [1], [1]
 };
-int record_state(neo_ctx *c, const FleetArgs &f, const double *cmd, int cap, const int *cmd_len, const int *cmd_index,
+int record_state(neo_ctx *c, const LaunchList &l, const double *cmd, int cap, const int *cmd_len, const int *cmd_index,
                  const double *head, double *cur_vel);
-int record_commit(neo_ctx *c, const FleetArgs &f, const RecordCommitArgs &a);  // rank, then commit
+int record_commit(neo_ctx *c, const LaunchList &l, const RecordCommitArgs &a);  // rank, then commit
 
 // neo_batch_*_dev: the `batch` planner mode on resident arrays (neo_disp_batch.hip, kernels in neo_batch.hpp).  P =
-// f.launched() requests; tau, off and w are HOST arrays (M, K and 4 values), handed to the kernels by value.
+// the list's n requests; tau, off and w are HOST arrays (M, K and 4 values), handed to the kernels by value.
 struct BatchCandArgs {
   int M, K;
   const double *head, *tail;  // [B][3][2], by request
@@ -286,24 +275,22 @@ struct BatchCandArgs {
 };
 struct BatchSelectArgs {
   int n, K;
-  const double *x_k, *costs4_k, *last_k;  // packed [P * K] rows: the optimiser's results
-  const int *nit_k, *nfev_k, *status_k;
+  RunRowsIn packed;                       // [P * K] rows: the optimiser's results (nfev: or NULL)
   const double *w;                        // host, 4 weights
   int *chosen;                            // everything below by request
   double *cand_cost;
   int *solved;
-  double *x, *costs4, *costs4_last;
-  int *nit, *nfev, *status;               // nit, nfev: or NULL
+  RunRows out;                            // nit, nfev: or NULL
   int *nit_total, *opt_runs;
   int *fallback, *n_fallback;             // [P] and [1]
 };
-int batch_candidates(neo_ctx *c, const FleetArgs &f, const BatchCandArgs &a);
-int batch_select(neo_ctx *c, const FleetArgs &f, const BatchSelectArgs &a);
+int batch_candidates(neo_ctx *c, const LaunchList &l, const BatchCandArgs &a);
+int batch_select(neo_ctx *c, const LaunchList &l, const BatchSelectArgs &a);
 // pending[P] (request indices, or -1) packed in place in position order, *n_pending their number: one launch
 int batch_compact(neo_ctx *c, int P, int *pending, int *n_pending);
 
 // neo_plan_*_dev: BatchPlanner.plan's retry chain on resident arrays (neo_disp_plan.hip, kernels in neo_plan.hpp).
-// P = f.launched() requests; frac and tau are HOST arrays (M - 1 and M values), handed to the kernel by value.
+// P = the list's n requests; frac and tau are HOST arrays (M - 1 and M values), handed to the kernel by value.
 struct PlanGuessArgs {
   int M;
   const double *head, *tail;     // [B][3][D], by request
@@ -316,16 +303,15 @@ struct PlanGuessArgs {
 };
 struct PlanMergeArgs {
   int n, reset;
-  const double *x_k, *costs4_k, *last_k;  // packed [P] rows: the optimiser's results
-  const int *nit_k, *nfev_k, *status_k;
-  double *x, *costs4, *costs4_last;       // everything below by request
-  int *nit, *nfev, *status, *attempts;
+  RunRowsIn packed;                       // [P] rows: the optimiser's results
+  RunRows out;                            // everything below by request
+  int *attempts;
   long long *nit_total;
   int *solved;
   int *failed, *n_failed, *bad_scene;     // [P], [1] and [1]
 };
-int plan_guess(neo_ctx *c, const FleetArgs &f, int D, const PlanGuessArgs &a);
-int plan_merge(neo_ctx *c, const FleetArgs &f, const PlanMergeArgs &a);
+int plan_guess(neo_ctx *c, const LaunchList &l, int D, const PlanGuessArgs &a);
+int plan_merge(neo_ctx *c, const LaunchList &l, const PlanMergeArgs &a);
 
 // neo_geo_search_batch_dev / neo_geo_prune_batch (neo_disp_geo.hip); the context is locked and its tables rebuilt
 struct GeoArgs {
@@ -363,8 +349,7 @@ void depth_release(neo_ctx *c);  // frees the camera's buffers (neo_ctx_destroy)
 // neo_onboard_integrate_batch_dev (neo_disp_onboard.hip, kernel in neo_onboard.hpp): one launch on the context's
 // stream; every pointer is a device array, the arguments are checked, N and half sized by the caller
 struct OnboardCall {
-  int B, n_launch;
-  const int *subset;  // or NULL
+  LaunchList list;
   const float *depth_m;
   const double *pose;
   int W, H;

@@ -24,6 +24,7 @@
 #include <cstdint>
 
 #include "../../include/neo_planner.h"
+#include "neo_launch_list.hpp"
 
 namespace neo {
 
@@ -34,10 +35,9 @@ constexpr int kOnboardUnknown = -128;            // the log-odds byte of a cell 
 constexpr size_t kOnboardLds = 64 * 1024 - 64;   // dynamic LDS a workgroup may ask for (the kernel has one static word)
 
 struct OnboardArgs {
-  int B, n_launch;
-  const int *subset;        // [n_launch] missions, or NULL
-  const float *depth_m;     // [n_launch][H][W], by launch position
-  const double *pose;       // [n_launch][5], by launch position
+  LaunchList list;          // the missions of the launch (neo_launch_list.hpp)
+  const float *depth_m;     // [list.n][H][W], by launch position
+  const double *pose;       // [list.n][5], by launch position
   int W, H;
   double focal;
   int grid_w, grid_h;
@@ -91,9 +91,8 @@ __global__ __launch_bounds__(kOnboardThreads) void onboard_integrate_kernel(Onbo
   __shared__ int s_changed;
   const int t = threadIdx.x, lane = t & (kOnboardCols - 1), wave = t / kOnboardCols;
   const int i_launch = blockIdx.x;
-  if (i_launch >= a.n_launch) return;
-  const int b = a.subset ? a.subset[i_launch] : i_launch;
-  if (b < 0 || b >= a.B) return;  // (workgroup-uniform)
+  const int b = a.list.request(i_launch);  // (workgroup-uniform)
+  if (b < 0) return;
 
   const int N = a.N, H = a.H, W = a.W;
   const int side = 2 * a.half + 1;

@@ -8,10 +8,10 @@
 //   (batch_compact_kernel, neo_batch.hpp, then packs the failed requests: the next attempt's launch list)
 //
 // Included by neo_disp_plan.hip only.  fp64, D = 2 or 3.  Request-indexed arrays are indexed by request b; packed
-// arrays by the request's position p in the launch: lane / workgroup p works on request subset[p] (p without a subset),
-// an index outside 0 .. B - 1 is skipped and its packed rows stay as they are.  No atomics, no scratch.
+// arrays by the request's position p in the launch list (neo_launch_list.hpp).  No atomics, no scratch.
 #pragma once
 #include "neo_device.hpp"
+#include "neo_launch_list.hpp"
 
 namespace neo {
 
@@ -26,35 +26,23 @@ struct PlanTau {
   double v[NEO_MAX_PIECES];
 };
 
-__device__ __forceinline__ int plan_request(int p, int P, const int *__restrict__ subset, int B) {
-  if (p >= P) return -1;
-  const int b = subset ? subset[p] : p;
-  return (b >= 0 && b < B) ? b : -1;
-}
-
 // The waypoints are BatchPlanner.init_guess's, operation by operation (every one rounded on its own, nothing fused):
 //   wp = start + (target - start) * f[k]        and, for a re-seeded attempt, wp = wp + noise
 // `x_init` (request-indexed [B][n]) replaces all of that: the row is the caller's own start point, copied.
 // `noise` is packed [P][D][M - 1]: the host draws it for the launch list in position order.
 template <int D>
 __global__ __launch_bounds__(kPlanThreads) void plan_guess_kernel(
-    int B, int P, const int *__restrict__ subset, int M, const double *__restrict__ head,
-    const double *__restrict__ tail, const int *__restrict__ slots, const double *__restrict__ x_init,
-    const double *__restrict__ noise, PlanFrac f, PlanTau tau, double *__restrict__ x0, double *__restrict__ head_k,
-    double *__restrict__ tail_k, int *__restrict__ slots_k) {
+    LaunchList list, int M, const double *__restrict__ head, const double *__restrict__ tail,
+    const int *__restrict__ slots, const double *__restrict__ x_init, const double *__restrict__ noise, PlanFrac f,
+    PlanTau tau, double *__restrict__ x0, double *__restrict__ head_k, double *__restrict__ tail_k,
+    int *__restrict__ slots_k) {
 #pragma clang fp contract(off)
   const int p = blockIdx.x * kPlanThreads + threadIdx.x;
-  const int b = plan_request(p, P, subset, B);
+  const int b = list.request(p);
   if (b < 0) return;
   const int count = M - 1, n = D * count + M;
   const double *hd = head + (size_t)b * 3 * D, *tl = tail + (size_t)b * 3 * D;
-  double *hk = head_k + (size_t)p * 3 * D, *tk = tail_k + (size_t)p * 3 * D;
-#pragma unroll
-  for (int q = 0; q < 3 * D; ++q) {
-    hk[q] = hd[q];
-    tk[q] = tl[q];
-  }
-  if (slots_k) slots_k[p] = slots ? slots[b] : 0;
+  pack_boundary<D>(head, tail, slots, b, head_k, tail_k, slots_k, (size_t)p);
   double *xr = x0 + (size_t)p * n;
   if (x_init) {
     const double *xi = x_init + (size_t)b * n;
@@ -83,33 +71,21 @@ __global__ __launch_bounds__(kPlanThreads) void plan_guess_kernel(
 // `bad_scene` (zeroed before the launch) becomes 1 when a launched request ended with NEO_TRAJ_BAD_SCENE -- every
 // wavefront that sees one stores the same 1.
 __global__ __launch_bounds__(kWave) void plan_merge_kernel(
-    int B, int P, const int *__restrict__ subset, int n, int reset, const double *__restrict__ x_k,
-    const double *__restrict__ costs4_k, const double *__restrict__ last_k, const int *__restrict__ nit_k,
-    const int *__restrict__ nfev_k, const int *__restrict__ status_k, double *__restrict__ x,
-    double *__restrict__ costs4, double *__restrict__ costs4_last, int *__restrict__ nit, int *__restrict__ nfev,
-    int *__restrict__ status, int *__restrict__ attempts, long long *__restrict__ nit_total, int *__restrict__ solved,
-    int *__restrict__ pending, int *__restrict__ bad_scene) {
+    LaunchList list, int n, int reset, RunRowsIn packed, RunRows out, int *__restrict__ attempts,
+    long long *__restrict__ nit_total, int *__restrict__ solved, int *__restrict__ pending, int *__restrict__ bad_scene) {
   const int p = blockIdx.x;
   const int lane = lane_id();
-  const int b = plan_request(p, P, subset, B);  // wave-uniform
+  const int b = list.request(p);  // wave-uniform
   if (b < 0) {
-    if (lane == 0 && p < P) pending[p] = -1;
+    if (lane == 0 && p < list.size()) pending[p] = -1;
     return;
   }
-  for (int i = lane; i < n; i += kWave) x[(size_t)b * n + i] = x_k[(size_t)p * n + i];
-  if (lane < 4) {
-    costs4[(size_t)b * 4 + lane] = costs4_k[(size_t)p * 4 + lane];
-    costs4_last[(size_t)b * 4 + lane] = last_k[(size_t)p * 4 + lane];
-  }
+  const int st = packed.status[p], its = packed.nit[p];  // (wave-uniform loads, ahead of the scatter's stores)
+  scatter_run_row(lane, n, packed, (size_t)p, out, b);
   if (lane == 0) {
-    const int st = status_k[p];
     const int code = st & 0xff;
     const bool failed = (code > NEO_TRAJ_MAXITER && code != NEO_TRAJ_BAD_SCENE) || (st & NEO_TRAJ_FLAG_COLLISION);
-    const int its = nit_k[p];
     const long long counted = code >= NEO_TRAJ_NUMERIC_RANGE ? 0 : its;
-    status[b] = st;
-    nit[b] = its;
-    nfev[b] = nfev_k[p];
     attempts[b] = reset ? 1 : attempts[b] + 1;
     nit_total[b] = reset ? counted : nit_total[b] + counted;
     solved[b] = failed ? 0 : 1;

@@ -8,10 +8,11 @@
 //
 // Included by neo_disp_record.hip only.  D = 2, fp64, every operation rounded on its own (contraction off): NumPy gives
 // the same bits (tests/record_oracle_np.py).  No atomics: the row of a mission follows from its position in the launch
-// and the counters alone.  Mission-indexed arrays are indexed by mission b; workgroup / lane k works on mission
-// subset[k] (k without a subset), an index outside 0 .. B - 1 is skipped.
+// and the counters alone.  Mission-indexed arrays are indexed by mission b; workgroup / lane k works on the mission at
+// position k of the launch list (neo_launch_list.hpp).
 #pragma once
 #include "neo_device.hpp"
+#include "neo_launch_list.hpp"
 
 namespace neo {
 
@@ -22,19 +23,12 @@ constexpr int kRecordRow = 3 * kRecordD;  // doubles of a command row / a head o
 constexpr int kRecordMotion = 24;         // form_nn_input's vector
 constexpr int kRecordUnroll = 4;          // 16-byte pieces a lane has in flight in the image copy (written out below)
 
-__device__ __forceinline__ int record_mission(int k, int n, const int *__restrict__ subset, int B) {
-  if (k >= n) return -1;
-  const int b = subset ? subset[k] : k;
-  return (b >= 0 && b < B) ? b : -1;
-}
-
 // drone_state.global_vel at the time of the plan: the velocity of the command row being flown, or, before the first
 // plan, of the plan's initial state (traj_planner_node.py first_plan: drone_state is plan_init_state).
 __global__ __launch_bounds__(kRecordThreads) void record_state_kernel(
-    int B, int n, const int *__restrict__ subset, const double *__restrict__ cmd, int cap,
-    const int *__restrict__ cmd_len, const int *__restrict__ cmd_index, const double *__restrict__ head,
-    double *__restrict__ cur_vel) {
-  const int b = record_mission(blockIdx.x * kRecordThreads + threadIdx.x, n, subset, B);
+    LaunchList list, const double *__restrict__ cmd, int cap, const int *__restrict__ cmd_len,
+    const int *__restrict__ cmd_index, const double *__restrict__ head, double *__restrict__ cur_vel) {
+  const int b = list.request(blockIdx.x * kRecordThreads + threadIdx.x);
   if (b < 0) return;
   int len = cmd_len[b];
   len = len > cap ? cap : len;
@@ -52,44 +46,31 @@ __global__ __launch_bounds__(kRecordThreads) void record_state_kernel(
 
 // row_of[k], k < n: the dataset row of the mission at position k -- *n_rows + its rank among the launched missions
 // with solved != 0 -- or -1: not solved, not a mission, or the row would lie at or beyond `capacity` (counted in
-// *dropped).  ONE workgroup walks the positions in chunks of kRecordRankThreads with a ballot and prefix counts, as
-// batch_compact_kernel does: rows follow the positions whatever the scheduling.  *n_rows advances by the rows given.
+// *dropped).  ONE workgroup walks the positions in chunks of kRecordRankThreads with ordered_rank
+// (neo_launch_list.hpp): rows follow the positions whatever the scheduling.  *n_rows advances by the rows given.
 __global__ __launch_bounds__(kRecordRankThreads) void record_rank_kernel(
-    int B, int n, const int *__restrict__ subset, const int *__restrict__ solved, int capacity,
-    int *__restrict__ row_of, int *__restrict__ n_rows, int *__restrict__ dropped) {
-  constexpr int kWaves = kRecordRankThreads / kWave;
-  __shared__ int wave_cnt[kWaves];
-  __shared__ int base_s, first_s;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    LaunchList list, const int *__restrict__ solved, int capacity, int *__restrict__ row_of, int *__restrict__ n_rows,
+    int *__restrict__ dropped) {
+  __shared__ RankLds<kRecordRankThreads> ranks;
+  __shared__ int first_s;
+  const int tid = threadIdx.x, n = list.size();
   if (tid == 0) {
     const int at = *n_rows;
     first_s = at < 0 ? 0 : (at > capacity ? capacity : at);
-    base_s = 0;
+    ranks.base = 0;
   }
   __syncthreads();
   const int first = first_s;
   const int room = capacity - first;  // >= 0
   for (int at = 0; at < n; at += kRecordRankThreads) {
     const int k = at + tid;
-    const int b = record_mission(k, n, subset, B);
+    const int b = list.request(k);
     const bool take = b >= 0 && (!solved || solved[b] != 0);
-    const unsigned long long m = __ballot(take);
-    if (lane == 0) wave_cnt[wv] = __popcll(m);
-    __syncthreads();
-    int rank = base_s;
-    for (int q = 0; q < wv; ++q) rank += wave_cnt[q];
-    rank += __popcll(m & ((1ull << lane) - 1ull));
+    const int rank = ordered_rank(take, ranks);
     if (k < n) row_of[k] = (take && rank < room) ? first + rank : -1;
-    __syncthreads();
-    if (tid == 0) {
-      int total = 0;
-      for (int q = 0; q < kWaves; ++q) total += wave_cnt[q];
-      base_s += total;
-    }
-    __syncthreads();
   }
   if (tid == 0) {
-    const int total = base_s, given = total < room ? total : room;
+    const int total = ranks.base, given = total < room ? total : room;
     *n_rows = first + given;
     *dropped += total - given;
   }
@@ -170,13 +151,13 @@ struct RecordData {  // the dataset: `capacity` rows each
 };
 
 __global__ __launch_bounds__(kRecordThreads) void record_commit_kernel(
-    int B, int n, const int *__restrict__ subset, const int *__restrict__ row_of, int capacity, int M,
-    const double *__restrict__ x, const double *__restrict__ head, const double *__restrict__ tail,
-    const double *__restrict__ pose, const double *__restrict__ cur_vel, const unsigned char *__restrict__ staging,
-    size_t hw, const int *__restrict__ mission_ids, int tick, int round, RecordData d) {
+    LaunchList list, const int *__restrict__ row_of, int capacity, int M, const double *__restrict__ x,
+    const double *__restrict__ head, const double *__restrict__ tail, const double *__restrict__ pose,
+    const double *__restrict__ cur_vel, const unsigned char *__restrict__ staging, size_t hw,
+    const int *__restrict__ mission_ids, int tick, int round, RecordData d) {
 #pragma clang fp contract(off)
   const int k = blockIdx.x;
-  const int b = record_mission(k, n, subset, B);  // workgroup-uniform
+  const int b = list.request(k);  // workgroup-uniform
   if (b < 0) return;
   const int row = row_of[k];
   if (row < 0 || row >= capacity) return;

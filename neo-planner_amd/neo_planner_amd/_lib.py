@@ -188,6 +188,16 @@ def as_f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def dev_ptr(t):
+    """device pointer of a torch tensor (None -> NULL)"""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def launch_count(subset, B):
+    """positions a launch covers: the subset's entries, or all B requests without one"""
+    return B if subset is None else int(subset.numel())
+
+
 class Context:
     """one neo_ctx: a device, a HIP stream, the uploaded maps"""
 

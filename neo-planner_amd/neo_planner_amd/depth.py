@@ -6,7 +6,6 @@ warm starts to `BatchPlanner.plan`.
 The arithmetic is raycast_depth's in float32, fixed operation by operation (tests/depth_oracle_np.py restates it in
 NumPy and the kernel is tested against that bit for bit); against the float64 raycast_depth the uint8 image differs, if
 at all, in a silhouette pixel whose ray passes an edge within fp32 rounding."""
-import ctypes
 
 import numpy as np
 
@@ -115,7 +114,7 @@ class DepthCamera:
                 (scene_index is not None and scene_index.dtype != torch.int32):
             raise ValueError("DepthCamera.render_dev: boxes and pose float64, box_begin and scene_index int32")
         c = self.ctx
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        p = _lib.dev_ptr
         torch.cuda.synchronize(dev)        # (the context has its own stream: the tensors above are ready before it starts)
         for b0 in range(0, B, chunk):
             n = min(chunk, B - b0)

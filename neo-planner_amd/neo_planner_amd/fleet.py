@@ -37,7 +37,6 @@ A mission's flight does not depend on which other missions share the fleet: the 
 jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
 retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream_ids`).
 """
-import ctypes
 import time
 
 import numpy as np
@@ -221,7 +220,7 @@ class FleetReplanLoop:
         import torch
         c = self.bp.ctx
         self._device = dev = torch.device("cuda", c.device)
-        self._p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        self._p = _lib.dev_ptr
         B = self.B
         f = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
         i = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)

@@ -8,7 +8,6 @@ scenes' map-table slots.  A tick of sensing is `update`: render the depth images
 cells changed (neo_esdf_build_2d_batch_dev, in place: slots stay valid).  Unknown cells count as free, as in
 ESDF.occupancy_map_cb.  `FleetReplanLoop(..., onboard=mapper, scenes=..., scene_index=...)` flies on these maps and is
 audited against the true ones."""
-import ctypes
 import time
 
 import numpy as np
@@ -51,7 +50,7 @@ class OnboardMapper:
         self.origins = np.array(np.broadcast_to(org.reshape(-1, 2), (self.B, 2)), dtype=np.float64, order="C")
         self.chunk = max(1, int(chunk))
         self._device = dev = torch.device("cuda", self.ctx.device)
-        self._p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        self._p = _lib.dev_ptr
         self.logodds = torch.empty((self.B, self.height, self.width), dtype=torch.int8, device=dev)
         self.occupancy = torch.empty((self.B, self.height, self.width), dtype=torch.int8, device=dev)
         self.changed = torch.zeros(self.B, dtype=torch.int32, device=dev)
@@ -118,7 +117,7 @@ class OnboardMapper:
             sub = subset if hasattr(subset, "data_ptr") else torch.from_numpy(self._host_subset(subset)).to(self._device)
             if sub.dtype != torch.int32 or not sub.is_contiguous():
                 raise ValueError("OnboardMapper.integrate: subset must be a contiguous int32 array")
-        n = self.B if sub is None else int(sub.numel())
+        n = _lib.launch_count(sub, self.B)
         if tuple(depth_m.shape) != (n, cam.height, cam.width) or depth_m.dtype != torch.float32 or not depth_m.is_contiguous():
             raise ValueError("OnboardMapper.integrate: depth_m must be a contiguous (n, H, W) float32 tensor")
         if tuple(pose.shape) != (n, 5) or pose.dtype != torch.float64 or not pose.is_contiguous():

@@ -14,7 +14,6 @@ GPU through libneo_planner_hip.so; this file only packs arguments, keeps the ref
 retry/exception control flow, and unpacks results.  `BatchPlanner` is the batched entry the
 reference does not have: B independent replans in one launch.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -569,7 +568,7 @@ class BatchPlanner:
         D = head.shape[2]
         M = (n + D) // (D + 1)
         c = self.ctx
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        p = _lib.dev_ptr
         w = _audit_weights(weights)
         c.check(c.lib.neo_audit_traj_batch_dev(c.h, map.scene_id, p(slots), B, M, D, p(x), p(head), p(tail), float(hz),
                                                _lib.ptr(w), p(audit), p(count), p(flags)))
@@ -610,7 +609,7 @@ class BatchPlanner:
         results into key_pts (B, 4, 2), path_cost (B,) float64, path_len, expansions, flags (B,) int32 and, when given,
         paths (B, path_cap, 2) float64.  `slots`: optional int32 device tensor of map-table slots, as in optimize_dev"""
         c = self.ctx
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        p = _lib.dev_ptr
         B = start.shape[0]
         cap = 0 if paths is None else paths.shape[1]
         c.check(c.lib.neo_geo_search_batch_dev(c.h, map.scene_id, p(slots), B, p(start), p(target), int(max_expansions),
@@ -654,7 +653,7 @@ class BatchPlanner:
         B, n = x.shape
         D = head.shape[2]
         M = (n + D) // (D + 1)
-        pp = lambda t: ctypes.c_void_p(t.data_ptr())
+        pp = _lib.dev_ptr
         sizes = []
         subset, resume = None, 0
         for _ in range(max_launches):
@@ -662,7 +661,7 @@ class BatchPlanner:
                 c.h, map.scene_id, B, M, D, pp(x0), pp(x), pp(head), pp(tail), pp(costs), pp(costs_last), pp(nit), pp(nfev),
                 pp(status), pp(state), int(eval_budget), None if subset is None else pp(subset),
                 0 if subset is None else int(subset.numel()), resume))
-            sizes.append(B if subset is None else int(subset.numel()))
+            sizes.append(_lib.launch_count(subset, B))
             c.synchronize()
             # (the statuses decide the next launch: this is the host round trip a budget costs)
             subset = torch.nonzero(status == _lib.NEO_TRAJ_SUSPENDED).flatten().to(torch.int32)
@@ -908,11 +907,11 @@ class BatchPlanner:
         if seed is None:
             seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
         frac, tau = self._plan_frac_tau(count)
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        p = _lib.dev_ptr
         slots_k = p(d["slots_k"]) if slots is not None else None
         out_x, out_solved = (x if x is not None else d["x"]), (solved if solved is not None else d["solved"])
         n_failed, bad = p(d["counts"][0:]), p(d["counts"][1:])
-        sub, P = p(subset), (B if subset is None else int(subset.numel()))
+        sub, P = p(subset), _lib.launch_count(subset, B)
         launches = []
         bad_scene = None
         c.check(c.lib.neo_optimize_progress_counter(c.h, None))
@@ -1046,8 +1045,8 @@ class BatchPlanner:
         count = int(self.cfg.init_wpts_num)
         M = count + 1
         _, tau = self._batch_ts_tau(count)
-        P = B if subset is None else int(subset.numel())
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        P = _lib.launch_count(subset, B)
+        p = _lib.dev_ptr
         d = bufs
         c.check(c.lib.neo_batch_candidates_dev(c.h, B, p(subset), P, M, D, K, p(head), p(tail), p(slots), _lib.ptr(tau),
                                                _lib.ptr(off), p(d["x_k"]), p(d["head_k"]), p(d["tail_k"]),
@@ -1156,7 +1155,6 @@ class BatchPlanner:
     def expected_effort_order_dev(self, x0, head, tail):
         """the same order computed on the device from RESIDENT torch tensors x0 (B, n), head / tail (B, 3, D) -- a keys kernel
         and a radix sort on the context's stream (neo_effort_order_dev); returns (order int32 [B], keys float64 [B]) device tensors"""
-        import ctypes
         import torch
         self._sync()
         c = self.ctx
@@ -1165,7 +1163,7 @@ class BatchPlanner:
         M = (n + D) // (D + 1)
         scratch = torch.empty(int(c.lib.neo_effort_order_scratch_bytes(B)) // 8 + 1, dtype=torch.float64, device=x0.device)   # (keys first)
         order = torch.empty(B, dtype=torch.int32, device=x0.device)
-        pp = lambda t: ctypes.c_void_p(t.data_ptr())
+        pp = _lib.dev_ptr
         c.check(c.lib.neo_effort_order_dev(c.h, B, M, D, pp(x0), pp(head), pp(tail), pp(scratch), pp(order)))
         return order, scratch[:B]
 
@@ -1224,7 +1222,7 @@ class BatchPlanner:
         D = head.shape[2]
         M = (n + D) // (D + 1)
         c = self.ctx
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        p = _lib.dev_ptr
         c.check(c.lib.neo_optimize_progress_counter(c.h, p(progress)))
         c.check(c.lib.neo_optimize_batch_from_dev(c.h, map.scene_id, p(slots), B, M, D, p(x0 if x0 is not None else x),
                                                   p(x), p(head), p(tail), p(costs), p(costs_last), p(nit), p(nfev),

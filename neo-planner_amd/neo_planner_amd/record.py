@@ -10,7 +10,6 @@ network to `training_tensors()`.
 
 The reference writes one CSV line and one PNG per plan; here the rows stay in HBM until `rows()` or `save()` asks for
 them, and the loop reads nothing back on their account."""
-import ctypes
 import math
 
 import numpy as np
@@ -102,7 +101,7 @@ class DemoRecorder:
         """one neo_record_commit_dev over the missions `sub` (device int32, or None: all B) -- asynchronous on the context's
         stream; every argument a device tensor indexed by mission"""
         d, c = self._alloc(), self.ctx
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        p = _lib.dev_ptr
         c.check(c.lib.neo_record_commit_dev(
             c.h, int(B), p(sub), int(sub.numel()) if sub is not None else 0, self.M, p(x), p(head), p(tail), p(solved), p(pose),
             p(self.cur_vel), p(self.staging), self.width, self.height, p(mission_ids), int(tick), int(round_), self.capacity,

@@ -26,8 +26,9 @@ def pack_results(x, costs, weights, ctx=None, out=None):
         out = torch.empty(B, n + 5, dtype=torch.float32, device=x.device)
     if ctx is not None and x.is_cuda:
         import ctypes
+        from . import _lib
         w4 = (ctypes.c_double * 4)(*[float(v) for v in weights])
-        pp = lambda t: ctypes.c_void_p(t.data_ptr())
+        pp = _lib.dev_ptr
         ctx.check(ctx.lib.neo_pack_results_dev(ctx.h, B, n, pp(x), pp(costs), ctypes.cast(w4, ctypes.c_void_p), pp(out)))
         return out
     out[:, :n] = x

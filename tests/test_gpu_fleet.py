@@ -458,6 +458,87 @@ def _check_audit_of_flown_rows(maps, flight3, bp):
     assert np.isnan(a3[1]).all() and c3[1] == 0 and f3[1] == _lib.NEO_AUDIT_FLAG_NONFINITE
 
 
+# ------------------------------------------------------------------ 4b. indices to skip, and the empty subset
+SKIP_B = 5
+SKIP_SUBSET = np.array([3, -1, 1, SKIP_B, SKIP_B + 7], dtype=np.int32)     # missions 3 and 1; three indices to skip
+
+
+def _skip_rows(maps, entry):
+    """(call, outputs) of one `_dev` entry point for 5 missions: call(sub, n_sub, outs) launches it on fresh sentinel
+    outputs made by outputs(); every array a launch may write is among them"""
+    torch, dev = _torch()
+    rng = np.random.default_rng(77)
+    B = SKIP_B
+    L = _lib.default_context().lib
+    i32 = lambda a: torch.from_numpy(np.asarray(a, np.int32)).to(dev)
+    f64 = lambda a: torch.from_numpy(np.asarray(a, np.float64)).to(dev)
+    sent = lambda *shape: torch.full(shape, SENTINEL, dtype=torch.float64, device=dev)
+    if entry in ("advance", "pose"):
+        cap = 40
+        cmd = f64(rng.normal(0, 1, (B, cap, 3, 2)))
+        cmd_len = i32(rng.integers(10, cap + 1, B))
+        start = rng.integers(1, 8, B)
+        cur, goal = f64(rng.normal(0, 1, (B, 2))), f64(rng.normal(0, 1, (B, 2)))
+        if entry == "advance":
+            outputs = lambda: [i32(start), i32(np.full(B, -7)), sent(B, 2), sent(B, 3, 2)]
+            call = lambda h, sub, n, o: L.neo_fleet_advance_dev(h, B, sub, n, _p(cmd), cap, _p(cmd_len), _p(o[0]), _p(o[1]),
+                                                                3, 2, _p(o[2]), _p(o[3]))
+        else:
+            idx = i32(start)
+            outputs = lambda: [sent(B, 5)]
+            call = lambda h, sub, n, o: L.neo_fleet_pose_dev(h, B, sub, n, _p(cmd), cap, _p(cmd_len), _p(idx), _p(cur), _p(goal),
+                                                             2.0, _p(o[0]))
+    elif entry == "splice":
+        cap, M = 1200, 3
+        head, tail, wp, ts = synth.replan_requests(1, B, M - 1, D=2)
+        x = f64(npa.BatchPlanner().pack_x(wp, ts))
+        head, tail = f64(head), f64(tail)
+        outputs = lambda: [sent(B, cap, 3, 2), i32(np.full(B, 9)), i32(np.full(B, 5)), i32(np.full(B, 4)), i32(np.zeros(B))]
+        call = lambda h, sub, n, o: L.neo_fleet_splice_dev(h, B, sub, n, M, _p(x), _p(head), _p(tail), None, 60.0, 0, _p(o[0]),
+                                                           cap, _p(o[1]), _p(o[2]), _p(o[3]), _p(o[4]))
+    else:
+        cap = 2400
+        rows = np.zeros((B, cap, 3, 2))
+        rows[:, :, 0, 0] = np.linspace(1.0, 29.0, cap)
+        rows[:, :, 0, 1] = np.linspace(-9.0, 9.0, B)[:, None]
+        rows[:, :, 1:] = rng.normal(0, 0.5, (B, cap, 2, 2))
+        cmd, n_flown = f64(rows), i32(rng.integers(600, cap, B))
+        sid = maps[3][0].scene_id
+        outputs = lambda: [sent(B, _lib.NEO_AUDIT_FIELDS), i32(np.full(B, -1)), i32(np.full(B, -1))]
+        call = lambda h, sub, n, o: L.neo_fleet_audit_batch_dev(h, sid, None, B, sub, n, _p(cmd), cap, _p(n_flown), 6, 60.0,
+                                                                None, _p(o[0]), _p(o[1]), _p(o[2]))
+    return call, outputs
+
+
+@pytest.mark.parametrize("entry", ["advance", "pose", "splice", "audit"])
+def test_indices_to_skip_and_the_empty_subset(maps, entry):
+    """subset [3, -1, 1, B, B + 7] of 5 missions: missions 3 and 1 get the bits of the call without a subset, every
+    other row keeps its sentinel; a subset of no entries returns 0 and writes nothing"""
+    torch, dev = _torch()
+    bp = npa.BatchPlanner()
+    bp._sync()
+    ctx = bp.ctx
+    call, outputs = _skip_rows(maps, entry)
+    sub = torch.from_numpy(SKIP_SUBSET).to(dev)
+
+    def run(s, n):
+        outs = outputs()
+        torch.cuda.synchronize(dev)
+        assert call(ctx.h, _p(s), n, outs) == 0
+        ctx.synchronize()
+        return [o.cpu().numpy() for o in outs]
+
+    fresh = [o.cpu().numpy() for o in outputs()]
+    full, part, none = run(None, 0), run(sub, len(SKIP_SUBSET)), run(sub, 0)
+    on = np.isin(np.arange(SKIP_B), [3, 1])
+    assert all(any(not np.array_equal(f[b], s[b]) for f, s in zip(full, fresh)) for b in range(SKIP_B)), \
+        "the call without a subset left a mission as it was: its rows would check nothing"
+    for f, p, e, s in zip(full, part, none, fresh):
+        assert np.array_equal(p[on], f[on], equal_nan=True)
+        assert np.array_equal(p[~on], s[~on])
+        assert np.array_equal(e, s)
+
+
 # ------------------------------------------------------------------ 5. fleet independence
 @pytest.mark.parametrize("mode", ["basic", "geo"])
 def test_a_mission_flies_the_same_alone_and_in_a_fleet(maps, mode):

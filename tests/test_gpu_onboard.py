@@ -218,6 +218,42 @@ def test_a_subset_leaves_the_other_missions_alone_and_nan_images_mark_nothing():
     assert not np.array_equal(mp.logodds[0].cpu().numpy(), L1[0])
 
 
+def test_indices_to_skip_and_the_empty_subset_in_the_device_form():
+    """subset [3, -1, 1, B, B + 7] of 5 missions (5 x 3 images, the 40 x 30 grid): missions 3 and 1 get the bits of the
+    call without a subset, every other grid keeps its sentinel; a subset of no entries returns 0 and writes nothing"""
+    torch, dev = _torch()
+    cam = DepthCamera(width=5, height=3)
+    cfg, B = SMALL, 5
+    gw, gh = cfg["grid"]
+    scans = [reference(cam, "small", cfg, b)[0] for b in range(B)]
+    origins = torch.from_numpy(np.array([origin_of(cfg, b) for b in range(B)])).to(dev)
+    sub = np.array([3, -1, 1, B, B + 7], dtype=np.int32)
+    c = _lib.default_context()
+
+    def run(subset, n):
+        at = list(range(B)) if subset is None else [int(b) if 0 <= b < B else 0 for b in subset]   # rows by launch position
+        depth = torch.from_numpy(np.stack([scans[b][0] for b in at])).to(dev)
+        pose = torch.from_numpy(np.stack([scans[b][1] for b in at])).to(dev)
+        L = torch.full((B, gh, gw), oon.UNKNOWN, dtype=torch.int8, device=dev)
+        occ = torch.full((B, gh, gw), -1, dtype=torch.int8, device=dev)
+        changed = torch.full((B,), 9, dtype=torch.int32, device=dev)
+        d_sub = None if subset is None else torch.from_numpy(subset).to(dev)
+        torch.cuda.synchronize(dev)
+        assert c.lib.neo_onboard_integrate_batch_dev(
+            c.h, B, _p(d_sub), n, _p(depth), _p(pose), cam.width, cam.height, cam.focal_px, cam.max_range, gw, gh, cfg["res"],
+            _p(origins), cfg["rng"], cfg["band"][0], cfg["band"][1], 17, -8, -40, 70, _p(L), _p(occ), _p(changed)) == 0
+        c.synchronize()
+        return L.cpu().numpy(), occ.cpu().numpy(), changed.cpu().numpy()
+
+    full, part, none = run(None, 0), run(sub, len(sub)), run(sub, 0)
+    on = np.isin(np.arange(B), [3, 1])
+    assert np.all(full[2] != 9) and all((full[0][b] != oon.UNKNOWN).any() for b in (3, 1))
+    for f, p, e, sentinel in zip(full, part, none, (oon.UNKNOWN, -1, 9)):
+        assert np.array_equal(p[on], f[on])
+        assert np.all(p[~on] == sentinel)
+        assert np.all(e == sentinel)
+
+
 def test_host_twin_equals_the_device_form():
     cam = DepthCamera(width=61, height=37)
     cfg = SMALL
