@@ -18,18 +18,13 @@ constexpr int kAuditU = 4;  // samples per lane and round: 256 a round, 4 gather
 
 // (value, index) minimum over the wavefront, ties to the smaller index; the result is returned wave-uniform.  The same
 // scan as wave_max_nonneg (row_shr 1, 2, 4, 8, then the two row broadcasts, read at lane 63), but every DPP move keeps
-// the lane's OWN value where it has no source (bound_ctrl off, old = the value): neutral for a minimum, whatever the
-// values are.
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ int dpp_keep_i(int v) {
-  return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xf, false);
-}
+// the lane's OWN value where it has no source (dpp_keep): neutral for a minimum, whatever the values are.
+// (The six steps are written out: as wave_scan over a (value, index) pair the compiler turns the tie test into other
+//  branches and selects.)
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ void min_first_step(double &v, int &k) {
-  const int lo = dpp_keep_i<CTRL, ROW_MASK>(__double2loint(v));
-  const int hi = dpp_keep_i<CTRL, ROW_MASK>(__double2hiint(v));
-  const int ok = dpp_keep_i<CTRL, ROW_MASK>(k);
-  const double ov = __hiloint2double(hi, lo);
+  const double ov = dpp_keep<CTRL, ROW_MASK>(v);
+  const int ok = dpp_keep<CTRL, ROW_MASK>(k);
   const bool take = ov < v || (ov == v && ok < k);
   v = take ? ov : v;
   k = take ? ok : k;
@@ -41,8 +36,8 @@ __device__ __forceinline__ void wave_min_first(double &v, int &k) {
   min_first_step<0x118>(v, k);
   min_first_step<0x142, 0xa>(v, k);
   min_first_step<0x143, 0xc>(v, k);
-  v = rdlane(v, 63);
-  k = __builtin_amdgcn_readlane(k, 63);
+  v = rdlane(v, kWave - 1);
+  k = rdlane(k, kWave - 1);
 }
 
 // position, velocity and acceleration of piece pc at local time T: the expressions of traj_state_kernel (neo_abi.hip),

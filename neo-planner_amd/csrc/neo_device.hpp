@@ -28,10 +28,10 @@
 #include <hip/hip_fp16.h>
 
 #include "../../include/neo_planner.h"
+#include "neo_wave.hpp"
 
 namespace neo {
 
-constexpr int kWave = 64;
 constexpr int kSlots = 4;  // FLAT layout: n <= 256
 
 struct DevParams {
@@ -122,261 +122,6 @@ struct Map3D {
     f_hi[2] = (float)nz - 0.5f;
   }
 };
-
-// ------------------------------------------------------------------ wave helpers
-__device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
-
-// Ordering of LDS traffic inside ONE wavefront (every workgroup of these kernels is a single wavefront): the LDS
-// executes a wavefront's DS instructions in issue order, so a read issued after a write sees it -- whichever lanes
-// wrote and read.  All that is needed is that the compiler keeps the order: a wavefront-scope fence and a scheduling
-// barrier, no s_barrier and no wait for every outstanding LDS operation as __syncthreads() would add.
-__device__ __forceinline__ void lds_wave_sync() {
-#ifdef NEO_STRONG_SYNC  // (diagnostic builds: a workgroup barrier with its full waits)
-  __syncthreads();
-#else
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-#endif
-}
-
-__device__ __forceinline__ double rdlane(double v, int src /*wave-uniform*/) {
-  int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-  int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float rdlane(float v, int src /*wave-uniform*/) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
-// reciprocal to working precision: v_rcp_f64 (4.6e-8 raw on gfx950) with two Newton steps, v_rcp_f32 (1 ulp) as it is
-__device__ __forceinline__ double precise_rcp(double d) {
-  double r = __builtin_amdgcn_rcp(d);
-  r = fma(fma(-d, r, 1.0), r, r);
-  r = fma(fma(-d, r, 1.0), r, r);
-  return r;
-}
-__device__ __forceinline__ float precise_rcp(float d) { return __builtin_amdgcn_rcpf(d); }
-__device__ __forceinline__ double uniform(double v) {
-  int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-// position markers in the assembly listing (tools/probe/mark_counts.py prices the phases between them); no code
-#ifdef NEO_MARKS
-#define NEO_MARK(name) asm volatile("; NEOMARK " name)
-#else
-#define NEO_MARK(name)
-#endif
-// the value, hidden from loop-invariant code motion and common-subexpression elimination: what is computed from it is
-// computed where it is written (no instruction; used where a hoisted address costs a register across a whole loop)
-__device__ __forceinline__ int opaque(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-// the same for a wave-uniform value (it stays in a scalar register)
-__device__ __forceinline__ int opaque_uniform(int v) {
-  asm volatile("" : "+s"(v));
-  return v;
-}
-// lane predicates compared WHERE THEY ARE USED: the bound goes through an opaque scalar copy, so the compare cannot be
-// hoisted out of the optimiser loop -- where it would be a scalar register pair that lives across the whole loop, is
-// spilled to a lane of a vector register and costs two v_readlane at every use instead of one v_cmp (DevBackend::eval)
-__device__ __forceinline__ bool lane_lt(int bound) { return (int)__lane_id() < opaque_uniform(bound); }
-__device__ __forceinline__ bool lane_ge(int bound) { return (int)__lane_id() >= opaque_uniform(bound); }
-__device__ __forceinline__ bool lane_eq(int which) { return (int)__lane_id() == opaque_uniform(which); }
-__device__ __forceinline__ float uniform(float v) {
-  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
-}
-// ---- DPP cross-lane moves (no LDS round trip).  ctrl: 0x110+n = row_shr:n (lane i <- lane i-n inside
-// its row of 16), 0x142 / 0x143 = row_bcast:15 / row_bcast:31, 0x130 / 0x138 = wave_shl:1 / wave_shr:1.
-// Lanes without a valid source (or masked off by row_mask) receive 0.  With every row enabled that is the
-// instruction's own bound_ctrl zero fill: no register has to be preset to 0 ahead of each move (two v_mov_b32 per
-// fp64 step, 8 of the 34 instructions of a wave_sum); with a row mask the masked rows keep `old`, which must be the 0.
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ int dpp_i(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, ROW_MASK == 0xf);
-}
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __int_as_float(dpp_i<CTRL, ROW_MASK>(__float_as_int(v)));
-}
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ double dpp_d(double v) {
-  const int lo = dpp_i<CTRL, ROW_MASK>(__double2loint(v));
-  const int hi = dpp_i<CTRL, ROW_MASK>(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-// The two row broadcasts of a reduction that is read at lane 63 only: rows masked off by row_mask are left UNDEFINED
-// (no preset register, v_mov_dpp with an undefined `old`).  Lane 63 depends only on written rows: row_bcast:15 (rows 1,
-// 3) gives lane 31 = S1 + S0 and lane 63 = S3 + S2, row_bcast:31 (rows 2, 3) adds lane 31 to lane 63.  Not for scans.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_any_i(int v) {
-  return __builtin_amdgcn_mov_dpp(v, CTRL, ROW_MASK, 0xf, false);
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_any_d(double v) {
-  const int lo = dpp_any_i<CTRL, ROW_MASK>(__double2loint(v));
-  const int hi = dpp_any_i<CTRL, ROW_MASK>(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-// wave-wide sum / max with a fixed association order; the result is returned wave-uniform
-// (taken from lane 63 through v_readlane).  Inclusive scan inside rows, then the two row broadcasts.
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp_d<0x111>(v);
-  v += dpp_d<0x112>(v);
-  v += dpp_d<0x114>(v);
-  v += dpp_d<0x118>(v);
-  v += dpp_any_d<0x142, 0xa>(v);
-  v += dpp_any_d<0x143, 0xc>(v);
-  return rdlane(v, 63);
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  v += dpp_f<0x111>(v);
-  v += dpp_f<0x112>(v);
-  v += dpp_f<0x114>(v);
-  v += dpp_f<0x118>(v);
-  v += __int_as_float(dpp_any_i<0x142, 0xa>(__float_as_int(v)));
-  v += __int_as_float(dpp_any_i<0x143, 0xc>(__float_as_int(v)));
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ __forceinline__ int wave_sum(int v) {
-  v += dpp_i<0x111>(v);
-  v += dpp_i<0x112>(v);
-  v += dpp_i<0x114>(v);
-  v += dpp_i<0x118>(v);
-  v += dpp_any_i<0x142, 0xa>(v);
-  v += dpp_any_i<0x143, 0xc>(v);
-  return __builtin_amdgcn_readlane(v, 63);
-}
-// Four wave-wide sums for little more than the price of one: the four per-lane values are first folded onto one
-// register -- v_permlane32_swap / v_permlane16_swap (gfx950) exchange half-waves and odd/even rows of two registers, so
-// two adds leave the 64 partials of value k on the 16 lanes of row k -- then ONE row-wise DPP scan finishes all four
-// (lane 15 of row k holds the total of value k).  One dependent chain of 7 additions instead of four of 6, 37
-// instructions instead of 80; fixed association order.
-__device__ __forceinline__ void swap_half_waves(double &x, double &y) {  // lanes 32..63 of x <-> lanes 0..31 of y
-  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
-  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
-  x = __hiloint2double((int)hi[0], (int)lo[0]);
-  y = __hiloint2double((int)hi[1], (int)lo[1]);
-}
-__device__ __forceinline__ void swap_odd_even_rows(double &x, double &y) {  // odd rows of x <-> even rows of y
-  const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
-  const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
-  x = __hiloint2double((int)hi[0], (int)lo[0]);
-  y = __hiloint2double((int)hi[1], (int)lo[1]);
-}
-__device__ __forceinline__ void wave_sum4(double a, double b, double c, double d, double &ta, double &tb, double &tc,
-                                          double &td) {
-  swap_half_waves(a, c);
-  double x = a + c;  // lanes 0..31: a folded to 32 values, lanes 32..63: c
-  swap_half_waves(b, d);
-  double y = b + d;
-  swap_odd_even_rows(x, y);
-  double z = x + y;  // row 0: a, row 1: b, row 2: c, row 3: d (16 partials each)
-  z += dpp_d<0x111>(z);
-  z += dpp_d<0x112>(z);
-  z += dpp_d<0x114>(z);
-  z += dpp_d<0x118>(z);
-  ta = rdlane(z, 15);
-  tb = rdlane(z, 31);
-  tc = rdlane(z, 47);
-  td = rdlane(z, 63);
-}
-
-// the same for four fp32 values: 2 + 1 register swaps, 3 adds, one row-wise DPP scan, 4 v_readlane -- the price of about one
-// and a half wave_sum(float) for four sums on ONE dependent chain (the paired two-loop recursion batches its dots).
-// Fixed association order: half-waves first, then odd / even rows, then the 16 lanes of a row left to right.
-__device__ __forceinline__ void wave_sum4(float a, float b, float c, float d, float &ta, float &tb, float &tc, float &td) {
-  auto swap32 = [](float &x, float &y) {  // lanes 32..63 of x <-> lanes 0..31 of y
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-    x = __uint_as_float(r[0]);
-    y = __uint_as_float(r[1]);
-  };
-  auto swap16 = [](float &x, float &y) {  // odd rows of x <-> even rows of y
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-    x = __uint_as_float(r[0]);
-    y = __uint_as_float(r[1]);
-  };
-  swap32(a, c);
-  float x = a + c;  // lanes 0..31: a folded to 32 values, lanes 32..63: c
-  swap32(b, d);
-  float y = b + d;
-  swap16(x, y);
-  float z = x + y;  // row 0: a, row 1: b, row 2: c, row 3: d (16 partials each)
-  z += dpp_f<0x111>(z);
-  z += dpp_f<0x112>(z);
-  z += dpp_f<0x114>(z);
-  z += dpp_f<0x118>(z);
-  ta = rdlane(z, 15);
-  tb = rdlane(z, 31);
-  tc = rdlane(z, 47);
-  td = rdlane(z, 63);
-}
-
-// inclusive prefix sum / prefix maximum over the lanes of the wavefront (non-negative ints; the same DPP sequence as
-// wave_sum, which is that scan read at lane 63)
-__device__ __forceinline__ int wave_scan_add(int v) {
-  v += dpp_i<0x111>(v);
-  v += dpp_i<0x112>(v);
-  v += dpp_i<0x114>(v);
-  v += dpp_i<0x118>(v);
-  v += dpp_i<0x142, 0xa>(v);
-  v += dpp_i<0x143, 0xc>(v);
-  return v;
-}
-__device__ __forceinline__ int wave_scan_max_nonneg(int v) {
-  v = max(v, dpp_i<0x111>(v));
-  v = max(v, dpp_i<0x112>(v));
-  v = max(v, dpp_i<0x114>(v));
-  v = max(v, dpp_i<0x118>(v));
-  v = max(v, dpp_i<0x142, 0xa>(v));
-  v = max(v, dpp_i<0x143, 0xc>(v));
-  return v;
-}
-// maxima of NON-NEGATIVE values (the 0 fill of the DPP moves is then neutral)
-__device__ __forceinline__ double wave_max_nonneg(double v) {
-  v = fmax(v, dpp_d<0x111>(v));
-  v = fmax(v, dpp_d<0x112>(v));
-  v = fmax(v, dpp_d<0x114>(v));
-  v = fmax(v, dpp_d<0x118>(v));
-  v = fmax(v, dpp_any_d<0x142, 0xa>(v));
-  v = fmax(v, dpp_any_d<0x143, 0xc>(v));
-  return rdlane(v, 63);
-}
-__device__ __forceinline__ float wave_max_nonneg(float v) {
-  v = fmaxf(v, dpp_f<0x111>(v));
-  v = fmaxf(v, dpp_f<0x112>(v));
-  v = fmaxf(v, dpp_f<0x114>(v));
-  v = fmaxf(v, dpp_f<0x118>(v));
-  v = fmaxf(v, __int_as_float(dpp_any_i<0x142, 0xa>(__float_as_int(v))));
-  v = fmaxf(v, __int_as_float(dpp_any_i<0x143, 0xc>(__float_as_int(v))));
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ __forceinline__ int wave_max_nonneg(int v) {
-  v = max(v, dpp_i<0x111>(v));
-  v = max(v, dpp_i<0x112>(v));
-  v = max(v, dpp_i<0x114>(v));
-  v = max(v, dpp_i<0x118>(v));
-  v = max(v, dpp_any_i<0x142, 0xa>(v));
-  v = max(v, dpp_any_i<0x143, 0xc>(v));
-  return __builtin_amdgcn_readlane(v, 63);
-}
-// value of lane (l-1) / (l+1); lanes without such a neighbour get `fill`
-__device__ __forceinline__ double from_prev(double v, double fill) {
-  const double o = dpp_d<0x138>(v);  // wave_shr:1
-  return lane_eq(0) ? fill : o;
-}
-__device__ __forceinline__ double from_next(double v, double fill) {
-  const double o = dpp_d<0x130>(v);  // wave_shl:1
-  return lane_eq(kWave - 1) ? fill : o;
-}
-__device__ __forceinline__ float from_prev(float v, float fill) {
-  const float o = dpp_f<0x138>(v);
-  return lane_eq(0) ? fill : o;
-}
-__device__ __forceinline__ float from_next(float v, float fill) {
-  const float o = dpp_f<0x130>(v);
-  return lane_eq(kWave - 1) ? fill : o;
-}
 
 // ------------------------------------------------------------------ map lookups
 // esdf.py:53-82: nearest cell with int() truncation; out of range -> 10000 / zero gradient.
@@ -682,19 +427,13 @@ struct WaveLanes {
   static __device__ __forceinline__ int lane() { return lane_id(); }
   static __device__ __forceinline__ int piece() { return lane_id(); }
   static __device__ __forceinline__ int dim0() { return 0; }
-  static __device__ __forceinline__ double sum_dims(double v) { return v; }
   static __device__ __forceinline__ int base() { return 0; }
-  static __device__ __forceinline__ double read(double v, int src /*wave-uniform*/) { return rdlane(v, src); }
-  static __device__ __forceinline__ double prev(double v, double fill) { return from_prev(v, fill); }
-  static __device__ __forceinline__ double next(double v, double fill) { return from_next(v, fill); }
-  static __device__ __forceinline__ double sum(double v) { return wave_sum(v); }
-  static __device__ __forceinline__ int sum(int v) { return wave_sum(v); }
+  template <class T> static __device__ __forceinline__ T sum_dims(T v) { return v; }
+  template <class T> static __device__ __forceinline__ T read(T v, int src /*wave-uniform*/) { return rdlane(v, src); }
+  template <class T> static __device__ __forceinline__ T prev(T v, T fill) { return from_prev(v, fill); }
+  template <class T> static __device__ __forceinline__ T next(T v, T fill) { return from_next(v, fill); }
+  template <class T> static __device__ __forceinline__ T sum(T v) { return wave_sum(v); }
   static __device__ __forceinline__ int any(int pred) { return __any(pred); }
-  static __device__ __forceinline__ float sum_dims(float v) { return v; }
-  static __device__ __forceinline__ float read(float v, int src) { return rdlane(v, src); }
-  static __device__ __forceinline__ float prev(float v, float fill) { return from_prev(v, fill); }
-  static __device__ __forceinline__ float next(float v, float fill) { return from_next(v, fill); }
-  static __device__ __forceinline__ float sum(float v) { return wave_sum(v); }
   static __host__ __device__ __forceinline__ int lanes_per_piece(int M);
 };
 
@@ -706,72 +445,37 @@ struct GroupLanes {
   static constexpr int dl(int D) { return D; }
   static __device__ __forceinline__ int piece() { return lane_id() & (W - 1); }
   static __device__ __forceinline__ int dim0() { return 0; }
-  static __device__ __forceinline__ double sum_dims(double v) { return v; }
   static __device__ __forceinline__ int lane() { return lane_id() & (W - 1); }
   static __device__ __forceinline__ int base() { return lane_id() & ~(W - 1); }
+  template <class T> static __device__ __forceinline__ T sum_dims(T v) { return v; }
   // sums / maxima over the group, result in every lane.  W = 16: the in-row part of wave_sum (row_shr scan, then the
   // last lane's value to everybody).  W = 8: xor butterfly (quad_perm swaps, then row_half_mirror), which never reads
   // the other group of the row.  Both associate ((v0+v1)+(v2+v3)) + ((v4+v5)+(v6+v7)) [+ the same of the upper half].
   template <class T, class Op>
   static __device__ __forceinline__ T reduce(T v, Op op) {
     if constexpr (W == 16) {
-      if constexpr (sizeof(T) == 8) {
-        v = op(v, dpp_d<0x111>(v)); v = op(v, dpp_d<0x112>(v)); v = op(v, dpp_d<0x114>(v)); v = op(v, dpp_d<0x118>(v));
-      } else if constexpr (std::is_same<T, float>::value) {
-        v = op(v, dpp_f<0x111>(v)); v = op(v, dpp_f<0x112>(v)); v = op(v, dpp_f<0x114>(v)); v = op(v, dpp_f<0x118>(v));
-      } else {
-        v = op(v, dpp_i<0x111>(v)); v = op(v, dpp_i<0x112>(v)); v = op(v, dpp_i<0x114>(v)); v = op(v, dpp_i<0x118>(v));
-      }
-      return __shfl(v, base() + W - 1, kWave);
+      return __shfl(row_scan(v, op), base() + W - 1, kWave);
     } else {
       // quad_perm:[1,0,3,2] = 0xB1, quad_perm:[2,3,0,1] = 0x4E, row_half_mirror = 0x141
-      if constexpr (sizeof(T) == 8) {
-        v = op(v, dpp_d<0xB1>(v)); v = op(v, dpp_d<0x4E>(v)); v = op(v, dpp_d<0x141>(v));
-      } else if constexpr (std::is_same<T, float>::value) {
-        v = op(v, dpp_f<0xB1>(v)); v = op(v, dpp_f<0x4E>(v)); v = op(v, dpp_f<0x141>(v));
-      } else {
-        v = op(v, dpp_i<0xB1>(v)); v = op(v, dpp_i<0x4E>(v)); v = op(v, dpp_i<0x141>(v));
-      }
+      v = op(v, dpp<0xB1>(v)); v = op(v, dpp<0x4E>(v)); v = op(v, dpp<0x141>(v));
       return v;
     }
   }
-  static __device__ __forceinline__ double sum(double v) {
-    return reduce(v, [](double a, double b) { return a + b; });
-  }
-  static __device__ __forceinline__ int sum(int v) {
-    return reduce(v, [](int a, int b) { return a + b; });
-  }
-  static __device__ __forceinline__ double max_nonneg(double v) {
-    return reduce(v, [](double a, double b) { return fmax(a, b); });
-  }
+  template <class T> static __device__ __forceinline__ T sum(T v) { return reduce(v, OpAdd()); }
+  template <class T> static __device__ __forceinline__ T max_nonneg(T v) { return reduce(v, OpMax()); }
   static __device__ __forceinline__ int any(int pred) {
     return reduce(pred ? 1 : 0, [](int a, int b) { return a | b; });
   }
-  static __device__ __forceinline__ double read(double v, int src /* lane inside the group, the same for all groups */) {
+  template <class T>
+  static __device__ __forceinline__ T read(T v, int src /* lane inside the group, the same for all groups */) {
     return __shfl(v, base() + src, kWave);
   }
-  static __device__ __forceinline__ float sum(float v) {
-    return reduce(v, [](float a, float b) { return a + b; });
-  }
-  static __device__ __forceinline__ float max_nonneg(float v) {
-    return reduce(v, [](float a, float b) { return fmaxf(a, b); });
-  }
-  static __device__ __forceinline__ float sum_dims(float v) { return v; }
-  static __device__ __forceinline__ float read(float v, int src) { return __shfl(v, base() + src, kWave); }
-  static __device__ __forceinline__ float prev(float v, float fill) {
-    const float o = dpp_f<0x138>(v);
+  template <class T> static __device__ __forceinline__ T prev(T v, T fill) {
+    const T o = dpp<0x138>(v);  // wave_shr:1
     return lane() == 0 ? fill : o;
   }
-  static __device__ __forceinline__ float next(float v, float fill) {
-    const float o = dpp_f<0x130>(v);
-    return lane() == W - 1 ? fill : o;
-  }
-  static __device__ __forceinline__ double prev(double v, double fill) {
-    const double o = dpp_d<0x138>(v);  // wave_shr:1
-    return lane() == 0 ? fill : o;
-  }
-  static __device__ __forceinline__ double next(double v, double fill) {
-    const double o = dpp_d<0x130>(v);  // wave_shl:1
+  template <class T> static __device__ __forceinline__ T next(T v, T fill) {
+    const T o = dpp<0x130>(v);  // wave_shl:1
     return lane() == W - 1 ? fill : o;
   }
   static __host__ __device__ __forceinline__ int lanes_per_piece(int M) {
@@ -794,50 +498,28 @@ struct WaveLanesPD {
   //  reloads an evaluation and adds 65 vector instructions: 1.457 against 1.455 M traj/s, not kept)
   static __device__ __forceinline__ int dim0() { return lane_id() - S * piece(); }
   // value held by piece q (any of its lanes: used for quantities that depend on the durations only)
-  static __device__ __forceinline__ double read(double v, int q /*wave-uniform*/) { return rdlane(v, S * q); }
+  template <class T> static __device__ __forceinline__ T read(T v, int q /*wave-uniform*/) { return rdlane(v, S * q); }
   // value of the same dimension in the previous / next piece: S single-lane DPP shifts
-  static __device__ __forceinline__ double prev(double v, double fill) {
-#pragma unroll
-    for (int k = 0; k < S; ++k) v = dpp_d<0x138>(v);  // wave_shr:1
-    return lane_lt(S) ? fill : v;
-  }
-  static __device__ __forceinline__ double next(double v, double fill) {
-#pragma unroll
-    for (int k = 0; k < S; ++k) v = dpp_d<0x130>(v);  // wave_shl:1
-    return lane_ge(kWave - S) ? fill : v;
-  }
-  static __device__ __forceinline__ double sum(double v) { return wave_sum(v); }
-  static __device__ __forceinline__ int sum(int v) { return wave_sum(v); }
-  static __device__ __forceinline__ int any(int pred) { return __any(pred); }
-  static __device__ __forceinline__ float read(float v, int q) { return rdlane(v, S * q); }
   // (one ds_bpermute instead of the S chained shifts was measured on the MI355X and lost: cfg2 1.39 -> 1.37 M traj/s, a
   //  single batch 692 k -> 660 k -- the LDS round trip sits on the dependent chain, and the LDS pipe is busy too)
-  static __device__ __forceinline__ float prev(float v, float fill) {
+  template <class T> static __device__ __forceinline__ T prev(T v, T fill) {
 #pragma unroll
-    for (int k = 0; k < S; ++k) v = dpp_f<0x138>(v);
+    for (int k = 0; k < S; ++k) v = dpp<0x138>(v);  // wave_shr:1
     return lane_lt(S) ? fill : v;
   }
-  static __device__ __forceinline__ float next(float v, float fill) {
+  template <class T> static __device__ __forceinline__ T next(T v, T fill) {
 #pragma unroll
-    for (int k = 0; k < S; ++k) v = dpp_f<0x130>(v);
+    for (int k = 0; k < S; ++k) v = dpp<0x130>(v);  // wave_shl:1
     return lane_ge(kWave - S) ? fill : v;
   }
-  static __device__ __forceinline__ float sum(float v) { return wave_sum(v); }
-  static __device__ __forceinline__ float sum_dims(float v) {
-    float acc = v, t = v;
-#pragma unroll
-    for (int k = 1; k < S; ++k) {
-      t = dpp_f<0x130>(t);
-      acc += t;
-    }
-    return acc;
-  }
+  template <class T> static __device__ __forceinline__ T sum(T v) { return wave_sum(v); }
+  static __device__ __forceinline__ int any(int pred) { return __any(pred); }
   // sum over the S lanes (dimensions) of a piece; valid in the piece's first lane
-  static __device__ __forceinline__ double sum_dims(double v) {
-    double acc = v, t = v;
+  template <class T> static __device__ __forceinline__ T sum_dims(T v) {
+    T acc = v, t = v;
 #pragma unroll
     for (int k = 1; k < S; ++k) {
-      t = dpp_d<0x130>(t);
+      t = dpp<0x130>(t);
       acc += t;
     }
     return acc;
@@ -1516,14 +1198,6 @@ __host__ __device__ __forceinline__ int sample_lanes_per_piece(int M) {
 __host__ __device__ __forceinline__ int WaveLanes::lanes_per_piece(int M) { return sample_lanes_per_piece(M); }
 __host__ __device__ __forceinline__ int sample_lanes_per_piece_fwd(int M) { return sample_lanes_per_piece(M); }
 
-template <typename Real, int CTRL>
-__device__ __forceinline__ Real dpp_real(Real v) {
-  if constexpr (sizeof(Real) == 4)
-    return dpp_f<CTRL>(v);
-  else
-    return dpp_d<CTRL>(v);
-}
-
 // sum over the L lanes (residues r = 0..L-1, adjacent lanes) of each piece; valid in the lane with r = 0.
 // L <= 4 (M >= 16): wave_shl:1 DPP moves, summed left to right ((v_0 + v_1) + v_2) + v_3.
 // L = 8, 16, 32, 64: halving tree with row_shl DPP moves (lane i <- lane i + s inside its row of 16), rows joined
@@ -1539,7 +1213,7 @@ __device__ __forceinline__ void fold_piece_lanes(Real (&v)[N], int L, int r) {
     for (int i = 1; i < L; ++i) {
 #pragma unroll
       for (int q = 0; q < N; ++q) {
-        t[q] = dpp_real<Real, 0x130>(t[q]);
+        t[q] = dpp<0x130>(t[q]);
         v[q] += t[q];
       }
     }
@@ -1548,13 +1222,13 @@ __device__ __forceinline__ void fold_piece_lanes(Real (&v)[N], int L, int r) {
   if ((L & (L - 1)) == 0) {
     if (L >= 16) {
 #pragma unroll
-      for (int q = 0; q < N; ++q) v[q] += dpp_real<Real, 0x108>(v[q]);  // row_shl:8
+      for (int q = 0; q < N; ++q) v[q] += dpp<0x108>(v[q]);  // row_shl:8
     }
 #pragma unroll
     for (int q = 0; q < N; ++q) {
-      v[q] += dpp_real<Real, 0x104>(v[q]);  // row_shl:4
-      v[q] += dpp_real<Real, 0x102>(v[q]);
-      v[q] += dpp_real<Real, 0x101>(v[q]);
+      v[q] += dpp<0x104>(v[q]);  // row_shl:4
+      v[q] += dpp<0x102>(v[q]);
+      v[q] += dpp<0x101>(v[q]);
     }
     if (L >= 32) {
 #pragma unroll

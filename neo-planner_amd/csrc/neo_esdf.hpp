@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void edt3_x_kernel(const uint8_t *__restrict__
     const int v = (idx < nx && o[idx]) ? idx + 1 : 0;
     const int s = max(wave_scan_max_nonneg(v), carry);
     if (idx < nx) left[idx] = (uint16_t)(s ? min(idx + 1 - s, kXInf) : kXInf);
-    carry = __builtin_amdgcn_readlane(s, kWave - 1);
+    carry = rdlane(s, kWave - 1);
   }
   lds_wave_sync();
   carry = 0;  // nx - index of the nearest occupied voxel to the right so far (>= 1), 0 = none
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void edt3_x_kernel(const uint8_t *__restrict__
       const int right = s ? (nx - s) - idx : kXInf;
       gx[row * nx + idx] = (uint16_t)min(min((int)left[idx], right), kXInf);
     }
-    carry = __builtin_amdgcn_readlane(s, kWave - 1);
+    carry = rdlane(s, kWave - 1);
   }
 }
 

@@ -2,7 +2,7 @@
 // w = 1..3 wavefronts per SIMD; with and without independent v_fma_f32 work beside it (does the matrix pipe overlap?).
 //   hipcc --offload-arch=gfx950 -O3 tools/probe/reduce_rate.hip -o tools/probe/_build/reduce_rate
 // Variants:
-//   0  six DPP adds (row_shr 1,2,4,8, row_bcast15, row_bcast31) + v_readlane 63   (csrc/neo_device.hpp wave_sum)
+//   0  six DPP adds (row_shr 1,2,4,8, row_bcast15, row_bcast31) + v_readlane 63   (csrc/neo_wave.hpp wave_sum)
 //   1  v_mfma_f32_16x16x4_f32 (ones x v: lane l gets v[l%16] + v[l%16+16] + v[l%16+32] + v[l%16+48]) + four DPP adds
 //      (row_ror 8,4,2,1): total in every lane, no v_readlane
 //   2  four DPP adds (row_ror) + v_permlane16_swap + add + v_permlane32_swap + add: total in every lane

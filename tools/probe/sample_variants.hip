@@ -181,7 +181,7 @@ __device__ __forceinline__ void consume(const Field &f, const float (&c)[6][3], 
 __device__ __forceinline__ float fold_dpp(float v, int L, int r) {
   if (L <= 4) {
     float acc = v;
-    for (int i = 1; i < L; ++i) acc = v + dpp_f<0x130>(acc);  // wave_shl:1
+    for (int i = 1; i < L; ++i) acc = v + dpp<0x130>(acc);  // wave_shl:1
     return acc;
   }
   for (int sft = 1; sft < L; sft <<= 1) {
