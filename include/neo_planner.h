@@ -814,6 +814,12 @@ int neo_pack_results_dev(neo_ctx *ctx, int B, int n, const double *x, const doub
  * B = 0 resets.  Independent of neo_optimize_dispatch_order. */
 int neo_sampled_terms_dispatch_order(neo_ctx *ctx, const int32_t *order, int on_device, int B);
 int neo_profile_read(neo_ctx *ctx, int kernel, int64_t *launches, double *total_ms);
+/* diagnostics, read-only: optimiser launches of this context since it was created, by the form of the kernel that ran
+ * them.  The all-fp32 kernels with one lane per (piece, dimension) and n <= 128 variables exist twice: compiled for the one
+ * launch plan the launcher always chooses for them (fixed_plan), and with the plan's selectors tested at run time
+ * (dynamic_plan) -- the latter runs comparison launches (flags bit 4096), launches with a trace buffer, budgeted launches
+ * and every kernel family that has no fixed plan.  Same results bit for bit; either pointer may be NULL. */
+int neo_optimize_plan_launches(neo_ctx *ctx, int64_t *fixed_plan, int64_t *dynamic_plan);
 int neo_profile_reset(neo_ctx *ctx);
 
 #ifdef __cplusplus

@@ -2194,6 +2194,14 @@ int neo_esdf_build_config(neo_ctx *c, int flags) {
   return NEO_OK;
 }
 
+int neo_optimize_plan_launches(neo_ctx *c, int64_t *fixed_plan, int64_t *dynamic_plan) {
+  if (!c) return NEO_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (fixed_plan) *fixed_plan = c->opt_plan_launches[0];
+  if (dynamic_plan) *dynamic_plan = c->opt_plan_launches[1];
+  return NEO_OK;
+}
+
 int neo_profile_enable(neo_ctx *c, int on) {
   if (!c) return NEO_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> g(c->mu);

@@ -527,6 +527,33 @@ struct WaveLanesPD {
   static __host__ __device__ __forceinline__ int lanes_per_piece(int M) { return sample_lanes_per_piece_fwd(M); }
 };
 
+// ------------------------------------------------------------------ launch plan as a compile-time argument
+// What the launcher decides before a launch (neo_launch_opt.hpp opt_lds_plan) and the kernels otherwise test at run time,
+// evaluation after evaluation, as wave-uniform selectors: which fold of the sampled partials runs, whether the cyclic
+// reduction keeps its multipliers / has its exchange table, whether the lane-assignment cache, the trace hooks and the
+// coefficient store exist.  A kernel compiled for a Plan with `dynamic = false` holds the one alternative the plan names
+// and none of the others; PlanDynamic keeps every selector a run-time value (the kernels as they always were).
+struct PlanDynamic {
+  static constexpr bool dynamic = true;
+  static constexpr bool fold_acc = false, fold_rows = false, pcr_mult = false, pcr_xch = false, sl_cache = false,
+                        trace = false, coeff_out = false;  // (not read: every selector is the run-time value)
+};
+// the plan opt_lds_plan produces for the all-fp32 kernels with lane = (piece, dimension) and n <= 128 variables:
+// accumulator fold, multipliers in LDS, exchange table in the staging buffer, lane cache, no trace, no coefficient store
+struct PlanFixedX {
+  static constexpr bool dynamic = false;
+  static constexpr bool fold_acc = true, fold_rows = true, pcr_mult = true, pcr_xch = true, sl_cache = true,
+                        trace = false, coeff_out = false;
+};
+// a selector under a plan: its run-time value when the plan is dynamic, the plan's constant K otherwise
+template <class Plan, bool K>
+__host__ __device__ __forceinline__ constexpr bool plan_pick(bool run_time) {
+  if constexpr (Plan::dynamic)
+    return run_time;
+  else
+    return K;
+}
+
 // ------------------------------------------------------------------ per-trajectory state
 // DL = dimensions held per lane: D (PIECE layout: lane = piece) or 1 (lane = (piece, dimension), WaveLanesPD)
 template <int D, int DL = D, typename Num = double>
@@ -734,7 +761,8 @@ __device__ __forceinline__ void thomas_solve(int M, const Num (&Lo)[2][2], const
 // `mult` (LDS, may be nullptr): when given, every level's multipliers a, g of every joint and the final pivot inverses are
 // written there -- [level][M + 1][8] (negated) then [M + 1][4] -- for pcr_solve_transposed: K^-1 = Dfin^-1 P_last ... P_1 with P_k = I + (a, g of
 // level k), hence K^-T = P_1^T ... P_last^T Dfin^-T, and the adjoint system K^T lambda = r needs no reduction of its own.
-template <int DL, class LG, typename Num>
+// Plan (fixed launch plans): whether `mult` / `xch` are given is then a constant of the plan, not a test of the pointer.
+template <int DL, class LG, typename Num, class Plan = PlanDynamic>
 __device__ __forceinline__ void pcr_solve(int M, Num (&L)[2][2], Num (&Dg)[2][2], Num (&U)[2][2], Num (&R)[2][DL],
                                           Num (&y)[2][DL], Num *mult = nullptr, Num *xch = nullptr) {
   static_assert(LG::W == kWave, "written for lane groups that span the wavefront");
@@ -757,7 +785,8 @@ __device__ __forceinline__ void pcr_solve(int M, Num (&L)[2][2], Num (&Dg)[2][2]
   // sixth level (M > 33: cfg5) would eliminate is five orders below the rounding of the fp32 solve.
   const int s_end = sizeof(Num) == 4 ? min(M - 1, 32) : M - 1;
   typedef Num Quad __attribute__((ext_vector_type(4)));
-  const bool writer = mult != nullptr && in && LG::dim0() == opaque_uniform(0);  // one lane per joint writes
+  const bool keep = plan_pick<Plan, Plan::pcr_mult>(mult != nullptr), use_xch = plan_pick<Plan, Plan::pcr_xch>(xch != nullptr);
+  const bool writer = keep && in && LG::dim0() == opaque_uniform(0);  // one lane per joint writes
   int level = 0;
   if constexpr (sizeof(Num) == 4) {
     // fp32: the 2 x 2 blocks as ROWS in register pairs, their products as packed operations (v_pk_mul_f32 / v_pk_fma_f32
@@ -783,14 +812,13 @@ __device__ __forceinline__ void pcr_solve(int M, Num (&L)[2][2], Num (&Dg)[2][2]
     // like the others: cheaper than the selects that kept them out.  Every lane stores its multipliers -- the lanes of a
     // joint the same values to the same place, the lanes without a joint into slots nobody reads: piece 0, and slot M, which
     // every level and the table of pivot inverses have for themselves (M + 1 slots each: pcr_mult_elems).
-    const bool keep = mult != nullptr;
     const int ps = min(p, M);  // (store slot: every lane beyond the last piece shares the one past it)
     for (int s = 1; s < s_end; s <<= 1, ++level) {
       invert();
       const int sp = lane - s * LG::S, sn = lane + s * LG::S;
       f2 Ip[2], Lp[2], Upv[2], In[2], Ln[2], Un[2];
       Num Rp[2][DL], Rn[2][DL];
-      if (xch != nullptr) {
+      if (use_xch) {
         // The neighbours' blocks through an LDS table instead of 24 + 4 DL ds_bpermute: every piece writes its I, L, U as
         // three 16-byte stores (the lanes of a piece the same values), every lane reads the two neighbouring pieces'
         // with six 16-byte loads; the right-hand sides travel as 8-byte pairs per lane.  Measured on the MI355X
@@ -861,7 +889,7 @@ __device__ __forceinline__ void pcr_solve(int M, Num (&L)[2][2], Num (&Dg)[2][2]
       }
     }
     invert();
-    if (xch != nullptr) lds_wave_sync();  // (the exchange table is the caller's staging buffer again)
+    if (use_xch) lds_wave_sync();  // (the exchange table is the caller's staging buffer again)
     if (keep) *reinterpret_cast<Quad *>(mult + (size_t)level * (M + 1) * 8 + (size_t)ps * 4) = Quad{Ir[0].x, Ir[0].y, Ir[1].x, Ir[1].y};
 #pragma unroll
     for (int d = 0; d < DL; ++d) {
@@ -1035,7 +1063,8 @@ __device__ __forceinline__ void joint_blocks(const TrajT &t, Num a1, Num a2, Num
 // PCR: solve the joint system by parallel cyclic reduction (pcr_solve) instead of block Thomas -- the all-fp32 mode on a
 // wavefront-wide lane group; fp64 solves keep block Thomas (the parity mode's recorded runs are pinned to that rounding,
 // and the mixed mode measured slower with the reduction in fp64).  The caller passes the same value to minco_backward.
-template <int D, class LG = WaveLanes, typename Num = double, bool PCR = (sizeof(Num) == 4 && LG::W == kWave)>
+template <int D, class LG = WaveLanes, typename Num = double, bool PCR = (sizeof(Num) == 4 && LG::W == kWave),
+          class Plan = PlanDynamic>
 __device__ __forceinline__ int minco_forward(Traj<D, LG::dl(D), Num> &t, const DevParams &prm, double &energy,
                                              double &time_sum) {
   constexpr int DL = LG::dl(D);
@@ -1112,7 +1141,7 @@ __device__ __forceinline__ int minco_forward(Traj<D, LG::dl(D), Num> &t, const D
           Up[i][j] = lane == t.M - 1 ? Num(0.0) : Up[i][j];
         }
       NEO_MARK("fwd_pcr_begin");
-      pcr_solve<DL, LG, Num>(t.M, Lo, Di, Up, R, y, t.pcr_mult, t.pcr_xch);
+      pcr_solve<DL, LG, Num, Plan>(t.M, Lo, Di, Up, R, y, t.pcr_mult, t.pcr_xch);
       NEO_MARK("fwd_pcr_end");
     } else {
       thomas_solve<DL, LG, Num>(NEO_DBG(prm, 2 | 16) ? 1 : t.M, Lo, t.N, E, R, y0, yM, y);
@@ -1441,7 +1470,8 @@ __host__ __device__ constexpr int fold_acc_stride(int D) { return (6 * D + 1 + 3
 // SAMPLE_IO = true (stand-alone kernel): cp / ns_in are already those of the SAMPLE-layout lane's piece, and
 //   gC / gT are left in the first lane (r = 0) of each piece.
 // Costs are returned wave-uniform.  U = samples per lane whose gathers are put in flight together.
-template <typename Real, int D, class LookupT, int U, bool SAMPLE_IO = false, class LG = WaveLanes>
+// Plan (fixed launch plans): which fold runs is then a constant of the plan -- `fold_rows` is still the staging buffer.
+template <typename Real, int D, class LookupT, int U, bool SAMPLE_IO = false, class LG = WaveLanes, class Plan = PlanDynamic>
 __device__ __forceinline__ void minco_sample(int M, const SampleLanes &sl, int ns_in, const Real (&cp)[6][LG::dl(D)],
                                              const DevParams &prm, const LookupT &lk, Real (&gC)[6][LG::dl(D)], Real &gT,
                                              double &cost_feas, double &cost_coll, Real *fold_rows = nullptr,
@@ -1558,8 +1588,11 @@ __device__ __forceinline__ void minco_sample(int M, const SampleLanes &sl, int n
   NEO_MARK("loop_end");
   // (fp32 sampling only: the fp64 parity mode keeps the summation order below, the one its runs were pinned to the
   //  reference's recorded iterates with)
+  // a fixed plan with the accumulator fold: pieces with different numbers of sample lanes (lmax != 0) fold there and
+  // nowhere else -- neither the rows nor fold_piece_segments exist in that kernel
+  constexpr bool kAccOnly = !Plan::dynamic && Plan::fold_rows && Plan::fold_acc && sizeof(Real) == 4 && !SAMPLE_IO && LG::S > 1;
   if constexpr (sizeof(Real) == 4 && !SAMPLE_IO && LG::S > 1) {
-    if (fold_rows != nullptr && fold_acc && sl.lmax != 0) {
+    if (plan_pick<Plan, Plan::fold_rows>(fold_rows != nullptr) && plan_pick<Plan, Plan::fold_acc>(fold_acc) && sl.lmax != 0) {
       // The same per-piece sums in 80 bytes a piece instead of 96 a sample lane (the kernels that keep the cyclic
       // reduction's multipliers in LDS across this phase have no room for the rows): `fold_rows` is [M][fold_acc_stride(D)]
       // = per piece [d][6] partials, the duration partial, padding to 16 bytes (D = 3: 20 floats).  The sample lanes of a piece add their values one after the other --
@@ -1614,8 +1647,8 @@ __device__ __forceinline__ void minco_sample(int M, const SampleLanes &sl, int n
       return;
     }
   }
-  if constexpr (sizeof(Real) == 4) {
-    if (fold_rows != nullptr && sl.lmax != 0) {
+  if constexpr (sizeof(Real) == 4 && !kAccOnly) {
+    if (plan_pick<Plan, Plan::fold_rows>(fold_rows != nullptr) && sl.lmax != 0) {
       // Pieces with different numbers of sample lanes: the per-piece sums go through LDS.  Every sample lane writes its
       // row [d][8] = (aC[0..5][d], aT, 0) (two 16-byte stores a dimension); the receiving lane -- the lane of (piece,
       // dimension) in the fused kernels, the first sample lane of the piece in the stand-alone kernel -- then adds up
@@ -1680,10 +1713,14 @@ __device__ __forceinline__ void minco_sample(int M, const SampleLanes &sl, int n
   fv[6 * D] = aT;
   fv[6 * D + 1] = aF;
   fv[6 * D + 2] = aK;
-  if (sl.lmax == 0)
-    fold_piece_lanes<Real, 6 * D + 3>(fv, L, r);
-  else
-    fold_piece_segments<Real, 6 * D + 3>(fv, r, L, sl.lmax);
+  if constexpr (kAccOnly) {
+    fold_piece_lanes<Real, 6 * D + 3>(fv, L, r);  // (lmax == 0 here: every piece has the same L)
+  } else {
+    if (sl.lmax == 0)
+      fold_piece_lanes<Real, 6 * D + 3>(fv, L, r);
+    else
+      fold_piece_segments<Real, 6 * D + 3>(fv, r, L, sl.lmax);
+  }
   if constexpr (!SAMPLE_IO) {
     // back to the lanes of the piece (sl.first is held by lane p for piece p)
     int src = LG::base() + sl.first;
@@ -1720,7 +1757,8 @@ __device__ __forceinline__ void minco_sample(int M, const SampleLanes &sl, int n
 // Returns 0, or 4 where the reference would leave through OverflowError: it raises Python floats to
 // a power in two places, `(np.dot(c, beta3).item())**2` (:382) and `(1+math.exp(-tau))**2` (:490),
 // and Python raises once such a result exceeds the double range instead of returning inf.
-template <int D, class LG = WaveLanes, typename Num = double, bool PCR = (sizeof(Num) == 4 && LG::W == kWave)>
+template <int D, class LG = WaveLanes, typename Num = double, bool PCR = (sizeof(Num) == 4 && LG::W == kWave),
+          class Plan = PlanDynamic>
 __device__ __forceinline__ int minco_backward(const Traj<D, LG::dl(D), Num> &t, const DevParams &prm,
                                               Num (&gC)[6][LG::dl(D)], Num gT, Num (&gq)[LG::dl(D)], Num &gtau) {
   constexpr int DL = LG::dl(D);
@@ -1778,7 +1816,7 @@ __device__ __forceinline__ int minco_backward(const Traj<D, LG::dl(D), Num> &t, 
   for (int d = 0; d < DL; ++d) lam[0][d] = lam[1][d] = Num(0.0);
   constexpr bool kPcr = PCR;  // the transposed system by pcr_solve, too
   if constexpr (kPcr) {
-    if (M > 1 && t.pcr_mult != nullptr) {
+    if (M > 1 && plan_pick<Plan, Plan::pcr_mult>(t.pcr_mult != nullptr)) {
       Num R[2][DL], y[2][DL];
 #pragma unroll
       for (int d = 0; d < DL; ++d) {

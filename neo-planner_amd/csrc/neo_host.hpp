@@ -90,6 +90,9 @@ struct neo_ctx {
   bool profile = false;
   neo::ProfileSlot prof[NEO_KERNEL_COUNT];
   long long *sample_counter = nullptr;  // optional device array [B] (neo_optimize_sample_counter)
+  // optimize_kernel launches since the context was created, by wrapper: [0] the one compiled for its member's fixed plan,
+  // [1] the one with run-time selectors (neo_launch_opt.hpp; read by neo_optimize_plan_launches)
+  int64_t opt_plan_launches[2] = {0, 0};
   int *progress = nullptr;              // optional device-accessible counter of finished trajectories (neo_optimize_progress_counter)
   const int *dispatch_order = nullptr;  // optional device permutation [B] (neo_optimize_dispatch_order)
   int order_B = 0;                      // batch size the permutation was given for (ignored for any other B)

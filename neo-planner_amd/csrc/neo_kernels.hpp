@@ -72,8 +72,9 @@ __host__ __device__ constexpr bool pairs_in_f32() {
 }
 // PAIRS32: the L-BFGS pairs are stored in fp32
 // Num: arithmetic of the coefficient solve, the adjoint and the optimiser vectors (double; float = the all-fp32 mode)
+// Plan: the launch plan as compile-time constants (neo_device.hpp), or PlanDynamic: the members below decide at run time
 template <int D, int NS, typename Real, class MapT, class LookupT, int SU = NEO_FUSED_U, class LG = WaveLanes,
-          bool PAIRS32 = false, typename Num = double>
+          bool PAIRS32 = false, typename Num = double, class Plan = PlanDynamic>
 struct DevBackend {
   static constexpr int DL = LG::dl(D);
   static constexpr int kSlotsN = NS;  // FLAT slots of a Vec
@@ -288,6 +289,7 @@ struct DevBackend {
   __device__ __forceinline__ void note_eval(int nfev, int iter, double stp, double f, const Vec &x, const Vec &g) {
     // (trace_cap is 0 when neither buffer was given: ONE scalar test in the product path -- the two pointers tested
     //  here were four spilled scalar registers re-read at every evaluation)
+    if constexpr (!Plan::dynamic && !Plan::trace) return;  // (a plan without trace buffers: no hook at all)
     if (nfev > trace_cap) return;
     if (trace != nullptr && lane_id() == 0) {
       double *r = trace + (size_t)(nfev - 1) * 4;
@@ -346,7 +348,7 @@ struct DevBackend {
     NEO_MARK("scatter_done");
     Num *xn = reinterpret_cast<Num *>(xs);
     double energy, tsum;
-    const int st = minco_forward<D, LG, Num, kPcr>(t, prm, energy, tsum);
+    const int st = minco_forward<D, LG, Num, kPcr, Plan>(t, prm, energy, tsum);
     NEO_MARK("forward_done");
     if (st != 0) {
       f = 0.0;
@@ -354,7 +356,7 @@ struct DevBackend {
       for (int k = 0; k < 4; ++k) costs[k] = 0.0;
       return st;
     }
-    if (coeff_out != nullptr && p < t.M) {
+    if (plan_pick<Plan, Plan::coeff_out>(coeff_out != nullptr) && p < t.M) {
 #pragma unroll
       for (int k = 0; k < 6; ++k)
 #pragma unroll
@@ -378,7 +380,8 @@ struct DevBackend {
       SampleLanes sl;
       bool cached = false;
       const int ns_key = lane < t.M ? ns_by_piece : 0;  // (what balanced_sample_lanes sees of this lane)
-      if (sl_cache != nullptr) cached = __ballot(ns_key == (int)reinterpret_cast<const unsigned char *>(sl_cache)[lane]) == ~0ull;
+      const bool have_cache = plan_pick<Plan, Plan::sl_cache>(sl_cache != nullptr);
+      if (have_cache) cached = __ballot(ns_key == (int)reinterpret_cast<const unsigned char *>(sl_cache)[lane]) == ~0ull;
       if (cached) {
         const unsigned pk = (unsigned)sl_cache[kWave / 4 + lane];
         sl.piece = pk & 63;
@@ -392,7 +395,7 @@ struct DevBackend {
         sl.total = __builtin_amdgcn_readfirstlane(sl_cache[kWave / 4 + kWave + 2]);
       } else {
         sl = balanced_sample_lanes(t.M, ns_by_piece, reinterpret_cast<int *>(xs));
-        if (sl_cache != nullptr) {
+        if (have_cache) {
           // one byte a lane for the key (sample counts stay below T_max / delta_t; 255 = never equal), one word for the
           // assignment; a piece with more than 63 lanes (M = 1) does not fit the word's six bits: not cached
           const bool fits = sl.lmax < 64 && ns_key < 255;
@@ -410,8 +413,9 @@ struct DevBackend {
       last_ns = sl.total;  // (the lane assignment has summed the sample counts already)
       samples += (long long)last_ns;
       NEO_MARK("assign_done");
-      minco_sample<Real, D, LookupT, SU, false, LG>(t.M, sl, t.ns, cr, prm, lk, gCr, gTr, cf, ck,
-                                                    fold_rows ? reinterpret_cast<Real *>(xs) : nullptr, fold_acc);
+      minco_sample<Real, D, LookupT, SU, false, LG, Plan>(
+          t.M, sl, t.ns, cr, prm, lk, gCr, gTr, cf, ck,
+          plan_pick<Plan, Plan::fold_rows>(fold_rows) ? reinterpret_cast<Real *>(xs) : nullptr, fold_acc);
 #pragma unroll
       for (int k = 0; k < 6; ++k)
 #pragma unroll
@@ -426,7 +430,7 @@ struct DevBackend {
     Num gq[DL], gtau;
     NEO_MARK("sample_done");
     t.M = opaque_uniform(M_all);
-    const int bst = minco_backward<D, LG, Num, kPcr>(t, prm, gC, gT, gq, gtau);
+    const int bst = minco_backward<D, LG, Num, kPcr, Plan>(t, prm, gC, gT, gq, gtau);
     NEO_MARK("backward_done");
     if (bst != 0) return bst;
     // PIECE -> FLAT (addresses formed here, as in scatter_x)
@@ -609,22 +613,18 @@ __global__ __launch_bounds__(kWave) void eval_kernel(int B, int M, DevParams prm
 // BUDGET (neo_optimize_batch_budget_dev; instantiated in neo_disp_opt3d_b.hip only): a run that has not terminated after
 // `budget` evaluations in this launch is suspended -- its state to `state`, status NEO_TRAJ_SUSPENDED -- and a launch
 // with `resume` set continues the suspended runs of its trajectories (the others it leaves untouched).
-template <int D, int NS, typename Real, class MapT, class LookupT, int WAVES, class LG = WaveLanes, typename Num = double,
-          bool BUDGET = false>
-__global__ __launch_bounds__(kWave, (WAVES == 2 ? (sizeof(Num) == 4 && NS <= 2 ? NEO_X_OCC : NEO_W2_OCC) : 1)) void optimize_kernel(int B, int M, DevParams prm, const MapT *maps,
-                                                          const int *__restrict__ scene_slot, int nmaps,
-                                                          const double *x0, double *x,
-                                                          const double *__restrict__ head,
-                                                          const double *__restrict__ tail,
-                                                          double *__restrict__ costs4,
-                                                          double *__restrict__ costs4_last,
-                                                          int *__restrict__ nit, int *__restrict__ nfev,
-                                                          int *__restrict__ status,
-                                                          long long *__restrict__ nsamples,
-                                                          const int *__restrict__ order, double *__restrict__ trace,
-                                                          double *__restrict__ trace_xg, int trace_cap, int stage, int pcr_off,
-                                                          double *state, int state_doubles, int budget, int resume,
-                                                          int traj_total) {
+// The kernel is compiled once per launch plan (neo_device.hpp PlanDynamic / PlanFixedX): optimize_body is the whole run,
+// optimize_kernel and optimize_dyn_kernel below are its two wrappers.
+template <class Plan, int D, int NS, typename Real, class MapT, class LookupT, int WAVES, class LG, typename Num, bool BUDGET>
+__device__ __forceinline__ void optimize_body(int B, int M, const DevParams &prm, const MapT *maps,
+                                              const int *__restrict__ scene_slot, int nmaps, const double *x0, double *x,
+                                              const double *__restrict__ head, const double *__restrict__ tail,
+                                              double *__restrict__ costs4, double *__restrict__ costs4_last,
+                                              int *__restrict__ nit, int *__restrict__ nfev, int *__restrict__ status,
+                                              long long *__restrict__ nsamples, const int *__restrict__ order,
+                                              double *__restrict__ trace, double *__restrict__ trace_xg, int trace_cap, int stage,
+                                              int pcr_off, double *state, int state_doubles, int budget, int resume,
+                                              int traj_total) {
   extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
   __shared__ LineSearchT<opt_scalar_t<Num, NS>> lsm;
   __shared__ double cst[12];
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(kWave, (WAVES == 2 ? (sizeof(Num) == 4 && NS <= 2 ?
   // the two-waves variant has half the registers: two samples per lane in flight instead of four (with the lean
   // Horner form, cfg2 with three batches in flight: 414 k -> 541 k traj/s; scratch 640 -> 336 B per lane)
   using BE = DevBackend<D, NS, Real, MapT, LookupT, (WAVES == 2 ? NEO_W2_U : NEO_FUSED_U), LG,
-                        pairs_in_f32<Real, NS, WAVES>() || sizeof(Num) == 4, Num>;
+                        pairs_in_f32<Real, NS, WAVES>() || sizeof(Num) == 4, Num, Plan>;
   // a slot outside the table (a stale or foreign slot array): the trajectory is left untouched and flagged
   const int slot = scene_slot ? scene_slot[b] : 0;
   if (slot < 0 || slot >= nmaps) {
@@ -661,14 +661,15 @@ __global__ __launch_bounds__(kWave, (WAVES == 2 ? (sizeof(Num) == 4 && NS <= 2 ?
   // pcr_off != 0 (all-fp32 mode, lane = (piece, dimension), launch_opt): the multipliers of the forward cyclic reduction
   // live at dyn_lds + pcr_off (doubles) for the adjoint pass, and the staging holds per-piece accumulators for the fold
   if constexpr (sizeof(Num) == 4 && LG::S > 1) {
-    if (pcr_off != 0) {
+    if (plan_pick<Plan, Plan::pcr_mult>(pcr_off != 0)) {
       be.t.pcr_mult = reinterpret_cast<Num *>(dyn_lds + pcr_off);
       be.fold_rows = true;
       be.fold_acc = true;
     }
   }
   if constexpr (sizeof(Num) == 4 && LG::W == kWave)   // (the staging doubles as the cyclic reduction's exchange table)
-    if (be.fold_rows && pcr_xch_elems(M, LG::dl(D)) * (int)sizeof(Num) <= stage * 8) be.t.pcr_xch = reinterpret_cast<Num *>(dyn_lds);
+    if (plan_pick<Plan, Plan::pcr_xch>(be.fold_rows && pcr_xch_elems(M, LG::dl(D)) * (int)sizeof(Num) <= stage * 8))
+      be.t.pcr_xch = reinterpret_cast<Num *>(dyn_lds);
   be.lsp = &lsm;
   be.cst = cst;
   be.m = NEO_LBFGS_M;
@@ -677,9 +678,11 @@ __global__ __launch_bounds__(kWave, (WAVES == 2 ? (sizeof(Num) == 4 && NS <= 2 ?
     if (lane_id() < kWave / 4) slc[lane_id()] = -1;  // (key bytes 255: the first evaluation misses)
     be.sl_cache = slc;
   }
-  be.trace = trace ? trace + (size_t)b * trace_cap * 4 : nullptr;
-  be.trace_cap = (trace != nullptr || trace_xg != nullptr) ? trace_cap : 0;
-  be.trace_xg = trace_xg ? trace_xg + (size_t)b * trace_cap * 2 * (D * (M - 1) + M) : nullptr;
+  if constexpr (Plan::dynamic || Plan::trace) {
+    be.trace = trace ? trace + (size_t)b * trace_cap * 4 : nullptr;
+    be.trace_cap = (trace != nullptr || trace_xg != nullptr) ? trace_cap : 0;
+    be.trace_xg = trace_xg ? trace_xg + (size_t)b * trace_cap * 2 * (D * (M - 1) + M) : nullptr;
+  }
   load_boundary<LG>(be.t, head + (size_t)b * 3 * D, tail + (size_t)b * 3 * D, M, bnd);
   const int n = be.t.n;
   be.npad = NS * kWave;
@@ -763,6 +766,65 @@ __global__ __launch_bounds__(kWave, (WAVES == 2 ? (sizeof(Num) == 4 && NS <= 2 ?
       __hip_atomic_fetch_add(reinterpret_cast<int *>(state), 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
+
+// The plan optimize_kernel<...> is compiled for.  The all-fp32 kernels with lane = (piece, dimension) and n <= 128
+// variables (cfg2's member among them) always get PlanFixedX from opt_lds_plan unless flags bit 4096 is set: their
+// optimize_kernel holds that plan alone, and launch_opt_kernel (neo_launch_opt.hpp) sends every other launch -- comparison
+// runs, trace buffers, a plan that is not the fixed one -- to optimize_dyn_kernel.  Every other member, the budgeted ones
+// included, has the dynamic plan in optimize_kernel itself.
+template <int NS, class LG, typename Num, bool BUDGET>
+using opt_plan_t = std::conditional_t<sizeof(Num) == 4 && (LG::S > 1) && NS <= 2 && !BUDGET, PlanFixedX, PlanDynamic>;
+
+#define NEO_OPT_LAUNCH_BOUNDS __launch_bounds__(kWave, (WAVES == 2 ? (sizeof(Num) == 4 && NS <= 2 ? NEO_X_OCC : NEO_W2_OCC) : 1))
+
+// the product kernel.  (One argument list for every plan: under a fixed plan the trace arguments are never read -- the
+// launcher passes them to optimize_dyn_kernel instead -- and an argument nobody reads is not loaded from the segment.)
+template <int D, int NS, typename Real, class MapT, class LookupT, int WAVES, class LG = WaveLanes, typename Num = double,
+          bool BUDGET = false>
+__global__ NEO_OPT_LAUNCH_BOUNDS void optimize_kernel(int B, int M, DevParams prm, const MapT *maps,
+                                                          const int *__restrict__ scene_slot, int nmaps,
+                                                          const double *x0, double *x,
+                                                          const double *__restrict__ head,
+                                                          const double *__restrict__ tail,
+                                                          double *__restrict__ costs4,
+                                                          double *__restrict__ costs4_last,
+                                                          int *__restrict__ nit, int *__restrict__ nfev,
+                                                          int *__restrict__ status,
+                                                          long long *__restrict__ nsamples,
+                                                          const int *__restrict__ order, double *__restrict__ trace,
+                                                          double *__restrict__ trace_xg, int trace_cap,
+                                                          int stage, int pcr_off,
+                                                          double *state, int state_doubles, int budget, int resume,
+                                                          int traj_total) {
+  optimize_body<opt_plan_t<NS, LG, Num, BUDGET>, D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>(
+      B, M, prm, maps, scene_slot, nmaps, x0, x, head, tail, costs4, costs4_last, nit, nfev, status, nsamples, order, trace,
+      trace_xg, trace_cap, stage, pcr_off, state, state_doubles, budget, resume, traj_total);
+}
+
+// the same run with every selector of the plan a run-time value: comparison runs (flags bit 4096), launches with a trace
+// buffer, and any launch whose plan is not the one optimize_kernel was compiled for.  Same arithmetic, same bits.
+template <int D, int NS, typename Real, class MapT, class LookupT, int WAVES, class LG = WaveLanes, typename Num = double,
+          bool BUDGET = false>
+__global__ NEO_OPT_LAUNCH_BOUNDS void optimize_dyn_kernel(int B, int M, DevParams prm, const MapT *maps,
+                                                              const int *__restrict__ scene_slot, int nmaps,
+                                                              const double *x0, double *x,
+                                                              const double *__restrict__ head,
+                                                              const double *__restrict__ tail,
+                                                              double *__restrict__ costs4,
+                                                              double *__restrict__ costs4_last,
+                                                              int *__restrict__ nit, int *__restrict__ nfev,
+                                                              int *__restrict__ status,
+                                                              long long *__restrict__ nsamples,
+                                                              const int *__restrict__ order, double *__restrict__ trace,
+                                                              double *__restrict__ trace_xg, int trace_cap,
+                                                              int stage, int pcr_off,
+                                                              double *state, int state_doubles, int budget, int resume,
+                                                              int traj_total) {
+  optimize_body<PlanDynamic, D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>(
+      B, M, prm, maps, scene_slot, nmaps, x0, x, head, tail, costs4, costs4_last, nit, nfev, status, nsamples, order, trace,
+      trace_xg, trace_cap, stage, pcr_off, state, state_doubles, budget, resume, traj_total);
+}
+#undef NEO_OPT_LAUNCH_BOUNDS
 
 // add_sampled_cost + add_sampled_grad_CT (expert_planner.py:392-466) as a kernel of its own: the ESDF
 // lookup kernel.  Input: polynomial coefficients and durations; output: the two sampled cost terms and

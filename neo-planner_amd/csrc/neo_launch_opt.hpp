@@ -53,7 +53,20 @@ int launch_opt_kernel(neo_ctx *c, const OptArgs &a) {
   const int n_launch = a.subset ? a.n_subset : a.B;
   const int *launch_order = a.subset ? a.subset : (c->order_B == a.B ? c->dispatch_order : nullptr);
   const OptLds l = opt_lds_plan<D, NS, Real, WAVES, LG, Num>(a.M, c->params.flags);
-  hipLaunchKernelGGL((optimize_kernel<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>), dim3(n_launch), dim3(kWave), l.dyn,
+  // optimize_kernel is compiled for ONE plan (neo_kernels.hpp opt_plan_t).  Where that is a fixed plan, it runs only the
+  // launches whose plan -- decided here, on the host -- is that one: accumulator fold and multipliers in LDS (pcr_off), the
+  // exchange table within the staging buffer, no trace buffer.  Everything else (flags bit 4096, traces, an M whose
+  // multipliers do not fit) goes to optimize_dyn_kernel, which tests the selectors at run time.  The kernel checks nothing.
+  using Plan = opt_plan_t<NS, LG, Num, BUDGET>;
+  bool fixed = !Plan::dynamic;
+  if constexpr (!Plan::dynamic)
+    fixed = l.pcr_off != 0 && pcr_xch_elems(a.M, LG::dl(D)) * (int)sizeof(Num) <= l.stage * 8 && !c->trace && !c->trace_xg &&
+            !(c->params.flags & 4096);
+  auto kernel = optimize_kernel<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>;
+  if constexpr (!Plan::dynamic)  // (only the members with a fixed plan have the second form)
+    if (!fixed) kernel = optimize_dyn_kernel<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>;
+  ++c->opt_plan_launches[fixed ? 0 : 1];
+  hipLaunchKernelGGL(kernel, dim3(n_launch), dim3(kWave), l.dyn,
                      c->stream, n_launch, a.M, c->dev, static_cast<const MapT *>(a.table), a.slots, a.nmaps,
                      a.x0 ? a.x0 : a.x, a.x, a.head, a.tail, a.costs4, a.costs4_last, a.nit, a.nfev, a.status,
                      c->sample_counter, launch_order, c->trace, c->trace_xg, c->trace_cap, l.stage, l.pcr_off,

@@ -55,6 +55,7 @@ EXPORTS = [
     "neo_plan_merge", "neo_plan_merge_dev", "neo_depth_render_batch", "neo_depth_render_batch_dev",
     "neo_depth_box_test_counter", "neo_onboard_integrate_batch", "neo_onboard_integrate_batch_dev",
     "neo_esdf_build_2d_batch_dev", "neo_fleet_pose_dev", "neo_record_state_dev", "neo_record_commit_dev",
+    "neo_optimize_plan_launches",
 ]
 
 
@@ -149,6 +150,7 @@ def load():
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]
+    L.neo_optimize_plan_launches.argtypes = [c_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.neo_optimize_sample_counter.argtypes = [c_p, c_p]
     L.neo_optimize_trace.argtypes = [c_p, c_p, c_i]
     L.neo_optimize_trace_xg.argtypes = [c_p, c_p, c_i]
