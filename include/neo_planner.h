@@ -525,6 +525,45 @@ int neo_record_commit_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subs
                           double *wpts_local, double *tau, double *pose_rows, int32_t *meta, uint8_t *images,
                           int32_t *row_of, int32_t *n_rows, int32_t *dropped);
 
+/* ---- the learned warm start on resident arrays (traj_planner/neo_planner.py:10-51) ----------------------------
+ * What NeoPlanner.enhanced_traj_plan does between the depth image's 24 features and the optimiser, for B requests:
+ *   motion (form_nn_input's vector) -> head (PlannerNet's dense layers) -> guess (the first guess neo_plan_guess_dev
+ *   takes as x_init).
+ * The image backbone is not part of it: its features come in as an array.  Device pointers only, asynchronous on the
+ * context's stream, one launch each.  Every array is indexed by REQUEST; `subset` (n_subset request indices, a device
+ * array) names the requests launched, NULL = all B; an index outside 0 .. B - 1 is skipped and its rows stay.  A
+ * request's results depend on neither B, the subset nor its position.  M = 3 pieces, D = 2.
+ * NEO_ERR_INVALID before any launch, with a neo_last_error message: B < 1, a bad subset size, a NULL buffer,
+ * n_weights != NEO_INIT_HEAD_FLOATS, feature_rows not 1 or B. */
+#define NEO_INIT_MOTION 24  /* form_nn_input's vector */
+#define NEO_INIT_FEATURE 24 /* features of an image, and of the motion branch */
+#define NEO_INIT_OUTPUT 9   /* 2 body-frame waypoints (x, y, z) and 3 durations */
+#define NEO_INIT_X 7        /* x0 of a request: D (M - 1) + M */
+/* floats of the weight blob: the eight Linear layers of PlannerNet.head in forward order -- the motion branch
+ * 24 -> 48 -> 24 -> 24 -> 24, then the fusion MLP 48 -> 48 -> 96 -> 96 -> 9 -- each as W row-major [out][in], then
+ * b[out] */
+#define NEO_INIT_HEAD_FLOATS 20817
+/* One lane per request: motion[B][24] = the 24 doubles neo_record_commit_dev writes into a row's motion, from the same
+ * pose[B][5], cur_vel[B][2] (neo_record_state_dev), head[B][3][2] and tail[B][3][2] with the same fp64 operations, each
+ * then converted to fp32 once: the network is fed in flight the bits it was trained on. */
+int neo_init_motion_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const double *pose,
+                        const double *cur_vel, const double *head, const double *tail, float *motion);
+/* PlannerNet.head: out[B][9] = mlp([feature, motion_backbone(motion)]), LeakyReLU (v > 0 ? v : 0.01f v) after every
+ * layer but the last of each stack.  feature[feature_rows][24]: one row per request (feature_rows = B) or one shared
+ * row (feature_rows = 1).  fp32; a lane computes a whole dot product as acc = b[j], then for k ascending
+ * acc = acc + W[j][k] * a[k], product and sum rounded on their own: the result is reproducible bit for bit on the
+ * host.  A workgroup of 256 lanes per 32 requests, weights and activations in LDS. */
+int neo_init_head_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const float *weights, size_t n_weights,
+                      const float *feature, int feature_rows, const float *motion, float *out);
+/* One lane per request: x0[B][7] = [x_0, x_1, y_0, y_1, tau_0, tau_1, tau_2] from out[B][9] and pose[B][5].  With
+ * (lx, ly) the doubles of out[3 i], out[3 i + 1] (the body-frame z is dropped): x_i = (c lx - s ly) + px,
+ * y_i = (s lx + c ly) + py.  Duration t = (double) out[6 + j] is clamped to [T_min + e, T_max - e],
+ * e = 1e-3 (T_max - T_min), T_min and T_max the context's parameters (a NaN stays a NaN), and
+ * tau_j = -log((T_max - T_min) / (t - T_min) - 1) (map_T2tau).  The waypoints are NumPy's bits; tau is the device's
+ * fp64 log of the same argument. */
+int neo_init_guess_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const float *out, const double *pose,
+                       double *x0);
+
 /* ---- the `batch` planner mode on resident arrays (traj_planner/expert_planner.py:103-168) ----------------
  * MinJerkPlanner.batch_plan optimises K laterally shifted initial guesses of one request and keeps the cheapest
  * feasible one.  These two calls are what surrounds the optimiser launch for P requests at once, 2-D (D = 2), fp64:

@@ -1634,6 +1634,47 @@ int neo_record_commit_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset
                                                              pose_rows, meta, images, row_of, n_rows, dropped}));
 }
 
+// ---- the learned warm start on resident arrays (traj_planner/neo_planner.py:10-51; kernels: neo_init.hpp)
+int neo_init_motion_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *pose, const double *cur_vel,
+                        const double *head, const double *tail, float *motion) {
+  int rc = list_check(c, "init motion", B, 1, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  if (!pose || !cur_vel || !head || !tail || !motion) return fail_locked(c, NEO_ERR_INVALID, "init motion: null buffer");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, init_motion(c, list, pose, cur_vel, head, tail, motion));
+}
+
+int neo_init_head_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const float *weights, size_t n_weights,
+                      const float *feature, int feature_rows, const float *motion, float *out) {
+  int rc = list_check(c, "init head", B, 1, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  if (!weights || !feature || !motion || !out) return fail_locked(c, NEO_ERR_INVALID, "init head: null buffer");
+  if (n_weights != (size_t)NEO_INIT_HEAD_FLOATS)
+    return fail_locked(c, NEO_ERR_INVALID, "init head: n_weights must be NEO_INIT_HEAD_FLOATS (20817)");
+  if (feature_rows != 1 && feature_rows != B)
+    return fail_locked(c, NEO_ERR_INVALID, "init head: feature_rows must be 1 or B");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, init_head(c, list, weights, feature, feature_rows, motion, out));
+}
+
+int neo_init_guess_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const float *out, const double *pose,
+                       double *x0) {
+  int rc = list_check(c, "init guess", B, 1, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  if (!out || !pose || !x0) return fail_locked(c, NEO_ERR_INVALID, "init guess: null buffer");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, init_guess(c, list, out, pose, x0));
+}
+
 // ---- the `batch` planner mode on resident arrays (traj_planner/expert_planner.py:103-168; kernels: neo_batch.hpp)
 static const double kBatchOffset = 0.6;  // :135
 static int batch_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M, int D, int K) {

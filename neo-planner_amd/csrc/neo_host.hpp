@@ -266,6 +266,14 @@ int record_state(neo_ctx *c, const LaunchList &l, const double *cmd, int cap, co
                  const double *head, double *cur_vel);
 int record_commit(neo_ctx *c, const LaunchList &l, const RecordCommitArgs &a);  // rank, then commit
 
+// neo_init_*_dev: the learned warm start on resident arrays (neo_disp_init.hip, kernels in neo_init.hpp): one launch
+// each.  Every pointer is a device array indexed by request; the arguments were checked by the C ABI.
+int init_motion(neo_ctx *c, const LaunchList &l, const double *pose, const double *cur_vel, const double *head,
+                const double *tail, float *motion);
+int init_head(neo_ctx *c, const LaunchList &l, const float *weights, const float *feature, int feature_rows,
+              const float *motion, float *out);
+int init_guess(neo_ctx *c, const LaunchList &l, const float *out, const double *pose, double *x0);  // T_min, T_max: the context's
+
 // neo_batch_*_dev: the `batch` planner mode on resident arrays (neo_disp_batch.hip, kernels in neo_batch.hpp).  P =
 // the list's n requests; tau, off and w are HOST arrays (M, K and 4 values), handed to the kernels by value.
 struct BatchCandArgs {

@@ -6,9 +6,10 @@
 //   record_rank_kernel     the dataset rows of the launched missions that solved        one workgroup
 //   record_commit_kernel   one dataset row: motion, waypoints, tau, pose, meta, image   one workgroup per mission
 //
-// Included by neo_disp_record.hip only.  D = 2, fp64, every operation rounded on its own (contraction off): NumPy gives
-// the same bits (tests/record_oracle_np.py).  No atomics: the row of a mission follows from its position in the launch
-// and the counters alone.  Mission-indexed arrays are indexed by mission b; workgroup / lane k works on the mission at
+// Included by neo_disp_record.hip and, for record_to_body and the sizes of a row, by neo_init.hpp, which defines
+// NEO_RECORD_HELPERS_ONLY first: its unit then gets no copy of the kernels.  D = 2, fp64, every operation rounded on its
+// own (contraction off): NumPy gives the same bits (tests/record_oracle_np.py).  No atomics: the row of a mission
+// follows from its position in the launch and the counters alone.  Mission-indexed arrays are indexed by mission b; workgroup / lane k works on the mission at
 // position k of the launch list (neo_launch_list.hpp).
 #pragma once
 #include "neo_device.hpp"
@@ -23,6 +24,7 @@ constexpr int kRecordRow = 3 * kRecordD;  // doubles of a command row / a head o
 constexpr int kRecordMotion = 24;         // form_nn_input's vector
 constexpr int kRecordUnroll = 4;          // 16-byte pieces a lane has in flight in the image copy (written out below)
 
+#ifndef NEO_RECORD_HELPERS_ONLY
 // drone_state.global_vel at the time of the plan: the velocity of the command row being flown, or, before the first
 // plan, of the plan's initial state (traj_planner_node.py first_plan: drone_state is plan_init_state).
 __global__ __launch_bounds__(kRecordThreads) void record_state_kernel(
@@ -75,6 +77,8 @@ __global__ __launch_bounds__(kRecordRankThreads) void record_rank_kernel(
     *dropped += total - given;
   }
 }
+
+#endif  // NEO_RECORD_HELPERS_ONLY
 
 // R^T v for R = [[c, -s, 0], [s, c, 0], [0, 0, 1]]: (c vx + s vy, -s vx + c vy, vz), every product rounded on its own
 __device__ __forceinline__ void record_to_body(double c, double s, double vx, double vy, double vz, double *o) {
@@ -141,6 +145,7 @@ __device__ __forceinline__ void record_copy_bytes(const unsigned char *__restric
   if (tail0 + (size_t)tid < n) dst[tail0 + tid] = src[tail0 + tid];  // fewer than 16 bytes
 }
 
+#ifndef NEO_RECORD_HELPERS_ONLY
 struct RecordData {  // the dataset: `capacity` rows each
   double *motion;         // [capacity][24]
   double *wpts_local;     // [capacity][3 (M - 1)]
@@ -191,5 +196,6 @@ __global__ __launch_bounds__(kRecordThreads) void record_commit_kernel(
   }
   record_copy_bytes(staging + (size_t)b * hw, d.images + (size_t)row * hw, hw, tid);
 }
+#endif  // NEO_RECORD_HELPERS_ONLY
 
 }  // namespace neo

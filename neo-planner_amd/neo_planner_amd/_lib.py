@@ -33,6 +33,8 @@ NEO_FLEET_FLAG_TARGET_CAPPED, NEO_FLEET_FLAG_CMD_FULL, NEO_FLEET_FLAG_BAD_SCENE,
 NEO_FLEET_FLAG_ABANDONED = 16
 NEO_BATCH_MAX_CANDIDATES = 8       # neo_batch_*: candidates a request
 NEO_DEPTH_MAX_BOXES = 1024         # neo_depth_*: boxes a scene
+# neo_init_*: sizes of the motion vector, a feature row, the network's output, x0, and the head's weight blob
+NEO_INIT_MOTION, NEO_INIT_FEATURE, NEO_INIT_OUTPUT, NEO_INIT_X, NEO_INIT_HEAD_FLOATS = 24, 24, 9, 7, 20817
 
 # every symbol include/neo_planner.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -55,7 +57,7 @@ EXPORTS = [
     "neo_plan_merge", "neo_plan_merge_dev", "neo_depth_render_batch", "neo_depth_render_batch_dev",
     "neo_depth_box_test_counter", "neo_onboard_integrate_batch", "neo_onboard_integrate_batch_dev",
     "neo_esdf_build_2d_batch_dev", "neo_fleet_pose_dev", "neo_record_state_dev", "neo_record_commit_dev",
-    "neo_optimize_plan_launches",
+    "neo_optimize_plan_launches", "neo_init_motion_dev", "neo_init_head_dev", "neo_init_guess_dev",
 ]
 
 
@@ -147,6 +149,9 @@ def load():
     L.neo_fleet_pose_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_d, c_p]
     L.neo_record_state_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p]
     L.neo_record_commit_dev.argtypes = [c_p, c_i, c_p, c_i, c_i] + [c_p] * 7 + [c_i, c_i, c_p, c_i, c_i, c_i] + [c_p] * 9
+    L.neo_init_motion_dev.argtypes = [c_p, c_i, c_p, c_i] + [c_p] * 5
+    L.neo_init_head_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, ctypes.c_size_t, c_p, c_i, c_p, c_p]
+    L.neo_init_guess_dev.argtypes = [c_p, c_i, c_p, c_i] + [c_p] * 3
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]

@@ -33,6 +33,14 @@ per-mission buffers, and every target round, just before the splice, one neo_rec
 mission whose plan solved.  The flights are the same with and without it, and no host read is added: the rows and
 their counters stay on the device until the recorder is asked.
 
+Modes "neo" and "nn" fly on the learned warm start (the reference's `selected_planner:=neo` and `:=nn`,
+traj_planner/neo_planner.py, nn_planner.py) with neo=BatchNeoPlanner: once a tick, before the targets, the active
+missions' poses, their velocities now (neo_record_state_dev into the loop's own buffer) and the backbone's features of
+what their cameras see go into resident arrays; every target round BatchNeoPlanner.warm_start_dev turns the pending
+missions' pose, velocity, look-ahead state, target and features into the resident first guess (three launches on the
+context's stream, csrc/neo_init.hpp).  "neo" hands it to plan_dev as attempt 0's start; "nn" splices it as it is, without
+an optimiser launch.  Both imply resident plans and work with onboard and record.
+
 A mission's flight does not depend on which other missions share the fleet: the kernels work per mission, the target
 jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
 retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream_ids`).
@@ -80,14 +88,33 @@ class FleetReplanLoop:
     round, ascending mission); works with every mode, resident or not, with or without onboard, and needs scenes /
     scene_index as onboard does (the recorder's camera looks at the same scenes).  run() appends to what the recorder
     holds: recorder.reset() starts over.  With onboard set as well the images are rendered twice a tick, once by the
-    mapper (float32 metres) and once for the recorder (uint8), from the same poses."""
+    mapper (float32 metres) and once for the recorder (uint8), from the same poses.
+    mode "neo" / "nn" with neo: a BatchNeoPlanner built on this batch_planner (init_wpts_num = 2) -- plan_dev from the
+    network's guess, or the guess flown as it is; scenes / scene_index as for onboard; resident plans always.  The
+    network's camera renders its own images (a third render with onboard and record set).  `x` is a host copy of the
+    resident plan array."""
 
     def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
                  longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
                  scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False, onboard=None, scenes=None,
-                 scene_index=None, des_pos_z=2.0, record_poses=False, record=None):
-        if mode not in ("basic", "geo", "batch"):
-            raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo' or 'batch'")
+                 scene_index=None, des_pos_z=2.0, record_poses=False, record=None, neo=None):
+        if mode not in ("basic", "geo", "batch", "neo", "nn"):
+            raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo', 'batch', 'neo' or 'nn'")
+        learned = mode in ("neo", "nn")
+        if learned:
+            if neo is None:
+                raise ValueError("FleetReplanLoop: modes 'neo' and 'nn' need neo=BatchNeoPlanner")
+            if neo.bp is not batch_planner:
+                raise ValueError("FleetReplanLoop: neo's planner must be the loop's batch_planner")
+            if int(batch_planner.cfg.init_wpts_num) != 2:
+                raise ValueError("FleetReplanLoop: the network plans M = 3 pieces: modes 'neo' and 'nn' need init_wpts_num = 2")
+            net, cam = neo.init.net, neo.camera
+            if (cam.height, cam.width) != (net.img_height, net.img_width):
+                raise ValueError("FleetReplanLoop: neo's camera renders %d x %d, its network takes %d x %d"
+                                 % (cam.height, cam.width, net.img_height, net.img_width))
+            if scenes is None:
+                raise ValueError("FleetReplanLoop: modes 'neo' and 'nn' need scenes=(boxes, box_begin), what the cameras see")
+            resident = True
         if resident and mode == "geo":
             raise ValueError("FleetReplanLoop: resident=True needs mode 'basic' or 'batch' (geo_plan has no resident form)")
         if onboard is not None and mode == "geo":
@@ -97,6 +124,7 @@ class FleetReplanLoop:
         self.resident = bool(resident)
         self.onboard, self.scenes, self.des_pos_z, self.record_poses = onboard, scenes, float(des_pos_z), bool(record_poses)
         self.record = record
+        self.neo = neo if learned else None
         self.scene_index = None if scene_index is None else np.ascontiguousarray(scene_index, dtype=np.int32).reshape(-1)
         self.bp, self.map, self.mode = batch_planner, map, mode
         self.goals = _lib.as_f64(goals).reshape(-1, 2)
@@ -115,7 +143,8 @@ class FleetReplanLoop:
             raise ValueError("FleetReplanLoop: one mission id and one scene id per goal")
         if onboard is not None and onboard.B != self.B:
             raise ValueError("FleetReplanLoop: the onboard mapper must have one entry per goal")
-        if (onboard is not None or record is not None) and self.scene_index is not None and self.scene_index.shape[0] != self.B:
+        if (onboard is not None or record is not None or learned) and self.scene_index is not None and \
+                self.scene_index.shape[0] != self.B:
             raise ValueError("FleetReplanLoop: scene_index must have one entry per goal")
         if record is not None and record.M != int(batch_planner.cfg.init_wpts_num) + 1:
             raise ValueError("FleetReplanLoop: the recorder's M must be the planner's init_wpts_num + 1")
@@ -195,6 +224,32 @@ class FleetReplanLoop:
             rec.staging.index_copy_(0, idx64, img)
         tm["record_s"] = time.perf_counter() - t0
 
+    def _neo_tick(self, active, tm):
+        """modes "neo" and "nn": the active missions' poses (the ones _sense took, with onboard), their velocities now and
+        the features of what their cameras see into the loop's resident cur_vel and feature arrays"""
+        c, d, p, neo = self.bp.ctx, self._dev, self._p, self.neo
+        t0 = time.perf_counter()
+        sub = self._subset(active)
+        self._sync()
+        if self.onboard is None:
+            c.check(c.lib.neo_fleet_pose_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
+                                             p(d["cmd_index"]), p(d["cur_pos"]), p(d["goal"]), self.des_pos_z, p(d["pose"])))
+        c.check(c.lib.neo_record_state_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
+                                           p(d["cmd_index"]), p(d["head"]), p(d["cur_vel"])))
+        c.synchronize()
+        whole = active.size == self.B
+        idx64 = None if whole else sub.long()
+        pose_k = d["pose"] if whole else d["pose"].index_select(0, idx64).contiguous()
+        sidx = d["scene_index"]
+        sidx_k = sidx if (sidx is None or whole) else sidx.index_select(0, idx64).contiguous()
+        feat = neo.features_dev(d["boxes"], d["box_begin"], pose_k, sidx_k)
+        if whole:
+            d["feature"].copy_(feat)
+        else:
+            d["feature"].index_copy_(0, idx64, feat)
+        self._sync()
+        tm["neo_s"] = time.perf_counter() - t0
+
     def _advance(self, sub):
         c, d, p = self.bp.ctx, self._dev, self._p
         step = int(round(self.replan_period * self.cmd_hz))
@@ -237,7 +292,9 @@ class FleetReplanLoop:
         if self.onboard is not None:
             self.onboard.reset()      # all unknown, and the slots as the map table numbers them now
             self._dev.update(plan_slots=self.onboard.slots)
-        if self.onboard is not None or self.record is not None:      # what the cameras see, and where they look from
+        if self.neo is not None:      # the network's inputs that are not the plan's own: velocity now, image features
+            self._dev.update(cur_vel=f(B, 2), feature=torch.zeros((B, 24), dtype=torch.float32, device=dev))
+        if self.onboard is not None or self.record is not None or self.neo is not None:      # what the cameras see, and where from
             boxes, box_begin = self.scenes
             self._dev.update(pose=f(B, 5),
                              boxes=torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 6)).to(dev),
@@ -258,16 +315,36 @@ class FleetReplanLoop:
             self._sync()
         return self._plan
 
-    def _plan_resident(self, sub, pending, tick, r):
+    def _plan_resident(self, sub, pending, tick, r, x0=None):
         """resident=True, mode "basic": one target round's plans for the missions `pending` (`sub` the same on the device)
-        on the resident head / tail -- plan_dev writes the resident x and solved.  Returns (ok over pending, nit_total,
-        attempts) as the host planner's dict has them."""
-        bufs = self.bp.plan_dev(self.plan_map, self._dev["head"], self._dev["tail"], bufs=self._plan_bufs(), slots=self._dev["plan_slots"],
-                                subset=sub, x=self._dev["x"], solved=self._dev["solved"], seed=plan_seed(self.seed, tick, r),
-                                stream_ids=self.mission_ids)
+        on the resident head / tail -- plan_dev writes the resident x and solved; mode "neo": the same with the network's
+        guess `x0` as attempt 0's start.  Returns (ok over pending, nit_total, attempts) as the host planner's dict has
+        them."""
+        bufs = self.bp.plan_dev(self.plan_map, self._dev["head"], self._dev["tail"], bufs=self._plan_bufs(), x0=x0,
+                                slots=self._dev["plan_slots"], subset=sub, x=self._dev["x"], solved=self._dev["solved"],
+                                seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids)
         idx = sub.long()
         return (self._dev["solved"][idx].cpu().numpy() != 0, bufs["nit_total"][idx].cpu().numpy(),
                 bufs["attempts"][idx].cpu().numpy())
+
+    def _plan_neo(self, sub, pending, tick, r):
+        """mode "neo": the network's guess for the pending missions on the resident pose, velocity, head, tail and
+        features (BatchNeoPlanner.warm_start_dev, on the context's stream), then plan_dev from it"""
+        d = self._dev
+        if "x0" not in d:
+            import torch
+            d["x0"] = torch.zeros_like(d["x"])
+            self._sync()
+        x0 = self.neo.warm_start_dev(d["pose"], d["cur_vel"], d["head"], d["tail"], d["feature"], subset=sub, x0=d["x0"])
+        return self._plan_resident(sub, pending, tick, r, x0=x0)
+
+    def _plan_nn(self, sub, pending, tick, r):
+        """mode "nn" (the reference's selected_planner:=nn): the network's guess straight into the resident x, solved = 1
+        for the round's missions, no optimiser launch"""
+        d = self._dev
+        self.neo.warm_start_dev(d["pose"], d["cur_vel"], d["head"], d["tail"], d["feature"], subset=sub, x0=d["x"])
+        d["solved"].index_fill_(0, sub.long(), 1)      # (torch's stream: the loop waits for it before the splice)
+        return np.ones(pending.size, bool), np.zeros(pending.size, np.int64), np.zeros(pending.size, np.int32)
 
     def _plan_batch(self, sub, pending, tick, r):
         """mode "batch": one target round's plans for the missions `pending` (ascending; `sub` the same on the device) on the
@@ -364,6 +441,8 @@ class FleetReplanLoop:
                 self._up("head", head)
             if self.onboard is not None:
                 self._sense(active, tm)
+            if self.neo is not None:
+                self._neo_tick(active, tm)
             if self.record is not None:
                 self._record_tick(active, tm)
             pending = active
@@ -383,6 +462,10 @@ class FleetReplanLoop:
                 t0 = time.perf_counter()
                 if self.mode == "batch":
                     ok, nit_total, attempts = self._plan_batch(sub, pending, tick, r)
+                elif self.mode == "neo":
+                    ok, nit_total, attempts = self._plan_neo(sub, pending, tick, r)
+                elif self.mode == "nn":
+                    ok, nit_total, attempts = self._plan_nn(sub, pending, tick, r)
                 elif self.resident:
                     ok, nit_total, attempts = self._plan_resident(sub, pending, tick, r)
                 else:
@@ -419,7 +502,8 @@ class FleetReplanLoop:
             stuck = (flags & (_lib.NEO_FLEET_FLAG_CMD_FULL | _lib.NEO_FLEET_FLAG_SPLICE_FAILED)) != 0
             active = active[~(abandoned | landed | stuck)[active]]
             tm["tick_s"] = time.perf_counter() - t_tick
-            tm["host_s"] = tm["tick_s"] - tm["fleet_s"] - tm["plan_s"] - tm.get("sense_s", 0.0) - tm.get("record_s", 0.0)
+            tm["host_s"] = tm["tick_s"] - tm["fleet_s"] - tm["plan_s"] - tm.get("sense_s", 0.0) - tm.get("record_s", 0.0) - \
+                tm.get("neo_s", 0.0)
             self.timings.append(tm)
         return self._finish(replans, failed, iter_num, opt_runs, abandoned, landed)
 
@@ -452,6 +536,15 @@ class FleetReplanLoop:
             out.update(poses=np.stack(self._poses) if self._poses else np.zeros((0, self.B, 5)),
                        sensed=np.stack(self._sensed) if self._sensed else np.zeros((0, self.B), bool))
         return out
+
+    @property
+    def x(self):
+        """a host copy of the resident (B, n) plan array: every mission's last plan (read-only: writing it changes nothing)"""
+        if self._dev is None:
+            raise _lib.NeoError("FleetReplanLoop.x: no flight yet")
+        x = self._dev["x"].cpu().numpy()
+        x.flags.writeable = False
+        return x
 
     def commands(self, i):
         """the command array of mission i (n_cmd, 3, 2) copied to the host"""

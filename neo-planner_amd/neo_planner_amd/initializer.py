@@ -260,6 +260,22 @@ class PlannerNetConv(PlannerNet):
         return self.mlp(torch.cat([img_feature, mf], dim=1).unsqueeze(1))
 
 
+def head_layers(net):
+    """the eight Linear layers of PlannerNet.head in forward order: the motion branch, then the fusion MLP"""
+    return [m for m in list(net.motion_backbone) + list(net.mlp) if isinstance(m, nn.Linear)]
+
+
+def pack_head_weights(net):
+    """the weight blob of neo_init_head_dev (include/neo_planner.h): the eight Linear layers of `net`.head in forward
+    order, each as W row-major [out][in] followed by b[out] -- NEO_INIT_HEAD_FLOATS = 20 817 float32 values in one
+    tensor on `net`'s device.  A plain PlannerNet only: PlannerNetConv's stacks stay on the torch head."""
+    if type(net) is not PlannerNet:
+        raise ValueError("pack_head_weights: a plain PlannerNet (got %s; other networks use the torch head)" % type(net).__name__)
+    with torch.no_grad():
+        blob = torch.cat([t.detach().reshape(-1).to(torch.float32) for l in head_layers(net) for t in (l.weight, l.bias)])
+    return blob.contiguous()
+
+
 def raycast_depth(pillars, canopy=(), eye=(1.5, 0.0, 2.0), yaw=0.0, hfov_deg=87.0, max_range=20.0,
                   height=IMG_HEIGHT, width=IMG_WIDTH):
     """Synthetic depth image of a forest scene ("ray-cast of the pillars, 480 x 640"): a pinhole camera
@@ -408,7 +424,11 @@ class BatchNeoPlanner:
     """NeoPlanner.enhanced_traj_plan (neo_planner.py:10-51) for B requests: every request's own depth image from the
     batched camera (depth.DepthCamera), the motion vectors, the initializer network, and the warm starts into
     BatchPlanner.plan.  batch_planner: a BatchPlanner; initializer: a BatchInitializer; camera: a DepthCamera of the
-    network's image size."""
+    network's image size.
+
+    `warm_start` / `plan` take host arrays.  `warm_start_dev` / `plan_dev` work on RESIDENT torch tensors: the motion
+    vector, the network's dense layers and the first guess are the neo_init_* kernels on the context's stream
+    (csrc/neo_init.hpp), and the guess goes to BatchPlanner.plan_dev as `x0` without passing through the host."""
 
     def __init__(self, batch_planner, initializer, camera, des_pos_z=2.0):
         net = initializer.net
@@ -417,6 +437,8 @@ class BatchNeoPlanner:
                              % (camera.height, camera.width, net.img_height, net.img_width))
         self.bp, self.init, self.camera, self.des_pos_z = batch_planner, initializer, camera, float(des_pos_z)
         self.chunk = 64          # images per render launch and backbone pass
+        self.motion = self.out = self.x0 = None      # what the last warm_start_dev wrote: (B, 24) and (B, 9) float32, (B, 7) float64
+        self._weights = self._own_x0 = None
 
     def warm_start(self, scenes, drone_pos, drone_vel, local_vel, yaw, head, tail, scene_index=None):
         """scenes: the camera's scenes (DepthCamera.pack_scenes), scene_index (B,) the scene each request sees (None:
@@ -449,3 +471,92 @@ class BatchNeoPlanner:
         out = self.bp.plan(map, head, tail, int_wpts=wp, ts=ts, **plan_kw)
         out["int_wpts0"], out["ts0"], out["depth_u8"] = wp, ts, depth_u8
         return out
+
+    # ------------------------------------------------------------ on resident arrays
+    @property
+    def kernel_head(self):
+        """the network's dense layers can run as neo_init_head_dev: a plain PlannerNet"""
+        return type(self.init.net) is PlannerNet
+
+    def head_weights(self, refresh=False):
+        """the network's blob for neo_init_head_dev (pack_head_weights), packed at first use; refresh=True packs it again
+        after the network's parameters changed"""
+        if self._weights is None or refresh:
+            self._weights = pack_head_weights(self.init.net)
+            torch.cuda.synchronize(self._weights.device)
+        return self._weights
+
+    @torch.no_grad()
+    def features_dev(self, boxes, box_begin, pose, scene_index=None):
+        """the image features (n, 24) float32 of what the camera sees from pose (n, 5): DepthCamera.render_dev's uint8
+        images through the backbone, `chunk` images at a time (device tensors in and out; torch's stream has finished
+        when it returns)"""
+        img = self.camera.render_dev(boxes, box_begin, pose, scene_index, chunk=self.chunk, want_m=False)["depth_u8"]
+        feat = self.init.image_features(img, chunk=self.chunk).to(torch.float32).contiguous()
+        torch.cuda.synchronize(feat.device)
+        return feat
+
+    @torch.no_grad()
+    def warm_start_dev(self, pose, cur_vel, head, tail, feature, subset=None, x0=None, head_impl=None):
+        """The network's first guess for the requests `subset` (an int32 device tensor; None: all B) on resident tensors
+        indexed by request: pose (B, 5) float64 (eye x, y, z, cos, sin: neo_fleet_pose_dev / DepthCamera.poses), cur_vel
+        (B, 2), head and tail (B, 3, 2) float64, feature (B, 24) or (1, 24) float32 (one shared image).  Three launches on
+        the context's stream -- neo_init_motion_dev, neo_init_head_dev, neo_init_guess_dev -- into `self.motion` (B, 24)
+        and `self.out` (B, 9) float32 and `x0` (B, 7) float64 (the caller's array, or one kept here), which is returned
+        and stays readable as `self.x0`; rows of requests outside the subset stay as they are.  head_impl "kernel" (the
+        default for a plain PlannerNet) or "torch" (every other network's default): net.head on torch's stream between
+        the motion and the guess kernels, with the waits that takes.  The caller's tensors must be ready (as for
+        plan_dev: torch.cuda.synchronize after torch wrote them); the launches are asynchronous -- ctx.synchronize()
+        before torch reads the results, or plan_dev, which runs on the same stream."""
+        if head_impl is None:
+            head_impl = "kernel" if self.kernel_head else "torch"
+        if head_impl not in ("kernel", "torch"):
+            raise ValueError("BatchNeoPlanner.warm_start_dev: head_impl must be 'kernel' or 'torch'")
+        if head_impl == "kernel" and not self.kernel_head:
+            raise ValueError("BatchNeoPlanner.warm_start_dev: head_impl 'kernel' needs a plain PlannerNet")
+        B, dev = int(pose.shape[0]), pose.device
+        if tuple(pose.shape) != (B, 5) or tuple(cur_vel.shape) != (B, 2) or tuple(head.shape) != (B, 3, 2) or \
+                tuple(tail.shape) != (B, 3, 2) or feature.ndim != 2 or feature.shape[1] != IMG_FEATURE_SIZE or \
+                feature.shape[0] not in (1, B):
+            raise ValueError("BatchNeoPlanner.warm_start_dev: pose (B, 5), cur_vel (B, 2), head and tail (B, 3, 2), "
+                             "feature (B or 1, 24)")
+        if any(t.dtype != torch.float64 or not t.is_contiguous() for t in (pose, cur_vel, head, tail)) or \
+                feature.dtype != torch.float32 or not feature.is_contiguous():
+            raise ValueError("BatchNeoPlanner.warm_start_dev: contiguous tensors, float64 but for the float32 feature")
+        if x0 is not None and (tuple(x0.shape) != (B, 7) or x0.dtype != torch.float64 or not x0.is_contiguous()):
+            raise ValueError("BatchNeoPlanner.warm_start_dev: x0 (B, 7) float64, contiguous")
+        from . import _lib
+        fresh = False
+        if self.motion is None or self.motion.shape[0] != B or self.motion.device != dev:
+            self.motion = torch.zeros((B, MOTION_INPUT_SIZE), dtype=torch.float32, device=dev)
+            self.out = torch.zeros((B, OUTPUT_SIZE), dtype=torch.float32, device=dev)
+            fresh = True
+        if x0 is None:
+            if self._own_x0 is None or self._own_x0.shape[0] != B or self._own_x0.device != dev:
+                self._own_x0 = torch.zeros((B, 7), dtype=torch.float64, device=dev)
+                fresh = True
+            x0 = self._own_x0
+        self.x0 = x0
+        weights = self.head_weights() if head_impl == "kernel" else None
+        if fresh:
+            torch.cuda.synchronize(dev)      # (the context has its own stream: the buffers are ready before it starts)
+        self.bp._sync()                      # the context's T_min / T_max are the planner's
+        c, p = self.bp.ctx, _lib.dev_ptr
+        sub, n_sub = p(subset), (0 if subset is None else int(subset.numel()))
+        c.check(c.lib.neo_init_motion_dev(c.h, B, sub, n_sub, p(pose), p(cur_vel), p(head), p(tail), p(self.motion)))
+        if head_impl == "kernel":
+            c.check(c.lib.neo_init_head_dev(c.h, B, sub, n_sub, p(weights), int(weights.numel()), p(feature),
+                                            int(feature.shape[0]), p(self.motion), p(self.out)))
+        else:
+            c.synchronize()
+            self.out.copy_(self.init.net.head(feature, self.motion).to(torch.float32))
+            torch.cuda.synchronize(dev)
+        c.check(c.lib.neo_init_guess_dev(c.h, B, sub, n_sub, p(self.out), p(pose), p(x0)))
+        return x0
+
+    def plan_dev(self, map, pose, cur_vel, head, tail, feature, subset=None, head_impl=None, **plan_dev_kw):
+        """warm_start_dev, then BatchPlanner.plan_dev(map, head, tail, x0=the guess, subset=subset, **plan_dev_kw): attempt 0
+        starts from the network's guess, the retries from the straight line plus noise as plan_dev draws them (the
+        reference's warm_start_plan after a failed first attempt).  Returns plan_dev's bufs; the guess stays in `self.x0`."""
+        x0 = self.warm_start_dev(pose, cur_vel, head, tail, feature, subset=subset, head_impl=head_impl)
+        return self.bp.plan_dev(map, head, tail, x0=x0, subset=subset, **plan_dev_kw)
