@@ -435,6 +435,19 @@ int neo_fleet_target_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_
                                int n_subset, const double *cur_pos, const double *goal, const double *jitter,
                                double longitu_step_dis, double lateral_step_length, double move_vel, double *tail,
                                int32_t *near_goal, int32_t *lateral_steps, int32_t *flags);
+/* the re-targeting's draws on the device, one lane per mission of the subset: jitter[B][2], the array the target
+ * kernel reads, from the counter stream of mission_ids[b] (int32, mission-indexed [B], ids in 0 .. 2^31 - 1; NULL: b
+ * itself):
+ *   jitter[b][i] = z(seed, id, tick, target, value i),   zeros, without drawing, when target == 0,
+ * z the unit normal of csrc/neo_counter_rng.hpp with the counter (id, tick, target, 2 << 24) (see neo_plan_jitter):
+ * neo_planner_amd.fleet.target_jitter_counter's rows bit for bit.  Missions outside the subset keep their rows (the
+ * host form copies jitter up first).  Errors, before anything is launched: a NULL jitter, B < 0, a bad subset size,
+ * tick or target < 0: NEO_ERR_INVALID. */
+int neo_fleet_jitter(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, uint64_t seed, int tick, int target,
+                     const int32_t *mission_ids, double *jitter);
+/* the same with DEVICE pointers, asynchronous on the context's stream */
+int neo_fleet_jitter_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, uint64_t seed, int tick, int target,
+                         const int32_t *mission_ids, double *jitter);
 /* perfect tracking for one replan period, then get_drone_state_ahead (:527-537), one lane per mission:
  *   cmd_index = min(cmd_index + step, cmd_len - 1);  cur_pos[B][2] = position of row cmd_index;
  *   future_index = min(ahead + cmd_index, cmd_len - 1);  head[B][3][2] = position and velocity of row future_index, zero
@@ -668,6 +681,20 @@ int neo_plan_guess_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset,
                        const double *tail, const int32_t *slots, const double *x_init, const double *noise,
                        const double *frac, const double *tau, double *x0, double *head_k, double *tail_k,
                        int32_t *slots_k);
+/* the re-seeded attempts' jitter drawn on the device, one lane per value: the PACKED noise[P][D][M - 1] that guess
+ * adds, without a host draw, a read-back of the list or an upload.  Position p takes the counter stream of
+ * stream_ids[b], b its request (stream_ids: int32, REQUEST-INDEXED [B], ids in 0 .. 2^31 - 1; NULL: b itself):
+ *   noise[p][d][k] = 0.5 * z(seed, id, attempt, value d (M - 1) + k),
+ * z the unit normal of csrc/neo_counter_rng.hpp -- Philox4x32-10 with the key (seed's low word, seed's high word) and
+ * the counter (id, attempt, 0, 1 << 24 | value / 2), a 52-bit uniform from two output words, Wichura's AS241 -- which
+ * neo_planner_amd/counter_rng.py restates in NumPy bit for bit (BatchPlanner.retry_noise_counter).  A value depends on
+ * (seed, id, attempt, d, k) alone: not on B, the subset or the launch.  The rows of a skipped index stay (the host form
+ * copies the P rows up first).  Further errors, before anything is launched: attempt < 0: NEO_ERR_INVALID. */
+int neo_plan_jitter(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, uint64_t seed, int attempt,
+                    const int32_t *stream_ids, double *noise);
+/* the same with DEVICE pointers, asynchronous on the context's stream */
+int neo_plan_jitter_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, uint64_t seed,
+                        int attempt, const int32_t *stream_ids, double *noise);
 /* one attempt's bookkeeping, one wavefront per launched request, from the optimiser's PACKED results x_k [P][n],
  * costs4_k, costs4_last_k [P][4], nit_k, nfev_k, status_k [P].  REQUEST-INDEXED results, written for every launched
  * request (requests not launched keep theirs):

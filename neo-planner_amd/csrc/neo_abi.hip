@@ -1476,6 +1476,45 @@ int neo_fleet_target_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, i
   return st.download();
 }
 
+static int fleet_jitter_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int tick, int target,
+                              const double *jitter) {
+  int rc = list_check(c, "fleet jitter", B, 0, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  if (!jitter) return fail_locked(c, NEO_ERR_INVALID, "fleet jitter: null buffer");
+  if (tick < 0 || target < 0) return fail_locked(c, NEO_ERR_INVALID, "fleet jitter: tick and target must be >= 0");
+  return NEO_OK;
+}
+
+int neo_fleet_jitter_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, uint64_t seed, int tick, int target,
+                         const int32_t *mission_ids, double *jitter) {
+  int rc = fleet_jitter_check(c, B, subset, n_subset, tick, target, jitter);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, fleet_jitter(c, list, seed, tick, target, mission_ids, jitter));
+}
+
+int neo_fleet_jitter(neo_ctx *c, int B, const int32_t *subset, int n_subset, uint64_t seed, int tick, int target,
+                     const int32_t *mission_ids, double *jitter) {
+  int rc = fleet_jitter_check(c, B, subset, n_subset, tick, target, jitter);
+  if (rc) return rc;
+  if (launch_list(B, subset, n_subset).n == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  const size_t bs = (size_t)B;
+  // the rows go up too: missions outside the subset keep theirs
+  HostStage st(c, kStagedUpTo);
+  const auto fi = st.in_optional(mission_ids, bs), fsub = st.in_optional(subset, (size_t)n_subset);
+  const auto fj = st.inout(jitter, bs * 2);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_fleet_jitter_dev(c, B, st.dev(fsub), n_subset, seed, tick, target, st.dev(fi), st.dev(fj));
+  if (rc) return rc;
+  return st.download();
+}
+
 static int fleet_cmd_check(neo_ctx *c, const char *who, const double *cmd, int cap, const int32_t *cmd_len,
                            const int32_t *cmd_index, const int32_t *future_index) {
   if (!cmd || !cmd_len || !cmd_index || !future_index)
@@ -1862,6 +1901,45 @@ int neo_plan_guess(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M
   if (rc) return rc;
   rc = neo_plan_guess_dev(c, B, st.dev(fsub), n_subset, M, D, st.dev(fh), st.dev(ft), st.dev(fs), st.dev(fxi), st.dev(fno),
                           frac, tau, st.dev(fx), st.dev(fhk), st.dev(ftk), st.dev(fsk));
+  if (rc) return rc;
+  return st.download();
+}
+
+static int plan_jitter_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int attempt,
+                             const double *noise) {
+  int rc = plan_check(c, "plan jitter", B, subset, n_subset, M, D);
+  if (rc) return rc;
+  if (!noise) return fail_locked(c, NEO_ERR_INVALID, "plan jitter: null buffer");
+  if (attempt < 0) return fail_locked(c, NEO_ERR_INVALID, "plan jitter: attempt must be >= 0");
+  return NEO_OK;
+}
+
+int neo_plan_jitter_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, uint64_t seed, int attempt,
+                        const int32_t *stream_ids, double *noise) {
+  int rc = plan_jitter_check(c, B, subset, n_subset, M, D, attempt, noise);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, plan_jitter(c, list, M, D, seed, attempt, stream_ids, noise));
+}
+
+int neo_plan_jitter(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, uint64_t seed, int attempt,
+                    const int32_t *stream_ids, double *noise) {
+  int rc = plan_jitter_check(c, B, subset, n_subset, M, D, attempt, noise);
+  if (rc) return rc;
+  const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n;
+  if (P == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  // the packed rows go up too: the rows of a skipped index come back as they were
+  HostStage st(c, kStagedUpTo);
+  const auto fi = st.in_optional(stream_ids, bs), fsub = st.in_optional(subset, (size_t)n_subset);
+  const auto fno = st.inout(noise, P * (size_t)D * (M - 1));
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_plan_jitter_dev(c, B, st.dev(fsub), n_subset, M, D, seed, attempt, st.dev(fi), st.dev(fno));
   if (rc) return rc;
   return st.download();
 }

@@ -15,6 +15,13 @@ int fleet_target(neo_ctx *c, const LaunchList &l, const MapRef &m, const FleetTa
   return NEO_OK;
 }
 
+int fleet_jitter(neo_ctx *c, const LaunchList &l, uint64_t seed, int tick, int target, const int *mission_ids,
+                 double *jitter) {
+  hipLaunchKernelGGL(fleet_jitter_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l, (unsigned long long)seed,
+                     tick, target, mission_ids, jitter);
+  return NEO_OK;
+}
+
 int fleet_advance(neo_ctx *c, const LaunchList &l, const FleetCmd &m, int step, int ahead, double *cur_pos, double *head) {
   hipLaunchKernelGGL(fleet_advance_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l, m.cmd, m.cap, m.cmd_len,
                      m.cmd_index, m.future_index, step, ahead, cur_pos, head);

@@ -23,6 +23,15 @@ int plan_guess(neo_ctx *c, const LaunchList &l, int D, const PlanGuessArgs &a) {
   return NEO_OK;
 }
 
+int plan_jitter(neo_ctx *c, const LaunchList &l, int M, int D, uint64_t seed, int attempt, const int *stream_ids,
+                double *noise) {
+  const int per = D * (M - 1);
+  const size_t values = (size_t)l.n * per;
+  hipLaunchKernelGGL(plan_jitter_kernel, dim3((unsigned)((values + kPlanThreads - 1) / kPlanThreads)), dim3(kPlanThreads), 0,
+                     c->stream, l, per, (unsigned long long)seed, attempt, stream_ids, noise);
+  return NEO_OK;
+}
+
 int plan_merge(neo_ctx *c, const LaunchList &l, const PlanMergeArgs &a) {
   hipLaunchKernelGGL(plan_merge_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.n, a.reset, a.packed, a.out, a.attempts,
                      a.nit_total, a.solved, a.failed, a.bad_scene);

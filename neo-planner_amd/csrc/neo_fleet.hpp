@@ -2,6 +2,7 @@
 // ros_node/traj_planner_node.py does per mission between two plans, for B missions whose command arrays stay in HBM.
 //
 //   fleet_target_kernel    set_local_target       (:450-488)   one lane per mission
+//   fleet_jitter_kernel    the re-targeting's N(0, 1) draws (:469) on the device (neo_counter_rng.hpp)   one lane per mission
 //   fleet_advance_kernel   perfect tracking + get_drone_state_ahead (:527-537)   one lane per mission
 //   fleet_pose_kernel      the camera pose a mission senses from (:685-687)          one lane per mission
 //   fleet_splice_kernel    the splice of replan   (:574-578, first_plan :515-519)   one wavefront per mission
@@ -14,6 +15,7 @@
 // read-modify-write.
 #pragma once
 #include "neo_audit.hpp"
+#include "neo_counter_rng.hpp"
 #include "neo_launch_list.hpp"
 
 namespace neo {
@@ -99,6 +101,25 @@ __global__ __launch_bounds__(kFleetThreads) void fleet_target_kernel(
   near_goal[b] = 0;
   lateral_steps[b] = steps;
   if (capped) flags[b] |= NEO_FLEET_FLAG_TARGET_CAPPED;
+}
+
+// jitter[b][0 .. 1] = values 0 and 1 (one block) of the stream (seed, mission_ids[b], tick, target, domain 2):
+// fleet.target_jitter_counter's rows, bit for bit; zeros, without drawing, for the first target of a tick.
+// `mission_ids` is mission-indexed, or NULL: the mission's index.
+__global__ __launch_bounds__(kFleetThreads) void fleet_jitter_kernel(LaunchList list, unsigned long long seed, int tick,
+                                                                     int target, const int *__restrict__ mission_ids,
+                                                                     double *__restrict__ jitter) {
+  const int b = list.request(blockIdx.x * kFleetThreads + threadIdx.x);
+  if (b < 0) return;
+  double z0 = 0.0, z1 = 0.0;
+  if (target != 0) {
+    const uint32_t id = (uint32_t)(mission_ids ? mission_ids[b] : b);
+    const Philox4 o = counter_stream_block(seed, id, (uint32_t)tick, (uint32_t)target, kRngDomainTarget, 0u);
+    z0 = counter_block_normal(o, 0);
+    z1 = counter_block_normal(o, 1);
+  }
+  jitter[(size_t)b * 2] = z0;
+  jitter[(size_t)b * 2 + 1] = z1;
 }
 
 // The camera pose a mission senses from (onboard maps): the eye is where the mission is, at height eye_z; the heading is

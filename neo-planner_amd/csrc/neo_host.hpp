@@ -239,6 +239,9 @@ struct FleetAuditArgs {
   int *count, *flags;
 };
 int fleet_target(neo_ctx *c, const LaunchList &l, const MapRef &m, const FleetTargetArgs &a);
+// jitter [B][2] by mission: the re-targeting draws of (tick, target) from the missions' own counter streams
+int fleet_jitter(neo_ctx *c, const LaunchList &l, uint64_t seed, int tick, int target, const int *mission_ids,
+                 double *jitter);
 int fleet_advance(neo_ctx *c, const LaunchList &l, const FleetCmd &m, int step, int ahead, double *cur_pos, double *head);
 int fleet_splice(neo_ctx *c, const LaunchList &l, const FleetCmd &m, const FleetSpliceArgs &a);
 int fleet_audit(neo_ctx *c, const LaunchList &l, const MapRef &m, const FleetAuditArgs &a);
@@ -323,6 +326,9 @@ struct PlanMergeArgs {
 };
 int plan_guess(neo_ctx *c, const LaunchList &l, int D, const PlanGuessArgs &a);
 int plan_merge(neo_ctx *c, const LaunchList &l, const PlanMergeArgs &a);
+// noise [P][D][M - 1] packed: the retry jitter of attempt `attempt` from the requests' own counter streams
+int plan_jitter(neo_ctx *c, const LaunchList &l, int M, int D, uint64_t seed, int attempt, const int *stream_ids,
+                double *noise);
 
 // neo_geo_search_batch_dev / neo_geo_prune_batch (neo_disp_geo.hip); the context is locked and its tables rebuilt
 struct GeoArgs {

@@ -3,6 +3,8 @@
 //
 //   plan_guess_kernel   generate_init_variables (:82-101): the straight-line guess, with the re-seeded attempts' jitter
 //                       added when the host hands it over, packed for one optimiser launch      one lane per request
+//   plan_jitter_kernel  the re-seeded attempts' jitter drawn on the device (neo_counter_rng.hpp): the packed noise that
+//                       plan_guess_kernel adds, from the request's own stream                     one lane per value
 //   plan_merge_kernel   plan's bookkeeping over the launch's results: scatter to the request-indexed arrays, attempts,
 //                       nit_total, failed / solved, the bad-scene word                     one wavefront per request
 //   (batch_compact_kernel, neo_batch.hpp, then packs the failed requests: the next attempt's launch list)
@@ -10,6 +12,7 @@
 // Included by neo_disp_plan.hip only.  fp64, D = 2 or 3.  Request-indexed arrays are indexed by request b; packed
 // arrays by the request's position p in the launch list (neo_launch_list.hpp).  No atomics, no scratch.
 #pragma once
+#include "neo_counter_rng.hpp"
 #include "neo_device.hpp"
 #include "neo_launch_list.hpp"
 
@@ -61,6 +64,25 @@ __global__ __launch_bounds__(kPlanThreads) void plan_guess_kernel(
     }
   }
   for (int i = 0; i < M; ++i) xr[D * count + i] = tau.v[i];
+}
+
+// noise[p][d][k] = 0.5 * value d * count + k of the stream (seed, stream_ids[b], attempt, 0, domain 1), b the request at
+// position p: BatchPlanner.retry_noise_counter's array for the launch list, bit for bit (the reference's N(0, 0.5), :94).
+// `stream_ids` is request-indexed, or NULL: the request's index.  One lane per value; `per` = D * (M - 1) values a
+// request.  The rows of a skipped position stay.
+__global__ __launch_bounds__(kPlanThreads) void plan_jitter_kernel(LaunchList list, int per, unsigned long long seed,
+                                                                   int attempt, const int *__restrict__ stream_ids,
+                                                                   double *__restrict__ noise) {
+#pragma clang fp contract(off)
+  const size_t v = (size_t)blockIdx.x * kPlanThreads + threadIdx.x;
+  const size_t p = v / (size_t)per;
+  if (p >= (size_t)list.size()) return;
+  const int b = list.request((int)p);
+  if (b < 0) return;
+  const uint32_t e = (uint32_t)(v - p * (size_t)per);
+  const uint32_t id = (uint32_t)(stream_ids ? stream_ids[b] : b);
+  const double z = counter_normal(seed, id, (uint32_t)attempt, 0u, kRngDomainRetry, e);
+  noise[v] = 0.5 * z;
 }
 
 // One attempt's results, packed [P] rows, into the request-indexed arrays, with BatchPlanner.plan's bookkeeping:

@@ -58,6 +58,7 @@ EXPORTS = [
     "neo_depth_box_test_counter", "neo_onboard_integrate_batch", "neo_onboard_integrate_batch_dev",
     "neo_esdf_build_2d_batch_dev", "neo_fleet_pose_dev", "neo_record_state_dev", "neo_record_commit_dev",
     "neo_optimize_plan_launches", "neo_init_motion_dev", "neo_init_head_dev", "neo_init_guess_dev",
+    "neo_plan_jitter", "neo_plan_jitter_dev", "neo_fleet_jitter", "neo_fleet_jitter_dev",
 ]
 
 
@@ -139,6 +140,10 @@ def load():
     L.neo_plan_guess_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i] + [c_p] * 11
     L.neo_plan_merge.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 18
     L.neo_plan_merge_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i] + [c_p] * 18
+    L.neo_plan_jitter.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, ctypes.c_uint64, c_i, c_p, c_p]
+    L.neo_plan_jitter_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, ctypes.c_uint64, c_i, c_p, c_p]
+    L.neo_fleet_jitter.argtypes = [c_p, c_i, c_p, c_i, ctypes.c_uint64, c_i, c_i, c_p, c_p]
+    L.neo_fleet_jitter_dev.argtypes = [c_p, c_i, c_p, c_i, ctypes.c_uint64, c_i, c_i, c_p, c_p]
     L.neo_depth_render_batch.argtypes = [c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_i, c_p, c_i] + [c_p] * 4
     L.neo_depth_render_batch_dev.argtypes = [c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_i, c_p, c_i] + [c_p] * 4
     L.neo_depth_box_test_counter.argtypes = [c_p, c_p]

@@ -21,7 +21,9 @@ SOURCES = ["neo_abi.hip", "neo_disp_eval.hip", "neo_disp_sample.hip", "neo_disp_
            "neo_disp_audit.hip", "neo_disp_geo.hip", "neo_disp_fleet.hip", "neo_disp_batch.hip", "neo_disp_esdf.hip",
            "neo_disp_plan.hip", "neo_disp_depth.hip", "neo_disp_onboard.hip", "neo_disp_record.hip", "neo_disp_init.hip"]
 HEADERS = ["neo_wave.hpp", "neo_device.hpp", "neo_kernels.hpp", "neo_host.hpp", "neo_launch_list.hpp", "neo_launch_opt.hpp", "neo_lbfgs.hpp",
-           "neo_linesearch.hpp", "neo_lbfgs_sm.hpp", "neo_lbfgs_dir.hpp", "neo_group_kernel.hpp"]
+           "neo_linesearch.hpp", "neo_lbfgs_sm.hpp", "neo_lbfgs_dir.hpp", "neo_group_kernel.hpp",
+           # (the counter-based jitter, included by the plan and the fleet unit; small enough to sit with the shared ones)
+           "neo_counter_rng.hpp"]
 STAMP = LIB + ".stamp"    # hash of command lines + sources + headers the library was built from (travels with the library)
 
 

@@ -43,13 +43,16 @@ an optimiser launch.  Both imply resident plans and work with onboard and record
 
 A mission's flight does not depend on which other missions share the fleet: the kernels work per mission, the target
 jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
-retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream_ids`).
+retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream_ids`).  With jitter="counter" both come
+from the counter-based streams of counter_rng.py / csrc/neo_counter_rng.hpp instead -- a value is a pure function of
+(seed, mission id, tick, target) or (plan_seed, mission id, attempt) -- drawn on the device: neo_fleet_jitter_dev in front
+of the target kernel, neo_plan_jitter_dev inside plan_dev.  The property is the same, the flights are other flights.
 """
 import time
 
 import numpy as np
 
-from . import _lib
+from . import _lib, counter_rng
 
 MAX_TARGETS = 11        # :429-445: seed 0 .. 10 are planned, the mission is abandoned after the plan of target 10 fails
 
@@ -62,6 +65,12 @@ def target_jitter(seed, mission_ids, tick, target):
         return np.zeros((ids.shape[0], 2))
     return np.stack([np.random.default_rng([int(seed), int(i), int(tick), int(target)]).normal(0.0, 1.0, 2) for i in ids]) \
         if ids.shape[0] else np.zeros((0, 2))
+
+
+def target_jitter_counter(seed, mission_ids, tick, target):
+    """`target_jitter` from the counter-based streams (counter_rng.py): mission i's two unit normals of (seed, i, tick,
+    target), zeros for target 0 -- the rows neo_fleet_jitter_dev writes, bit for bit"""
+    return counter_rng.target_jitter(seed, mission_ids, tick, target)
 
 
 def plan_seed(seed, tick, target):
@@ -92,12 +101,17 @@ class FleetReplanLoop:
     mode "neo" / "nn" with neo: a BatchNeoPlanner built on this batch_planner (init_wpts_num = 2) -- plan_dev from the
     network's guess, or the guess flown as it is; scenes / scene_index as for onboard; resident plans always.  The
     network's camera renders its own images (a third render with onboard and record set).  `x` is a host copy of the
-    resident plan array."""
+    resident plan array.
+    jitter "numpy" (one NumPy generator per mission and draw, on the host) or "counter" (every mode, resident or not): the
+    target jitter of a round is drawn by neo_fleet_jitter_dev on the context's stream in front of the target kernel, and
+    every plan call gets jitter="counter"; mission ids in 0 .. 2^31 - 1 and a seed in 0 .. 2^64 - 1."""
 
     def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
                  longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
                  scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False, onboard=None, scenes=None,
-                 scene_index=None, des_pos_z=2.0, record_poses=False, record=None, neo=None):
+                 scene_index=None, des_pos_z=2.0, record_poses=False, record=None, neo=None, jitter="numpy"):
+        self.counter = counter_rng.check_jitter(jitter, "FleetReplanLoop")
+        self.jitter = jitter
         if mode not in ("basic", "geo", "batch", "neo", "nn"):
             raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo', 'batch', 'neo' or 'nn'")
         learned = mode in ("neo", "nn")
@@ -141,6 +155,9 @@ class FleetReplanLoop:
         self.mission_ids = np.arange(self.B) if mission_ids is None else np.asarray(mission_ids).reshape(-1)
         if self.mission_ids.shape[0] != self.B or (self.scene_ids is not None and self.scene_ids.shape[0] != self.B):
             raise ValueError("FleetReplanLoop: one mission id and one scene id per goal")
+        if self.counter:
+            counter_rng.check_seed(self.seed, "FleetReplanLoop")
+            counter_rng.check_ids(self.mission_ids, "FleetReplanLoop")
         if onboard is not None and onboard.B != self.B:
             raise ValueError("FleetReplanLoop: the onboard mapper must have one entry per goal")
         if (onboard is not None or record is not None or learned) and self.scene_index is not None and \
@@ -179,6 +196,12 @@ class FleetReplanLoop:
                                                  p(d["cur_pos"]), p(d["goal"]), p(d["jitter"]), self.longitu_step_dis,
                                                  self.lateral_step_length, self.move_vel, p(d["tail"]), p(d["near"]),
                                                  p(d["steps"]), p(d["flags"])))
+
+    def _jitter(self, sub, tick, r):
+        """jitter="counter": the round's target jitter of the missions `sub`, on the context's stream"""
+        c, d, p = self.bp.ctx, self._dev, self._p
+        c.check(c.lib.neo_fleet_jitter_dev(c.h, self.B, p(sub), int(sub.numel()), self.seed, int(tick), int(r),
+                                           p(d["mission_ids"]), p(d["jitter"])))
 
     def _sense(self, active, tm):
         """the active missions' poses from where they are, then mapper.update on what their cameras see"""
@@ -305,6 +328,7 @@ class FleetReplanLoop:
         if self.record is not None:
             self.record.bind(B)
             self.record.T_min, self.record.T_max = float(self.bp.cfg.T_min), float(self.bp.cfg.T_max)   # what rows() maps tau with
+        if self.record is not None or self.counter:
             self._dev["mission_ids"] = self._subset(self.mission_ids)
         self._poses, self._sensed = [], []
         self._up("goal", self.goals)
@@ -322,7 +346,8 @@ class FleetReplanLoop:
         them."""
         bufs = self.bp.plan_dev(self.plan_map, self._dev["head"], self._dev["tail"], bufs=self._plan_bufs(), x0=x0,
                                 slots=self._dev["plan_slots"], subset=sub, x=self._dev["x"], solved=self._dev["solved"],
-                                seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids)
+                                seed=plan_seed(self.seed, tick, r), jitter=self.jitter,
+                                stream_ids=self._dev["mission_ids"] if self.counter else self.mission_ids)
         idx = sub.long()
         return (self._dev["solved"][idx].cpu().numpy() != 0, bufs["nit_total"][idx].cpu().numpy(),
                 bufs["attempts"][idx].cpu().numpy())
@@ -371,7 +396,8 @@ class FleetReplanLoop:
                                                    p(pb["x_k"]), p(pb["head_k"]), p(pb["tail_k"]),
                                                    p(pb["slots_k"]) if d["plan_slots"] is not None else None))
             bp.plan_dev(self.plan_map, d["head"], d["tail"], bufs=pb, slots=d["plan_slots"], subset=fb_dev, x=d["x"], solved=d["solved"],
-                        seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids, _guessed=True)
+                        seed=plan_seed(self.seed, tick, r), jitter=self.jitter, _guessed=True,
+                        stream_ids=d["mission_ids"] if self.counter else self.mission_ids)
             idx = fb_dev.long()
             at = np.searchsorted(pending, fb)
             nit[at] += pb["nit_total"][idx].cpu().numpy()
@@ -383,7 +409,7 @@ class FleetReplanLoop:
             res = bp.plan(self.plan_map, head, tail, int_wpts=bp.batch_init_guess(head, tail, K=1)[0][:, 0],
                           ts=np.tile(bp._batch_ts_tau(count)[0], (fb.size, 1)),
                           scene_ids=None if self.plan_scene_ids is None else self.plan_scene_ids[fb],
-                          seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[fb])
+                          seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[fb], jitter=self.jitter)
             d["x"][idx] = torch.from_numpy(np.ascontiguousarray(res["x"])).to(self._device)
             d["solved"][idx] = torch.from_numpy(res["solved"].astype(np.int32)).to(self._device)
             at = np.searchsorted(pending, fb)
@@ -448,11 +474,14 @@ class FleetReplanLoop:
             pending = active
             for r in range(MAX_TARGETS):
                 t0 = time.perf_counter()
-                jit = np.zeros((B, 2))
-                jit[pending] = target_jitter(self.seed, self.mission_ids[pending], tick, r)
-                self._up("jitter", jit)
+                if not self.counter:
+                    jit = np.zeros((B, 2))
+                    jit[pending] = target_jitter(self.seed, self.mission_ids[pending], tick, r)
+                    self._up("jitter", jit)
                 sub = self._subset(pending)
                 self._sync()
+                if self.counter:
+                    self._jitter(sub, tick, r)
                 self._target(sub)
                 bp.ctx.synchronize()
                 if self.mode != "batch" and not self.resident:
@@ -471,7 +500,8 @@ class FleetReplanLoop:
                 else:
                     out = planner(self.plan_map, head[pending], tail[pending],
                                   scene_ids=None if self.plan_scene_ids is None else self.plan_scene_ids[pending],
-                                  seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[pending])
+                                  seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[pending],
+                                  **({"jitter": "counter"} if self.counter else {}))
                     ok, nit_total, attempts = out["solved"], out["nit_total"], out["attempts"]
                 tm["plan_s"] += time.perf_counter() - t0
                 tm["plans"] += 1

@@ -18,7 +18,7 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, counter_rng
 from .esdf import ESDF, ESDF3D
 
 
@@ -777,8 +777,15 @@ class BatchPlanner:
         return np.stack([np.random.default_rng([int(seed), int(i), int(attempt)]).normal(0.0, 0.5, (D, count))
                          for i in stream_ids])
 
+    @staticmethod
+    def retry_noise_counter(seed, stream_ids, attempt, D, count):
+        """`retry_noise` from the counter-based streams (counter_rng.py, the model of csrc/neo_counter_rng.hpp): request i's
+        (D, count) block is 0.5 * the unit normals (seed, i, attempt, value d * count + k) -- a pure function of those, so
+        neo_plan_jitter_dev draws the same bits on the device.  seed in 0 .. 2^64 - 1, ids in 0 .. 2^31 - 1."""
+        return counter_rng.retry_noise(seed, stream_ids, attempt, D, count)
+
     def plan(self, map, head, tail, int_wpts=None, ts=None, waypoints=None, max_attempts=5, rng=None, scene_ids=None,
-             seed=None, return_launch_sizes=False, stream_ids=None):
+             seed=None, return_launch_sizes=False, stream_ids=None, jitter="numpy"):
         """warm_start_plan (:186-203) for a batch: every request gets up to `max_attempts` plan_once runs.  An attempt that
         ends the way the reference raises on -- OverflowError statuses or `collision cost too large` (:235-237) -- is
         re-seeded like the reference's retries (straight line + N(0, 0.5), :94, :201) and optimised again; only the
@@ -787,14 +794,23 @@ class BatchPlanner:
         reference's warm_start_plan of one request does not depend on other requests (`seed`: an int; None draws one from
         `rng` or from the OS).  `stream_ids` (B,): the i of each request's streams in place of its position in the batch
         (None: the position) -- a caller that plans a changing subset of longer-lived requests (FleetReplanLoop: missions)
-        passes their ids, so that a request's retries do not depend on who else is in the batch.  Returns the optimiser's
+        passes their ids, so that a request's retries do not depend on who else is in the batch.  jitter="counter" draws
+        the retries from `retry_noise_counter` instead (still on the host here: the oracle of plan_dev(jitter="counter"));
+        a seed outside 0 .. 2^64 - 1 or an id outside 0 .. 2^31 - 1 then raises ValueError.  Returns the optimiser's
         dict plus `attempts` (B,), `nit_total` (B,: L-BFGS iterations over all attempts that ran to an answer, what the
         reference's planner.iter_num accumulates) and `solved` (B,): a request with solved False is one the reference
         answers with Exception("No solution for the given target")."""
         if (int_wpts is None) != (ts is None):
             raise ValueError("BatchPlanner.plan: give both int_wpts and ts, or neither")
+        counter = counter_rng.check_jitter(jitter, "BatchPlanner.plan")
         head = _lib.as_f64(head); tail = _lib.as_f64(tail)
         B, D = head.shape[0], head.shape[2]
+        if counter:         # (before any device use)
+            if seed is not None:
+                seed = counter_rng.check_seed(seed, "BatchPlanner.plan")
+            if stream_ids is not None:
+                counter_rng.check_ids(stream_ids, "BatchPlanner.plan")
+        draw = self.retry_noise_counter if counter else self.retry_noise
         if int_wpts is None:
             int_wpts, ts = self.init_guess(head, tail, waypoints if waypoints is not None else int(self.cfg.init_wpts_num))
         count = np.asarray(int_wpts).shape[2]
@@ -820,7 +836,7 @@ class BatchPlanner:
         for attempt in range(1, max_attempts):
             if todo.size == 0:
                 break
-            noise = self.retry_noise(seed, stream_ids[todo], attempt, D, count)
+            noise = draw(seed, stream_ids[todo], attempt, D, count)
             wp_n, ts_n = self.init_guess(head[todo], tail[todo], count)
             r = self.optimize(map, self.pack_x(wp_n + noise, ts_n), head[todo], tail[todo],
                               scene_ids=None if scene_ids is None else np.asarray(scene_ids)[todo])
@@ -865,7 +881,7 @@ class BatchPlanner:
         return bufs
 
     def plan_dev(self, map, head, tail, bufs=None, x0=None, slots=None, subset=None, x=None, solved=None, max_attempts=5,
-                 seed=None, rng=None, stream_ids=None, waypoints=None, _guessed=False):
+                 seed=None, rng=None, stream_ids=None, waypoints=None, _guessed=False, jitter="numpy"):
         """`plan` on RESIDENT torch tensors, every returned array bit for bit `plan`'s: head / tail (B, 3, D) float64 by
         request; `x0` (B, n) an optional first guess by request (plan's int_wpts / ts, packed: a warm start) -- without,
         attempt 0 starts from the straight line; `slots` (B,) int32 map-table slots by request or None; `subset` an
@@ -874,6 +890,11 @@ class BatchPlanner:
         neo_plan_merge_dev; between two attempts the host reads two words and the list of the failed requests, draws
         `retry_noise` for those -- from the streams SeedSequence(seed, stream_ids[request], attempt), `stream_ids` a HOST
         array by request (None: the index) -- and uploads it.  seed / rng / max_attempts / waypoints as in `plan`.
+        jitter="counter": plan(jitter="counter")'s arrays bit for bit, and the jitter never leaves the device --
+        `stream_ids` is a host array (checked, uploaded once a call) or an int32 DEVICE tensor by request (not read by the
+        host: ids in 0 .. 2^31 - 1 are the caller's word); between two attempts the host waits for the context's stream and
+        reads the two count words only, then neo_plan_jitter_dev fills the packed noise over the failed list where it
+        lies and the guess follows on the same stream: no list read-back, no host draw, no upload.
         Results by request in `bufs` (plan_buffers; made when None): x, costs, costs_last, nit, nfev, status (with the
         collision flag), attempts, nit_total (int64), solved (int32) and launch_sizes (a host list); `x` / `solved`: the
         caller's own resident arrays to write instead of the ones in bufs (FleetReplanLoop's).  Requests outside the
@@ -892,9 +913,22 @@ class BatchPlanner:
         M = count + 1
         if max_attempts < 1:
             raise ValueError("BatchPlanner.plan_dev: max_attempts must be >= 1")
-        stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
-        if stream_ids.shape[0] != B:
-            raise ValueError("BatchPlanner.plan_dev: stream_ids needs one id per request")
+        counter = counter_rng.check_jitter(jitter, "BatchPlanner.plan_dev")
+        ids_dev = None
+        if counter and isinstance(stream_ids, torch.Tensor):
+            if stream_ids.dtype != torch.int32 or stream_ids.device != head.device or stream_ids.numel() != B or \
+                    not stream_ids.is_contiguous():
+                raise ValueError("BatchPlanner.plan_dev: a device stream_ids is a contiguous int32 tensor, one id per request")
+            ids_dev = stream_ids
+        else:
+            stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
+            if stream_ids.shape[0] != B:
+                raise ValueError("BatchPlanner.plan_dev: stream_ids needs one id per request")
+        if counter:         # (before any device use)
+            if seed is not None:
+                seed = counter_rng.check_seed(seed, "BatchPlanner.plan_dev")
+            if ids_dev is None:
+                stream_ids = counter_rng.check_ids(stream_ids, "BatchPlanner.plan_dev").astype(np.int32)
         if bufs is not None and (bufs["B"] < B or bufs["D"] != D or bufs["M"] != M):
             raise ValueError("BatchPlanner.plan_dev: bufs were made for another B, D or number of waypoints")
         self._sync()
@@ -908,6 +942,8 @@ class BatchPlanner:
             seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
         frac, tau = self._plan_frac_tau(count)
         p = _lib.dev_ptr
+        if counter and ids_dev is None and max_attempts > 1:
+            ids_dev = torch.from_numpy(stream_ids).to(dev)      # (a blocking copy: there before the context's stream starts)
         slots_k = p(d["slots_k"]) if slots is not None else None
         out_x, out_solved = (x if x is not None else d["x"]), (solved if solved is not None else d["solved"])
         n_failed, bad = p(d["counts"][0:]), p(d["counts"][1:])
@@ -923,10 +959,13 @@ class BatchPlanner:
                     if bad_scene or nf == 0:
                         break
                     todo = d["todo"][(attempt - 1) % 2]
-                    ids = todo[:nf].cpu().numpy()
-                    noise = self.retry_noise(seed, stream_ids[ids], attempt, D, count)
-                    d["noise"][:nf].copy_(torch.from_numpy(np.ascontiguousarray(noise)))
-                    torch.cuda.synchronize(dev)
+                    if counter:
+                        c.check(c.lib.neo_plan_jitter_dev(c.h, B, p(todo), nf, M, D, seed, attempt, p(ids_dev), p(d["noise"])))
+                    else:
+                        ids = todo[:nf].cpu().numpy()
+                        noise = self.retry_noise(seed, stream_ids[ids], attempt, D, count)
+                        d["noise"][:nf].copy_(torch.from_numpy(np.ascontiguousarray(noise)))
+                        torch.cuda.synchronize(dev)
                     sub, P = p(todo), nf
                 if not (attempt == 0 and _guessed):
                     c.check(c.lib.neo_plan_guess_dev(c.h, B, sub, P, M, D, p(head), p(tail), p(slots),

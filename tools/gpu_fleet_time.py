@@ -9,14 +9,19 @@
   fleet     one whole run of 4096 missions (8 scenes x 512 goals drawn at 25 - 30 m) in mode basic, geo or batch: wall time per
             tick split into fleet kernels (with their small copies) / plan launches / host, missions per second, success
             rate, plans and failed attempts per mission, median weighted metric; --resident plans through
-            BatchPlanner.plan_dev on the resident arrays (modes basic and batch; the same flights)
+            BatchPlanner.plan_dev on the resident arrays (modes basic and batch; the same flights); --jitter counter draws
+            the target jitter and the retry noise from the counter-based streams on the device (other flights)
+  jitter    the counter-based jitter (neo_counter_rng.hpp) in one session: plan_jitter_kernel and fleet_jitter_kernel alone
+            at 4096 requests, M = 3, D = 2 (HIP events, 20 launches after 3 warm-ups), then whole runs of 4096 missions in
+            modes basic and batch, resident off and on, jitter numpy and counter, each flown once as a warm-up and then timed
 
 Each step is one process: run them one after the other, every one under its own time limit, e.g.
   timeout -k 10 300 python tools/gpu_fleet_time.py kernels --json profiles/fleet_kernels.json && \\
   timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode basic --json profiles/fleet_basic.json && \\
   timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode geo --json profiles/fleet_geo.json && \\
   timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode batch --json profiles/fleet_batch.json && \\
-  timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode basic --resident --json profiles/fleet_basic_resident.json
+  timeout -k 10 600 python tools/gpu_fleet_time.py fleet --mode basic --resident --json profiles/fleet_basic_resident.json && \\
+  timeout -k 10 600 python tools/gpu_fleet_time.py jitter --json profiles/fleet_jitter.json
 Prints one line per figure; --json PATH also writes them."""
 import argparse, ctypes, json, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,7 +32,7 @@ from neo_planner_amd import synth, _lib
 from neo_planner_amd.fleet import draw_missions
 
 ap = argparse.ArgumentParser()
-ap.add_argument("what", choices=["kernels", "fleet"])
+ap.add_argument("what", choices=["kernels", "fleet", "jitter"])
 ap.add_argument("--mode", default="basic", choices=["basic", "geo", "batch"])
 ap.add_argument("--scenes", type=int, default=8)
 ap.add_argument("--per-scene", type=int, default=512)
@@ -35,6 +40,7 @@ ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--launches", type=int, default=20)
 ap.add_argument("--max-replans", type=int, default=60)
 ap.add_argument("--resident", action="store_true")
+ap.add_argument("--jitter", default="numpy", choices=["numpy", "counter"])
 ap.add_argument("--json", default=None)
 a = ap.parse_args()
 
@@ -53,13 +59,13 @@ def dump(obj):
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
             json.dump(obj, f, indent=1)
+            f.write("\n")
 
 
-if a.what == "fleet":
-    maps = [scene_map(s) for s in range(a.scenes)]
-    start, goals, sids = draw_missions(maps, a.per_scene, seed=0)
+def fly(maps, start, goals, sids, mode, resident, jitter, detail=True):
+    """one whole run: the figures of a row"""
     bp = npa.BatchPlanner(ctx=ctx)
-    loop = npa.FleetReplanLoop(bp, maps[0], goals, mode=a.mode, scene_ids=sids, seed=0, resident=a.resident)
+    loop = npa.FleetReplanLoop(bp, maps[0], goals, mode=mode, scene_ids=sids, seed=0, resident=resident, jitter=jitter)
     t0 = time.perf_counter()
     out = loop.run(start, max_replans=a.max_replans)
     wall = time.perf_counter() - t0
@@ -67,7 +73,7 @@ if a.what == "fleet":
     ticks = loop.timings
     tot = {k: sum(t[k] for t in ticks) for k in ("tick_s", "fleet_s", "plan_s", "host_s")}
     ok = out["success"]
-    res = dict(mode=a.mode, resident=bool(a.resident), missions=B, scenes=a.scenes, wall_s=round(wall, 3), ticks=len(ticks),
+    res = dict(mode=mode, resident=bool(resident), jitter=jitter, missions=B, scenes=a.scenes, wall_s=round(wall, 3), ticks=len(ticks),
                missions_per_s=round(B / wall, 1), success_rate=float(ok.mean()),
                plans_per_mission=float(out["replans"].mean()), failed_attempts_per_mission=float(out["failed_attempts"].mean()),
                plan_launch_rounds=int(sum(t["plans"] for t in ticks)), plan_requests=int(sum(t["plan_requests"] for t in ticks)),
@@ -80,16 +86,74 @@ if a.what == "fleet":
                iterations_per_run=float(out["iter_num"].sum() / max(int(out["opt_runs"].sum()), 1)),
                audit_ms=round(1e3 * loop.audit_s, 3),
                per_tick_ms={k: round(1e3 * v / len(ticks), 3) for k, v in tot.items()},
-               share={k: round(v / tot["tick_s"], 4) for k, v in tot.items() if k != "tick_s"},
-               ticks_detail=[{k: (round(v, 5) if isinstance(v, float) else v) for k, v in t.items()} for t in ticks])
-    print(f"{a.mode}: {B} missions in {wall:.2f} s ({B / wall:.0f} missions/s), {len(ticks)} ticks; success "
+               share={k: round(v / tot["tick_s"], 4) for k, v in tot.items() if k != "tick_s"})
+    if detail:
+        res["ticks_detail"] = [{k: (round(v, 5) if isinstance(v, float) else v) for k, v in t.items()} for t in ticks]
+    tag = f"{mode}{' resident' if resident else ''}{' counter' if jitter == 'counter' else ''}"
+    print(f"{tag}: {B} missions in {wall:.2f} s ({B / wall:.0f} missions/s), {len(ticks)} ticks; success "
           f"{res['success_rate']:.3f}, plans a mission {res['plans_per_mission']:.2f}, failed attempts a mission "
           f"{res['failed_attempts_per_mission']:.3f}, abandoned {res['abandoned']}, metric_fail {res['metric_fail']}, "
           f"median weighted metric {res['median_weighted_metric']:.2f}", flush=True)
-    print(f"{a.mode}: per tick {res['per_tick_ms']['tick_s']:.1f} ms = fleet kernels and their copies "
+    print(f"{tag}: per tick {res['per_tick_ms']['tick_s']:.1f} ms = fleet kernels and their copies "
           f"{res['per_tick_ms']['fleet_s']:.1f} + plan launches {res['per_tick_ms']['plan_s']:.1f} + host "
           f"{res['per_tick_ms']['host_s']:.1f}; final audit {res['audit_ms']:.2f} ms", flush=True)
-    dump(res)
+    return res
+
+
+if a.what == "fleet":
+    maps = [scene_map(s) for s in range(a.scenes)]
+    start, goals, sids = draw_missions(maps, a.per_scene, seed=0)
+    dump(fly(maps, start, goals, sids, a.mode, a.resident, a.jitter))
+    sys.exit(0)
+
+if a.what == "jitter":
+    # the two kernels alone, on the context's own stream, timed with HIP events
+    stream = torch.cuda.Stream()
+    torch.cuda.set_stream(stream)
+    ctx.set_stream(stream.cuda_stream)
+    B, M, D = a.batch, 3, 2
+    p = lambda v: ctypes.c_void_p(v.data_ptr()) if v is not None else None
+    ids = torch.arange(B, dtype=torch.int32, device=dev) * 3 + 500
+    noise = torch.zeros((B, D, M - 1), dtype=torch.float64, device=dev)
+    jit = torch.zeros((B, 2), dtype=torch.float64, device=dev)
+    lib, h = ctx.lib, ctx.h
+    calls = {"plan_jitter": lambda: lib.neo_plan_jitter_dev(h, B, None, 0, M, D, 12345, 1, p(ids), p(noise)),
+             "fleet_jitter": lambda: lib.neo_fleet_jitter_dev(h, B, None, 0, 12345, 7, 3, p(ids), p(jit))}
+    stream.synchronize()
+    rows = []
+    for name, call in calls.items():
+        for _ in range(3):
+            ctx.check(call())
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(a.launches):
+            ctx.check(call())
+        e1.record(stream)
+        e1.synchronize()
+        us = 1e3 * e0.elapsed_time(e1) / a.launches
+        row = dict(kernel=name, batch=B, values=int(noise.numel() if name == "plan_jitter" else jit.numel()),
+                   us_per_launch=round(us, 2))
+        if name == "plan_jitter":
+            row.update(M=M, D=D)
+        rows.append(row)
+        print(f"{name:>12}: {us:8.1f} us per launch of {B}", flush=True)
+    from neo_planner_amd import counter_rng
+    assert np.array_equal(noise.cpu().numpy(), counter_rng.retry_noise(12345, ids.cpu().numpy(), 1, D, M - 1))
+    assert np.array_equal(jit.cpu().numpy(), counter_rng.target_jitter(12345, ids.cpu().numpy(), 7, 3))
+    ctx.set_stream(None)
+    torch.cuda.set_stream(torch.cuda.default_stream())
+    # whole runs, one session: every configuration flown once as a warm-up, then timed
+    maps = [scene_map(s) for s in range(a.scenes)]
+    start, goals, sids = draw_missions(maps, a.per_scene, seed=0)
+    runs = []
+    for mode in ("basic", "batch"):
+        for resident in (False, True):
+            for jitter in ("numpy", "counter"):
+                warm = fly(maps, start, goals, sids, mode, resident, jitter, detail=False)
+                res = fly(maps, start, goals, sids, mode, resident, jitter, detail=False)
+                res["warm_up_wall_s"] = warm["wall_s"]
+                runs.append(res)
+    dump(dict(kernels=rows, runs=runs))
     sys.exit(0)
 
 # ---- kernels: B missions on scene 0, timed on the state a short fleet run leaves (arrays a few plans long)
