@@ -724,6 +724,64 @@ int neo_plan_merge_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset,
                        int32_t *nit, int32_t *nfev, int32_t *status, int32_t *attempts, int64_t *nit_total,
                        int32_t *solved, int32_t *failed, int32_t *n_failed, int32_t *bad_scene);
 
+/* ---- adaptive waypoint counts: mixed M in one plan chain (traj_planner/expert_planner.py:86-88) ----------
+ * With init_wpts_mode 'adaptive' the reference places one waypoint per init_seg_len metres of straight-line distance:
+ * max(ceil(L / init_seg_len - 1), 1).  These calls give every request of a launch list its own count, group the list
+ * by count on the device, and carry BatchPlanner.plan's retry chain over the groups: per attempt and group
+ *   neo_plan_guess_dev -> neo_optimize_batch_from_dev (M = count + 1) -> neo_adaptive_merge_dev,
+ * then ONE neo_adaptive_compact_dev for all groups.  A host reads the group table once and the groups' failed counts
+ * once per attempt; it never waits per group.  REQUEST-INDEXED and PACKED arrays, `subset` and skipped indices as in
+ * the neo_plan_* block; a group is `count` = 0 .. NEO_MAX_PIECES - 1 (0 stays empty: a count is at least 1).
+ * Errors, before anything is launched and with every output untouched, with a neo_last_error message: B < 1, a bad
+ * subset size, D outside {2, 3}, max_waypoints outside 1 .. NEO_MAX_PIECES - 1, a seg_len that is not finite or not
+ * > 0, a NULL required buffer, and for merge a shape neo_plan_merge refuses or x_stride < n: NEO_ERR_INVALID. */
+/* the count of every launched request, one lane per position.  head / tail [B][3][D] request-indexed; only the
+ * positions head[b][0], tail[b][0] are read.  Every operation rounded on its own, no fused multiply-add:
+ *   d_k = tail[b][0][k] - head[b][0][k];  s = d_0 d_0 + d_1 d_1 (+ d_2 d_2), left to right;  L = sqrt(s);
+ *   c = ceil(L / seg_len - 1.0);  counts[b] = max(c, 1), and 1 when L is not finite;
+ *   above max_waypoints: counts[b] = max_waypoints and clamped[b] = 1 (0 otherwise)
+ * -- BatchPlanner.adaptive_counts, bit for bit.  counts, clamped [B] request-indexed: rows of requests not launched
+ * stay (the host form copies both up first). */
+int neo_adaptive_count(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int D, const double *head,
+                       const double *tail, double seg_len, int max_waypoints, int32_t *counts, int32_t *clamped);
+int neo_adaptive_count_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int D, const double *head,
+                           const double *tail, double seg_len, int max_waypoints, int32_t *counts, int32_t *clamped);
+/* the launch list grouped by count: a stable counting sort by ONE workgroup (a histogram pass, a scan over the
+ * NEO_MAX_PIECES counters, a placement pass; ballots and per-wavefront counters in LDS, no atomics -- nothing depends
+ * on scheduling).  counts [B] request-indexed.
+ *   order[P]         the launched request indices by ascending count, in launch-list order within a count: what
+ *                    np.argsort(counts[list], kind="stable") gives.  Skipped indices, and requests whose count is
+ *                    outside 0 .. NEO_MAX_PIECES - 1, are dropped; entries from total on stay.  Must not be `subset`;
+ *   bucket_begin[NEO_MAX_PIECES + 1]   group c is order[bucket_begin[c] .. bucket_begin[c + 1] - 1];
+ *   total[1]         the entries kept (= bucket_begin[NEO_MAX_PIECES]).
+ * An empty list (n_subset = 0 with a subset) writes an all-zero table and total 0. */
+int neo_adaptive_bucket(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const int32_t *counts, int32_t *order,
+                        int32_t *bucket_begin, int32_t *total);
+int neo_adaptive_bucket_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const int32_t *counts,
+                            int32_t *order, int32_t *bucket_begin, int32_t *total);
+/* neo_plan_merge_dev's bookkeeping for ONE group of a mixed chain (DEVICE pointers, asynchronous), two differences:
+ * the request-indexed x has rows of x_stride >= n doubles -- row b gets the group's n = D (M - 1) + M values, then NaN
+ * up to x_stride -- and nothing is compacted: pending[P] gets the request's index where it failed, -1 elsewhere
+ * (skipped positions too), for neo_adaptive_compact_dev.  bad_scene[1] is set to 1 as in merge but zeroed only when
+ * clear_bad != 0 (the first group a chain issues): it gathers over the groups.  An empty list launches nothing. */
+int neo_adaptive_merge_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, int D, int x_stride,
+                           int reset, int clear_bad, const double *x_k, const double *costs4_k,
+                           const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
+                           const int32_t *status_k, double *x, double *costs4, double *costs4_last, int32_t *nit,
+                           int32_t *nfev, int32_t *status, int32_t *attempts, int64_t *nit_total, int32_t *solved,
+                           int32_t *pending, int32_t *bad_scene);
+/* the segmented compaction of an attempt: one workgroup per group, the in-place ordered walk of the plan chain's
+ * compaction.  seg_begin, seg_len: HOST arrays [NEO_MAX_PIECES] (handed to the kernel by value): group c owns
+ * pending[seg_begin[c] .. seg_begin[c] + seg_len[c] - 1]; segments must not overlap.  Its entries >= 0 are packed to the
+ * front of the segment in position order and n_failed[c] is their number (0 for an empty segment); entries behind
+ * them are scratch.  pending [rows], n_failed [NEO_MAX_PIECES]: device arrays in the _dev form; the host form takes
+ * `rows`, the length of pending, and checks the segments against it.  Further errors: a negative seg_begin or seg_len:
+ * NEO_ERR_INVALID. */
+int neo_adaptive_compact(neo_ctx *ctx, const int32_t *seg_begin, const int32_t *seg_len, int rows, int32_t *pending,
+                         int32_t *n_failed);
+int neo_adaptive_compact_dev(neo_ctx *ctx, const int32_t *seg_begin, const int32_t *seg_len, int32_t *pending,
+                             int32_t *n_failed);
+
 /* ---- batched depth camera ---------------------------------------------------
  * B pinhole depth images of box scenes in one call: neo_planner_amd/initializer.py raycast_depth, the sensor in front
  * of the initializer network (traj_planner/record_planner.py:16-18 scales the image to uint8 by its maximum), for B

@@ -2017,6 +2017,168 @@ int neo_plan_merge(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M
   return st.download();
 }
 
+// ---- adaptive waypoint counts and the plan chain over groups of one count (expert_planner.py:86-88; kernels:
+// neo_adaptive.hpp)
+static int adaptive_list_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset) {
+  return list_check(c, who, B, 1, INT32_MAX, subset, n_subset);
+}
+
+static int adaptive_count_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int D, const double *head,
+                                const double *tail, double seg_len, int max_waypoints, const int32_t *counts,
+                                const int32_t *clamped) {
+  int rc = adaptive_list_check(c, "adaptive count", B, subset, n_subset);
+  if (rc) return rc;
+  if (D < 2 || D > NEO_MAX_DIM) return fail_locked(c, NEO_ERR_INVALID, "adaptive count: D must be 2 or 3");
+  if (max_waypoints < 1 || max_waypoints > NEO_MAX_PIECES - 1)
+    return fail_locked(c, NEO_ERR_INVALID, "adaptive count: max_waypoints must be in 1 .. NEO_MAX_PIECES - 1");
+  if (!std::isfinite(seg_len) || !(seg_len > 0.0))
+    return fail_locked(c, NEO_ERR_INVALID, "adaptive count: seg_len must be finite and > 0");
+  if (!head || !tail || !counts || !clamped) return fail_locked(c, NEO_ERR_INVALID, "adaptive count: null buffer");
+  return NEO_OK;
+}
+
+int neo_adaptive_count_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int D, const double *head,
+                           const double *tail, double seg_len, int max_waypoints, int32_t *counts, int32_t *clamped) {
+  int rc = adaptive_count_check(c, B, subset, n_subset, D, head, tail, seg_len, max_waypoints, counts, clamped);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, adaptive_count(c, list, D, head, tail, seg_len, max_waypoints, counts, clamped));
+}
+
+int neo_adaptive_count(neo_ctx *c, int B, const int32_t *subset, int n_subset, int D, const double *head,
+                       const double *tail, double seg_len, int max_waypoints, int32_t *counts, int32_t *clamped) {
+  int rc = adaptive_count_check(c, B, subset, n_subset, D, head, tail, seg_len, max_waypoints, counts, clamped);
+  if (rc) return rc;
+  const size_t bs = (size_t)B, hd = (size_t)3 * D;
+  if (launch_list(B, subset, n_subset).n == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  // the results go up too: the rows of requests not launched come back as they were
+  HostStage st(c, kStagedUpTo);
+  const auto fh = st.in(head, bs * hd), ft = st.in(tail, bs * hd);
+  const auto fsub = st.in_optional(subset, (size_t)n_subset);
+  const auto oc = st.inout(counts, bs), ocl = st.inout(clamped, bs);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_adaptive_count_dev(c, B, st.dev(fsub), n_subset, D, st.dev(fh), st.dev(ft), seg_len, max_waypoints, st.dev(oc),
+                              st.dev(ocl));
+  if (rc) return rc;
+  return st.download();
+}
+
+static int adaptive_bucket_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const int32_t *counts,
+                                 const int32_t *order, const int32_t *bucket_begin, const int32_t *total) {
+  int rc = adaptive_list_check(c, "adaptive bucket", B, subset, n_subset);
+  if (rc) return rc;
+  if (!counts || !order || !bucket_begin || !total) return fail_locked(c, NEO_ERR_INVALID, "adaptive bucket: null buffer");
+  if (subset && order == subset) return fail_locked(c, NEO_ERR_INVALID, "adaptive bucket: order must not be the subset");
+  return NEO_OK;
+}
+
+int neo_adaptive_bucket_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const int32_t *counts, int32_t *order,
+                            int32_t *bucket_begin, int32_t *total) {
+  int rc = adaptive_bucket_check(c, B, subset, n_subset, counts, order, bucket_begin, total);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) {
+    HIPCHK(c, hipMemsetAsync(bucket_begin, 0, (NEO_MAX_PIECES + 1) * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(total, 0, sizeof(int32_t), c->stream));
+    return NEO_OK;
+  }
+  return launched(c, adaptive_bucket(c, list, counts, order, bucket_begin, total));
+}
+
+int neo_adaptive_bucket(neo_ctx *c, int B, const int32_t *subset, int n_subset, const int32_t *counts, int32_t *order,
+                        int32_t *bucket_begin, int32_t *total) {
+  int rc = adaptive_bucket_check(c, B, subset, n_subset, counts, order, bucket_begin, total);
+  if (rc) return rc;
+  const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n;
+  if (P == 0) {
+    std::memset(bucket_begin, 0, (NEO_MAX_PIECES + 1) * sizeof(int32_t));
+    *total = 0;
+    return NEO_OK;
+  }
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  // the order goes up too: its entries from total on come back as they were
+  HostStage st(c, kStagedUpTo);
+  const auto fc = st.in(counts, bs);
+  const auto fsub = st.in_optional(subset, (size_t)n_subset);
+  const auto oo = st.inout(order, P);
+  const auto ob = st.out(bucket_begin, (size_t)NEO_MAX_PIECES + 1), ot = st.out(total, 1);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_adaptive_bucket_dev(c, B, st.dev(fsub), n_subset, st.dev(fc), st.dev(oo), st.dev(ob), st.dev(ot));
+  if (rc) return rc;
+  return st.download();
+}
+
+int neo_adaptive_merge_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int x_stride, int reset,
+                           int clear_bad, const double *x_k, const double *costs4_k, const double *costs4_last_k,
+                           const int32_t *nit_k, const int32_t *nfev_k, const int32_t *status_k, double *x, double *costs4,
+                           double *costs4_last, int32_t *nit, int32_t *nfev, int32_t *status, int32_t *attempts,
+                           int64_t *nit_total, int32_t *solved, int32_t *pending, int32_t *bad_scene) {
+  int rc = adaptive_list_check(c, "adaptive merge", B, subset, n_subset);
+  if (rc) return rc;
+  rc = plan_check(c, "adaptive merge", B, subset, n_subset, M, D);
+  if (rc) return rc;
+  const int n = D * (M - 1) + M;
+  if (x_stride < n) return fail_locked(c, NEO_ERR_INVALID, "adaptive merge: x_stride must be >= n = D (M - 1) + M");
+  if (!x_k || !costs4_k || !costs4_last_k || !nit_k || !nfev_k || !status_k || !x || !costs4 || !costs4_last || !nit || !nfev ||
+      !status || !attempts || !nit_total || !solved || !pending || !bad_scene)
+    return fail_locked(c, NEO_ERR_INVALID, "adaptive merge: null buffer");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (clear_bad) HIPCHK(c, hipMemsetAsync(bad_scene, 0, sizeof(int32_t), c->stream));
+  if (list.n == 0) return NEO_OK;
+  const AdaptiveMergeArgs a{n, x_stride, reset ? 1 : 0, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k},
+                            {x, costs4, costs4_last, nit, nfev, status}, attempts, reinterpret_cast<long long *>(nit_total),
+                            solved, pending, bad_scene};
+  return launched(c, adaptive_merge(c, list, a));
+}
+
+static int adaptive_compact_check(neo_ctx *c, const int32_t *seg_begin, const int32_t *seg_len, long long rows,
+                                  const int32_t *pending, const int32_t *n_failed) {
+  if (!c) return NEO_ERR_INVALID;
+  if (!seg_begin || !seg_len || !pending || !n_failed) return fail_locked(c, NEO_ERR_INVALID, "adaptive compact: null buffer");
+  for (int g = 0; g < NEO_MAX_PIECES; ++g)
+    if (seg_begin[g] < 0 || seg_len[g] < 0 || (rows >= 0 && (long long)seg_begin[g] + seg_len[g] > rows))
+      return fail_locked(c, NEO_ERR_INVALID, "adaptive compact: a segment is negative or ends beyond pending");
+  return NEO_OK;
+}
+
+int neo_adaptive_compact_dev(neo_ctx *c, const int32_t *seg_begin, const int32_t *seg_len, int32_t *pending,
+                             int32_t *n_failed) {
+  int rc = adaptive_compact_check(c, seg_begin, seg_len, -1, pending, n_failed);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  return launched(c, adaptive_compact(c, seg_begin, seg_len, pending, n_failed));
+}
+
+int neo_adaptive_compact(neo_ctx *c, const int32_t *seg_begin, const int32_t *seg_len, int rows, int32_t *pending,
+                         int32_t *n_failed) {
+  if (c && rows < 0) return fail_locked(c, NEO_ERR_INVALID, "adaptive compact: rows must be >= 0");
+  int rc = adaptive_compact_check(c, seg_begin, seg_len, rows, pending, n_failed);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  HostStage st(c, kStagedUpTo);
+  const auto fp = st.inout(pending, (size_t)rows);
+  const auto on = st.out(n_failed, (size_t)NEO_MAX_PIECES);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_adaptive_compact_dev(c, seg_begin, seg_len, st.dev(fp), st.dev(on));
+  if (rc) return rc;
+  return st.download();
+}
+
 // ---- geo warm start (traj_planner/astar_planner.py, geo_planner.py:19-101; kernels: neo_geo.hpp)
 static int geo_check(neo_ctx *c, int B, const double *start, const double *target, int max_expansions, int path_cap,
                      const double *key_pts, const double *path, const int32_t *path_len, const double *path_cost,

@@ -31,6 +31,7 @@ NEO_GEO_FLAG_BAD_SCENE = 16
 # neo_fleet_*: flag bits of a mission
 NEO_FLEET_FLAG_TARGET_CAPPED, NEO_FLEET_FLAG_CMD_FULL, NEO_FLEET_FLAG_BAD_SCENE, NEO_FLEET_FLAG_SPLICE_FAILED = 1, 2, 4, 8
 NEO_FLEET_FLAG_ABANDONED = 16
+NEO_MAX_PIECES = 64                # M of any trajectory; neo_adaptive_*: one group per waypoint count below it
 NEO_BATCH_MAX_CANDIDATES = 8       # neo_batch_*: candidates a request
 NEO_DEPTH_MAX_BOXES = 1024         # neo_depth_*: boxes a scene
 # neo_init_*: sizes of the motion vector, a feature row, the network's output, x0, and the head's weight blob
@@ -59,6 +60,8 @@ EXPORTS = [
     "neo_esdf_build_2d_batch_dev", "neo_fleet_pose_dev", "neo_record_state_dev", "neo_record_commit_dev",
     "neo_optimize_plan_launches", "neo_init_motion_dev", "neo_init_head_dev", "neo_init_guess_dev",
     "neo_plan_jitter", "neo_plan_jitter_dev", "neo_fleet_jitter", "neo_fleet_jitter_dev",
+    "neo_adaptive_count", "neo_adaptive_count_dev", "neo_adaptive_bucket", "neo_adaptive_bucket_dev",
+    "neo_adaptive_merge_dev", "neo_adaptive_compact", "neo_adaptive_compact_dev",
 ]
 
 
@@ -144,6 +147,13 @@ def load():
     L.neo_plan_jitter_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, ctypes.c_uint64, c_i, c_p, c_p]
     L.neo_fleet_jitter.argtypes = [c_p, c_i, c_p, c_i, ctypes.c_uint64, c_i, c_i, c_p, c_p]
     L.neo_fleet_jitter_dev.argtypes = [c_p, c_i, c_p, c_i, ctypes.c_uint64, c_i, c_i, c_p, c_p]
+    L.neo_adaptive_count.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p]
+    L.neo_adaptive_count_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p]
+    L.neo_adaptive_bucket.argtypes = [c_p, c_i, c_p, c_i] + [c_p] * 4
+    L.neo_adaptive_bucket_dev.argtypes = [c_p, c_i, c_p, c_i] + [c_p] * 4
+    L.neo_adaptive_merge_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i] + [c_p] * 17
+    L.neo_adaptive_compact.argtypes = [c_p, c_p, c_p, c_i, c_p, c_p]
+    L.neo_adaptive_compact_dev.argtypes = [c_p, c_p, c_p, c_p, c_p]
     L.neo_depth_render_batch.argtypes = [c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_i, c_p, c_i] + [c_p] * 4
     L.neo_depth_render_batch_dev.argtypes = [c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_i, c_p, c_i] + [c_p] * 4
     L.neo_depth_box_test_counter.argtypes = [c_p, c_p]

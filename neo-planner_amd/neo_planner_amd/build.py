@@ -19,7 +19,8 @@ OBJDIR = os.path.join(CSRC, "build")
 SOURCES = ["neo_abi.hip", "neo_disp_eval.hip", "neo_disp_sample.hip", "neo_disp_opt2d.hip", "neo_disp_opt2d_x.hip", "neo_disp_opt3d_f32.hip",
            "neo_disp_opt3d_f64.hip", "neo_disp_opt3d_w2.hip", "neo_disp_opt3d_x.hip", "neo_disp_group.hip", "neo_disp_opt3d_b.hip",
            "neo_disp_audit.hip", "neo_disp_geo.hip", "neo_disp_fleet.hip", "neo_disp_batch.hip", "neo_disp_esdf.hip",
-           "neo_disp_plan.hip", "neo_disp_depth.hip", "neo_disp_onboard.hip", "neo_disp_record.hip", "neo_disp_init.hip"]
+           "neo_disp_plan.hip", "neo_disp_depth.hip", "neo_disp_onboard.hip", "neo_disp_record.hip", "neo_disp_init.hip",
+           "neo_disp_adaptive.hip"]
 HEADERS = ["neo_wave.hpp", "neo_device.hpp", "neo_kernels.hpp", "neo_host.hpp", "neo_launch_list.hpp", "neo_launch_opt.hpp", "neo_lbfgs.hpp",
            "neo_linesearch.hpp", "neo_lbfgs_sm.hpp", "neo_lbfgs_dir.hpp", "neo_group_kernel.hpp",
            # (the counter-based jitter, included by the plan and the fleet unit; small enough to sit with the shared ones)
@@ -62,7 +63,8 @@ UNIT_HEADERS = {"neo_disp_audit.hip": ["neo_audit.hpp"], "neo_disp_geo.hip": ["n
                 "neo_disp_fleet.hip": ["neo_fleet.hpp", "neo_audit.hpp"], "neo_disp_batch.hip": ["neo_batch.hpp"],
                 "neo_disp_esdf.hip": ["neo_esdf.hpp"], "neo_disp_plan.hip": ["neo_plan.hpp"],
                 "neo_disp_depth.hip": ["neo_depth.hpp"], "neo_disp_onboard.hip": ["neo_onboard.hpp"],
-                "neo_disp_record.hip": ["neo_record.hpp"], "neo_disp_init.hip": ["neo_init.hpp", "neo_record.hpp"]}
+                "neo_disp_record.hip": ["neo_record.hpp"], "neo_disp_init.hip": ["neo_init.hpp", "neo_record.hpp"],
+                "neo_disp_adaptive.hip": ["neo_adaptive.hpp"]}
 
 
 def _headers(src=None):

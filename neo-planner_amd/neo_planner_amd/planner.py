@@ -785,7 +785,7 @@ class BatchPlanner:
         return counter_rng.retry_noise(seed, stream_ids, attempt, D, count)
 
     def plan(self, map, head, tail, int_wpts=None, ts=None, waypoints=None, max_attempts=5, rng=None, scene_ids=None,
-             seed=None, return_launch_sizes=False, stream_ids=None, jitter="numpy"):
+             seed=None, return_launch_sizes=False, stream_ids=None, jitter="numpy", max_waypoints=63):
         """warm_start_plan (:186-203) for a batch: every request gets up to `max_attempts` plan_once runs.  An attempt that
         ends the way the reference raises on -- OverflowError statuses or `collision cost too large` (:235-237) -- is
         re-seeded like the reference's retries (straight line + N(0, 0.5), :94, :201) and optimised again; only the
@@ -799,7 +799,12 @@ class BatchPlanner:
         a seed outside 0 .. 2^64 - 1 or an id outside 0 .. 2^31 - 1 then raises ValueError.  Returns the optimiser's
         dict plus `attempts` (B,), `nit_total` (B,: L-BFGS iterations over all attempts that ran to an answer, what the
         reference's planner.iter_num accumulates) and `solved` (B,): a request with solved False is one the reference
-        answers with Exception("No solution for the given target")."""
+        answers with Exception("No solution for the given target").
+        waypoints="adaptive": every request its own number of waypoints (`adaptive_counts`, at most `max_waypoints`), see
+        `_plan_adaptive` for the ragged dict that comes back."""
+        if isinstance(waypoints, str):
+            return self._plan_adaptive(map, head, tail, int_wpts, ts, waypoints, max_attempts, rng, scene_ids, seed,
+                                       return_launch_sizes, stream_ids, jitter, max_waypoints)
         if (int_wpts is None) != (ts is None):
             raise ValueError("BatchPlanner.plan: give both int_wpts and ts, or neither")
         counter = counter_rng.check_jitter(jitter, "BatchPlanner.plan")
@@ -851,6 +856,107 @@ class BatchPlanner:
             out["launch_sizes"] = launches
         return out
 
+    # ------------------------------------------------------------ adaptive waypoint counts (:86-88) for a batch
+    def _adaptive_args(self, max_waypoints, who):
+        """init_seg_len as a float, after the checks of `adaptive_counts` (before any device use)"""
+        if int(max_waypoints) != max_waypoints or not 1 <= max_waypoints <= _lib.NEO_MAX_PIECES - 1:
+            raise ValueError("%s: max_waypoints must be in 1 .. %d" % (who, _lib.NEO_MAX_PIECES - 1))
+        seg = float(self.cfg.init_seg_len)
+        if not (math.isfinite(seg) and seg > 0.0):
+            raise ValueError("%s: init_seg_len must be finite and > 0" % who)
+        return seg
+
+    def adaptive_counts(self, head, tail, max_waypoints=63):
+        """the reference's adaptive waypoint count (generate_init_variables, :86-88) for B requests: one waypoint per
+        init_seg_len metres of straight-line distance, max(ceil(L / init_seg_len - 1), 1).  head / tail (B, >= 1, D), D =
+        2 or 3.  Every operation is rounded on its own, in this order -- the definition adaptive_count_kernel restates:
+        d_k = tail[0][k] - head[0][k]; s = d_0 * d_0 + d_1 * d_1 (+ d_2 * d_2) from left to right; L = sqrt(s);
+        c = ceil(L / init_seg_len - 1.0); count = max(c, 1).  A non-finite L gives 1 (the optimiser reports such a request
+        as it does today); a count above `max_waypoints` becomes max_waypoints with `clamped` set.
+        Returns (counts int32 (B,), clamped bool (B,))."""
+        seg = self._adaptive_args(max_waypoints, "BatchPlanner.adaptive_counts")
+        head = np.asarray(head, dtype=np.float64); tail = np.asarray(tail, dtype=np.float64)
+        if head.ndim != 3 or head.shape[2] not in (2, 3) or tail.shape[0] != head.shape[0] or tail.shape[2] != head.shape[2]:
+            raise ValueError("BatchPlanner.adaptive_counts: head and tail (B, 3, D), D = 2 or 3")
+        with np.errstate(all="ignore"):
+            d = tail[:, 0] - head[:, 0]
+            s = d[:, 0] * d[:, 0]
+            for k in range(1, d.shape[1]):
+                s = s + d[:, k] * d[:, k]
+            L = np.sqrt(s)
+            c = np.ceil(L / seg - 1.0)
+        finite = np.isfinite(L)
+        clamped = finite & (c > max_waypoints)
+        counts = np.where(finite, np.minimum(np.maximum(c, 1.0), float(max_waypoints)), 1.0)
+        return counts.astype(np.int32), clamped
+
+    @staticmethod
+    def adaptive_groups(result, rows=None):
+        """the ragged result of plan / plan_dev(waypoints="adaptive") group by group, for eval_traj, audit and every
+        other consumer of one M: yields (count, indices (k,), x_dense (k, n)) by ascending count, indices ascending, n =
+        D * count + count + 1 the group's own row length (D from the row length of `x` and the buffers' max_waypoints).
+        `result`: the dict of either form (NumPy arrays or torch tensors).  `rows`: the request indices to look at
+        (None: all) -- after a plan_dev over a subset, the subset."""
+        host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        counts, x = host(result["counts"]), host(result["x"])
+        W = int(result["max_waypoints"])
+        D = (x.shape[1] - 1) // W - 1
+        if D * W + W + 1 != x.shape[1]:
+            raise ValueError("BatchPlanner.adaptive_groups: x is not (B, D * max_waypoints + max_waypoints + 1)")
+        rows = np.arange(counts.shape[0]) if rows is None else np.sort(np.asarray(rows).reshape(-1))
+        for c in np.unique(counts[rows]):
+            if not 1 <= c <= W:
+                raise ValueError("BatchPlanner.adaptive_groups: a count outside 1 .. max_waypoints (rows= names the planned requests)")
+            idx = rows[counts[rows] == c]
+            yield int(c), idx, np.ascontiguousarray(x[idx, :D * int(c) + int(c) + 1])
+
+    def _plan_adaptive(self, map, head, tail, int_wpts, ts, waypoints, max_attempts, rng, scene_ids, seed,
+                       return_launch_sizes, stream_ids, jitter, max_waypoints):
+        """plan(waypoints="adaptive"), the host form and plan_dev's oracle: `adaptive_counts`, a stable grouping by
+        count, `plan` per group with the group's count -- a request's streams are its own, so its retries are those of the
+        request planned alone -- and the groups' results in one RAGGED dict: x (B, n_max), n_max = D * max_waypoints +
+        max_waypoints + 1, request b's row its n_b = D * count_b + count_b + 1 values [q row-major ; tau], then NaN; the
+        other arrays of `plan` by request; counts, clamped (`adaptive_counts`) and max_waypoints; launch_sizes
+        (requests launched per attempt over all groups) and group_launch_sizes {count: sizes per attempt}."""
+        if waypoints != "adaptive":
+            raise ValueError("BatchPlanner.plan: waypoints is a number, None or 'adaptive'")
+        if int_wpts is not None or ts is not None:
+            raise ValueError("BatchPlanner.plan: int_wpts / ts fix their own shape: not with waypoints='adaptive'")
+        self._adaptive_args(max_waypoints, "BatchPlanner.plan")
+        counter = counter_rng.check_jitter(jitter, "BatchPlanner.plan")
+        head = _lib.as_f64(head); tail = _lib.as_f64(tail)
+        B, D = head.shape[0], head.shape[2]
+        W = int(max_waypoints)
+        counts, clamped = self.adaptive_counts(head, tail, W)
+        if counter and seed is not None:
+            seed = counter_rng.check_seed(seed, "BatchPlanner.plan")
+        if seed is None:        # (one seed for every group)
+            seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
+        stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
+        if stream_ids.shape[0] != B:
+            raise ValueError("BatchPlanner.plan: stream_ids needs one id per request")
+        order = np.argsort(counts, kind="stable")
+        out = dict(x=np.full((B, D * W + W + 1), np.nan), counts=counts, clamped=clamped, max_waypoints=W)
+        launches, by_group = [], {}
+        for c in np.unique(counts):
+            g = order[counts[order] == c]
+            r = self.plan(map, head[g], tail[g], waypoints=int(c), max_attempts=max_attempts, seed=seed, jitter=jitter,
+                          scene_ids=None if scene_ids is None else np.asarray(scene_ids)[g], stream_ids=stream_ids[g],
+                          return_launch_sizes=True)
+            sizes = by_group[int(c)] = r.pop("launch_sizes")
+            launches += [0] * (len(sizes) - len(launches))
+            for a, k in enumerate(sizes):
+                launches[a] += k
+            xg = r.pop("x")
+            out["x"][g, :xg.shape[1]] = xg
+            for k, v in r.items():
+                if k not in out:
+                    out[k] = np.zeros((B,) + v.shape[1:], dtype=v.dtype)
+                out[k][g] = v
+        if return_launch_sizes:
+            out.update(launch_sizes=launches, group_launch_sizes=by_group)
+        return out
+
     # ------------------------------------------------------------ `plan` on resident arrays
     def _plan_frac_tau(self, count):
         """what neo_plan_guess takes from the host: init_guess's fractions f[k] = k / (count + 1) and the tau of its
@@ -861,11 +967,19 @@ class BatchPlanner:
         ts[:, -1] *= 1.5
         return frac, np.ascontiguousarray(self.pack_x(np.zeros((1, 1, count)), ts)[0, count:])
 
-    def plan_buffers(self, B, device, D=2, waypoints=None):
+    def plan_buffers(self, B, device, D=2, waypoints=None, max_waypoints=63):
         """the resident arrays of `plan_dev` for up to B requests of dimension D with `waypoints` waypoints (None: the
         config's init_wpts_num): the packed work arrays of an attempt's launch, the two launch lists, and the
-        request-indexed results (torch tensors, zeroed)"""
+        request-indexed results (torch tensors, zeroed).  waypoints="adaptive": the same arrays sized for `max_waypoints`
+        (x: rows of n_max), plus the request-indexed counts and clamped, the grouped list `group_order` and the group
+        `table` the host reads (bucket_begin, the groups' failed counts, the bad-scene word, the total)"""
         import torch
+        adaptive = isinstance(waypoints, str)
+        if adaptive:
+            if waypoints != "adaptive":
+                raise ValueError("BatchPlanner.plan_buffers: waypoints is a number, None or 'adaptive'")
+            self._adaptive_args(max_waypoints, "BatchPlanner.plan_buffers")
+            waypoints = max_waypoints
         count = int(waypoints if waypoints is not None else self.cfg.init_wpts_num)
         M, n = count + 1, D * count + count + 1
         f = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
@@ -878,10 +992,37 @@ class BatchPlanner:
         if B > 1024:        # (launches this large are dispatched longest-expected first, as `optimize` does)
             nbytes = int(_lib.load().neo_effort_order_scratch_bytes(B))
             bufs.update(order=i(B), order_scratch=f(nbytes // 8 + 1))
+        if adaptive:
+            G = _lib.NEO_MAX_PIECES
+            bufs.update(adaptive=True, max_waypoints=count, counts=i(B), clamped=i(B), group_order=i(R), table=i(2 * G + 3),
+                        group_launch_sizes={}, host_waits={})
         return bufs
 
+    @staticmethod
+    def _plan_dev_streams(stream_ids, head, counter, seed):
+        """plan_dev's stream ids and seed, checked before any device use: (the host array or None, the device tensor or
+        None, the seed)"""
+        import torch
+        B = head.shape[0]
+        ids_dev = None
+        if counter and isinstance(stream_ids, torch.Tensor):
+            if stream_ids.dtype != torch.int32 or stream_ids.device != head.device or stream_ids.numel() != B or \
+                    not stream_ids.is_contiguous():
+                raise ValueError("BatchPlanner.plan_dev: a device stream_ids is a contiguous int32 tensor, one id per request")
+            ids_dev = stream_ids
+        else:
+            stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
+            if stream_ids.shape[0] != B:
+                raise ValueError("BatchPlanner.plan_dev: stream_ids needs one id per request")
+        if counter:
+            if seed is not None:
+                seed = counter_rng.check_seed(seed, "BatchPlanner.plan_dev")
+            if ids_dev is None:
+                stream_ids = counter_rng.check_ids(stream_ids, "BatchPlanner.plan_dev").astype(np.int32)
+        return stream_ids, ids_dev, seed
+
     def plan_dev(self, map, head, tail, bufs=None, x0=None, slots=None, subset=None, x=None, solved=None, max_attempts=5,
-                 seed=None, rng=None, stream_ids=None, waypoints=None, _guessed=False, jitter="numpy"):
+                 seed=None, rng=None, stream_ids=None, waypoints=None, _guessed=False, jitter="numpy", max_waypoints=63):
         """`plan` on RESIDENT torch tensors, every returned array bit for bit `plan`'s: head / tail (B, 3, D) float64 by
         request; `x0` (B, n) an optional first guess by request (plan's int_wpts / ts, packed: a warm start) -- without,
         attempt 0 starts from the straight line; `slots` (B,) int32 map-table slots by request or None; `subset` an
@@ -899,10 +1040,19 @@ class BatchPlanner:
         collision flag), attempts, nit_total (int64), solved (int32) and launch_sizes (a host list); `x` / `solved`: the
         caller's own resident arrays to write instead of the ones in bufs (FleetReplanLoop's).  Requests outside the
         subset keep what they had.  The chain has ended when the call returns (the context's stream is waited for).  A
-        request that names a map-table slot without a map raises NeoError, as in `plan`.  Returns bufs."""
+        request that names a map-table slot without a map raises NeoError, as in `plan`.  Returns bufs.
+        waypoints="adaptive": plan(waypoints="adaptive")'s ragged arrays bit for bit, every request with its own count of
+        at most `max_waypoints` -- see `_plan_dev_adaptive`."""
         import torch
         if head.ndim != 3 or head.shape[1] != 3 or tuple(tail.shape) != tuple(head.shape):
             raise ValueError("BatchPlanner.plan_dev: head and tail (B, 3, D)")
+        if isinstance(waypoints, str):
+            if waypoints != "adaptive":
+                raise ValueError("BatchPlanner.plan_dev: waypoints is a number, None or 'adaptive'")
+            if x0 is not None:
+                raise ValueError("BatchPlanner.plan_dev: a warm start x0 fixes its own shape: not with waypoints='adaptive'")
+            return self._plan_dev_adaptive(map, head, tail, bufs, slots, subset, x, solved, max_attempts, seed, rng, stream_ids,
+                                           jitter, max_waypoints)
         B, D = head.shape[0], head.shape[2]
         count = int(waypoints if waypoints is not None else self.cfg.init_wpts_num)
         if x0 is not None:
@@ -914,21 +1064,7 @@ class BatchPlanner:
         if max_attempts < 1:
             raise ValueError("BatchPlanner.plan_dev: max_attempts must be >= 1")
         counter = counter_rng.check_jitter(jitter, "BatchPlanner.plan_dev")
-        ids_dev = None
-        if counter and isinstance(stream_ids, torch.Tensor):
-            if stream_ids.dtype != torch.int32 or stream_ids.device != head.device or stream_ids.numel() != B or \
-                    not stream_ids.is_contiguous():
-                raise ValueError("BatchPlanner.plan_dev: a device stream_ids is a contiguous int32 tensor, one id per request")
-            ids_dev = stream_ids
-        else:
-            stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
-            if stream_ids.shape[0] != B:
-                raise ValueError("BatchPlanner.plan_dev: stream_ids needs one id per request")
-        if counter:         # (before any device use)
-            if seed is not None:
-                seed = counter_rng.check_seed(seed, "BatchPlanner.plan_dev")
-            if ids_dev is None:
-                stream_ids = counter_rng.check_ids(stream_ids, "BatchPlanner.plan_dev").astype(np.int32)
+        stream_ids, ids_dev, seed = self._plan_dev_streams(stream_ids, head, counter, seed)
         if bufs is not None and (bufs["B"] < B or bufs["D"] != D or bufs["M"] != M):
             raise ValueError("BatchPlanner.plan_dev: bufs were made for another B, D or number of waypoints")
         self._sync()
@@ -997,6 +1133,128 @@ class BatchPlanner:
         if bad_scene:
             raise _lib.NeoError("BatchPlanner.plan_dev: a request names a scene without a map (NEO_TRAJ_BAD_SCENE)")
         d["launch_sizes"] = launches
+        return bufs
+
+    def _plan_dev_adaptive(self, map, head, tail, bufs, slots, subset, x, solved, max_attempts, seed, rng, stream_ids, jitter,
+                           max_waypoints):
+        """plan_dev(waypoints="adaptive"): `_plan_adaptive`'s arrays bit for bit on resident tensors.  neo_adaptive_count_dev
+        gives the launched requests their counts, neo_adaptive_bucket_dev groups the launch list by count, and the host
+        waits ONCE to read the group table.  The chain is attempt-major: in an attempt every non-empty group, longest
+        first, gets its guess, its effort order above 1024 rows, its optimiser launch with M = count + 1 and
+        neo_adaptive_merge_dev -- on rows of the packed arrays that start where the group's segment of the list starts,
+        all on the context's stream, no wait in between -- then ONE neo_adaptive_compact_dev packs every group's failed
+        requests to the front of its segment.  The host waits once per attempt and reads the table (the groups' failed
+        counts, the bad-scene word).  jitter="counter": neo_plan_jitter_dev per group over its failed segment, no list is
+        read; jitter="numpy": the failed lists are read and `retry_noise` drawn per group.
+        Results in `bufs` (plan_buffers(..., waypoints="adaptive")): x (B, n_max) ragged with NaN behind a request's own
+        values, counts, clamped (int32), the arrays of plan_dev, launch_sizes (requests per attempt over all groups),
+        group_launch_sizes {count: sizes per attempt} and host_waits {"grouping": 1, "attempts": waits that followed an
+        attempt}.  `x` / `solved` / `subset` as in plan_dev (`x`: rows of n_max)."""
+        import torch
+        seg = self._adaptive_args(max_waypoints, "BatchPlanner.plan_dev")
+        W = int(max_waypoints)
+        B, D = head.shape[0], head.shape[2]
+        n_max = D * W + W + 1
+        if max_attempts < 1:
+            raise ValueError("BatchPlanner.plan_dev: max_attempts must be >= 1")
+        counter = counter_rng.check_jitter(jitter, "BatchPlanner.plan_dev")
+        stream_ids, ids_dev, seed = self._plan_dev_streams(stream_ids, head, counter, seed)
+        if bufs is not None and (not bufs.get("adaptive") or bufs["B"] < B or bufs["D"] != D or bufs["max_waypoints"] != W):
+            raise ValueError("BatchPlanner.plan_dev: bufs were not made for waypoints='adaptive' with this B, D and max_waypoints")
+        if x is not None and (x.ndim != 2 or x.shape[1] != n_max):
+            raise ValueError("BatchPlanner.plan_dev: x (B, D * max_waypoints + max_waypoints + 1) with waypoints='adaptive'")
+        self._sync()
+        c = self.ctx
+        dev = head.device
+        if bufs is None:
+            bufs = self.plan_buffers(B, dev, D=D, waypoints="adaptive", max_waypoints=W)
+            torch.cuda.synchronize(dev)     # (the context has its own stream: the buffers are ready before it starts)
+        d = bufs
+        if seed is None:
+            seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
+        p = _lib.dev_ptr
+        if counter and ids_dev is None and max_attempts > 1:
+            ids_dev = torch.from_numpy(stream_ids).to(dev)      # (a blocking copy: there before the context's stream starts)
+        out_x, out_solved = (x if x is not None else d["x"]), (solved if solved is not None else d["solved"])
+        G = _lib.NEO_MAX_PIECES
+        table = d["table"]      # bucket_begin [G + 1], the groups' failed counts [G], the bad-scene word, the total
+        n_failed, bad = table[G + 1:], table[2 * G + 1:]
+        if _lib.launch_count(subset, B) == 0:       # (an empty list: nothing to count, nothing to wait for)
+            d.update(launch_sizes=[], group_launch_sizes={}, host_waits=dict(grouping=0, attempts=0))
+            return bufs
+        rows = lambda t, first, per=1: p(t.view(-1)[first * per:])   # a packed array from row `first` on
+        c.check(c.lib.neo_adaptive_count_dev(c.h, B, p(subset), _lib.launch_count(subset, B), D, p(head), p(tail), seg, W,
+                                             p(d["counts"]), p(d["clamped"])))
+        c.check(c.lib.neo_adaptive_bucket_dev(c.h, B, p(subset), _lib.launch_count(subset, B), p(d["counts"]),
+                                              p(d["group_order"]), p(table), p(table[2 * G + 2:])))
+        c.synchronize()
+        begin = table[:G + 1].tolist()
+        seg_begin = np.asarray(begin[:G], dtype=np.int32)
+        seg_len = np.diff(np.asarray(begin, dtype=np.int32)).astype(np.int32)
+        lists = d["group_order"]
+        launches, by_group, waits, frac_tau = [], {}, 0, {}
+        bad_scene = 0
+        c.check(c.lib.neo_optimize_progress_counter(c.h, None))
+        try:
+            for attempt in range(max_attempts):
+                if attempt > 0:
+                    c.synchronize()
+                    waits += 1
+                    words = table[G + 1:2 * G + 2].tolist()
+                    seg_len, bad_scene = np.asarray(words[:G], dtype=np.int32), words[G]
+                    lists = d["todo"][(attempt - 1) % 2]
+                groups = [g for g in range(G - 1, 0, -1) if seg_len[g] > 0]      # the longest M first
+                if bad_scene or not groups:
+                    break
+                if attempt > 0 and not counter:
+                    for g in groups:
+                        o, P = int(seg_begin[g]), int(seg_len[g])
+                        ids = lists[o:o + P].cpu().numpy()
+                        noise = self.retry_noise(seed, stream_ids[ids], attempt, D, g)
+                        d["noise"].view(-1)[o * D * W:o * D * W + P * D * g].copy_(torch.from_numpy(noise.reshape(-1)))
+                    torch.cuda.synchronize(dev)
+                pending = d["todo"][attempt % 2]
+                for k, g in enumerate(groups):
+                    o, P, M = int(seg_begin[g]), int(seg_len[g]), g + 1
+                    sub = rows(lists, o)
+                    x_k, head_k, tail_k = rows(d["x_k"], o, n_max), rows(d["head_k"], o, 3 * D), rows(d["tail_k"], o, 3 * D)
+                    slots_k = rows(d["slots_k"], o) if slots is not None else None
+                    noise_k = rows(d["noise"], o, D * W)
+                    res_k = (rows(d["costs_k"], o, 4), rows(d["last_k"], o, 4), rows(d["nit_k"], o), rows(d["nfev_k"], o),
+                             rows(d["status_k"], o))
+                    if g not in frac_tau:
+                        frac_tau[g] = self._plan_frac_tau(g)
+                    frac, tau = frac_tau[g]
+                    if attempt > 0 and counter:
+                        c.check(c.lib.neo_plan_jitter_dev(c.h, B, sub, P, M, D, seed, attempt, p(ids_dev), noise_k))
+                    c.check(c.lib.neo_plan_guess_dev(c.h, B, sub, P, M, D, p(head), p(tail), p(slots), None,
+                                                     noise_k if attempt > 0 else None, _lib.ptr(frac), _lib.ptr(tau), x_k,
+                                                     head_k, tail_k, slots_k))
+                    if P > 1024:
+                        order = rows(d["order"], o)
+                        c.check(c.lib.neo_effort_order_dev(c.h, P, M, D, x_k, head_k, tail_k, p(d["order_scratch"]), order))
+                        c.check(c.lib.neo_optimize_dispatch_order(c.h, order, P))
+                    else:
+                        c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))
+                    c.check(c.lib.neo_optimize_batch_from_dev(c.h, map.scene_id, slots_k, P, M, D, x_k, x_k, head_k, tail_k,
+                                                              *res_k))
+                    c.check(c.lib.neo_adaptive_merge_dev(c.h, B, sub, P, M, D, n_max, int(attempt == 0),
+                                                         int(attempt == 0 and k == 0), x_k, *res_k, p(out_x), p(d["costs"]),
+                                                         p(d["costs_last"]), p(d["nit"]), p(d["nfev"]), p(d["status"]),
+                                                         p(d["attempts"]), p(d["nit_total"]), p(out_solved), rows(pending, o),
+                                                         p(bad)))
+                    by_group.setdefault(g, []).append(P)
+                c.check(c.lib.neo_adaptive_compact_dev(c.h, _lib.ptr(seg_begin), _lib.ptr(seg_len), p(pending), p(n_failed)))
+                launches.append(int(seg_len.sum()))
+            else:
+                c.synchronize()     # (every attempt has run: the last one's wait)
+                waits += 1
+                bad_scene = int(table[2 * G + 1].item())
+        finally:
+            c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))     # (the order is in bufs: no launch after this reads it)
+        if bad_scene:
+            raise _lib.NeoError("BatchPlanner.plan_dev: a request names a scene without a map (NEO_TRAJ_BAD_SCENE)")
+        d.update(launch_sizes=launches, group_launch_sizes=by_group, host_waits=dict(grouping=1, attempts=waits))
         return bufs
 
     # ------------------------------------------------------------ the reference's `batch` mode (:103-168) for B requests
