@@ -477,6 +477,41 @@ int neo_fleet_splice_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subse
                          const double *head, const double *tail, const int32_t *solved, double hz, int first,
                          double *cmd, int cap, int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index,
                          int32_t *flags);
+/* ---- fleet mode "warmstart" (ros_node/traj_planner_node.py:570-571, :597-611) ----
+ * The reference's `selected_planner:=warmstart` starts every replan from the previous plan: its waypoints, carried along
+ * relative to the planning start state, and the durations the planner last held.  Per mission, caller-owned DEVICE
+ * buffers indexed by MISSION:
+ *   wpts_local[B][2][M - 1]   the last SOLVED plan's waypoints minus the position that plan started from (head[b][0]);
+ *   ts_carry[B][M]            the durations the planner last held.
+ * x rows are a plan's [x_0 .. x_{M-2}, y_0 .. y_{M-2}, tau_0 .. tau_{M-1}], n = 2 (M - 1) + M doubles.  D = 2, fp64, one
+ * lane per mission, one launch each.  Device pointers only, asynchronous on the context's stream.  `subset` (n_subset
+ * mission indices, a device array) names the missions launched, NULL = all B; an index outside 0 .. B - 1 is skipped
+ * and its rows stay.  A mission's values depend on neither B, the subset nor its position.  T_min, T_max: the context's
+ * parameters.  Sums, differences and quotients only, each rounded on its own.
+ * NEO_ERR_INVALID before any launch, with a neo_last_error message: B < 1, a bad subset size, M outside 2 .. 64, a NULL
+ * buffer. */
+/* the first guess of a replan: x0[b] (x0[B][n], what neo_plan_guess_dev takes as x_init) from what mission b carries,
+ *   x0[b][d (M - 1) + k] = wpts_local[b][d][k] + head[b][0][d]      -- NumPy's bits;
+ *   tau_k = -log((T_max - T_min) / (ts_carry[b][k] - T_min) - 1)    -- map_T2tau, the device's fp64 log.
+ * Where the reference's map_T2tau raises -- ts_carry - T_min is not > 0, or the log's argument is not > 0 (a duration
+ * that saturated to T_min or T_max: |tau| beyond about 37) -- and for a NaN duration, tau_k is NaN: the optimiser ends
+ * that attempt NEO_TRAJ_NONFINITE at its first evaluation, uncounted, and the plan chain re-seeds it from the straight
+ * line, as the reference does when warm_start_plan catches the exception. */
+int neo_fleet_warm_guess_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, const double *head,
+                             const double *wpts_local, const double *ts_carry, double *x0);
+/* what the launched missions keep of a target round's plan: x[B][n] the plan, head[B][3][2] the state it started from,
+ * solved[B], status[B] (NEO_TRAJ_* | NEO_TRAJ_FLAG_COLLISION of the last attempt) and attempts[B] as neo_plan_merge_dev
+ * leaves them; init_ts: a HOST array [M], the start durations of a re-seeded attempt (init_T * [1.5, 1, ..., 1, 1.5]).
+ *   solved[b] != 0:   wpts_local[b][d][k] = x[b][d (M - 1) + k] - head[b][0][d]   -- NumPy's bits;
+ *                     ts_carry[b][k] = (T_max - T_min) / (1 + exp(-tau_k)) + T_min -- map_tau2T, the device's fp64 exp;
+ *   solved[b] == 0:   wpts_local[b] stays (the reference raises before :570).  ts_carry[b] is map_tau2T of x[b]'s tau when
+ *                     the last attempt ran to an answer ((status & 0xff) <= NEO_TRAJ_MAXITER: its collision was too
+ *                     large); when it raised instead ((status & 0xff) >= NEO_TRAJ_NUMERIC_RANGE) ts_carry[b] is that
+ *                     attempt's START durations: init_ts with attempts[b] > 1, unchanged with attempts[b] == 1.
+ * exp(-tau) overflows to +inf and gives T_min, as it does to rounding from -tau = 37 on; a NaN tau gives NaN. */
+int neo_fleet_warm_carry_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, int M, const double *x,
+                             const double *head, const int32_t *solved, const int32_t *status, const int32_t *attempts,
+                             const double *init_ts, double *wpts_local, double *ts_carry);
 /* get_weighted_metric (:333-363) over what was FLOWN, one wavefront per mission: the samples are rows 0, stride,
  * 2 stride, ... < n_flown[b] of cmd[b] (stride = cmd_hz * metric_eva_interval: 6 at the reference's 60 Hz and 0.1 s;
  * n_flown = the final cmd_index + 1, or cmd_len for a mission flown to its end; values outside 0 .. cap are clamped).

@@ -1576,6 +1576,40 @@ int neo_fleet_splice_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset,
                                   {M, x, head, tail, solved, hz, first ? 1 : 0, flags}));
 }
 
+// mode "warmstart": the state a mission carries from one plan to the next
+static int fleet_warm_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M) {
+  int rc = list_check(c, who, B, 1, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  if (M < 2 || M > NEO_MAX_PIECES) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": M must be in 2 .. 64").c_str());
+  return NEO_OK;
+}
+
+int neo_fleet_warm_guess_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, const double *head,
+                             const double *wpts_local, const double *ts_carry, double *x0) {
+  int rc = fleet_warm_check(c, "fleet warm guess", B, subset, n_subset, M);
+  if (rc) return rc;
+  if (!head || !wpts_local || !ts_carry || !x0) return fail_locked(c, NEO_ERR_INVALID, "fleet warm guess: null buffer");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, fleet_warm_guess(c, list, M, head, wpts_local, ts_carry, x0));
+}
+
+int neo_fleet_warm_carry_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, const double *x,
+                             const double *head, const int32_t *solved, const int32_t *status, const int32_t *attempts,
+                             const double *init_ts, double *wpts_local, double *ts_carry) {
+  int rc = fleet_warm_check(c, "fleet warm carry", B, subset, n_subset, M);
+  if (rc) return rc;
+  if (!x || !head || !solved || !status || !attempts || !init_ts || !wpts_local || !ts_carry)
+    return fail_locked(c, NEO_ERR_INVALID, "fleet warm carry: null buffer");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, fleet_warm_carry(c, list, {M, x, head, solved, status, attempts, init_ts, wpts_local, ts_carry}));
+}
+
 static int fleet_audit_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
                              const int32_t *n_flown, int stride, double cmd_hz, const double *audit, const int32_t *count,
                              const int32_t *flags) {

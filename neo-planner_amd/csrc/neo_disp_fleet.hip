@@ -35,6 +35,21 @@ int fleet_pose(neo_ctx *c, const LaunchList &l, const FleetCmd &m, const double 
   return NEO_OK;
 }
 
+int fleet_warm_guess(neo_ctx *c, const LaunchList &l, int M, const double *head, const double *wpts_local,
+                     const double *ts_carry, double *x0) {
+  hipLaunchKernelGGL(fleet_warm_guess_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l, M, c->params.T_min,
+                     c->params.T_max, head, wpts_local, ts_carry, x0);
+  return NEO_OK;
+}
+
+int fleet_warm_carry(neo_ctx *c, const LaunchList &l, const FleetWarmCarryArgs &a) {
+  WarmInitTs ts{};
+  for (int k = 0; k < a.M; ++k) ts.v[k] = a.init_ts[k];
+  hipLaunchKernelGGL(fleet_warm_carry_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l, a.M, c->params.T_min,
+                     c->params.T_max, a.x, a.head, a.solved, a.status, a.attempts, ts, a.wpts_local, a.ts_carry);
+  return NEO_OK;
+}
+
 int fleet_splice(neo_ctx *c, const LaunchList &l, const FleetCmd &m, const FleetSpliceArgs &a) {
   hipLaunchKernelGGL(fleet_splice_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.M, c->dev, a.x, a.head, a.tail,
                      a.solved, a.hz, a.first, m.cmd, m.cap, m.cmd_len, m.cmd_index, m.future_index, a.flags);

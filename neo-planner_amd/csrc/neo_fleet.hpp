@@ -5,6 +5,8 @@
 //   fleet_jitter_kernel    the re-targeting's N(0, 1) draws (:469) on the device (neo_counter_rng.hpp)   one lane per mission
 //   fleet_advance_kernel   perfect tracking + get_drone_state_ahead (:527-537)   one lane per mission
 //   fleet_pose_kernel      the camera pose a mission senses from (:685-687)          one lane per mission
+//   fleet_warm_guess_kernel  the previous plan as the next one's first guess (:597-611)   one lane per mission
+//   fleet_warm_carry_kernel  what a mission keeps of a plan for that (:570-571)           one lane per mission
 //   fleet_splice_kernel    the splice of replan   (:574-578, first_plan :515-519)   one wavefront per mission
 //   fleet_audit_kernel     get_weighted_metric    (:333-363) over the flown rows   one wavefront per mission
 //
@@ -190,6 +192,75 @@ __global__ __launch_bounds__(kFleetThreads) void fleet_advance_kernel(
   hd[2] = fr[2];
   hd[3] = fr[3];
   hd[4] = hd[5] = 0.0;  // the reference hands plan() a 2 x 2 state (:534-535)
+}
+
+// ---- mode "warmstart": what a mission carries from one plan to the next (:570-571, :597-611).  Per mission
+// wpts_local[2][M - 1], the last solved plan's waypoints minus the position that plan started from, and ts_carry[M], the
+// durations the planner last held.  A mission's x row is [x_0 .. x_{M-2}, y_0 .. y_{M-2}, tau_0 .. tau_{M-1}].
+// Differences, sums and quotients only, each rounded on its own: no product meets a sum, so nothing here can contract.
+struct WarmInitTs {  // the re-seeded attempts' start durations init_T * [1.5, 1, ..., 1, 1.5], handed over by value
+  double v[NEO_MAX_PIECES];
+};
+
+// x0[b] = the carried plan seen from head[b]'s position, and map_T2tau (:468-475) of the carried durations.  Where the
+// reference's map_T2tau raises (t - T_min not > 0, the log's argument not > 0) or the duration is NaN, tau is NaN: the
+// optimiser ends that attempt NEO_TRAJ_NONFINITE at its first evaluation and the plan chain re-seeds it.
+__global__ __launch_bounds__(kFleetThreads) void fleet_warm_guess_kernel(
+    LaunchList list, int M, double T_min, double T_max, const double *__restrict__ head,
+    const double *__restrict__ wpts_local, const double *__restrict__ ts_carry, double *__restrict__ x0) {
+#pragma clang fp contract(off)
+  const int b = list.request(blockIdx.x * kFleetThreads + threadIdx.x);
+  if (b < 0) return;
+  const int count = M - 1;
+  const double *hd = head + (size_t)b * kFleetRow;
+  const double *wl = wpts_local + (size_t)b * kFleetD * count;
+  const double *tc = ts_carry + (size_t)b * M;
+  double *x = x0 + (size_t)b * (kFleetD * count + M);
+  const double px = hd[0], py = hd[1];
+  for (int k = 0; k < count; ++k) {
+    x[k] = wl[k] + px;
+    x[count + k] = wl[count + k] + py;
+  }
+  const double span = T_max - T_min;
+  double *tau = x + kFleetD * count;
+  for (int k = 0; k < M; ++k) {
+    const double dt = tc[k] - T_min;
+    const double arg = span / dt - 1.0;
+    tau[k] = (dt > 0.0 && arg > 0.0) ? -log(arg) : __builtin_nan("");  // (a NaN duration compares false)
+  }
+}
+
+// After a target round's plan call.  Solved: both carries from the plan x[b].  Not solved: the waypoints stay (the
+// reference raises before :570); the durations are map_tau2T (:477-483) of the last attempt's answer when it ran to one
+// ((status & 0xff) <= NEO_TRAJ_MAXITER: the collision was too large), and that attempt's START durations when it
+// raised instead -- init_ts for a re-seeded attempt (attempts > 1), what they were for the first.
+__global__ __launch_bounds__(kFleetThreads) void fleet_warm_carry_kernel(
+    LaunchList list, int M, double T_min, double T_max, const double *__restrict__ x, const double *__restrict__ head,
+    const int *__restrict__ solved, const int *__restrict__ status, const int *__restrict__ attempts, WarmInitTs init_ts,
+    double *__restrict__ wpts_local, double *__restrict__ ts_carry) {
+#pragma clang fp contract(off)
+  const int b = list.request(blockIdx.x * kFleetThreads + threadIdx.x);
+  if (b < 0) return;
+  const int count = M - 1;
+  const double *xr = x + (size_t)b * (kFleetD * count + M);
+  double *tc = ts_carry + (size_t)b * M;
+  const bool ok = solved[b] != 0;
+  if (ok) {
+    const double *hd = head + (size_t)b * kFleetRow;
+    double *wl = wpts_local + (size_t)b * kFleetD * count;
+    const double px = hd[0], py = hd[1];
+    for (int k = 0; k < count; ++k) {
+      wl[k] = xr[k] - px;
+      wl[count + k] = xr[count + k] - py;
+    }
+  }
+  if (ok || (status[b] & 0xff) <= NEO_TRAJ_MAXITER) {
+    const double span = T_max - T_min;
+    const double *tau = xr + kFleetD * count;
+    for (int k = 0; k < M; ++k) tc[k] = span / (1.0 + exp(-tau[k])) + T_min;
+  } else if (attempts[b] > 1) {
+    for (int k = 0; k < M; ++k) tc[k] = init_ts.v[k];
+  }
 }
 
 // The solve and the rows are traj_state_kernel's (neo_abi.hip) through audit_sample_state, its expressions written out

@@ -248,6 +248,18 @@ int fleet_audit(neo_ctx *c, const LaunchList &l, const MapRef &m, const FleetAud
 // the missions' camera poses (eye x y z, cos, sin) from where they are on their command arrays
 int fleet_pose(neo_ctx *c, const LaunchList &l, const FleetCmd &m, const double *cur_pos, const double *goal, double eye_z,
                double *pose);
+// mode "warmstart": the carried plan as x0 [B][n], and what a mission keeps of a target round's plan.  T_min, T_max: the
+// context's; init_ts: a HOST array of M durations, handed to the kernel by value
+struct FleetWarmCarryArgs {
+  int M;
+  const double *x, *head;                 // [B][n], [B][3][2] by mission
+  const int *solved, *status, *attempts;  // [B]: plan_dev's
+  const double *init_ts;                  // host
+  double *wpts_local, *ts_carry;          // [B][2][M - 1], [B][M]
+};
+int fleet_warm_guess(neo_ctx *c, const LaunchList &l, int M, const double *head, const double *wpts_local,
+                     const double *ts_carry, double *x0);
+int fleet_warm_carry(neo_ctx *c, const LaunchList &l, const FleetWarmCarryArgs &a);
 
 // neo_record_*_dev: the fleet's `record` mode (neo_disp_record.hip, kernels in neo_record.hpp).  Every pointer is a
 // device array; the arguments were checked by the C ABI.

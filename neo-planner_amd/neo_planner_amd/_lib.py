@@ -62,6 +62,7 @@ EXPORTS = [
     "neo_plan_jitter", "neo_plan_jitter_dev", "neo_fleet_jitter", "neo_fleet_jitter_dev",
     "neo_adaptive_count", "neo_adaptive_count_dev", "neo_adaptive_bucket", "neo_adaptive_bucket_dev",
     "neo_adaptive_merge_dev", "neo_adaptive_compact", "neo_adaptive_compact_dev",
+    "neo_fleet_warm_guess_dev", "neo_fleet_warm_carry_dev",
 ]
 
 
@@ -147,6 +148,8 @@ def load():
     L.neo_plan_jitter_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_i, ctypes.c_uint64, c_i, c_p, c_p]
     L.neo_fleet_jitter.argtypes = [c_p, c_i, c_p, c_i, ctypes.c_uint64, c_i, c_i, c_p, c_p]
     L.neo_fleet_jitter_dev.argtypes = [c_p, c_i, c_p, c_i, ctypes.c_uint64, c_i, c_i, c_p, c_p]
+    L.neo_fleet_warm_guess_dev.argtypes = [c_p, c_i, c_p, c_i, c_i] + [c_p] * 4
+    L.neo_fleet_warm_carry_dev.argtypes = [c_p, c_i, c_p, c_i, c_i] + [c_p] * 8
     L.neo_adaptive_count.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p]
     L.neo_adaptive_count_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p]
     L.neo_adaptive_bucket.argtypes = [c_p, c_i, c_p, c_i] + [c_p] * 4

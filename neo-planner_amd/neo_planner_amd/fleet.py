@@ -41,6 +41,16 @@ missions' pose, velocity, look-ahead state, target and features into the residen
 context's stream, csrc/neo_init.hpp).  "neo" hands it to plan_dev as attempt 0's start; "nn" splices it as it is, without
 an optimiser launch.  Both imply resident plans and work with onboard and record.
 
+Mode "warmstart" starts every replan from the previous plan (the reference's `selected_planner:=warmstart`, :493,
+:570-571, :597-611).  A mission's first plan, re-targeted repeats included, is a basic plan.  From then on every mission
+carries two resident rows: the last SOLVED plan's waypoints relative to the position that plan started from, and the
+durations the planner last held.  Before a plan call neo_fleet_warm_guess_dev moves the waypoints to the new look-ahead
+position and maps the durations to tau -- the first guess plan_dev takes as attempt 0's start; after every plan call, in
+front of the splice, neo_fleet_warm_carry_dev keeps what the round's missions carry on (csrc/neo_fleet.hpp).  A carried
+duration the reference's map_T2tau raises for (one saturated to T_min or T_max) gives a NaN tau: that attempt ends at its
+first evaluation, uncounted, and plan_dev re-seeds from the straight line, as warm_start_plan does when it catches the
+exception.  Resident plans always; works with onboard, record and both jitter settings; no host read is added.
+
 A mission's flight does not depend on which other missions share the fleet: the kernels work per mission, the target
 jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
 retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream_ids`).  With jitter="counter" both come
@@ -82,9 +92,9 @@ def plan_seed(seed, tick, target):
 class FleetReplanLoop:
     """`ReplanLoop` for B missions at once.  goals (B, 2); `map` one 2-D ESDF for all missions, or any of the maps plus
     scene_ids (B,) of per-mission scene ids (as BatchPlanner.optimize).  mode "basic" (BatchPlanner.plan), "geo"
-    (geo_plan: the A* warm start) or "batch" (batch_plan: the cheapest feasible of three lateral candidates, on the
-    device).  mission_ids (B,): the ids the random streams are keyed by (None: 0 .. B - 1) -- a mission flown alone with
-    its id flies as it does in the fleet.  max_cmd_seconds sizes the resident command arrays
+    (geo_plan: the A* warm start), "batch" (batch_plan: the cheapest feasible of three lateral candidates, on the
+    device), "neo" / "nn" or "warmstart" (below).  mission_ids (B,): the ids the random streams are keyed by
+    (None: 0 .. B - 1) -- a mission flown alone with its id flies as it does in the fleet.  max_cmd_seconds sizes the resident command arrays
     (cap = max_cmd_seconds * cmd_hz rows a mission); a mission whose array fills up ends as not reached.
     resident=True (modes "basic" and "batch"): the plans run through BatchPlanner.plan_dev on the resident arrays --
     the same flights; head, tail and x no longer pass through the host.
@@ -102,6 +112,9 @@ class FleetReplanLoop:
     network's guess, or the guess flown as it is; scenes / scene_index as for onboard; resident plans always.  The
     network's camera renders its own images (a third render with onboard and record set).  `x` is a host copy of the
     resident plan array.
+    mode "warmstart": every replan starts from the mission's previous plan -- its waypoints carried along relative to the
+    planning start state, the durations the planner last held (BatchPlanner.warm_guess_dev / warm_carry_dev around
+    plan_dev); the first plan is a basic plan; resident plans always; with onboard, record and either jitter.
     jitter "numpy" (one NumPy generator per mission and draw, on the host) or "counter" (every mode, resident or not): the
     target jitter of a round is drawn by neo_fleet_jitter_dev on the context's stream in front of the target kernel, and
     every plan call gets jitter="counter"; mission ids in 0 .. 2^31 - 1 and a seed in 0 .. 2^64 - 1."""
@@ -112,8 +125,8 @@ class FleetReplanLoop:
                  scene_index=None, des_pos_z=2.0, record_poses=False, record=None, neo=None, jitter="numpy"):
         self.counter = counter_rng.check_jitter(jitter, "FleetReplanLoop")
         self.jitter = jitter
-        if mode not in ("basic", "geo", "batch", "neo", "nn"):
-            raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo', 'batch', 'neo' or 'nn'")
+        if mode not in ("basic", "geo", "batch", "neo", "nn", "warmstart"):
+            raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo', 'batch', 'neo', 'nn' or 'warmstart'")
         learned = mode in ("neo", "nn")
         if learned:
             if neo is None:
@@ -128,6 +141,8 @@ class FleetReplanLoop:
                                  % (cam.height, cam.width, net.img_height, net.img_width))
             if scenes is None:
                 raise ValueError("FleetReplanLoop: modes 'neo' and 'nn' need scenes=(boxes, box_begin), what the cameras see")
+            resident = True
+        if mode == "warmstart":      # the carried plan lives on the device: resident plans always
             resident = True
         if resident and mode == "geo":
             raise ValueError("FleetReplanLoop: resident=True needs mode 'basic' or 'batch' (geo_plan has no resident form)")
@@ -315,6 +330,9 @@ class FleetReplanLoop:
         if self.onboard is not None:
             self.onboard.reset()      # all unknown, and the slots as the map table numbers them now
             self._dev.update(plan_slots=self.onboard.slots)
+        if self.mode == "warmstart":      # what a mission carries from one plan to the next, and the guess made of it
+            M = (n + 2) // 3
+            self._dev.update(wpts_local=f(B, 2, M - 1), ts_carry=f(B, M), x0=f(B, n))
         if self.neo is not None:      # the network's inputs that are not the plan's own: velocity now, image features
             self._dev.update(cur_vel=f(B, 2), feature=torch.zeros((B, 24), dtype=torch.float32, device=dev))
         if self.onboard is not None or self.record is not None or self.neo is not None:      # what the cameras see, and where from
@@ -362,6 +380,23 @@ class FleetReplanLoop:
             self._sync()
         x0 = self.neo.warm_start_dev(d["pose"], d["cur_vel"], d["head"], d["tail"], d["feature"], subset=sub, x0=d["x0"])
         return self._plan_resident(sub, pending, tick, r, x0=x0)
+
+    def _plan_warm(self, sub, pending, tick, r):
+        """mode "warmstart": the first plan of a mission (tick 0, and its re-targeted repeats) is a basic plan; every
+        later one starts from what the mission carries -- neo_fleet_warm_guess_dev writes the resident x0 on the context's
+        stream, plan_dev takes it as attempt 0's start"""
+        d = self._dev
+        if tick == 0:
+            return self._plan_resident(sub, pending, tick, r)
+        x0 = self.bp.warm_guess_dev(d["head"], d["wpts_local"], d["ts_carry"], d["x0"], subset=sub)
+        return self._plan_resident(sub, pending, tick, r, x0=x0)
+
+    def _warm_carry(self, sub):
+        """mode "warmstart": what the round's missions keep of the plan call just made (neo_fleet_warm_carry_dev, on the
+        context's stream, in front of the splice); status and attempts are plan_dev's"""
+        d, pb = self._dev, self._plan_bufs()
+        self.bp.warm_carry_dev(d["x"], d["head"], d["solved"], pb["status"], pb["attempts"], d["wpts_local"], d["ts_carry"],
+                               subset=sub)
 
     def _plan_nn(self, sub, pending, tick, r):
         """mode "nn" (the reference's selected_planner:=nn): the network's guess straight into the resident x, solved = 1
@@ -495,6 +530,8 @@ class FleetReplanLoop:
                     ok, nit_total, attempts = self._plan_neo(sub, pending, tick, r)
                 elif self.mode == "nn":
                     ok, nit_total, attempts = self._plan_nn(sub, pending, tick, r)
+                elif self.mode == "warmstart":
+                    ok, nit_total, attempts = self._plan_warm(sub, pending, tick, r)
                 elif self.resident:
                     ok, nit_total, attempts = self._plan_resident(sub, pending, tick, r)
                 else:
@@ -516,6 +553,8 @@ class FleetReplanLoop:
                     self._up("x", x)
                     self._up("solved", solved)
                 self._sync()
+                if self.mode == "warmstart":
+                    self._warm_carry(sub)
                 if self.record is not None:      # the round's rows, from the plans about to be spliced
                     self.record.commit(B, sub, d["x"], d["head"], d["tail"], d["solved"], d["pose"], d["mission_ids"], tick, r)
                 self._splice(sub, M, first=(tick == 0))

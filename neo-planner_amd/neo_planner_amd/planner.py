@@ -967,6 +967,38 @@ class BatchPlanner:
         ts[:, -1] *= 1.5
         return frac, np.ascontiguousarray(self.pack_x(np.zeros((1, 1, count)), ts)[0, count:])
 
+    def warm_guess_dev(self, head, wpts_local, ts_carry, x0, subset=None):
+        """the reference's `warmstart` planner on resident tensors (neo_fleet_warm_guess_dev, asynchronous on the
+        context's stream): x0 (B, n) float64, plan_dev's first guess, from what the requests carry -- wpts_local
+        (B, 2, M - 1), the last solved plan's waypoints relative to where that plan started, moved to head (B, 3, 2)'s
+        position, and ts_carry (B, M), the durations held, through map_T2tau; a duration map_T2tau raises for gives a NaN
+        tau, which plan_dev answers by re-seeding.  `subset`: an int32 tensor of request indices (None: all B).
+        Returns x0."""
+        self._sync()
+        B, M = int(ts_carry.shape[0]), int(ts_carry.shape[1])
+        if tuple(head.shape) != (B, 3, 2) or tuple(wpts_local.shape) != (B, 2, M - 1) or tuple(x0.shape) != (B, 3 * M - 2):
+            raise ValueError("BatchPlanner.warm_guess_dev: head (B, 3, 2), wpts_local (B, 2, M - 1), ts_carry (B, M), x0 (B, 3 M - 2)")
+        c, p = self.ctx, _lib.dev_ptr
+        c.check(c.lib.neo_fleet_warm_guess_dev(c.h, B, p(subset), _lib.launch_count(subset, B), M,
+                                               p(head), p(wpts_local), p(ts_carry), p(x0)))
+        return x0
+
+    def warm_carry_dev(self, x, head, solved, status, attempts, wpts_local, ts_carry, subset=None):
+        """what the requests keep of a plan call for the next warm start (neo_fleet_warm_carry_dev, asynchronous on the
+        context's stream): x (B, n) and head (B, 3, 2) of the call, solved, status and attempts (B,) int32 as plan_dev
+        leaves them, into wpts_local (B, 2, M - 1) and ts_carry (B, M).  A solved request keeps the plan's waypoints relative
+        to head's position and its durations; an unsolved one keeps its waypoints, and the durations of the last attempt's
+        answer or, where that attempt raised, its start durations (include/neo_planner.h)."""
+        self._sync()
+        B, M = int(ts_carry.shape[0]), int(ts_carry.shape[1])
+        if tuple(head.shape) != (B, 3, 2) or tuple(wpts_local.shape) != (B, 2, M - 1) or tuple(x.shape) != (B, 3 * M - 2):
+            raise ValueError("BatchPlanner.warm_carry_dev: x (B, 3 M - 2), head (B, 3, 2), wpts_local (B, 2, M - 1), ts_carry (B, M)")
+        c, p = self.ctx, _lib.dev_ptr
+        init_ts = self._batch_ts_tau(M - 1)[0]      # a re-seeded attempt's start durations: init_T * [1.5, 1, ..., 1, 1.5]
+        c.check(c.lib.neo_fleet_warm_carry_dev(c.h, B, p(subset), _lib.launch_count(subset, B), M,
+                                               p(x), p(head), p(solved), p(status), p(attempts), _lib.ptr(init_ts),
+                                               p(wpts_local), p(ts_carry)))
+
     def plan_buffers(self, B, device, D=2, waypoints=None, max_waypoints=63):
         """the resident arrays of `plan_dev` for up to B requests of dimension D with `waypoints` waypoints (None: the
         config's init_wpts_num): the packed work arrays of an attempt's launch, the two launch lists, and the

@@ -9,6 +9,10 @@ ros_node/traj_planner_node.py, with perfect tracking in place of PX4/Gazebo.
   try_local_planning/replan :421-448, :539-578             <= 11 re-targeted attempts, splice the new
                                                            command array at the look-ahead index
   first_plan                :490-525
+  mode "warmstart"          :493, :570-571, :597-611       the first plan is basic; every replan is
+                                                           warm_start_plan from the previous plan's waypoints,
+                                                           carried along relative to the planning start state,
+                                                           and the durations the planner last held
 
 Works with any planner object that has the reference's interface (`plan`, `batch_plan`,
 `get_full_state_cmd`, `int_wpts`, `ts`, `iter_num`): neo_planner_amd.MinJerkPlanner on the GPU, or the
@@ -41,6 +45,7 @@ class ReplanLoop:
         self.near_global_target = False
         self.des_state_index = 0
         self.n_plans = self.n_failed_attempts = 0
+        self.wpts_local = None      # mode "warmstart": the last plan's waypoints relative to where it started (count, 2)
 
     # ---- :450-488
     def set_local_target(self, current_pos, seed=0):
@@ -72,8 +77,13 @@ class ReplanLoop:
                 self.planner.batch_plan(self.map, start_2d, self.target_state)
             elif self.mode == "geo":      # :548-549: A* warm start from the look-ahead state (a GeoPlanner)
                 self.planner.geo_traj_plan(self.map, start, self.target_state)
-            else:
+            elif self.mode == "warmstart" and self.wpts_local is not None:      # :597-611: from the previous plan
+                self.planner.warm_start_plan(self.map, start_2d, self.target_state,
+                                             (self.wpts_local + start.global_pos[:2]).T, self.planner.ts)
+            else:      # (warmstart: the first plan, and its re-targeted repeats, are basic plans, :493)
                 self.planner.plan(self.map, start_2d, self.target_state)
+        if self.mode == "warmstart":      # :570-571, only reached without an exception
+            self.wpts_local = self.planner.int_wpts.T - start.global_pos[:2]
         self.n_plans += 1
 
     def _plan_with_retargeting(self, start_fn, current_pos):
