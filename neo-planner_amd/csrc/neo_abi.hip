@@ -1978,38 +1978,51 @@ int neo_plan_jitter(neo_ctx *c, int B, const int32_t *subset, int n_subset, int 
   return st.download();
 }
 
-static int plan_merge_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const PlanMergeArgs &a) {
-  int rc = plan_check(c, "plan merge", B, subset, n_subset, M, D);
+// the arrays of the three merge entry points as the launcher takes them (x in rows of n), their one check -- `compacts`:
+// n_failed is needed -- and the body of the two device ones: the merge, then with n_failed the compaction
+static PlanMergeArgs plan_merge_args(int M, int D, int reset, const double *x_k, const double *costs4_k, const double *costs4_last_k,
+                                     const int32_t *nit_k, const int32_t *nfev_k, const int32_t *status_k, double *x, double *costs4,
+                                     double *costs4_last, int32_t *nit, int32_t *nfev, int32_t *status, int32_t *attempts,
+                                     int64_t *nit_total, int32_t *solved, int32_t *failed, int32_t *n_failed, int32_t *bad_scene) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "nit_total is a 64-bit integer on both sides");
+  const int n = D * (M - 1) + M;
+  return {n, n, reset ? 1 : 0, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k}, {x, costs4, costs4_last, nit, nfev, status},
+          attempts, reinterpret_cast<long long *>(nit_total), solved, failed, n_failed, bad_scene};
+}
+
+static int plan_merge_check(neo_ctx *c, const std::string &who, int B, const int32_t *subset, int n_subset, int M, int D,
+                            const PlanMergeArgs &a, bool compacts) {
+  int rc = plan_check(c, who.c_str(), B, subset, n_subset, M, D);
   if (rc) return rc;
+  if (a.ldx < a.n) return fail_locked(c, NEO_ERR_INVALID, (who + ": x_stride must be >= n = D (M - 1) + M").c_str());
   const RunRowsIn &k = a.packed;
   const RunRows &o = a.out;
-  if (!k.x || !k.costs4 || !k.costs4_last || !k.nit || !k.nfev || !k.status || !o.x || !o.costs4 || !o.costs4_last ||
-      !o.nit || !o.nfev || !o.status || !a.attempts || !a.nit_total || !a.solved || !a.failed || !a.n_failed || !a.bad_scene)
-    return fail_locked(c, NEO_ERR_INVALID, "plan merge: null buffer");
+  if (!k.x || !k.costs4 || !k.costs4_last || !k.nit || !k.nfev || !k.status || !o.x || !o.costs4 || !o.costs4_last || !o.nit ||
+      !o.nfev || !o.status || !a.attempts || !a.nit_total || !a.solved || !a.failed || !a.bad_scene || (compacts && !a.n_failed))
+    return fail_locked(c, NEO_ERR_INVALID, (who + ": null buffer").c_str());
   return NEO_OK;
 }
 
-static_assert(sizeof(long long) == sizeof(int64_t), "nit_total is a 64-bit integer on both sides");
+static int plan_merge_dev(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M, int D,
+                          const PlanMergeArgs &a, bool compacts, bool clear_bad) {
+  if (int rc = plan_merge_check(c, who, B, subset, n_subset, M, D, a, compacts)) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (clear_bad) HIPCHK(c, hipMemsetAsync(a.bad_scene, 0, sizeof(int32_t), c->stream));
+  if (list.n > 0) return launched(c, plan_merge(c, list, a));
+  if (compacts) HIPCHK(c, hipMemsetAsync(a.n_failed, 0, sizeof(int32_t), c->stream));
+  return NEO_OK;
+}
 
 int neo_plan_merge_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int reset, const double *x_k,
                        const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
                        const int32_t *status_k, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
                        int32_t *status, int32_t *attempts, int64_t *nit_total, int32_t *solved, int32_t *failed,
                        int32_t *n_failed, int32_t *bad_scene) {
-  const PlanMergeArgs a{D * (M - 1) + M, reset ? 1 : 0, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k},
-                        {x, costs4, costs4_last, nit, nfev, status}, attempts, reinterpret_cast<long long *>(nit_total), solved,
-                        failed, n_failed, bad_scene};
-  int rc = plan_merge_check(c, B, subset, n_subset, M, D, a);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  HIPCHK(c, hipMemsetAsync(bad_scene, 0, sizeof(int32_t), c->stream));
-  if (list.n == 0) {
-    HIPCHK(c, hipMemsetAsync(n_failed, 0, sizeof(int32_t), c->stream));
-    return NEO_OK;
-  }
-  return launched(c, plan_merge(c, list, a));
+  const PlanMergeArgs a = plan_merge_args(M, D, reset, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4, costs4_last,
+                                          nit, nfev, status, attempts, nit_total, solved, failed, n_failed, bad_scene);
+  return plan_merge_dev(c, "plan merge", B, subset, n_subset, M, D, a, true, true);
 }
 
 int neo_plan_merge(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int reset, const double *x_k,
@@ -2017,10 +2030,9 @@ int neo_plan_merge(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M
                    const int32_t *status_k, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
                    int32_t *status, int32_t *attempts, int64_t *nit_total, int32_t *solved, int32_t *failed,
                    int32_t *n_failed, int32_t *bad_scene) {
-  const PlanMergeArgs a{D * (M - 1) + M, reset ? 1 : 0, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k},
-                        {x, costs4, costs4_last, nit, nfev, status}, attempts, reinterpret_cast<long long *>(nit_total), solved,
-                        failed, n_failed, bad_scene};
-  int rc = plan_merge_check(c, B, subset, n_subset, M, D, a);
+  const PlanMergeArgs a = plan_merge_args(M, D, reset, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4, costs4_last,
+                                          nit, nfev, status, attempts, nit_total, solved, failed, n_failed, bad_scene);
+  int rc = plan_merge_check(c, "plan merge", B, subset, n_subset, M, D, a, true);
   if (rc) return rc;
   const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n;
   if (P == 0) {
@@ -2157,24 +2169,11 @@ int neo_adaptive_merge_dev(neo_ctx *c, int B, const int32_t *subset, int n_subse
                            const int32_t *nit_k, const int32_t *nfev_k, const int32_t *status_k, double *x, double *costs4,
                            double *costs4_last, int32_t *nit, int32_t *nfev, int32_t *status, int32_t *attempts,
                            int64_t *nit_total, int32_t *solved, int32_t *pending, int32_t *bad_scene) {
-  int rc = adaptive_list_check(c, "adaptive merge", B, subset, n_subset);
-  if (rc) return rc;
-  rc = plan_check(c, "adaptive merge", B, subset, n_subset, M, D);
-  if (rc) return rc;
-  const int n = D * (M - 1) + M;
-  if (x_stride < n) return fail_locked(c, NEO_ERR_INVALID, "adaptive merge: x_stride must be >= n = D (M - 1) + M");
-  if (!x_k || !costs4_k || !costs4_last_k || !nit_k || !nfev_k || !status_k || !x || !costs4 || !costs4_last || !nit || !nfev ||
-      !status || !attempts || !nit_total || !solved || !pending || !bad_scene)
-    return fail_locked(c, NEO_ERR_INVALID, "adaptive merge: null buffer");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (clear_bad) HIPCHK(c, hipMemsetAsync(bad_scene, 0, sizeof(int32_t), c->stream));
-  if (list.n == 0) return NEO_OK;
-  const AdaptiveMergeArgs a{n, x_stride, reset ? 1 : 0, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k},
-                            {x, costs4, costs4_last, nit, nfev, status}, attempts, reinterpret_cast<long long *>(nit_total),
-                            solved, pending, bad_scene};
-  return launched(c, adaptive_merge(c, list, a));
+  if (int rc = adaptive_list_check(c, "adaptive merge", B, subset, n_subset)) return rc;
+  PlanMergeArgs a = plan_merge_args(M, D, reset, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4, costs4_last,
+                                    nit, nfev, status, attempts, nit_total, solved, pending, nullptr, bad_scene);
+  a.ldx = x_stride;
+  return plan_merge_dev(c, "adaptive merge", B, subset, n_subset, M, D, a, false, clear_bad != 0);
 }
 
 static int adaptive_compact_check(neo_ctx *c, const int32_t *seg_begin, const int32_t *seg_len, long long rows,

@@ -5,9 +5,8 @@
 //
 //   adaptive_count_kernel     max(ceil(L / init_seg_len - 1), 1), clamped                one lane per request
 //   adaptive_bucket_kernel    the launch list as a stable counting sort by count         ONE workgroup
-//   adaptive_merge_kernel     plan_merge_kernel (neo_plan.hpp) for one group: the request-indexed x in rows of the
-//                             longest group's length, NaN behind the group's own          one wavefront per request
 //   adaptive_compact_kernel   batch_compact_kernel (neo_batch.hpp) per group's segment    one workgroup per group
+// A group's merge is the plan unit's plan_merge_kernel, with the row length of the longest group for x.
 //
 // Included by neo_disp_adaptive.hip only.  fp64, D = 2 or 3.  Request-indexed arrays are indexed by request b; packed
 // arrays by the request's position p in the launch list (neo_launch_list.hpp).  No atomics, no scratch.
@@ -141,44 +140,6 @@ __global__ __launch_bounds__(kBucketThreads) void adaptive_bucket_kernel(LaunchL
   }
 }
 
-// plan_merge_kernel's bookkeeping (neo_plan.hpp) for one group of a mixed chain.  The request-indexed x has rows of
-// `ldx` >= n doubles: the group's n values, then NaN.  `pending[p]` gets the request's index when it failed, -1
-// otherwise; adaptive_compact_kernel packs the groups' segments afterwards.  `bad_scene` as there: every wavefront
-// that sees a NEO_TRAJ_BAD_SCENE stores the same 1.
-__global__ __launch_bounds__(kWave) void adaptive_merge_kernel(LaunchList list, int n, int ldx, int reset, RunRowsIn packed,
-                                                               RunRows out, int *__restrict__ attempts,
-                                                               long long *__restrict__ nit_total, int *__restrict__ solved,
-                                                               int *__restrict__ pending, int *__restrict__ bad_scene) {
-  const int p = blockIdx.x;
-  const int lane = lane_id();
-  const int b = list.request(p);  // wave-uniform
-  if (b < 0) {
-    if (lane == 0 && p < list.size()) pending[p] = -1;
-    return;
-  }
-  const int st = packed.status[p], its = packed.nit[p];  // (wave-uniform loads, ahead of the stores)
-  double *xr = out.x + (size_t)b * ldx;
-  for (int i = lane; i < n; i += kWave) xr[i] = packed.x[(size_t)p * n + i];
-  for (int i = n + lane; i < ldx; i += kWave) xr[i] = __builtin_nan("");
-  if (lane < 4) {
-    out.costs4[(size_t)b * 4 + lane] = packed.costs4[(size_t)p * 4 + lane];
-    out.costs4_last[(size_t)b * 4 + lane] = packed.costs4_last[(size_t)p * 4 + lane];
-  }
-  if (lane == 0) {
-    out.status[b] = st;
-    out.nit[b] = its;
-    out.nfev[b] = packed.nfev[p];
-    const int code = st & 0xff;
-    const bool failed = (code > NEO_TRAJ_MAXITER && code != NEO_TRAJ_BAD_SCENE) || (st & NEO_TRAJ_FLAG_COLLISION);
-    const long long counted = code >= NEO_TRAJ_NUMERIC_RANGE ? 0 : its;
-    attempts[b] = reset ? 1 : attempts[b] + 1;
-    nit_total[b] = reset ? counted : nit_total[b] + counted;
-    solved[b] = failed ? 0 : 1;
-    pending[p] = failed ? b : -1;
-    if (code == NEO_TRAJ_BAD_SCENE) *bad_scene = 1;
-  }
-}
-
 // the groups' segments of `pending`, by value: group c owns pending[begin[c] .. begin[c] + len[c] - 1]
 struct AdaptiveSegs {
   int begin[kBuckets];
@@ -186,24 +147,13 @@ struct AdaptiveSegs {
 };
 
 // batch_compact_kernel (neo_batch.hpp) per segment: workgroup c packs the entries >= 0 of its group's segment to the
-// segment's front in the order of their positions -- a chunk is read whole, then written at or before the places it was
-// read from -- and writes their number to n_failed[c] (0 for an empty segment).
+// segment's front in the order of their positions (compact_in_place, neo_launch_list.hpp) and writes their number to
+// n_failed[c] (0 for an empty segment).
 __global__ __launch_bounds__(kAdaptiveThreads) void adaptive_compact_kernel(AdaptiveSegs segs, int *__restrict__ pending,
                                                                             int *__restrict__ n_failed) {
-  __shared__ RankLds<kAdaptiveThreads> ranks;
-  const int tid = threadIdx.x;
   const int c = blockIdx.x;
-  const int len = segs.len[c];  // workgroup-uniform
-  int *seg = pending + segs.begin[c];
-  if (tid == 0) ranks.base = 0;
-  __syncthreads();
-  for (int at = 0; at < len; at += kAdaptiveThreads) {
-    const int i = at + tid;
-    const int v = i < len ? seg[i] : -1;        // the chunk is read whole ...
-    const int rank = ordered_rank(v >= 0, ranks);
-    if (v >= 0) seg[rank] = v;                  // ... before any of it is written: rank <= i
-  }
-  if (tid == 0) n_failed[c] = ranks.base;
+  const int kept = compact_in_place<kAdaptiveThreads>(pending + segs.begin[c], segs.len[c]);  // workgroup-uniform
+  if (threadIdx.x == 0) n_failed[c] = kept;
 }
 
 }  // namespace neo

@@ -155,26 +155,16 @@ __global__ __launch_bounds__(kWave) void batch_select_kernel(
     pending[p] = pick >= 0 ? -1 : b;
   }
   if (pick < 0) return;  // x[b] and the other results of the request stay untouched
-  scatter_run_row(lane, n, packed, (size_t)p * K + pick, out, b);
+  scatter_run_row(lane, n, n, packed, (size_t)p * K + pick, out, b);
 }
 
 // pending[P] (a request index, or -1) -> its entries >= 0 packed to the front in the order of their positions, and
-// their number.  ONE workgroup walks the array in chunks of kCompactThreads with ordered_rank (neo_launch_list.hpp): a
-// chunk is read whole, then written at or before the places it was read from, so the packing is done in place and no
-// position depends on scheduling.  With an ascending subset (or none) the list is ascending.
+// their number.  ONE workgroup walks the array in chunks of kCompactThreads: compact_in_place (neo_launch_list.hpp).
+// With an ascending subset (or none) the list is ascending.
 __global__ __launch_bounds__(kCompactThreads) void batch_compact_kernel(int P, int *__restrict__ pending,
                                                                         int *__restrict__ n_pending) {
-  __shared__ RankLds<kCompactThreads> ranks;
-  const int tid = threadIdx.x;
-  if (tid == 0) ranks.base = 0;
-  __syncthreads();
-  for (int at = 0; at < P; at += kCompactThreads) {
-    const int i = at + tid;
-    const int v = i < P ? pending[i] : -1;      // the chunk is read whole ...
-    const int rank = ordered_rank(v >= 0, ranks);
-    if (v >= 0) pending[rank] = v;              // ... before any of it is written: rank <= i
-  }
-  if (tid == 0) *n_pending = ranks.base;
+  const int kept = compact_in_place<kCompactThreads>(pending, P);
+  if (threadIdx.x == 0) *n_pending = kept;
 }
 
 }  // namespace neo

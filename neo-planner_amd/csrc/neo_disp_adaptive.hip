@@ -1,6 +1,6 @@
 // neo_disp_adaptive.hip -- adaptive waypoint counts on resident arrays (neo_adaptive.hpp): every request's count, the
-// launch list grouped by count, and the merge and the segmented compaction of BatchPlanner.plan's retry chain over
-// the groups (traj_planner/expert_planner.py:86-88, :186-203).
+// launch list grouped by count, and the segmented compaction of BatchPlanner.plan's retry chain over the groups
+// (traj_planner/expert_planner.py:86-88, :186-203).  A group's merge is the plan unit's (plan_merge, neo_disp_plan.hip).
 #include "neo_host.hpp"
 #include "neo_adaptive.hpp"
 
@@ -21,12 +21,6 @@ int adaptive_count(neo_ctx *c, const LaunchList &l, int D, const double *head, c
 int adaptive_bucket(neo_ctx *c, const LaunchList &l, const int *counts, int *order, int *bucket_begin, int *total) {
   hipLaunchKernelGGL(adaptive_bucket_kernel, dim3(1), dim3(kBucketThreads), 0, c->stream, l, counts, order, bucket_begin,
                      total);
-  return NEO_OK;
-}
-
-int adaptive_merge(neo_ctx *c, const LaunchList &l, const AdaptiveMergeArgs &a) {
-  hipLaunchKernelGGL(adaptive_merge_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.n, a.x_stride, a.reset, a.packed,
-                     a.out, a.attempts, a.nit_total, a.solved, a.pending, a.bad_scene);
   return NEO_OK;
 }
 

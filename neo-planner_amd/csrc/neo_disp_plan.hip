@@ -1,6 +1,7 @@
 // neo_disp_plan.hip -- BatchPlanner.plan's retry chain on resident arrays (neo_plan.hpp): the guess of one attempt
 // packed for the optimiser launch, and the merge of its results with the compacted list of the requests to launch
-// again (traj_planner/expert_planner.py:186-203).  The compaction is the batch unit's (batch_compact).
+// again (traj_planner/expert_planner.py:186-203).  The compaction is the batch unit's (batch_compact); the chain over
+// mixed waypoint counts merges group by group through the same launcher and compacts on its own (neo_disp_adaptive.hip).
 #include "neo_host.hpp"
 #include "neo_plan.hpp"
 
@@ -33,9 +34,9 @@ int plan_jitter(neo_ctx *c, const LaunchList &l, int M, int D, uint64_t seed, in
 }
 
 int plan_merge(neo_ctx *c, const LaunchList &l, const PlanMergeArgs &a) {
-  hipLaunchKernelGGL(plan_merge_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.n, a.reset, a.packed, a.out, a.attempts,
-                     a.nit_total, a.solved, a.failed, a.bad_scene);
-  return batch_compact(c, l.n, a.failed, a.n_failed);
+  hipLaunchKernelGGL(plan_merge_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.n, a.ldx, a.reset, a.packed, a.out,
+                     a.attempts, a.nit_total, a.solved, a.failed, a.bad_scene);
+  return a.n_failed ? batch_compact(c, l.n, a.failed, a.n_failed) : NEO_OK;
 }
 
 }  // namespace neo

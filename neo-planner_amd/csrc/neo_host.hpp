@@ -328,13 +328,14 @@ struct PlanGuessArgs {
   int *slots_k;                  // packed, or NULL
 };
 struct PlanMergeArgs {
-  int n, reset;
+  int n, ldx, reset;                      // ldx >= n: the row length of out.x (NaN behind a row's n values)
   RunRowsIn packed;                       // [P] rows: the optimiser's results
   RunRows out;                            // everything below by request
   int *attempts;
   long long *nit_total;
   int *solved;
-  int *failed, *n_failed, *bad_scene;     // [P], [1] and [1]
+  int *failed, *n_failed, *bad_scene;     // [P], [1] and [1] (not zeroed here); n_failed NULL: the merge alone, no
+                                          // compaction launch after it (a group of a mixed chain)
 };
 int plan_guess(neo_ctx *c, const LaunchList &l, int D, const PlanGuessArgs &a);
 int plan_merge(neo_ctx *c, const LaunchList &l, const PlanMergeArgs &a);
@@ -343,21 +344,12 @@ int plan_jitter(neo_ctx *c, const LaunchList &l, int M, int D, uint64_t seed, in
                 double *noise);
 
 // neo_adaptive_*_dev: per-request waypoint counts and the plan chain over groups of one count (neo_disp_adaptive.hip,
-// kernels in neo_adaptive.hpp): one launch each on the context's stream.  Every pointer is a device array but
-// seg_begin / seg_len (HOST, NEO_MAX_PIECES values each, handed to the kernel by value); the arguments were checked.
-struct AdaptiveMergeArgs {
-  int n, x_stride, reset;
-  RunRowsIn packed;                       // [P] rows: the optimiser's results
-  RunRows out;                            // everything below by request; x in rows of x_stride
-  int *attempts;
-  long long *nit_total;
-  int *solved;
-  int *pending, *bad_scene;               // [P] and [1] (not zeroed here)
-};
+// kernels in neo_adaptive.hpp; a group's merge is plan_merge above): one launch each on the context's stream.  Every
+// pointer is a device array but seg_begin / seg_len (HOST, NEO_MAX_PIECES values each, handed to the kernel by value);
+// the arguments were checked.
 int adaptive_count(neo_ctx *c, const LaunchList &l, int D, const double *head, const double *tail, double seg_len,
                    int max_waypoints, int *counts, int *clamped);
 int adaptive_bucket(neo_ctx *c, const LaunchList &l, const int *counts, int *order, int *bucket_begin, int *total);
-int adaptive_merge(neo_ctx *c, const LaunchList &l, const AdaptiveMergeArgs &a);
 int adaptive_compact(neo_ctx *c, const int *seg_begin, const int *seg_len, int *pending, int *n_failed);
 
 // neo_geo_search_batch_dev / neo_geo_prune_batch (neo_disp_geo.hip); the context is locked and its tables rebuilt

@@ -1,6 +1,6 @@
 // neo_launch_list.hpp -- what the kernels that run on RESIDENT arrays share (fleet, record, onboard, batch, plan,
 // init and adaptive units): the list of a launch, the map table of a call, the six result arrays of an optimiser launch,
-// and the one-workgroup ordered rank.  Included by neo_host.hpp and by the seven kernel headers; it needs nothing but HIP.
+// and the one-workgroup ordered rank with the in-place compaction built on it.  Included by neo_host.hpp and by the seven kernel headers; it needs nothing but HIP.
 //
 // A launch covers n positions.  Position p works on request (mission) subset[p], or on p when there is no subset.  An
 // index outside 0 .. B - 1 is skipped: request() answers -1, the kernel returns, and every row of that index -- the
@@ -45,10 +45,11 @@ struct RunRows {
 };
 
 // row `row` of the packed results to row b of the request-indexed ones, by one wavefront: x strided over the lanes,
-// the two cost rows by lanes 0 - 3, the integers by lane 0
-__device__ __forceinline__ void scatter_run_row(int lane, int n, const RunRowsIn &packed, size_t row, const RunRows &out,
-                                                int b) {
-  for (int i = lane; i < n; i += kListWave) out.x[(size_t)b * n + i] = packed.x[row * n + i];
+// the two cost rows by lanes 0 - 3, the integers by lane 0.  The request-indexed x has rows of `ldx` >= n doubles (the
+// packed one rows of n); what lies behind the n values of a row is the caller's.
+__device__ __forceinline__ void scatter_run_row(int lane, int n, int ldx, const RunRowsIn &packed, size_t row,
+                                                const RunRows &out, int b) {
+  for (int i = lane; i < n; i += kListWave) out.x[(size_t)b * ldx + i] = packed.x[row * n + i];
   if (lane < 4) {
     out.costs4[(size_t)b * 4 + lane] = packed.costs4[row * 4 + lane];
     out.costs4_last[(size_t)b * 4 + lane] = packed.costs4_last[row * 4 + lane];
@@ -104,6 +105,25 @@ __device__ __forceinline__ int ordered_rank(bool take, RankLds<THREADS> &s) {
   }
   __syncthreads();
   return rank;
+}
+
+// seg[len] (a request index, or -1) -> its entries >= 0 packed to the front in the order of their positions, by ONE
+// workgroup of THREADS lanes; returns their number (to every lane).  A chunk is read whole, then written at or before
+// the places it was read from, so the packing is done in place and no position depends on scheduling.  `len` is
+// workgroup-uniform; every lane of the workgroup makes the call.
+template <int THREADS>
+__device__ __forceinline__ int compact_in_place(int *__restrict__ seg, int len) {
+  __shared__ RankLds<THREADS> ranks;
+  const int tid = threadIdx.x;
+  if (tid == 0) ranks.base = 0;
+  __syncthreads();
+  for (int at = 0; at < len; at += THREADS) {
+    const int i = at + tid;
+    const int v = i < len ? seg[i] : -1;        // the chunk is read whole ...
+    const int rank = ordered_rank(v >= 0, ranks);
+    if (v >= 0) seg[rank] = v;                  // ... before any of it is written: rank <= i
+  }
+  return ranks.base;
 }
 
 }  // namespace neo

@@ -8,6 +8,8 @@
 //   plan_merge_kernel   plan's bookkeeping over the launch's results: scatter to the request-indexed arrays, attempts,
 //                       nit_total, failed / solved, the bad-scene word                     one wavefront per request
 //   (batch_compact_kernel, neo_batch.hpp, then packs the failed requests: the next attempt's launch list)
+// The merge serves the fixed chain and, group by group, the chain over mixed waypoint counts (neo_adaptive_merge_dev):
+// the one difference is the row length of the request-indexed x.
 //
 // Included by neo_disp_plan.hip only.  fp64, D = 2 or 3.  Request-indexed arrays are indexed by request b; packed
 // arrays by the request's position p in the launch list (neo_launch_list.hpp).  No atomics, no scratch.
@@ -89,11 +91,14 @@ __global__ __launch_bounds__(kPlanThreads) void plan_jitter_kernel(LaunchList li
 //   attempts += 1 (`reset`: = 1, the chain's first attempt); nit_total += nit unless the run overflowed
 //   ((status & 0xff) >= NEO_TRAJ_NUMERIC_RANGE: the reference raises before it counts such a run; `reset`: =);
 //   failed = ((status & 0xff) > NEO_TRAJ_MAXITER and != NEO_TRAJ_BAD_SCENE) or NEO_TRAJ_FLAG_COLLISION; solved = !failed.
-// `pending[p]` gets the request's index when it failed, -1 otherwise: batch_compact_kernel packs it afterwards.
-// `bad_scene` (zeroed before the launch) becomes 1 when a launched request ended with NEO_TRAJ_BAD_SCENE -- every
-// wavefront that sees one stores the same 1.
+// The request-indexed x has rows of `ldx` >= n doubles: the row's n values, then NaN (a group of a mixed chain in rows
+// of the longest group's length; ldx == n: no tail).
+// `pending[p]` gets the request's index when it failed, -1 otherwise: batch_compact_kernel, or adaptive_compact_kernel
+// over the groups' segments, packs it afterwards.
+// `bad_scene` (zeroed before the chain's first launch) becomes 1 when a launched request ended with
+// NEO_TRAJ_BAD_SCENE -- every wavefront that sees one stores the same 1.
 __global__ __launch_bounds__(kWave) void plan_merge_kernel(
-    LaunchList list, int n, int reset, RunRowsIn packed, RunRows out, int *__restrict__ attempts,
+    LaunchList list, int n, int ldx, int reset, RunRowsIn packed, RunRows out, int *__restrict__ attempts,
     long long *__restrict__ nit_total, int *__restrict__ solved, int *__restrict__ pending, int *__restrict__ bad_scene) {
   const int p = blockIdx.x;
   const int lane = lane_id();
@@ -103,7 +108,9 @@ __global__ __launch_bounds__(kWave) void plan_merge_kernel(
     return;
   }
   const int st = packed.status[p], its = packed.nit[p];  // (wave-uniform loads, ahead of the scatter's stores)
-  scatter_run_row(lane, n, packed, (size_t)p, out, b);
+  scatter_run_row(lane, n, ldx, packed, (size_t)p, out, b);
+  double *xr = out.x + (size_t)b * ldx;
+  for (int i = n + lane; i < ldx; i += kWave) xr[i] = __builtin_nan("");
   if (lane == 0) {
     const int code = st & 0xff;
     const bool failed = (code > NEO_TRAJ_MAXITER && code != NEO_TRAJ_BAD_SCENE) || (st & NEO_TRAJ_FLAG_COLLISION);

@@ -213,9 +213,9 @@ def as_f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-def dev_ptr(t):
-    """device pointer of a torch tensor (None -> NULL)"""
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+def dev_ptr(t, first=0):
+    """device pointer of a torch tensor, from its element `first` on (None -> NULL)"""
+    return ctypes.c_void_p(t.data_ptr() + first * t.element_size()) if t is not None else None
 
 
 def launch_count(subset, B):

@@ -1074,156 +1074,100 @@ class BatchPlanner:
         subset keep what they had.  The chain has ended when the call returns (the context's stream is waited for).  A
         request that names a map-table slot without a map raises NeoError, as in `plan`.  Returns bufs.
         waypoints="adaptive": plan(waypoints="adaptive")'s ragged arrays bit for bit, every request with its own count of
-        at most `max_waypoints` -- see `_plan_dev_adaptive`."""
-        import torch
+        at most `max_waypoints` -- see `_plan_chain`."""
         if head.ndim != 3 or head.shape[1] != 3 or tuple(tail.shape) != tuple(head.shape):
             raise ValueError("BatchPlanner.plan_dev: head and tail (B, 3, D)")
+        B, D = head.shape[0], head.shape[2]
+        seg = None
         if isinstance(waypoints, str):
             if waypoints != "adaptive":
                 raise ValueError("BatchPlanner.plan_dev: waypoints is a number, None or 'adaptive'")
             if x0 is not None:
                 raise ValueError("BatchPlanner.plan_dev: a warm start x0 fixes its own shape: not with waypoints='adaptive'")
-            return self._plan_dev_adaptive(map, head, tail, bufs, slots, subset, x, solved, max_attempts, seed, rng, stream_ids,
-                                           jitter, max_waypoints)
-        B, D = head.shape[0], head.shape[2]
-        count = int(waypoints if waypoints is not None else self.cfg.init_wpts_num)
-        if x0 is not None:
-            n0 = x0.shape[1]
-            count = (n0 + D) // (D + 1) - 1
-            if x0.shape[0] != B or count < 1 or D * count + count + 1 != n0 or (waypoints is not None and int(waypoints) != count):
-                raise ValueError("BatchPlanner.plan_dev: x0 (B, D * waypoints + waypoints + 1)")
-        M = count + 1
-        if max_attempts < 1:
-            raise ValueError("BatchPlanner.plan_dev: max_attempts must be >= 1")
-        counter = counter_rng.check_jitter(jitter, "BatchPlanner.plan_dev")
-        stream_ids, ids_dev, seed = self._plan_dev_streams(stream_ids, head, counter, seed)
-        if bufs is not None and (bufs["B"] < B or bufs["D"] != D or bufs["M"] != M):
-            raise ValueError("BatchPlanner.plan_dev: bufs were made for another B, D or number of waypoints")
-        self._sync()
-        c = self.ctx
-        dev = head.device
-        if bufs is None:
-            bufs = self.plan_buffers(B, dev, D=D, waypoints=count)
-            torch.cuda.synchronize(dev)     # (the context has its own stream: the buffers are ready before it starts)
-        d = bufs
-        if seed is None:
-            seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
-        frac, tau = self._plan_frac_tau(count)
-        p = _lib.dev_ptr
-        if counter and ids_dev is None and max_attempts > 1:
-            ids_dev = torch.from_numpy(stream_ids).to(dev)      # (a blocking copy: there before the context's stream starts)
-        slots_k = p(d["slots_k"]) if slots is not None else None
-        out_x, out_solved = (x if x is not None else d["x"]), (solved if solved is not None else d["solved"])
-        n_failed, bad = p(d["counts"][0:]), p(d["counts"][1:])
-        sub, P = p(subset), _lib.launch_count(subset, B)
-        launches = []
-        bad_scene = None
-        c.check(c.lib.neo_optimize_progress_counter(c.h, None))
-        try:
-            for attempt in range(max_attempts):
-                if attempt > 0:
-                    c.synchronize()
-                    nf, bad_scene = d["counts"].tolist()
-                    if bad_scene or nf == 0:
-                        break
-                    todo = d["todo"][(attempt - 1) % 2]
-                    if counter:
-                        c.check(c.lib.neo_plan_jitter_dev(c.h, B, p(todo), nf, M, D, seed, attempt, p(ids_dev), p(d["noise"])))
-                    else:
-                        ids = todo[:nf].cpu().numpy()
-                        noise = self.retry_noise(seed, stream_ids[ids], attempt, D, count)
-                        d["noise"][:nf].copy_(torch.from_numpy(np.ascontiguousarray(noise)))
-                        torch.cuda.synchronize(dev)
-                    sub, P = p(todo), nf
-                if not (attempt == 0 and _guessed):
-                    c.check(c.lib.neo_plan_guess_dev(c.h, B, sub, P, M, D, p(head), p(tail), p(slots),
-                                                     p(x0) if attempt == 0 else None, p(d["noise"]) if attempt > 0 else None,
-                                                     _lib.ptr(frac), _lib.ptr(tau), p(d["x_k"]), p(d["head_k"]), p(d["tail_k"]),
-                                                     slots_k))
-                if P > 0:
-                    if P > 1024:
-                        c.check(c.lib.neo_effort_order_dev(c.h, P, M, D, p(d["x_k"]), p(d["head_k"]), p(d["tail_k"]),
-                                                           p(d["order_scratch"]), p(d["order"])))
-                        c.check(c.lib.neo_optimize_dispatch_order(c.h, p(d["order"]), P))
-                    else:
-                        c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))
-                    c.check(c.lib.neo_optimize_batch_from_dev(c.h, map.scene_id, slots_k, P, M, D, p(d["x_k"]), p(d["x_k"]),
-                                                              p(d["head_k"]), p(d["tail_k"]), p(d["costs_k"]), p(d["last_k"]),
-                                                              p(d["nit_k"]), p(d["nfev_k"]), p(d["status_k"])))
-                c.check(c.lib.neo_plan_merge_dev(c.h, B, sub, P, M, D, int(attempt == 0), p(d["x_k"]), p(d["costs_k"]),
-                                                 p(d["last_k"]), p(d["nit_k"]), p(d["nfev_k"]), p(d["status_k"]), p(out_x),
-                                                 p(d["costs"]), p(d["costs_last"]), p(d["nit"]), p(d["nfev"]), p(d["status"]),
-                                                 p(d["attempts"]), p(d["nit_total"]), p(out_solved), p(d["todo"][attempt % 2]),
-                                                 n_failed, bad))
-                launches.append(P)
-                bad_scene = None
-            c.synchronize()
-        finally:
-            c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))     # (the order is in bufs: no launch after this reads it)
-        if bad_scene is None:       # (the last attempt's word has not been read yet)
-            bad_scene = int(d["counts"][1].item())
-        if bad_scene:
-            raise _lib.NeoError("BatchPlanner.plan_dev: a request names a scene without a map (NEO_TRAJ_BAD_SCENE)")
-        d["launch_sizes"] = launches
-        return bufs
+            seg = self._adaptive_args(max_waypoints, "BatchPlanner.plan_dev")
+            count = int(max_waypoints)
+        else:
+            count = int(waypoints if waypoints is not None else self.cfg.init_wpts_num)
+            if x0 is not None:
+                n0 = x0.shape[1]
+                count = (n0 + D) // (D + 1) - 1
+                if x0.shape[0] != B or count < 1 or D * count + count + 1 != n0 or (waypoints is not None and int(waypoints) != count):
+                    raise ValueError("BatchPlanner.plan_dev: x0 (B, D * waypoints + waypoints + 1)")
+        return self._plan_chain(map, head, tail, bufs, count, seg, x0, slots, subset, x, solved, max_attempts, seed, rng,
+                                stream_ids, _guessed, jitter)
 
-    def _plan_dev_adaptive(self, map, head, tail, bufs, slots, subset, x, solved, max_attempts, seed, rng, stream_ids, jitter,
-                           max_waypoints):
-        """plan_dev(waypoints="adaptive"): `_plan_adaptive`'s arrays bit for bit on resident tensors.  neo_adaptive_count_dev
-        gives the launched requests their counts, neo_adaptive_bucket_dev groups the launch list by count, and the host
-        waits ONCE to read the group table.  The chain is attempt-major: in an attempt every non-empty group, longest
-        first, gets its guess, its effort order above 1024 rows, its optimiser launch with M = count + 1 and
-        neo_adaptive_merge_dev -- on rows of the packed arrays that start where the group's segment of the list starts,
-        all on the context's stream, no wait in between -- then ONE neo_adaptive_compact_dev packs every group's failed
-        requests to the front of its segment.  The host waits once per attempt and reads the table (the groups' failed
-        counts, the bad-scene word).  jitter="counter": neo_plan_jitter_dev per group over its failed segment, no list is
-        read; jitter="numpy": the failed lists are read and `retry_noise` drawn per group.
-        Results in `bufs` (plan_buffers(..., waypoints="adaptive")): x (B, n_max) ragged with NaN behind a request's own
-        values, counts, clamped (int32), the arrays of plan_dev, launch_sizes (requests per attempt over all groups),
+    def _plan_chain(self, map, head, tail, bufs, W, seg, x0, slots, subset, x, solved, max_attempts, seed, rng, stream_ids,
+                    guessed, jitter):
+        """the retry chain behind plan_dev, over GROUPS of requests with one waypoint count each.  `seg` None: the fixed
+        form, ONE group -- the caller's subset (or all B) with W waypoints, packed from row 0.  Otherwise
+        plan_dev(waypoints="adaptive"), `_plan_adaptive`'s arrays bit for bit: neo_adaptive_count_dev gives the launched
+        requests their counts (at most W, segments of length `seg`), neo_adaptive_bucket_dev groups the launch list by
+        count, and the host waits ONCE to read the group table.  The chain is attempt-major: in an attempt every group,
+        longest first, gets its jitter (attempts after the first), its guess, its effort order above 1024 rows, its
+        optimiser launch with M = count + 1 and its merge -- on rows of the packed arrays that start where the group's
+        segment of the list starts, all on the context's stream, no wait in between.  The fixed form's merge
+        (neo_plan_merge_dev) compacts its failed list itself; the groups' merges (neo_adaptive_merge_dev) are followed by
+        ONE neo_adaptive_compact_dev that packs every group's failed requests to the front of its segment.  The host waits
+        once per attempt and reads the failed counts and the bad-scene word: the two words of `counts`, or the table.
+        jitter="counter": neo_plan_jitter_dev per group over its failed segment, no list is read; jitter="numpy": the
+        failed lists are read and `retry_noise` drawn per group.
+        Adaptive results in `bufs` (plan_buffers(..., waypoints="adaptive")): x (B, n_max) ragged with NaN behind a request's
+        own values, counts, clamped (int32), the arrays of plan_dev, launch_sizes (requests per attempt over all groups),
         group_launch_sizes {count: sizes per attempt} and host_waits {"grouping": 1, "attempts": waits that followed an
         attempt}.  `x` / `solved` / `subset` as in plan_dev (`x`: rows of n_max)."""
         import torch
-        seg = self._adaptive_args(max_waypoints, "BatchPlanner.plan_dev")
-        W = int(max_waypoints)
+        adaptive = seg is not None
         B, D = head.shape[0], head.shape[2]
         n_max = D * W + W + 1
         if max_attempts < 1:
             raise ValueError("BatchPlanner.plan_dev: max_attempts must be >= 1")
         counter = counter_rng.check_jitter(jitter, "BatchPlanner.plan_dev")
         stream_ids, ids_dev, seed = self._plan_dev_streams(stream_ids, head, counter, seed)
-        if bufs is not None and (not bufs.get("adaptive") or bufs["B"] < B or bufs["D"] != D or bufs["max_waypoints"] != W):
-            raise ValueError("BatchPlanner.plan_dev: bufs were not made for waypoints='adaptive' with this B, D and max_waypoints")
-        if x is not None and (x.ndim != 2 or x.shape[1] != n_max):
+        if bufs is not None and (bufs["B"] < B or bufs["D"] != D or bufs["M"] != W + 1 or (adaptive and not bufs.get("adaptive"))):
+            raise ValueError("BatchPlanner.plan_dev: bufs were " +
+                             ("not made for waypoints='adaptive' with this B, D and max_waypoints" if adaptive else
+                              "made for another B, D or number of waypoints"))
+        if adaptive and x is not None and (x.ndim != 2 or x.shape[1] != n_max):
             raise ValueError("BatchPlanner.plan_dev: x (B, D * max_waypoints + max_waypoints + 1) with waypoints='adaptive'")
         self._sync()
         c = self.ctx
         dev = head.device
         if bufs is None:
-            bufs = self.plan_buffers(B, dev, D=D, waypoints="adaptive", max_waypoints=W)
+            bufs = self.plan_buffers(B, dev, D=D, waypoints="adaptive" if adaptive else W, max_waypoints=W)
             torch.cuda.synchronize(dev)     # (the context has its own stream: the buffers are ready before it starts)
         d = bufs
         if seed is None:
             seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
         p = _lib.dev_ptr
+        rows = lambda t, first, per=1: p(t, first * per)    # an array from row `first` on (no tensor is made for it)
         if counter and ids_dev is None and max_attempts > 1:
             ids_dev = torch.from_numpy(stream_ids).to(dev)      # (a blocking copy: there before the context's stream starts)
         out_x, out_solved = (x if x is not None else d["x"]), (solved if solved is not None else d["solved"])
-        G = _lib.NEO_MAX_PIECES
-        table = d["table"]      # bucket_begin [G + 1], the groups' failed counts [G], the bad-scene word, the total
-        n_failed, bad = table[G + 1:], table[2 * G + 1:]
-        if _lib.launch_count(subset, B) == 0:       # (an empty list: nothing to count, nothing to wait for)
-            d.update(launch_sizes=[], group_launch_sizes={}, host_waits=dict(grouping=0, attempts=0))
-            return bufs
-        rows = lambda t, first, per=1: p(t.view(-1)[first * per:])   # a packed array from row `first` on
-        c.check(c.lib.neo_adaptive_count_dev(c.h, B, p(subset), _lib.launch_count(subset, B), D, p(head), p(tail), seg, W,
-                                             p(d["counts"]), p(d["clamped"])))
-        c.check(c.lib.neo_adaptive_bucket_dev(c.h, B, p(subset), _lib.launch_count(subset, B), p(d["counts"]),
-                                              p(d["group_order"]), p(table), p(table[2 * G + 2:])))
-        c.synchronize()
-        begin = table[:G + 1].tolist()
-        seg_begin = np.asarray(begin[:G], dtype=np.int32)
-        seg_len = np.diff(np.asarray(begin, dtype=np.int32)).astype(np.int32)
-        lists = d["group_order"]
+        # the groups: (count, first row, index of the group's word), `lens` the words' rows to launch, `lists` their requests;
+        # `words`: what the host reads after an attempt's wait -- the groups' failed counts, then the bad-scene word
+        lists, lens = subset, [_lib.launch_count(subset, B)]
+        if adaptive:
+            G = _lib.NEO_MAX_PIECES
+            table = d["table"]      # bucket_begin [G + 1], the groups' failed counts [G], the bad-scene word, the total
+            words = table[G + 1:2 * G + 2]
+            if lens[0] == 0:       # (an empty list: nothing to count, nothing to wait for)
+                d.update(launch_sizes=[], group_launch_sizes={}, host_waits=dict(grouping=0, attempts=0))
+                return bufs
+            c.check(c.lib.neo_adaptive_count_dev(c.h, B, p(subset), lens[0], D, p(head), p(tail), seg, W, p(d["counts"]),
+                                                 p(d["clamped"])))
+            c.check(c.lib.neo_adaptive_bucket_dev(c.h, B, p(subset), lens[0], p(d["counts"]), p(d["group_order"]), p(table),
+                                                  p(table[2 * G + 2:])))
+            c.synchronize()
+            begin = table[:G + 1].tolist()
+            seg_begin = np.asarray(begin[:G], dtype=np.int32)
+            segs = [(g, begin[g], g) for g in range(G - 1, 0, -1)]      # the longest M first
+            lists, lens = d["group_order"], np.diff(begin).tolist()
+        else:
+            words = d["counts"]
+            segs = [(W, 0, 0)]
+            if subset is not None and lens[0] == 0:
+                lists = d["todo"][1]    # (an empty tensor may own no memory, and a NULL list would mean all B requests)
+        counts_at, bad_at = p(words), p(words[-1:])
         launches, by_group, waits, frac_tau = [], {}, 0, {}
         bad_scene = 0
         c.check(c.lib.neo_optimize_progress_counter(c.h, None))
@@ -1232,22 +1176,23 @@ class BatchPlanner:
                 if attempt > 0:
                     c.synchronize()
                     waits += 1
-                    words = table[G + 1:2 * G + 2].tolist()
-                    seg_len, bad_scene = np.asarray(words[:G], dtype=np.int32), words[G]
+                    *lens, bad_scene = words.tolist()
                     lists = d["todo"][(attempt - 1) % 2]
-                groups = [g for g in range(G - 1, 0, -1) if seg_len[g] > 0]      # the longest M first
+                # (the fixed form launches its first list even when it is empty: the merge zeroes the two words)
+                groups = [(g, o, lens[k]) for g, o, k in segs if lens[k] > 0 or not (adaptive or attempt)]
                 if bad_scene or not groups:
+                    if not adaptive:
+                        c.synchronize()     # (the fixed form ends with a wait of its own)
                     break
                 if attempt > 0 and not counter:
-                    for g in groups:
-                        o, P = int(seg_begin[g]), int(seg_len[g])
+                    for g, o, P in groups:
                         ids = lists[o:o + P].cpu().numpy()
                         noise = self.retry_noise(seed, stream_ids[ids], attempt, D, g)
                         d["noise"].view(-1)[o * D * W:o * D * W + P * D * g].copy_(torch.from_numpy(noise.reshape(-1)))
                     torch.cuda.synchronize(dev)
                 pending = d["todo"][attempt % 2]
-                for k, g in enumerate(groups):
-                    o, P, M = int(seg_begin[g]), int(seg_len[g]), g + 1
+                for k, (g, o, P) in enumerate(groups):
+                    M = g + 1
                     sub = rows(lists, o)
                     x_k, head_k, tail_k = rows(d["x_k"], o, n_max), rows(d["head_k"], o, 3 * D), rows(d["tail_k"], o, 3 * D)
                     slots_k = rows(d["slots_k"], o) if slots is not None else None
@@ -1259,34 +1204,42 @@ class BatchPlanner:
                     frac, tau = frac_tau[g]
                     if attempt > 0 and counter:
                         c.check(c.lib.neo_plan_jitter_dev(c.h, B, sub, P, M, D, seed, attempt, p(ids_dev), noise_k))
-                    c.check(c.lib.neo_plan_guess_dev(c.h, B, sub, P, M, D, p(head), p(tail), p(slots), None,
-                                                     noise_k if attempt > 0 else None, _lib.ptr(frac), _lib.ptr(tau), x_k,
-                                                     head_k, tail_k, slots_k))
-                    if P > 1024:
-                        order = rows(d["order"], o)
-                        c.check(c.lib.neo_effort_order_dev(c.h, P, M, D, x_k, head_k, tail_k, p(d["order_scratch"]), order))
-                        c.check(c.lib.neo_optimize_dispatch_order(c.h, order, P))
+                    if not (attempt == 0 and guessed):
+                        c.check(c.lib.neo_plan_guess_dev(c.h, B, sub, P, M, D, p(head), p(tail), p(slots),
+                                                         p(x0) if attempt == 0 else None, noise_k if attempt > 0 else None,
+                                                         _lib.ptr(frac), _lib.ptr(tau), x_k, head_k, tail_k, slots_k))
+                    if P > 0:
+                        if P > 1024:
+                            order = rows(d["order"], o)
+                            c.check(c.lib.neo_effort_order_dev(c.h, P, M, D, x_k, head_k, tail_k, p(d["order_scratch"]), order))
+                            c.check(c.lib.neo_optimize_dispatch_order(c.h, order, P))
+                        else:
+                            c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))
+                        c.check(c.lib.neo_optimize_batch_from_dev(c.h, map.scene_id, slots_k, P, M, D, x_k, x_k, head_k, tail_k,
+                                                                  *res_k))
+                    merged = (x_k, *res_k, p(out_x), p(d["costs"]), p(d["costs_last"]), p(d["nit"]), p(d["nfev"]), p(d["status"]),
+                              p(d["attempts"]), p(d["nit_total"]), p(out_solved), rows(pending, o))
+                    if adaptive:
+                        c.check(c.lib.neo_adaptive_merge_dev(c.h, B, sub, P, M, D, n_max, int(attempt == 0),
+                                                             int(attempt == 0 and k == 0), *merged, bad_at))
                     else:
-                        c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))
-                    c.check(c.lib.neo_optimize_batch_from_dev(c.h, map.scene_id, slots_k, P, M, D, x_k, x_k, head_k, tail_k,
-                                                              *res_k))
-                    c.check(c.lib.neo_adaptive_merge_dev(c.h, B, sub, P, M, D, n_max, int(attempt == 0),
-                                                         int(attempt == 0 and k == 0), x_k, *res_k, p(out_x), p(d["costs"]),
-                                                         p(d["costs_last"]), p(d["nit"]), p(d["nfev"]), p(d["status"]),
-                                                         p(d["attempts"]), p(d["nit_total"]), p(out_solved), rows(pending, o),
-                                                         p(bad)))
+                        c.check(c.lib.neo_plan_merge_dev(c.h, B, sub, P, M, D, int(attempt == 0), *merged, counts_at, bad_at))
                     by_group.setdefault(g, []).append(P)
-                c.check(c.lib.neo_adaptive_compact_dev(c.h, _lib.ptr(seg_begin), _lib.ptr(seg_len), p(pending), p(n_failed)))
-                launches.append(int(seg_len.sum()))
+                if adaptive:
+                    c.check(c.lib.neo_adaptive_compact_dev(c.h, _lib.ptr(seg_begin), _lib.ptr(np.asarray(lens, dtype=np.int32)),
+                                                           p(pending), counts_at))
+                launches.append(sum(P for _, _, P in groups))
             else:
                 c.synchronize()     # (every attempt has run: the last one's wait)
                 waits += 1
-                bad_scene = int(table[2 * G + 1].item())
+                bad_scene = int(words[-1].item())
         finally:
             c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))     # (the order is in bufs: no launch after this reads it)
         if bad_scene:
             raise _lib.NeoError("BatchPlanner.plan_dev: a request names a scene without a map (NEO_TRAJ_BAD_SCENE)")
-        d.update(launch_sizes=launches, group_launch_sizes=by_group, host_waits=dict(grouping=1, attempts=waits))
+        d["launch_sizes"] = launches
+        if adaptive:
+            d.update(group_launch_sizes=by_group, host_waits=dict(grouping=1, attempts=waits))
         return bufs
 
     # ------------------------------------------------------------ the reference's `batch` mode (:103-168) for B requests

@@ -3,6 +3,7 @@ the two kernels against NumPy (init_guess / pack_x, and the merge restatement te
 own bookkeeping), plan_dev against plan -- every returned array bit for bit, the launch sizes too -- a request alone
 against its row in the batch, and the fleet's resident form against its host form, flight by flight."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -208,6 +209,103 @@ def test_merge_equals_the_numpy_restatement_on_synthetic_results(P0):
         assert both.size > 1000 and np.all(ref["attempts"][both] == 2)
 
 
+# ------------------------------------------------------------------ 2b. one merge kernel behind both entry points
+MERGE_B, MERGE_P = 1300, 1100          # more than one chunk of the compactions' 1024 and 256 lanes
+
+
+@functools.lru_cache(maxsize=None)
+def _merge_case(M, D):
+    """one merge's inputs, made once: a shuffled subset of MERGE_P of MERGE_B requests with one index to skip, packed
+    results whose status column walks the codes 0 .. 7 without and with the collision flag, sentinel request-indexed
+    arrays -- and for reset = 1 and 0 what merge_restated makes of them"""
+    n = D * (M - 1) + M
+    rng = np.random.default_rng(1000 * M + D)
+    B, P = MERGE_B, MERGE_P
+    sub = rng.permutation(B)[:P].astype(np.int32)
+    sub[700] = B                                                # an index outside 0 .. B - 1
+    st = (np.arange(P) % 8 + np.where(np.arange(P) // 8 % 2 == 1, _lib.NEO_TRAJ_FLAG_COLLISION, 0)).astype(np.int32)
+    packed = (rng.normal(0, 1, (P, n)), rng.random((P, 4)), rng.random((P, 4)), rng.integers(0, 15000, P).astype(np.int32),
+              rng.integers(0, 15000, P).astype(np.int32), st)
+    init = dict(x=np.full((B, n), SENTINEL), costs4=np.full((B, 4), SENTINEL), costs4_last=np.full((B, 4), SENTINEL),
+                nit=np.full(B, -9, np.int32), nfev=np.full(B, -9, np.int32), status=np.full(B, -9, np.int32),
+                attempts=np.full(B, 40, np.int32), nit_total=np.full(B, 5_000_000_000, np.int64),
+                solved=np.full(B, -9, np.int32))
+    refs = {reset: merge_restated(B, sub, reset, *packed, init) for reset in (1, 0)}
+    assert all(0 < len(lst) < P - 1 and bad == 1 for _, lst, bad in refs.values())
+    return n, sub, packed, init, refs
+
+
+def _grouped_merge(ctx, M, D, stride, reset, sub, packed, init):
+    """neo_adaptive_merge_dev (clear_bad = 1) over the case as the one group of M - 1 waypoints, then
+    neo_adaptive_compact_dev with the one segment [0, P): (request-indexed arrays, failed list, its length, bad word)"""
+    torch, dev = _torch()
+    B, P, G = MERGE_B, MERGE_P, _lib.NEO_MAX_PIECES
+    d = {k: _dev(v) for k, v in init.items()}
+    if stride != init["x"].shape[1]:
+        d["x"] = torch.full((B, stride), SENTINEL, dtype=torch.float64, device=dev)
+    ins = [_dev(a) for a in (sub,) + packed]
+    d_lst = torch.full((P,), -3, dtype=torch.int32, device=dev)
+    d_nf = torch.full((G,), -3, dtype=torch.int32, device=dev)
+    d_bad = torch.full((1,), -3, dtype=torch.int32, device=dev)
+    begin, lens = np.zeros(G, np.int32), np.zeros(G, np.int32)
+    lens[M - 1] = P
+    torch.cuda.synchronize(dev)
+    ctx.check(ctx.lib.neo_adaptive_merge_dev(ctx.h, B, _p(ins[0]), P, M, D, stride, reset, 1, *[_p(t) for t in ins[1:]],
+                                             *[_p(d[k]) for k in MERGED], _p(d_lst), _p(d_bad)))
+    ctx.check(ctx.lib.neo_adaptive_compact_dev(ctx.h, _lib.ptr(begin), _lib.ptr(lens), _p(d_lst), _p(d_nf)))
+    ctx.synchronize()
+    nf = d_nf.cpu().numpy()
+    assert np.all(np.delete(nf, M - 1) == 0)                    # (an empty segment: 0)
+    return {k: v.cpu().numpy() for k, v in d.items()}, d_lst.cpu().numpy(), int(nf[M - 1]), int(d_bad.item())
+
+
+@pytest.mark.parametrize("M, D", [(3, 2), (33, 3)])
+def test_the_grouped_merge_is_the_fixed_merge(M, D):
+    """neo_plan_merge_dev, and on copies of the same inputs neo_adaptive_merge_dev with x_stride = n and
+    neo_adaptive_compact_dev over one segment: equal request-indexed arrays, failed list and count, bad-scene word --
+    both the NumPy restatement's.  n = 7 and n = 129 (the x copy takes more than two strides of 64 lanes)"""
+    torch, dev = _torch()
+    ctx = _lib.default_context()
+    n, sub, packed, init, refs = _merge_case(M, D)
+    assert n == {3: 7, 33: 129}[M]
+    B, P = MERGE_B, MERGE_P
+    for reset in (1, 0):
+        ref, ref_list, ref_bad = refs[reset]
+        d = {k: _dev(v) for k, v in init.items()}
+        ins = [_dev(a) for a in (sub,) + packed]
+        d_lst = torch.full((P,), -3, dtype=torch.int32, device=dev)
+        d_cnt = torch.full((2,), -3, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        ctx.check(ctx.lib.neo_plan_merge_dev(ctx.h, B, _p(ins[0]), P, M, D, reset, *[_p(t) for t in ins[1:]],
+                                             *[_p(d[k]) for k in MERGED], _p(d_lst), _p(d_cnt[0:]), _p(d_cnt[1:])))
+        ctx.synchronize()
+        fixed = ({k: v.cpu().numpy() for k, v in d.items()}, d_lst.cpu().numpy()) + tuple(d_cnt.tolist())
+        grouped = _grouped_merge(ctx, M, D, n, reset, sub, packed, init)
+        for got, lst, nl, bad in (fixed, grouped):
+            for k in MERGED:
+                assert np.array_equal(got[k], ref[k]), (reset, k)       # bit for bit, the rows not launched included
+            assert nl == len(ref_list) and np.array_equal(lst[:nl], ref_list) and bad == ref_bad, reset
+        assert np.array_equal(fixed[1][:fixed[2]], grouped[1][:grouped[2]])
+
+
+def test_the_merge_writes_x_in_rows_of_its_stride():
+    """the (3, 2) case with x_stride = 10 over a sentinel x: columns 0 .. 6 of a launched request's row are its packed
+    row, columns 7 .. 9 NaN; the rows of the skipped index and of the requests not listed keep the sentinel"""
+    ctx = _lib.default_context()
+    n, sub, packed, init, refs = _merge_case(3, 2)
+    ref, ref_list, ref_bad = refs[1]
+    got, lst, nl, bad = _grouped_merge(ctx, 3, 2, 10, 1, sub, packed, init)
+    valid = (sub >= 0) & (sub < MERGE_B)
+    on = np.zeros(MERGE_B, bool)
+    on[sub[valid]] = True
+    assert on.sum() == MERGE_P - 1
+    assert np.array_equal(got["x"][sub[valid], :n], packed[0][valid]) and np.isnan(got["x"][on, n:]).all()
+    assert np.all(got["x"][~on] == SENTINEL)
+    for k in MERGED[1:]:
+        assert np.array_equal(got[k], ref[k]), k
+    assert nl == len(ref_list) and np.array_equal(lst[:nl], ref_list) and bad == ref_bad
+
+
 # ------------------------------------------------------------------ 3. plan_dev against plan
 PLAN_KEYS = ("x", "costs", "costs_last", "nit", "nfev", "status", "collision", "attempts", "nit_total", "solved")
 
@@ -289,6 +387,26 @@ def test_plan_dev_over_a_subset_is_plan_over_those_requests(scenes, requests, pl
     bp.plan_dev(scenes[1][0], d_head, d_tail, bufs=bufs, slots=d_slots, subset=d_sub, x=own_x, solved=own_s, seed=23, stream_ids=IDS)
     assert torch.equal(bufs["x"], before) and np.array_equal(own_x.cpu().numpy()[sub], ref["x"])
     assert np.array_equal(own_s.cpu().numpy()[sub] != 0, ref["solved"]) and np.all(own_s.cpu().numpy()[rest] == -9)
+
+
+def test_plan_dev_over_an_empty_subset_plans_nothing(scenes, planned):
+    """the fixed form with a subset of no entries: the same bufs come back, every result as it was, and one launch of
+    size 0 on record (the guess and the merge are called for the empty list, the optimiser is not)"""
+    torch, dev = _torch()
+    bp, _, _, (d_head, d_tail, d_slots) = planned["f32x"]
+    bufs = bp.plan_buffers(48, dev)
+    keys = ("x", "costs", "costs_last", "nit", "nfev", "status", "attempts", "nit_total", "solved")
+    for k in keys:
+        bufs[k].fill_(SENTINEL if bufs[k].dtype == torch.float64 else -9)
+    for k in ("x_k", "costs_k", "last_k"):
+        bufs[k].fill_(-SENTINEL)            # (what a merge of rows that were never launched would bring over)
+    before = {k: bufs[k].clone() for k in keys}
+    empty = torch.zeros((0,), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    assert bp.plan_dev(scenes[1][0], d_head, d_tail, bufs=bufs, slots=d_slots, subset=empty, seed=23, stream_ids=IDS) is bufs
+    for k in keys:
+        assert torch.equal(bufs[k], before[k]), k
+    assert bufs["launch_sizes"] == [0]
 
 
 def test_plan_dev_from_a_callers_first_guess_is_plan_with_int_wpts(scenes, requests, planned):

@@ -5,14 +5,14 @@
     python tools/kernel_resource_usage.py > profiles/rNN_kernel_resource_usage.txt
 
 Listed: the brick-layout instantiations of the bench's configurations, the budgeted kernels, the ESDF-lookup kernels,
-the depth camera's kernels, the record kernels, the warm-start (init) kernels, the two counter-based jitter kernels, the adaptive-count kernels."""
+the depth camera's kernels, the record kernels, the warm-start (init) kernels, the two counter-based jitter kernels, the adaptive-count kernels, the plan chain's merge and the two compactions."""
 import concurrent.futures, os, re, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "neo-planner_amd"))
 from neo_planner_amd import build as b
 
 UNITS = ["neo_disp_opt3d_x.hip", "neo_disp_opt3d_w2.hip", "neo_disp_opt3d_f64.hip", "neo_disp_opt3d_b.hip", "neo_disp_sample.hip",
-         "neo_disp_group.hip", "neo_disp_depth.hip", "neo_disp_record.hip", "neo_disp_init.hip", "neo_disp_plan.hip", "neo_disp_fleet.hip", "neo_disp_adaptive.hip"]
+         "neo_disp_group.hip", "neo_disp_depth.hip", "neo_disp_record.hip", "neo_disp_init.hip", "neo_disp_plan.hip", "neo_disp_fleet.hip", "neo_disp_adaptive.hip", "neo_disp_batch.hip"]
 JITTER_UNITS = ("neo_disp_plan.hip", "neo_disp_fleet.hip")
 
 
@@ -38,10 +38,10 @@ for src, err in results:
     print(f"---- {src}  ({' '.join(b._unit_flags(src)) or 'no unit options'})")
     for r, n in zip(recs, names):
         n = re.sub(r"\(.*$", "", n).replace("neo::", "")
-        if src in JITTER_UNITS:      # (of these two units only the jitter kernels are listed)
-            if "jitter_kernel" not in n:
+        if src in JITTER_UNITS:      # (of these two units only the jitter kernels and the plan chain's merge are listed)
+            if "jitter_kernel" not in n and "plan_merge_kernel" not in n:
                 continue
-        elif not (", 3>" in n or "sample_kernel" in n or "group" in n or "depth_" in n or "record_" in n or "init_" in n or "adaptive_" in n):
+        elif not ("_compact_kernel" in n or ", 3>" in n or "sample_kernel" in n or "group" in n or "depth_" in n or "record_" in n or "init_" in n or "adaptive_" in n):
             continue
         if "sample_kernel" in n and "Lookup3D" in n and not re.search(r"Lookup3D<\w+, \w+, 3>", n):
             continue
