@@ -140,6 +140,7 @@ struct Lookup2D {
   struct Raw {
     double4 r;
   };
+  static constexpr bool gather_ahead = false;  // (one record a sample: the sample loop stays as it is, minco_sample)
   // `on` = false (an idle sample slot): treated like a point outside the map, so that all idle lanes of a
   // wavefront read one and the same record instead of 64 scattered ones
   template <int D>
@@ -245,6 +246,14 @@ struct Lookup3D {
   struct Raw {
     float c[2][2][2];
   };
+  // the gather-ahead form of the sample loop (minco_sample) exists for this lookup on fp32 fields (fp16 fields: the brick
+  // members spill 5 - 10 vector registers in that form and keep the blocked loop); pin(): the loaded corners as opaque
+  // copies, made where the call stands
+  static constexpr bool gather_ahead = sizeof(E) == 4;
+  static __device__ __forceinline__ void pin(Raw &q) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) q.c[k >> 2][(k >> 1) & 1][k & 1] = opaque(q.c[k >> 2][(k >> 1) & 1][k & 1]);
+  }
 
   // `on` = false (an idle sample slot): treated like a point outside the field -- corner (0,0,0) for every
   // idle lane, i.e. one cache line per wavefront instead of 64 scattered gathers
@@ -537,6 +546,7 @@ struct PlanDynamic {
   static constexpr bool dynamic = true;
   static constexpr bool fold_acc = false, fold_rows = false, pcr_mult = false, pcr_xch = false, sl_cache = false,
                         trace = false, coeff_out = false;  // (not read: every selector is the run-time value)
+  static constexpr bool gather_ahead = false;  // the sample loop as it always was (minco_sample)
 };
 // the plan opt_lds_plan produces for the all-fp32 kernels with lane = (piece, dimension) and n <= 128 variables:
 // accumulator fold, multipliers in LDS, exchange table in the staging buffer, lane cache, no trace, no coefficient store
@@ -544,6 +554,9 @@ struct PlanFixedX {
   static constexpr bool dynamic = false;
   static constexpr bool fold_acc = true, fold_rows = true, pcr_mult = true, pcr_xch = true, sl_cache = true,
                         trace = false, coeff_out = false;
+  // not a launch decision but a form of the sample loop only this plan's kernels take: the ESDF gathers of a round are
+  // issued one round ahead of their use (minco_sample)
+  static constexpr bool gather_ahead = true;
 };
 // a selector under a plan: its run-time value when the plan is dynamic, the plan's constant K otherwise
 template <class Plan, bool K>
@@ -1355,6 +1368,9 @@ __device__ __forceinline__ SampleLanes group_sample_lanes(int M, int ns_piece) {
 // are optimisation variables, so the pieces of a trajectory under optimisation differ widely in length: with
 // the same three lanes for every piece the longest piece sets the rounds (cfg2: 8.6 on average against 4.9 for a
 // perfect split).  ns_piece: PIECE layout (lane p < M).  seg: 64 ints of LDS scratch.
+// KEY_HERE: the lane's part of the segment key is formed where it is stored (hoisted out of the optimiser loop it is a
+// register held across every phase -- the one the kernels with the gather-ahead sample loop would spill).
+template <bool KEY_HERE = false>
 __device__ __forceinline__ SampleLanes balanced_sample_lanes(int M, int ns_piece, int *seg) {
   const int lane = lane_id();
   // `seg` is the caller's staging buffer seen as ints; the caller has just READ it as its own type (scatter_x: the
@@ -1379,7 +1395,7 @@ __device__ __forceinline__ SampleLanes balanced_sample_lanes(int M, int ns_piece
   const int start = incl - Lp;
   seg[lane] = 0;
   lds_wave_sync();
-  if (Lp > 0) seg[start] = ((lane + 1) << 16) | (Lp << 8) | start;
+  if (Lp > 0) seg[start] = (((KEY_HERE ? opaque(lane) : lane) + 1) << 16) | (Lp << 8) | start;
   lds_wave_sync();
   const int key = wave_scan_max_nonneg(seg[lane]);  // the segment this lane falls in: the last start at or before it
   lds_wave_sync();                                  // (seg is the caller's staging buffer again after this)
@@ -1522,10 +1538,57 @@ __device__ __forceinline__ void minco_sample(int M, const SampleLanes &sl, int n
     for (int d = 0; d < D; ++d) aC[k][d] = Real(0);
   Real aT = Real(0), aF = Real(0), aK = Real(0);
 
-  // U samples per lane are prepared together and their gathers issued back to back before any of
-  // them is consumed
   NEO_MARK("loop_begin");
-  for (int it0 = 0; it0 < iters; it0 += U) {
+  // A plan with `gather_ahead` (one sample per lane in flight, fused fp32 kernels): the gathers of round i + 1 are issued
+  // before round i is consumed, so a round's memory latency runs under the arithmetic of the round before it instead of
+  // in series with it.  Between issue and use only the eight corners, the three fractions and the inside mask are
+  // held; the sample index, its time and the velocity are formed again from the round counter when the round is
+  // consumed -- the same expressions on the same inputs, rounds and lanes in the same order: the same bits as the loop
+  // below.  In a round ahead, lanes whose piece has run out of samples park on cell 0 (prepare with on = false).  The
+  // last round is consumed after the loop with nothing in flight.
+  constexpr bool kAhead = !Plan::dynamic && Plan::gather_ahead && LookupT::gather_ahead && U == 1 && !SAMPLE_IO && sizeof(Real) == 4;
+  if constexpr (kAhead) {
+    auto ahead = [&](int it) {  // addresses of round `it`
+      const int j = r + it * L;
+      const Real s = (Real)((double)j * prm.delta_t);
+      Real pos[D], vdrop[D];
+      piece_pos_vel<Real, D>(c, s, pos, vdrop);
+      return lk.template prepare<D>(pos, j < ns);
+    };
+    auto consume = [&](int it, const typename LookupT::Addr &ad, const typename LookupT::Raw &rw) {
+      const int j = r + it * L;
+      const bool on = j < ns;
+      const Real s = (Real)((double)j * prm.delta_t);  // beta_full row j: t = j * delta_t (:251)
+      Real pos[D], vel[D];
+      piece_pos_vel<Real, D>(c, s, pos, vel);
+      Real v2 = Real(0);
+#pragma unroll
+      for (int d = 0; d < D; ++d) v2 += vel[d] * vel[d];
+      const Real vv = v2 - vmax2;
+      Real gdrop[D];
+      const Real vd = safe - lk.template finish<D>(ad, rw, gdrop);
+      const bool any_violation = on && (vv > Real(0) || vd > Real(0));
+      if (any_violation) sample_accumulate<Real, D, LookupT>(c, j, ns, s, inv_ns, vel, vv, vd, lk, ad, rw, dt, w2, w3, aC, aT, aF, aK);
+    };
+    if (iters > 0) {
+      typename LookupT::Addr ad = ahead(0);
+      typename LookupT::Raw rw = lk.load(ad);
+      for (int it = 0; it + 1 < iters; ++it) {
+        const typename LookupT::Addr adn = ahead(it + 1);
+        // (opaque: this round's corners leave the registers the gathers write HERE, after the next round's address
+        // arithmetic and before its gathers -- as copies at the loop's end they would put the wait for the gathers there)
+        LookupT::pin(rw);
+        const typename LookupT::Raw rwn = lk.load(adn);
+        consume(it, ad, rw);
+        ad = adn;
+        rw = rwn;
+      }
+      consume(iters - 1, ad, rw);
+    }
+  }
+  // every other kernel: U samples per lane are prepared together and their gathers issued back to back before any of
+  // them is consumed
+  for (int it0 = 0; it0 < (kAhead ? 0 : iters); it0 += U) {
     Real sv[U], vel[U][D];
     typename LookupT::Addr ad[U];
     typename LookupT::Raw rw[U];
@@ -1724,7 +1787,9 @@ __device__ __forceinline__ void minco_sample(int M, const SampleLanes &sl, int n
   if constexpr (!SAMPLE_IO) {
     // back to the lanes of the piece (sl.first is held by lane p for piece p)
     int src = LG::base() + sl.first;
-    if constexpr (LG::S > 1) src = __shfl(sl.first, LG::piece(), kWave);
+    // (gather-ahead kernels: the shuffle's address is formed here -- hoisted out of the optimiser loop it is one register more
+    //  than they have)
+    if constexpr (LG::S > 1) src = __shfl(sl.first, kAhead ? opaque(LG::piece()) : LG::piece(), kWave);
 #pragma unroll
     for (int q = 0; q < 6 * D + 3; ++q) fv[q] = __shfl(fv[q], src, kWave);
   }

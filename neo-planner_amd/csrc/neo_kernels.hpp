@@ -19,7 +19,11 @@
 #define NEO_FUSED_U (sizeof(Real) == 4 ? 4 : 2)
 #endif
 #ifndef NEO_W2_U
-#define NEO_W2_U 1  // (one sample per lane in flight: the two-waves variant then has no VGPR spills; 2 -> 7 % slower)
+// one sample per lane in the blocked sample loop: no VGPR spills.  2: cfg2's all-fp32 member spills 7 registers (32 B of
+// scratch) on the current tree and was not timed again; the last timing of the blocked form, with 13 spilled, read 1.437 M
+// against 1.513 M traj/s.  What overlaps a round's gathers with arithmetic in that member is the gather-ahead loop
+// (neo_device.hpp Plan::gather_ahead), which keeps U = 1: +2.0 %, HISTORY.md
+#define NEO_W2_U 1
 #endif
 #ifndef NEO_W2_OCC
 #define NEO_W2_OCC 2  // wavefronts per SIMD the throughput variant is allocated for (experiments: 3)
@@ -85,6 +89,8 @@ struct DevBackend {
   // (measured again after the spills had gone: in the lane = (piece, dimension) kernel the fp64 reduction fits the
   // registers -- 251 of 256, no spills -- and changes nothing: 774 k traj/s either way)
   static constexpr bool kPcr = sizeof(Num) == 4 && LG::W == kWave;
+  // the sample loop runs in its gather-ahead form (minco_sample): a plan's constant, for the lookups that have the form
+  static constexpr bool kAhead = !Plan::dynamic && Plan::gather_ahead && LookupT::gather_ahead && SU == 1 && sizeof(Real) == 4;
   // FLAT layout with NS slots: n <= 64 * NS
   struct Vec {
     Num v[NS];
@@ -394,7 +400,7 @@ struct DevBackend {
         sl.lmax = __builtin_amdgcn_readfirstlane(sl_cache[kWave / 4 + kWave + 1]);
         sl.total = __builtin_amdgcn_readfirstlane(sl_cache[kWave / 4 + kWave + 2]);
       } else {
-        sl = balanced_sample_lanes(t.M, ns_by_piece, reinterpret_cast<int *>(xs));
+        sl = balanced_sample_lanes<kAhead>(t.M, ns_by_piece, reinterpret_cast<int *>(xs));
         if (have_cache) {
           // one byte a lane for the key (sample counts stay below T_max / delta_t; 255 = never equal), one word for the
           // assignment; a piece with more than 63 lanes (M = 1) does not fit the word's six bits: not cached
@@ -430,6 +436,14 @@ struct DevBackend {
     Num gq[DL], gtau;
     NEO_MARK("sample_done");
     t.M = opaque_uniform(M_all);
+    if constexpr (kAhead && sizeof(Num) == 4) {
+      // the powers of 1 / T are formed again for the adjoint by minco_forward's expressions (the same bits) instead of
+      // being held across the sample phase: three registers for the round the sample loop keeps in flight
+      const Num i1 = opaque(t.i1);
+      t.i2 = i1 * i1;
+      t.i3 = t.i2 * i1;
+      t.i4 = t.i2 * t.i2;
+    }
     const int bst = minco_backward<D, LG, Num, kPcr, Plan>(t, prm, gC, gT, gq, gtau);
     NEO_MARK("backward_done");
     if (bst != 0) return bst;

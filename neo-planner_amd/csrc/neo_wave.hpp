@@ -45,6 +45,10 @@ __device__ __forceinline__ int opaque(int v) {
   asm volatile("" : "+v"(v));
   return v;
 }
+__device__ __forceinline__ float opaque(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
 // the same for a wave-uniform value (it stays in a scalar register)
 __device__ __forceinline__ int opaque_uniform(int v) {
   asm volatile("" : "+s"(v));

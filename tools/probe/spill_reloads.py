@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """SGPR spill traffic of optimize_kernel by NEO_MARK region (listing built with -DNEO_MARKS -S): v_writelane into / v_readlane
 out of the vector registers the allocator uses as scalar spill space.  Every reload inside the optimiser loop is a
-vector-pipe instruction.   python3 tools/probe/spill_reloads.py /tmp/marks.s 'Li2EfNS_5Map3D.*WaveLanesPD'"""
+vector-pipe instruction.   python3 tools/probe/spill_reloads.py /tmp/marks.s 'Li2EfNS_5Map3D.*WaveLanesPD'
+The listing is the one of mark_counts.py: on the current tree the whole unit with -DNEO_MARKS -S, no patch applied (about two
+minutes)."""
 import re, sys, collections
 lines = open(sys.argv[1]).read().split("\n")
 pat = re.compile(sys.argv[2])
