@@ -528,6 +528,65 @@ int neo_fleet_audit_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_i
                               int n_subset, const double *cmd, int cap, const int32_t *n_flown, int stride,
                               double cmd_hz, const double *weights3, double *audit, int32_t *count, int32_t *flags);
 
+/* ---- fleet goal routes (ros_node/tracker_planner_node.py: a goal that keeps moving) ----------------
+ * A mission's goal moves along a polyline at constant speed (csrc/neo_track.hpp; neo_planner_amd.goal_routes.GoalRoutes
+ * is its NumPy model, bit for bit).  The routes are a ragged table laid out as the depth camera's box_begin is:
+ *   vertices[n_vertices][2]   the points of all routes, one route after the other;
+ *   route_begin[B + 1]        mission b's points are vertices[route_begin[b] .. route_begin[b + 1]): 2 to
+ *                             NEO_FLEET_ROUTE_MAX of them;
+ *   speed[B]                  metres a second along the route, >= 0;
+ *   closed[B]                 != 0: the route gets the closing segment back to its first point (NULL: all open).
+ * The point at time t: seg_k = sqrt(dx * dx + dy * dy), cum their sequential running sum from cum_0 = 0, s = speed * t,
+ * closed: s = fmod(s, total), open: s = min(s, total); k the largest index with cum_k <= s, at most the last segment;
+ * v_k + ((s - cum_k) / seg_k) * (v_{k+1} - v_k), and v_k itself where seg_k or the total is 0.  Every operation is
+ * rounded on its own.  A mission whose route has fewer than 2 or more than NEO_FLEET_ROUTE_MAX points, or points outside
+ * the table, gets a NaN goal / a NaN record; no other row is touched.
+ * Everything is indexed by MISSION, fp64; `subset` as for the other fleet calls; same bits whatever the subset, its
+ * order and the launch.  NEO_ERR_INVALID before any launch, with a neo_last_error message: a NULL required buffer,
+ * B < 0, a bad subset size, n_vertices < 0, step, stride or cap < 1, step > 2^30, a cmd that is not 16-byte aligned
+ * (hold), a cmd_hz that is not finite and > 0, a t or radius that is not finite. */
+#define NEO_FLEET_ROUTE_MAX 256
+#define NEO_TRACK_FIELDS 8
+enum {
+  NEO_TRACK_GAP_MEAN = 0,       /* mean distance between the flown position and the goal, over the samples */
+  NEO_TRACK_GAP_MAX = 1,        /* the largest gap ... */
+  NEO_TRACK_T_GAP_MAX = 2,      /* ... and its time; the first sample wins ties */
+  NEO_TRACK_GAP_MIN = 3,        /* the smallest gap ... */
+  NEO_TRACK_T_GAP_MIN = 4,      /* ... and its time; the first sample wins ties */
+  NEO_TRACK_GAP_FINAL = 5,      /* the gap at the last sample */
+  NEO_TRACK_T_FIRST_WITHIN = 6, /* time of the first sample with gap <= radius, or -1 */
+  NEO_TRACK_FRAC_WITHIN = 7     /* samples with gap <= radius over count */
+};
+/* goal[b] = the point of mission b's route at time t, one lane per mission: goal[B][2]. */
+int neo_fleet_goal_route(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const double *vertices,
+                         int n_vertices, const int32_t *route_begin, const double *speed, const int32_t *closed,
+                         double t, double *goal);
+/* the same with DEVICE pointers, asynchronous on the context's stream */
+int neo_fleet_goal_route_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const double *vertices,
+                             int n_vertices, const int32_t *route_begin, const double *speed, const int32_t *closed,
+                             double t, double *goal);
+/* a drone that runs out of commands holds the last one (tracker_planner_node.py:387-391 re-reads that row), one
+ * wavefront per mission, in front of neo_fleet_advance_dev: with need = cmd_index[b] + step + 1, a mission with
+ * 1 <= cmd_len[b] < need gets copies of row cmd_len[b] - 1 (position, velocity and acceleration as they are) appended
+ * up to min(need, cap) rows, cmd_len[b] becomes that, and need > cap raises NEO_FLEET_FLAG_CMD_FULL.  After it row i of
+ * the mission is its command at time i / cmd_hz.  cmd must be 16-byte aligned.  Device pointers only. */
+int neo_fleet_hold_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, double *cmd, int cap,
+                       int32_t *cmd_len, const int32_t *cmd_index, int step, int32_t *flags);
+/* how well the flown rows followed the moving goal, one wavefront per mission: sample j is row j * stride of cmd[b],
+ * j * stride < n_flown[b] (clamped to 0 .. cap), at time t_j = (j * stride) / cmd_hz; its gap is the square root of the
+ * squared distance between the row's position and the route's point at t_j.  track[B][NEO_TRACK_FIELDS] as the enum
+ * above, count[B] the samples, flags[B] written (not OR-ed): 0, or NEO_AUDIT_FLAG_NONFINITE with a NaN record and count 0
+ * for a sampled row or gap that is not finite and for a bad route.  No samples: a NaN record, count 0, flags 0.  The
+ * mean is the sum over count; each lane sums its own samples in time order, the lanes are combined in a fixed order. */
+int neo_fleet_track_audit(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                          const int32_t *n_flown, int stride, double cmd_hz, const double *vertices, int n_vertices,
+                          const int32_t *route_begin, const double *speed, const int32_t *closed, double radius,
+                          double *track, int32_t *count, int32_t *flags);
+int neo_fleet_track_audit_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                              const int32_t *n_flown, int stride, double cmd_hz, const double *vertices,
+                              int n_vertices, const int32_t *route_begin, const double *speed, const int32_t *closed,
+                              double radius, double *track, int32_t *count, int32_t *flags);
+
 /* ---- fleet record mode (traj_planner/record_planner.py:13-72, :152-185) ----------------
  * What the reference's `record` planner saves of every successful plan, for the missions of a fleet: one row of a
  * RESIDENT dataset of `capacity` rows, caller-owned DEVICE buffers:

@@ -1670,6 +1670,134 @@ int neo_fleet_audit_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, in
   return st.download();
 }
 
+// ---- fleet goal routes (ros_node/tracker_planner_node.py; kernels: neo_track.hpp)
+static int fleet_routes_check(neo_ctx *c, const char *who, const double *vertices, int n_vertices,
+                              const int32_t *route_begin, const double *speed) {
+  if (!vertices || !route_begin || !speed)
+    return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": null buffer").c_str());
+  if (n_vertices < 0) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": n_vertices must be >= 0").c_str());
+  return NEO_OK;
+}
+
+static int fleet_goal_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *vertices, int n_vertices,
+                            const int32_t *route_begin, const double *speed, double t, const double *goal) {
+  int rc = list_check(c, "fleet goal", B, 0, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  rc = fleet_routes_check(c, "fleet goal", vertices, n_vertices, route_begin, speed);
+  if (rc) return rc;
+  if (!goal) return fail_locked(c, NEO_ERR_INVALID, "fleet goal: null buffer");
+  if (!std::isfinite(t)) return fail_locked(c, NEO_ERR_INVALID, "fleet goal: t must be finite");
+  return NEO_OK;
+}
+
+int neo_fleet_goal_route_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *vertices, int n_vertices,
+                             const int32_t *route_begin, const double *speed, const int32_t *closed, double t,
+                             double *goal) {
+  int rc = fleet_goal_check(c, B, subset, n_subset, vertices, n_vertices, route_begin, speed, t, goal);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, fleet_goal(c, list, {vertices, n_vertices, route_begin, speed, closed}, t, goal));
+}
+
+int neo_fleet_goal_route(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *vertices, int n_vertices,
+                         const int32_t *route_begin, const double *speed, const int32_t *closed, double t, double *goal) {
+  int rc = fleet_goal_check(c, B, subset, n_subset, vertices, n_vertices, route_begin, speed, t, goal);
+  if (rc) return rc;
+  if (launch_list(B, subset, n_subset).n == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  const size_t bs = (size_t)B;
+  // the rows go up too: missions outside the subset keep theirs
+  HostStage st(c, kStagedUpTo);
+  const auto fv = st.in(vertices, (size_t)n_vertices * 2, 2), fs = st.in(speed, bs);
+  const auto fb = st.in(route_begin, bs + 1);
+  const auto fc = st.in_optional(closed, bs), fsub = st.in_optional(subset, (size_t)n_subset);
+  const auto fg = st.inout(goal, bs * 2);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_fleet_goal_route_dev(c, B, st.dev(fsub), n_subset, st.dev(fv), n_vertices, st.dev(fb), st.dev(fs), st.dev(fc), t,
+                                st.dev(fg));
+  if (rc) return rc;
+  return st.download();
+}
+
+int neo_fleet_hold_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, double *cmd, int cap, int32_t *cmd_len,
+                       const int32_t *cmd_index, int step, int32_t *flags) {
+  int rc = list_check(c, "fleet hold", B, 0, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  if (!cmd || !cmd_len || !cmd_index || !flags) return fail_locked(c, NEO_ERR_INVALID, "fleet hold: null buffer");
+  if (cap < 1) return fail_locked(c, NEO_ERR_INVALID, "fleet hold: cap must be >= 1");
+  if (step < 1 || step > (1 << 30)) return fail_locked(c, NEO_ERR_INVALID, "fleet hold: step must be in 1 .. 2^30");
+  if (reinterpret_cast<uintptr_t>(cmd) & 15) return fail_locked(c, NEO_ERR_INVALID, "fleet hold: cmd must be 16-byte aligned");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, fleet_hold(c, list, {cmd, cap, cmd_len, const_cast<int32_t *>(cmd_index), nullptr}, step, flags));
+}
+
+static int fleet_track_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                             const int32_t *n_flown, int stride, double cmd_hz, const double *vertices, int n_vertices,
+                             const int32_t *route_begin, const double *speed, double radius, const double *track,
+                             const int32_t *count, const int32_t *flags) {
+  int rc = list_check(c, "fleet track audit", B, 0, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  rc = fleet_routes_check(c, "fleet track audit", vertices, n_vertices, route_begin, speed);
+  if (rc) return rc;
+  if (!cmd || !n_flown || !track || !count || !flags) return fail_locked(c, NEO_ERR_INVALID, "fleet track audit: null buffer");
+  if (cap < 1) return fail_locked(c, NEO_ERR_INVALID, "fleet track audit: cap must be >= 1");
+  if (stride < 1) return fail_locked(c, NEO_ERR_INVALID, "fleet track audit: stride must be >= 1");
+  if (!fleet_positive(cmd_hz)) return fail_locked(c, NEO_ERR_INVALID, "fleet track audit: cmd_hz must be finite and > 0");
+  if (!std::isfinite(radius)) return fail_locked(c, NEO_ERR_INVALID, "fleet track audit: radius must be finite");
+  return NEO_OK;
+}
+
+int neo_fleet_track_audit_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                              const int32_t *n_flown, int stride, double cmd_hz, const double *vertices, int n_vertices,
+                              const int32_t *route_begin, const double *speed, const int32_t *closed, double radius,
+                              double *track, int32_t *count, int32_t *flags) {
+  int rc = fleet_track_check(c, B, subset, n_subset, cmd, cap, n_flown, stride, cmd_hz, vertices, n_vertices, route_begin,
+                             speed, radius, track, count, flags);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  const LaunchList list = launch_list(B, subset, n_subset);
+  if (list.n == 0) return NEO_OK;
+  return launched(c, fleet_track_audit(c, list, {vertices, n_vertices, route_begin, speed, closed},
+                                       {cmd, cap, n_flown, stride, cmd_hz, radius, track, count, flags}));
+}
+
+int neo_fleet_track_audit(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
+                          const int32_t *n_flown, int stride, double cmd_hz, const double *vertices, int n_vertices,
+                          const int32_t *route_begin, const double *speed, const int32_t *closed, double radius,
+                          double *track, int32_t *count, int32_t *flags) {
+  int rc = fleet_track_check(c, B, subset, n_subset, cmd, cap, n_flown, stride, cmd_hz, vertices, n_vertices, route_begin,
+                             speed, radius, track, count, flags);
+  if (rc) return rc;
+  if (launch_list(B, subset, n_subset).n == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  const size_t bs = (size_t)B;
+  HostStage st(c, 0);
+  const auto fc = st.in(cmd, bs * cap * 6);
+  const auto fnf = st.in(n_flown, bs);
+  const auto fv = st.in(vertices, (size_t)n_vertices * 2, 2), fs = st.in(speed, bs);
+  const auto fb = st.in(route_begin, bs + 1);
+  const auto fcl = st.in_optional(closed, bs), fsub = st.in_optional(subset, (size_t)n_subset);
+  const auto ft = st.inout(track, bs * NEO_TRACK_FIELDS);  // (missions outside the subset keep their records)
+  const auto fcnt = st.inout(count, bs), ffl = st.inout(flags, bs);
+  rc = st.upload();
+  if (rc) return rc;
+  rc = neo_fleet_track_audit_dev(c, B, st.dev(fsub), n_subset, st.dev(fc), cap, st.dev(fnf), stride, cmd_hz, st.dev(fv),
+                                 n_vertices, st.dev(fb), st.dev(fs), st.dev(fcl), radius, st.dev(ft), st.dev(fcnt),
+                                 st.dev(ffl));
+  if (rc) return rc;
+  return st.download();
+}
+
 // ---- the fleet's record mode (traj_planner/record_planner.py:13-72; kernels: neo_record.hpp)
 int neo_record_state_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
                          const int32_t *cmd_len, const int32_t *cmd_index, const double *head, double *cur_vel) {

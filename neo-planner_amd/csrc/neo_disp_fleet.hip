@@ -1,8 +1,9 @@
-// neo_disp_fleet.hip -- the fleet kernels (neo_fleet.hpp): local targets, tracking and look-ahead, the splice of a new
+// neo_disp_fleet.hip -- the fleet kernels (neo_fleet.hpp; goal routes: neo_track.hpp): local targets, tracking and look-ahead, the splice of a new
 // plan into the resident command array and the flight metric of what was flown (ros_node/traj_planner_node.py:333-363,
 // :450-488, :527-537, :574-578) for B missions.  2-D reference map, D = 2: one instantiation each.
 #include "neo_host.hpp"
 #include "neo_fleet.hpp"
+#include "neo_track.hpp"
 
 namespace neo {
 
@@ -60,6 +61,24 @@ int fleet_audit(neo_ctx *c, const LaunchList &l, const MapRef &m, const FleetAud
   hipLaunchKernelGGL(fleet_audit_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, c->dev,
                      static_cast<const Map2D *>(m.table), m.slots, m.nmaps, a.cmd, a.cap, a.n_flown, a.stride, a.hz, a.w[0],
                      a.w[1], a.w[2], a.audit, a.count, a.flags);
+  return NEO_OK;
+}
+
+int fleet_goal(neo_ctx *c, const LaunchList &l, const FleetRoutes &r, double t, double *goal) {
+  hipLaunchKernelGGL(fleet_goal_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l, r.vertices, r.n_vertices,
+                     r.route_begin, r.speed, r.closed, t, goal);
+  return NEO_OK;
+}
+
+int fleet_hold(neo_ctx *c, const LaunchList &l, const FleetCmd &m, int step, int *flags) {
+  hipLaunchKernelGGL(fleet_hold_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, m.cmd, m.cap, m.cmd_len, m.cmd_index, step,
+                     flags);
+  return NEO_OK;
+}
+
+int fleet_track_audit(neo_ctx *c, const LaunchList &l, const FleetRoutes &r, const FleetTrackArgs &a) {
+  hipLaunchKernelGGL(fleet_track_audit_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.cmd, a.cap, a.n_flown, a.stride,
+                     a.hz, r.vertices, r.n_vertices, r.route_begin, r.speed, r.closed, a.radius, a.track, a.count, a.flags);
   return NEO_OK;
 }
 

@@ -260,6 +260,27 @@ struct FleetWarmCarryArgs {
 int fleet_warm_guess(neo_ctx *c, const LaunchList &l, int M, const double *head, const double *wpts_local,
                      const double *ts_carry, double *x0);
 int fleet_warm_carry(neo_ctx *c, const LaunchList &l, const FleetWarmCarryArgs &a);
+// goal routes (kernels in neo_track.hpp): the ragged route table, by mission
+struct FleetRoutes {
+  const double *vertices;  // [n_vertices][2]
+  int n_vertices;
+  const int *route_begin;  // [B + 1]
+  const double *speed;     // [B]
+  const int *closed;       // [B], or NULL: all open
+};
+struct FleetTrackArgs {
+  const double *cmd;
+  int cap;
+  const int *n_flown;
+  int stride;
+  double hz, radius;
+  double *track;
+  int *count, *flags;
+};
+int fleet_goal(neo_ctx *c, const LaunchList &l, const FleetRoutes &r, double t, double *goal);
+// rows appended to a command array that ends before cmd_index + step + 1 (m.future_index is not used)
+int fleet_hold(neo_ctx *c, const LaunchList &l, const FleetCmd &m, int step, int *flags);
+int fleet_track_audit(neo_ctx *c, const LaunchList &l, const FleetRoutes &r, const FleetTrackArgs &a);
 
 // neo_record_*_dev: the fleet's `record` mode (neo_disp_record.hip, kernels in neo_record.hpp).  Every pointer is a
 // device array; the arguments were checked by the C ABI.

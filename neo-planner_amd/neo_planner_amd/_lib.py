@@ -31,6 +31,10 @@ NEO_GEO_FLAG_BAD_SCENE = 16
 # neo_fleet_*: flag bits of a mission
 NEO_FLEET_FLAG_TARGET_CAPPED, NEO_FLEET_FLAG_CMD_FULL, NEO_FLEET_FLAG_BAD_SCENE, NEO_FLEET_FLAG_SPLICE_FAILED = 1, 2, 4, 8
 NEO_FLEET_FLAG_ABANDONED = 16
+# neo_fleet_goal_route / neo_fleet_track_audit: vertices a route, fields of a tracking record
+NEO_FLEET_ROUTE_MAX = 256
+TRACK_FIELDS = ("gap_mean", "gap_max", "t_gap_max", "gap_min", "t_gap_min", "gap_final", "t_first_within", "frac_within")
+NEO_TRACK_FIELDS = len(TRACK_FIELDS)
 NEO_MAX_PIECES = 64                # M of any trajectory; neo_adaptive_*: one group per waypoint count below it
 NEO_BATCH_MAX_CANDIDATES = 8       # neo_batch_*: candidates a request
 NEO_DEPTH_MAX_BOXES = 1024         # neo_depth_*: boxes a scene
@@ -63,6 +67,8 @@ EXPORTS = [
     "neo_adaptive_count", "neo_adaptive_count_dev", "neo_adaptive_bucket", "neo_adaptive_bucket_dev",
     "neo_adaptive_merge_dev", "neo_adaptive_compact", "neo_adaptive_compact_dev",
     "neo_fleet_warm_guess_dev", "neo_fleet_warm_carry_dev",
+    "neo_fleet_goal_route", "neo_fleet_goal_route_dev", "neo_fleet_hold_dev", "neo_fleet_track_audit",
+    "neo_fleet_track_audit_dev",
 ]
 
 
@@ -150,6 +156,11 @@ def load():
     L.neo_fleet_jitter_dev.argtypes = [c_p, c_i, c_p, c_i, ctypes.c_uint64, c_i, c_i, c_p, c_p]
     L.neo_fleet_warm_guess_dev.argtypes = [c_p, c_i, c_p, c_i, c_i] + [c_p] * 4
     L.neo_fleet_warm_carry_dev.argtypes = [c_p, c_i, c_p, c_i, c_i] + [c_p] * 8
+    L.neo_fleet_goal_route.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_d, c_p]
+    L.neo_fleet_goal_route_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_d, c_p]
+    L.neo_fleet_hold_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p]
+    L.neo_fleet_track_audit.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_d, c_p, c_i, c_p, c_p, c_p, c_d] + [c_p] * 3
+    L.neo_fleet_track_audit_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_d, c_p, c_i, c_p, c_p, c_p, c_d] + [c_p] * 3
     L.neo_adaptive_count.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p]
     L.neo_adaptive_count_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p]
     L.neo_adaptive_bucket.argtypes = [c_p, c_i, c_p, c_i] + [c_p] * 4

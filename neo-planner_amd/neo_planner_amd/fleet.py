@@ -51,6 +51,19 @@ duration the reference's map_T2tau raises for (one saturated to T_min or T_max) 
 first evaluation, uncounted, and plan_dev re-seeds from the straight line, as warm_start_plan does when it catches the
 exception.  Resident plans always; works with onboard, record and both jitter settings; no host read is added.
 
+With goal_routes=GoalRoutes the missions chase goals that keep moving (ros_node/tracker_planner_node.py with
+tracker_manager_node.py): every mission's goal moves along its polyline at constant speed (goal_routes.py is the model of
+csrc/neo_track.hpp, bit for bit).  Tick k is at time (k * step) / cmd_hz, step = round(replan_period * cmd_hz).  Per tick
+neo_fleet_hold_dev runs in front of the advance -- a mission whose commands end before the coming period is over holds
+its last one, so row i of its array is its command at time i / cmd_hz, always -- and neo_fleet_goal_route_dev writes the
+active missions' resident goals before sensing and the targets, tick 0 included.  Closer than longitu_step_dis the local
+target is the goal itself with zero velocity (:319-321) and planning goes on: `near` lands nobody.  A tick whose 11
+targets all fail counts in failed_ticks and the mission flies on along its old commands (:265-279); only CMD_FULL and
+SPLICE_FAILED end a mission, and the run lasts max_replans ticks.  At the end the flight metric takes the tracker node's
+weights (1, 1, 1) (:175) and neo_fleet_track_audit_dev measures the gap between the flown rows and the goal at their times.
+The hooks are the same for every mode but "geo" (the tracker node has no geo planner), resident or not, with onboard,
+record and both jitters.  Without goal_routes no launch, host read or allocation is added.
+
 A mission's flight does not depend on which other missions share the fleet: the kernels work per mission, the target
 jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
 retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream_ids`).  With jitter="counter" both come
@@ -63,6 +76,7 @@ import time
 import numpy as np
 
 from . import _lib, counter_rng
+from .goal_routes import GoalRoutes
 
 MAX_TARGETS = 11        # :429-445: seed 0 .. 10 are planned, the mission is abandoned after the plan of target 10 fails
 
@@ -117,16 +131,44 @@ class FleetReplanLoop:
     plan_dev); the first plan is a basic plan; resident plans always; with onboard, record and either jitter.
     jitter "numpy" (one NumPy generator per mission and draw, on the host) or "counter" (every mode, resident or not): the
     target jitter of a round is drawn by neo_fleet_jitter_dev on the context's stream in front of the target kernel, and
-    every plan call gets jitter="counter"; mission ids in 0 .. 2^31 - 1 and a seed in 0 .. 2^64 - 1."""
+    every plan call gets jitter="counter"; mission ids in 0 .. 2^31 - 1 and a seed in 0 .. 2^64 - 1.
+    goal_routes: a GoalRoutes (goal_routes.py) of B routes -- the goals move, `goals` may be None (the goals are the
+    routes at t = 0) and mode "geo" is refused.  run() then flies max_replans ticks without landing anybody; its result
+    gains the eight track_* fields (gap_mean, gap_max, t_gap_max, gap_min, t_gap_min, gap_final, t_first_within,
+    frac_within: within track_radius metres of the goal), track_count, track_flags, failed_ticks and goal_final;
+    final_dist is the distance to goal_final, n_flown = cmd_index + 1 and success = nothing went wrong (flags == 0, no
+    metric failure).  metric_weights (3,): the flight metric's weights; None: the audit's default (1, 1, 100) for fixed
+    goals, the tracker node's (1, 1, 1) with routes."""
 
     def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
                  longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
                  scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False, onboard=None, scenes=None,
-                 scene_index=None, des_pos_z=2.0, record_poses=False, record=None, neo=None, jitter="numpy"):
+                 scene_index=None, des_pos_z=2.0, record_poses=False, record=None, neo=None, jitter="numpy",
+                 goal_routes=None, track_radius=1.0, metric_weights=None):
         self.counter = counter_rng.check_jitter(jitter, "FleetReplanLoop")
         self.jitter = jitter
         if mode not in ("basic", "geo", "batch", "neo", "nn", "warmstart"):
             raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo', 'batch', 'neo', 'nn' or 'warmstart'")
+        self.routes = goal_routes
+        if goal_routes is not None:
+            if not isinstance(goal_routes, GoalRoutes):
+                raise ValueError("FleetReplanLoop: goal_routes must be a GoalRoutes")
+            if mode == "geo":
+                raise ValueError("FleetReplanLoop: goal routes need a mode other than 'geo' (the tracker node has no geo planner)")
+            if goals is not None and _lib.as_f64(goals).reshape(-1, 2).shape[0] != goal_routes.B:
+                raise ValueError("FleetReplanLoop: one goal route per mission")
+            goals = goal_routes.at(0.0)      # where the goals start
+        elif goals is None:
+            raise ValueError("FleetReplanLoop: goals may be None only with goal_routes")
+        self.track_radius = float(track_radius)
+        if not (np.isfinite(self.track_radius) and self.track_radius >= 0.0):
+            raise ValueError("FleetReplanLoop: track_radius must be finite and >= 0")
+        if metric_weights is None:      # the audit's default for a fixed goal, the tracker node's (1, 1, 1) (:175) with routes
+            self.metric_weights = None if goal_routes is None else np.ones(3)
+        else:
+            self.metric_weights = _lib.as_f64(metric_weights).reshape(-1)
+            if self.metric_weights.shape[0] != 3 or not np.all(np.isfinite(self.metric_weights)):
+                raise ValueError("FleetReplanLoop: metric_weights must be three finite numbers")
         learned = mode in ("neo", "nn")
         if learned:
             if neo is None:
@@ -306,8 +348,32 @@ class FleetReplanLoop:
     def _audit(self):
         c, d, p = self.bp.ctx, self._dev, self._p
         c.check(c.lib.neo_fleet_audit_batch_dev(c.h, self.map.scene_id, p(d["slots"]), self.B, None, 0, p(d["cmd"]),
-                                                self.cap, p(d["n_flown"]), self.stride, float(self.cmd_hz), None,
+                                                self.cap, p(d["n_flown"]), self.stride, float(self.cmd_hz),
+                                                None if self.metric_weights is None else _lib.ptr(self.metric_weights),
                                                 p(d["audit"]), p(d["count"]), p(d["audit_flags"])))
+
+    # ---- goal routes (csrc/neo_track.hpp): the hooks of a tracked flight, the same for every mode
+    def _hold(self, sub, step):
+        """a mission whose commands end before the coming replan period is over holds its last one"""
+        c, d, p = self.bp.ctx, self._dev, self._p
+        c.check(c.lib.neo_fleet_hold_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
+                                         p(d["cmd_index"]), int(step), p(d["flags"])))
+
+    def _routes_args(self):
+        d, p = self._dev, self._p
+        return p(d["vertices"]), int(d["vertices"].shape[0]), p(d["route_begin"]), p(d["speed"]), p(d["closed"])
+
+    def _goal(self, sub, t):
+        """the resident goals of the missions `sub` at time t"""
+        c, d, p = self.bp.ctx, self._dev, self._p
+        c.check(c.lib.neo_fleet_goal_route_dev(c.h, self.B, p(sub), int(sub.numel()), *self._routes_args(), float(t),
+                                               p(d["goal"])))
+
+    def _track_audit(self):
+        c, d, p = self.bp.ctx, self._dev, self._p
+        c.check(c.lib.neo_fleet_track_audit_dev(c.h, self.B, None, 0, p(d["cmd"]), self.cap, p(d["n_flown"]), self.stride,
+                                                float(self.cmd_hz), *self._routes_args(), self.track_radius, p(d["track"]),
+                                                p(d["track_count"]), p(d["track_flags"])))
 
     def _alloc(self, n):
         import torch
@@ -348,6 +414,11 @@ class FleetReplanLoop:
             self.record.T_min, self.record.T_max = float(self.bp.cfg.T_min), float(self.bp.cfg.T_max)   # what rows() maps tau with
         if self.record is not None or self.counter:
             self._dev["mission_ids"] = self._subset(self.mission_ids)
+        if self.routes is not None:      # the route table, and what the track audit writes
+            r = self.routes
+            self._dev.update(vertices=torch.from_numpy(r.vertices).to(dev), route_begin=torch.from_numpy(r.route_begin).to(dev),
+                             speed=torch.from_numpy(r.speed).to(dev), closed=torch.from_numpy(r.closed).to(dev),
+                             track=f(B, _lib.NEO_TRACK_FIELDS), track_count=i(B), track_flags=i(B))
         self._poses, self._sensed = [], []
         self._up("goal", self.goals)
 
@@ -460,7 +531,7 @@ class FleetReplanLoop:
         reached_target: the flight ended within target_reach_threshold of the goal, was not abandoned and is no
         METRIC_FAIL), replans (plans that were spliced), failed_attempts, iter_num, opt_runs, n_cmd (rows of the command
         array), n_flown, final_dist, flags (NEO_FLEET_FLAG_*), audit_flags (NEO_AUDIT_FLAG_*), count and the ten audit
-        fields by name."""
+        fields by name.  With goal_routes: the first plan and `max_replans` ticks of chasing (class docstring)."""
         B = self.B
         bp = self.bp
         count = int(bp.cfg.init_wpts_num)
@@ -483,6 +554,9 @@ class FleetReplanLoop:
         self.uncounted_candidates[:] = 0
         d = self._dev
         planner = bp.geo_plan if self.mode == "geo" else bp.plan
+        tracked = self.routes is not None
+        failed_ticks = np.zeros(B, np.int32) if tracked else None
+        step = int(round(self.replan_period * self.cmd_hz))
         for tick in range(max_replans + 1):
             if active.size == 0:
                 break
@@ -490,8 +564,11 @@ class FleetReplanLoop:
             t_tick = time.perf_counter()
             if tick > 0:
                 t0 = time.perf_counter()
+                sub_a = self._subset(active)
                 self._sync()
-                self._advance(self._subset(active))
+                if tracked:
+                    self._hold(sub_a, step)
+                self._advance(sub_a)
                 bp.ctx.synchronize()
                 if self.mode != "batch" and not self.resident:      # (batch and resident plans use the resident states)
                     cur_pos = d["cur_pos"].cpu().numpy()
@@ -500,6 +577,13 @@ class FleetReplanLoop:
             else:
                 self._up("cur_pos", cur_pos)
                 self._up("head", head)
+            if tracked:      # where the goals are now: before sensing and the targets, tick 0 included
+                t0 = time.perf_counter()
+                sub_a = self._subset(active)
+                self._sync()
+                self._goal(sub_a, (tick * step) / self.cmd_hz)
+                bp.ctx.synchronize()
+                tm["fleet_s"] += time.perf_counter() - t0
             if self.onboard is not None:
                 self._sense(active, tm)
             if self.neo is not None:
@@ -562,11 +646,15 @@ class FleetReplanLoop:
                 tm["fleet_s"] += time.perf_counter() - t0
                 replans[pending[ok]] += 1
                 failed[pending[~ok]] += 1
-                landed[pending[ok]] = near[pending[ok]]
+                if not tracked:      # (a tracked mission never lands: planning goes on, :319-321)
+                    landed[pending[ok]] = near[pending[ok]]
                 pending = pending[~ok]
                 if pending.size == 0:
                     break
-            abandoned[pending] = True
+            if tracked:      # all targets of the tick failed: the mission flies on along its old commands (:265-279)
+                failed_ticks[pending] += 1
+            else:
+                abandoned[pending] = True
             flags = d["flags"].cpu().numpy()
             stuck = (flags & (_lib.NEO_FLEET_FLAG_CMD_FULL | _lib.NEO_FLEET_FLAG_SPLICE_FAILED)) != 0
             active = active[~(abandoned | landed | stuck)[active]]
@@ -574,14 +662,16 @@ class FleetReplanLoop:
             tm["host_s"] = tm["tick_s"] - tm["fleet_s"] - tm["plan_s"] - tm.get("sense_s", 0.0) - tm.get("record_s", 0.0) - \
                 tm.get("neo_s", 0.0)
             self.timings.append(tm)
-        return self._finish(replans, failed, iter_num, opt_runs, abandoned, landed)
+        return self._finish(replans, failed, iter_num, opt_runs, abandoned, landed, failed_ticks)
 
-    def _finish(self, replans, failed, iter_num, opt_runs, abandoned, landed):
+    def _finish(self, replans, failed, iter_num, opt_runs, abandoned, landed, failed_ticks=None):
         import torch
         d = self._dev
+        tracked = self.routes is not None
         cmd_len = d["cmd_len"].cpu().numpy()
         cmd_index = d["cmd_index"].cpu().numpy()
-        # a mission that landed flies its array to the end; the others stopped at the row they were on
+        # a mission that landed flies its array to the end; the others stopped at the row they were on (a tracked mission
+        # is always on a row of its array: n_flown = cmd_index + 1, whatever it held on the way)
         n_flown = np.where(landed, cmd_len, np.minimum(cmd_index + 1, cmd_len)).astype(np.int32)
         self._up("n_flown", n_flown)
         self._sync()
@@ -589,18 +679,33 @@ class FleetReplanLoop:
         self._audit()
         self.bp.ctx.synchronize()
         self.audit_s = time.perf_counter() - t0
+        if tracked:
+            t0 = time.perf_counter()
+            self._track_audit()
+            self.bp.ctx.synchronize()
+            self.track_audit_s = time.perf_counter() - t0
+        goals = d["goal"].cpu().numpy() if tracked else self.goals      # tracked: where the goals were at the last tick
         last = torch.from_numpy(np.maximum(n_flown - 1, 0).astype(np.int64)).to(self._device)
         end = d["cmd"][torch.arange(self.B, device=self._device), last, 0].cpu().numpy()
-        final_dist = np.where(n_flown > 0, np.linalg.norm(end - self.goals, axis=1), np.inf)
+        final_dist = np.where(n_flown > 0, np.linalg.norm(end - goals, axis=1), np.inf)
         flags = d["flags"].cpu().numpy() | np.where(abandoned, _lib.NEO_FLEET_FLAG_ABANDONED, 0).astype(np.int32)
         audit = d["audit"].cpu().numpy()
         audit_flags = d["audit_flags"].cpu().numpy()
         metric_fail = (audit_flags & (_lib.NEO_AUDIT_FLAG_METRIC_FAIL | _lib.NEO_AUDIT_FLAG_NONFINITE)) != 0
         out = {name: audit[:, k] for k, name in enumerate(_lib.AUDIT_FIELDS)}
-        out.update(success=(final_dist < self.target_reach_threshold) & ~abandoned & ~metric_fail & (flags == 0),
+        if tracked:      # a chase has no arrival: it succeeds when nothing went wrong on the way
+            success = (flags == 0) & ~metric_fail
+        else:
+            success = (final_dist < self.target_reach_threshold) & ~abandoned & ~metric_fail & (flags == 0)
+        out.update(success=success,
                    replans=replans, failed_attempts=failed, iter_num=iter_num, opt_runs=opt_runs, n_cmd=cmd_len,
                    n_flown=n_flown, final_dist=final_dist, flags=flags, audit_flags=audit_flags,
                    count=d["count"].cpu().numpy(), abandoned=abandoned, metric_fail=metric_fail)
+        if tracked:
+            track = d["track"].cpu().numpy()
+            out.update({"track_" + name: track[:, k] for k, name in enumerate(_lib.TRACK_FIELDS)})
+            out.update(track_count=d["track_count"].cpu().numpy(), track_flags=d["track_flags"].cpu().numpy(),
+                       failed_ticks=failed_ticks, goal_final=goals)
         if self.record_poses and self.onboard is not None:
             out.update(poses=np.stack(self._poses) if self._poses else np.zeros((0, self.B, 5)),
                        sensed=np.stack(self._sensed) if self._sensed else np.zeros((0, self.B), bool))

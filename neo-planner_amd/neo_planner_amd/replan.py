@@ -14,6 +14,9 @@ ros_node/traj_planner_node.py, with perfect tracking in place of PX4/Gazebo.
                                                            carried along relative to the planning start state,
                                                            and the durations the planner last held
 
+`TrackerLoop` is the same orchestration as ros_node/tracker_planner_node.py runs it: a goal that keeps moving along a
+route (goal_routes.GoalRoutes), no landing, failed ticks flown through, the last command held.
+
 Works with any planner object that has the reference's interface (`plan`, `batch_plan`,
 `get_full_state_cmd`, `int_wpts`, `ts`, `iter_num`): neo_planner_amd.MinJerkPlanner on the GPU, or the
 CPU oracle in tests.  This is BASELINE.json configs[0] (one trajectory at a time, goal (30, 0)).
@@ -135,3 +138,58 @@ class ReplanLoop:
                     iter_num=self.planner.iter_num, opt_runs=self.planner.opt_running_times, path=path,
                     min_clearance=float(dists.min()), duration=path.shape[0] / self.cmd_hz,
                     max_speed=float(np.linalg.norm(self.des_state_array[:, 1, :], axis=1).max()))
+
+
+class TrackerLoop(ReplanLoop):
+    """The loop of ros_node/tracker_planner_node.py (with tracker_manager_node.py) on any planner with the reference's
+    interface: the goal keeps moving, and the mission chases it.
+
+      global target        whatever the last message said when set_local_target runs (:160-162, :313-316): here the
+                           mission's goal route (goal_routes.GoalRoutes) at the tick's time
+      set_local_target     closer than longitu_step_dis the local target is the goal itself with zero velocity
+                           (:319-321) -- and planning goes on: there is no near_global_target
+      try_local_planning   a tick whose 11 targets all fail just returns (:265-279): the mission flies on along its old
+                           commands, nothing is abandoned
+      tracking             a drone that runs out of commands holds the last one (get_drone_state_ahead re-reads that
+                           row, :387-391): the array is padded with copies of it, so row i is the command at i / cmd_hz
+
+    Tick k is at time (k * step) / cmd_hz, step = round(replan_period * cmd_hz) commands."""
+
+    def set_local_target(self, current_pos, seed=0):
+        super().set_local_target(current_pos, seed)
+        self.near_global_target = False      # (:319-321 return without a flag)
+
+    def run_tracking(self, routes_of_one, ticks, start_pos=(0.0, 0.0), start_vel=(0.0, 0.0)):
+        """the first plan at tick 0 and one replan at each of the `ticks` ticks after it, chasing the one route of
+        `routes_of_one`.  Returns a dict: replans (plans made), failed_attempts, failed_ticks, iter_num, opt_runs,
+        commands (n_cmd, 3, 2), n_flown (= ticks * step + 1 once there are commands), path (the flown positions) and
+        goals (ticks + 1, 2), where the goal was at every tick."""
+        if routes_of_one.B != 1:
+            raise ValueError("TrackerLoop.run_tracking: one route")
+        step = int(round(self.replan_period * self.cmd_hz))
+        drone = _State(np.append(np.asarray(start_pos, float), self.des_pos_z), np.append(np.asarray(start_vel, float), 0.0))
+        self.des_state_array = np.zeros((0, 3, 2))
+        self.des_state_index = 0
+        failed_ticks = 0
+        goals = np.zeros((ticks + 1, 2))
+        for k in range(ticks + 1):
+            self.global_target = goals[k] = routes_of_one.at((k * step) / self.cmd_hz)[0]
+            have = self.des_state_array.shape[0]
+            if k > 0 and have >= 1:
+                need = self.des_state_index + step + 1
+                if have < need:      # out of commands before the period is over: hold the last one
+                    self.des_state_array = np.concatenate((self.des_state_array, np.repeat(self.des_state_array[-1:], need - have, axis=0)))
+                self.des_state_index += step
+            if self.des_state_array.shape[0] >= 1:
+                cur, start_fn = self.des_state_array[self.des_state_index, 0, :], self.get_drone_state_ahead
+            else:      # nothing planned yet: the first plan, from where the drone stands
+                cur, start_fn, self.future_index = drone.global_pos[:2], (lambda: drone), 0
+            if not self._plan_with_retargeting(start_fn, cur):
+                failed_ticks += 1
+                continue
+            new = self.planner.get_full_state_cmd(self.cmd_hz)
+            self.des_state_array = np.concatenate((self.des_state_array[:self.future_index], new), axis=0)   # :430
+        n_flown = min(self.des_state_index + 1, self.des_state_array.shape[0])
+        return dict(replans=self.n_plans, failed_attempts=self.n_failed_attempts, failed_ticks=failed_ticks,
+                    iter_num=self.planner.iter_num, opt_runs=self.planner.opt_running_times,
+                    commands=self.des_state_array, n_flown=n_flown, path=self.des_state_array[:n_flown, 0, :], goals=goals)

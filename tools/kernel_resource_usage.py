@@ -5,7 +5,7 @@
     python tools/kernel_resource_usage.py > profiles/rNN_kernel_resource_usage.txt
 
 Listed: the brick-layout instantiations of the bench's configurations, the budgeted kernels, the ESDF-lookup kernels,
-the depth camera's kernels, the record kernels, the warm-start (init) kernels, the two counter-based jitter kernels, the adaptive-count kernels, the plan chain's merge and the two compactions."""
+the depth camera's kernels, the record kernels, the warm-start (init) kernels, the two counter-based jitter kernels, the three goal-route kernels next to the flight audit's, the adaptive-count kernels, the plan chain's merge and the two compactions."""
 import concurrent.futures, os, re, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "neo-planner_amd"))
@@ -39,7 +39,8 @@ for src, err in results:
     for r, n in zip(recs, names):
         n = re.sub(r"\(.*$", "", n).replace("neo::", "")
         if src in JITTER_UNITS:      # (of these two units only the jitter kernels and the plan chain's merge are listed)
-            if "jitter_kernel" not in n and "plan_merge_kernel" not in n:
+            if not any(k in n for k in ("jitter_kernel", "plan_merge_kernel", "fleet_goal_kernel", "fleet_hold_kernel",
+                                        "fleet_track_audit_kernel", "fleet_audit_kernel")):
                 continue
         elif not ("_compact_kernel" in n or ", 3>" in n or "sample_kernel" in n or "group" in n or "depth_" in n or "record_" in n or "init_" in n or "adaptive_" in n):
             continue
