@@ -1,6 +1,10 @@
-// neo_abi.hip -- C ABI of libneo_planner_hip.so (include/neo_planner.h): argument checks, locking, scratch layout
-// (Carver, HostStage) and host copies, the map bookkeeping, and one call into the kernel family's unit (neo_disp_*.hip)
-// per entry point.  The kernels it still holds are the small ones around the optimiser's results:
+// neo_abi.hip -- C ABI of libneo_planner_hip.so (include/neo_planner.h), first of three units: the context, the
+// parameters, the maps, cost-grad, the sampled terms, the optimiser, the trajectory states and audit, the geo warm start
+// and the trace / counter / order / profile calls.  neo_abi_fleet.hip has the depth camera, onboard maps, the fleet,
+// record and init entry points, neo_abi_plan.hip the batch, plan and adaptive ones.  Argument checks, locking, scratch
+// layout and host copies and the map bookkeeping are shared (neo_abi_util.hpp); every entry point makes one call into
+// the kernel family's unit (neo_disp_*.hip).  The kernels this unit still holds are the small ones around the
+// optimiser's results:
 //
 //   traj_state_kernel   get_full_state_cmd                      (traj_utils.py:85-195)
 //   pack_results_kernel, effort_keys_kernel and the rocPRIM sort of the dispatch order
@@ -8,7 +12,7 @@
 // The map kernels are in neo_esdf.hpp (launched from neo_disp_esdf.hip); the fused kernels (eval / optimize / sample)
 // are templates in neo_kernels.hpp, instantiated per family in the neo_disp_*.hip translation units.
 #include <cstring>
-#include "neo_host.hpp"
+#include "neo_abi_util.hpp"
 #include <rocprim/device/device_radix_sort.hpp>
 #include "neo_kernels.hpp"
 
@@ -96,6 +100,7 @@ __global__ __launch_bounds__(kWave) void traj_state_kernel(int B, int M, DevPara
 
 // =================================================================== host side
 using namespace neo;
+using namespace neo::abi;
 
 namespace {
 
@@ -119,213 +124,6 @@ void fill_dev_params(neo_ctx *c) {
   d.derive();
 }
 
-int ensure_scratch(neo_ctx *c, size_t bytes) {
-  if (bytes <= c->scratch_bytes) return NEO_OK;
-  if (c->scratch) hipFree(c->scratch);
-  c->scratch = nullptr;
-  c->scratch_bytes = 0;
-  HIPCHK(c, hipMalloc(&c->scratch, bytes));
-  c->scratch_bytes = bytes;
-  return NEO_OK;
-}
-
-int ensure_pinned(neo_ctx *c, size_t bytes) {
-  if (bytes <= c->pinned_bytes) return NEO_OK;
-  if (c->pinned) hipHostFree(c->pinned);
-  c->pinned = nullptr;
-  c->pinned_bytes = 0;
-  HIPCHK(c, hipHostMalloc(&c->pinned, bytes, hipHostMallocDefault));
-  c->pinned_bytes = bytes;
-  return NEO_OK;
-}
-
-// bump allocator over the scratch buffer (device-only work buffers of the ESDF upload / build paths)
-struct Carver {
-  char *base;
-  size_t off = 0;
-  explicit Carver(void *b) : base(static_cast<char *>(b)) {}
-  template <typename T>
-  T *take(size_t count) {
-    off = (off + 255) & ~size_t(255);
-    T *p = reinterpret_cast<T *>(base + off);
-    off += count * sizeof(T);
-    return p;
-  }
-};
-
-// Calls whose whole scratch layout is at most this many bytes go through the pinned mirror: ONE copy in and ONE copy out
-// instead of one per array from pageable memory (a single plan() of the reference's shape: 0.36 -> 0.27 ms; ten such
-// copies cost almost as much as the kernel).  Small calls only: from a megabyte on, the extra pass over the data costs
-// more than the copies' latencies -- 8192 replans of the reference's shape per call: 1.46 M/s direct, 1.28 M/s staged.
-// (neo_optimize_batch, neo_cost_grad_batch, neo_eval_traj_batch; the other host forms pass 0 = never: the mirror has
-// not been measured there.)
-constexpr size_t kStagedUpTo = (size_t)256 * 1024;
-
-// The arrays of one host-pointer call, staged through c->scratch.  Declare the fields in layout order -- in(), then
-// inout(), then out(), each 256-byte aligned -- then upload(), run the `_dev` form on dev() pointers, then download().
-// A null host pointer reserves the field and copies nothing for it (device-only, or the caller did not ask).  The
-// scratch is sized from the declarations.  Calls up to `staged_up_to` bytes move the contiguous input range and the
-// contiguous output range through the pinned mirror of the same layout, whole, null fields included; larger ones copy
-// field by field.  A stage that goes out of scope between upload() and a completed download() (an error return) waits
-// for the stream first: copies in flight read the caller's arrays and the wrapper's locals.
-// The context stays locked for the stage's lifetime (c->scratch and c->pinned are the context's only ones).
-class HostStage {
- public:
-  template <typename T>
-  struct Ref { int i; };
-
-  HostStage(neo_ctx *c, size_t staged_up_to) : c_(c), staged_up_to_(staged_up_to) { f_.reserve(12); }
-  HostStage(const HostStage &) = delete;
-  HostStage &operator=(const HostStage &) = delete;
-  ~HostStage() {
-    if (in_flight_) hipStreamSynchronize(c_->stream);
-  }
-
-  // `count` elements are copied; `reserve` (>= count) sizes the field when the device side wants more room
-  template <typename T>
-  Ref<T> in(const T *host, size_t count, size_t reserve = 0) { return {add(0, host, nullptr, count * sizeof(T), reserve * sizeof(T))}; }
-  template <typename T>
-  Ref<T> inout(T *host, size_t count) { return {add(1, host, host, count * sizeof(T), 0)}; }
-  template <typename T>
-  Ref<T> out(T *host, size_t count, size_t reserve = 0) { return {add(2, nullptr, host, count * sizeof(T), reserve * sizeof(T))}; }
-
-  // an array the caller may leave out (a subset, slots, ...): staged like in() / inout() when it is given; dev() of
-  // the field is NULL when it is not, which is what the `_dev` form takes for "none"
-  template <typename T>
-  Ref<T> in_optional(const T *host, size_t count) { return {add(0, host, nullptr, host ? count * sizeof(T) : 0, sizeof(T), !host)}; }
-  template <typename T>
-  Ref<T> inout_optional(T *host, size_t count) { return {add(1, host, host, host ? count * sizeof(T) : 0, 0, !host)}; }
-
-  // the field's device array: valid from upload() on (growing the scratch moves it), NULL before
-  template <typename T>
-  T *dev(Ref<T> r) const { return dbase_ && !f_[r.i].absent ? reinterpret_cast<T *>(dbase_ + f_[r.i].off) : nullptr; }
-
-  int upload() {
-    if (!ordered_) return fail(c_, NEO_ERR_INVALID, "internal: staged fields declared out of order");
-    staged_ = staged_up_to_ && end_ <= staged_up_to_;
-    int rc = ensure_scratch(c_, end_ + 256);
-    if (!rc && staged_) rc = ensure_pinned(c_, end_ + 256);
-    if (rc) return rc;
-    dbase_ = static_cast<char *>(c_->scratch);
-    hbase_ = static_cast<char *>(c_->pinned);
-    in_flight_ = true;
-    if (staged_) {
-      for (const Field &f : f_)
-        if (f.src) std::memcpy(hbase_ + f.off, f.src, f.bytes);
-      HIPCHK(c_, hipMemcpyAsync(dbase_, hbase_, std::min(in_end_, end_), hipMemcpyHostToDevice, c_->stream));
-      return NEO_OK;
-    }
-    for (const Field &f : f_)
-      if (f.src) HIPCHK(c_, hipMemcpyAsync(dbase_ + f.off, f.src, f.bytes, hipMemcpyHostToDevice, c_->stream));
-    return NEO_OK;
-  }
-
-  int download() {
-    if (staged_) {
-      const size_t o = std::min(out_begin_, end_);
-      HIPCHK(c_, hipMemcpyAsync(hbase_ + o, dbase_ + o, end_ - o, hipMemcpyDeviceToHost, c_->stream));
-    } else {
-      for (const Field &f : f_)
-        if (f.dst) HIPCHK(c_, hipMemcpyAsync(f.dst, dbase_ + f.off, f.bytes, hipMemcpyDeviceToHost, c_->stream));
-    }
-    HIPCHK(c_, hipStreamSynchronize(c_->stream));
-    in_flight_ = false;
-    if (staged_)
-      for (const Field &f : f_)
-        if (f.dst) std::memcpy(f.dst, hbase_ + f.off, f.bytes);
-    return NEO_OK;
-  }
-
- private:
-  struct Field {
-    size_t off, bytes;
-    const void *src;  // host array copied up, or NULL
-    void *dst;        // host array copied back, or NULL
-    bool absent;      // an optional field the caller left out
-  };
-  int add(int role, const void *src, void *dst, size_t bytes, size_t reserve, bool absent = false) {
-    ordered_ = ordered_ && role >= role_;
-    role_ = role;
-    const size_t off = (end_ + 255) & ~size_t(255);
-    if (role >= 1) out_begin_ = std::min(out_begin_, off);
-    if (role == 2) in_end_ = std::min(in_end_, off);
-    end_ = off + std::max(bytes, reserve);
-    f_.push_back({off, bytes, src, dst, absent});
-    return (int)f_.size() - 1;
-  }
-  neo_ctx *c_;
-  size_t staged_up_to_;
-  std::vector<Field> f_;
-  size_t end_ = 0;                  // bytes of the layout (the last field's end)
-  size_t in_end_ = ~size_t(0);      // the input range is [0, first out() field)
-  size_t out_begin_ = ~size_t(0);   // the output range is [first inout() / out() field, end)
-  int role_ = 0;
-  bool ordered_ = true, staged_ = false, in_flight_ = false;
-  char *dbase_ = nullptr, *hbase_ = nullptr;
-};
-
-int rebuild_tables(neo_ctx *c) {
-  if (!c->table_dirty) return NEO_OK;
-  std::vector<Map2D> t2;
-  std::vector<Map3D> t3;
-  for (auto &kv : c->maps) {
-    MapEntry &e = kv.second;
-    if (e.kind == 0) {
-      e.slot = (int)t2.size();
-      t2.push_back(e.m2);
-    } else if (e.kind == 1) {
-      e.slot = (int)t3.size();
-      t3.push_back(e.m3);
-    }
-  }
-  if (c->table2d) hipFree(c->table2d);
-  if (c->table3d) hipFree(c->table3d);
-  c->table2d = c->table3d = nullptr;
-  if (!t2.empty()) {
-    HIPCHK(c, hipMalloc(&c->table2d, t2.size() * sizeof(Map2D)));
-    HIPCHK(c, hipMemcpyAsync(c->table2d, t2.data(), t2.size() * sizeof(Map2D), hipMemcpyHostToDevice, c->stream));
-  }
-  if (!t3.empty()) {
-    HIPCHK(c, hipMalloc(&c->table3d, t3.size() * sizeof(Map3D)));
-    HIPCHK(c, hipMemcpyAsync(c->table3d, t3.data(), t3.size() * sizeof(Map3D), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->n2d = (int)t2.size();
-  c->n3d = (int)t3.size();
-  c->table_dirty = false;
-  return NEO_OK;
-}
-
-// (callers do not hold the context lock yet: take it for the error string)
-int check_shape(neo_ctx *c, int B, int M, int D) {
-  if (!c) return NEO_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  if (B < 0 || M < 1 || M > NEO_MAX_PIECES || D < 2 || D > NEO_MAX_DIM)
-    return fail(c, NEO_ERR_INVALID, "shape out of range (1 <= M <= 64, D in {2,3})");
-  if (D * (M - 1) + M > kSlots * kWave) return fail(c, NEO_ERR_INVALID, "n = D(M-1)+M exceeds 256");
-  return NEO_OK;
-}
-
-// host scene ids of a multi-scene call -> map-table slots (context locked).  The maps must all be of one kind, or, for
-// the geo warm start (`geo`: the reference's A* is 2-D only), all 2-D.
-int scene_slots(neo_ctx *c, const int32_t *scene_ids, size_t B, bool geo, std::vector<int> &slots) {
-  int rc = rebuild_tables(c);
-  if (rc) return rc;
-  slots.resize(B);
-  int kind0 = geo ? 0 : -1;
-  for (size_t i = 0; i < B; ++i) {
-    auto it = c->maps.find(scene_ids[i]);
-    if (it == c->maps.end())
-      return fail(c, NEO_ERR_NO_MAP, geo ? "geo: no ESDF for one of scene_ids" : "no ESDF for one of scene_ids");
-    if (kind0 < 0) kind0 = it->second.kind;
-    if (it->second.kind != kind0)
-      return geo ? fail(c, NEO_ERR_UNSUPPORTED, "geo: one of scene_ids is a 3-D map")
-                 : fail(c, NEO_ERR_INVALID, "scene_ids mix 2-D and 3-D maps");
-    slots[i] = it->second.slot;
-  }
-  return NEO_OK;
-}
-
 // From this batch size on the kernels take the two-wavefronts-per-SIMD register allocation (three in the all-fp32
 // mode, always).  Measured in round 3, one launch at a time, two waves against one: fp64 mode +4 % at 1024, +9 % at 2048,
 // +23 % at 3072 trajectories; mixed mode +2 %, +5 %, +23 % (round 2 had found one wave faster up to 2048: 9.1 against
@@ -335,57 +133,6 @@ bool two_waves_wanted(const neo_ctx *c, int B) {
   const int fl = c->params.flags;
   return (B >= kTwoWavesFromBatch && !(fl & NEO_FLAG_ONE_WAVE_PER_SIMD)) || (fl & NEO_FLAG_TWO_WAVES_PER_SIMD);
 }
-
-int fail_locked(neo_ctx *c, int code, const char *msg) {
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  return fail(c, code, msg);
-}
-
-// the end of a `_dev` entry point: the launcher's return code, then the launch's own error
-int launched(neo_ctx *c, int rc) {
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return NEO_OK;
-}
-
-// the (B, subset, n_subset) of the entry points that take a launch list (context unlocked): B_min <= B, B <= B_max
-// where there is a bound (a power of two), at most B entries
-int list_check(neo_ctx *c, const char *who, int B, int B_min, int B_max, const int32_t *subset, int n_subset) {
-  if (!c) return NEO_ERR_INVALID;
-  if (B < B_min || B > B_max) {
-    std::string msg = std::string(who) + ": B must be ";
-    if (B_max == INT32_MAX) {
-      msg += ">= " + std::to_string(B_min);
-    } else {
-      int k = 0;
-      while ((1 << k) < B_max) ++k;
-      msg += "in " + std::to_string(B_min) + " .. 2^" + std::to_string(k);
-    }
-    return fail_locked(c, NEO_ERR_INVALID, msg.c_str());
-  }
-  if (subset && (n_subset < 0 || n_subset > B))
-    return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": bad subset size").c_str());
-  return NEO_OK;
-}
-
-// the six result arrays of an optimiser launch through a stage: the packed rows go up, the request-indexed ones go up
-// and come back (rows outside the launch stay); an array the caller left out stays out
-struct RowRefs {
-  HostStage::Ref<double> x, costs4, costs4_last;
-  HostStage::Ref<int32_t> nit, nfev, status;
-};
-RowRefs stage_rows_in(HostStage &st, const RunRowsIn &r, size_t rows, size_t n) {
-  return {st.in(r.x, rows * n), st.in(r.costs4, rows * 4), st.in(r.costs4_last, rows * 4), st.in(r.nit, rows),
-          st.in_optional(r.nfev, rows), st.in(r.status, rows)};
-}
-RowRefs stage_rows_inout(HostStage &st, const RunRows &r, size_t rows, size_t n) {
-  return {st.inout(r.x, rows * n), st.inout(r.costs4, rows * 4), st.inout(r.costs4_last, rows * 4),
-          st.inout_optional(r.nit, rows), st.inout_optional(r.nfev, rows), st.inout(r.status, rows)};
-}
-RunRows staged_rows(const HostStage &st, const RowRefs &f) {
-  return {st.dev(f.x), st.dev(f.costs4), st.dev(f.costs4_last), st.dev(f.nit), st.dev(f.nfev), st.dev(f.status)};
-}
-RunRowsIn as_const(const RunRows &r) { return {r.x, r.costs4, r.costs4_last, r.nit, r.nfev, r.status}; }
 
 // dispatch_opt sends this launch to the lane-group kernel (several small trajectories per wavefront, opt-in):
 // on the reference's own map small planar problems (M = 3 -> n = 7), on 3-D fields small problems in fp32 sampling
@@ -681,7 +428,7 @@ int neo_esdf_build_2d_batch_dev(neo_ctx *c, const int32_t *scene_ids, int n, con
   if (n < 0 || W < 1 || H < 1 || !(res > 0.0) || !std::isfinite(res))
     return fail_locked(c, NEO_ERR_INVALID, "batch build: n >= 0, width and height >= 1, resolution finite and > 0");
   if (n == 0) return NEO_OK;
-  if (!scene_ids || !occ || !origins) return fail_locked(c, NEO_ERR_INVALID, "batch build: null buffer");
+  if (int rc = null_check(c, "batch build: null buffer", {scene_ids, occ, origins})) return rc;
   if ((size_t)W * H > (size_t)1 << 28) return fail_locked(c, NEO_ERR_INVALID, "batch build: more than 2^28 cells a map");
   {
     std::vector<int32_t> ids(scene_ids, scene_ids + n);
@@ -886,11 +633,10 @@ int neo_esdf_query(neo_ctx *c, int scene_id, int n, const double *pts, double *d
   HostStage st(c, 0);
   const auto f_p = st.in(pts, (size_t)n * dm);
   const auto f_d = st.out(dist, (size_t)n), f_g = st.out(grad, (size_t)n * dm);
-  int rc = st.upload();
-  if (rc) return rc;
-  double *d_p = st.dev(f_p), *d_d = st.dev(f_d), *d_g = st.dev(f_g);
-  esdf_query(c, e, n, d_p, d_d, d_g);
-  return st.download();
+  return st.run([&]() -> int {
+    esdf_query(c, e, n, st.dev(f_p), st.dev(f_d), st.dev(f_g));
+    return NEO_OK;
+  });
 }
 
 int neo_cost_grad_batch_dev(neo_ctx *c, int scene_id, int B, int M, int D, const double *x, const double *head,
@@ -898,7 +644,7 @@ int neo_cost_grad_batch_dev(neo_ctx *c, int scene_id, int B, int M, int D, const
                             int32_t *status) {
   int rc = check_shape(c, B, M, D);
   if (rc) return rc;
-  if (!x || !head || !tail || !cost || !costs4 || !grad) return fail_locked(c, NEO_ERR_INVALID, "null buffer");
+  if ((rc = null_check(c, "null buffer", {x, head, tail, cost, costs4, grad}))) return rc;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
   auto it = c->maps.find(scene_id);
@@ -914,7 +660,7 @@ int neo_cost_grad_batch(neo_ctx *c, int scene_id, int B, int M, int D, const dou
                         int32_t *status) {
   int rc = check_shape(c, B, M, D);
   if (rc) return rc;
-  if (!x || !head || !tail || !cost || !costs4 || !grad) return fail_locked(c, NEO_ERR_INVALID, "null buffer");
+  if ((rc = null_check(c, "null buffer", {x, head, tail, cost, costs4, grad}))) return rc;
   if (B == 0) return NEO_OK;
   std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
   hipSetDevice(c->device);
@@ -924,12 +670,10 @@ int neo_cost_grad_batch(neo_ctx *c, int scene_id, int B, int M, int D, const dou
   const auto fc = st.out(cost, bs), fc4 = st.out(costs4, bs * 4), fg = st.out(grad, bs * n);
   const auto fco = st.out(coeffs, bs * 6 * M * D);
   const auto fst = st.out(status, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_cost_grad_batch_dev(c, scene_id, B, M, D, st.dev(fx), st.dev(fh), st.dev(ft), st.dev(fc), st.dev(fc4), st.dev(fg),
-                               coeffs ? st.dev(fco) : nullptr, st.dev(fst));
-  if (rc) return rc;
-  return st.download();
+  return st.run([&] {
+    return neo_cost_grad_batch_dev(c, scene_id, B, M, D, st.dev(fx), st.dev(fh), st.dev(ft), st.dev(fc), st.dev(fc4),
+                                   st.dev(fg), coeffs ? st.dev(fco) : nullptr, st.dev(fst));
+  });
 }
 
 // IO32: coeffs / grad_C / grad_T are floats (the _f32 entry points; fp32 sampling only)
@@ -937,7 +681,7 @@ static int sampled_terms_dev(neo_ctx *c, int scene_id, int B, int M, int D, cons
                              void *grad_C, void *grad_T, bool io32) {
   int rc = check_shape(c, B, M, D);
   if (rc) return rc;
-  if (!coeffs || !ts || !costs2 || !grad_C || !grad_T) return fail_locked(c, NEO_ERR_INVALID, "null buffer");
+  if ((rc = null_check(c, "null buffer", {coeffs, ts, costs2, grad_C, grad_T}))) return rc;
   if (((uintptr_t)coeffs | (uintptr_t)grad_C) & (io32 ? 7 : 15))
     return fail_locked(c, NEO_ERR_INVALID, io32 ? "coeffs and grad_C must be 8-byte aligned" : "coeffs and grad_C must be 16-byte aligned");
   std::lock_guard<std::recursive_mutex> g(c->mu);
@@ -965,7 +709,7 @@ static int sampled_terms_host(neo_ctx *c, int scene_id, int B, int M, int D, con
                               void *grad_C, void *grad_T, bool io32) {
   int rc = check_shape(c, B, M, D);
   if (rc) return rc;
-  if (!coeffs || !ts || !costs2 || !grad_C || !grad_T) return fail_locked(c, NEO_ERR_INVALID, "null buffer");
+  if ((rc = null_check(c, "null buffer", {coeffs, ts, costs2, grad_C, grad_T}))) return rc;
   if (B == 0) return NEO_OK;
   std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
   hipSetDevice(c->device);
@@ -977,11 +721,9 @@ static int sampled_terms_host(neo_ctx *c, int scene_id, int B, int M, int D, con
   const auto fc2 = st.out(costs2, bs * 2);
   const auto fgc = st.out(static_cast<char *>(grad_C), bs * nc * es, bs * nc * sizeof(double));
   const auto fgt = st.out(static_cast<char *>(grad_T), bs * M * es, bs * M * sizeof(double));
-  rc = st.upload();
-  if (rc) return rc;
-  rc = sampled_terms_dev(c, scene_id, B, M, D, st.dev(fco), st.dev(fts), st.dev(fc2), st.dev(fgc), st.dev(fgt), io32);
-  if (rc) return rc;
-  return st.download();
+  return st.run([&] {
+    return sampled_terms_dev(c, scene_id, B, M, D, st.dev(fco), st.dev(fts), st.dev(fc2), st.dev(fgc), st.dev(fgt), io32);
+  });
 }
 
 int neo_sampled_terms_batch(neo_ctx *c, int scene_id, int B, int M, int D, const double *coeffs, const double *ts,
@@ -997,40 +739,6 @@ int neo_sampled_terms_batch_f32(neo_ctx *c, int scene_id, int B, int M, int D, c
 // the L-BFGS pairs (2 * maxcor * n doubles per trajectory) live in LDS: no HBM workspace
 size_t neo_optimize_workspace_bytes(int, int, int) { return 0; }
 
-// the maps of a `_dev` call (neo_optimize_batch_from_dev, neo_audit_traj_batch_dev): with slots, the whole table of the
-// reference scene's kind -- one kernel instantiation serves the whole call, so every map a slot can name (all maps of
-// that kind in this context) must share its element type and layout; without, the one map of scene_id.
-// Call with the context locked and the tables rebuilt.
-struct CallMaps {
-  int kind = 0, elem = 0, layout = 0, nmaps = 1;
-  const void *table = nullptr;
-};
-static int resolve_call_maps(neo_ctx *c, int scene_id, bool with_slots, CallMaps &cm) {
-  if (with_slots) {
-    auto it = c->maps.find(scene_id);
-    if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "no ESDF for the reference scene");
-    cm.kind = it->second.kind;
-    cm.elem = it->second.elem;
-    cm.layout = it->second.m3.layout;
-    for (const auto &kv : c->maps)
-      if (kv.second.kind == cm.kind && (kv.second.elem != cm.elem || (cm.kind == 1 && kv.second.m3.layout != cm.layout)))
-        return fail(c, NEO_ERR_INVALID, "multi-scene call: the context holds maps of this kind with different element "
-                                        "types or layouts");
-    cm.table = cm.kind == 0 ? c->table2d : c->table3d;
-    cm.nmaps = cm.kind == 0 ? c->n2d : c->n3d;
-  } else {
-    auto it = c->maps.find(scene_id);
-    if (it == c->maps.end()) return fail(c, NEO_ERR_NO_MAP, "no ESDF for this scene");
-    cm.kind = it->second.kind;
-    cm.elem = it->second.elem;
-    cm.layout = it->second.m3.layout;
-    const char *base = static_cast<const char *>(cm.kind == 0 ? c->table2d : c->table3d);
-    cm.table = base + (size_t)it->second.slot * (cm.kind == 0 ? sizeof(Map2D) : sizeof(Map3D));
-    cm.nmaps = 1;
-  }
-  return NEO_OK;
-}
-
 int neo_optimize_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, int M, int D, double *x,
                            const double *head, const double *tail, double *costs4, double *costs4_last, int32_t *nit,
                            int32_t *nfev, int32_t *status) {
@@ -1043,8 +751,7 @@ int neo_optimize_batch_from_dev(neo_ctx *c, int scene_id, const int32_t *scene_i
                                 int32_t *nit, int32_t *nfev, int32_t *status) {
   int rc = check_shape(c, B, M, D);
   if (rc) return rc;
-  if (!x0 || !x || !head || !tail || !costs4 || !nit || !nfev || !status)
-    return fail_locked(c, NEO_ERR_INVALID, "null buffer");
+  if ((rc = null_check(c, "null buffer", {x0, x, head, tail, costs4, nit, nfev, status}))) return rc;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
   if (B == 0) return NEO_OK;
@@ -1078,8 +785,7 @@ int neo_optimize_batch_budget_dev(neo_ctx *c, int scene_id, int B, int M, int D,
                                   int resume) {
   int rc = check_shape(c, B, M, D);
   if (rc) return rc;
-  if (!x0 || !x || !head || !tail || !costs4 || !nit || !nfev || !status || !state)
-    return fail_locked(c, NEO_ERR_INVALID, "null buffer");
+  if ((rc = null_check(c, "null buffer", {x0, x, head, tail, costs4, nit, nfev, status, state}))) return rc;
   if (eval_budget < 1) return fail_locked(c, NEO_ERR_INVALID, "eval_budget < 1");
   if (subset && (n_subset < 0 || n_subset > B)) return fail_locked(c, NEO_ERR_INVALID, "bad subset size");
   std::lock_guard<std::recursive_mutex> g(c->mu);
@@ -1121,36 +827,31 @@ int neo_optimize_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B
                        int32_t *nfev, int32_t *status) {
   int rc = check_shape(c, B, M, D);
   if (rc) return rc;
-  if (!x || !head || !tail || !costs4 || !nit || !nfev || !status) return fail_locked(c, NEO_ERR_INVALID, "null buffer");
+  if ((rc = null_check(c, "null buffer", {x, head, tail, costs4, nit, nfev, status}))) return rc;
   if (B == 0) return NEO_OK;
   std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
   hipSetDevice(c->device);
   const size_t n = (size_t)D * (M - 1) + M, bs = (size_t)B;
-  std::vector<int> slots;
-  if (scene_ids) {
-    rc = scene_slots(c, scene_ids, bs, false, slots);
-    if (rc) return rc;
-  }
+  SceneList scenes(scene_ids);
+  if ((rc = scenes.resolve(c, bs))) return rc;
   // the inputs are one contiguous range ending with x, the outputs one starting with it
   HostStage st(c, kStagedUpTo);
   const auto fh = st.in(head, bs * 3 * D), ft = st.in(tail, bs * 3 * D);
-  const auto fs = st.in(scene_ids ? slots.data() : nullptr, bs);
+  scenes.stage(st, bs);
   const auto fx = st.inout(x, bs * n);
   const auto fc4 = st.out(costs4, bs * 4), fc4l = st.out(costs4_last, bs * 4);
   const auto fnit = st.out(nit, bs), fnfev = st.out(nfev, bs), fst = st.out(status, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_optimize_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fs) : nullptr, B, M, D, st.dev(fx),
-                              st.dev(fh), st.dev(ft), st.dev(fc4), st.dev(fc4l), st.dev(fnit), st.dev(fnfev), st.dev(fst));
-  if (rc) return rc;
-  return st.download();
+  return st.run([&] {
+    return neo_optimize_batch_dev(c, scenes.scene(scene_id), scenes.slots(st), B, M, D, st.dev(fx), st.dev(fh), st.dev(ft),
+                                  st.dev(fc4), st.dev(fc4l), st.dev(fnit), st.dev(fnfev), st.dev(fst));
+  });
 }
 
 int neo_eval_traj_batch(neo_ctx *c, int B, int M, int D, const double *x, const double *head, const double *tail,
                         double hz, int K, double *state, int32_t *count) {
   int rc = check_shape(c, B, M, D);
   if (rc) return rc;
-  if (!x || !head || !tail || !state || !count || K < 0 || !(hz > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "bad argument");
+  if ((rc = null_check(c, "bad argument", {x, head, tail, state, count}, K < 0 || !(hz > 0.0)))) return rc;
   if (B == 0 || K == 0) return NEO_OK;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
@@ -1159,18 +860,18 @@ int neo_eval_traj_batch(neo_ctx *c, int B, int M, int D, const double *x, const 
   const auto fx = st.in(x, bs * n), fh = st.in(head, bs * 3 * D), ft = st.in(tail, bs * 3 * D);
   const auto fs = st.out(state, bs * K * 3 * D);
   const auto fcnt = st.out(count, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  double *dx = st.dev(fx), *dh = st.dev(fh), *dt = st.dev(ft), *ds = st.dev(fs);
-  int *dcnt = st.dev(fcnt);
-  if (D == 2)
-    hipLaunchKernelGGL((traj_state_kernel<2>), dim3(B), dim3(kWave), 0, c->stream, B, M, c->dev, dx, dh, dt, hz, K, ds,
-                       dcnt);
-  else
-    hipLaunchKernelGGL((traj_state_kernel<3>), dim3(B), dim3(kWave), 0, c->stream, B, M, c->dev, dx, dh, dt, hz, K, ds,
-                       dcnt);
-  HIPCHK(c, hipGetLastError());
-  return st.download();
+  return st.run([&]() -> int {
+    double *dx = st.dev(fx), *dh = st.dev(fh), *dt = st.dev(ft), *ds = st.dev(fs);
+    int *dcnt = st.dev(fcnt);
+    if (D == 2)
+      hipLaunchKernelGGL((traj_state_kernel<2>), dim3(B), dim3(kWave), 0, c->stream, B, M, c->dev, dx, dh, dt, hz, K, ds,
+                         dcnt);
+    else
+      hipLaunchKernelGGL((traj_state_kernel<3>), dim3(B), dim3(kWave), 0, c->stream, B, M, c->dev, dx, dh, dt, hz, K, ds,
+                         dcnt);
+    HIPCHK(c, hipGetLastError());
+    return NEO_OK;
+  });
 }
 
 // ---- trajectory audit (ros_node/traj_planner_node.py:333-363; kernel: neo_audit.hpp)
@@ -1179,7 +880,7 @@ static int audit_check(neo_ctx *c, int B, int M, int D, const double *x, const d
                        const double *audit, const int32_t *count, const int32_t *flags) {
   int rc = check_shape(c, B, M, D);
   if (rc) return rc;
-  if (!x || !head || !tail || !audit || !count || !flags) return fail_locked(c, NEO_ERR_INVALID, "audit: null buffer");
+  if ((rc = null_check(c, "audit: null buffer", {x, head, tail, audit, count, flags}))) return rc;
   if (!std::isfinite(hz) || !(hz > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "audit: hz must be finite and > 0");
   std::lock_guard<std::recursive_mutex> g(c->mu);
   // a trajectory lasts at most M * T_max: its sample count must fit the kernel's int range with room to spare
@@ -1217,1127 +918,17 @@ int neo_audit_traj_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int
   std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
   hipSetDevice(c->device);
   const size_t n = (size_t)D * (M - 1) + M, bs = (size_t)B;
-  std::vector<int> slots;
-  if (scene_ids) {
-    rc = scene_slots(c, scene_ids, bs, false, slots);
-    if (rc) return rc;
-  }
+  SceneList scenes(scene_ids);
+  if ((rc = scenes.resolve(c, bs))) return rc;
   HostStage st(c, 0);
   const auto fx = st.in(x, bs * n), fh = st.in(head, bs * 3 * D), ft = st.in(tail, bs * 3 * D);
-  const auto fs = st.in(scene_ids ? slots.data() : nullptr, bs);
+  scenes.stage(st, bs);
   const auto fa = st.out(audit, bs * NEO_AUDIT_FIELDS);
   const auto fcnt = st.out(count, bs), ffl = st.out(flags, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_audit_traj_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fs) : nullptr, B, M, D, st.dev(fx),
-                                st.dev(fh), st.dev(ft), hz, weights3, st.dev(fa), st.dev(fcnt), st.dev(ffl));
-  if (rc) return rc;
-  return st.download();
-}
-
-// ---- batched depth camera (neo_planner_amd/initializer.py raycast_depth for B requests; kernels: neo_depth.hpp)
-// the argument checks both forms make before anything is copied or launched (context unlocked)
-static int depth_check(neo_ctx *c, int width, int height, double focal_px, double max_range, const double *boxes,
-                       const int32_t *box_begin, int n_scenes, int B, const double *pose, const float *depth_m) {
-  if (!c) return NEO_ERR_INVALID;
-  if (B < 1) return fail_locked(c, NEO_ERR_INVALID, "depth: B must be >= 1");
-  if (width < 1 || width > 4096 || height < 1 || height > 4096)
-    return fail_locked(c, NEO_ERR_INVALID, "depth: width and height must be in 1..4096");
-  if (!std::isfinite(focal_px) || !(focal_px > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "depth: focal_px must be finite and > 0");
-  if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "depth: max_range must be finite and > 0");
-  if (n_scenes < 1) return fail_locked(c, NEO_ERR_INVALID, "depth: n_scenes must be >= 1");
-  if (!boxes || !box_begin || !pose || !depth_m) return fail_locked(c, NEO_ERR_INVALID, "depth: null buffer");
-  return NEO_OK;
-}
-
-int neo_depth_render_batch_dev(neo_ctx *c, int width, int height, double focal_px, double max_range, const double *boxes,
-                               const int32_t *box_begin, int n_scenes, const int32_t *scene_index, int B,
-                               const double *pose, float *depth_m, uint8_t *depth_u8, float *depth_max) {
-  int rc = depth_check(c, width, height, focal_px, max_range, boxes, box_begin, n_scenes, B, pose, depth_m);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  return depth_render(c, DepthCall{width, height, focal_px, max_range, boxes, box_begin, n_scenes, scene_index, B, pose,
-                                   depth_m, depth_u8, depth_max});
-}
-
-int neo_depth_render_batch(neo_ctx *c, int width, int height, double focal_px, double max_range, const double *boxes,
-                           const int32_t *box_begin, int n_scenes, const int32_t *scene_index, int B, const double *pose,
-                           float *depth_m, uint8_t *depth_u8, float *depth_max) {
-  int rc = depth_check(c, width, height, focal_px, max_range, boxes, box_begin, n_scenes, B, pose, depth_m);
-  if (rc) return rc;
-  // what the device form cannot read on the host
-  if (box_begin[0] != 0) return fail_locked(c, NEO_ERR_INVALID, "depth: box_begin must start at 0");
-  for (int s = 0; s < n_scenes; ++s) {
-    if (box_begin[s + 1] < box_begin[s]) return fail_locked(c, NEO_ERR_INVALID, "depth: box_begin must be non-decreasing");
-    if (box_begin[s + 1] - box_begin[s] > NEO_DEPTH_MAX_BOXES)
-      return fail_locked(c, NEO_ERR_INVALID, "depth: a scene has more than NEO_DEPTH_MAX_BOXES boxes");
-  }
-  if (scene_index)
-    for (int b = 0; b < B; ++b)
-      if (scene_index[b] < 0 || scene_index[b] >= n_scenes)
-        return fail_locked(c, NEO_ERR_INVALID, "depth: a scene_index is outside 0 .. n_scenes - 1");
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  const size_t bs = (size_t)B, hw = (size_t)width * height, nbox = (size_t)box_begin[n_scenes];
-  HostStage st(c, 0);
-  const auto fb = st.in(nbox ? boxes : nullptr, nbox * 6, 6);  // (without any box: a valid pointer nothing is read from)
-  const auto fbb = st.in(box_begin, (size_t)n_scenes + 1);
-  const auto fsi = st.in(scene_index, bs);
-  const auto fp = st.in(pose, bs * 5);
-  const auto fm = st.out(depth_m, bs * hw);
-  const auto fu = st.out(depth_u8, depth_u8 ? bs * hw : 0);
-  const auto fx = st.out(depth_max, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_depth_render_batch_dev(c, width, height, focal_px, max_range, st.dev(fb), st.dev(fbb), n_scenes,
-                                  scene_index ? st.dev(fsi) : nullptr, B, st.dev(fp), st.dev(fm),
-                                  depth_u8 ? st.dev(fu) : nullptr, st.dev(fx));
-  if (rc) return rc;
-  return st.download();
-}
-
-int neo_depth_box_test_counter(neo_ctx *c, uint64_t *dev_count) {
-  if (!c) return NEO_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  c->depth.box_tests = reinterpret_cast<unsigned long long *>(dev_count);
-  return NEO_OK;
-}
-
-// ---- onboard mapping (launch/map_server_onboard.launch: octomap_server's scan insertion projected to 2-D; kernel:
-// neo_onboard.hpp).  The checks both forms make before anything is copied or launched (context unlocked); N and half
-// are the samples a ray and the window's reach in cells.
-static int onboard_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const float *depth_m, const double *pose,
-                         int width, int height, double focal_px, double max_range, int grid_w, int grid_h, double res,
-                         const double *origins, double sensor_range, double z_lo, double z_hi, int l_hit, int l_miss,
-                         int l_lo, int l_hi, const int8_t *logodds, const int8_t *occupancy, const int32_t *changed, int &N,
-                         int &half) {
-  int rc = list_check(c, "onboard", B, 1, 1 << 20, subset, n_subset);
-  if (rc) return rc;
-  if (width < 1 || width > 4096 || height < 1 || height > 4096)
-    return fail_locked(c, NEO_ERR_INVALID, "onboard: width and height must be in 1..4096");
-  if (!std::isfinite(focal_px) || !(focal_px > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "onboard: focal_px must be finite and > 0");
-  if (!std::isfinite(res) || !(res > 0.0)) return fail_locked(c, NEO_ERR_INVALID, "onboard: resolution must be finite and > 0");
-  if (!std::isfinite(sensor_range) || !(sensor_range > 0.0))
-    return fail_locked(c, NEO_ERR_INVALID, "onboard: sensor_range must be finite and > 0");
-  if (!(max_range >= sensor_range))
-    return fail_locked(c, NEO_ERR_INVALID, "onboard: the camera's max_range must reach sensor_range (a depth clipped below "
-                                           "it would read as a hit)");
-  if (!std::isfinite(z_lo) || !std::isfinite(z_hi) || !(z_lo <= z_hi))
-    return fail_locked(c, NEO_ERR_INVALID, "onboard: the band needs finite z_lo <= z_hi");
-  if (grid_w < 1 || grid_h < 1 || (size_t)grid_w * grid_h > (size_t)1 << 30)
-    return fail_locked(c, NEO_ERR_INVALID, "onboard: grid width and height >= 1, at most 2^30 cells");
-  if (l_lo < -127 || l_hi > 127 || l_lo > l_hi || l_hit < 0 || l_hit > 127 || l_miss > 0 || l_miss < -127)
-    return fail_locked(c, NEO_ERR_INVALID, "onboard: log-odds need -127 <= lo <= hi <= 127, 0 <= hit <= 127, -127 <= miss <= 0");
-  if (!depth_m || !pose || !origins || !logodds || !occupancy || !changed)
-    return fail_locked(c, NEO_ERR_INVALID, "onboard: null buffer");
-  const double nd = std::ceil(sensor_range / (res / 2.0));
-  half = onboard_window_half(width, focal_px, sensor_range, res);
-  if (!(nd <= 32767.0) || half > 4096 || onboard_lds_need(half, (int)nd, height) > onboard_lds_limit())
-    return fail_locked(c, NEO_ERR_INVALID, "onboard: the window a scan can touch (sensor_range against the resolution and "
-                                           "the camera's field of view) does not fit the 64 KB of LDS a workgroup has");
-  N = (int)nd;
-  return NEO_OK;
-}
-
-int neo_onboard_integrate_batch_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const float *depth_m,
-                                    const double *pose, int width, int height, double focal_px, double max_range, int grid_w,
-                                    int grid_h, double res, const double *origins, double sensor_range, double z_lo,
-                                    double z_hi, int l_hit, int l_miss, int l_lo, int l_hi, int8_t *logodds,
-                                    int8_t *occupancy, int32_t *changed) {
-  int N = 0, half = 0;
-  int rc = onboard_check(c, B, subset, n_subset, depth_m, pose, width, height, focal_px, max_range, grid_w, grid_h, res,
-                         origins, sensor_range, z_lo, z_hi, l_hit, l_miss, l_lo, l_hi, logodds, occupancy, changed, N, half);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return onboard_integrate(c, OnboardCall{list, depth_m, pose, width, height, focal_px, grid_w, grid_h, res,
-                                          origins, sensor_range, z_lo, z_hi, l_hit, l_miss, l_lo, l_hi, N, half, logodds,
-                                          occupancy, changed});
-}
-
-int neo_onboard_integrate_batch(neo_ctx *c, int B, const int32_t *subset, int n_subset, const float *depth_m,
-                                const double *pose, int width, int height, double focal_px, double max_range, int grid_w,
-                                int grid_h, double res, const double *origins, double sensor_range, double z_lo, double z_hi,
-                                int l_hit, int l_miss, int l_lo, int l_hi, int8_t *logodds, int8_t *occupancy,
-                                int32_t *changed) {
-  int N = 0, half = 0;
-  int rc = onboard_check(c, B, subset, n_subset, depth_m, pose, width, height, focal_px, max_range, grid_w, grid_h, res,
-                         origins, sensor_range, z_lo, z_hi, l_hit, l_miss, l_lo, l_hi, logodds, occupancy, changed, N, half);
-  if (rc) return rc;
-  if (subset) {
-    std::vector<char> seen((size_t)B, 0);
-    for (int i = 0; i < n_subset; ++i) {
-      if (subset[i] < 0 || subset[i] >= B) return fail_locked(c, NEO_ERR_INVALID, "onboard: a subset entry is outside 0 .. B - 1");
-      if (seen[subset[i]]) return fail_locked(c, NEO_ERR_INVALID, "onboard: a mission is listed twice in the subset");
-      seen[subset[i]] = 1;
-    }
-  }
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  const size_t bs = (size_t)B, nl = (size_t)launch_list(B, subset, n_subset).n, hw = (size_t)width * height;
-  const size_t ncell = (size_t)grid_w * grid_h;
-  if (nl == 0) return NEO_OK;
-  HostStage st(c, 0);
-  const auto fsub = st.in_optional(subset, nl);
-  const auto fd = st.in(depth_m, nl * hw);
-  const auto fp = st.in(pose, nl * 5);
-  const auto fo = st.in(origins, bs * 2);
-  const auto fl = st.inout(logodds, bs * ncell);    // (missions outside the subset keep their grids)
-  const auto fc = st.inout(occupancy, bs * ncell);
-  const auto fg = st.inout(changed, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_onboard_integrate_batch_dev(c, B, st.dev(fsub), n_subset, st.dev(fd), st.dev(fp), width, height,
-                                       focal_px, max_range, grid_w, grid_h, res, st.dev(fo), sensor_range, z_lo, z_hi, l_hit,
-                                       l_miss, l_lo, l_hi, st.dev(fl), st.dev(fc), st.dev(fg));
-  if (rc) return rc;
-  return st.download();
-}
-
-// ---- fleet replan loop (ros_node/traj_planner_node.py:390-578; kernels: neo_fleet.hpp)
-static bool fleet_positive(double v) { return std::isfinite(v) && v > 0.0; }
-
-// the 2-D maps of a fleet call (context locked)
-static int fleet_maps(neo_ctx *c, int scene_id, const int32_t *slots, MapRef &m) {
-  int rc = rebuild_tables(c);
-  if (rc) return rc;
-  CallMaps cm;
-  rc = resolve_call_maps(c, scene_id, slots != nullptr, cm);
-  if (rc) return rc;
-  if (cm.kind != 0) return fail(c, NEO_ERR_INVALID, "fleet: the 2-D reference map only (a 3-D map was given)");
-  m = {cm.table, slots, cm.nmaps};
-  return NEO_OK;
-}
-
-static int fleet_target_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cur_pos,
-                              const double *goal, const double *jitter, double longitu, double lateral, double move_vel,
-                              const double *tail, const int32_t *near_goal, const int32_t *lateral_steps,
-                              const int32_t *flags) {
-  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (!cur_pos || !goal || !jitter || !tail || !near_goal || !lateral_steps || !flags)
-    return fail_locked(c, NEO_ERR_INVALID, "fleet target: null buffer");
-  if (!fleet_positive(longitu) || !fleet_positive(lateral) || !std::isfinite(move_vel))
-    return fail_locked(c, NEO_ERR_INVALID, "fleet target: longitu_step_dis and lateral_step_length must be finite and > 0, "
-                                           "move_vel finite");
-  return NEO_OK;
-}
-
-int neo_fleet_target_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset,
-                               int n_subset, const double *cur_pos, const double *goal, const double *jitter,
-                               double longitu_step_dis, double lateral_step_length, double move_vel, double *tail,
-                               int32_t *near_goal, int32_t *lateral_steps, int32_t *flags) {
-  int rc = fleet_target_check(c, B, subset, n_subset, cur_pos, goal, jitter, longitu_step_dis, lateral_step_length,
-                              move_vel, tail, near_goal, lateral_steps, flags);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  MapRef maps;
-  rc = fleet_maps(c, scene_id, scene_ids, maps);
-  if (rc) return rc;
-  if (list.n == 0) return NEO_OK;
-  return launched(c, fleet_target(c, list, maps, {cur_pos, goal, jitter, longitu_step_dis, lateral_step_length, move_vel,
-                                                  tail, near_goal, lateral_steps, flags}));
-}
-
-int neo_fleet_target_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset, int n_subset,
-                           const double *cur_pos, const double *goal, const double *jitter, double longitu_step_dis,
-                           double lateral_step_length, double move_vel, double *tail, int32_t *near_goal,
-                           int32_t *lateral_steps, int32_t *flags) {
-  int rc = fleet_target_check(c, B, subset, n_subset, cur_pos, goal, jitter, longitu_step_dis, lateral_step_length,
-                              move_vel, tail, near_goal, lateral_steps, flags);
-  if (rc) return rc;
-  if (B == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  const size_t bs = (size_t)B;
-  std::vector<int> slots;
-  if (scene_ids) {
-    rc = scene_slots(c, scene_ids, bs, false, slots);
-    if (rc) return rc;
-  }
-  // all arrays small: the pinned mirror.  The outputs go up too: missions outside the subset keep their rows
-  HostStage st(c, kStagedUpTo);
-  const auto fp = st.in(cur_pos, bs * 2), fg = st.in(goal, bs * 2), fj = st.in(jitter, bs * 2);
-  const auto fs = st.in(scene_ids ? slots.data() : nullptr, bs);
-  const auto fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto ft = st.inout(tail, bs * 6);
-  const auto fn = st.inout(near_goal, bs), fl = st.inout(lateral_steps, bs), ff = st.inout(flags, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_fleet_target_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fs) : nullptr, B,
-                                  st.dev(fsub), n_subset, st.dev(fp), st.dev(fg), st.dev(fj), longitu_step_dis, lateral_step_length, move_vel, st.dev(ft), st.dev(fn), st.dev(fl),
-                                  st.dev(ff));
-  if (rc) return rc;
-  return st.download();
-}
-
-static int fleet_jitter_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int tick, int target,
-                              const double *jitter) {
-  int rc = list_check(c, "fleet jitter", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (!jitter) return fail_locked(c, NEO_ERR_INVALID, "fleet jitter: null buffer");
-  if (tick < 0 || target < 0) return fail_locked(c, NEO_ERR_INVALID, "fleet jitter: tick and target must be >= 0");
-  return NEO_OK;
-}
-
-int neo_fleet_jitter_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, uint64_t seed, int tick, int target,
-                         const int32_t *mission_ids, double *jitter) {
-  int rc = fleet_jitter_check(c, B, subset, n_subset, tick, target, jitter);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, fleet_jitter(c, list, seed, tick, target, mission_ids, jitter));
-}
-
-int neo_fleet_jitter(neo_ctx *c, int B, const int32_t *subset, int n_subset, uint64_t seed, int tick, int target,
-                     const int32_t *mission_ids, double *jitter) {
-  int rc = fleet_jitter_check(c, B, subset, n_subset, tick, target, jitter);
-  if (rc) return rc;
-  if (launch_list(B, subset, n_subset).n == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  const size_t bs = (size_t)B;
-  // the rows go up too: missions outside the subset keep theirs
-  HostStage st(c, kStagedUpTo);
-  const auto fi = st.in_optional(mission_ids, bs), fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto fj = st.inout(jitter, bs * 2);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_fleet_jitter_dev(c, B, st.dev(fsub), n_subset, seed, tick, target, st.dev(fi), st.dev(fj));
-  if (rc) return rc;
-  return st.download();
-}
-
-static int fleet_cmd_check(neo_ctx *c, const char *who, const double *cmd, int cap, const int32_t *cmd_len,
-                           const int32_t *cmd_index, const int32_t *future_index) {
-  if (!cmd || !cmd_len || !cmd_index || !future_index)
-    return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": null buffer").c_str());
-  if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": cap must be > 0").c_str());
-  return NEO_OK;
-}
-
-int neo_fleet_advance_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
-                          const int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index, int step, int ahead,
-                          double *cur_pos, double *head) {
-  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  rc = fleet_cmd_check(c, "fleet advance", cmd, cap, cmd_len, cmd_index, future_index);
-  if (rc) return rc;
-  if (!cur_pos || !head) return fail_locked(c, NEO_ERR_INVALID, "fleet advance: null buffer");
-  if (step < 0 || step > (1 << 30) || ahead < 0 || ahead > (1 << 30))
-    return fail_locked(c, NEO_ERR_INVALID, "fleet advance: step and ahead must be in 0 .. 2^30");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, fleet_advance(c, list, {const_cast<double *>(cmd), cap, const_cast<int32_t *>(cmd_len), cmd_index,
-                                             future_index}, step, ahead, cur_pos, head));
-}
-
-int neo_fleet_pose_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
-                       const int32_t *cmd_len, const int32_t *cmd_index, const double *cur_pos, const double *goal,
-                       double eye_z, double *pose) {
-  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (!cmd || !cmd_len || !cmd_index || !cur_pos || !goal || !pose) return fail_locked(c, NEO_ERR_INVALID, "fleet pose: null buffer");
-  if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, "fleet pose: cap must be > 0");
-  if (!std::isfinite(eye_z)) return fail_locked(c, NEO_ERR_INVALID, "fleet pose: eye_z must be finite");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, fleet_pose(c, list, {const_cast<double *>(cmd), cap, const_cast<int32_t *>(cmd_len),
-                                          const_cast<int32_t *>(cmd_index), nullptr}, cur_pos, goal, eye_z, pose));
-}
-
-int neo_fleet_splice_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, const double *x, const double *head,
-                         const double *tail, const int32_t *solved, double hz, int first, double *cmd, int cap,
-                         int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index, int32_t *flags) {
-  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  rc = check_shape(c, B, M, 2);
-  if (rc) return rc;
-  rc = fleet_cmd_check(c, "fleet splice", cmd, cap, cmd_len, cmd_index, future_index);
-  if (rc) return rc;
-  if (!x || !head || !tail || !flags) return fail_locked(c, NEO_ERR_INVALID, "fleet splice: null buffer");
-  if (!fleet_positive(hz)) return fail_locked(c, NEO_ERR_INVALID, "fleet splice: hz must be finite and > 0");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, fleet_splice(c, list, {cmd, cap, cmd_len, cmd_index, future_index},
-                                  {M, x, head, tail, solved, hz, first ? 1 : 0, flags}));
-}
-
-// mode "warmstart": the state a mission carries from one plan to the next
-static int fleet_warm_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M) {
-  int rc = list_check(c, who, B, 1, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (M < 2 || M > NEO_MAX_PIECES) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": M must be in 2 .. 64").c_str());
-  return NEO_OK;
-}
-
-int neo_fleet_warm_guess_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, const double *head,
-                             const double *wpts_local, const double *ts_carry, double *x0) {
-  int rc = fleet_warm_check(c, "fleet warm guess", B, subset, n_subset, M);
-  if (rc) return rc;
-  if (!head || !wpts_local || !ts_carry || !x0) return fail_locked(c, NEO_ERR_INVALID, "fleet warm guess: null buffer");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, fleet_warm_guess(c, list, M, head, wpts_local, ts_carry, x0));
-}
-
-int neo_fleet_warm_carry_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, const double *x,
-                             const double *head, const int32_t *solved, const int32_t *status, const int32_t *attempts,
-                             const double *init_ts, double *wpts_local, double *ts_carry) {
-  int rc = fleet_warm_check(c, "fleet warm carry", B, subset, n_subset, M);
-  if (rc) return rc;
-  if (!x || !head || !solved || !status || !attempts || !init_ts || !wpts_local || !ts_carry)
-    return fail_locked(c, NEO_ERR_INVALID, "fleet warm carry: null buffer");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, fleet_warm_carry(c, list, {M, x, head, solved, status, attempts, init_ts, wpts_local, ts_carry}));
-}
-
-static int fleet_audit_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
-                             const int32_t *n_flown, int stride, double cmd_hz, const double *audit, const int32_t *count,
-                             const int32_t *flags) {
-  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (!cmd || !n_flown || !audit || !count || !flags) return fail_locked(c, NEO_ERR_INVALID, "fleet audit: null buffer");
-  if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, "fleet audit: cap must be > 0");
-  if (stride <= 0) return fail_locked(c, NEO_ERR_INVALID, "fleet audit: stride must be > 0");
-  if (!fleet_positive(cmd_hz)) return fail_locked(c, NEO_ERR_INVALID, "fleet audit: cmd_hz must be finite and > 0");
-  return NEO_OK;
-}
-
-int neo_fleet_audit_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset, int n_subset,
-                              const double *cmd, int cap, const int32_t *n_flown, int stride, double cmd_hz,
-                              const double *weights3, double *audit, int32_t *count, int32_t *flags) {
-  int rc = fleet_audit_check(c, B, subset, n_subset, cmd, cap, n_flown, stride, cmd_hz, audit, count, flags);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  MapRef maps;
-  rc = fleet_maps(c, scene_id, scene_ids, maps);
-  if (rc) return rc;
-  if (list.n == 0) return NEO_OK;
-  FleetAuditArgs aa{cmd, cap, n_flown, stride, cmd_hz, {1.0, 1.0, 100.0}, audit, count, flags};
-  if (weights3)
-    for (int k = 0; k < 3; ++k) aa.w[k] = weights3[k];
-  return launched(c, fleet_audit(c, list, maps, aa));
-}
-
-int neo_fleet_audit_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const int32_t *subset, int n_subset,
-                          const double *cmd, int cap, const int32_t *n_flown, int stride, double cmd_hz,
-                          const double *weights3, double *audit, int32_t *count, int32_t *flags) {
-  int rc = fleet_audit_check(c, B, subset, n_subset, cmd, cap, n_flown, stride, cmd_hz, audit, count, flags);
-  if (rc) return rc;
-  if (B == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  const size_t bs = (size_t)B;
-  std::vector<int> slots;
-  if (scene_ids) {
-    rc = scene_slots(c, scene_ids, bs, false, slots);
-    if (rc) return rc;
-  }
-  HostStage st(c, 0);
-  const auto fc = st.in(cmd, bs * cap * 6);
-  const auto fnf = st.in(n_flown, bs);
-  const auto fs = st.in(scene_ids ? slots.data() : nullptr, bs);
-  const auto fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto fa = st.inout(audit, bs * NEO_AUDIT_FIELDS);  // (missions outside the subset keep their records)
-  const auto fcnt = st.inout(count, bs), ffl = st.inout(flags, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_fleet_audit_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fs) : nullptr, B,
-                                 st.dev(fsub), n_subset, st.dev(fc), cap, st.dev(fnf), stride, cmd_hz,
-                                 weights3, st.dev(fa), st.dev(fcnt), st.dev(ffl));
-  if (rc) return rc;
-  return st.download();
-}
-
-// ---- fleet goal routes (ros_node/tracker_planner_node.py; kernels: neo_track.hpp)
-static int fleet_routes_check(neo_ctx *c, const char *who, const double *vertices, int n_vertices,
-                              const int32_t *route_begin, const double *speed) {
-  if (!vertices || !route_begin || !speed)
-    return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": null buffer").c_str());
-  if (n_vertices < 0) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": n_vertices must be >= 0").c_str());
-  return NEO_OK;
-}
-
-static int fleet_goal_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *vertices, int n_vertices,
-                            const int32_t *route_begin, const double *speed, double t, const double *goal) {
-  int rc = list_check(c, "fleet goal", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  rc = fleet_routes_check(c, "fleet goal", vertices, n_vertices, route_begin, speed);
-  if (rc) return rc;
-  if (!goal) return fail_locked(c, NEO_ERR_INVALID, "fleet goal: null buffer");
-  if (!std::isfinite(t)) return fail_locked(c, NEO_ERR_INVALID, "fleet goal: t must be finite");
-  return NEO_OK;
-}
-
-int neo_fleet_goal_route_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *vertices, int n_vertices,
-                             const int32_t *route_begin, const double *speed, const int32_t *closed, double t,
-                             double *goal) {
-  int rc = fleet_goal_check(c, B, subset, n_subset, vertices, n_vertices, route_begin, speed, t, goal);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, fleet_goal(c, list, {vertices, n_vertices, route_begin, speed, closed}, t, goal));
-}
-
-int neo_fleet_goal_route(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *vertices, int n_vertices,
-                         const int32_t *route_begin, const double *speed, const int32_t *closed, double t, double *goal) {
-  int rc = fleet_goal_check(c, B, subset, n_subset, vertices, n_vertices, route_begin, speed, t, goal);
-  if (rc) return rc;
-  if (launch_list(B, subset, n_subset).n == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  const size_t bs = (size_t)B;
-  // the rows go up too: missions outside the subset keep theirs
-  HostStage st(c, kStagedUpTo);
-  const auto fv = st.in(vertices, (size_t)n_vertices * 2, 2), fs = st.in(speed, bs);
-  const auto fb = st.in(route_begin, bs + 1);
-  const auto fc = st.in_optional(closed, bs), fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto fg = st.inout(goal, bs * 2);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_fleet_goal_route_dev(c, B, st.dev(fsub), n_subset, st.dev(fv), n_vertices, st.dev(fb), st.dev(fs), st.dev(fc), t,
-                                st.dev(fg));
-  if (rc) return rc;
-  return st.download();
-}
-
-int neo_fleet_hold_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, double *cmd, int cap, int32_t *cmd_len,
-                       const int32_t *cmd_index, int step, int32_t *flags) {
-  int rc = list_check(c, "fleet hold", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (!cmd || !cmd_len || !cmd_index || !flags) return fail_locked(c, NEO_ERR_INVALID, "fleet hold: null buffer");
-  if (cap < 1) return fail_locked(c, NEO_ERR_INVALID, "fleet hold: cap must be >= 1");
-  if (step < 1 || step > (1 << 30)) return fail_locked(c, NEO_ERR_INVALID, "fleet hold: step must be in 1 .. 2^30");
-  if (reinterpret_cast<uintptr_t>(cmd) & 15) return fail_locked(c, NEO_ERR_INVALID, "fleet hold: cmd must be 16-byte aligned");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, fleet_hold(c, list, {cmd, cap, cmd_len, const_cast<int32_t *>(cmd_index), nullptr}, step, flags));
-}
-
-static int fleet_track_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
-                             const int32_t *n_flown, int stride, double cmd_hz, const double *vertices, int n_vertices,
-                             const int32_t *route_begin, const double *speed, double radius, const double *track,
-                             const int32_t *count, const int32_t *flags) {
-  int rc = list_check(c, "fleet track audit", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  rc = fleet_routes_check(c, "fleet track audit", vertices, n_vertices, route_begin, speed);
-  if (rc) return rc;
-  if (!cmd || !n_flown || !track || !count || !flags) return fail_locked(c, NEO_ERR_INVALID, "fleet track audit: null buffer");
-  if (cap < 1) return fail_locked(c, NEO_ERR_INVALID, "fleet track audit: cap must be >= 1");
-  if (stride < 1) return fail_locked(c, NEO_ERR_INVALID, "fleet track audit: stride must be >= 1");
-  if (!fleet_positive(cmd_hz)) return fail_locked(c, NEO_ERR_INVALID, "fleet track audit: cmd_hz must be finite and > 0");
-  if (!std::isfinite(radius)) return fail_locked(c, NEO_ERR_INVALID, "fleet track audit: radius must be finite");
-  return NEO_OK;
-}
-
-int neo_fleet_track_audit_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
-                              const int32_t *n_flown, int stride, double cmd_hz, const double *vertices, int n_vertices,
-                              const int32_t *route_begin, const double *speed, const int32_t *closed, double radius,
-                              double *track, int32_t *count, int32_t *flags) {
-  int rc = fleet_track_check(c, B, subset, n_subset, cmd, cap, n_flown, stride, cmd_hz, vertices, n_vertices, route_begin,
-                             speed, radius, track, count, flags);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, fleet_track_audit(c, list, {vertices, n_vertices, route_begin, speed, closed},
-                                       {cmd, cap, n_flown, stride, cmd_hz, radius, track, count, flags}));
-}
-
-int neo_fleet_track_audit(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
-                          const int32_t *n_flown, int stride, double cmd_hz, const double *vertices, int n_vertices,
-                          const int32_t *route_begin, const double *speed, const int32_t *closed, double radius,
-                          double *track, int32_t *count, int32_t *flags) {
-  int rc = fleet_track_check(c, B, subset, n_subset, cmd, cap, n_flown, stride, cmd_hz, vertices, n_vertices, route_begin,
-                             speed, radius, track, count, flags);
-  if (rc) return rc;
-  if (launch_list(B, subset, n_subset).n == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  const size_t bs = (size_t)B;
-  HostStage st(c, 0);
-  const auto fc = st.in(cmd, bs * cap * 6);
-  const auto fnf = st.in(n_flown, bs);
-  const auto fv = st.in(vertices, (size_t)n_vertices * 2, 2), fs = st.in(speed, bs);
-  const auto fb = st.in(route_begin, bs + 1);
-  const auto fcl = st.in_optional(closed, bs), fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto ft = st.inout(track, bs * NEO_TRACK_FIELDS);  // (missions outside the subset keep their records)
-  const auto fcnt = st.inout(count, bs), ffl = st.inout(flags, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_fleet_track_audit_dev(c, B, st.dev(fsub), n_subset, st.dev(fc), cap, st.dev(fnf), stride, cmd_hz, st.dev(fv),
-                                 n_vertices, st.dev(fb), st.dev(fs), st.dev(fcl), radius, st.dev(ft), st.dev(fcnt),
-                                 st.dev(ffl));
-  if (rc) return rc;
-  return st.download();
-}
-
-// ---- the fleet's record mode (traj_planner/record_planner.py:13-72; kernels: neo_record.hpp)
-int neo_record_state_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *cmd, int cap,
-                         const int32_t *cmd_len, const int32_t *cmd_index, const double *head, double *cur_vel) {
-  int rc = list_check(c, "record", B, 1, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (!cmd || !cmd_len || !cmd_index || !head || !cur_vel) return fail_locked(c, NEO_ERR_INVALID, "record state: null buffer");
-  if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, "record state: cap must be > 0");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, record_state(c, list, cmd, cap, cmd_len, cmd_index, head, cur_vel));
-}
-
-int neo_record_commit_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, const double *x, const double *head,
-                          const double *tail, const int32_t *solved, const double *pose, const double *cur_vel,
-                          const uint8_t *staging, int width, int height, const int32_t *mission_ids, int tick, int round,
-                          int capacity, double *motion, double *wpts_local, double *tau, double *pose_rows, int32_t *meta,
-                          uint8_t *images, int32_t *row_of, int32_t *n_rows, int32_t *dropped) {
-  int rc = list_check(c, "record", B, 1, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (M < 2 || M > NEO_MAX_PIECES) return fail_locked(c, NEO_ERR_INVALID, "record commit: M must be in 2 .. 64");
-  if (capacity < 1) return fail_locked(c, NEO_ERR_INVALID, "record commit: capacity must be >= 1");
-  if (width < 1 || width > 4096 || height < 1 || height > 4096)
-    return fail_locked(c, NEO_ERR_INVALID, "record commit: width and height must be in 1 .. 4096");
-  if (!x || !head || !tail || !pose || !cur_vel || !staging || !motion || !wpts_local || !tau || !pose_rows || !meta ||
-      !images || !row_of || !n_rows || !dropped)
-    return fail_locked(c, NEO_ERR_INVALID, "record commit: null buffer");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, record_commit(c, list, RecordCommitArgs{M, x, head, tail, solved, pose, cur_vel, staging, width, height,
-                                                             mission_ids, tick, round, capacity, motion, wpts_local, tau,
-                                                             pose_rows, meta, images, row_of, n_rows, dropped}));
-}
-
-// ---- the learned warm start on resident arrays (traj_planner/neo_planner.py:10-51; kernels: neo_init.hpp)
-int neo_init_motion_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const double *pose, const double *cur_vel,
-                        const double *head, const double *tail, float *motion) {
-  int rc = list_check(c, "init motion", B, 1, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (!pose || !cur_vel || !head || !tail || !motion) return fail_locked(c, NEO_ERR_INVALID, "init motion: null buffer");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, init_motion(c, list, pose, cur_vel, head, tail, motion));
-}
-
-int neo_init_head_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const float *weights, size_t n_weights,
-                      const float *feature, int feature_rows, const float *motion, float *out) {
-  int rc = list_check(c, "init head", B, 1, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (!weights || !feature || !motion || !out) return fail_locked(c, NEO_ERR_INVALID, "init head: null buffer");
-  if (n_weights != (size_t)NEO_INIT_HEAD_FLOATS)
-    return fail_locked(c, NEO_ERR_INVALID, "init head: n_weights must be NEO_INIT_HEAD_FLOATS (20817)");
-  if (feature_rows != 1 && feature_rows != B)
-    return fail_locked(c, NEO_ERR_INVALID, "init head: feature_rows must be 1 or B");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, init_head(c, list, weights, feature, feature_rows, motion, out));
-}
-
-int neo_init_guess_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const float *out, const double *pose,
-                       double *x0) {
-  int rc = list_check(c, "init guess", B, 1, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (!out || !pose || !x0) return fail_locked(c, NEO_ERR_INVALID, "init guess: null buffer");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, init_guess(c, list, out, pose, x0));
-}
-
-// ---- the `batch` planner mode on resident arrays (traj_planner/expert_planner.py:103-168; kernels: neo_batch.hpp)
-static const double kBatchOffset = 0.6;  // :135
-static int batch_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M, int D, int K) {
-  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  if (D != 2) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": D must be 2 (the reference's lateral candidates are 2-D)").c_str());
-  if (K < 1 || K > NEO_BATCH_MAX_CANDIDATES)
-    return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": K must be in 1 .. 8").c_str());
-  rc = check_shape(c, B, M, D);
-  if (rc) return rc;
-  if (M < 2) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": M must be >= 2 (at least one waypoint)").c_str());
-  if ((long long)launch_list(B, subset, n_subset).n * K > (long long)INT32_MAX)
-    return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": more than 2^31 - 1 candidate rows").c_str());
-  return NEO_OK;
-}
-// the reference's offsets 0, +0.6, -0.6, +0.6, ... (lateral_dir[(k - 1) % 2], :131-137)
-static void batch_default_offsets(int K, double *off) {
-  for (int k = 0; k < K; ++k) off[k] = k == 0 ? 0.0 : (k % 2 ? kBatchOffset : -kBatchOffset);
-}
-
-int neo_batch_candidates_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *head,
-                             const double *tail, const int32_t *slots, const double *tau, const double *lateral_offsets,
-                             double *x0, double *head_k, double *tail_k, int32_t *slots_k) {
-  int rc = batch_check(c, "batch candidates", B, subset, n_subset, M, D, K);
-  if (rc) return rc;
-  if (!head || !tail || !tau || !x0 || !head_k || !tail_k)
-    return fail_locked(c, NEO_ERR_INVALID, "batch candidates: null buffer");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  double off[NEO_BATCH_MAX_CANDIDATES];
-  batch_default_offsets(K, off);
-  if (lateral_offsets)
-    for (int k = 0; k < K; ++k) off[k] = lateral_offsets[k];
-  return launched(c, batch_candidates(c, list, {M, K, head, tail, slots, tau, off, x0, head_k, tail_k, slots_k}));
-}
-
-int neo_batch_candidates(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *head,
-                         const double *tail, const int32_t *slots, const double *tau, const double *lateral_offsets,
-                         double *x0, double *head_k, double *tail_k, int32_t *slots_k) {
-  int rc = batch_check(c, "batch candidates", B, subset, n_subset, M, D, K);
-  if (rc) return rc;
-  if (!head || !tail || !tau || !x0 || !head_k || !tail_k)
-    return fail_locked(c, NEO_ERR_INVALID, "batch candidates: null buffer");
-  const size_t bs = (size_t)B, rows = (size_t)launch_list(B, subset, n_subset).n * K, n = (size_t)D * (M - 1) + M;
-  if (rows == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  // the packed outputs go up too: the rows of a skipped index come back as they were
-  HostStage st(c, kStagedUpTo);
-  const auto fh = st.in(head, bs * 6), ft = st.in(tail, bs * 6);
-  const auto fs = st.in_optional(slots, bs), fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto fx = st.inout(x0, rows * n), fhk = st.inout(head_k, rows * 6), ftk = st.inout(tail_k, rows * 6);
-  const auto fsk = st.inout_optional(slots_k, rows);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_batch_candidates_dev(c, B, st.dev(fsub), n_subset, M, D, K, st.dev(fh), st.dev(ft), st.dev(fs), tau,
-                                lateral_offsets, st.dev(fx), st.dev(fhk), st.dev(ftk), st.dev(fsk));
-  if (rc) return rc;
-  return st.download();
-}
-
-static int batch_select_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const BatchSelectArgs &a) {
-  int rc = batch_check(c, "batch select", B, subset, n_subset, M, D, a.K);
-  if (rc) return rc;
-  const RunRowsIn &k = a.packed;
-  const RunRows &o = a.out;
-  if (!k.x || !k.costs4 || !k.costs4_last || !k.nit || !k.status || !a.chosen || !a.cand_cost || !a.solved || !o.x ||
-      !o.costs4 || !o.costs4_last || !o.status || !a.nit_total || !a.opt_runs || !a.fallback || !a.n_fallback)
-    return fail_locked(c, NEO_ERR_INVALID, "batch select: null buffer");
-  if (o.nfev && !k.nfev) return fail_locked(c, NEO_ERR_INVALID, "batch select: nfev without nfev_k");
-  return NEO_OK;
-}
-
-int neo_batch_select_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *x_k,
-                         const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
-                         const int32_t *status_k, const double *weights4, int32_t *chosen, double *cand_cost,
-                         int32_t *solved, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
-                         int32_t *status, int32_t *nit_total, int32_t *opt_runs, int32_t *fallback, int32_t *n_fallback) {
-  BatchSelectArgs a{D * (M - 1) + M, K, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k}, weights4, chosen, cand_cost,
-                    solved, {x, costs4, costs4_last, nit, nfev, status}, nit_total, opt_runs, fallback, n_fallback};
-  int rc = batch_select_check(c, B, subset, n_subset, M, D, a);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) {
-    HIPCHK(c, hipMemsetAsync(n_fallback, 0, sizeof(int32_t), c->stream));
-    return NEO_OK;
-  }
-  if (!a.w) a.w = c->params.weights;
-  return launched(c, batch_select(c, list, a));
-}
-
-int neo_batch_select(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int K, const double *x_k,
-                     const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
-                     const int32_t *status_k, const double *weights4, int32_t *chosen, double *cand_cost, int32_t *solved,
-                     double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev, int32_t *status,
-                     int32_t *nit_total, int32_t *opt_runs, int32_t *fallback, int32_t *n_fallback) {
-  const BatchSelectArgs a{D * (M - 1) + M, K, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k}, weights4, chosen,
-                          cand_cost, solved, {x, costs4, costs4_last, nit, nfev, status}, nit_total, opt_runs, fallback,
-                          n_fallback};
-  int rc = batch_select_check(c, B, subset, n_subset, M, D, a);
-  if (rc) return rc;
-  const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n;
-  if (P == 0) {
-    *n_fallback = 0;
-    return NEO_OK;
-  }
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  // the request-indexed outputs go up too: requests outside the subset, and x of a request without a choice, stay
-  HostStage st(c, kStagedUpTo);
-  const RowRefs fk = stage_rows_in(st, a.packed, P * K, (size_t)a.n);
-  const auto fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto och = st.inout(chosen, bs);
-  const auto occ = st.inout(cand_cost, bs * K);
-  const auto oso = st.inout(solved, bs);
-  const RowRefs fo = stage_rows_inout(st, a.out, bs, (size_t)a.n);
-  const auto ont = st.inout(nit_total, bs), oru = st.inout(opt_runs, bs);
-  // (the whole list comes back; its entries from n_fallback on are scratch)
-  const auto ofb = st.out(fallback, P), onb = st.out(n_fallback, 1);
-  rc = st.upload();
-  if (rc) return rc;
-  const RunRowsIn k = as_const(staged_rows(st, fk));
-  const RunRows o = staged_rows(st, fo);
-  rc = neo_batch_select_dev(c, B, st.dev(fsub), n_subset, M, D, K, k.x, k.costs4, k.costs4_last, k.nit, k.nfev, k.status,
-                            weights4, st.dev(och), st.dev(occ), st.dev(oso), o.x, o.costs4, o.costs4_last, o.nit, o.nfev,
-                            o.status, st.dev(ont), st.dev(oru), st.dev(ofb), st.dev(onb));
-  if (rc) return rc;
-  return st.download();
-}
-
-// ---- BatchPlanner.plan's retry chain on resident arrays (traj_planner/expert_planner.py:186-203; kernels: neo_plan.hpp)
-static int plan_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M, int D) {
-  int rc = list_check(c, "fleet", B, 0, INT32_MAX, subset, n_subset);
-  if (rc) return rc;
-  rc = check_shape(c, B, M, D);
-  if (rc) return rc;
-  if (M < 2) return fail_locked(c, NEO_ERR_INVALID, (std::string(who) + ": M must be >= 2 (at least one waypoint)").c_str());
-  return NEO_OK;
-}
-
-static int plan_guess_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const void *head,
-                            const void *tail, const void *x_init, const void *frac, const void *tau, const void *x0,
-                            const void *head_k, const void *tail_k) {
-  int rc = plan_check(c, "plan guess", B, subset, n_subset, M, D);
-  if (rc) return rc;
-  if (!head || !tail || !x0 || !head_k || !tail_k) return fail_locked(c, NEO_ERR_INVALID, "plan guess: null buffer");
-  if (!x_init && (!frac || !tau)) return fail_locked(c, NEO_ERR_INVALID, "plan guess: frac and tau are needed without x_init");
-  return NEO_OK;
-}
-
-int neo_plan_guess_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const double *head,
-                       const double *tail, const int32_t *slots, const double *x_init, const double *noise,
-                       const double *frac, const double *tau, double *x0, double *head_k, double *tail_k,
-                       int32_t *slots_k) {
-  int rc = plan_guess_check(c, B, subset, n_subset, M, D, head, tail, x_init, frac, tau, x0, head_k, tail_k);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, plan_guess(c, list, D, {M, head, tail, slots, x_init, noise, frac, tau, x0, head_k, tail_k, slots_k}));
-}
-
-int neo_plan_guess(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, const double *head,
-                   const double *tail, const int32_t *slots, const double *x_init, const double *noise, const double *frac,
-                   const double *tau, double *x0, double *head_k, double *tail_k, int32_t *slots_k) {
-  int rc = plan_guess_check(c, B, subset, n_subset, M, D, head, tail, x_init, frac, tau, x0, head_k, tail_k);
-  if (rc) return rc;
-  const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n, n = (size_t)D * (M - 1) + M, hd = (size_t)3 * D;
-  if (P == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  // the packed outputs go up too: the rows of a skipped index come back as they were
-  HostStage st(c, kStagedUpTo);
-  const auto fh = st.in(head, bs * hd), ft = st.in(tail, bs * hd);
-  const auto fs = st.in_optional(slots, bs), fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto fxi = st.in_optional(x_init, bs * n), fno = st.in_optional(noise, P * (size_t)D * (M - 1));
-  const auto fx = st.inout(x0, P * n), fhk = st.inout(head_k, P * hd), ftk = st.inout(tail_k, P * hd);
-  const auto fsk = st.inout_optional(slots_k, P);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_plan_guess_dev(c, B, st.dev(fsub), n_subset, M, D, st.dev(fh), st.dev(ft), st.dev(fs), st.dev(fxi), st.dev(fno),
-                          frac, tau, st.dev(fx), st.dev(fhk), st.dev(ftk), st.dev(fsk));
-  if (rc) return rc;
-  return st.download();
-}
-
-static int plan_jitter_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int attempt,
-                             const double *noise) {
-  int rc = plan_check(c, "plan jitter", B, subset, n_subset, M, D);
-  if (rc) return rc;
-  if (!noise) return fail_locked(c, NEO_ERR_INVALID, "plan jitter: null buffer");
-  if (attempt < 0) return fail_locked(c, NEO_ERR_INVALID, "plan jitter: attempt must be >= 0");
-  return NEO_OK;
-}
-
-int neo_plan_jitter_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, uint64_t seed, int attempt,
-                        const int32_t *stream_ids, double *noise) {
-  int rc = plan_jitter_check(c, B, subset, n_subset, M, D, attempt, noise);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, plan_jitter(c, list, M, D, seed, attempt, stream_ids, noise));
-}
-
-int neo_plan_jitter(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, uint64_t seed, int attempt,
-                    const int32_t *stream_ids, double *noise) {
-  int rc = plan_jitter_check(c, B, subset, n_subset, M, D, attempt, noise);
-  if (rc) return rc;
-  const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n;
-  if (P == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  // the packed rows go up too: the rows of a skipped index come back as they were
-  HostStage st(c, kStagedUpTo);
-  const auto fi = st.in_optional(stream_ids, bs), fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto fno = st.inout(noise, P * (size_t)D * (M - 1));
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_plan_jitter_dev(c, B, st.dev(fsub), n_subset, M, D, seed, attempt, st.dev(fi), st.dev(fno));
-  if (rc) return rc;
-  return st.download();
-}
-
-// the arrays of the three merge entry points as the launcher takes them (x in rows of n), their one check -- `compacts`:
-// n_failed is needed -- and the body of the two device ones: the merge, then with n_failed the compaction
-static PlanMergeArgs plan_merge_args(int M, int D, int reset, const double *x_k, const double *costs4_k, const double *costs4_last_k,
-                                     const int32_t *nit_k, const int32_t *nfev_k, const int32_t *status_k, double *x, double *costs4,
-                                     double *costs4_last, int32_t *nit, int32_t *nfev, int32_t *status, int32_t *attempts,
-                                     int64_t *nit_total, int32_t *solved, int32_t *failed, int32_t *n_failed, int32_t *bad_scene) {
-  static_assert(sizeof(long long) == sizeof(int64_t), "nit_total is a 64-bit integer on both sides");
-  const int n = D * (M - 1) + M;
-  return {n, n, reset ? 1 : 0, {x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k}, {x, costs4, costs4_last, nit, nfev, status},
-          attempts, reinterpret_cast<long long *>(nit_total), solved, failed, n_failed, bad_scene};
-}
-
-static int plan_merge_check(neo_ctx *c, const std::string &who, int B, const int32_t *subset, int n_subset, int M, int D,
-                            const PlanMergeArgs &a, bool compacts) {
-  int rc = plan_check(c, who.c_str(), B, subset, n_subset, M, D);
-  if (rc) return rc;
-  if (a.ldx < a.n) return fail_locked(c, NEO_ERR_INVALID, (who + ": x_stride must be >= n = D (M - 1) + M").c_str());
-  const RunRowsIn &k = a.packed;
-  const RunRows &o = a.out;
-  if (!k.x || !k.costs4 || !k.costs4_last || !k.nit || !k.nfev || !k.status || !o.x || !o.costs4 || !o.costs4_last || !o.nit ||
-      !o.nfev || !o.status || !a.attempts || !a.nit_total || !a.solved || !a.failed || !a.bad_scene || (compacts && !a.n_failed))
-    return fail_locked(c, NEO_ERR_INVALID, (who + ": null buffer").c_str());
-  return NEO_OK;
-}
-
-static int plan_merge_dev(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset, int M, int D,
-                          const PlanMergeArgs &a, bool compacts, bool clear_bad) {
-  if (int rc = plan_merge_check(c, who, B, subset, n_subset, M, D, a, compacts)) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (clear_bad) HIPCHK(c, hipMemsetAsync(a.bad_scene, 0, sizeof(int32_t), c->stream));
-  if (list.n > 0) return launched(c, plan_merge(c, list, a));
-  if (compacts) HIPCHK(c, hipMemsetAsync(a.n_failed, 0, sizeof(int32_t), c->stream));
-  return NEO_OK;
-}
-
-int neo_plan_merge_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int reset, const double *x_k,
-                       const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
-                       const int32_t *status_k, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
-                       int32_t *status, int32_t *attempts, int64_t *nit_total, int32_t *solved, int32_t *failed,
-                       int32_t *n_failed, int32_t *bad_scene) {
-  const PlanMergeArgs a = plan_merge_args(M, D, reset, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4, costs4_last,
-                                          nit, nfev, status, attempts, nit_total, solved, failed, n_failed, bad_scene);
-  return plan_merge_dev(c, "plan merge", B, subset, n_subset, M, D, a, true, true);
-}
-
-int neo_plan_merge(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int reset, const double *x_k,
-                   const double *costs4_k, const double *costs4_last_k, const int32_t *nit_k, const int32_t *nfev_k,
-                   const int32_t *status_k, double *x, double *costs4, double *costs4_last, int32_t *nit, int32_t *nfev,
-                   int32_t *status, int32_t *attempts, int64_t *nit_total, int32_t *solved, int32_t *failed,
-                   int32_t *n_failed, int32_t *bad_scene) {
-  const PlanMergeArgs a = plan_merge_args(M, D, reset, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4, costs4_last,
-                                          nit, nfev, status, attempts, nit_total, solved, failed, n_failed, bad_scene);
-  int rc = plan_merge_check(c, "plan merge", B, subset, n_subset, M, D, a, true);
-  if (rc) return rc;
-  const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n;
-  if (P == 0) {
-    *n_failed = 0;
-    *bad_scene = 0;
-    return NEO_OK;
-  }
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  // the request-indexed arrays go up too: requests outside the subset stay, attempts and nit_total accumulate
-  HostStage st(c, kStagedUpTo);
-  const RowRefs fk = stage_rows_in(st, a.packed, P, (size_t)a.n);
-  const auto fsub = st.in_optional(subset, (size_t)n_subset);
-  const RowRefs fo = stage_rows_inout(st, a.out, bs, (size_t)a.n);
-  const auto oat = st.inout(attempts, bs);
-  const auto ont = st.inout(nit_total, bs);
-  const auto oso = st.inout(solved, bs);
-  // (the whole list comes back; its entries from n_failed on are scratch)
-  const auto ofl = st.out(failed, P), onl = st.out(n_failed, 1), obs = st.out(bad_scene, 1);
-  rc = st.upload();
-  if (rc) return rc;
-  const RunRowsIn k = as_const(staged_rows(st, fk));
-  const RunRows o = staged_rows(st, fo);
-  rc = neo_plan_merge_dev(c, B, st.dev(fsub), n_subset, M, D, reset, k.x, k.costs4, k.costs4_last, k.nit, k.nfev, k.status, o.x,
-                          o.costs4, o.costs4_last, o.nit, o.nfev, o.status, st.dev(oat), st.dev(ont), st.dev(oso), st.dev(ofl),
-                          st.dev(onl), st.dev(obs));
-  if (rc) return rc;
-  return st.download();
-}
-
-// ---- adaptive waypoint counts and the plan chain over groups of one count (expert_planner.py:86-88; kernels:
-// neo_adaptive.hpp)
-static int adaptive_list_check(neo_ctx *c, const char *who, int B, const int32_t *subset, int n_subset) {
-  return list_check(c, who, B, 1, INT32_MAX, subset, n_subset);
-}
-
-static int adaptive_count_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, int D, const double *head,
-                                const double *tail, double seg_len, int max_waypoints, const int32_t *counts,
-                                const int32_t *clamped) {
-  int rc = adaptive_list_check(c, "adaptive count", B, subset, n_subset);
-  if (rc) return rc;
-  if (D < 2 || D > NEO_MAX_DIM) return fail_locked(c, NEO_ERR_INVALID, "adaptive count: D must be 2 or 3");
-  if (max_waypoints < 1 || max_waypoints > NEO_MAX_PIECES - 1)
-    return fail_locked(c, NEO_ERR_INVALID, "adaptive count: max_waypoints must be in 1 .. NEO_MAX_PIECES - 1");
-  if (!std::isfinite(seg_len) || !(seg_len > 0.0))
-    return fail_locked(c, NEO_ERR_INVALID, "adaptive count: seg_len must be finite and > 0");
-  if (!head || !tail || !counts || !clamped) return fail_locked(c, NEO_ERR_INVALID, "adaptive count: null buffer");
-  return NEO_OK;
-}
-
-int neo_adaptive_count_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int D, const double *head,
-                           const double *tail, double seg_len, int max_waypoints, int32_t *counts, int32_t *clamped) {
-  int rc = adaptive_count_check(c, B, subset, n_subset, D, head, tail, seg_len, max_waypoints, counts, clamped);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) return NEO_OK;
-  return launched(c, adaptive_count(c, list, D, head, tail, seg_len, max_waypoints, counts, clamped));
-}
-
-int neo_adaptive_count(neo_ctx *c, int B, const int32_t *subset, int n_subset, int D, const double *head,
-                       const double *tail, double seg_len, int max_waypoints, int32_t *counts, int32_t *clamped) {
-  int rc = adaptive_count_check(c, B, subset, n_subset, D, head, tail, seg_len, max_waypoints, counts, clamped);
-  if (rc) return rc;
-  const size_t bs = (size_t)B, hd = (size_t)3 * D;
-  if (launch_list(B, subset, n_subset).n == 0) return NEO_OK;
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  // the results go up too: the rows of requests not launched come back as they were
-  HostStage st(c, kStagedUpTo);
-  const auto fh = st.in(head, bs * hd), ft = st.in(tail, bs * hd);
-  const auto fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto oc = st.inout(counts, bs), ocl = st.inout(clamped, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_adaptive_count_dev(c, B, st.dev(fsub), n_subset, D, st.dev(fh), st.dev(ft), seg_len, max_waypoints, st.dev(oc),
-                              st.dev(ocl));
-  if (rc) return rc;
-  return st.download();
-}
-
-static int adaptive_bucket_check(neo_ctx *c, int B, const int32_t *subset, int n_subset, const int32_t *counts,
-                                 const int32_t *order, const int32_t *bucket_begin, const int32_t *total) {
-  int rc = adaptive_list_check(c, "adaptive bucket", B, subset, n_subset);
-  if (rc) return rc;
-  if (!counts || !order || !bucket_begin || !total) return fail_locked(c, NEO_ERR_INVALID, "adaptive bucket: null buffer");
-  if (subset && order == subset) return fail_locked(c, NEO_ERR_INVALID, "adaptive bucket: order must not be the subset");
-  return NEO_OK;
-}
-
-int neo_adaptive_bucket_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, const int32_t *counts, int32_t *order,
-                            int32_t *bucket_begin, int32_t *total) {
-  int rc = adaptive_bucket_check(c, B, subset, n_subset, counts, order, bucket_begin, total);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  const LaunchList list = launch_list(B, subset, n_subset);
-  if (list.n == 0) {
-    HIPCHK(c, hipMemsetAsync(bucket_begin, 0, (NEO_MAX_PIECES + 1) * sizeof(int32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(total, 0, sizeof(int32_t), c->stream));
-    return NEO_OK;
-  }
-  return launched(c, adaptive_bucket(c, list, counts, order, bucket_begin, total));
-}
-
-int neo_adaptive_bucket(neo_ctx *c, int B, const int32_t *subset, int n_subset, const int32_t *counts, int32_t *order,
-                        int32_t *bucket_begin, int32_t *total) {
-  int rc = adaptive_bucket_check(c, B, subset, n_subset, counts, order, bucket_begin, total);
-  if (rc) return rc;
-  const size_t bs = (size_t)B, P = (size_t)launch_list(B, subset, n_subset).n;
-  if (P == 0) {
-    std::memset(bucket_begin, 0, (NEO_MAX_PIECES + 1) * sizeof(int32_t));
-    *total = 0;
-    return NEO_OK;
-  }
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  // the order goes up too: its entries from total on come back as they were
-  HostStage st(c, kStagedUpTo);
-  const auto fc = st.in(counts, bs);
-  const auto fsub = st.in_optional(subset, (size_t)n_subset);
-  const auto oo = st.inout(order, P);
-  const auto ob = st.out(bucket_begin, (size_t)NEO_MAX_PIECES + 1), ot = st.out(total, 1);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_adaptive_bucket_dev(c, B, st.dev(fsub), n_subset, st.dev(fc), st.dev(oo), st.dev(ob), st.dev(ot));
-  if (rc) return rc;
-  return st.download();
-}
-
-int neo_adaptive_merge_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, int M, int D, int x_stride, int reset,
-                           int clear_bad, const double *x_k, const double *costs4_k, const double *costs4_last_k,
-                           const int32_t *nit_k, const int32_t *nfev_k, const int32_t *status_k, double *x, double *costs4,
-                           double *costs4_last, int32_t *nit, int32_t *nfev, int32_t *status, int32_t *attempts,
-                           int64_t *nit_total, int32_t *solved, int32_t *pending, int32_t *bad_scene) {
-  if (int rc = adaptive_list_check(c, "adaptive merge", B, subset, n_subset)) return rc;
-  PlanMergeArgs a = plan_merge_args(M, D, reset, x_k, costs4_k, costs4_last_k, nit_k, nfev_k, status_k, x, costs4, costs4_last,
-                                    nit, nfev, status, attempts, nit_total, solved, pending, nullptr, bad_scene);
-  a.ldx = x_stride;
-  return plan_merge_dev(c, "adaptive merge", B, subset, n_subset, M, D, a, false, clear_bad != 0);
-}
-
-static int adaptive_compact_check(neo_ctx *c, const int32_t *seg_begin, const int32_t *seg_len, long long rows,
-                                  const int32_t *pending, const int32_t *n_failed) {
-  if (!c) return NEO_ERR_INVALID;
-  if (!seg_begin || !seg_len || !pending || !n_failed) return fail_locked(c, NEO_ERR_INVALID, "adaptive compact: null buffer");
-  for (int g = 0; g < NEO_MAX_PIECES; ++g)
-    if (seg_begin[g] < 0 || seg_len[g] < 0 || (rows >= 0 && (long long)seg_begin[g] + seg_len[g] > rows))
-      return fail_locked(c, NEO_ERR_INVALID, "adaptive compact: a segment is negative or ends beyond pending");
-  return NEO_OK;
-}
-
-int neo_adaptive_compact_dev(neo_ctx *c, const int32_t *seg_begin, const int32_t *seg_len, int32_t *pending,
-                             int32_t *n_failed) {
-  int rc = adaptive_compact_check(c, seg_begin, seg_len, -1, pending, n_failed);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  hipSetDevice(c->device);
-  return launched(c, adaptive_compact(c, seg_begin, seg_len, pending, n_failed));
-}
-
-int neo_adaptive_compact(neo_ctx *c, const int32_t *seg_begin, const int32_t *seg_len, int rows, int32_t *pending,
-                         int32_t *n_failed) {
-  if (c && rows < 0) return fail_locked(c, NEO_ERR_INVALID, "adaptive compact: rows must be >= 0");
-  int rc = adaptive_compact_check(c, seg_begin, seg_len, rows, pending, n_failed);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
-  hipSetDevice(c->device);
-  HostStage st(c, kStagedUpTo);
-  const auto fp = st.inout(pending, (size_t)rows);
-  const auto on = st.out(n_failed, (size_t)NEO_MAX_PIECES);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_adaptive_compact_dev(c, seg_begin, seg_len, st.dev(fp), st.dev(on));
-  if (rc) return rc;
-  return st.download();
+  return st.run([&] {
+    return neo_audit_traj_batch_dev(c, scenes.scene(scene_id), scenes.slots(st), B, M, D, st.dev(fx), st.dev(fh), st.dev(ft),
+                                    hz, weights3, st.dev(fa), st.dev(fcnt), st.dev(ffl));
+  });
 }
 
 // ---- geo warm start (traj_planner/astar_planner.py, geo_planner.py:19-101; kernels: neo_geo.hpp)
@@ -2348,9 +939,7 @@ static int geo_check(neo_ctx *c, int B, const double *start, const double *targe
   if (B < 1) return fail_locked(c, NEO_ERR_INVALID, "geo: B must be >= 1");
   if (max_expansions < 0 || path_cap < 0 || (path && path_cap < 1))
     return fail_locked(c, NEO_ERR_INVALID, "geo: max_expansions and path_cap must be >= 0 (path_cap >= 1 with a path)");
-  if (!start || !target || !key_pts || !path_len || !path_cost || !expansions || !flags)
-    return fail_locked(c, NEO_ERR_INVALID, "geo: null buffer");
-  return NEO_OK;
+  return null_check(c, "geo: null buffer", {start, target, key_pts, path_len, path_cost, expansions, flags});
 }
 
 // the reference scene of a call: it must exist and be 2-D (the reference's A* is 2-D only)
@@ -2387,28 +976,26 @@ int neo_geo_search_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int
   rc = rebuild_tables(c);
   if (rc) return rc;
   const size_t bs = (size_t)B, pc = path ? (size_t)path_cap : 0;
-  std::vector<int> slots;
-  rc = scene_ids ? scene_slots(c, scene_ids, bs, true, slots) : geo_scene_kind(c, scene_id);
+  SceneList scenes(scene_ids);
+  rc = scene_ids ? scenes.resolve(c, bs, true) : geo_scene_kind(c, scene_id);
   if (rc) return rc;
   HostStage st(c, 0);
   const auto fs = st.in(start, 2 * bs), ft = st.in(target, 2 * bs);
-  const auto fsl = st.in(scene_ids ? slots.data() : nullptr, bs);
+  scenes.stage(st, bs);
   const auto fk = st.out(key_pts, 8 * bs), fc = st.out(path_cost, bs), fp = st.out(path, 2 * bs * pc);
   const auto fl = st.out(path_len, bs), fe = st.out(expansions, bs), ff = st.out(flags, bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = neo_geo_search_batch_dev(c, scene_ids ? scene_ids[0] : scene_id, scene_ids ? st.dev(fsl) : nullptr, B, st.dev(fs),
-                                st.dev(ft), max_expansions, path_cap, st.dev(fk), path ? st.dev(fp) : nullptr, st.dev(fl),
-                                st.dev(fc), st.dev(fe), st.dev(ff));
-  if (rc) return rc;
-  return st.download();
+  return st.run([&] {
+    return neo_geo_search_batch_dev(c, scenes.scene(scene_id), scenes.slots(st), B, st.dev(fs), st.dev(ft), max_expansions,
+                                    path_cap, st.dev(fk), path ? st.dev(fp) : nullptr, st.dev(fl), st.dev(fc), st.dev(fe),
+                                    st.dev(ff));
+  });
 }
 
 int neo_geo_prune_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const double *paths,
                         const int32_t *path_len, int path_stride, double *key_pts) {
   if (!c) return NEO_ERR_INVALID;
   if (B < 1 || path_stride < 1) return fail_locked(c, NEO_ERR_INVALID, "geo prune: B and path_stride must be >= 1");
-  if (!paths || !path_len || !key_pts) return fail_locked(c, NEO_ERR_INVALID, "geo prune: null buffer");
+  if (int rc = null_check(c, "geo prune: null buffer", {paths, path_len, key_pts})) return rc;
   for (int i = 0; i < B; ++i)
     if (path_len[i] < 1 || path_len[i] > path_stride)
       return fail_locked(c, NEO_ERR_INVALID, "geo prune: path_len must be in [1, path_stride]");
@@ -2417,19 +1004,17 @@ int neo_geo_prune_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int 
   int rc = rebuild_tables(c);
   if (rc) return rc;
   const size_t bs = (size_t)B, ps = (size_t)path_stride;
-  std::vector<int> slots;
-  rc = scene_ids ? scene_slots(c, scene_ids, bs, true, slots) : geo_scene_kind(c, scene_id);
+  SceneList scenes(scene_ids);
+  rc = scene_ids ? scenes.resolve(c, bs, true) : geo_scene_kind(c, scene_id);
   if (rc) return rc;
   HostStage st(c, 0);
   const auto fp = st.in(paths, 2 * bs * ps);
-  const auto fl = st.in(path_len, bs), fsl = st.in(scene_ids ? slots.data() : nullptr, bs);
+  const auto fl = st.in(path_len, bs);
+  scenes.stage(st, bs);
   const auto fk = st.out(key_pts, 8 * bs);
-  rc = st.upload();
-  if (rc) return rc;
-  rc = geo_prune(c, scene_ids ? scene_ids[0] : scene_id, B, scene_ids ? st.dev(fsl) : nullptr, st.dev(fp), st.dev(fl),
-                 path_stride, st.dev(fk));
-  if (rc) return rc;
-  return st.download();
+  return st.run([&] {
+    return geo_prune(c, scenes.scene(scene_id), B, scenes.slots(st), st.dev(fp), st.dev(fl), path_stride, st.dev(fk));
+  });
 }
 
 int neo_geo_workspace_budget(neo_ctx *c, size_t bytes) {
@@ -2529,7 +1114,7 @@ __global__ void pack_results_kernel(int B, int n, const double *__restrict__ x, 
 
 int neo_pack_results_dev(neo_ctx *c, int B, int n, const double *x, const double *costs4, const double *weights4, float *out) {
   if (!c || B < 0 || n < 1) return NEO_ERR_INVALID;
-  if (!x || !costs4 || !weights4 || !out) return fail_locked(c, NEO_ERR_INVALID, "null buffer");
+  if (int rc = null_check(c, "null buffer", {x, costs4, weights4, out})) return rc;
   if (B == 0) return NEO_OK;
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
@@ -2587,7 +1172,7 @@ int neo_effort_order_dev(neo_ctx *c, int B, int M, int D, const double *x0, cons
                          int32_t *order) {
   int rc = check_shape(c, B, M, D);
   if (rc) return rc;
-  if (!x0 || !head || !tail || !scratch || !order) return fail_locked(c, NEO_ERR_INVALID, "null buffer");
+  if ((rc = null_check(c, "null buffer", {x0, head, tail, scratch, order}))) return rc;
   if (((uintptr_t)scratch) & 255) return fail_locked(c, NEO_ERR_INVALID, "scratch must be 256-byte aligned");
   if (B == 0) return NEO_OK;
   std::lock_guard<std::recursive_mutex> g(c->mu);

@@ -1,6 +1,6 @@
 // neo_disp_onboard.hip -- onboard mapping (neo_onboard.hpp): one launch of the integration kernel per
 // neo_onboard_integrate_batch_dev call, on the context's stream; every pointer is a device array, the arguments were
-// checked by the C ABI (neo_abi.hip), which also sized the window.
+// checked by the C ABI (neo_abi_fleet.hip), which also sized the window.
 #include "neo_host.hpp"
 #include "neo_onboard.hpp"
 

@@ -1,6 +1,7 @@
 """Builds libneo_planner_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-The library is several translation units -- the C ABI plus one unit per kernel family (neo_disp_*.hip) -- compiled
+The library is several translation units -- the C ABI in three (neo_abi.hip, neo_abi_fleet.hip, neo_abi_plan.hip, which
+share neo_abi_util.hpp and nobody else sees it) plus one unit per kernel family (neo_disp_*.hip) -- compiled
 in parallel and linked into one shared object.  Objects are cached under csrc/build/ by CONTENT: an object's name carries a
 hash of its command line, its source and every header; the library's stamp file the hash of all of them.  Time stamps
 play no part (a checkout that restores a file, or a copy of the tree that does not keep them, rebuilds nothing)."""
@@ -20,7 +21,9 @@ SOURCES = ["neo_abi.hip", "neo_disp_eval.hip", "neo_disp_sample.hip", "neo_disp_
            "neo_disp_opt3d_f64.hip", "neo_disp_opt3d_w2.hip", "neo_disp_opt3d_x.hip", "neo_disp_group.hip", "neo_disp_opt3d_b.hip",
            "neo_disp_audit.hip", "neo_disp_geo.hip", "neo_disp_fleet.hip", "neo_disp_batch.hip", "neo_disp_esdf.hip",
            "neo_disp_plan.hip", "neo_disp_depth.hip", "neo_disp_onboard.hip", "neo_disp_record.hip", "neo_disp_init.hip",
-           "neo_disp_adaptive.hip"]
+           "neo_disp_adaptive.hip",
+           # (the kernel-less units of the C ABI last: the units with device code keep their places in the link)
+           "neo_abi_fleet.hip", "neo_abi_plan.hip"]
 HEADERS = ["neo_wave.hpp", "neo_device.hpp", "neo_kernels.hpp", "neo_host.hpp", "neo_launch_list.hpp", "neo_launch_opt.hpp", "neo_lbfgs.hpp",
            "neo_linesearch.hpp", "neo_lbfgs_sm.hpp", "neo_lbfgs_dir.hpp", "neo_group_kernel.hpp",
            # (the counter-based jitter, included by the plan and the fleet unit; small enough to sit with the shared ones)
@@ -58,8 +61,9 @@ def _flags():
         os.environ.get("NEO_BUILD_DEFS", "").split()
 
 
-# headers only one unit includes: a change there recompiles that unit alone
-UNIT_HEADERS = {"neo_disp_audit.hip": ["neo_audit.hpp"], "neo_disp_geo.hip": ["neo_geo.hpp"],
+# headers only one unit (or the three of the C ABI) includes: a change there recompiles those alone
+UNIT_HEADERS = {"neo_abi.hip": ["neo_abi_util.hpp"], "neo_abi_fleet.hip": ["neo_abi_util.hpp"], "neo_abi_plan.hip": ["neo_abi_util.hpp"],
+                "neo_disp_audit.hip": ["neo_audit.hpp"], "neo_disp_geo.hip": ["neo_geo.hpp"],
                 "neo_disp_fleet.hip": ["neo_fleet.hpp", "neo_audit.hpp", "neo_track.hpp"], "neo_disp_batch.hip": ["neo_batch.hpp"],
                 "neo_disp_esdf.hip": ["neo_esdf.hpp"], "neo_disp_plan.hip": ["neo_plan.hpp"],
                 "neo_disp_depth.hip": ["neo_depth.hpp"], "neo_disp_onboard.hip": ["neo_onboard.hpp"],
