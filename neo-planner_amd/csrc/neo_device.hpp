@@ -1479,6 +1479,8 @@ __device__ __forceinline__ void sample_accumulate(const Real (&c)[6][D], int j, 
 
 // floats per piece of the accumulator fold (minco_sample, fold_acc)
 __host__ __device__ constexpr int fold_acc_stride(int D) { return (6 * D + 1 + 3) / 4 * 4; }
+// bytes of staging the gather-ahead sample loop keeps two rounds of velocity in (minco_sample: [2][D][kWave] floats)
+__host__ __device__ constexpr int velocity_stash_bytes(int D) { return 2 * D * kWave * (int)sizeof(float); }
 
 // sampled feasibility + collision terms (:392-466), SAMPLE layout.
 // SAMPLE_IO = false (fused kernels): in (PIECE layout) cp = coefficients of the lane's piece, ns_in = its sample
@@ -1541,34 +1543,46 @@ __device__ __forceinline__ void minco_sample(int M, const SampleLanes &sl, int n
   NEO_MARK("loop_begin");
   // A plan with `gather_ahead` (one sample per lane in flight, fused fp32 kernels): the gathers of round i + 1 are issued
   // before round i is consumed, so a round's memory latency runs under the arithmetic of the round before it instead of
-  // in series with it.  Between issue and use only the eight corners, the three fractions and the inside mask are
-  // held; the sample index, its time and the velocity are formed again from the round counter when the round is
-  // consumed -- the same expressions on the same inputs, rounds and lanes in the same order: the same bits as the loop
-  // below.  In a round ahead, lanes whose piece has run out of samples park on cell 0 (prepare with on = false).  The
-  // last round is consumed after the loop with nothing in flight.
+  // in series with it.  Between issue and use the registers hold only the eight corners, the three fractions and the
+  // inside mask.  The velocity comes out of the same Horner chain as the position the addresses are formed from, so it is
+  // formed ONCE, with them, and waits for its round in LDS: the staging buffer is idle for the whole loop (the lane
+  // assignment has handed it back, the fold writes it after the loop), and holds two rounds of velocity as
+  // [it & 1][d][lane] floats (velocity_stash_bytes: the launcher sizes the staging for it, neo_launch_opt.hpp).  Every
+  // lane reads back its own slot a whole round after it wrote it, and round it + 2 overwrites a half only after round it
+  // has read it.  The sample index and its time are formed again from the round counter where they are used -- the same
+  // expressions on the same inputs, rounds and lanes in the same order: the same bits as the loop below.  In a round
+  // ahead, lanes whose piece has run out of samples park on cell 0 (prepare with on = false).  The last round is
+  // consumed after the loop with nothing in flight.
   constexpr bool kAhead = !Plan::dynamic && Plan::gather_ahead && LookupT::gather_ahead && U == 1 && !SAMPLE_IO && sizeof(Real) == 4;
   if constexpr (kAhead) {
-    auto ahead = [&](int it) {  // addresses of round `it`
+    Real *const stash = fold_rows + lane_id();
+    auto ahead = [&](int it) {  // addresses of round `it`; its velocity to the stash
       const int j = r + it * L;
       const Real s = (Real)((double)j * prm.delta_t);
-      Real pos[D], vdrop[D];
-      piece_pos_vel<Real, D>(c, s, pos, vdrop);
+      Real pos[D], vel[D];
+      piece_pos_vel<Real, D>(c, s, pos, vel);
+#pragma unroll
+      for (int d = 0; d < D; ++d) stash[((it & 1) * D + d) * kWave] = vel[d];
       return lk.template prepare<D>(pos, j < ns);
     };
     auto consume = [&](int it, const typename LookupT::Addr &ad, const typename LookupT::Raw &rw) {
       const int j = r + it * L;
       const bool on = j < ns;
-      const Real s = (Real)((double)j * prm.delta_t);  // beta_full row j: t = j * delta_t (:251)
-      Real pos[D], vel[D];
-      piece_pos_vel<Real, D>(c, s, pos, vel);
+      // (read first: the trilinear interpolation runs under the LDS latency)
+      Real vel[D];
+#pragma unroll
+      for (int d = 0; d < D; ++d) vel[d] = stash[((it & 1) * D + d) * kWave];
+      Real gdrop[D];
+      const Real vd = safe - lk.template finish<D>(ad, rw, gdrop);
       Real v2 = Real(0);
 #pragma unroll
       for (int d = 0; d < D; ++d) v2 += vel[d] * vel[d];
       const Real vv = v2 - vmax2;
-      Real gdrop[D];
-      const Real vd = safe - lk.template finish<D>(ad, rw, gdrop);
       const bool any_violation = on && (vv > Real(0) || vd > Real(0));
-      if (any_violation) sample_accumulate<Real, D, LookupT>(c, j, ns, s, inv_ns, vel, vv, vd, lk, ad, rw, dt, w2, w3, aC, aT, aF, aK);
+      if (any_violation) {
+        const Real s = (Real)((double)j * prm.delta_t);  // beta_full row j: t = j * delta_t (:251)
+        sample_accumulate<Real, D, LookupT>(c, j, ns, s, inv_ns, vel, vv, vd, lk, ad, rw, dt, w2, w3, aC, aT, aF, aK);
+      }
     };
     if (iters > 0) {
       typename LookupT::Addr ad = ahead(0);

@@ -99,7 +99,8 @@ struct DevBackend {
   const DevParams &prm;
   const MapT &map;
   double *xs;    // LDS [kStage]: FLAT <-> PIECE staging; between scatter_x and the gradient gather the same memory
-                 // holds the lane assignment's segment table and the rows of the per-piece fold (minco_sample)
+                 // holds the lane assignment's segment table, the gather-ahead loop's velocity stash and the rows or
+                 // accumulators of the per-piece fold, one after the other (minco_sample)
   static constexpr int kStage = stage_doubles<D, NS, Real>();
   // LDS [kSlCacheInts] or nullptr: the lane assignment of the last evaluation (a key byte and a word a lane + three wave-uniform ints).
   // The assignment depends on the pieces' sample counts int(T / delta_t) alone, and along a run 58 % of consecutive
@@ -788,6 +789,14 @@ __device__ __forceinline__ void optimize_body(int B, int M, const DevParams &prm
 // included, has the dynamic plan in optimize_kernel itself.
 template <int NS, class LG, typename Num, bool BUDGET>
 using opt_plan_t = std::conditional_t<sizeof(Num) == 4 && (LG::S > 1) && NS <= 2 && !BUDGET, PlanFixedX, PlanDynamic>;
+
+// optimize_kernel<...>'s sample loop is the gather-ahead form, which keeps two rounds of velocity in the staging buffer
+// (velocity_stash_bytes: the launcher makes the room and sends a launch without it to optimize_dyn_kernel)
+template <int D, int NS, typename Real, class MapT, class LookupT, int WAVES, class LG, typename Num, bool BUDGET>
+constexpr bool opt_gather_ahead() {
+  return DevBackend<D, NS, Real, MapT, LookupT, (WAVES == 2 ? NEO_W2_U : NEO_FUSED_U), LG, false, Num,
+                    opt_plan_t<NS, LG, Num, BUDGET>>::kAhead;
+}
 
 #define NEO_OPT_LAUNCH_BOUNDS __launch_bounds__(kWave, (WAVES == 2 ? (sizeof(Num) == 4 && NS <= 2 ? NEO_X_OCC : NEO_W2_OCC) : 1))
 

@@ -12,8 +12,10 @@ struct OptLds {
   size_t dyn;  // bytes
 };
 
+// stash: bytes of the staging the sample loop itself uses, beside the fold and the exchange table (the gather-ahead form's
+// two rounds of velocity, velocity_stash_bytes; 0: none)
 template <int D, int NS, typename Real, int WAVES, class LG, typename Num>
-OptLds opt_lds_plan(int M, int flags) {
+OptLds opt_lds_plan(int M, int flags, int stash = 0) {
   const size_t pair_elems = (size_t)2 * NEO_LBFGS_M * (D * (M - 1) + M);  // L-BFGS pairs in LDS
   // staging in front of the pairs: the full size (with the rows of the per-piece fold) unless that costs the two-waves
   // variant occupancy -- eight wavefronts per CU want 160 KB / 8 each, less ~0.5 KB of static LDS.  The one-wave
@@ -34,7 +36,9 @@ OptLds opt_lds_plan(int M, int flags) {
   if (sizeof(Num) == 4 && LG::S > 1 && !(flags & 4096)) {
     // all-fp32, lane = (piece, dimension): room for the reduction's multipliers next to the pairs when the fold runs on
     // per-piece accumulators (80 B a piece at D = 3) instead of rows (96 B a lane); flags bit 4096: off (comparison runs)
-    const int acc = std::max(std::max(small, (M * fold_acc_stride(D) * 4 + 7) / 8), (pcr_xch_elems(M, 1) * 4 + 7) / 8);
+    // (the stash is the largest of the four below M = 20 at D = 3: there the pairs behind it shrink faster than it grows)
+    const int acc = std::max(std::max(std::max(small, (M * fold_acc_stride(D) * 4 + 7) / 8), (pcr_xch_elems(M, 1) * 4 + 7) / 8),
+                             (stash + 7) / 8);
     const size_t off = ((size_t)acc * 8 + pairs + 15) / 16 * 2;
     const size_t need = off * 8 + (size_t)pcr_mult_elems(M) * sizeof(float);
     if (need <= lds_share) {
@@ -52,16 +56,19 @@ int launch_opt_kernel(neo_ctx *c, const OptArgs &a) {
   // (a budgeted launch may cover a subset of the batch: workgroup i then works on trajectory subset[i])
   const int n_launch = a.subset ? a.n_subset : a.B;
   const int *launch_order = a.subset ? a.subset : (c->order_B == a.B ? c->dispatch_order : nullptr);
-  const OptLds l = opt_lds_plan<D, NS, Real, WAVES, LG, Num>(a.M, c->params.flags);
+  // (the gather-ahead sample loop keeps two rounds of velocity in the staging buffer, in front of the L-BFGS pairs)
+  constexpr int stash = opt_gather_ahead<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>() ? velocity_stash_bytes(D) : 0;
+  const OptLds l = opt_lds_plan<D, NS, Real, WAVES, LG, Num>(a.M, c->params.flags, stash);
   // optimize_kernel is compiled for ONE plan (neo_kernels.hpp opt_plan_t).  Where that is a fixed plan, it runs only the
   // launches whose plan -- decided here, on the host -- is that one: accumulator fold and multipliers in LDS (pcr_off), the
-  // exchange table within the staging buffer, no trace buffer.  Everything else (flags bit 4096, traces, an M whose
-  // multipliers do not fit) goes to optimize_dyn_kernel, which tests the selectors at run time.  The kernel checks nothing.
+  // exchange table and the velocity stash within the staging buffer, no trace buffer.  Everything else (flags bit 4096,
+  // traces, an M whose multipliers do not fit) goes to optimize_dyn_kernel, which tests the selectors at run time.  The
+  // kernel checks nothing.
   using Plan = opt_plan_t<NS, LG, Num, BUDGET>;
   bool fixed = !Plan::dynamic;
   if constexpr (!Plan::dynamic)
-    fixed = l.pcr_off != 0 && pcr_xch_elems(a.M, LG::dl(D)) * (int)sizeof(Num) <= l.stage * 8 && !c->trace && !c->trace_xg &&
-            !(c->params.flags & 4096);
+    fixed = l.pcr_off != 0 && pcr_xch_elems(a.M, LG::dl(D)) * (int)sizeof(Num) <= l.stage * 8 && stash <= l.stage * 8 &&
+            !c->trace && !c->trace_xg && !(c->params.flags & 4096);
   auto kernel = optimize_kernel<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>;
   if constexpr (!Plan::dynamic)  // (only the members with a fixed plan have the second form)
     if (!fixed) kernel = optimize_dyn_kernel<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>;
