@@ -70,6 +70,13 @@ retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream
 from the counter-based streams of counter_rng.py / csrc/neo_counter_rng.hpp instead -- a value is a pure function of
 (seed, mission id, tick, target) or (plan_seed, mission id, attempt) -- drawn on the device: neo_fleet_jitter_dev in front
 of the target kernel, neo_plan_jitter_dev inside plan_dev.  The property is the same, the flights are other flights.
+
+Two streams, one rule.  torch works on its own stream, the context launches on another, and nothing orders the two but
+the host.  Every stage of the loop therefore goes: torch work (uploads, gathers, scatters), then `_torch_done`, then the
+context's launches, then `_ctx_done`, then torch or host reads of what they wrote.  A launch may only read a tensor torch
+wrote before the last `_torch_done`; torch and the host may only read what the context wrote before the last `_ctx_done`.
+(Launches whose results only later launches read need no `_ctx_done` of their own: the context's stream orders them.)
+The planners' and cameras' own methods (plan_dev, render_dev, OnboardMapper.update ...) follow the same rule inside.
 """
 import time
 
@@ -101,6 +108,102 @@ def plan_seed(seed, tick, target):
     """the seed BatchPlanner.plan gets for the plans of (tick, target): its retries then draw from
     SeedSequence(plan_seed, mission id, attempt)"""
     return int(np.random.SeedSequence([int(seed), int(tick), int(target)]).generate_state(1, np.uint64)[0] >> np.uint64(2))
+
+
+def _check_arguments(batch_planner, goals, mode, seed, scene_ids, mission_ids, resident, onboard, scenes, scene_index,
+                     record, neo, jitter, goal_routes, track_radius, metric_weights):
+    """FleetReplanLoop's refusals, in the order its callers meet them; returns the arguments it had to bring into shape
+    on the way, by name"""
+    counter = counter_rng.check_jitter(jitter, "FleetReplanLoop")
+    if mode not in ("basic", "geo", "batch", "neo", "nn", "warmstart"):
+        raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo', 'batch', 'neo', 'nn' or 'warmstart'")
+    if goal_routes is not None:
+        if not isinstance(goal_routes, GoalRoutes):
+            raise ValueError("FleetReplanLoop: goal_routes must be a GoalRoutes")
+        if mode == "geo":
+            raise ValueError("FleetReplanLoop: goal routes need a mode other than 'geo' (the tracker node has no geo planner)")
+        if goals is not None and _lib.as_f64(goals).reshape(-1, 2).shape[0] != goal_routes.B:
+            raise ValueError("FleetReplanLoop: one goal route per mission")
+        goals = goal_routes.at(0.0)      # where the goals start
+    elif goals is None:
+        raise ValueError("FleetReplanLoop: goals may be None only with goal_routes")
+    track_radius = float(track_radius)
+    if not (np.isfinite(track_radius) and track_radius >= 0.0):
+        raise ValueError("FleetReplanLoop: track_radius must be finite and >= 0")
+    if metric_weights is None:      # the audit's default for a fixed goal, the tracker node's (1, 1, 1) (:175) with routes
+        metric_weights = None if goal_routes is None else np.ones(3)
+    else:
+        metric_weights = _lib.as_f64(metric_weights).reshape(-1)
+        if metric_weights.shape[0] != 3 or not np.all(np.isfinite(metric_weights)):
+            raise ValueError("FleetReplanLoop: metric_weights must be three finite numbers")
+    learned = mode in ("neo", "nn")
+    if learned:
+        if neo is None:
+            raise ValueError("FleetReplanLoop: modes 'neo' and 'nn' need neo=BatchNeoPlanner")
+        if neo.bp is not batch_planner:
+            raise ValueError("FleetReplanLoop: neo's planner must be the loop's batch_planner")
+        if int(batch_planner.cfg.init_wpts_num) != 2:
+            raise ValueError("FleetReplanLoop: the network plans M = 3 pieces: modes 'neo' and 'nn' need init_wpts_num = 2")
+        net, cam = neo.init.net, neo.camera
+        if (cam.height, cam.width) != (net.img_height, net.img_width):
+            raise ValueError("FleetReplanLoop: neo's camera renders %d x %d, its network takes %d x %d"
+                             % (cam.height, cam.width, net.img_height, net.img_width))
+        if scenes is None:
+            raise ValueError("FleetReplanLoop: modes 'neo' and 'nn' need scenes=(boxes, box_begin), what the cameras see")
+    # the network's guess and the carried plan live on the device: resident plans always
+    resident = bool(resident) or learned or mode == "warmstart"
+    if resident and mode == "geo":
+        raise ValueError("FleetReplanLoop: resident=True needs mode 'basic' or 'batch' (geo_plan has no resident form)")
+    if onboard is not None and mode == "geo":
+        raise ValueError("FleetReplanLoop: onboard maps need mode 'basic' or 'batch' (geo on onboard maps is not built)")
+    if (onboard is not None or record is not None) and scenes is None:
+        raise ValueError("FleetReplanLoop: onboard and record need scenes=(boxes, box_begin), what the cameras see")
+    goals = _lib.as_f64(goals).reshape(-1, 2)
+    B = goals.shape[0]
+    seed = int(seed)
+    scene_index = None if scene_index is None else np.ascontiguousarray(scene_index, dtype=np.int32).reshape(-1)
+    scene_ids = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32).reshape(-1)
+    mission_ids = np.arange(B) if mission_ids is None else np.asarray(mission_ids).reshape(-1)
+    if mission_ids.shape[0] != B or (scene_ids is not None and scene_ids.shape[0] != B):
+        raise ValueError("FleetReplanLoop: one mission id and one scene id per goal")
+    if counter:
+        counter_rng.check_seed(seed, "FleetReplanLoop")
+        counter_rng.check_ids(mission_ids, "FleetReplanLoop")
+    if onboard is not None and onboard.B != B:
+        raise ValueError("FleetReplanLoop: the onboard mapper must have one entry per goal")
+    if (onboard is not None or record is not None or learned) and scene_index is not None and scene_index.shape[0] != B:
+        raise ValueError("FleetReplanLoop: scene_index must have one entry per goal")
+    if record is not None and record.M != int(batch_planner.cfg.init_wpts_num) + 1:
+        raise ValueError("FleetReplanLoop: the recorder's M must be the planner's init_wpts_num + 1")
+    if record is not None and record.ctx is not batch_planner.ctx:
+        raise ValueError("FleetReplanLoop: the recorder and the planner must share one context")
+    return dict(counter=counter, goals=goals, track_radius=track_radius, metric_weights=metric_weights, resident=resident,
+                seed=seed, scene_index=scene_index, scene_ids=scene_ids, mission_ids=mission_ids)
+
+
+class _Timed:
+    """`with _Timed(tm, key):` adds the wall time of the block to tm[key]"""
+    __slots__ = ("tm", "key", "t0")
+
+    def __init__(self, tm, key):
+        self.tm, self.key = tm, key
+
+    def __enter__(self):
+        self.t0 = time.perf_counter()
+
+    def __exit__(self, *exc):
+        self.tm[self.key] = self.tm.get(self.key, 0.0) + time.perf_counter() - self.t0
+
+
+class _Tally:
+    """the per-mission host counters of one run"""
+
+    def __init__(self, B, tracked):
+        self.replans, self.failed, self.opt_runs = (np.zeros(B, np.int32) for _ in range(3))
+        self.iter_num = np.zeros(B, np.int64)
+        self.abandoned = np.zeros(B, bool)
+        self.landed = np.zeros(B, bool)      # near the goal and that plan spliced (:421-427)
+        self.failed_ticks = np.zeros(B, np.int32) if tracked else None
 
 
 class FleetReplanLoop:
@@ -145,60 +248,15 @@ class FleetReplanLoop:
                  scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False, onboard=None, scenes=None,
                  scene_index=None, des_pos_z=2.0, record_poses=False, record=None, neo=None, jitter="numpy",
                  goal_routes=None, track_radius=1.0, metric_weights=None):
-        self.counter = counter_rng.check_jitter(jitter, "FleetReplanLoop")
-        self.jitter = jitter
-        if mode not in ("basic", "geo", "batch", "neo", "nn", "warmstart"):
-            raise ValueError("FleetReplanLoop: mode must be 'basic', 'geo', 'batch', 'neo', 'nn' or 'warmstart'")
-        self.routes = goal_routes
-        if goal_routes is not None:
-            if not isinstance(goal_routes, GoalRoutes):
-                raise ValueError("FleetReplanLoop: goal_routes must be a GoalRoutes")
-            if mode == "geo":
-                raise ValueError("FleetReplanLoop: goal routes need a mode other than 'geo' (the tracker node has no geo planner)")
-            if goals is not None and _lib.as_f64(goals).reshape(-1, 2).shape[0] != goal_routes.B:
-                raise ValueError("FleetReplanLoop: one goal route per mission")
-            goals = goal_routes.at(0.0)      # where the goals start
-        elif goals is None:
-            raise ValueError("FleetReplanLoop: goals may be None only with goal_routes")
-        self.track_radius = float(track_radius)
-        if not (np.isfinite(self.track_radius) and self.track_radius >= 0.0):
-            raise ValueError("FleetReplanLoop: track_radius must be finite and >= 0")
-        if metric_weights is None:      # the audit's default for a fixed goal, the tracker node's (1, 1, 1) (:175) with routes
-            self.metric_weights = None if goal_routes is None else np.ones(3)
-        else:
-            self.metric_weights = _lib.as_f64(metric_weights).reshape(-1)
-            if self.metric_weights.shape[0] != 3 or not np.all(np.isfinite(self.metric_weights)):
-                raise ValueError("FleetReplanLoop: metric_weights must be three finite numbers")
-        learned = mode in ("neo", "nn")
-        if learned:
-            if neo is None:
-                raise ValueError("FleetReplanLoop: modes 'neo' and 'nn' need neo=BatchNeoPlanner")
-            if neo.bp is not batch_planner:
-                raise ValueError("FleetReplanLoop: neo's planner must be the loop's batch_planner")
-            if int(batch_planner.cfg.init_wpts_num) != 2:
-                raise ValueError("FleetReplanLoop: the network plans M = 3 pieces: modes 'neo' and 'nn' need init_wpts_num = 2")
-            net, cam = neo.init.net, neo.camera
-            if (cam.height, cam.width) != (net.img_height, net.img_width):
-                raise ValueError("FleetReplanLoop: neo's camera renders %d x %d, its network takes %d x %d"
-                                 % (cam.height, cam.width, net.img_height, net.img_width))
-            if scenes is None:
-                raise ValueError("FleetReplanLoop: modes 'neo' and 'nn' need scenes=(boxes, box_begin), what the cameras see")
-            resident = True
-        if mode == "warmstart":      # the carried plan lives on the device: resident plans always
-            resident = True
-        if resident and mode == "geo":
-            raise ValueError("FleetReplanLoop: resident=True needs mode 'basic' or 'batch' (geo_plan has no resident form)")
-        if onboard is not None and mode == "geo":
-            raise ValueError("FleetReplanLoop: onboard maps need mode 'basic' or 'batch' (geo on onboard maps is not built)")
-        if (onboard is not None or record is not None) and scenes is None:
-            raise ValueError("FleetReplanLoop: onboard and record need scenes=(boxes, box_begin), what the cameras see")
-        self.resident = bool(resident)
+        a = _check_arguments(batch_planner, goals, mode, seed, scene_ids, mission_ids, resident, onboard, scenes, scene_index,
+                             record, neo, jitter, goal_routes, track_radius, metric_weights)
+        self.counter, self.jitter, self.seed = a["counter"], jitter, a["seed"]
+        self.routes, self.track_radius, self.metric_weights = goal_routes, a["track_radius"], a["metric_weights"]
+        self.bp, self.map, self.mode, self.resident = batch_planner, map, mode, a["resident"]
         self.onboard, self.scenes, self.des_pos_z, self.record_poses = onboard, scenes, float(des_pos_z), bool(record_poses)
         self.record = record
-        self.neo = neo if learned else None
-        self.scene_index = None if scene_index is None else np.ascontiguousarray(scene_index, dtype=np.int32).reshape(-1)
-        self.bp, self.map, self.mode = batch_planner, map, mode
-        self.goals = _lib.as_f64(goals).reshape(-1, 2)
+        self.neo = neo if mode in ("neo", "nn") else None
+        self.goals, self.scene_index, self.scene_ids, self.mission_ids = a["goals"], a["scene_index"], a["scene_ids"], a["mission_ids"]
         self.B = self.goals.shape[0]
         self.cmd_hz = cmd_hz
         self.replan_period, self.planning_time_ahead = replan_period, planning_time_ahead
@@ -207,26 +265,19 @@ class FleetReplanLoop:
         self.move_vel = 0.8 * float(batch_planner.cfg.v_max)                      # :87
         self.cap = int(round(max_cmd_seconds * cmd_hz))
         self.stride = int(round(cmd_hz * metric_eva_interval))                    # rows between two metric samples (:119)
-        self.seed = int(seed)
-        self.scene_ids = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32).reshape(-1)
-        self.mission_ids = np.arange(self.B) if mission_ids is None else np.asarray(mission_ids).reshape(-1)
-        if self.mission_ids.shape[0] != self.B or (self.scene_ids is not None and self.scene_ids.shape[0] != self.B):
-            raise ValueError("FleetReplanLoop: one mission id and one scene id per goal")
-        if self.counter:
-            counter_rng.check_seed(self.seed, "FleetReplanLoop")
-            counter_rng.check_ids(self.mission_ids, "FleetReplanLoop")
-        if onboard is not None and onboard.B != self.B:
-            raise ValueError("FleetReplanLoop: the onboard mapper must have one entry per goal")
-        if (onboard is not None or record is not None or learned) and self.scene_index is not None and \
-                self.scene_index.shape[0] != self.B:
-            raise ValueError("FleetReplanLoop: scene_index must have one entry per goal")
-        if record is not None and record.M != int(batch_planner.cfg.init_wpts_num) + 1:
-            raise ValueError("FleetReplanLoop: the recorder's M must be the planner's init_wpts_num + 1")
-        if record is not None and record.ctx is not batch_planner.ctx:
-            raise ValueError("FleetReplanLoop: the recorder and the planner must share one context")
         # what targets and plans see: the missions' onboard scenes, or the given map(s)
         self.plan_map = map if onboard is None else onboard
         self.plan_scene_ids = self.scene_ids if onboard is None else onboard.scene_ids
+        # The mode's plan step (self, sub, pending, tick, r) -> (ok, nit_total, attempts): the resident x and solved are ready
+        # for the splice when it returns.  (The class's functions, not bound methods: the loop holds the command arrays, and
+        # a reference to itself would leave their release to the cycle collector.)
+        cls = type(self)
+        self._plan_step = {"basic": cls._plan_resident if self.resident else cls._plan_host, "geo": cls._plan_geo,
+                           "batch": cls._plan_batch, "neo": cls._plan_neo, "nn": cls._plan_nn, "warmstart": cls._plan_warm}[mode]
+        self._fallback = cls._fallback_resident if self.resident else cls._fallback_host      # mode "batch"
+        # who looks through the cameras once a tick, in this order: (its timing key, its function)
+        self._viewers = [(key, see) for key, who, see in (("sense_s", onboard, cls._see_onboard), ("neo_s", self.neo, cls._see_neo),
+                                                          ("record_s", record, cls._see_record)) if who is not None]
         self.timings = []
         self._dev = None
         self._batch = None      # mode "batch": BatchPlanner.batch_buffers, made at the first plan
@@ -243,137 +294,97 @@ class FleetReplanLoop:
         import torch
         self._dev[name].copy_(torch.from_numpy(np.ascontiguousarray(host)))
 
-    def _sync(self):
+    # ---- the stream rule (module docstring): torch work, _torch_done, the context's launches, _ctx_done, torch / host reads
+    def _torch_done(self):
+        """what torch has queued is in place: the context, on its own stream, may launch on it"""
         import torch
-        torch.cuda.synchronize(self._device)     # (the context runs on its own stream: torch's copies first, then its launches)
+        torch.cuda.synchronize(self._device)
 
-    def _target(self, sub):
-        c, d, p = self.bp.ctx, self._dev, self._p
-        c.check(c.lib.neo_fleet_target_batch_dev(c.h, self.plan_map.scene_id, p(d["plan_slots"]), self.B, p(sub), int(sub.numel()),
-                                                 p(d["cur_pos"]), p(d["goal"]), p(d["jitter"]), self.longitu_step_dis,
-                                                 self.lateral_step_length, self.move_vel, p(d["tail"]), p(d["near"]),
-                                                 p(d["steps"]), p(d["flags"])))
+    def _ctx_done(self):
+        """what the context has launched is in place: torch and the host may read it"""
+        self.bp.ctx.synchronize()
 
-    def _jitter(self, sub, tick, r):
-        """jitter="counter": the round's target jitter of the missions `sub`, on the context's stream"""
-        c, d, p = self.bp.ctx, self._dev, self._p
-        c.check(c.lib.neo_fleet_jitter_dev(c.h, self.B, p(sub), int(sub.numel()), self.seed, int(tick), int(r),
-                                           p(d["mission_ids"]), p(d["jitter"])))
+    def _call(self, name, *args):
+        """the library's entry point `name` on the loop's context; raises on its error code"""
+        c = self.bp.ctx
+        c.check(getattr(c.lib, name)(c.h, *args))
 
-    def _sense(self, active, tm):
-        """the active missions' poses from where they are, then mapper.update on what their cameras see"""
-        c, d, p = self.bp.ctx, self._dev, self._p
-        t0 = time.perf_counter()
-        sub = self._subset(active)
-        self._sync()
-        c.check(c.lib.neo_fleet_pose_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
-                                         p(d["cmd_index"]), p(d["cur_pos"]), p(d["goal"]), self.des_pos_z, p(d["pose"])))
-        c.synchronize()
-        rebuilt = self.onboard.update(d["boxes"], d["box_begin"], d["pose"], d["scene_index"], subset=active)
-        tm["sense_s"] = time.perf_counter() - t0
-        tm["rebuilt"] = int(len(rebuilt))
-        tm.update({k: self.onboard.last[k] for k in ("render_s", "integrate_s", "rebuild_s")})
-        if self.record_poses:
-            self._poses.append(d["pose"].cpu().numpy())
+    # the argument groups the fleet entry points share
+    def _rows(self, sub):
+        """the missions a launch works on: B, subset, count (None: all B)"""
+        return self.B, self._p(sub), 0 if sub is None else int(sub.numel())
+
+    def _cmd(self):
+        """the resident command arrays: cmd, cap, cmd_len, cmd_index"""
+        return (self._p(self._dev["cmd"]), self.cap) + self._ptrs("cmd_len", "cmd_index")
+
+    def _route_table(self):
+        return (self._p(self._dev["vertices"]), int(self._dev["vertices"].shape[0])) + self._ptrs("route_begin", "speed", "closed")
+
+    def _ptrs(self, *names):
+        """the device pointers of the named resident tensors"""
+        return tuple(self._p(self._dev[k]) for k in names)
+
+    # ---- the camera stage: one pose launch a tick, then whoever looks through the cameras
+    def _camera_stage(self, sub, active, tm):
+        """the active missions' poses from where they are (the eye at (cur_pos, des_pos_z), heading along the last step of
+        the command array), once, then the viewers in their order: the onboard mapper, the network's features, the
+        recorder's images.  The pose launch is charged to the first viewer.  `view` is the gather of the active missions'
+        pose / scene_index rows the network and the recorder share: made once, after a _ctx_done behind the pose launch."""
+        view = None
+        for k, (key, see) in enumerate(self._viewers):
+            with _Timed(tm, key):
+                if k == 0:
+                    self._torch_done()
+                    self._call("neo_fleet_pose_dev", *self._rows(sub), *self._cmd(), *self._ptrs("cur_pos", "goal"),
+                               self.des_pos_z, self._p(self._dev["pose"]))
+                view = see(self, sub, active, tm, view)
+        if self.record_poses and self.onboard is not None:
+            self._poses.append(self._dev["pose"].cpu().numpy())
             sensed = np.zeros(self.B, bool)
             sensed[active] = True
             self._sensed.append(sensed)
 
-    def _record_tick(self, active, tm):
-        """record: the active missions' poses (the ones _sense took, with onboard), their velocities now and their depth
-        images into the recorder's per-mission buffers"""
-        c, d, p, rec = self.bp.ctx, self._dev, self._p, self.record
-        t0 = time.perf_counter()
-        sub = self._subset(active)
-        self._sync()
-        if self.onboard is None:
-            c.check(c.lib.neo_fleet_pose_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
-                                             p(d["cmd_index"]), p(d["cur_pos"]), p(d["goal"]), self.des_pos_z, p(d["pose"])))
-        c.check(c.lib.neo_record_state_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
-                                           p(d["cmd_index"]), p(d["head"]), p(rec.cur_vel)))
-        c.synchronize()
-        whole = active.size == self.B
-        idx64 = None if whole else sub.long()
-        pose_k = d["pose"] if whole else d["pose"].index_select(0, idx64).contiguous()
-        sidx = d["scene_index"]
-        sidx_k = sidx if (sidx is None or whole) else sidx.index_select(0, idx64).contiguous()
-        img = rec.camera.render_dev(d["boxes"], d["box_begin"], pose_k, sidx_k, chunk=rec.chunk, want_m=False)["depth_u8"]
-        if whole:
-            rec.staging.copy_(img)
+    def _see_onboard(self, sub, active, tm, view):
+        """mapper.update on what the active missions' cameras see: render, integrate, rebuild"""
+        d = self._dev
+        self._ctx_done()
+        rebuilt = self.onboard.update(d["boxes"], d["box_begin"], d["pose"], d["scene_index"], subset=active)
+        tm["rebuilt"] = int(len(rebuilt))
+        tm.update({k: self.onboard.last[k] for k in ("render_s", "integrate_s", "rebuild_s")})
+        return view
+
+    def _see_neo(self, sub, active, tm, view):
+        """modes "neo" and "nn": the velocities now and the features of what the cameras see into the loop's resident
+        cur_vel and feature arrays (the scatter is torch's: every target round starts with a _torch_done)"""
+        d = self._dev
+        return self._see_images(sub, active, view, d["cur_vel"], self.neo.features_dev, d["feature"])
+
+    def _see_record(self, sub, active, tm, view):
+        """record: the velocities now and the depth images into the recorder's per-mission buffers"""
+        rec = self.record
+        render = lambda *a: rec.camera.render_dev(*a, chunk=rec.chunk, want_m=False)["depth_u8"]
+        return self._see_images(sub, active, view, rec.cur_vel, render, rec.staging)
+
+    def _see_images(self, sub, active, view, cur_vel, render, into):
+        """one image consumer: the active missions' velocities now into its `cur_vel`, then render(boxes, box_begin, pose
+        rows, scene_index rows) of the active missions scattered into its per-mission buffer `into`"""
+        d = self._dev
+        self._call("neo_record_state_dev", *self._rows(sub), *self._cmd(), self._p(d["head"]), self._p(cur_vel))
+        self._ctx_done()
+        if view is None:
+            whole = active.size == self.B
+            idx64 = None if whole else sub.long()
+            take = lambda t: t if (t is None or whole) else t.index_select(0, idx64).contiguous()
+            view = idx64, take(d["pose"]), take(d["scene_index"])
+        idx64, pose_k, sidx_k = view
+        out = render(d["boxes"], d["box_begin"], pose_k, sidx_k)
+        if idx64 is None:
+            into.copy_(out)
         else:
-            rec.staging.index_copy_(0, idx64, img)
-        tm["record_s"] = time.perf_counter() - t0
+            into.index_copy_(0, idx64, out)
+        return view
 
-    def _neo_tick(self, active, tm):
-        """modes "neo" and "nn": the active missions' poses (the ones _sense took, with onboard), their velocities now and
-        the features of what their cameras see into the loop's resident cur_vel and feature arrays"""
-        c, d, p, neo = self.bp.ctx, self._dev, self._p, self.neo
-        t0 = time.perf_counter()
-        sub = self._subset(active)
-        self._sync()
-        if self.onboard is None:
-            c.check(c.lib.neo_fleet_pose_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
-                                             p(d["cmd_index"]), p(d["cur_pos"]), p(d["goal"]), self.des_pos_z, p(d["pose"])))
-        c.check(c.lib.neo_record_state_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
-                                           p(d["cmd_index"]), p(d["head"]), p(d["cur_vel"])))
-        c.synchronize()
-        whole = active.size == self.B
-        idx64 = None if whole else sub.long()
-        pose_k = d["pose"] if whole else d["pose"].index_select(0, idx64).contiguous()
-        sidx = d["scene_index"]
-        sidx_k = sidx if (sidx is None or whole) else sidx.index_select(0, idx64).contiguous()
-        feat = neo.features_dev(d["boxes"], d["box_begin"], pose_k, sidx_k)
-        if whole:
-            d["feature"].copy_(feat)
-        else:
-            d["feature"].index_copy_(0, idx64, feat)
-        self._sync()
-        tm["neo_s"] = time.perf_counter() - t0
-
-    def _advance(self, sub):
-        c, d, p = self.bp.ctx, self._dev, self._p
-        step = int(round(self.replan_period * self.cmd_hz))
-        ahead = int(self.planning_time_ahead * self.cmd_hz)                        # :531
-        c.check(c.lib.neo_fleet_advance_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
-                                            p(d["cmd_index"]), p(d["future_index"]), step, ahead, p(d["cur_pos"]),
-                                            p(d["head"])))
-
-    def _splice(self, sub, M, first):
-        c, d, p = self.bp.ctx, self._dev, self._p
-        c.check(c.lib.neo_fleet_splice_dev(c.h, self.B, p(sub), int(sub.numel()), int(M), p(d["x"]), p(d["head"]),
-                                           p(d["tail"]), p(d["solved"]), float(self.cmd_hz), int(first), p(d["cmd"]),
-                                           self.cap, p(d["cmd_len"]), p(d["cmd_index"]), p(d["future_index"]),
-                                           p(d["flags"])))
-
-    def _audit(self):
-        c, d, p = self.bp.ctx, self._dev, self._p
-        c.check(c.lib.neo_fleet_audit_batch_dev(c.h, self.map.scene_id, p(d["slots"]), self.B, None, 0, p(d["cmd"]),
-                                                self.cap, p(d["n_flown"]), self.stride, float(self.cmd_hz),
-                                                None if self.metric_weights is None else _lib.ptr(self.metric_weights),
-                                                p(d["audit"]), p(d["count"]), p(d["audit_flags"])))
-
-    # ---- goal routes (csrc/neo_track.hpp): the hooks of a tracked flight, the same for every mode
-    def _hold(self, sub, step):
-        """a mission whose commands end before the coming replan period is over holds its last one"""
-        c, d, p = self.bp.ctx, self._dev, self._p
-        c.check(c.lib.neo_fleet_hold_dev(c.h, self.B, p(sub), int(sub.numel()), p(d["cmd"]), self.cap, p(d["cmd_len"]),
-                                         p(d["cmd_index"]), int(step), p(d["flags"])))
-
-    def _routes_args(self):
-        d, p = self._dev, self._p
-        return p(d["vertices"]), int(d["vertices"].shape[0]), p(d["route_begin"]), p(d["speed"]), p(d["closed"])
-
-    def _goal(self, sub, t):
-        """the resident goals of the missions `sub` at time t"""
-        c, d, p = self.bp.ctx, self._dev, self._p
-        c.check(c.lib.neo_fleet_goal_route_dev(c.h, self.B, p(sub), int(sub.numel()), *self._routes_args(), float(t),
-                                               p(d["goal"])))
-
-    def _track_audit(self):
-        c, d, p = self.bp.ctx, self._dev, self._p
-        c.check(c.lib.neo_fleet_track_audit_dev(c.h, self.B, None, 0, p(d["cmd"]), self.cap, p(d["n_flown"]), self.stride,
-                                                float(self.cmd_hz), *self._routes_args(), self.track_radius, p(d["track"]),
-                                                p(d["track_count"]), p(d["track_flags"])))
 
     def _alloc(self, n):
         import torch
@@ -401,6 +412,8 @@ class FleetReplanLoop:
             self._dev.update(wpts_local=f(B, 2, M - 1), ts_carry=f(B, M), x0=f(B, n))
         if self.neo is not None:      # the network's inputs that are not the plan's own: velocity now, image features
             self._dev.update(cur_vel=f(B, 2), feature=torch.zeros((B, 24), dtype=torch.float32, device=dev))
+        if self.mode == "neo":      # the network's guess, attempt 0's start
+            self._dev.update(x0=f(B, n))
         if self.onboard is not None or self.record is not None or self.neo is not None:      # what the cameras see, and where from
             boxes, box_begin = self.scenes
             self._dev.update(pose=f(B, 5),
@@ -420,54 +433,71 @@ class FleetReplanLoop:
                              speed=torch.from_numpy(r.speed).to(dev), closed=torch.from_numpy(r.closed).to(dev),
                              track=f(B, _lib.NEO_TRACK_FIELDS), track_count=i(B), track_flags=i(B))
         self._poses, self._sensed = [], []
+        self._host_head = self._host_x = None      # the host plan step's copies, made at its first plan
         self._up("goal", self.goals)
 
     def _plan_bufs(self):
         if self._plan is None:
             self._plan = self.bp.plan_buffers(self.B, self._device, D=2)
-            self._sync()
+            self._torch_done()
         return self._plan
 
+    # ---- the plan steps, one per mode: (sub, pending, tick, r) -> (ok over pending, nit_total, attempts) as the host
+    # planner's dict has them; `pending` ascending, `sub` the same on the device; the resident x and solved are written
+    def _plan_dev(self, sub, tick, r, **kw):
+        """BatchPlanner.plan_dev for the missions `sub` on the resident head / tail, into the resident x and solved"""
+        d = self._dev
+        return self.bp.plan_dev(self.plan_map, d["head"], d["tail"], bufs=self._plan_bufs(), slots=d["plan_slots"], subset=sub,
+                                x=d["x"], solved=d["solved"], seed=plan_seed(self.seed, tick, r), jitter=self.jitter,
+                                stream_ids=d["mission_ids"] if self.counter else self.mission_ids, **kw)
+
     def _plan_resident(self, sub, pending, tick, r, x0=None):
-        """resident=True, mode "basic": one target round's plans for the missions `pending` (`sub` the same on the device)
-        on the resident head / tail -- plan_dev writes the resident x and solved; mode "neo": the same with the network's
-        guess `x0` as attempt 0's start.  Returns (ok over pending, nit_total, attempts) as the host planner's dict has
-        them."""
-        bufs = self.bp.plan_dev(self.plan_map, self._dev["head"], self._dev["tail"], bufs=self._plan_bufs(), x0=x0,
-                                slots=self._dev["plan_slots"], subset=sub, x=self._dev["x"], solved=self._dev["solved"],
-                                seed=plan_seed(self.seed, tick, r), jitter=self.jitter,
-                                stream_ids=self._dev["mission_ids"] if self.counter else self.mission_ids)
+        """resident=True, mode "basic": plan_dev; the other resident modes hand it their guess `x0` as attempt 0's start"""
+        bufs = self._plan_dev(sub, tick, r, x0=x0)
         idx = sub.long()
         return (self._dev["solved"][idx].cpu().numpy() != 0, bufs["nit_total"][idx].cpu().numpy(),
                 bufs["attempts"][idx].cpu().numpy())
+
+    def _plan_host(self, sub, pending, tick, r, planner=None):
+        """resident=False, mode "basic", and mode "geo": BatchPlanner.plan / geo_plan on host arrays -- head and tail come
+        down (head once a tick: only the advance moves it), x and solved go up whole, from the host's copy of x"""
+        d = self._dev
+        if r == 0:
+            self._host_head = d["head"].cpu().numpy()
+        if self._host_x is None:
+            self._host_x = np.zeros(tuple(d["x"].shape))
+        out = (planner or self.bp.plan)(self.plan_map, self._host_head[pending], d["tail"].cpu().numpy()[pending],
+                                        scene_ids=None if self.plan_scene_ids is None else self.plan_scene_ids[pending],
+                                        seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[pending],
+                                        **({"jitter": "counter"} if self.counter else {}))
+        self._host_x[pending] = out["x"]
+        solved = np.zeros(self.B, np.int32)
+        solved[pending[out["solved"]]] = 1
+        self._up("x", self._host_x)
+        self._up("solved", solved)
+        return out["solved"], out["nit_total"], out["attempts"]
+
+    def _plan_geo(self, sub, pending, tick, r):
+        return self._plan_host(sub, pending, tick, r, planner=self.bp.geo_plan)
 
     def _plan_neo(self, sub, pending, tick, r):
         """mode "neo": the network's guess for the pending missions on the resident pose, velocity, head, tail and
         features (BatchNeoPlanner.warm_start_dev, on the context's stream), then plan_dev from it"""
         d = self._dev
-        if "x0" not in d:
-            import torch
-            d["x0"] = torch.zeros_like(d["x"])
-            self._sync()
         x0 = self.neo.warm_start_dev(d["pose"], d["cur_vel"], d["head"], d["tail"], d["feature"], subset=sub, x0=d["x0"])
         return self._plan_resident(sub, pending, tick, r, x0=x0)
 
     def _plan_warm(self, sub, pending, tick, r):
         """mode "warmstart": the first plan of a mission (tick 0, and its re-targeted repeats) is a basic plan; every
         later one starts from what the mission carries -- neo_fleet_warm_guess_dev writes the resident x0 on the context's
-        stream, plan_dev takes it as attempt 0's start"""
-        d = self._dev
-        if tick == 0:
-            return self._plan_resident(sub, pending, tick, r)
-        x0 = self.bp.warm_guess_dev(d["head"], d["wpts_local"], d["ts_carry"], d["x0"], subset=sub)
-        return self._plan_resident(sub, pending, tick, r, x0=x0)
-
-    def _warm_carry(self, sub):
-        """mode "warmstart": what the round's missions keep of the plan call just made (neo_fleet_warm_carry_dev, on the
-        context's stream, in front of the splice); status and attempts are plan_dev's"""
+        stream, plan_dev takes it as attempt 0's start.  Then neo_fleet_warm_carry_dev, on the same stream, keeps what the
+        round's missions carry on of the plan call just made; status and attempts are plan_dev's."""
         d, pb = self._dev, self._plan_bufs()
+        x0 = self.bp.warm_guess_dev(d["head"], d["wpts_local"], d["ts_carry"], d["x0"], subset=sub) if tick > 0 else None
+        res = self._plan_resident(sub, pending, tick, r, x0=x0)
         self.bp.warm_carry_dev(d["x"], d["head"], d["solved"], pb["status"], pb["attempts"], d["wpts_local"], d["ts_carry"],
                                subset=sub)
+        return res
 
     def _plan_nn(self, sub, pending, tick, r):
         """mode "nn" (the reference's selected_planner:=nn): the network's guess straight into the resident x, solved = 1
@@ -481,48 +511,50 @@ class FleetReplanLoop:
         """mode "batch": one target round's plans for the missions `pending` (ascending; `sub` the same on the device) on the
         resident head / tail -- select writes the resident x and solved -- then the host `plan` for the missions without
         a feasible candidate.  Returns (ok over pending, nit_total, attempts) as the host planners' dicts have them."""
-        import torch
         bp, d = self.bp, self._dev
         if self._batch is None:
             self._batch = bp.batch_buffers(self.B, 3, self._device)
-            self._sync()
+            self._torch_done()
         bufs = bp.batch_plan_dev(self.plan_map, d["head"], d["tail"], self._batch, slots=d["plan_slots"], subset=sub, x=d["x"],
                                  solved=d["solved"])
         fb = bp.batch_fallback(bufs)
         nit = bufs["nit_total"].cpu().numpy()[pending].astype(np.int64)
         runs = bufs["opt_runs"].cpu().numpy()[pending].copy()
         self.uncounted_candidates[pending] += 3 - runs      # candidate runs that overflowed: the reference counts none of them
-        if fb.size and self.resident:
-            # candidate 0 (linspace's bits, with pack_x's tau) of the listed missions straight into plan_dev's packed rows
-            c, p, pb = bp.ctx, self._p, self._plan_bufs()
-            count = int(bp.cfg.init_wpts_num)
-            fb_dev = bufs["fallback"][:fb.size]
-            c.check(c.lib.neo_batch_candidates_dev(c.h, self.B, p(fb_dev), int(fb.size), count + 1, 2, 1, p(d["head"]),
-                                                   p(d["tail"]), p(d["plan_slots"]), _lib.ptr(bp._plan_frac_tau(count)[1]), None,
-                                                   p(pb["x_k"]), p(pb["head_k"]), p(pb["tail_k"]),
-                                                   p(pb["slots_k"]) if d["plan_slots"] is not None else None))
-            bp.plan_dev(self.plan_map, d["head"], d["tail"], bufs=pb, slots=d["plan_slots"], subset=fb_dev, x=d["x"], solved=d["solved"],
-                        seed=plan_seed(self.seed, tick, r), jitter=self.jitter, _guessed=True,
-                        stream_ids=d["mission_ids"] if self.counter else self.mission_ids)
-            idx = fb_dev.long()
+        if fb.size:
             at = np.searchsorted(pending, fb)
-            nit[at] += pb["nit_total"][idx].cpu().numpy()
-            runs[at] += pb["attempts"][idx].cpu().numpy()
-        elif fb.size:
-            idx = torch.from_numpy(fb).to(self._device)
-            head, tail = d["head"][idx].cpu().numpy(), d["tail"][idx].cpu().numpy()
-            count = int(bp.cfg.init_wpts_num)
-            res = bp.plan(self.plan_map, head, tail, int_wpts=bp.batch_init_guess(head, tail, K=1)[0][:, 0],
-                          ts=np.tile(bp._batch_ts_tau(count)[0], (fb.size, 1)),
-                          scene_ids=None if self.plan_scene_ids is None else self.plan_scene_ids[fb],
-                          seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[fb], jitter=self.jitter)
-            d["x"][idx] = torch.from_numpy(np.ascontiguousarray(res["x"])).to(self._device)
-            d["solved"][idx] = torch.from_numpy(res["solved"].astype(np.int32)).to(self._device)
-            at = np.searchsorted(pending, fb)
-            nit[at] += res["nit_total"]
-            runs[at] += res["attempts"]
+            nit_fb, runs_fb = self._fallback(self, fb, bufs["fallback"][:fb.size], tick, r)
+            nit[at] += nit_fb
+            runs[at] += runs_fb
         ok = d["solved"].cpu().numpy()[pending] != 0
         return ok, nit, runs
+
+    def _fallback_resident(self, fb, fb_dev, tick, r):
+        """the missions `fb` (`fb_dev` the same on the device) through plan_dev: candidate 0 (linspace's bits, with pack_x's
+        tau) straight into plan_dev's packed rows.  Returns their nit_total and attempts."""
+        bp, d, p, pb = self.bp, self._dev, self._p, self._plan_bufs()
+        count = int(bp.cfg.init_wpts_num)
+        self._call("neo_batch_candidates_dev", *self._rows(fb_dev), count + 1, 2, 1, *self._ptrs("head", "tail", "plan_slots"),
+                   _lib.ptr(bp._plan_frac_tau(count)[1]), None, p(pb["x_k"]), p(pb["head_k"]), p(pb["tail_k"]),
+                   p(pb["slots_k"]) if d["plan_slots"] is not None else None)
+        self._plan_dev(fb_dev, tick, r, _guessed=True)
+        idx = fb_dev.long()
+        return pb["nit_total"][idx].cpu().numpy(), pb["attempts"][idx].cpu().numpy()
+
+    def _fallback_host(self, fb, fb_dev, tick, r):
+        """the missions `fb` through the host `plan` from candidate 0; their rows of x / solved are uploaded (torch's
+        stream: the loop waits for it before the splice).  Returns their nit_total and attempts."""
+        import torch
+        bp, d = self.bp, self._dev
+        idx = torch.from_numpy(fb).to(self._device)
+        head, tail = d["head"][idx].cpu().numpy(), d["tail"][idx].cpu().numpy()
+        res = bp.plan(self.plan_map, head, tail, int_wpts=bp.batch_init_guess(head, tail, K=1)[0][:, 0],
+                      ts=np.tile(bp._batch_ts_tau(int(bp.cfg.init_wpts_num))[0], (fb.size, 1)),
+                      scene_ids=None if self.plan_scene_ids is None else self.plan_scene_ids[fb],
+                      seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[fb], jitter=self.jitter)
+        d["x"][idx] = torch.from_numpy(np.ascontiguousarray(res["x"])).to(self._device)
+        d["solved"][idx] = torch.from_numpy(res["solved"].astype(np.int32)).to(self._device)
+        return res["nit_total"], res["attempts"]
 
     # ------------------------------------------------------------ the loop
     def run(self, start_pos, start_vel=None, max_replans=60):
@@ -532,141 +564,101 @@ class FleetReplanLoop:
         METRIC_FAIL), replans (plans that were spliced), failed_attempts, iter_num, opt_runs, n_cmd (rows of the command
         array), n_flown, final_dist, flags (NEO_FLEET_FLAG_*), audit_flags (NEO_AUDIT_FLAG_*), count and the ten audit
         fields by name.  With goal_routes: the first plan and `max_replans` ticks of chasing (class docstring)."""
-        B = self.B
-        bp = self.bp
+        B, bp = self.B, self.bp
         count = int(bp.cfg.init_wpts_num)
         M, n = count + 1, 2 * count + count + 1
         bp._sync()
         self._alloc(n)
-        start_pos = _lib.as_f64(start_pos).reshape(B, 2)
+        d, p = self._dev, self._p
         head = np.zeros((B, 3, 2))
-        head[:, 0] = start_pos
+        head[:, 0] = _lib.as_f64(start_pos).reshape(B, 2)
         if start_vel is not None:
             head[:, 1] = _lib.as_f64(start_vel).reshape(B, 2)
-        cur_pos = start_pos.copy()
-        tail = np.zeros((B, 3, 2))
-        x = np.zeros((B, n))
-        replans = np.zeros(B, np.int32); failed = np.zeros(B, np.int32); opt_runs = np.zeros(B, np.int32)
-        iter_num = np.zeros(B, np.int64)
-        abandoned = np.zeros(B, bool); landed = np.zeros(B, bool)      # landed: near the goal and that plan spliced (:421-427)
+        tracked = self.routes is not None
+        t = _Tally(B, tracked)
         active = np.arange(B)
         self.timings = []
         self.uncounted_candidates[:] = 0
-        d = self._dev
-        planner = bp.geo_plan if self.mode == "geo" else bp.plan
-        tracked = self.routes is not None
-        failed_ticks = np.zeros(B, np.int32) if tracked else None
         step = int(round(self.replan_period * self.cmd_hz))
+        ahead = int(self.planning_time_ahead * self.cmd_hz)                        # :531
         for tick in range(max_replans + 1):
             if active.size == 0:
                 break
             tm = dict(tick=tick, active=int(active.size), fleet_s=0.0, plan_s=0.0, plans=0, plan_requests=0)
             t_tick = time.perf_counter()
-            if tick > 0:
-                t0 = time.perf_counter()
-                sub_a = self._subset(active)
-                self._sync()
+            # hold / advance, then where the goals are now: before sensing and the targets, tick 0 included.  (No _ctx_done
+            # behind them: the next to read what they write are launches on the same stream, the camera stage's or a target's.)
+            with _Timed(tm, "fleet_s"):
+                sub_a = self._subset(active)      # the tick's missions, uploaded once
+                if tick == 0:
+                    self._up("cur_pos", head[:, 0])
+                    self._up("head", head)
+                if tick > 0 or tracked:
+                    self._torch_done()
+                if tick > 0:
+                    if tracked:      # a mission whose commands end before the coming period is over holds its last one
+                        self._call("neo_fleet_hold_dev", *self._rows(sub_a), *self._cmd(), step, p(d["flags"]))
+                    self._call("neo_fleet_advance_dev", *self._rows(sub_a), *self._cmd(), p(d["future_index"]), step, ahead,
+                               *self._ptrs("cur_pos", "head"))
                 if tracked:
-                    self._hold(sub_a, step)
-                self._advance(sub_a)
-                bp.ctx.synchronize()
-                if self.mode != "batch" and not self.resident:      # (batch and resident plans use the resident states)
-                    cur_pos = d["cur_pos"].cpu().numpy()
-                    head = d["head"].cpu().numpy()
-                tm["fleet_s"] += time.perf_counter() - t0
-            else:
-                self._up("cur_pos", cur_pos)
-                self._up("head", head)
-            if tracked:      # where the goals are now: before sensing and the targets, tick 0 included
-                t0 = time.perf_counter()
-                sub_a = self._subset(active)
-                self._sync()
-                self._goal(sub_a, (tick * step) / self.cmd_hz)
-                bp.ctx.synchronize()
-                tm["fleet_s"] += time.perf_counter() - t0
-            if self.onboard is not None:
-                self._sense(active, tm)
-            if self.neo is not None:
-                self._neo_tick(active, tm)
-            if self.record is not None:
-                self._record_tick(active, tm)
-            pending = active
+                    self._call("neo_fleet_goal_route_dev", *self._rows(sub_a), *self._route_table(),
+                               float((tick * step) / self.cmd_hz), p(d["goal"]))
+            self._camera_stage(sub_a, active, tm)
+            pending, sub = active, sub_a
             for r in range(MAX_TARGETS):
-                t0 = time.perf_counter()
-                if not self.counter:
-                    jit = np.zeros((B, 2))
-                    jit[pending] = target_jitter(self.seed, self.mission_ids[pending], tick, r)
-                    self._up("jitter", jit)
-                sub = self._subset(pending)
-                self._sync()
-                if self.counter:
-                    self._jitter(sub, tick, r)
-                self._target(sub)
-                bp.ctx.synchronize()
-                if self.mode != "batch" and not self.resident:
-                    tail[pending] = d["tail"].cpu().numpy()[pending]
-                near = d["near"].cpu().numpy() != 0
-                tm["fleet_s"] += time.perf_counter() - t0
-                t0 = time.perf_counter()
-                if self.mode == "batch":
-                    ok, nit_total, attempts = self._plan_batch(sub, pending, tick, r)
-                elif self.mode == "neo":
-                    ok, nit_total, attempts = self._plan_neo(sub, pending, tick, r)
-                elif self.mode == "nn":
-                    ok, nit_total, attempts = self._plan_nn(sub, pending, tick, r)
-                elif self.mode == "warmstart":
-                    ok, nit_total, attempts = self._plan_warm(sub, pending, tick, r)
-                elif self.resident:
-                    ok, nit_total, attempts = self._plan_resident(sub, pending, tick, r)
-                else:
-                    out = planner(self.plan_map, head[pending], tail[pending],
-                                  scene_ids=None if self.plan_scene_ids is None else self.plan_scene_ids[pending],
-                                  seed=plan_seed(self.seed, tick, r), stream_ids=self.mission_ids[pending],
-                                  **({"jitter": "counter"} if self.counter else {}))
-                    ok, nit_total, attempts = out["solved"], out["nit_total"], out["attempts"]
-                tm["plan_s"] += time.perf_counter() - t0
+                with _Timed(tm, "fleet_s"):      # jitter and target
+                    if r > 0:
+                        sub = self._subset(pending)      # the round's missions, uploaded once
+                    if not self.counter:
+                        jit = np.zeros((B, 2))
+                        jit[pending] = target_jitter(self.seed, self.mission_ids[pending], tick, r)
+                        self._up("jitter", jit)
+                    self._torch_done()
+                    if self.counter:
+                        self._call("neo_fleet_jitter_dev", *self._rows(sub), self.seed, tick, r, *self._ptrs("mission_ids", "jitter"))
+                    self._call("neo_fleet_target_batch_dev", self.plan_map.scene_id, p(d["plan_slots"]), *self._rows(sub),
+                               *self._ptrs("cur_pos", "goal", "jitter"), self.longitu_step_dis, self.lateral_step_length,
+                               self.move_vel, *self._ptrs("tail", "near", "steps", "flags"))
+                    self._ctx_done()
+                    near = d["near"].cpu().numpy() != 0
+                with _Timed(tm, "plan_s"):
+                    ok, nit_total, attempts = self._plan_step(self, sub, pending, tick, r)
                 tm["plans"] += 1
                 tm["plan_requests"] += int(pending.size)
-                iter_num[pending] += nit_total
-                opt_runs[pending] += attempts
-                t0 = time.perf_counter()
-                if self.mode != "batch" and not self.resident:
-                    x[pending] = out["x"]
-                    solved = np.zeros(B, np.int32)
-                    solved[pending[ok]] = 1
-                    self._up("x", x)
-                    self._up("solved", solved)
-                self._sync()
-                if self.mode == "warmstart":
-                    self._warm_carry(sub)
-                if self.record is not None:      # the round's rows, from the plans about to be spliced
-                    self.record.commit(B, sub, d["x"], d["head"], d["tail"], d["solved"], d["pose"], d["mission_ids"], tick, r)
-                self._splice(sub, M, first=(tick == 0))
-                bp.ctx.synchronize()
-                tm["fleet_s"] += time.perf_counter() - t0
-                replans[pending[ok]] += 1
-                failed[pending[~ok]] += 1
+                t.iter_num[pending] += nit_total
+                t.opt_runs[pending] += attempts
+                with _Timed(tm, "fleet_s"):      # record commit and splice
+                    self._torch_done()
+                    if self.record is not None:      # the round's rows, from the plans about to be spliced
+                        self.record.commit(B, sub, d["x"], d["head"], d["tail"], d["solved"], d["pose"], d["mission_ids"], tick, r)
+                    self._call("neo_fleet_splice_dev", *self._rows(sub), M, *self._ptrs("x", "head", "tail", "solved"),
+                               float(self.cmd_hz), int(tick == 0), *self._cmd(), *self._ptrs("future_index", "flags"))
+                    self._ctx_done()
+                t.replans[pending[ok]] += 1
+                t.failed[pending[~ok]] += 1
                 if not tracked:      # (a tracked mission never lands: planning goes on, :319-321)
-                    landed[pending[ok]] = near[pending[ok]]
+                    t.landed[pending[ok]] = near[pending[ok]]
                 pending = pending[~ok]
                 if pending.size == 0:
                     break
             if tracked:      # all targets of the tick failed: the mission flies on along its old commands (:265-279)
-                failed_ticks[pending] += 1
+                t.failed_ticks[pending] += 1
             else:
-                abandoned[pending] = True
+                t.abandoned[pending] = True
             flags = d["flags"].cpu().numpy()
             stuck = (flags & (_lib.NEO_FLEET_FLAG_CMD_FULL | _lib.NEO_FLEET_FLAG_SPLICE_FAILED)) != 0
-            active = active[~(abandoned | landed | stuck)[active]]
+            active = active[~(t.abandoned | t.landed | stuck)[active]]
             tm["tick_s"] = time.perf_counter() - t_tick
             tm["host_s"] = tm["tick_s"] - tm["fleet_s"] - tm["plan_s"] - tm.get("sense_s", 0.0) - tm.get("record_s", 0.0) - \
                 tm.get("neo_s", 0.0)
             self.timings.append(tm)
-        return self._finish(replans, failed, iter_num, opt_runs, abandoned, landed, failed_ticks)
+        return self._finish(t)
 
-    def _finish(self, replans, failed, iter_num, opt_runs, abandoned, landed, failed_ticks=None):
+    def _finish(self, tally):
+        """the audits on the true maps over what was flown, and the result dict"""
         import torch
-        d = self._dev
+        d, p = self._dev, self._p
+        abandoned, landed = tally.abandoned, tally.landed
         tracked = self.routes is not None
         cmd_len = d["cmd_len"].cpu().numpy()
         cmd_index = d["cmd_index"].cpu().numpy()
@@ -674,16 +666,21 @@ class FleetReplanLoop:
         # is always on a row of its array: n_flown = cmd_index + 1, whatever it held on the way)
         n_flown = np.where(landed, cmd_len, np.minimum(cmd_index + 1, cmd_len)).astype(np.int32)
         self._up("n_flown", n_flown)
-        self._sync()
-        t0 = time.perf_counter()
-        self._audit()
-        self.bp.ctx.synchronize()
-        self.audit_s = time.perf_counter() - t0
+        self._torch_done()
+        took = {}
+        flown = p(d["cmd"]), self.cap, p(d["n_flown"]), self.stride, float(self.cmd_hz)
+        with _Timed(took, "audit_s"):
+            self._call("neo_fleet_audit_batch_dev", self.map.scene_id, p(d["slots"]), *self._rows(None), *flown,
+                       None if self.metric_weights is None else _lib.ptr(self.metric_weights),
+                       *self._ptrs("audit", "count", "audit_flags"))
+            self._ctx_done()
         if tracked:
-            t0 = time.perf_counter()
-            self._track_audit()
-            self.bp.ctx.synchronize()
-            self.track_audit_s = time.perf_counter() - t0
+            with _Timed(took, "track_audit_s"):
+                self._call("neo_fleet_track_audit_dev", *self._rows(None), *flown, *self._route_table(), self.track_radius,
+                           *self._ptrs("track", "track_count", "track_flags"))
+                self._ctx_done()
+            self.track_audit_s = took["track_audit_s"]
+        self.audit_s = took["audit_s"]
         goals = d["goal"].cpu().numpy() if tracked else self.goals      # tracked: where the goals were at the last tick
         last = torch.from_numpy(np.maximum(n_flown - 1, 0).astype(np.int64)).to(self._device)
         end = d["cmd"][torch.arange(self.B, device=self._device), last, 0].cpu().numpy()
@@ -698,14 +695,14 @@ class FleetReplanLoop:
         else:
             success = (final_dist < self.target_reach_threshold) & ~abandoned & ~metric_fail & (flags == 0)
         out.update(success=success,
-                   replans=replans, failed_attempts=failed, iter_num=iter_num, opt_runs=opt_runs, n_cmd=cmd_len,
+                   replans=tally.replans, failed_attempts=tally.failed, iter_num=tally.iter_num, opt_runs=tally.opt_runs, n_cmd=cmd_len,
                    n_flown=n_flown, final_dist=final_dist, flags=flags, audit_flags=audit_flags,
                    count=d["count"].cpu().numpy(), abandoned=abandoned, metric_fail=metric_fail)
         if tracked:
             track = d["track"].cpu().numpy()
             out.update({"track_" + name: track[:, k] for k, name in enumerate(_lib.TRACK_FIELDS)})
             out.update(track_count=d["track_count"].cpu().numpy(), track_flags=d["track_flags"].cpu().numpy(),
-                       failed_ticks=failed_ticks, goal_final=goals)
+                       failed_ticks=tally.failed_ticks, goal_final=goals)
         if self.record_poses and self.onboard is not None:
             out.update(poses=np.stack(self._poses) if self._poses else np.zeros((0, self.B, 5)),
                        sensed=np.stack(self._sensed) if self._sensed else np.zeros((0, self.B), bool))
