@@ -254,6 +254,11 @@ class Context:
         if rc != NEO_OK:
             raise NeoError(f"libneo_planner_hip error {rc}: {self.lib.neo_last_error(self.h).decode()}")
 
+    def call(self, name, *args):
+        """the status-returning entry point `name` on this context; raises on its error code.  `lib` is looked up at
+        call time: a recording proxy stands in by replacing it"""
+        self.check(getattr(self.lib, name)(self.h, *args))
+
     def set_params(self, **kw):
         for k, v in kw.items():
             if k == "weights":

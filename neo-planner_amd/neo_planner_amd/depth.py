@@ -82,9 +82,9 @@ class DepthCamera:
         c = self.ctx
         # (a scene list without any box still hands over a valid pointer)
         bx = boxes if boxes.shape[0] else np.zeros((1, 6))
-        c.check(c.lib.neo_depth_render_batch(c.h, self.width, self.height, self.focal_px, self.max_range, _lib.ptr(bx),
-                                             _lib.ptr(begin), len(begin) - 1, _lib.ptr(sidx), B, _lib.ptr(pose),
-                                             _lib.ptr(depth_m), _lib.ptr(depth_u8), _lib.ptr(depth_max)))
+        c.call("neo_depth_render_batch", self.width, self.height, self.focal_px, self.max_range, _lib.ptr(bx),
+               _lib.ptr(begin), len(begin) - 1, _lib.ptr(sidx), B, _lib.ptr(pose),
+               _lib.ptr(depth_m), _lib.ptr(depth_u8), _lib.ptr(depth_max))
         return dict(depth_u8=depth_u8, depth_m=depth_m, depth_max=depth_max)
 
     def render_dev(self, boxes, box_begin, pose, scene_index=None, chunk=None, want_m=True, sync=True):
@@ -119,10 +119,9 @@ class DepthCamera:
         for b0 in range(0, B, chunk):
             n = min(chunk, B - b0)
             m = depth_m[b0:b0 + n] if want_m else self._buf[:n]
-            c.check(c.lib.neo_depth_render_batch_dev(
-                c.h, W, H, self.focal_px, self.max_range, p(boxes), p(box_begin), int(box_begin.shape[0]) - 1,
-                p(scene_index[b0:b0 + n]) if scene_index is not None else None, n, p(pose[b0:b0 + n]), p(m),
-                p(depth_u8[b0:b0 + n]), p(depth_max[b0:b0 + n])))
+            c.call("neo_depth_render_batch_dev", W, H, self.focal_px, self.max_range, p(boxes), p(box_begin),
+                   int(box_begin.shape[0]) - 1, p(scene_index[b0:b0 + n]) if scene_index is not None else None, n,
+                   p(pose[b0:b0 + n]), p(m), p(depth_u8[b0:b0 + n]), p(depth_max[b0:b0 + n]))
         if sync:
             c.synchronize()
         out = dict(depth_u8=depth_u8, depth_max=depth_max)

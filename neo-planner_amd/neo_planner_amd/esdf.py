@@ -36,9 +36,9 @@ class ESDF:
         n = (self.map_height, self.map_width)
         dist, gx, gy = np.empty(n), np.empty(n), np.empty(n)
         c = self.ctx
-        c.check(c.lib.neo_esdf_build_2d(c.h, self.scene_id, _lib.ptr(occ), self.map_width, self.map_height,
-                                        float(self.map_resolution), float(self.map_origin.x),
-                                        float(self.map_origin.y), _lib.ptr(dist), _lib.ptr(gx), _lib.ptr(gy)))
+        c.call("neo_esdf_build_2d", self.scene_id, _lib.ptr(occ), self.map_width, self.map_height,
+               float(self.map_resolution), float(self.map_origin.x),
+               float(self.map_origin.y), _lib.ptr(dist), _lib.ptr(gx), _lib.ptr(gy))
         self.esdf_map, self.esdf_grad_x, self.esdf_grad_y = dist, gx, gy
         self.version += 1
 
@@ -53,9 +53,9 @@ class ESDF:
         self.map_resolution = resolution
         self.map_origin = types.SimpleNamespace(x=float(origin_xy[0]), y=float(origin_xy[1]))
         c = self.ctx
-        c.check(c.lib.neo_esdf_upload_2d(c.h, self.scene_id, _lib.ptr(self.esdf_map), _lib.ptr(self.esdf_grad_x),
-                                         _lib.ptr(self.esdf_grad_y), self.map_width, self.map_height,
-                                         float(resolution), self.map_origin.x, self.map_origin.y))
+        c.call("neo_esdf_upload_2d", self.scene_id, _lib.ptr(self.esdf_map), _lib.ptr(self.esdf_grad_x),
+               _lib.ptr(self.esdf_grad_y), self.map_width, self.map_height,
+               float(resolution), self.map_origin.x, self.map_origin.y)
         self.version += 1
         return self
 
@@ -64,7 +64,7 @@ class ESDF:
         d = np.empty(1)
         g = np.empty((1, 2))
         c = self.ctx
-        c.check(c.lib.neo_esdf_query(c.h, self.scene_id, 1, _lib.ptr(p), _lib.ptr(d), _lib.ptr(g)))
+        c.call("neo_esdf_query", self.scene_id, 1, _lib.ptr(p), _lib.ptr(d), _lib.ptr(g))
         return d, g
 
     def query(self, pts):
@@ -73,7 +73,7 @@ class ESDF:
         d = np.empty(len(p))
         g = np.empty((len(p), 2))
         c = self.ctx
-        c.check(c.lib.neo_esdf_query(c.h, self.scene_id, len(p), _lib.ptr(p), _lib.ptr(d), _lib.ptr(g)))
+        c.call("neo_esdf_query", self.scene_id, len(p), _lib.ptr(p), _lib.ptr(d), _lib.ptr(g))
         return d, g
 
     def get_edt_dis(self, pos):                     # esdf.py:53-67
@@ -130,10 +130,10 @@ class ESDF3D:
         nz, ny, nx = self.shape
         org = (ctypes.c_double * 3)(*self.origin)
         c = self.ctx
-        c.check(c.lib.neo_esdf_upload_3d(c.h, self.scene_id, pointer, src_dtype, int(src_dev), nx, ny, nz,
-                                         self.resolution, ctypes.cast(org, ctypes.c_void_p),
-                                         {"f32": _lib.NEO_F32, "f16": _lib.NEO_F16}[store],
-                                         _lib.LAYOUTS[layout]))
+        c.call("neo_esdf_upload_3d", self.scene_id, pointer, src_dtype, int(src_dev), nx, ny, nz,
+               self.resolution, ctypes.cast(org, ctypes.c_void_p),
+               {"f32": _lib.NEO_F32, "f16": _lib.NEO_F16}[store],
+               _lib.LAYOUTS[layout])
 
     @classmethod
     def from_occupancy(cls, occ, resolution, origin_xyz, store="f32", layout="linear", ctx=None, want_dist=False):
@@ -162,11 +162,11 @@ class ESDF3D:
         self.dist = np.empty(self.shape, dtype=np.float32) if want_dist else None
         org = (ctypes.c_double * 3)(*self.origin)
         c = self.ctx
-        c.check(c.lib.neo_esdf_build_3d(c.h, self.scene_id, pointer, int(on_dev), nx, ny, nz, self.resolution,
-                                        ctypes.cast(org, ctypes.c_void_p),
-                                        {"f32": _lib.NEO_F32, "f16": _lib.NEO_F16}[store],
-                                        _lib.LAYOUTS[layout],
-                                        _lib.ptr(self.dist)))
+        c.call("neo_esdf_build_3d", self.scene_id, pointer, int(on_dev), nx, ny, nz, self.resolution,
+               ctypes.cast(org, ctypes.c_void_p),
+               {"f32": _lib.NEO_F32, "f16": _lib.NEO_F16}[store],
+               _lib.LAYOUTS[layout],
+               _lib.ptr(self.dist))
         return self
 
     def query(self, pts):
@@ -174,7 +174,7 @@ class ESDF3D:
         d = np.empty(len(p))
         g = np.empty((len(p), 3))
         c = self.ctx
-        c.check(c.lib.neo_esdf_query(c.h, self.scene_id, len(p), _lib.ptr(p), _lib.ptr(d), _lib.ptr(g)))
+        c.call("neo_esdf_query", self.scene_id, len(p), _lib.ptr(p), _lib.ptr(d), _lib.ptr(g))
         return d, g
 
     def get_edt_dis(self, pos):

@@ -305,9 +305,8 @@ class FleetReplanLoop:
         self.bp.ctx.synchronize()
 
     def _call(self, name, *args):
-        """the library's entry point `name` on the loop's context; raises on its error code"""
-        c = self.bp.ctx
-        c.check(getattr(c.lib, name)(c.h, *args))
+        """the library's entry point `name` on the loop's context (Context.call)"""
+        self.bp.ctx.call(name, *args)
 
     # the argument groups the fleet entry points share
     def _rows(self, sub):

@@ -543,15 +543,15 @@ class BatchNeoPlanner:
         self.bp._sync()                      # the context's T_min / T_max are the planner's
         c, p = self.bp.ctx, _lib.dev_ptr
         sub, n_sub = p(subset), (0 if subset is None else int(subset.numel()))
-        c.check(c.lib.neo_init_motion_dev(c.h, B, sub, n_sub, p(pose), p(cur_vel), p(head), p(tail), p(self.motion)))
+        c.call("neo_init_motion_dev", B, sub, n_sub, p(pose), p(cur_vel), p(head), p(tail), p(self.motion))
         if head_impl == "kernel":
-            c.check(c.lib.neo_init_head_dev(c.h, B, sub, n_sub, p(weights), int(weights.numel()), p(feature),
-                                            int(feature.shape[0]), p(self.motion), p(self.out)))
+            c.call("neo_init_head_dev", B, sub, n_sub, p(weights), int(weights.numel()), p(feature),
+                   int(feature.shape[0]), p(self.motion), p(self.out))
         else:
             c.synchronize()
             self.out.copy_(self.init.net.head(feature, self.motion).to(torch.float32))
             torch.cuda.synchronize(dev)
-        c.check(c.lib.neo_init_guess_dev(c.h, B, sub, n_sub, p(self.out), p(pose), p(x0)))
+        c.call("neo_init_guess_dev", B, sub, n_sub, p(self.out), p(pose), p(x0))
         return x0
 
     def plan_dev(self, map, pose, cur_vel, head, tail, feature, subset=None, head_impl=None, **plan_dev_kw):

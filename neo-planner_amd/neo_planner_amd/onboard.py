@@ -124,10 +124,10 @@ class OnboardMapper:
             raise ValueError("OnboardMapper.integrate: pose must be a contiguous (n, 5) float64 tensor")
         torch.cuda.synchronize(self._device)     # (the context has its own stream: torch's tensors are ready before it starts)
         l_hit, l_miss, l_lo, l_hi = self.lodds
-        c.check(c.lib.neo_onboard_integrate_batch_dev(
-            c.h, self.B, p(sub), n, p(depth_m), p(pose), cam.width, cam.height, cam.focal_px, cam.max_range, self.width,
-            self.height, self.resolution, p(self._origins_dev), self.sensor_range, self.z_band[0], self.z_band[1], l_hit,
-            l_miss, l_lo, l_hi, p(self.logodds), p(self.occupancy), p(self.changed)))
+        c.call("neo_onboard_integrate_batch_dev", self.B, p(sub), n, p(depth_m), p(pose), cam.width, cam.height,
+               cam.focal_px, cam.max_range, self.width, self.height, self.resolution, p(self._origins_dev),
+               self.sensor_range, self.z_band[0], self.z_band[1], l_hit, l_miss, l_lo, l_hi, p(self.logodds),
+               p(self.occupancy), p(self.changed))
         c.synchronize()
         return self.changed
 
@@ -148,9 +148,9 @@ class OnboardMapper:
         else:
             occ = self.occupancy.index_select(0, torch.from_numpy(idx.astype(np.int64)).to(self._device))
         torch.cuda.synchronize(self._device)
-        c.check(c.lib.neo_esdf_build_2d_batch_dev(c.h, _lib.ptr(np.ascontiguousarray(self.scene_ids[idx])), int(idx.size),
-                                                  p(occ), self.width, self.height, self.resolution,
-                                                  _lib.ptr(np.ascontiguousarray(self.origins[idx]))))
+        c.call("neo_esdf_build_2d_batch_dev", _lib.ptr(np.ascontiguousarray(self.scene_ids[idx])), int(idx.size),
+               p(occ), self.width, self.height, self.resolution,
+               _lib.ptr(np.ascontiguousarray(self.origins[idx])))
         self.version += 1
         return idx
 
@@ -178,9 +178,9 @@ class OnboardMapper:
             n = min(chunk, idx.size - k0)
             torch.cuda.synchronize(self._device)
             t0 = time.perf_counter()
-            c.check(c.lib.neo_depth_render_batch_dev(c.h, W, H, cam.focal_px, cam.max_range, p(boxes), p(box_begin), n_scenes,
-                                                     p(sidx_k[k0:k0 + n]) if sidx_k is not None else None, n,
-                                                     p(pose_k[k0:k0 + n]), p(self._depth), None, None))
+            c.call("neo_depth_render_batch_dev", W, H, cam.focal_px, cam.max_range, p(boxes), p(box_begin), n_scenes,
+                   p(sidx_k[k0:k0 + n]) if sidx_k is not None else None, n,
+                   p(pose_k[k0:k0 + n]), p(self._depth), None, None)
             c.synchronize()
             t1 = time.perf_counter()
             self.integrate(self._depth[:n], pose_k[k0:k0 + n], idx_dev[k0:k0 + n])
@@ -201,5 +201,5 @@ class OnboardMapper:
         d = np.empty(len(pts))
         g = np.empty((len(pts), 2))
         c = self.ctx
-        c.check(c.lib.neo_esdf_query(c.h, int(self.scene_ids[i]), len(pts), _lib.ptr(pts), _lib.ptr(d), _lib.ptr(g)))
+        c.call("neo_esdf_query", int(self.scene_ids[i]), len(pts), _lib.ptr(pts), _lib.ptr(d), _lib.ptr(g))
         return d, g

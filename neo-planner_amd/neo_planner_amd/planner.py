@@ -84,6 +84,113 @@ def _audit_weights(weights):
     return None if weights is None else _lib.as_f64(weights).reshape(3)
 
 
+def _f64(*arrays):
+    """the arrays as C-contiguous float64, what the host entry points read"""
+    return [_lib.as_f64(a) for a in arrays]
+
+
+def _ptrs(*arrays):
+    """host pointers of NumPy arrays, in order (None -> NULL)"""
+    return [_lib.ptr(a) for a in arrays]
+
+
+def _dev_ptrs(*tensors):
+    """device pointers of torch tensors, in order (None -> NULL)"""
+    return [_lib.dev_ptr(t) for t in tensors]
+
+
+def _eval_arrays(B, n, M, D, want_coeffs=True):
+    """what neo_cost_grad_batch fills, in the order it takes them: cost (B,), costs (B, 4), grad (B, n), coeffs (B, 6 M, D)
+    or None, status"""
+    return np.zeros(B), np.zeros((B, 4)), np.zeros((B, n)), np.zeros((B, 6 * M, D)) if want_coeffs else None, np.zeros(B, np.int32)
+
+
+def _audit_arrays(B):
+    """what neo_audit_traj_batch fills, in the order it takes them: audit (B, NEO_AUDIT_FIELDS), count, flags"""
+    return np.zeros((B, _lib.NEO_AUDIT_FIELDS)), np.zeros(B, np.int32), np.zeros(B, np.int32)
+
+
+# ---------------------------------------------------------------- what BatchPlanner's methods share (DESIGN.md, host layer)
+def _shape(x, head):
+    """(B, M, D, n) of the packed rows x (B, n) = [D * (M - 1) waypoint values ; M tau] with head (B, 3, D)"""
+    B, n = x.shape
+    D = head.shape[2]
+    return B, (n + D) // (D + 1), D, n
+
+
+def _host_results(B):
+    """the optimiser's five result arrays on the host, as ONE tuple in the order every entry point takes them:
+    costs (B, 4), costs_last (B, 4), nit, nfev, status (B,) int32"""
+    return np.zeros((B, 4)), np.zeros((B, 4)), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+
+
+def _dev_results(B, dev):
+    """`_host_results` as zeroed torch tensors on `dev`"""
+    import torch
+    f = lambda: torch.zeros(B, 4, dtype=torch.float64, device=dev)
+    i = lambda: torch.zeros(B, dtype=torch.int32, device=dev)
+    return f(), f(), i(), i(), i()
+
+
+def _result_dict(x, results, weights=None):
+    """the optimiser's result dict from x and the five arrays: status split into its code and the collision flag;
+    with `weights`, final_cost = (costs * weights).sum() -- the costs at x (batch_plan takes costs_last: it adds its own)"""
+    costs, last, nit, nfev, st = results
+    out = dict(x=x, costs=costs, costs_last=last, nit=nit, nfev=nfev, status=st & 0xff,
+               collision=(st & _lib.NEO_TRAJ_FLAG_COLLISION) != 0)
+    if weights is not None:
+        out["final_cost"] = (costs * np.asarray(weights, dtype=np.float64)).sum(axis=1)
+    return out
+
+
+def _upload(dev, *arrays):
+    """host arrays as tensors on `dev` (blocking copies on torch's stream)"""
+    import torch
+    return [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays]
+
+
+def _torch_done(dev):
+    """THE STREAM RULE: the context launches on a stream of its own, so what torch has queued -- uploads, zeroed buffers --
+    is waited for before the context's first launch on it; in the other direction Context.synchronize"""
+    import torch
+    torch.cuda.synchronize(dev)
+
+
+def _scene_ids(scene_ids):
+    """per-request scene ids as the ABI takes them: contiguous int32, or None (every request on the call's map)"""
+    return None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32)
+
+
+def _stream_ids(stream_ids, B, who):
+    """the stream of each request's retry noise: its position in the batch unless the caller names one per request"""
+    stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
+    if stream_ids.shape[0] != B:
+        raise ValueError("%s: stream_ids needs one id per request" % who)
+    return stream_ids
+
+
+def _draw_seed(rng):
+    """a call's seed when the caller gave none: from `rng`, or from the OS"""
+    return int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
+
+
+def _work_buffers(device, header, rows, B, n, D):
+    """what plan_buffers and batch_buffers share (torch tensors, zeroed): the packed work arrays of a launch of `rows`
+    rows and the request-indexed results, behind the sizes in `header`.  Returns (bufs, f, i): f / i make further float64 /
+    int32 arrays"""
+    import torch
+    f = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
+    i = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
+    bufs = dict(header, x_k=f(rows, n), head_k=f(rows, 3, D), tail_k=f(rows, 3, D), slots_k=i(rows), costs_k=f(rows, 4),
+                last_k=f(rows, 4), nit_k=i(rows), nfev_k=i(rows), status_k=i(rows), x=f(B, n), costs=f(B, 4),
+                costs_last=f(B, 4), nit=i(B), nfev=i(B), status=i(B), solved=i(B))
+    return bufs, f, i
+
+
+RESULTS_K = ("costs_k", "last_k", "nit_k", "nfev_k", "status_k")      # a launch's five result arrays in the buffers, packed
+RESULTS = ("costs", "costs_last", "nit", "nfev", "status")            # ... and by request
+
+
 class MinJerkPlanner:
     """MI355X-backed stand-in for expert_planner.py:MinJerkPlanner"""
 
@@ -249,15 +356,14 @@ class MinJerkPlanner:
         x = np.stack([np.concatenate((np.reshape(_lib.as_f64(w), (nq,)), tau), axis=0) for w in wpts_list])
         x = np.ascontiguousarray(x, dtype=np.float64)
         self._sync_params()
-        c = self.ctx
-        costs = np.zeros((nb, 4)); last = np.zeros((nb, 4))
-        nit = np.zeros(nb, np.int32); nfev = np.zeros(nb, np.int32); st = np.zeros(nb, np.int32)
-        head = np.ascontiguousarray(np.broadcast_to(_lib.as_f64(self.head_state), (nb, 3, self.D)))
-        tail = np.ascontiguousarray(np.broadcast_to(_lib.as_f64(self.tail_state), (nb, 3, self.D)))
-        c.check(c.lib.neo_optimize_batch(c.h, self._scene, None, nb, self.M, self.D, _lib.ptr(x), _lib.ptr(head),
-                                         _lib.ptr(tail), _lib.ptr(costs), _lib.ptr(last), _lib.ptr(nit),
-                                         _lib.ptr(nfev), _lib.ptr(st)))
-        return x, costs, last, nit, nfev, st
+        head, tail = self._ends(nb)
+        res = _host_results(nb)
+        self.ctx.call("neo_optimize_batch", self._scene, None, nb, self.M, self.D, *_ptrs(x, head, tail, *res))
+        return (x, *res)
+
+    def _ends(self, nb=1):
+        """head and tail state as the ABI takes them: (nb, 3, D) float64, every row the planner's"""
+        return [np.ascontiguousarray(np.broadcast_to(_lib.as_f64(s), (nb, 3, self.D))) for s in (self.head_state, self.tail_state)]
 
     def _finish_plan_once(self, x, costs, last, nit, nfev, st):
         """what plan_once does with the optimiser's answer (:226-237): exceptions first, then the side effects"""
@@ -289,16 +395,10 @@ class MinJerkPlanner:
     # ------------------------------------------------------------ callbacks (:539-585)
     def _device_eval(self, x, want_coeffs=True):
         self._sync_params()
-        c = self.ctx
         xx = _lib.as_f64(x).reshape(1, -1)
-        n = xx.shape[1]
-        cost = np.zeros(1); costs = np.zeros((1, 4)); grad = np.zeros((1, n))
-        coeffs = np.zeros((1, 6 * self.M, self.D)); st = np.zeros(1, np.int32)
-        head = _lib.as_f64(self.head_state).reshape(1, 3, self.D)
-        tail = _lib.as_f64(self.tail_state).reshape(1, 3, self.D)
-        c.check(c.lib.neo_cost_grad_batch(c.h, self._scene, 1, self.M, self.D, _lib.ptr(xx), _lib.ptr(head),
-                                          _lib.ptr(tail), _lib.ptr(cost), _lib.ptr(costs), _lib.ptr(grad),
-                                          _lib.ptr(coeffs), _lib.ptr(st)))
+        head, tail = self._ends()
+        cost, costs, grad, coeffs, st = out = _eval_arrays(1, xx.shape[1], self.M, self.D)
+        self.ctx.call("neo_cost_grad_batch", self._scene, 1, self.M, self.D, *_ptrs(xx, head, tail, *out))
         if int(st[0]) == _lib.NEO_TRAJ_NUMERIC_RANGE:
             raise OverflowError("math range error")
         return cost[0], costs[0], grad[0], coeffs[0]
@@ -356,13 +456,12 @@ class MinJerkPlanner:
         x = _lib.as_f64(self._pack_x()).reshape(1, -1)
         state = np.zeros((1, max(K, 1), 3, self.D))
         cnt = np.zeros(1, np.int32)
-        head = _lib.as_f64(self.head_state).reshape(1, 3, self.D)
-        tail = _lib.as_f64(self.tail_state).reshape(1, 3, self.D)
+        head, tail = self._ends()
         self._sync_params()
         c = self.ctx
         if K > 0:
-            c.check(c.lib.neo_eval_traj_batch(c.h, 1, self.M, self.D, _lib.ptr(x), _lib.ptr(head), _lib.ptr(tail),
-                                              float(hz), K, _lib.ptr(state), _lib.ptr(cnt)))
+            c.call("neo_eval_traj_batch", 1, self.M, self.D, _lib.ptr(x), _lib.ptr(head), _lib.ptr(tail), float(hz), K,
+                   _lib.ptr(state), _lib.ptr(cnt))
         return state[0, :K]
 
     def get_full_state_cmd(self, hz=300):
@@ -373,15 +472,12 @@ class MinJerkPlanner:
         on the planner's map snapshot, sampled at `hz`: BatchPlanner.audit's dict for this one trajectory"""
         self.tau = self.map_T2tau(np.asarray(self.ts, dtype=np.float64))
         x = _lib.as_f64(self._pack_x()).reshape(1, -1)
-        head = _lib.as_f64(self.head_state).reshape(1, 3, self.D)
-        tail = _lib.as_f64(self.tail_state).reshape(1, 3, self.D)
+        head, tail = self._ends()
         self._sync_params()
-        c = self.ctx
-        audit = np.zeros((1, _lib.NEO_AUDIT_FIELDS)); count = np.zeros(1, np.int32); flags = np.zeros(1, np.int32)
-        c.check(c.lib.neo_audit_traj_batch(c.h, self._scene, None, 1, self.M, self.D, _lib.ptr(x), _lib.ptr(head),
-                                           _lib.ptr(tail), float(hz), None, _lib.ptr(audit), _lib.ptr(count),
-                                           _lib.ptr(flags)))
-        return _audit_result(audit, count, flags)
+        record = _audit_arrays(1)
+        self.ctx.call("neo_audit_traj_batch", self._scene, None, 1, self.M, self.D, _lib.ptr(x), _lib.ptr(head), _lib.ptr(tail),
+                      float(hz), None, *_ptrs(*record))
+        return _audit_result(*record)
 
     def get_pos_array(self):
         return self._states(10.0)[:, 0, :]       # np.arange(0, sum(ts), 0.1): 1/10.0 == 0.1
@@ -464,6 +560,14 @@ class BatchPlanner:
     def _sync(self):
         _push_params(self.ctx, self.cfg, self.sample_dtype, self.stale_T, self.flags)
 
+    def _start_ts(self, count):
+        """the start durations of `count` waypoints: init_T * [1.5, 1, ..., 1, 1.5] (:97-99).  Durations only: who maps them
+        to tau, and through which log, is the caller's business (pack_x / _plan_frac_tau: np.log; _batch_ts_tau: math.log)"""
+        ts = float(self.cfg.init_T) * np.ones((count + 1,))
+        ts[0] *= 1.5
+        ts[-1] *= 1.5
+        return ts
+
     def pack_x(self, int_wpts, ts):
         """int_wpts (B, D, M-1), ts (B, M) -> x (B, n) with tau = map_T2tau(ts) (:468-475)"""
         B = ts.shape[0]
@@ -478,17 +582,11 @@ class BatchPlanner:
 
     def cost_grad(self, map, x, head, tail, want_coeffs=False):
         self._sync()
-        c = self.ctx
-        x = _lib.as_f64(x); head = _lib.as_f64(head); tail = _lib.as_f64(tail)
-        B, n = x.shape
-        D = head.shape[2]
-        M = (n + D) // (D + 1)
-        cost = np.zeros(B); costs = np.zeros((B, 4)); grad = np.zeros((B, n)); st = np.zeros(B, np.int32)
-        coeffs = np.zeros((B, 6 * M, D)) if want_coeffs else None
-        c.check(c.lib.neo_cost_grad_batch(c.h, map.scene_id, B, M, D, _lib.ptr(x), _lib.ptr(head), _lib.ptr(tail),
-                                          _lib.ptr(cost), _lib.ptr(costs), _lib.ptr(grad), _lib.ptr(coeffs),
-                                          _lib.ptr(st)))
-        return dict(cost=cost, costs=costs, grad=grad, coeffs=coeffs, status=st)
+        x, head, tail = _f64(x, head, tail)
+        B, M, D, n = _shape(x, head)
+        out = _eval_arrays(B, n, M, D, want_coeffs)
+        self.ctx.call("neo_cost_grad_batch", map.scene_id, B, M, D, *_ptrs(x, head, tail, *out))
+        return dict(zip(("cost", "costs", "grad", "coeffs", "status"), out))
 
     def sampled_terms(self, map, coeffs, ts, order=None, io32=False):
         """add_sampled_cost + add_sampled_grad_CT (:392-466) for B trajectories: coeffs (B, 6M, D), ts (B, M).
@@ -501,17 +599,13 @@ class BatchPlanner:
         B, M = ts.shape
         D = np.shape(coeffs)[2]
         perm = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
-        c.check(c.lib.neo_sampled_terms_dispatch_order(c.h, _lib.ptr(perm), 0, 0 if perm is None else B))
+        c.call("neo_sampled_terms_dispatch_order", _lib.ptr(perm), 0, 0 if perm is None else B)
         costs2 = np.zeros((B, 2))
-        if io32:
-            coeffs = np.ascontiguousarray(coeffs, dtype=np.float32)
-            gC = np.zeros((B, 6 * M, D), np.float32); gT = np.zeros((B, M), np.float32)
-            fn = c.lib.neo_sampled_terms_batch_f32
-        else:
-            coeffs = _lib.as_f64(coeffs)
-            gC = np.zeros((B, 6 * M, D)); gT = np.zeros((B, M))
-            fn = c.lib.neo_sampled_terms_batch
-        c.check(fn(c.h, map.scene_id, B, M, D, _lib.ptr(coeffs), _lib.ptr(ts), _lib.ptr(costs2), _lib.ptr(gC), _lib.ptr(gT)))
+        io = np.float32 if io32 else np.float64
+        coeffs = np.ascontiguousarray(coeffs, dtype=io)
+        gC = np.zeros((B, 6 * M, D), io); gT = np.zeros((B, M), io)
+        c.call("neo_sampled_terms_batch_f32" if io32 else "neo_sampled_terms_batch", map.scene_id, B, M, D,
+               *_ptrs(coeffs, ts, costs2, gC, gT))
         return dict(costs2=costs2, grad_C=gC, grad_T=gT)
 
     def optimize(self, map, x0, head, tail, scene_ids=None, order=True):
@@ -520,24 +614,17 @@ class BatchPlanner:
         first (`expected_effort_order`); results are in the caller's order either way."""
         self._sync()
         c = self.ctx
-        x = _lib.as_f64(x0).copy(); head = _lib.as_f64(head); tail = _lib.as_f64(tail)
-        B, n = x.shape
-        D = head.shape[2]
-        M = (n + D) // (D + 1)
+        x = _lib.as_f64(x0).copy()
+        head, tail = _f64(head, tail)
+        B, M, D, _ = _shape(x, head)
         perm = None
         if order and B > 1024:
             _, ts0 = self.unpack_x(x, M, D)
             perm = self.expected_effort_order(head, tail, ts0)
-        c.check(c.lib.neo_optimize_dispatch_order_host(c.h, _lib.ptr(perm), 0 if perm is None else B))
-        costs = np.zeros((B, 4)); last = np.zeros((B, 4))
-        nit = np.zeros(B, np.int32); nfev = np.zeros(B, np.int32); st = np.zeros(B, np.int32)
-        sid = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32)
-        c.check(c.lib.neo_optimize_batch(c.h, map.scene_id, _lib.ptr(sid), B, M, D, _lib.ptr(x), _lib.ptr(head),
-                                         _lib.ptr(tail), _lib.ptr(costs), _lib.ptr(last), _lib.ptr(nit),
-                                         _lib.ptr(nfev), _lib.ptr(st)))
-        w = np.asarray(self.cfg.weights, dtype=np.float64)
-        return dict(x=x, costs=costs, costs_last=last, nit=nit, nfev=nfev, status=st & 0xff,
-                    collision=(st & _lib.NEO_TRAJ_FLAG_COLLISION) != 0, final_cost=(costs * w).sum(axis=1))
+        c.call("neo_optimize_dispatch_order_host", _lib.ptr(perm), 0 if perm is None else B)
+        res = _host_results(B)
+        c.call("neo_optimize_batch", map.scene_id, _lib.ptr(_scene_ids(scene_ids)), B, M, D, *_ptrs(x, head, tail, *res))
+        return _result_dict(x, res, self.cfg.weights)
 
     def audit(self, map, x, head, tail, hz=10.0, scene_ids=None, weights=None):
         """the reference's flight metric (traj_planner_node.py:333-363, get_weighted_metric) of B trajectories x (B, n)
@@ -546,32 +633,22 @@ class BatchPlanner:
         record fields by name (path_length, feasibility, collision, weighted, min_clearance, t_min_clearance, max_speed,
         max_acc, t_first_unsafe, duration), count, flags (NEO_AUDIT_FLAG_*) and the masks unsafe / metric_fail"""
         self._sync()
-        c = self.ctx
-        x = _lib.as_f64(x); head = _lib.as_f64(head); tail = _lib.as_f64(tail)
-        B, n = x.shape
-        D = head.shape[2]
-        M = (n + D) // (D + 1)
-        audit = np.zeros((B, _lib.NEO_AUDIT_FIELDS)); count = np.zeros(B, np.int32); flags = np.zeros(B, np.int32)
-        sid = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32)
-        w = _audit_weights(weights)
-        c.check(c.lib.neo_audit_traj_batch(c.h, map.scene_id, _lib.ptr(sid), B, M, D, _lib.ptr(x), _lib.ptr(head),
-                                           _lib.ptr(tail), float(hz), _lib.ptr(w),
-                                           _lib.ptr(audit), _lib.ptr(count), _lib.ptr(flags)))
-        return _audit_result(audit, count, flags)
+        x, head, tail = _f64(x, head, tail)
+        B, M, D, _ = _shape(x, head)
+        record = _audit_arrays(B)
+        self.ctx.call("neo_audit_traj_batch", map.scene_id, _lib.ptr(_scene_ids(scene_ids)), B, M, D, _lib.ptr(x), _lib.ptr(head),
+                      _lib.ptr(tail), float(hz), _lib.ptr(_audit_weights(weights)), *_ptrs(*record))
+        return _audit_result(*record)
 
     def audit_dev(self, map, x, head, tail, audit, count, flags, hz=10.0, slots=None, weights=None):
         """`audit` on device tensors, asynchronous on the context's stream: x (B, n), head / tail (B, 3, D) float64,
         results into audit (B, NEO_AUDIT_FIELDS) float64, count and flags (B,) int32 -- e.g. straight on optimize_dev's
         results.  `slots`: optional int32 device tensor of map-table slots, as in optimize_dev"""
         self._sync()
-        B, n = x.shape
-        D = head.shape[2]
-        M = (n + D) // (D + 1)
-        c = self.ctx
+        B, M, D, _ = _shape(x, head)
         p = _lib.dev_ptr
-        w = _audit_weights(weights)
-        c.check(c.lib.neo_audit_traj_batch_dev(c.h, map.scene_id, p(slots), B, M, D, p(x), p(head), p(tail), float(hz),
-                                               _lib.ptr(w), p(audit), p(count), p(flags)))
+        self.ctx.call("neo_audit_traj_batch_dev", map.scene_id, p(slots), B, M, D, p(x), p(head), p(tail), float(hz),
+                      _lib.ptr(_audit_weights(weights)), p(audit), p(count), p(flags))
 
     def geo_init(self, map, start, target, scene_ids=None, max_expansions=0, path_cap=0):
         """the reference's `geo` warm start (geo_planner.py:19-35) for B requests on 2-D maps: AstarPlanner.plan from
@@ -588,15 +665,10 @@ class BatchPlanner:
         key_pts = np.zeros((B, 4, 2)); cost = np.zeros(B)
         plen = np.zeros(B, np.int32); nexp = np.zeros(B, np.int32); flags = np.zeros(B, np.int32)
         paths = np.zeros((B, path_cap, 2)) if path_cap > 0 else None
-        sid = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32)
-        c.check(c.lib.neo_geo_search_batch(c.h, map.scene_id, _lib.ptr(sid), B, _lib.ptr(start), _lib.ptr(target),
-                                           int(max_expansions), int(path_cap), _lib.ptr(key_pts), _lib.ptr(paths),
-                                           _lib.ptr(plen), _lib.ptr(cost), _lib.ptr(nexp), _lib.ptr(flags)))
-        ts = np.empty((B, 3))
-        ts[:] = float(self.cfg.init_T)
-        ts[:, 0] *= 1.5
-        ts[:, -1] *= 1.5
-        out = dict(int_wpts=key_pts[:, 1:3, :].transpose(0, 2, 1).copy(), ts=ts, key_pts=key_pts, path_len=plen,
+        c.call("neo_geo_search_batch", map.scene_id, _lib.ptr(_scene_ids(scene_ids)), B, _lib.ptr(start), _lib.ptr(target),
+               int(max_expansions), int(path_cap), *_ptrs(key_pts, paths, plen, cost, nexp, flags))
+        out = dict(int_wpts=key_pts[:, 1:3, :].transpose(0, 2, 1).copy(), ts=np.tile(self._start_ts(2), (B, 1)),
+                   key_pts=key_pts, path_len=plen,
                    path_cost=cost, expansions=nexp, flags=flags, no_path=(flags & _lib.NEO_GEO_FLAG_NO_PATH) != 0,
                    capped=(flags & _lib.NEO_GEO_FLAG_CAPPED) != 0)
         if paths is not None:
@@ -612,9 +684,8 @@ class BatchPlanner:
         p = _lib.dev_ptr
         B = start.shape[0]
         cap = 0 if paths is None else paths.shape[1]
-        c.check(c.lib.neo_geo_search_batch_dev(c.h, map.scene_id, p(slots), B, p(start), p(target), int(max_expansions),
-                                               cap, p(key_pts), p(paths), p(path_len), p(path_cost), p(expansions),
-                                               p(flags)))
+        c.call("neo_geo_search_batch_dev", map.scene_id, p(slots), B, p(start), p(target), int(max_expansions), cap,
+               p(key_pts), p(paths), p(path_len), p(path_cost), p(expansions), p(flags))
 
     def geo_prune(self, map, paths, path_len=None, scene_ids=None):
         """GeoPlanner.prune_path_nodes (geo_planner.py:61-101) of B given paths: paths (B, L, 2) (the first path_len[b]
@@ -624,9 +695,8 @@ class BatchPlanner:
         B, L = paths.shape[0], paths.shape[1]
         plen = np.full(B, L, np.int32) if path_len is None else np.ascontiguousarray(path_len, dtype=np.int32)
         key_pts = np.zeros((B, 4, 2))
-        sid = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32)
-        c.check(c.lib.neo_geo_prune_batch(c.h, map.scene_id, _lib.ptr(sid), B, _lib.ptr(paths), _lib.ptr(plen), L,
-                                          _lib.ptr(key_pts)))
+        c.call("neo_geo_prune_batch", map.scene_id, _lib.ptr(_scene_ids(scene_ids)), B, _lib.ptr(paths), _lib.ptr(plen), L,
+               _lib.ptr(key_pts))
         return key_pts
 
     def geo_plan(self, map, head, tail, scene_ids=None, max_expansions=0, **kw):
@@ -634,7 +704,7 @@ class BatchPlanner:
         (geo_planner.py:19-35) for a batch of 2-D requests head / tail (B, 2, 2).  Retries re-seed from straight lines,
         as the reference's warm_start_plan does after a geo start.  `plan`'s dict plus the search's results under
         "geo" """
-        head = _lib.as_f64(head); tail = _lib.as_f64(tail)
+        head, tail = _f64(head, tail)
         g = self.geo_init(map, head[:, 0, :2], tail[:, 0, :2], scene_ids=scene_ids, max_expansions=max_expansions)
         out = self.plan(map, head, tail, int_wpts=g["int_wpts"], ts=g["ts"], scene_ids=scene_ids, **kw)
         out["geo"] = g
@@ -650,17 +720,14 @@ class BatchPlanner:
         import torch
         self._sync()
         c = self.ctx
-        B, n = x.shape
-        D = head.shape[2]
-        M = (n + D) // (D + 1)
+        B, M, D, _ = _shape(x, head)
         pp = _lib.dev_ptr
         sizes = []
         subset, resume = None, 0
         for _ in range(max_launches):
-            c.check(c.lib.neo_optimize_batch_budget_dev(
-                c.h, map.scene_id, B, M, D, pp(x0), pp(x), pp(head), pp(tail), pp(costs), pp(costs_last), pp(nit), pp(nfev),
-                pp(status), pp(state), int(eval_budget), None if subset is None else pp(subset),
-                0 if subset is None else int(subset.numel()), resume))
+            c.call("neo_optimize_batch_budget_dev", map.scene_id, B, M, D,
+                   *_dev_ptrs(x0, x, head, tail, costs, costs_last, nit, nfev, status, state), int(eval_budget), pp(subset),
+                   0 if subset is None else int(subset.numel()), resume)
             sizes.append(_lib.launch_count(subset, B))
             c.synchronize()
             # (the statuses decide the next launch: this is the host round trip a budget costs)
@@ -675,24 +742,15 @@ class BatchPlanner:
         import torch
         c = self.ctx
         dev = torch.device("cuda", c.device)
-        x0 = _lib.as_f64(x0); head = _lib.as_f64(head); tail = _lib.as_f64(tail)
-        B, n = x0.shape
-        D = head.shape[2]
-        M = (n + D) // (D + 1)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        d_x0, d_h, d_t = t(x0), t(head), t(tail)
+        x0, head, tail = _f64(x0, head, tail)
+        B, M, D, _ = _shape(x0, head)
+        d_x0, d_h, d_t = _upload(dev, x0, head, tail)
         d_x = torch.empty_like(d_x0)
-        costs = torch.zeros(B, 4, dtype=torch.float64, device=dev); last = torch.zeros_like(costs)
-        nit = torch.zeros(B, dtype=torch.int32, device=dev); nfev = torch.zeros_like(nit); st = torch.zeros_like(nit)
+        res = _dev_results(B, dev)
         state = torch.empty(B * int(c.lib.neo_optimize_state_bytes(M, D)), dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)        # (the context has its own stream: the buffers above are ready before it starts)
-        sizes = self.optimize_budgeted_dev(map, d_x0, d_x, d_h, d_t, costs, last, nit, nfev, st, state, eval_budget)
-        stn = st.cpu().numpy()
-        w = np.asarray(self.cfg.weights, dtype=np.float64)
-        cn_ = costs.cpu().numpy()
-        return dict(x=d_x.cpu().numpy(), costs=cn_, costs_last=last.cpu().numpy(), nit=nit.cpu().numpy(), nfev=nfev.cpu().numpy(),
-                    status=stn & 0xff, collision=(stn & _lib.NEO_TRAJ_FLAG_COLLISION) != 0, final_cost=(cn_ * w).sum(axis=1),
-                    launch_sizes=sizes)
+        _torch_done(dev)
+        sizes = self.optimize_budgeted_dev(map, d_x0, d_x, d_h, d_t, *res, state, eval_budget)
+        return dict(_result_dict(d_x.cpu().numpy(), [r.cpu().numpy() for r in res], self.cfg.weights), launch_sizes=sizes)
 
     def optimize_progressive(self, map, x0, head, tail, shares=(0.8,)):
         """`optimize` as a generator that hands results over as they finish (round 6, neo_optimize_progress_counter): ONE plain
@@ -705,19 +763,16 @@ class BatchPlanner:
         c = self.ctx
         self._sync()
         dev = torch.device("cuda", c.device)
-        x0 = _lib.as_f64(x0); head = _lib.as_f64(head); tail = _lib.as_f64(tail)
-        B, n = x0.shape
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        d_x0, d_h, d_t = t(x0), t(head), t(tail)
-        bufs = dict(x=torch.empty_like(d_x0), costs=torch.zeros(B, 4, dtype=torch.float64, device=dev),
-                    costs_last=torch.zeros(B, 4, dtype=torch.float64, device=dev), nit=torch.zeros(B, dtype=torch.int32, device=dev),
-                    nfev=torch.zeros(B, dtype=torch.int32, device=dev), status=torch.full((B,), -1, dtype=torch.int32, device=dev))
+        x0, head, tail = _f64(x0, head, tail)
+        B = x0.shape[0]
+        d_x0, d_h, d_t = _upload(dev, x0, head, tail)
+        bufs = dict(zip(RESULTS, _dev_results(B, dev)), x=torch.empty_like(d_x0))
+        bufs["status"].fill_(-1)        # (no trajectory has finished)
         host = {k: torch.empty(tuple(v.shape), dtype=v.dtype).pin_memory() for k, v in bufs.items()}
         counter = torch.zeros(1, dtype=torch.int32, device=dev)
         h_cnt = torch.zeros(1, dtype=torch.int32).pin_memory()
         side = torch.cuda.Stream(device=dev)
-        torch.cuda.synchronize(dev)        # (the context has its own stream: the buffers above are ready before it starts)
-        w = np.asarray(self.cfg.weights, dtype=np.float64)
+        _torch_done(dev)
         seen = np.zeros(B, dtype=bool)
 
         def snapshot():
@@ -728,14 +783,10 @@ class BatchPlanner:
             st = host["status"].numpy()
             new = np.flatnonzero((st != -1) & ~seen)
             seen[new] = True
-            cn_ = host["costs"].numpy()[new]
-            return new, dict(x=host["x"].numpy()[new].copy(), costs=cn_.copy(), costs_last=host["costs_last"].numpy()[new].copy(),
-                             nit=host["nit"].numpy()[new].copy(), nfev=host["nfev"].numpy()[new].copy(), status=st[new] & 0xff,
-                             collision=(st[new] & _lib.NEO_TRAJ_FLAG_COLLISION) != 0, final_cost=(cn_ * w).sum(axis=1))
+            return new, _result_dict(host["x"].numpy()[new], [host[k].numpy()[new] for k in RESULTS], self.cfg.weights)
 
         try:
-            self.optimize_dev(map, bufs["x"], d_h, d_t, bufs["costs"], bufs["costs_last"], bufs["nit"], bufs["nfev"],
-                              bufs["status"], x0=d_x0, progress=counter)
+            self.optimize_dev(map, bufs["x"], d_h, d_t, *(bufs[k] for k in RESULTS), x0=d_x0, progress=counter)
             for share in sorted(float(s_) for s_ in shares):
                 need = min(B, int(np.ceil(share * B)))
                 while True:
@@ -753,7 +804,7 @@ class BatchPlanner:
                 yield new, res
         finally:
             c.synchronize()
-            c.check(c.lib.neo_optimize_progress_counter(c.h, None))
+            c.call("neo_optimize_progress_counter", None)
 
     def init_guess(self, head, tail, count, rng=None, noise=0.0):
         """generate_init_variables (:82-101) for a batch: `count` waypoints on the straight line from start to target,
@@ -765,10 +816,7 @@ class BatchPlanner:
         wp = start[:, :, None] + (target - start)[:, :, None] * f                     # (B, D, count)
         if noise > 0.0:
             wp = wp + (rng if rng is not None else np.random.default_rng()).normal(0.0, noise, wp.shape)
-        ts = np.full((head.shape[0], count + 1), float(self.cfg.init_T))
-        ts[:, 0] *= 1.5
-        ts[:, -1] *= 1.5
-        return wp, ts
+        return wp, np.tile(self._start_ts(count), (head.shape[0], 1))
 
     @staticmethod
     def retry_noise(seed, stream_ids, attempt, D, count):
@@ -808,7 +856,7 @@ class BatchPlanner:
         if (int_wpts is None) != (ts is None):
             raise ValueError("BatchPlanner.plan: give both int_wpts and ts, or neither")
         counter = counter_rng.check_jitter(jitter, "BatchPlanner.plan")
-        head = _lib.as_f64(head); tail = _lib.as_f64(tail)
+        head, tail = _f64(head, tail)
         B, D = head.shape[0], head.shape[2]
         if counter:         # (before any device use)
             if seed is not None:
@@ -825,18 +873,14 @@ class BatchPlanner:
             raise _lib.NeoError("BatchPlanner.plan: requests %s name a scene without a map (NEO_TRAJ_BAD_SCENE)"
                                 % np.flatnonzero(out["status"] == _lib.NEO_TRAJ_BAD_SCENE)[:8].tolist())
         out["attempts"] = np.ones(B, dtype=np.int32)
-        if stream_ids is None:
-            stream_ids = np.arange(B)
-        stream_ids = np.asarray(stream_ids).reshape(-1)
-        if stream_ids.shape[0] != B:
-            raise ValueError("BatchPlanner.plan: stream_ids needs one id per request")
+        stream_ids = _stream_ids(stream_ids, B, "BatchPlanner.plan")
         # (an attempt that overflowed raises before the reference counts it: expert_planner.py:226-232)
         counted = lambda r: np.where(r["status"] >= _lib.NEO_TRAJ_NUMERIC_RANGE, 0, r["nit"]).astype(np.int64)
         out["nit_total"] = counted(out)
         failed = lambda r: ((r["status"] > _lib.NEO_TRAJ_MAXITER) & (r["status"] != _lib.NEO_TRAJ_BAD_SCENE)) | r["collision"]
         todo = np.flatnonzero(failed(out))
         if seed is None:
-            seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
+            seed = _draw_seed(rng)
         launches = [B]
         for attempt in range(1, max_attempts):
             if todo.size == 0:
@@ -924,17 +968,15 @@ class BatchPlanner:
             raise ValueError("BatchPlanner.plan: int_wpts / ts fix their own shape: not with waypoints='adaptive'")
         self._adaptive_args(max_waypoints, "BatchPlanner.plan")
         counter = counter_rng.check_jitter(jitter, "BatchPlanner.plan")
-        head = _lib.as_f64(head); tail = _lib.as_f64(tail)
+        head, tail = _f64(head, tail)
         B, D = head.shape[0], head.shape[2]
         W = int(max_waypoints)
         counts, clamped = self.adaptive_counts(head, tail, W)
         if counter and seed is not None:
             seed = counter_rng.check_seed(seed, "BatchPlanner.plan")
         if seed is None:        # (one seed for every group)
-            seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
-        stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
-        if stream_ids.shape[0] != B:
-            raise ValueError("BatchPlanner.plan: stream_ids needs one id per request")
+            seed = _draw_seed(rng)
+        stream_ids = _stream_ids(stream_ids, B, "BatchPlanner.plan")
         order = np.argsort(counts, kind="stable")
         out = dict(x=np.full((B, D * W + W + 1), np.nan), counts=counts, clamped=clamped, max_waypoints=W)
         launches, by_group = [], {}
@@ -962,10 +1004,7 @@ class BatchPlanner:
         """what neo_plan_guess takes from the host: init_guess's fractions f[k] = k / (count + 1) and the tau of its
         durations -- through pack_x's own expression (np.log: math.log may differ in the last bit)"""
         frac = np.arange(1, count + 1) / (count + 1)
-        ts = np.full((1, count + 1), float(self.cfg.init_T))
-        ts[:, 0] *= 1.5
-        ts[:, -1] *= 1.5
-        return frac, np.ascontiguousarray(self.pack_x(np.zeros((1, 1, count)), ts)[0, count:])
+        return frac, np.ascontiguousarray(self.pack_x(np.zeros((1, 1, count)), self._start_ts(count)[None])[0, count:])
 
     def warm_guess_dev(self, head, wpts_local, ts_carry, x0, subset=None):
         """the reference's `warmstart` planner on resident tensors (neo_fleet_warm_guess_dev, asynchronous on the
@@ -978,9 +1017,9 @@ class BatchPlanner:
         B, M = int(ts_carry.shape[0]), int(ts_carry.shape[1])
         if tuple(head.shape) != (B, 3, 2) or tuple(wpts_local.shape) != (B, 2, M - 1) or tuple(x0.shape) != (B, 3 * M - 2):
             raise ValueError("BatchPlanner.warm_guess_dev: head (B, 3, 2), wpts_local (B, 2, M - 1), ts_carry (B, M), x0 (B, 3 M - 2)")
-        c, p = self.ctx, _lib.dev_ptr
-        c.check(c.lib.neo_fleet_warm_guess_dev(c.h, B, p(subset), _lib.launch_count(subset, B), M,
-                                               p(head), p(wpts_local), p(ts_carry), p(x0)))
+        p = _lib.dev_ptr
+        self.ctx.call("neo_fleet_warm_guess_dev", B, p(subset), _lib.launch_count(subset, B), M, p(head), p(wpts_local), p(ts_carry),
+                      p(x0))
         return x0
 
     def warm_carry_dev(self, x, head, solved, status, attempts, wpts_local, ts_carry, subset=None):
@@ -993,11 +1032,10 @@ class BatchPlanner:
         B, M = int(ts_carry.shape[0]), int(ts_carry.shape[1])
         if tuple(head.shape) != (B, 3, 2) or tuple(wpts_local.shape) != (B, 2, M - 1) or tuple(x.shape) != (B, 3 * M - 2):
             raise ValueError("BatchPlanner.warm_carry_dev: x (B, 3 M - 2), head (B, 3, 2), wpts_local (B, 2, M - 1), ts_carry (B, M)")
-        c, p = self.ctx, _lib.dev_ptr
-        init_ts = self._batch_ts_tau(M - 1)[0]      # a re-seeded attempt's start durations: init_T * [1.5, 1, ..., 1, 1.5]
-        c.check(c.lib.neo_fleet_warm_carry_dev(c.h, B, p(subset), _lib.launch_count(subset, B), M,
-                                               p(x), p(head), p(solved), p(status), p(attempts), _lib.ptr(init_ts),
-                                               p(wpts_local), p(ts_carry)))
+        p = _lib.dev_ptr
+        init_ts = self._batch_ts_tau(M - 1)[0]      # a re-seeded attempt's start durations
+        self.ctx.call("neo_fleet_warm_carry_dev", B, p(subset), _lib.launch_count(subset, B), M, p(x), p(head), p(solved), p(status),
+                      p(attempts), _lib.ptr(init_ts), p(wpts_local), p(ts_carry))
 
     def plan_buffers(self, B, device, D=2, waypoints=None, max_waypoints=63):
         """the resident arrays of `plan_dev` for up to B requests of dimension D with `waypoints` waypoints (None: the
@@ -1013,14 +1051,10 @@ class BatchPlanner:
             self._adaptive_args(max_waypoints, "BatchPlanner.plan_buffers")
             waypoints = max_waypoints
         count = int(waypoints if waypoints is not None else self.cfg.init_wpts_num)
-        M, n = count + 1, D * count + count + 1
-        f = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
-        i = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
         R = max(B, 1)
-        bufs = dict(B=B, D=D, M=M, x_k=f(R, n), head_k=f(R, 3, D), tail_k=f(R, 3, D), slots_k=i(R), noise=f(R, D, count),
-                    costs_k=f(R, 4), last_k=f(R, 4), nit_k=i(R), nfev_k=i(R), status_k=i(R), todo=i(2, R), counts=i(2),
-                    x=f(B, n), costs=f(B, 4), costs_last=f(B, 4), nit=i(B), nfev=i(B), status=i(B), attempts=i(B),
-                    nit_total=torch.zeros(B, dtype=torch.int64, device=device), solved=i(B), launch_sizes=[])
+        bufs, f, i = _work_buffers(device, dict(B=B, D=D, M=count + 1), R, B, D * count + count + 1, D)
+        bufs.update(noise=f(R, D, count), todo=i(2, R), counts=i(2), attempts=i(B),
+                    nit_total=torch.zeros(B, dtype=torch.int64, device=device), launch_sizes=[])
         if B > 1024:        # (launches this large are dispatched longest-expected first, as `optimize` does)
             nbytes = int(_lib.load().neo_effort_order_scratch_bytes(B))
             bufs.update(order=i(B), order_scratch=f(nbytes // 8 + 1))
@@ -1043,9 +1077,7 @@ class BatchPlanner:
                 raise ValueError("BatchPlanner.plan_dev: a device stream_ids is a contiguous int32 tensor, one id per request")
             ids_dev = stream_ids
         else:
-            stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
-            if stream_ids.shape[0] != B:
-                raise ValueError("BatchPlanner.plan_dev: stream_ids needs one id per request")
+            stream_ids = _stream_ids(stream_ids, B, "BatchPlanner.plan_dev")
         if counter:
             if seed is not None:
                 seed = counter_rng.check_seed(seed, "BatchPlanner.plan_dev")
@@ -1089,9 +1121,9 @@ class BatchPlanner:
         else:
             count = int(waypoints if waypoints is not None else self.cfg.init_wpts_num)
             if x0 is not None:
-                n0 = x0.shape[1]
-                count = (n0 + D) // (D + 1) - 1
-                if x0.shape[0] != B or count < 1 or D * count + count + 1 != n0 or (waypoints is not None and int(waypoints) != count):
+                B0, M0, _, n0 = _shape(x0, head)
+                count = M0 - 1
+                if B0 != B or count < 1 or D * count + count + 1 != n0 or (waypoints is not None and int(waypoints) != count):
                     raise ValueError("BatchPlanner.plan_dev: x0 (B, D * waypoints + waypoints + 1)")
         return self._plan_chain(map, head, tail, bufs, count, seg, x0, slots, subset, x, solved, max_attempts, seed, rng,
                                 stream_ids, _guessed, jitter)
@@ -1134,12 +1166,13 @@ class BatchPlanner:
         dev = head.device
         if bufs is None:
             bufs = self.plan_buffers(B, dev, D=D, waypoints="adaptive" if adaptive else W, max_waypoints=W)
-            torch.cuda.synchronize(dev)     # (the context has its own stream: the buffers are ready before it starts)
+            _torch_done(dev)
         d = bufs
         if seed is None:
-            seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2 ** 62))
+            seed = _draw_seed(rng)
         p = _lib.dev_ptr
-        rows = lambda t, first, per=1: p(t, first * per)    # an array from row `first` on (no tensor is made for it)
+        # an array from row `first` on (no tensor is made for it)
+        rows = lambda t, first: None if t is None else p(t, first * t.stride(0))
         if counter and ids_dev is None and max_attempts > 1:
             ids_dev = torch.from_numpy(stream_ids).to(dev)      # (a blocking copy: there before the context's stream starts)
         out_x, out_solved = (x if x is not None else d["x"]), (solved if solved is not None else d["solved"])
@@ -1153,10 +1186,9 @@ class BatchPlanner:
             if lens[0] == 0:       # (an empty list: nothing to count, nothing to wait for)
                 d.update(launch_sizes=[], group_launch_sizes={}, host_waits=dict(grouping=0, attempts=0))
                 return bufs
-            c.check(c.lib.neo_adaptive_count_dev(c.h, B, p(subset), lens[0], D, p(head), p(tail), seg, W, p(d["counts"]),
-                                                 p(d["clamped"])))
-            c.check(c.lib.neo_adaptive_bucket_dev(c.h, B, p(subset), lens[0], p(d["counts"]), p(d["group_order"]), p(table),
-                                                  p(table[2 * G + 2:])))
+            c.call("neo_adaptive_count_dev", B, p(subset), lens[0], D, p(head), p(tail), seg, W, p(d["counts"]), p(d["clamped"]))
+            c.call("neo_adaptive_bucket_dev", B, p(subset), lens[0], p(d["counts"]), p(d["group_order"]), p(table),
+                   p(table[2 * G + 2:]))
             c.synchronize()
             begin = table[:G + 1].tolist()
             seg_begin = np.asarray(begin[:G], dtype=np.int32)
@@ -1170,7 +1202,7 @@ class BatchPlanner:
         counts_at, bad_at = p(words), p(words[-1:])
         launches, by_group, waits, frac_tau = [], {}, 0, {}
         bad_scene = 0
-        c.check(c.lib.neo_optimize_progress_counter(c.h, None))
+        c.call("neo_optimize_progress_counter", None)
         try:
             for attempt in range(max_attempts):
                 if attempt > 0:
@@ -1189,52 +1221,47 @@ class BatchPlanner:
                         ids = lists[o:o + P].cpu().numpy()
                         noise = self.retry_noise(seed, stream_ids[ids], attempt, D, g)
                         d["noise"].view(-1)[o * D * W:o * D * W + P * D * g].copy_(torch.from_numpy(noise.reshape(-1)))
-                    torch.cuda.synchronize(dev)
+                    _torch_done(dev)
                 pending = d["todo"][attempt % 2]
                 for k, (g, o, P) in enumerate(groups):
                     M = g + 1
                     sub = rows(lists, o)
-                    x_k, head_k, tail_k = rows(d["x_k"], o, n_max), rows(d["head_k"], o, 3 * D), rows(d["tail_k"], o, 3 * D)
+                    x_k, head_k, tail_k, noise_k, *res_k = (rows(d[k], o) for k in ("x_k", "head_k", "tail_k", "noise") + RESULTS_K)
                     slots_k = rows(d["slots_k"], o) if slots is not None else None
-                    noise_k = rows(d["noise"], o, D * W)
-                    res_k = (rows(d["costs_k"], o, 4), rows(d["last_k"], o, 4), rows(d["nit_k"], o), rows(d["nfev_k"], o),
-                             rows(d["status_k"], o))
                     if g not in frac_tau:
                         frac_tau[g] = self._plan_frac_tau(g)
                     frac, tau = frac_tau[g]
                     if attempt > 0 and counter:
-                        c.check(c.lib.neo_plan_jitter_dev(c.h, B, sub, P, M, D, seed, attempt, p(ids_dev), noise_k))
+                        c.call("neo_plan_jitter_dev", B, sub, P, M, D, seed, attempt, p(ids_dev), noise_k)
                     if not (attempt == 0 and guessed):
-                        c.check(c.lib.neo_plan_guess_dev(c.h, B, sub, P, M, D, p(head), p(tail), p(slots),
-                                                         p(x0) if attempt == 0 else None, noise_k if attempt > 0 else None,
-                                                         _lib.ptr(frac), _lib.ptr(tau), x_k, head_k, tail_k, slots_k))
+                        c.call("neo_plan_guess_dev", B, sub, P, M, D, p(head), p(tail), p(slots), p(x0) if attempt == 0 else None,
+                               noise_k if attempt > 0 else None, _lib.ptr(frac), _lib.ptr(tau), x_k, head_k, tail_k, slots_k)
                     if P > 0:
                         if P > 1024:
                             order = rows(d["order"], o)
-                            c.check(c.lib.neo_effort_order_dev(c.h, P, M, D, x_k, head_k, tail_k, p(d["order_scratch"]), order))
-                            c.check(c.lib.neo_optimize_dispatch_order(c.h, order, P))
+                            c.call("neo_effort_order_dev", P, M, D, x_k, head_k, tail_k, p(d["order_scratch"]), order)
+                            c.call("neo_optimize_dispatch_order", order, P)
                         else:
-                            c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))
-                        c.check(c.lib.neo_optimize_batch_from_dev(c.h, map.scene_id, slots_k, P, M, D, x_k, x_k, head_k, tail_k,
-                                                                  *res_k))
-                    merged = (x_k, *res_k, p(out_x), p(d["costs"]), p(d["costs_last"]), p(d["nit"]), p(d["nfev"]), p(d["status"]),
-                              p(d["attempts"]), p(d["nit_total"]), p(out_solved), rows(pending, o))
+                            c.call("neo_optimize_dispatch_order", None, 0)
+                        c.call("neo_optimize_batch_from_dev", map.scene_id, slots_k, P, M, D, x_k, x_k, head_k, tail_k, *res_k)
+                    merged = (x_k, *res_k, p(out_x), *(p(d[k]) for k in RESULTS), p(d["attempts"]), p(d["nit_total"]), p(out_solved),
+                              rows(pending, o))
                     if adaptive:
-                        c.check(c.lib.neo_adaptive_merge_dev(c.h, B, sub, P, M, D, n_max, int(attempt == 0),
-                                                             int(attempt == 0 and k == 0), *merged, bad_at))
+                        c.call("neo_adaptive_merge_dev", B, sub, P, M, D, n_max, int(attempt == 0), int(attempt == 0 and k == 0),
+                               *merged, bad_at)
                     else:
-                        c.check(c.lib.neo_plan_merge_dev(c.h, B, sub, P, M, D, int(attempt == 0), *merged, counts_at, bad_at))
+                        c.call("neo_plan_merge_dev", B, sub, P, M, D, int(attempt == 0), *merged, counts_at, bad_at)
                     by_group.setdefault(g, []).append(P)
                 if adaptive:
-                    c.check(c.lib.neo_adaptive_compact_dev(c.h, _lib.ptr(seg_begin), _lib.ptr(np.asarray(lens, dtype=np.int32)),
-                                                           p(pending), counts_at))
+                    c.call("neo_adaptive_compact_dev", _lib.ptr(seg_begin), _lib.ptr(np.asarray(lens, dtype=np.int32)),
+                           p(pending), counts_at)
                 launches.append(sum(P for _, _, P in groups))
             else:
                 c.synchronize()     # (every attempt has run: the last one's wait)
                 waits += 1
                 bad_scene = int(words[-1].item())
         finally:
-            c.check(c.lib.neo_optimize_dispatch_order(c.h, None, 0))     # (the order is in bufs: no launch after this reads it)
+            c.call("neo_optimize_dispatch_order", None, 0)     # (the order is in bufs: no launch after this reads it)
         if bad_scene:
             raise _lib.NeoError("BatchPlanner.plan_dev: a request names a scene without a map (NEO_TRAJ_BAD_SCENE)")
         d["launch_sizes"] = launches
@@ -1260,9 +1287,7 @@ class BatchPlanner:
     def _batch_ts_tau(self, count):
         """the shared durations init_T * [1.5, 1, ..., 1, 1.5] and their tau, element by element through math.log as
         MinJerkPlanner.map_T2tau computes it (:468-475)"""
-        ts = float(self.cfg.init_T) * np.ones((count + 1,))
-        ts[0] *= 1.5
-        ts[-1] *= 1.5
+        ts = self._start_ts(count)
         tau = np.array([-math.log((self.cfg.T_max - self.cfg.T_min) / (t - self.cfg.T_min) - 1) for t in ts])
         return ts, tau
 
@@ -1271,7 +1296,7 @@ class BatchPlanner:
         is the straight line shifted by lateral_offsets[k] along lateral_dir[0] -- and the shared ts (M,).  Request by
         request the values are MinJerkPlanner.batch_generate_init_variables', bit for bit (what neo_batch_candidates
         computes on the device).  start == target: candidate 0 finite, the shifted ones NaN, as in the reference."""
-        head = _lib.as_f64(head); tail = _lib.as_f64(tail)
+        head, tail = _f64(head, tail)
         B, D = head.shape[0], head.shape[2]
         if D != 2:
             raise ValueError("BatchPlanner.batch_init_guess: the reference's lateral candidates are 2-D (D = 2)")
@@ -1292,15 +1317,10 @@ class BatchPlanner:
     def batch_buffers(self, B, K, device):
         """the resident arrays of `batch_plan_dev` for up to B requests of K candidates: the packed work arrays of the
         B * K optimiser runs and the request-indexed results (torch tensors, zeroed)"""
-        import torch
         count = int(self.cfg.init_wpts_num)
-        n, R = 2 * count + count + 1, B * K
-        f = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
-        i = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
-        return dict(B=B, K=K, x_k=f(R, n), head_k=f(R, 3, 2), tail_k=f(R, 3, 2), slots_k=i(R), costs_k=f(R, 4), last_k=f(R, 4),
-                    nit_k=i(R), nfev_k=i(R), status_k=i(R), chosen=i(B), candidate_cost=f(B, K), solved=i(B), x=f(B, n),
-                    costs=f(B, 4), costs_last=f(B, 4), nit=i(B), nfev=i(B), status=i(B), nit_total=i(B), opt_runs=i(B),
-                    fallback=i(max(B, 1)), n_fallback=i(1))
+        bufs, f, i = _work_buffers(device, dict(B=B, K=K), B * K, B, 2 * count + count + 1, 2)
+        bufs.update(chosen=i(B), candidate_cost=f(B, K), nit_total=i(B), opt_runs=i(B), fallback=i(max(B, 1)), n_fallback=i(1))
+        return bufs
 
     def batch_plan_dev(self, map, head, tail, bufs=None, K=None, lateral_offsets=None, slots=None, subset=None, x=None,
                        solved=None):
@@ -1330,23 +1350,18 @@ class BatchPlanner:
         P = _lib.launch_count(subset, B)
         p = _lib.dev_ptr
         d = bufs
-        c.check(c.lib.neo_batch_candidates_dev(c.h, B, p(subset), P, M, D, K, p(head), p(tail), p(slots), _lib.ptr(tau),
-                                               _lib.ptr(off), p(d["x_k"]), p(d["head_k"]), p(d["tail_k"]),
-                                               p(d["slots_k"]) if slots is not None else None))
+        x_k, head_k, tail_k, *res_k = (p(d[k]) for k in ("x_k", "head_k", "tail_k") + RESULTS_K)
+        slots_k = p(d["slots_k"]) if slots is not None else None
+        c.call("neo_batch_candidates_dev", B, p(subset), P, M, D, K, p(head), p(tail), p(slots), _lib.ptr(tau), _lib.ptr(off),
+               x_k, head_k, tail_k, slots_k)
         if P > 0:
-            c.check(c.lib.neo_optimize_dispatch_order_host(c.h, None, 0))
-            c.check(c.lib.neo_optimize_progress_counter(c.h, None))
-            c.check(c.lib.neo_optimize_batch_from_dev(c.h, map.scene_id, p(d["slots_k"]) if slots is not None else None,
-                                                      P * K, M, D, p(d["x_k"]), p(d["x_k"]), p(d["head_k"]), p(d["tail_k"]),
-                                                      p(d["costs_k"]), p(d["last_k"]), p(d["nit_k"]), p(d["nfev_k"]),
-                                                      p(d["status_k"])))
+            c.call("neo_optimize_dispatch_order_host", None, 0)
+            c.call("neo_optimize_progress_counter", None)
+            c.call("neo_optimize_batch_from_dev", map.scene_id, slots_k, P * K, M, D, x_k, x_k, head_k, tail_k, *res_k)
         w = _lib.as_f64(self.cfg.weights).reshape(4)
-        c.check(c.lib.neo_batch_select_dev(c.h, B, p(subset), P, M, D, K, p(d["x_k"]), p(d["costs_k"]), p(d["last_k"]),
-                                           p(d["nit_k"]), p(d["nfev_k"]), p(d["status_k"]), _lib.ptr(w), p(d["chosen"]),
-                                           p(d["candidate_cost"]), p(solved if solved is not None else d["solved"]),
-                                           p(x if x is not None else d["x"]), p(d["costs"]), p(d["costs_last"]), p(d["nit"]),
-                                           p(d["nfev"]), p(d["status"]), p(d["nit_total"]), p(d["opt_runs"]),
-                                           p(d["fallback"]), p(d["n_fallback"])))
+        c.call("neo_batch_select_dev", B, p(subset), P, M, D, K, x_k, *res_k, _lib.ptr(w), p(d["chosen"]), p(d["candidate_cost"]),
+               p(solved if solved is not None else d["solved"]), p(x if x is not None else d["x"]), *(p(d[k]) for k in RESULTS),
+               p(d["nit_total"]), p(d["opt_runs"]), p(d["fallback"]), p(d["n_fallback"]))
         return bufs
 
     def batch_fallback(self, bufs):
@@ -1370,46 +1385,40 @@ class BatchPlanner:
         to iter_num and opt_running_times over the candidates, an overflowed run not counted, plus the fallback's
         nit_total and attempts) and solved (B,).  A scene without a map among the requests raises NeoError, as in `plan`."""
         import torch
-        head = _lib.as_f64(head); tail = _lib.as_f64(tail)
+        head, tail = _f64(head, tail)
         if head.ndim != 3 or head.shape[2] != 2 or head.shape != tail.shape:
             raise ValueError("BatchPlanner.batch_plan: head and tail (B, 3, 2): the reference's lateral candidates are 2-D")
         B = head.shape[0]
         off = self._batch_offsets(K, lateral_offsets)
         K = off.shape[0]
-        stream_ids = np.arange(B) if stream_ids is None else np.asarray(stream_ids).reshape(-1)
-        if stream_ids.shape[0] != B:
-            raise ValueError("BatchPlanner.batch_plan: stream_ids needs one id per request")
-        sid = None if scene_ids is None else np.ascontiguousarray(scene_ids, dtype=np.int32).reshape(-1)
+        stream_ids = _stream_ids(stream_ids, B, "BatchPlanner.batch_plan")
+        sid = None if scene_ids is None else _scene_ids(scene_ids).reshape(-1)
         if sid is not None and sid.shape[0] != B:
             raise ValueError("BatchPlanner.batch_plan: scene_ids needs one id per request")
         count = int(self.cfg.init_wpts_num)
         n = 2 * count + count + 1
         w = np.asarray(self.cfg.weights, dtype=np.float64)
         if B == 0:
-            z = lambda *shape, dt=np.float64: np.zeros(shape, dtype=dt)
-            return dict(x=z(0, n), costs=z(0, 4), costs_last=z(0, 4), nit=z(0, dt=np.int32), nfev=z(0, dt=np.int32),
-                        status=z(0, dt=np.int32), collision=z(0, dt=bool), chosen=z(0, dt=np.int32), candidate_cost=z(0, K),
-                        final_cost=z(0), nit_total=z(0, dt=np.int64), attempts=z(0, dt=np.int32), solved=z(0, dt=bool))
+            return dict(_result_dict(np.zeros((0, n)), _host_results(0)), chosen=np.zeros(0, np.int32),
+                        candidate_cost=np.zeros((0, K)), final_cost=np.zeros(0), nit_total=np.zeros(0, np.int64),
+                        attempts=np.zeros(0, np.int32), solved=np.zeros(0, bool))
         c = self.ctx
         dev = torch.device("cuda", c.device)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         slots = None
         if sid is not None:
             slot_of = {int(s): int(c.lib.neo_scene_slot(c.h, int(s))) for s in np.unique(sid)}
             if min(slot_of.values()) < 0:
                 raise _lib.NeoError("BatchPlanner.batch_plan: requests name a scene without a map")
-            slots = t(np.array([slot_of[int(s)] for s in sid], dtype=np.int32))
-        d_head, d_tail = t(head), t(tail)
+            slots, = _upload(dev, np.array([slot_of[int(s)] for s in sid], dtype=np.int32))
+        d_head, d_tail = _upload(dev, head, tail)
         bufs = self.batch_buffers(B, K, dev)
-        torch.cuda.synchronize(dev)        # (the context has its own stream: the buffers above are ready before it starts)
+        _torch_done(dev)
         self.batch_plan_dev(map, d_head, d_tail, bufs, lateral_offsets=off, slots=slots)
         fb = self.batch_fallback(bufs)
-        h = {k: bufs[k].cpu().numpy() for k in ("x", "costs", "costs_last", "nit", "nfev", "status", "chosen",
-                                                "candidate_cost", "solved", "nit_total", "opt_runs")}
-        st = h["status"]
-        out = dict(x=h["x"], costs=h["costs"], costs_last=h["costs_last"], nit=h["nit"], nfev=h["nfev"], status=st & 0xff,
-                   collision=(st & _lib.NEO_TRAJ_FLAG_COLLISION) != 0, chosen=h["chosen"], candidate_cost=h["candidate_cost"],
-                   nit_total=h["nit_total"].astype(np.int64), attempts=h["opt_runs"].copy(), solved=h["solved"] != 0)
+        h = {k: bufs[k].cpu().numpy() for k in ("x", *RESULTS, "chosen", "candidate_cost", "solved", "nit_total", "opt_runs")}
+        out = _result_dict(h["x"], [h[k] for k in RESULTS])      # (without weights: final_cost is this method's own, below)
+        out.update(chosen=h["chosen"], candidate_cost=h["candidate_cost"], nit_total=h["nit_total"].astype(np.int64),
+                   attempts=h["opt_runs"].copy(), solved=h["solved"] != 0)
         if fb.size:
             cand0 = self.batch_init_guess(head[fb], tail[fb], K=1)[0][:, 0]
             ts = np.tile(self._batch_ts_tau(count)[0], (fb.size, 1))
@@ -1419,7 +1428,7 @@ class BatchPlanner:
                 out[k][fb] = r[k]
             out["attempts"][fb] += r["attempts"]
             out["nit_total"][fb] += r["nit_total"]
-        out["final_cost"] = (out["costs_last"] * w).sum(axis=1)
+        out["final_cost"] = (out["costs_last"] * w).sum(axis=1)      # costs_LAST, the reference's (:233-234); optimize: costs
         return out
 
     def expected_effort_order(self, head, tail, ts):
@@ -1440,13 +1449,11 @@ class BatchPlanner:
         import torch
         self._sync()
         c = self.ctx
-        B, n = x0.shape
-        D = head.shape[2]
-        M = (n + D) // (D + 1)
+        B, M, D, _ = _shape(x0, head)
         scratch = torch.empty(int(c.lib.neo_effort_order_scratch_bytes(B)) // 8 + 1, dtype=torch.float64, device=x0.device)   # (keys first)
         order = torch.empty(B, dtype=torch.int32, device=x0.device)
         pp = _lib.dev_ptr
-        c.check(c.lib.neo_effort_order_dev(c.h, B, M, D, pp(x0), pp(head), pp(tail), pp(scratch), pp(order)))
+        c.call("neo_effort_order_dev", B, M, D, pp(x0), pp(head), pp(tail), pp(scratch), pp(order))
         return order, scratch[:B]
 
     @staticmethod
@@ -1500,12 +1507,9 @@ class BatchPlanner:
         `progress`: optional int32 device tensor (one element, zeroed by the caller) that counts the trajectories as they
         finish (neo_optimize_progress_counter): poll it through a copy on another stream to use the finished results while
         the launch's long runs are still going"""
-        B, n = x.shape
-        D = head.shape[2]
-        M = (n + D) // (D + 1)
+        B, M, D, _ = _shape(x, head)
         c = self.ctx
         p = _lib.dev_ptr
-        c.check(c.lib.neo_optimize_progress_counter(c.h, p(progress)))
-        c.check(c.lib.neo_optimize_batch_from_dev(c.h, map.scene_id, p(slots), B, M, D, p(x0 if x0 is not None else x),
-                                                  p(x), p(head), p(tail), p(costs), p(costs_last), p(nit), p(nfev),
-                                                  p(status)))
+        c.call("neo_optimize_progress_counter", p(progress))
+        c.call("neo_optimize_batch_from_dev", map.scene_id, p(slots), B, M, D, p(x0 if x0 is not None else x), p(x), p(head),
+               p(tail), *_dev_ptrs(costs, costs_last, nit, nfev, status))

@@ -102,11 +102,10 @@ class DemoRecorder:
         stream; every argument a device tensor indexed by mission"""
         d, c = self._alloc(), self.ctx
         p = _lib.dev_ptr
-        c.check(c.lib.neo_record_commit_dev(
-            c.h, int(B), p(sub), int(sub.numel()) if sub is not None else 0, self.M, p(x), p(head), p(tail), p(solved), p(pose),
-            p(self.cur_vel), p(self.staging), self.width, self.height, p(mission_ids), int(tick), int(round_), self.capacity,
-            p(d["motion"]), p(d["wpts_local"]), p(d["tau"]), p(d["pose"]), p(d["meta"]), p(d["images"]), p(self.row_of),
-            p(d["n_rows"]), p(d["dropped"])))
+        c.call("neo_record_commit_dev", int(B), p(sub), int(sub.numel()) if sub is not None else 0, self.M, p(x), p(head),
+               p(tail), p(solved), p(pose), p(self.cur_vel), p(self.staging), self.width, self.height, p(mission_ids),
+               int(tick), int(round_), self.capacity, p(d["motion"]), p(d["wpts_local"]), p(d["tau"]), p(d["pose"]),
+               p(d["meta"]), p(d["images"]), p(self.row_of), p(d["n_rows"]), p(d["dropped"]))
 
     # ------------------------------------------------------------ what was recorded
     @property

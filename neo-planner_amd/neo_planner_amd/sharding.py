@@ -29,7 +29,7 @@ def pack_results(x, costs, weights, ctx=None, out=None):
         from . import _lib
         w4 = (ctypes.c_double * 4)(*[float(v) for v in weights])
         pp = _lib.dev_ptr
-        ctx.check(ctx.lib.neo_pack_results_dev(ctx.h, B, n, pp(x), pp(costs), ctypes.cast(w4, ctypes.c_void_p), pp(out)))
+        ctx.call("neo_pack_results_dev", B, n, pp(x), pp(costs), ctypes.cast(w4, ctypes.c_void_p), pp(out))
         return out
     out[:, :n] = x
     out[:, n] = (costs * weights).sum(dim=1)

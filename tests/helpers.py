@@ -46,3 +46,21 @@ def reference_jump(d, M, rel_noise=4e-6, trials=12):
         jump = max(jump, abs(pl.get_cost(xp) - c0) / abs(c0))
         gjump = max(gjump, float(np.max(np.abs(pl.get_grad(xp) - g0)) / np.max(np.abs(g0))))
     return float(jump), float(gjump)
+
+
+def _code_lines(source):
+    """lines of code: no blank lines, comments or docstrings"""
+    import io
+    import tokenize
+    lines, prev = set(), tokenize.INDENT
+    for tok in tokenize.generate_tokens(io.StringIO(source).readline):
+        if tok.type in (tokenize.COMMENT, tokenize.NL, tokenize.NEWLINE, tokenize.INDENT, tokenize.DEDENT, tokenize.ENDMARKER):
+            if tok.type in (tokenize.NEWLINE, tokenize.INDENT, tokenize.DEDENT):
+                prev = tok.type
+            continue
+        if tok.type == tokenize.STRING and prev in (tokenize.NEWLINE, tokenize.INDENT, tokenize.DEDENT) and \
+                tok.line.strip().startswith(('"""', "'''", 'r"""')):
+            continue      # a docstring: a string that is a statement of its own
+        prev = tok.type
+        lines.update(range(tok.start[0], tok.end[0] + 1))
+    return len(lines)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+from helpers import _code_lines
 
 import neo_planner_amd as npa
 from neo_planner_amd import _lib, build, fleet
@@ -111,24 +112,6 @@ MESSAGES = (
     "FleetReplanLoop: a scene id without a map",
     "FleetReplanLoop.x: no flight yet",
 )
-
-
-def _code_lines(source):
-    """lines of code: no blank lines, comments or docstrings"""
-    import io
-    import tokenize
-    lines, prev = set(), tokenize.INDENT
-    for tok in tokenize.generate_tokens(io.StringIO(source).readline):
-        if tok.type in (tokenize.COMMENT, tokenize.NL, tokenize.NEWLINE, tokenize.INDENT, tokenize.DEDENT, tokenize.ENDMARKER):
-            if tok.type in (tokenize.NEWLINE, tokenize.INDENT, tokenize.DEDENT):
-                prev = tok.type
-            continue
-        if tok.type == tokenize.STRING and prev in (tokenize.NEWLINE, tokenize.INDENT, tokenize.DEDENT) and \
-                tok.line.strip().startswith(('"""', "'''", 'r"""')):
-            continue      # a docstring: a string that is a statement of its own
-        prev = tok.type
-        lines.update(range(tok.start[0], tok.end[0] + 1))
-    return len(lines)
 
 
 def test_the_loop_keeps_its_structure():
