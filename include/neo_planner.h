@@ -587,6 +587,89 @@ int neo_fleet_track_audit_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_
                               int n_vertices, const int32_t *route_begin, const double *speed, const int32_t *closed,
                               double radius, double *track, int32_t *count, int32_t *flags);
 
+/* ---- fleet campaigns (ros_node/manager_node.py:153-193: the next goal as soon as one is reached or given up) --------
+ * A mission flies a sequence of goals; each goal is a LEG (csrc/neo_legs.hpp; neo_planner_amd.goal_sequences.GoalSequences
+ * is the NumPy model of the goal lists, bit for bit).  When a leg ends the caller uploads outcome[b] for the closing
+ * missions and runs, on the same subset: neo_fleet_leg_close_dev, neo_fleet_audit_batch_dev with close's n_flown (a leg's
+ * rows start at row 0 of the mission's command array), neo_fleet_leg_open_dev.  One lane per mission, fp64, everything
+ * indexed by MISSION; `subset` as for the other fleet calls; same bits whatever the subset, its order and the launch.
+ * outcome[B], the one input a leg's end adds, stands next to B in both calls; subset and n_subset follow it.
+ * The goal lists, struct neo_leg_sequences -- DEVICE pointers for the _dev calls, HOST pointers for neo_fleet_leg_goal:
+ *   kind NEO_LEGS_TABLE   goals[n_goals][2] and seq_begin[B + 1], laid out as the route table is: mission b's goals are
+ *                         goals[seq_begin[b] .. seq_begin[b + 1]), 1 to NEO_FLEET_LEGS_MAX of them;
+ *   kind NEO_LEGS_FLAP    the reference's set_random_goal: `legs` goals a mission, goal k = (x_pair[k & 1],
+ *                         y_scale * (u - y_shift)), u the 52-bit uniform of csrc/neo_counter_rng.hpp with the key `seed`
+ *                         and the counter (mission_ids[b], k, 0, 3 << 24), words 0 and 1 (mission_ids: int32 [B], ids in
+ *                         0 .. 2^31 - 1; NULL: b itself).
+ * NEO_ERR_INVALID before any launch, with a neo_last_error message: a NULL required buffer, B < 0, a bad subset size,
+ * cap < 1, max_legs outside 1 .. NEO_FLEET_LEGS_MAX, a threshold that is not finite and >= 0, a kind that is none of the
+ * two, a table with fewer goals than missions (some mission would have none) or a flap with legs outside
+ * 1 .. NEO_FLEET_LEGS_MAX, x_pair, y_scale or y_shift not finite; neo_fleet_leg_goal, which reads the table on the host,
+ * also for any mission with fewer than 1 or more than NEO_FLEET_LEGS_MAX goals.  (On the device a mission whose list is
+ * not one has no next goal.) */
+#define NEO_FLEET_LEGS_MAX 64
+#define NEO_LEGS_TABLE 0
+#define NEO_LEGS_FLAP 1
+typedef struct neo_leg_sequences {
+  int32_t kind;               /* NEO_LEGS_TABLE or NEO_LEGS_FLAP */
+  int32_t legs;               /* flap: goals a mission */
+  int32_t n_goals;            /* table */
+  const double *goals;        /* table */
+  const int32_t *seq_begin;   /* table */
+  uint64_t seed;              /* flap */
+  const int32_t *mission_ids; /* flap, or NULL */
+  double x_pair[2];           /* flap: x of the even and of the odd legs */
+  double y_scale, y_shift;    /* flap */
+} neo_leg_sequences;
+/* how a leg ended: outcome[b] */
+#define NEO_LEG_LANDED 1    /* the plan near the goal was spliced */
+#define NEO_LEG_ABANDONED 2 /* all 11 targets of a tick failed */
+#define NEO_LEG_TIMEOUT 3   /* the leg ran past its time limit (max_target_find_time) */
+#define NEO_LEG_STUCK 4     /* NEO_FLEET_FLAG_CMD_FULL or NEO_FLEET_FLAG_SPLICE_FAILED was raised */
+#define NEO_LEG_OPEN 5      /* the run ended first: logged, and nothing is opened */
+/* a row of leg_log[B][max_legs][NEO_LEG_FIELDS]; the integers are stored as doubles */
+#define NEO_LEG_FIELDS 21
+enum {
+  NEO_LEG_GOAL_X = 0,
+  NEO_LEG_GOAL_Y = 1,
+  NEO_LEG_START_X = 2,      /* where the leg began: leg_start[b] */
+  NEO_LEG_START_Y = 3,
+  NEO_LEG_OUTCOME = 4,      /* NEO_LEG_* */
+  NEO_LEG_N_FLOWN = 5,
+  NEO_LEG_FINAL_DIST = 6,
+  NEO_LEG_FLAGS = 7,        /* the mission's NEO_FLEET_FLAG_* of this leg, NEO_FLEET_FLAG_ABANDONED with that outcome */
+  NEO_LEG_COUNT = 8,        /* the audit's count ... */
+  NEO_LEG_AUDIT_FLAGS = 9,  /* ... and flags */
+  NEO_LEG_AUDIT = 10,       /* the NEO_AUDIT_FIELDS values of the audit record, in its order */
+  NEO_LEG_SUCCESS = 20      /* 1: LANDED, final_dist < threshold, no METRIC_FAIL | NONFINITE, flags == 0 */
+};
+/* what a leg was: n_flown[b] = cmd_len[b] for NEO_LEG_LANDED, else min(cmd_index[b] + 1, cmd_len[b]), clamped to 0 .. cap;
+ * leg_end[B][2][2] = position and velocity of row n_flown - 1, head[b][0 .. 1] when n_flown == 0 (a leg that never got a
+ * plan); final_dist[b] = sqrt(dx * dx + dy * dy) from there to goal[b], each operation rounded on its own
+ * (np.linalg.norm's bits), inf when n_flown == 0.  outcome[B] is read for the launched missions only. */
+int neo_fleet_leg_close_dev(neo_ctx *ctx, int B, const int32_t *outcome, const int32_t *subset, int n_subset,
+                            const double *cmd, int cap, const int32_t *cmd_len, const int32_t *cmd_index,
+                            const double *head, const double *goal, int32_t *n_flown, double *leg_end,
+                            double *final_dist);
+/* logs the leg and starts the next.  With k = leg[b] (outside 0 .. max_legs - 1: the mission is skipped): row k of
+ * leg_log from goal[b], leg_start[b], outcome, close's n_flown / leg_end / final_dist, flags[b], the audit's count /
+ * audit_flags / audit[B][NEO_AUDIT_FIELDS] and `threshold` (target_reach_threshold); leg[b] = k + 1; then, unless the
+ * outcome is NEO_LEG_OPEN, if the mission has a goal k + 1 and k + 1 < max_legs: that goal into goal[b], cur_pos[b] =
+ * leg_start[b] = the end position, head[b] = [end position, end velocity, 0], cmd_len = cmd_index = future_index = 0,
+ * flags[b] = 0 (first_plan plans from drone_state, :491-504; init_mission zeroes des_state_index).  Otherwise nothing
+ * more changes: the last leg's command array stays.  The caller writes leg_start of leg 0 (head[b][0] is the look-ahead
+ * state once a leg has flown a tick, so a leg's start has a row of its own). */
+int neo_fleet_leg_open_dev(neo_ctx *ctx, int B, const int32_t *outcome, const int32_t *subset, int n_subset,
+                           const neo_leg_sequences *seq, int max_legs, double threshold, const int32_t *n_flown,
+                           const double *leg_end, const double *final_dist, const int32_t *count,
+                           const int32_t *audit_flags, const double *audit, int32_t *leg, double *leg_log,
+                           double *leg_start, double *goal, double *cur_pos, double *head, int32_t *cmd_len,
+                           int32_t *cmd_index, int32_t *future_index, int32_t *flags);
+/* the goal model alone, HOST pointers (seq's too), evaluated on the device: goal[n][2] = goal leg_of[p] of mission
+ * mission[p] and exists[p] = 1; NaN and 0 where the mission has no such goal or is outside 0 .. B - 1. */
+int neo_fleet_leg_goal(neo_ctx *ctx, const neo_leg_sequences *seq, int B, int n, const int32_t *mission,
+                       const int32_t *leg_of, double *goal, int32_t *exists);
+
 /* ---- fleet record mode (traj_planner/record_planner.py:13-72, :152-185) ----------------
  * What the reference's `record` planner saves of every successful plan, for the missions of a fleet: one row of a
  * RESIDENT dataset of `capacity` rows, caller-owned DEVICE buffers:

@@ -1,5 +1,5 @@
 // neo_abi_fleet.hip -- C ABI of libneo_planner_hip.so (include/neo_planner.h), the unit of the closed-loop missions: the
-// depth camera, onboard integration, the fleet replan loop and its goal routes, record mode and the learned warm start.
+// depth camera, onboard integration, the fleet replan loop, its goal routes and its campaigns, record mode and the learned warm start.
 // Argument checks here, the skeletons in neo_abi_util.hpp, the kernels behind the launchers of neo_disp_depth.hip,
 // neo_disp_onboard.hip, neo_disp_fleet.hip, neo_disp_record.hip and neo_disp_init.hip.
 #include "neo_abi_util.hpp"
@@ -510,6 +510,98 @@ int neo_fleet_track_audit(neo_ctx *c, int B, const int32_t *subset, int n_subset
     return neo_fleet_track_audit_dev(c, B, st.dev(fsub), n_subset, st.dev(fc), cap, st.dev(fnf), stride, cmd_hz, st.dev(fv),
                                      n_vertices, st.dev(fb), st.dev(fs), st.dev(fcl), radius, st.dev(ft), st.dev(fcnt),
                                      st.dev(ffl));
+  });
+}
+
+// ---- fleet campaigns (ros_node/manager_node.py:153-193; kernels: neo_legs.hpp)
+// what can be said of the goal lists without reading them (the _dev forms hold device pointers)
+static int fleet_legs_seq_check(neo_ctx *c, const char *who, const neo_leg_sequences *seq, int B) {
+  const std::string w(who);
+  if (!seq) return fail_locked(c, NEO_ERR_INVALID, (w + ": null buffer").c_str());
+  if (seq->kind == NEO_LEGS_TABLE) {
+    if (int rc = null_check(c, (w + ": null buffer").c_str(), {seq->goals, seq->seq_begin})) return rc;
+    if (seq->n_goals < B)
+      return fail_locked(c, NEO_ERR_INVALID, (w + ": the table has fewer goals than missions: every mission needs at least 1").c_str());
+  } else if (seq->kind == NEO_LEGS_FLAP) {
+    if (seq->legs < 1 || seq->legs > NEO_FLEET_LEGS_MAX)
+      return fail_locked(c, NEO_ERR_INVALID, (w + ": a flap campaign has 1 .. NEO_FLEET_LEGS_MAX legs").c_str());
+    if (!std::isfinite(seq->x_pair[0]) || !std::isfinite(seq->x_pair[1]) || !std::isfinite(seq->y_scale) ||
+        !std::isfinite(seq->y_shift))
+      return fail_locked(c, NEO_ERR_INVALID, (w + ": x_pair, y_scale and y_shift must be finite").c_str());
+  } else {
+    return fail_locked(c, NEO_ERR_INVALID, (w + ": kind must be NEO_LEGS_TABLE or NEO_LEGS_FLAP").c_str());
+  }
+  return NEO_OK;
+}
+
+int neo_fleet_leg_close_dev(neo_ctx *c, int B, const int32_t *outcome, const int32_t *subset, int n_subset, const double *cmd,
+                            int cap, const int32_t *cmd_len, const int32_t *cmd_index, const double *head, const double *goal,
+                            int32_t *n_flown, double *leg_end, double *final_dist) {
+  int rc = list_check(c, "fleet leg close", B, 0, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  rc = null_check(c, "fleet leg close: null buffer", {outcome, cmd, cmd_len, cmd_index, head, goal, n_flown, leg_end, final_dist});
+  if (rc) return rc;
+  if (cap < 1) return fail_locked(c, NEO_ERR_INVALID, "fleet leg close: cap must be >= 1");
+  return list_launch(c, B, subset, n_subset, [&](const LaunchList &list) {
+    return fleet_leg_close(c, list, {outcome, cmd, cap, cmd_len, cmd_index, head, goal, n_flown, leg_end, final_dist});
+  });
+}
+
+int neo_fleet_leg_open_dev(neo_ctx *c, int B, const int32_t *outcome, const int32_t *subset, int n_subset,
+                           const neo_leg_sequences *seq, int max_legs, double threshold, const int32_t *n_flown, const double *leg_end,
+                           const double *final_dist, const int32_t *count, const int32_t *audit_flags, const double *audit,
+                           int32_t *leg, double *leg_log, double *leg_start, double *goal, double *cur_pos, double *head,
+                           int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index, int32_t *flags) {
+  int rc = list_check(c, "fleet leg open", B, 0, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  rc = null_check(c, "fleet leg open: null buffer", {outcome, n_flown, leg_end, final_dist, count, audit_flags, audit, leg, leg_log,
+                                                     leg_start, goal, cur_pos, head, cmd_len, cmd_index, future_index, flags});
+  if (rc) return rc;
+  if (!std::isfinite(threshold) || !(threshold >= 0.0))
+    return fail_locked(c, NEO_ERR_INVALID, "fleet leg open: the threshold must be finite and >= 0");
+  if ((rc = fleet_legs_seq_check(c, "fleet leg open", seq, B))) return rc;
+  if (max_legs < 1 || max_legs > NEO_FLEET_LEGS_MAX)
+    return fail_locked(c, NEO_ERR_INVALID, "fleet leg open: max_legs must be in 1 .. NEO_FLEET_LEGS_MAX");
+  return list_launch(c, B, subset, n_subset, [&](const LaunchList &list) {
+    return fleet_leg_open(c, list, *seq, {max_legs, threshold, outcome, n_flown, leg_end, final_dist, count, audit_flags, audit,
+                                          leg, leg_log, leg_start, goal, cur_pos, head, cmd_len, cmd_index, future_index, flags});
+  });
+}
+
+int neo_fleet_leg_goal(neo_ctx *c, const neo_leg_sequences *seq, int B, int n, const int32_t *mission, const int32_t *leg_of,
+                       double *goal, int32_t *exists) {
+  if (!c) return NEO_ERR_INVALID;
+  if (B < 0 || n < 0) return fail_locked(c, NEO_ERR_INVALID, "fleet leg goal: B and n must be >= 0");
+  int rc = fleet_legs_seq_check(c, "fleet leg goal", seq, B);
+  if (rc) return rc;
+  if ((rc = null_check(c, "fleet leg goal: null buffer", {mission, leg_of, goal, exists}))) return rc;
+  const bool table = seq->kind == NEO_LEGS_TABLE;
+  if (table) {  // what the device forms cannot read on the host
+    if (seq->seq_begin[0] != 0 || seq->seq_begin[B] != seq->n_goals)
+      return fail_locked(c, NEO_ERR_INVALID, "fleet leg goal: seq_begin must run from 0 to n_goals");
+    for (int b = 0; b < B; ++b) {
+      const long long k = (long long)seq->seq_begin[b + 1] - (long long)seq->seq_begin[b];
+      if (k < 1 || k > NEO_FLEET_LEGS_MAX)
+        return fail_locked(c, NEO_ERR_INVALID, "fleet leg goal: every mission needs 1 .. NEO_FLEET_LEGS_MAX goals");
+    }
+  }
+  if (n == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);  // scratch buffers stay ours until the copies back are done
+  hipSetDevice(c->device);
+  const size_t bs = (size_t)B, ns = (size_t)n;
+  HostStage st(c, kStagedUpTo);
+  const auto fg = st.in(table ? seq->goals : nullptr, table ? (size_t)seq->n_goals * 2 : 0, 2);
+  const auto fb = st.in(table ? seq->seq_begin : nullptr, table ? bs + 1 : 0, 2);
+  const auto fi = st.in_optional(table ? nullptr : seq->mission_ids, bs);
+  const auto fm = st.in(mission, ns), fl = st.in(leg_of, ns);
+  const auto fo = st.out(goal, ns * 2);
+  const auto fe = st.out(exists, ns);
+  return st.run([&] {
+    neo_leg_sequences dv = *seq;
+    dv.goals = st.dev(fg);
+    dv.seq_begin = st.dev(fb);
+    dv.mission_ids = st.dev(fi);
+    return launched(c, fleet_leg_goal(c, dv, B, n, st.dev(fm), st.dev(fl), st.dev(fo), st.dev(fe)));
   });
 }
 

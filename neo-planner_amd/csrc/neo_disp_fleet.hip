@@ -1,9 +1,10 @@
-// neo_disp_fleet.hip -- the fleet kernels (neo_fleet.hpp; goal routes: neo_track.hpp): local targets, tracking and look-ahead, the splice of a new
+// neo_disp_fleet.hip -- the fleet kernels (neo_fleet.hpp; goal routes: neo_track.hpp; campaigns: neo_legs.hpp): local targets, tracking and look-ahead, the splice of a new
 // plan into the resident command array and the flight metric of what was flown (ros_node/traj_planner_node.py:333-363,
 // :450-488, :527-537, :574-578) for B missions.  2-D reference map, D = 2: one instantiation each.
 #include "neo_host.hpp"
 #include "neo_fleet.hpp"
 #include "neo_track.hpp"
+#include "neo_legs.hpp"
 
 namespace neo {
 
@@ -79,6 +80,29 @@ int fleet_hold(neo_ctx *c, const LaunchList &l, const FleetCmd &m, int step, int
 int fleet_track_audit(neo_ctx *c, const LaunchList &l, const FleetRoutes &r, const FleetTrackArgs &a) {
   hipLaunchKernelGGL(fleet_track_audit_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.cmd, a.cap, a.n_flown, a.stride,
                      a.hz, r.vertices, r.n_vertices, r.route_begin, r.speed, r.closed, a.radius, a.track, a.count, a.flags);
+  return NEO_OK;
+}
+
+static LegSequences leg_sequences(const neo_leg_sequences &s) {
+  return {s.kind, s.legs, s.goals, s.n_goals, s.seq_begin, (unsigned long long)s.seed, s.mission_ids,
+          {s.x_pair[0], s.x_pair[1]}, s.y_scale, s.y_shift};
+}
+
+int fleet_leg_close(neo_ctx *c, const LaunchList &l, const FleetLegCloseArgs &a) {
+  hipLaunchKernelGGL(fleet_leg_close_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l, a.outcome, a.cmd, a.cap,
+                     a.cmd_len, a.cmd_index, a.head, a.goal, a.n_flown, a.leg_end, a.final_dist);
+  return NEO_OK;
+}
+
+int fleet_leg_open(neo_ctx *c, const LaunchList &l, const neo_leg_sequences &seq, const FleetLegOpenArgs &a) {
+  hipLaunchKernelGGL(fleet_leg_open_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l, leg_sequences(seq), a);
+  return NEO_OK;
+}
+
+int fleet_leg_goal(neo_ctx *c, const neo_leg_sequences &seq, int B, int n, const int *mission, const int *leg_of,
+                   double *goal, int *exists) {
+  hipLaunchKernelGGL(fleet_leg_goal_kernel, lanes_grid(n), dim3(kFleetThreads), 0, c->stream, leg_sequences(seq), B, n,
+                     mission, leg_of, goal, exists);
   return NEO_OK;
 }
 

@@ -281,6 +281,34 @@ int fleet_goal(neo_ctx *c, const LaunchList &l, const FleetRoutes &r, double t, 
 // rows appended to a command array that ends before cmd_index + step + 1 (m.future_index is not used)
 int fleet_hold(neo_ctx *c, const LaunchList &l, const FleetCmd &m, int step, int *flags);
 int fleet_track_audit(neo_ctx *c, const LaunchList &l, const FleetRoutes &r, const FleetTrackArgs &a);
+// campaigns (kernels in neo_legs.hpp): what a leg was, then its row of the log and the next leg's start
+struct FleetLegCloseArgs {
+  const int *outcome;                  // [B]: NEO_LEG_*
+  const double *cmd;
+  int cap;
+  const int *cmd_len, *cmd_index;
+  const double *head, *goal;           // [B][3][2], [B][2]
+  int *n_flown;
+  double *leg_end, *final_dist;        // [B][2][2], [B]
+};
+struct FleetLegOpenArgs {
+  int max_legs;
+  double threshold;                    // target_reach_threshold
+  const int *outcome, *n_flown;        // [B]: the caller's, close's
+  const double *leg_end, *final_dist;  // [B][2][2], [B]: close's
+  const int *count, *audit_flags;      // [B]: the audit's
+  const double *audit;                 // [B][NEO_AUDIT_FIELDS]
+  int *leg;                            // [B]: the index of the leg being flown
+  double *leg_log;                     // [B][max_legs][NEO_LEG_FIELDS]
+  double *leg_start;                   // [B][2]: where the leg being flown began
+  double *goal, *cur_pos, *head;       // [B][2], [B][2], [B][3][2]
+  int *cmd_len, *cmd_index, *future_index, *flags;
+};
+int fleet_leg_close(neo_ctx *c, const LaunchList &l, const FleetLegCloseArgs &a);
+int fleet_leg_open(neo_ctx *c, const LaunchList &l, const neo_leg_sequences &seq, const FleetLegOpenArgs &a);
+// goal[n][2], exists[n] for the n pairs (mission[p], leg_of[p]); every pointer, seq's too, a device array
+int fleet_leg_goal(neo_ctx *c, const neo_leg_sequences &seq, int B, int n, const int *mission, const int *leg_of,
+                   double *goal, int *exists);
 
 // neo_record_*_dev: the fleet's `record` mode (neo_disp_record.hip, kernels in neo_record.hpp).  Every pointer is a
 // device array; the arguments were checked by the C ABI.

@@ -35,6 +35,14 @@ NEO_FLEET_FLAG_ABANDONED = 16
 NEO_FLEET_ROUTE_MAX = 256
 TRACK_FIELDS = ("gap_mean", "gap_max", "t_gap_max", "gap_min", "t_gap_min", "gap_final", "t_first_within", "frac_within")
 NEO_TRACK_FIELDS = len(TRACK_FIELDS)
+# neo_fleet_leg_*: goals a mission, the kinds of goal lists, how a leg ended, fields of a row of the leg log
+NEO_FLEET_LEGS_MAX = 64
+NEO_LEGS_TABLE, NEO_LEGS_FLAP = 0, 1
+NEO_LEG_LANDED, NEO_LEG_ABANDONED, NEO_LEG_TIMEOUT, NEO_LEG_STUCK, NEO_LEG_OPEN = 1, 2, 3, 4, 5
+LEG_FIELDS = ("goal_x", "goal_y", "start_x", "start_y", "outcome", "n_flown", "final_dist", "flags", "count",
+              "audit_flags") + AUDIT_FIELDS + ("success",)
+LEG_INT_FIELDS = ("outcome", "n_flown", "flags", "count", "audit_flags", "success")      # stored as doubles, exact
+NEO_LEG_FIELDS = len(LEG_FIELDS)
 NEO_MAX_PIECES = 64                # M of any trajectory; neo_adaptive_*: one group per waypoint count below it
 NEO_BATCH_MAX_CANDIDATES = 8       # neo_batch_*: candidates a request
 NEO_DEPTH_MAX_BOXES = 1024         # neo_depth_*: boxes a scene
@@ -69,6 +77,7 @@ EXPORTS = [
     "neo_fleet_warm_guess_dev", "neo_fleet_warm_carry_dev",
     "neo_fleet_goal_route", "neo_fleet_goal_route_dev", "neo_fleet_hold_dev", "neo_fleet_track_audit",
     "neo_fleet_track_audit_dev",
+    "neo_fleet_leg_close_dev", "neo_fleet_leg_open_dev", "neo_fleet_leg_goal",
 ]
 
 
@@ -79,6 +88,13 @@ class NeoParams(ctypes.Structure):
                 ("maxls", ctypes.c_int32), ("maxiter", ctypes.c_int32), ("maxfun", ctypes.c_int32),
                 ("bugcompat_stale_T", ctypes.c_int32), ("sample_dtype", ctypes.c_int32),
                 ("flags", ctypes.c_int32)]
+
+
+class NeoLegSequences(ctypes.Structure):
+    """neo_leg_sequences: the goal lists of a campaign (goal_sequences.GoalSequences fills it)"""
+    _fields_ = [("kind", ctypes.c_int32), ("legs", ctypes.c_int32), ("n_goals", ctypes.c_int32),
+                ("goals", ctypes.c_void_p), ("seq_begin", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("mission_ids", ctypes.c_void_p),
+                ("x_pair", ctypes.c_double * 2), ("y_scale", ctypes.c_double), ("y_shift", ctypes.c_double)]
 
 
 _lib = None
@@ -161,6 +177,9 @@ def load():
     L.neo_fleet_hold_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p]
     L.neo_fleet_track_audit.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_d, c_p, c_i, c_p, c_p, c_p, c_d] + [c_p] * 3
     L.neo_fleet_track_audit_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_d, c_p, c_i, c_p, c_p, c_p, c_d] + [c_p] * 3
+    L.neo_fleet_leg_close_dev.argtypes = [c_p, c_i, c_p, c_p, c_i, c_p, c_i] + [c_p] * 7
+    L.neo_fleet_leg_open_dev.argtypes = [c_p, c_i, c_p, c_p, c_i, ctypes.POINTER(NeoLegSequences), c_i, c_d] + [c_p] * 16
+    L.neo_fleet_leg_goal.argtypes = [c_p, ctypes.POINTER(NeoLegSequences), c_i, c_i] + [c_p] * 4
     L.neo_adaptive_count.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p]
     L.neo_adaptive_count_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p]
     L.neo_adaptive_bucket.argtypes = [c_p, c_i, c_p, c_i] + [c_p] * 4

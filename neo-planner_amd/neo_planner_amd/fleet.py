@@ -64,6 +64,21 @@ weights (1, 1, 1) (:175) and neo_fleet_track_audit_dev measures the gap between 
 The hooks are the same for every mode but "geo" (the tracker node has no geo planner), resident or not, with onboard,
 record and both jitters.  Without goal_routes no launch, host read or allocation is added.
 
+With goal_sequences=GoalSequences every mission flies a CAMPAIGN, goal after goal (ros_node/manager_node.py:153-193 sends
+the next goal as soon as one is reached or given up; goal_sequences.py is the model of csrc/neo_legs.hpp's goal lists, bit
+for bit).  Each goal is a leg.  At the end of a tick the host knows which missions' legs ended -- landed, abandoned, stuck
+(CMD_FULL / SPLICE_FAILED) or past leg_timeout (the reference's max_target_find_time) -- and uploads (subset, outcome) for
+them once; then, on the context's stream, neo_fleet_leg_close_dev fixes what the leg was, neo_fleet_audit_batch_dev takes
+its flight metric on the TRUE map, and neo_fleet_leg_open_dev writes the leg's row of the resident log and opens the next
+leg: the sequence's next goal, cur_pos and head from where the leg ended (position and velocity: first_plan plans from
+drone_state, :491-504), the command array empty.  No device read is added and the mission never leaves the tick's launch
+list: its next plan is the next tick's, with that global tick number in the jitter keys, so the batch stays full and a
+mission still flies the same alone and in any fleet.  The kernels of a tick need nothing new for a freshly opened leg: the
+advance leaves a mission without commands untouched, the splice with first = 0 starts at future_index = 0, the pose looks
+from cur_pos towards the goal.  With onboard the mapper is reset at run()'s start and never at a leg's: the second goal is
+flown on the first one's map, as the reference's octomap persists from goal to goal.  Without goal_sequences no launch,
+host read or allocation is added.
+
 A mission's flight does not depend on which other missions share the fleet: the kernels work per mission, the target
 jitter of mission i at tick t and target r comes from SeedSequence(seed, i, t, r), and BatchPlanner.plan draws the
 retries of mission i from SeedSequence(plan_seed(t, r), i, attempt) (its `stream_ids`).  With jitter="counter" both come
@@ -84,6 +99,7 @@ import numpy as np
 
 from . import _lib, counter_rng
 from .goal_routes import GoalRoutes
+from . import fleet_legs
 
 MAX_TARGETS = 11        # :429-445: seed 0 .. 10 are planned, the mission is abandoned after the plan of target 10 fails
 
@@ -241,13 +257,30 @@ class FleetReplanLoop:
     frac_within: within track_radius metres of the goal), track_count, track_flags, failed_ticks and goal_final;
     final_dist is the distance to goal_final, n_flown = cmd_index + 1 and success = nothing went wrong (flags == 0, no
     metric failure).  metric_weights (3,): the flight metric's weights; None: the audit's default (1, 1, 100) for fixed
-    goals, the tracker node's (1, 1, 1) with routes."""
+    goals, the tracker node's (1, 1, 1) with routes.
+    goal_sequences: a GoalSequences (goal_sequences.py) of B goal lists -- every mission flies its goals one after the
+    other, `goals` may be None (the goals start as every mission's goal 0).  A leg ends LANDED, ABANDONED, STUCK or, with
+    leg_timeout (seconds; None: no limit), TIMEOUT: a leg whose own tick count j, from 0 at its first plan, has
+    (j + 1) * step / cmd_hz > leg_timeout closes at the end of that tick (the reference's max_target_find_time; its node
+    reports such a leg failed but forgets end_mission -- here it ends like an aborted one and the next goal follows).
+    max_legs (None: the longest list) caps the legs a mission flies and sizes the log.  max_replans is the run's tick
+    budget, as with routes; legs still open when it runs out are logged NEO_LEG_OPEN (a leg opened at the end of the last
+    tick, never planned, among them: n_flown 0, final_dist inf, and the "last leg" keys describe it).  Refused: goal_routes (a route
+    never lands), mode "warmstart" ("the first plan is basic" is a per-mission fact that _plan_warm takes from
+    tick > 0 today) and mode "geo" (as for routes).  Everything else works unchanged: basic and batch, resident or not,
+    "neo" / "nn", onboard (reset once, at run()'s start), record, both jitters; a flap's mission ids must be the
+    loop's.  The result keeps every key: replans, failed_attempts, iter_num and opt_runs are totals over the legs; n_cmd,
+    n_flown, final_dist, flags, abandoned, metric_fail, count, audit_flags and the audit fields describe the last leg
+    flown; success = every goal of the sequence was flown and every leg succeeded.  New: n_legs (B,), leg_<field>
+    (B, max_legs) for every field of the log (_lib.LEG_FIELDS) and the host tallies leg_replans, leg_failed_attempts,
+    leg_iter_num, leg_opt_runs, leg_ticks, leg_first_tick; NaN / -1 beyond n_legs."""
 
     def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
                  longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
                  scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False, onboard=None, scenes=None,
                  scene_index=None, des_pos_z=2.0, record_poses=False, record=None, neo=None, jitter="numpy",
-                 goal_routes=None, track_radius=1.0, metric_weights=None):
+                 goal_routes=None, track_radius=1.0, metric_weights=None, goal_sequences=None, leg_timeout=None, max_legs=None):
+        goals, self.leg_timeout, self.max_legs = fleet_legs.check_arguments(goal_sequences, leg_timeout, max_legs, goals, goal_routes, mode)
         a = _check_arguments(batch_planner, goals, mode, seed, scene_ids, mission_ids, resident, onboard, scenes, scene_index,
                              record, neo, jitter, goal_routes, track_radius, metric_weights)
         self.counter, self.jitter, self.seed = a["counter"], jitter, a["seed"]
@@ -258,6 +291,8 @@ class FleetReplanLoop:
         self.neo = neo if mode in ("neo", "nn") else None
         self.goals, self.scene_index, self.scene_ids, self.mission_ids = a["goals"], a["scene_index"], a["scene_ids"], a["mission_ids"]
         self.B = self.goals.shape[0]
+        self.sequences = goal_sequences
+        fleet_legs.check_ids(goal_sequences, self.mission_ids)
         self.cmd_hz = cmd_hz
         self.replan_period, self.planning_time_ahead = replan_period, planning_time_ahead
         self.longitu_step_dis, self.lateral_step_length = float(longitu_step_dis), float(lateral_step_length)
@@ -431,6 +466,8 @@ class FleetReplanLoop:
             self._dev.update(vertices=torch.from_numpy(r.vertices).to(dev), route_begin=torch.from_numpy(r.route_begin).to(dev),
                              speed=torch.from_numpy(r.speed).to(dev), closed=torch.from_numpy(r.closed).to(dev),
                              track=f(B, _lib.NEO_TRACK_FIELDS), track_count=i(B), track_flags=i(B))
+        if self.sequences is not None:      # the goal lists, the log, and what close hands to open
+            fleet_legs.alloc(self, f, i)
         self._poses, self._sensed = [], []
         self._host_head = self._host_x = None      # the host plan step's copies, made at its first plan
         self._up("goal", self.goals)
@@ -575,6 +612,7 @@ class FleetReplanLoop:
             head[:, 1] = _lib.as_f64(start_vel).reshape(B, 2)
         tracked = self.routes is not None
         t = _Tally(B, tracked)
+        legs = None if self.sequences is None else fleet_legs.LegTally(B, self.max_legs, self.sequences.count)
         active = np.arange(B)
         self.timings = []
         self.uncounted_candidates[:] = 0
@@ -592,6 +630,8 @@ class FleetReplanLoop:
                 if tick == 0:
                     self._up("cur_pos", head[:, 0])
                     self._up("head", head)
+                    if legs is not None:
+                        self._up("leg_start", head[:, 0])
                 if tick > 0 or tracked:
                     self._torch_done()
                 if tick > 0:
@@ -603,6 +643,8 @@ class FleetReplanLoop:
                     self._call("neo_fleet_goal_route_dev", *self._rows(sub_a), *self._route_table(),
                                float((tick * step) / self.cmd_hz), p(d["goal"]))
             self._camera_stage(sub_a, active, tm)
+            if legs is not None:
+                legs.begin_tick(active, tick)
             pending, sub = active, sub_a
             for r in range(MAX_TARGETS):
                 with _Timed(tm, "fleet_s"):      # jitter and target
@@ -626,6 +668,8 @@ class FleetReplanLoop:
                 tm["plan_requests"] += int(pending.size)
                 t.iter_num[pending] += nit_total
                 t.opt_runs[pending] += attempts
+                if legs is not None:
+                    legs.count_round(pending, ok, nit_total, attempts)
                 with _Timed(tm, "fleet_s"):      # record commit and splice
                     self._torch_done()
                     if self.record is not None:      # the round's rows, from the plans about to be spliced
@@ -646,11 +690,17 @@ class FleetReplanLoop:
                 t.abandoned[pending] = True
             flags = d["flags"].cpu().numpy()
             stuck = (flags & (_lib.NEO_FLEET_FLAG_CMD_FULL | _lib.NEO_FLEET_FLAG_SPLICE_FAILED)) != 0
-            active = active[~(t.abandoned | t.landed | stuck)[active]]
+            if legs is None:
+                active = active[~(t.abandoned | t.landed | stuck)[active]]
+            else:
+                with _Timed(tm, "legs_s"):
+                    active = fleet_legs.end_of_tick(self, t, legs, active, stuck, step)
             tm["tick_s"] = time.perf_counter() - t_tick
             tm["host_s"] = tm["tick_s"] - tm["fleet_s"] - tm["plan_s"] - tm.get("sense_s", 0.0) - tm.get("record_s", 0.0) - \
-                tm.get("neo_s", 0.0)
+                tm.get("neo_s", 0.0) - tm.get("legs_s", 0.0)
             self.timings.append(tm)
+        if legs is not None:
+            return fleet_legs.finish(self, t, legs)
         return self._finish(t)
 
     def _finish(self, tally):
@@ -702,6 +752,9 @@ class FleetReplanLoop:
             out.update({"track_" + name: track[:, k] for k, name in enumerate(_lib.TRACK_FIELDS)})
             out.update(track_count=d["track_count"].cpu().numpy(), track_flags=d["track_flags"].cpu().numpy(),
                        failed_ticks=tally.failed_ticks, goal_final=goals)
+        return self._with_poses(out)
+
+    def _with_poses(self, out):
         if self.record_poses and self.onboard is not None:
             out.update(poses=np.stack(self._poses) if self._poses else np.zeros((0, self.B, 5)),
                        sensed=np.stack(self._sensed) if self._sensed else np.zeros((0, self.B), bool))
