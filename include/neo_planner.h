@@ -587,6 +587,73 @@ int neo_fleet_track_audit_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_
                               int n_vertices, const int32_t *route_begin, const double *speed, const int32_t *closed,
                               double radius, double *track, int32_t *count, int32_t *flags);
 
+/* ---- fleet flight model (a drone that tracks its commands with lag and gusts, in place of PX4 / Gazebo) ----------------
+ * The reference reads the drone's odometry, not the command, for set_local_target (:452), the reach test (:183), the
+ * camera pose, the flight metric (:333-363) and save_tracking_err (:310-331); only the planning start state comes from
+ * the command array (:527-537).  csrc/neo_flight.hpp is the model, neo_planner_amd.flight_model its NumPy twin and its
+ * definition, bit for bit.  Per mission, caller-owned DEVICE buffers indexed by MISSION:
+ *   drone[B][8]          position p, velocity v, lagged thrust acceleration a, gust acceleration g, 2-D each;
+ *   flown[B][cap][3][2]  the flown rows, in the command rows' layout: row t is the drone at t / cmd_hz;
+ *   flown_len[B]         rows flown so far; saturated[B] sub-steps whose command was clipped to a_max.
+ * Sub-step t (one command period h; t the absolute row) takes the drone from row t - 1 to row t against the command it
+ * holds during that period, r = cmd[min(t - 1, cmd_len - 1)] = (p_d, v_d, a_d):
+ *   u = a_d + kp (p_d - p) + kv (v_d - v);  n = |u| > a_max: u *= a_max / n, saturated += 1;  a += alpha (u - a);
+ *   t % gust_every == 0 and scale != 0: g = rho g + scale z, z values 0 and 1 of csrc/neo_counter_rng.hpp's stream with
+ *   the key `seed` and the counter (mission_ids[b], t / gust_every, 0, 4 << 24);  v += h (a + g - drag v);  p += h v;
+ *   flown row t = (p, v, a + g - drag v).  fp64, + - * / and sqrt, every operation rounded on its own.
+ * The caller computes the derived values once: h = 1 / cmd_hz, alpha = h / (tau + h), rho = exp(-gust_every h / gust_tau),
+ * scale = gust_sigma sqrt(1 - rho^2).  The draw index is the absolute row: a flight does not depend on how launches cut
+ * it, nor on B, the subset or its order.
+ * The launch parameter stands next to B in both calls (the model, a HOST struct read before the launch; flown_len, a device
+ * array); subset and n_subset follow it.
+ * NEO_ERR_INVALID before any launch, with a neo_last_error message: a NULL required buffer, B < 0, a bad subset size,
+ * cap <= 0, step, ahead or settle outside 0 .. 2^30, stride < 1, a model with a field that is not finite, h, a_max or
+ * alpha not > 0, or gust_every < 1, a reach that is not finite. */
+typedef struct neo_flight_model {
+  double h;            /* 1 / cmd_hz */
+  double kp, kv;       /* gains on the position and the velocity error */
+  double a_max;        /* the largest commanded acceleration */
+  double alpha;        /* h / (tau + h): the thrust lag */
+  double drag;         /* linear drag, 1 / s */
+  double rho, scale;   /* the gust's AR(1) step; scale 0: no gusts, nothing is drawn */
+  int32_t gust_every;  /* sub-steps between two draws */
+  uint64_t seed;       /* the key of the gust streams */
+} neo_flight_model;
+#define NEO_FLY_FIELDS 6
+enum {
+  NEO_FLY_POS_ERR_RMS = 0,    /* sqrt(sum(e^2) / count), e the distance between the flown and the commanded position */
+  NEO_FLY_POS_ERR_MAX = 1,    /* the largest e ... */
+  NEO_FLY_POS_ERR_MAX_AT = 2, /* ... and its row; the first sample wins ties */
+  NEO_FLY_VEL_ERR_RMS = 3,    /* the same of the velocities */
+  NEO_FLY_VEL_ERR_MAX = 4,
+  NEO_FLY_POS_ERR_FINAL = 5   /* e at row flown_len - 1, whatever the stride */
+};
+/* neo_fleet_advance_dev with the model in place of perfect tracking, one lane per mission.  For a mission with
+ * cmd_len >= 1 (clamped to cap): `first` != 0 (or flown_len[b] < 1: nothing of it flown yet) writes flown row cmd_index
+ * from the state as it stands, so row 0 is the start state; the sub-steps cmd_index + 1 .. min(cmd_index + step,
+ * cmd_len - 1) follow, each writing its flown row; cmd_index, future_index and head[B][3][2] are exactly
+ * neo_fleet_advance_dev's -- the planning start state comes from the COMMAND array -- cur_pos[B][2] is the actual
+ * position and flown_len = cmd_index + 1.  settle > 0 is the last launch of a landed mission: on the array's last row the
+ * last command is held for at most `settle` more sub-steps, up to the first that starts with sqrt(dx * dx + dy * dy) <
+ * reach, measured to goal[B][2]; those rows are appended to flown (flown_len counts them).  Nothing is written at or past
+ * row cap: a flight that would go past it stops there and raises NEO_FLEET_FLAG_CMD_FULL in flags[B].  A mission with
+ * cmd_len < 1 keeps every row and word it has.  mission_ids: int32 [B], ids in 0 .. 2^31 - 1; NULL: b itself.  Device
+ * pointers only. */
+int neo_fleet_fly_dev(neo_ctx *ctx, int B, const neo_flight_model *model, const int32_t *subset, int n_subset,
+                      const double *cmd, int cap, const int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index,
+                      int step, int ahead, int first, int settle, double reach, const int32_t *mission_ids,
+                      const double *goal, double *drone, double *flown, int32_t *flown_len, int32_t *saturated,
+                      int32_t *flags, double *cur_pos, double *head);
+/* save_tracking_err's table (:310-331) reduced per mission, one wavefront per mission: sample j is flown row j * stride
+ * < flown_len[b] (clamped to 0 .. cap) against command row min(j * stride, cmd_len[b] - 1) -- the settle rows against the
+ * last command.  fly[B][NEO_FLY_FIELDS] as the enum above, count[B] the samples, flags[B] written (not OR-ed): 0, or
+ * NEO_AUDIT_FLAG_NONFINITE with a NaN record and count 0 for a sampled position, velocity or result that is not finite.
+ * No samples or no commands: a NaN record, count 0, flags 0.  Each lane sums its own samples in time order, the lanes are
+ * combined in a fixed order.  Device pointers only. */
+int neo_fleet_fly_error_dev(neo_ctx *ctx, int B, const int32_t *flown_len, const int32_t *subset, int n_subset,
+                            const double *flown, const double *cmd, int cap, const int32_t *cmd_len, int stride,
+                            double *fly, int32_t *count, int32_t *flags);
+
 /* ---- fleet campaigns (ros_node/manager_node.py:153-193: the next goal as soon as one is reached or given up) --------
  * A mission flies a sequence of goals; each goal is a LEG (csrc/neo_legs.hpp; neo_planner_amd.goal_sequences.GoalSequences
  * is the NumPy model of the goal lists, bit for bit).  When a leg ends the caller uploads outcome[b] for the closing

@@ -513,6 +513,46 @@ int neo_fleet_track_audit(neo_ctx *c, int B, const int32_t *subset, int n_subset
   });
 }
 
+// ---- the fleet's flight model (kernels: neo_flight.hpp)
+int neo_fleet_fly_dev(neo_ctx *c, int B, const neo_flight_model *model, const int32_t *subset, int n_subset, const double *cmd,
+                      int cap, const int32_t *cmd_len, int32_t *cmd_index, int32_t *future_index, int step, int ahead,
+                      int first, int settle, double reach, const int32_t *mission_ids, const double *goal, double *drone,
+                      double *flown, int32_t *flown_len, int32_t *saturated, int32_t *flags, double *cur_pos, double *head) {
+  int rc = list_check(c, "fleet fly", B, 0, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  rc = fleet_cmd_check(c, "fleet fly", cmd, cap, cmd_len, cmd_index, future_index);
+  if (rc) return rc;
+  rc = null_check(c, "fleet fly: null buffer", {model, goal, drone, flown, flown_len, saturated, flags, cur_pos, head});
+  if (rc) return rc;
+  // (sums of two of them stay below 2^31: the kernel's index arithmetic cannot overflow)
+  if (step < 0 || step > (1 << 30) || ahead < 0 || ahead > (1 << 30) || settle < 0 || settle > (1 << 30))
+    return fail_locked(c, NEO_ERR_INVALID, "fleet fly: step, ahead and settle must be in 0 .. 2^30");
+  if (!std::isfinite(reach)) return fail_locked(c, NEO_ERR_INVALID, "fleet fly: reach must be finite");
+  for (double v : {model->h, model->kp, model->kv, model->a_max, model->alpha, model->drag, model->rho, model->scale})
+    if (!std::isfinite(v)) return fail_locked(c, NEO_ERR_INVALID, "fleet fly: the model has a field that is not finite");
+  if (!(model->h > 0.0) || !(model->a_max > 0.0) || !(model->alpha > 0.0))
+    return fail_locked(c, NEO_ERR_INVALID, "fleet fly: the model's h, a_max and alpha must be > 0");
+  if (model->gust_every < 1) return fail_locked(c, NEO_ERR_INVALID, "fleet fly: the model's gust_every must be >= 1");
+  return list_launch(c, B, subset, n_subset, [&](const LaunchList &list) {
+    return fleet_fly(c, list, *model, {const_cast<double *>(cmd), cap, const_cast<int32_t *>(cmd_len), cmd_index, future_index},
+                     {step, ahead, first ? 1 : 0, settle, reach, mission_ids, goal, drone, flown, flown_len, saturated, flags,
+                      cur_pos, head});
+  });
+}
+
+int neo_fleet_fly_error_dev(neo_ctx *c, int B, const int32_t *flown_len, const int32_t *subset, int n_subset,
+                            const double *flown, const double *cmd, int cap, const int32_t *cmd_len, int stride, double *fly,
+                            int32_t *count, int32_t *flags) {
+  int rc = list_check(c, "fleet fly error", B, 0, INT32_MAX, subset, n_subset);
+  if (rc) return rc;
+  if ((rc = null_check(c, "fleet fly error: null buffer", {flown_len, flown, cmd, cmd_len, fly, count, flags}))) return rc;
+  if (cap <= 0) return fail_locked(c, NEO_ERR_INVALID, "fleet fly error: cap must be > 0");
+  if (stride < 1) return fail_locked(c, NEO_ERR_INVALID, "fleet fly error: stride must be >= 1");
+  return list_launch(c, B, subset, n_subset, [&](const LaunchList &list) {
+    return fleet_fly_error(c, list, {flown, cmd, cap, flown_len, cmd_len, stride, fly, count, flags});
+  });
+}
+
 // ---- fleet campaigns (ros_node/manager_node.py:153-193; kernels: neo_legs.hpp)
 // what can be said of the goal lists without reading them (the _dev forms hold device pointers)
 static int fleet_legs_seq_check(neo_ctx *c, const char *who, const neo_leg_sequences *seq, int B) {

@@ -1,10 +1,11 @@
-// neo_disp_fleet.hip -- the fleet kernels (neo_fleet.hpp; goal routes: neo_track.hpp; campaigns: neo_legs.hpp): local targets, tracking and look-ahead, the splice of a new
+// neo_disp_fleet.hip -- the fleet kernels (neo_fleet.hpp; goal routes: neo_track.hpp; campaigns: neo_legs.hpp; the flight model: neo_flight.hpp): local targets, tracking and look-ahead, the splice of a new
 // plan into the resident command array and the flight metric of what was flown (ros_node/traj_planner_node.py:333-363,
 // :450-488, :527-537, :574-578) for B missions.  2-D reference map, D = 2: one instantiation each.
 #include "neo_host.hpp"
 #include "neo_fleet.hpp"
 #include "neo_track.hpp"
 #include "neo_legs.hpp"
+#include "neo_flight.hpp"
 
 namespace neo {
 
@@ -80,6 +81,22 @@ int fleet_hold(neo_ctx *c, const LaunchList &l, const FleetCmd &m, int step, int
 int fleet_track_audit(neo_ctx *c, const LaunchList &l, const FleetRoutes &r, const FleetTrackArgs &a) {
   hipLaunchKernelGGL(fleet_track_audit_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.cmd, a.cap, a.n_flown, a.stride,
                      a.hz, r.vertices, r.n_vertices, r.route_begin, r.speed, r.closed, a.radius, a.track, a.count, a.flags);
+  return NEO_OK;
+}
+
+int fleet_fly(neo_ctx *c, const LaunchList &l, const neo_flight_model &model, const FleetCmd &m, const FleetFlyArgs &a) {
+  const FlightParams fp = {model.h, model.kp, model.kv, model.a_max, model.alpha, model.drag, model.rho, model.scale,
+                           model.gust_every, (unsigned long long)model.seed};
+  const FlightLaunch fl = {m.cap, a.step, a.ahead, a.first, a.settle, a.reach};
+  hipLaunchKernelGGL(fleet_fly_kernel, lanes_grid(l.n), dim3(kFleetThreads), 0, c->stream, l, fp, fl, m.cmd, m.cmd_len,
+                     m.cmd_index, m.future_index, a.mission_ids, a.goal, a.drone, a.flown, a.flown_len, a.saturated, a.flags,
+                     a.cur_pos, a.head);
+  return NEO_OK;
+}
+
+int fleet_fly_error(neo_ctx *c, const LaunchList &l, const FleetFlyErrorArgs &a) {
+  hipLaunchKernelGGL(fleet_fly_error_kernel, dim3(l.n), dim3(kWave), 0, c->stream, l, a.flown, a.cmd, a.cap, a.flown_len,
+                     a.cmd_len, a.stride, a.fly, a.count, a.flags);
   return NEO_OK;
 }
 

@@ -9,6 +9,9 @@
 //   fleet_warm_carry_kernel  what a mission keeps of a plan for that (:570-571)           one lane per mission
 //   fleet_splice_kernel    the splice of replan   (:574-578, first_plan :515-519)   one wavefront per mission
 //   fleet_audit_kernel     get_weighted_metric    (:333-363) over the flown rows   one wavefront per mission
+// and, in neo_flight.hpp (which includes this file), the drone that is not on its command row:
+//   fleet_fly_kernel       the advance with a flight model: lag, saturation, drag, gusts   one lane per mission
+//   fleet_fly_error_kernel save_tracking_err (:310-331) reduced per mission             one wavefront per mission
 //
 // Included by neo_disp_fleet.hip only.  2-D reference map, D = 2, fp64.  No floating-point atomics, fixed summation
 // order: a mission's results depend on neither the batch, the subset nor the launch.  All arrays are indexed by mission;

@@ -281,6 +281,26 @@ int fleet_goal(neo_ctx *c, const LaunchList &l, const FleetRoutes &r, double t, 
 // rows appended to a command array that ends before cmd_index + step + 1 (m.future_index is not used)
 int fleet_hold(neo_ctx *c, const LaunchList &l, const FleetCmd &m, int step, int *flags);
 int fleet_track_audit(neo_ctx *c, const LaunchList &l, const FleetRoutes &r, const FleetTrackArgs &a);
+// the flight model (kernels in neo_flight.hpp): the advance with a drone that lags, and its tracking-error record
+struct FleetFlyArgs {
+  int step, ahead, first, settle;
+  double reach;
+  const int *mission_ids;              // [B], or NULL: the mission's index
+  const double *goal;                  // [B][2]
+  double *drone, *flown;               // [B][8], [B][cap][3][2]
+  int *flown_len, *saturated, *flags;  // [B]
+  double *cur_pos, *head;              // [B][2], [B][3][2]
+};
+struct FleetFlyErrorArgs {
+  const double *flown, *cmd;
+  int cap;
+  const int *flown_len, *cmd_len;
+  int stride;
+  double *fly;
+  int *count, *flags;
+};
+int fleet_fly(neo_ctx *c, const LaunchList &l, const neo_flight_model &model, const FleetCmd &m, const FleetFlyArgs &a);
+int fleet_fly_error(neo_ctx *c, const LaunchList &l, const FleetFlyErrorArgs &a);
 // campaigns (kernels in neo_legs.hpp): what a leg was, then its row of the log and the next leg's start
 struct FleetLegCloseArgs {
   const int *outcome;                  // [B]: NEO_LEG_*

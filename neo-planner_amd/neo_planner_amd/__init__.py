@@ -13,6 +13,7 @@ from .geo import GeoPlanner  # noqa: F401
 from .fleet import FleetReplanLoop  # noqa: F401
 from .goal_routes import GoalRoutes  # noqa: F401
 from .goal_sequences import GoalSequences  # noqa: F401
+from .flight_model import FlightModel  # noqa: F401
 from .depth import DepthCamera  # noqa: F401
 from .onboard import OnboardMapper  # noqa: F401
 from .record import DemoRecorder  # noqa: F401
@@ -20,5 +21,5 @@ from .training import train_initializer  # noqa: F401  (torch and the network ar
 # the initializer network (torch) is imported on demand: `from neo_planner_amd import initializer`
 
 __all__ = ["Context", "NeoError", "default_context", "ESDF", "ESDF3D", "BatchPlanner", "MinJerkPlanner",
-           "PlannerConfig", "GeoPlanner", "FleetReplanLoop", "GoalRoutes", "GoalSequences", "DepthCamera", "OnboardMapper", "DemoRecorder",
+           "PlannerConfig", "GeoPlanner", "FleetReplanLoop", "GoalRoutes", "GoalSequences", "FlightModel", "DepthCamera", "OnboardMapper", "DemoRecorder",
            "train_initializer"]

@@ -35,6 +35,9 @@ NEO_FLEET_FLAG_ABANDONED = 16
 NEO_FLEET_ROUTE_MAX = 256
 TRACK_FIELDS = ("gap_mean", "gap_max", "t_gap_max", "gap_min", "t_gap_min", "gap_final", "t_first_within", "frac_within")
 NEO_TRACK_FIELDS = len(TRACK_FIELDS)
+# neo_fleet_fly_error_dev: fields of a tracking-error record (flight_model.py)
+FLY_FIELDS = ("pos_err_rms", "pos_err_max", "pos_err_max_at", "vel_err_rms", "vel_err_max", "pos_err_final")
+NEO_FLY_FIELDS = len(FLY_FIELDS)
 # neo_fleet_leg_*: goals a mission, the kinds of goal lists, how a leg ended, fields of a row of the leg log
 NEO_FLEET_LEGS_MAX = 64
 NEO_LEGS_TABLE, NEO_LEGS_FLAP = 0, 1
@@ -78,6 +81,7 @@ EXPORTS = [
     "neo_fleet_goal_route", "neo_fleet_goal_route_dev", "neo_fleet_hold_dev", "neo_fleet_track_audit",
     "neo_fleet_track_audit_dev",
     "neo_fleet_leg_close_dev", "neo_fleet_leg_open_dev", "neo_fleet_leg_goal",
+    "neo_fleet_fly_dev", "neo_fleet_fly_error_dev",
 ]
 
 
@@ -95,6 +99,12 @@ class NeoLegSequences(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("legs", ctypes.c_int32), ("n_goals", ctypes.c_int32),
                 ("goals", ctypes.c_void_p), ("seq_begin", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("mission_ids", ctypes.c_void_p),
                 ("x_pair", ctypes.c_double * 2), ("y_scale", ctypes.c_double), ("y_shift", ctypes.c_double)]
+
+
+class NeoFlightModel(ctypes.Structure):
+    """neo_flight_model: the derived constants of a flight (flight_model.FlightModel.derived fills it)"""
+    _fields_ = [(k, ctypes.c_double) for k in ("h", "kp", "kv", "a_max", "alpha", "drag", "rho", "scale")] + \
+               [("gust_every", ctypes.c_int32), ("seed", ctypes.c_uint64)]
 
 
 _lib = None
@@ -180,6 +190,9 @@ def load():
     L.neo_fleet_leg_close_dev.argtypes = [c_p, c_i, c_p, c_p, c_i, c_p, c_i] + [c_p] * 7
     L.neo_fleet_leg_open_dev.argtypes = [c_p, c_i, c_p, c_p, c_i, ctypes.POINTER(NeoLegSequences), c_i, c_d] + [c_p] * 16
     L.neo_fleet_leg_goal.argtypes = [c_p, ctypes.POINTER(NeoLegSequences), c_i, c_i] + [c_p] * 4
+    L.neo_fleet_fly_dev.argtypes = [c_p, c_i, ctypes.POINTER(NeoFlightModel), c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i,
+                                    c_d] + [c_p] * 9
+    L.neo_fleet_fly_error_dev.argtypes = [c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p]
     L.neo_adaptive_count.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p]
     L.neo_adaptive_count_dev.argtypes = [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p]
     L.neo_adaptive_bucket.argtypes = [c_p, c_i, c_p, c_i] + [c_p] * 4

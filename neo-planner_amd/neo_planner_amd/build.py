@@ -64,7 +64,7 @@ def _flags():
 # headers only one unit (or the three of the C ABI) includes: a change there recompiles those alone
 UNIT_HEADERS = {"neo_abi.hip": ["neo_abi_util.hpp"], "neo_abi_fleet.hip": ["neo_abi_util.hpp"], "neo_abi_plan.hip": ["neo_abi_util.hpp"],
                 "neo_disp_audit.hip": ["neo_audit.hpp"], "neo_disp_geo.hip": ["neo_geo.hpp"],
-                "neo_disp_fleet.hip": ["neo_fleet.hpp", "neo_audit.hpp", "neo_track.hpp", "neo_legs.hpp"], "neo_disp_batch.hip": ["neo_batch.hpp"],
+                "neo_disp_fleet.hip": ["neo_fleet.hpp", "neo_audit.hpp", "neo_track.hpp", "neo_legs.hpp", "neo_flight.hpp"], "neo_disp_batch.hip": ["neo_batch.hpp"],
                 "neo_disp_esdf.hip": ["neo_esdf.hpp"], "neo_disp_plan.hip": ["neo_plan.hpp"],
                 "neo_disp_depth.hip": ["neo_depth.hpp"], "neo_disp_onboard.hip": ["neo_onboard.hpp"],
                 "neo_disp_record.hip": ["neo_record.hpp"], "neo_disp_init.hip": ["neo_init.hpp", "neo_record.hpp"],

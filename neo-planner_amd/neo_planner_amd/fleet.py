@@ -86,6 +86,20 @@ from the counter-based streams of counter_rng.py / csrc/neo_counter_rng.hpp inst
 (seed, mission id, tick, target) or (plan_seed, mission id, attempt) -- drawn on the device: neo_fleet_jitter_dev in front
 of the target kernel, neo_plan_jitter_dev inside plan_dev.  The property is the same, the flights are other flights.
 
+With flight=FlightModel (flight_model.py, the model of csrc/neo_flight.hpp, bit for bit) the missions no longer sit on
+their command rows: every mission has a resident drone state (position, velocity, lagged thrust, gust), and from tick 1
+on neo_fleet_fly_dev stands where neo_fleet_advance_dev stood (behind neo_fleet_hold_dev when goals move) -- the same
+index arithmetic, the same look-ahead state FROM THE COMMAND ARRAY (:527-537), but cur_pos is where the drone is after
+`step` sub-steps of tracking with lag, saturation, drag and gusts, and every sub-step leaves a row of the resident `flown`
+array.  What the reference reads from odometry reads the flown rows here: the targets and the camera's eye (cur_pos), the
+recorder's and the network's velocity now, the end audit, the tracking audit and final_dist; the camera's heading stays
+the command's (:685-687).  At the end one more fly launch flies the landed missions out and holds their last command for
+at most settle_seconds, up to the reach test; n_flown is the number of flown rows, and neo_fleet_fly_error_dev reduces the
+reference's save_tracking_err table (:310-331) to fly_<field> (_lib.FLY_FIELDS), fly_count, fly_flags and fly_saturated.
+The gust of sub-step t is keyed by (model seed, mission id, t): a mission flies the same alone and in any fleet, however
+the ticks cut its flight.  Every mode and option works but goal_sequences (campaigns re-open legs from command rows;
+carrying a drone state across legs is left out).  Without flight no launch, host read or allocation is added.
+
 Two streams, one rule.  torch works on its own stream, the context launches on another, and nothing orders the two but
 the host.  Every stage of the loop therefore goes: torch work (uploads, gathers, scatters), then `_torch_done`, then the
 context's launches, then `_ctx_done`, then torch or host reads of what they wrote.  A launch may only read a tensor torch
@@ -99,7 +113,7 @@ import numpy as np
 
 from . import _lib, counter_rng
 from .goal_routes import GoalRoutes
-from . import fleet_legs
+from . import fleet_legs, fleet_flight
 
 MAX_TARGETS = 11        # :429-445: seed 0 .. 10 are planned, the mission is abandoned after the plan of target 10 fails
 
@@ -273,13 +287,20 @@ class FleetReplanLoop:
     n_flown, final_dist, flags, abandoned, metric_fail, count, audit_flags and the audit fields describe the last leg
     flown; success = every goal of the sequence was flown and every leg succeeded.  New: n_legs (B,), leg_<field>
     (B, max_legs) for every field of the log (_lib.LEG_FIELDS) and the host tallies leg_replans, leg_failed_attempts,
-    leg_iter_num, leg_opt_runs, leg_ticks, leg_first_tick; NaN / -1 beyond n_legs."""
+    leg_iter_num, leg_opt_runs, leg_ticks, leg_first_tick; NaN / -1 beyond n_legs.
+    flight: a FlightModel (flight_model.py) -- the missions track their commands with lag and gusts instead of sitting on
+    them (module docstring); settle_seconds: how long a landed mission may hold its last command until it is within
+    target_reach_threshold of the goal.  The result gains fly_<field> for _lib.FLY_FIELDS, fly_count, fly_flags and
+    fly_saturated; n_flown counts flown rows (a landed mission's settle rows included) and flown_rows(i) returns them.
+    Refused with goal_sequences."""
 
     def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
                  longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
                  scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False, onboard=None, scenes=None,
                  scene_index=None, des_pos_z=2.0, record_poses=False, record=None, neo=None, jitter="numpy",
-                 goal_routes=None, track_radius=1.0, metric_weights=None, goal_sequences=None, leg_timeout=None, max_legs=None):
+                 goal_routes=None, track_radius=1.0, metric_weights=None, goal_sequences=None, leg_timeout=None, max_legs=None,
+                 flight=None, settle_seconds=2.0):
+        self.flight, self.settle_seconds, self._fly_model = fleet_flight.check_arguments(flight, settle_seconds, goal_sequences, cmd_hz)
         goals, self.leg_timeout, self.max_legs = fleet_legs.check_arguments(goal_sequences, leg_timeout, max_legs, goals, goal_routes, mode)
         a = _check_arguments(batch_planner, goals, mode, seed, scene_ids, mission_ids, resident, onboard, scenes, scene_index,
                              record, neo, jitter, goal_routes, track_radius, metric_weights)
@@ -294,6 +315,7 @@ class FleetReplanLoop:
         self.sequences = goal_sequences
         fleet_legs.check_ids(goal_sequences, self.mission_ids)
         self.cmd_hz = cmd_hz
+        fleet_flight.check_ids(flight, self.mission_ids)
         self.replan_period, self.planning_time_ahead = replan_period, planning_time_ahead
         self.longitu_step_dis, self.lateral_step_length = float(longitu_step_dis), float(lateral_step_length)
         self.target_reach_threshold = target_reach_threshold
@@ -352,6 +374,11 @@ class FleetReplanLoop:
         """the resident command arrays: cmd, cap, cmd_len, cmd_index"""
         return (self._p(self._dev["cmd"]), self.cap) + self._ptrs("cmd_len", "cmd_index")
 
+    def _flown(self):
+        """the rows that say where the drone WAS: the flown rows with a flight model, the command rows without one --
+        same argument group as _cmd(), for whoever reads the actual state"""
+        return self._cmd() if self.flight is None else (self._p(self._dev["flown"]), self.cap) + self._ptrs("cmd_len", "cmd_index")
+
     def _route_table(self):
         return (self._p(self._dev["vertices"]), int(self._dev["vertices"].shape[0])) + self._ptrs("route_begin", "speed", "closed")
 
@@ -404,7 +431,7 @@ class FleetReplanLoop:
         """one image consumer: the active missions' velocities now into its `cur_vel`, then render(boxes, box_begin, pose
         rows, scene_index rows) of the active missions scattered into its per-mission buffer `into`"""
         d = self._dev
-        self._call("neo_record_state_dev", *self._rows(sub), *self._cmd(), self._p(d["head"]), self._p(cur_vel))
+        self._call("neo_record_state_dev", *self._rows(sub), *self._flown(), self._p(d["head"]), self._p(cur_vel))
         self._ctx_done()
         if view is None:
             whole = active.size == self.B
@@ -459,7 +486,9 @@ class FleetReplanLoop:
         if self.record is not None:
             self.record.bind(B)
             self.record.T_min, self.record.T_max = float(self.bp.cfg.T_min), float(self.bp.cfg.T_max)   # what rows() maps tau with
-        if self.record is not None or self.counter:
+        if self.flight is not None:      # the drones, what they flew, and the tracking-error record
+            fleet_flight.alloc(self, f, i)
+        if self.record is not None or self.counter or self.flight is not None:
             self._dev["mission_ids"] = self._subset(self.mission_ids)
         if self.routes is not None:      # the route table, and what the track audit writes
             r = self.routes
@@ -632,13 +661,18 @@ class FleetReplanLoop:
                     self._up("head", head)
                     if legs is not None:
                         self._up("leg_start", head[:, 0])
+                    if self.flight is not None:
+                        fleet_flight.start(self, head)
                 if tick > 0 or tracked:
                     self._torch_done()
                 if tick > 0:
                     if tracked:      # a mission whose commands end before the coming period is over holds its last one
                         self._call("neo_fleet_hold_dev", *self._rows(sub_a), *self._cmd(), step, p(d["flags"]))
-                    self._call("neo_fleet_advance_dev", *self._rows(sub_a), *self._cmd(), p(d["future_index"]), step, ahead,
-                               *self._ptrs("cur_pos", "head"))
+                    if self.flight is None:
+                        self._call("neo_fleet_advance_dev", *self._rows(sub_a), *self._cmd(), p(d["future_index"]), step, ahead,
+                                   *self._ptrs("cur_pos", "head"))
+                    else:
+                        fleet_flight.fly(self, sub_a, step, ahead, int(tick == 1))
                 if tracked:
                     self._call("neo_fleet_goal_route_dev", *self._rows(sub_a), *self._route_table(),
                                float((tick * step) / self.cmd_hz), p(d["goal"]))
@@ -713,11 +747,15 @@ class FleetReplanLoop:
         cmd_index = d["cmd_index"].cpu().numpy()
         # a mission that landed flies its array to the end; the others stopped at the row they were on (a tracked mission
         # is always on a row of its array: n_flown = cmd_index + 1, whatever it held on the way)
-        n_flown = np.where(landed, cmd_len, np.minimum(cmd_index + 1, cmd_len)).astype(np.int32)
-        self._up("n_flown", n_flown)
-        self._torch_done()
         took = {}
-        flown = p(d["cmd"]), self.cap, p(d["n_flown"]), self.stride, float(self.cmd_hz)
+        if self.flight is None:
+            n_flown = np.where(landed, cmd_len, np.minimum(cmd_index + 1, cmd_len)).astype(np.int32)
+            self._up("n_flown", n_flown)
+            self._torch_done()
+            rows = d["cmd"]
+        else:      # the landed missions fly their arrays out and settle; the others stopped on the row they were on
+            n_flown, rows = fleet_flight.settle(self, landed, took)
+        flown = p(rows), self.cap, p(d["n_flown"]), self.stride, float(self.cmd_hz)
         with _Timed(took, "audit_s"):
             self._call("neo_fleet_audit_batch_dev", self.map.scene_id, p(d["slots"]), *self._rows(None), *flown,
                        None if self.metric_weights is None else _lib.ptr(self.metric_weights),
@@ -730,9 +768,11 @@ class FleetReplanLoop:
                 self._ctx_done()
             self.track_audit_s = took["track_audit_s"]
         self.audit_s = took["audit_s"]
+        if self.flight is not None:
+            fleet_flight.error(self, took)
         goals = d["goal"].cpu().numpy() if tracked else self.goals      # tracked: where the goals were at the last tick
         last = torch.from_numpy(np.maximum(n_flown - 1, 0).astype(np.int64)).to(self._device)
-        end = d["cmd"][torch.arange(self.B, device=self._device), last, 0].cpu().numpy()
+        end = rows[torch.arange(self.B, device=self._device), last, 0].cpu().numpy()
         final_dist = np.where(n_flown > 0, np.linalg.norm(end - goals, axis=1), np.inf)
         flags = d["flags"].cpu().numpy() | np.where(abandoned, _lib.NEO_FLEET_FLAG_ABANDONED, 0).astype(np.int32)
         audit = d["audit"].cpu().numpy()
@@ -752,6 +792,8 @@ class FleetReplanLoop:
             out.update({"track_" + name: track[:, k] for k, name in enumerate(_lib.TRACK_FIELDS)})
             out.update(track_count=d["track_count"].cpu().numpy(), track_flags=d["track_flags"].cpu().numpy(),
                        failed_ticks=tally.failed_ticks, goal_final=goals)
+        if self.flight is not None:
+            fleet_flight.results(self, out)
         return self._with_poses(out)
 
     def _with_poses(self, out):
@@ -773,6 +815,9 @@ class FleetReplanLoop:
         """the command array of mission i (n_cmd, 3, 2) copied to the host"""
         n = int(self._dev["cmd_len"][i].item())
         return self._dev["cmd"][i, :n].cpu().numpy()
+
+
+    flown_rows = fleet_flight.flown_rows      # with a flight model: the flown rows of mission i (flown_len, 3, 2), on the host
 
 
 def draw_missions(maps, per_map, seed=0, dist_range=(25.0, 30.0), safe_dis=0.7):

@@ -1,6 +1,9 @@
 """
 ROS-free replan loop: the orchestration that sits directly above the optimiser in
-ros_node/traj_planner_node.py, with perfect tracking in place of PX4/Gazebo.
+ros_node/traj_planner_node.py, with perfect tracking in place of PX4/Gazebo -- or, with flight=FlightModel
+(flight_model.py), a drone that tracks its commands with lag and gusts: set_local_target and the returned path then read
+the drone's actual state, as the reference reads its odometry (:452, :183, :333-363), and only the planning start state
+still comes from the command array (:527-537).
 
   set_local_target          traj_planner_node.py:450-488   5 m ahead toward the goal, lateral steps out
                                                            of obstacles, target speed 0.8 v_max
@@ -26,6 +29,8 @@ import io
 
 import numpy as np
 
+from . import flight_model
+
 
 class _State:
     def __init__(self, pos, vel):
@@ -36,7 +41,7 @@ class _State:
 class ReplanLoop:
     def __init__(self, planner, map, goal=(30.0, 0.0), v_max=1.0, des_pos_z=2.0, cmd_hz=60,
                  replan_period=1.0, planning_time_ahead=1.0, longitu_step_dis=5.0, lateral_step_length=1.0,
-                 target_reach_threshold=0.2, mode="basic", quiet=True):
+                 target_reach_threshold=0.2, mode="basic", quiet=True, flight=None, settle_seconds=2.0, mission_id=0):
         self.planner, self.map = planner, map
         self.global_target = np.asarray(goal, dtype=np.float64)
         self.move_vel = 0.8 * v_max                               # :87
@@ -49,6 +54,8 @@ class ReplanLoop:
         self.des_state_index = 0
         self.n_plans = self.n_failed_attempts = 0
         self.wpts_local = None      # mode "warmstart": the last plan's waypoints relative to where it started (count, 2)
+        # flight: a flight_model.FlightModel, or None for perfect tracking; mission_id keys its gust stream
+        self.flight, self.settle_seconds, self.mission_id = flight, settle_seconds, mission_id
 
     # ---- :450-488
     def set_local_target(self, current_pos, seed=0):
@@ -112,7 +119,12 @@ class ReplanLoop:
                       np.append(self.des_state_array[self.future_index, 1, :], 0.0))
 
     def run(self, start_pos=(0.0, 0.0), start_vel=(0.0, 0.0), max_replans=60):
-        """fly to the goal; returns a dict of what the reference's metrics file records (:288-308)"""
+        """fly to the goal; returns a dict of what the reference's metrics file records (:288-308).  With a flight model
+        `path` is the flown positions (the whole array flown out, a landed mission's settle rows behind it), `commands` the
+        command array, fly_* the tracking-error record, its sample count and flags and the saturation count, `landed`
+        whether the plan near the goal was made and n_flown_planned the rows flown when planning stopped"""
+        if self.flight is not None:
+            return self._run_flown(start_pos, start_vel, max_replans)
         drone = _State(np.append(np.asarray(start_pos, float), self.des_pos_z), np.append(np.asarray(start_vel, float), 0.0))
         if not self._plan_with_retargeting(lambda: drone, drone.global_pos[:2]):      # first_plan :490-525
             return dict(success=False, replans=self.n_plans, path=np.zeros((0, 2)))
@@ -138,6 +150,43 @@ class ReplanLoop:
                     iter_num=self.planner.iter_num, opt_runs=self.planner.opt_running_times, path=path,
                     min_clearance=float(dists.min()), duration=path.shape[0] / self.cmd_hz,
                     max_speed=float(np.linalg.norm(self.des_state_array[:, 1, :], axis=1).max()))
+
+
+    def _run_flown(self, start_pos, start_vel, max_replans):
+        """`run` with a drone that lags: the same orchestration, the drone's position read from the flight"""
+        drone = _State(np.append(np.asarray(start_pos, float), self.des_pos_z), np.append(np.asarray(start_vel, float), 0.0))
+        if not self._plan_with_retargeting(lambda: drone, drone.global_pos[:2]):      # first_plan :490-525
+            return dict(success=False, replans=self.n_plans, path=np.zeros((0, 2)))
+        self.des_state_array = self.planner.get_full_state_cmd(self.cmd_hz)
+        self.des_state_index = 0
+        fl = flight_model.Flight(self.flight, self.cmd_hz, start_pos, start_vel, self.mission_id)
+        step = int(round(self.replan_period * self.cmd_hz))
+        ok = True
+        for _ in range(max_replans):
+            if self.near_global_target:
+                break
+            self.des_state_index = min(self.des_state_index + step, self.des_state_array.shape[0] - 1)
+            fl.advance(self.des_state_array, self.des_state_index)
+            ok = self._plan_with_retargeting(self.get_drone_state_ahead, fl.pos)      # :452: where the drone IS
+            if not ok:
+                break
+            new = self.planner.get_full_state_cmd(self.cmd_hz)
+            self.des_state_array = np.concatenate((self.des_state_array[:self.future_index], new), axis=0)   # :577
+        planned = fl.n      # rows flown when planning stopped
+        landed = bool(ok and self.near_global_target)
+        fl.advance(self.des_state_array, self.des_state_array.shape[0] - 1)
+        if landed:
+            fl.settle(self.des_state_array, self.global_target, int(round(self.settle_seconds * self.cmd_hz)),
+                      self.target_reach_threshold)
+        out = fl.result(self.des_state_array, int(round(self.cmd_hz * 0.1)))
+        path = out["flown"][:, 0, :]
+        reached = ok and np.linalg.norm(path[-1] - self.global_target) < self.target_reach_threshold
+        dists = np.array([self.map.get_edt_dis(p) for p in path[::6]])
+        out.update(success=bool(reached), replans=self.n_plans, failed_attempts=self.n_failed_attempts,
+                   iter_num=self.planner.iter_num, opt_runs=self.planner.opt_running_times, path=path,
+                   commands=self.des_state_array, landed=landed, n_flown_planned=planned, min_clearance=float(dists.min()), duration=path.shape[0] / self.cmd_hz,
+                   max_speed=float(np.linalg.norm(out["flown"][:, 1, :], axis=1).max()))
+        return out
 
 
 class TrackerLoop(ReplanLoop):
@@ -172,6 +221,7 @@ class TrackerLoop(ReplanLoop):
         self.des_state_index = 0
         failed_ticks = 0
         goals = np.zeros((ticks + 1, 2))
+        fl = None if self.flight is None else flight_model.Flight(self.flight, self.cmd_hz, start_pos, start_vel, self.mission_id)
         for k in range(ticks + 1):
             self.global_target = goals[k] = routes_of_one.at((k * step) / self.cmd_hz)[0]
             have = self.des_state_array.shape[0]
@@ -180,8 +230,12 @@ class TrackerLoop(ReplanLoop):
                 if have < need:      # out of commands before the period is over: hold the last one
                     self.des_state_array = np.concatenate((self.des_state_array, np.repeat(self.des_state_array[-1:], need - have, axis=0)))
                 self.des_state_index += step
+                if fl is not None:
+                    fl.advance(self.des_state_array, self.des_state_index)
             if self.des_state_array.shape[0] >= 1:
                 cur, start_fn = self.des_state_array[self.des_state_index, 0, :], self.get_drone_state_ahead
+                if fl is not None:
+                    cur = fl.pos
             else:      # nothing planned yet: the first plan, from where the drone stands
                 cur, start_fn, self.future_index = drone.global_pos[:2], (lambda: drone), 0
             if not self._plan_with_retargeting(start_fn, cur):
@@ -190,6 +244,12 @@ class TrackerLoop(ReplanLoop):
             new = self.planner.get_full_state_cmd(self.cmd_hz)
             self.des_state_array = np.concatenate((self.des_state_array[:self.future_index], new), axis=0)   # :430
         n_flown = min(self.des_state_index + 1, self.des_state_array.shape[0])
+        if fl is not None:      # the flown rows stand in for the command rows; the commands stay next to them
+            out = fl.result(self.des_state_array, int(round(self.cmd_hz * 0.1)))
+            out.update(replans=self.n_plans, failed_attempts=self.n_failed_attempts, failed_ticks=failed_ticks,
+                       iter_num=self.planner.iter_num, opt_runs=self.planner.opt_running_times, commands=self.des_state_array,
+                       n_flown=n_flown, path=out["flown"][:n_flown, 0, :], goals=goals)
+            return out
         return dict(replans=self.n_plans, failed_attempts=self.n_failed_attempts, failed_ticks=failed_ticks,
                     iter_num=self.planner.iter_num, opt_runs=self.planner.opt_running_times,
                     commands=self.des_state_array, n_flown=n_flown, path=self.des_state_array[:n_flown, 0, :], goals=goals)
