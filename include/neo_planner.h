@@ -386,6 +386,36 @@ int neo_geo_search_batch(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, i
 int neo_geo_search_batch_dev(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, const double *start,
                              const double *target, int max_expansions, int path_cap, double *key_pts, double *path,
                              int32_t *path_len, double *path_cost, int32_t *expansions, int32_t *flags);
+/* The geo warm start on RESIDENT arrays, ONE launch, asynchronous on the context's stream: search, prune and the pack of
+ * the optimiser's first guess over a launch list.  Position p works on request subset[p] (a device array of `count`
+ * indices), or on p when subset is NULL (all B; count is then ignored); an index outside 0 .. B - 1 is skipped and its
+ * rows stay.  Every pointer
+ * is a device array indexed by REQUEST, except tau3:
+ *   slots[B]          2-D map-table slots (neo_scene_slot), or NULL: every request uses scene_id;
+ *   head, tail        [B][3][2], read where they lie: start = head[b][0], target = tail[b][0]; the velocity and
+ *                     acceleration rows are not read;
+ *   tau3              HOST pointer to the three start values of tau (map_T2tau of init_T * [1.5, 1, 1.5]), read before
+ *                     the call returns;
+ *   x0[B][7]          = [k1.x, k2.x, k1.y, k2.y, tau3[0], tau3[1], tau3[2]], k1 and k2 the two inner key nodes: the x
+ *                     neo_optimize_batch_from_dev / neo_plan_guess_dev take as a start, with M = 3, D = 2;
+ *   key_pts, path_len, path_cost, expansions, flags   as neo_geo_search_batch_dev writes them.  A request without a path
+ *                     has four equal key nodes, the target cell; a slot outside the table gives NaN key nodes and
+ *                     waypoints (tau as above), path_cost NaN and NEO_GEO_FLAG_BAD_SCENE.
+ * direct: 0 -- the search reads the scenes' blocked masks (built on first use, rebuilt when a map changes: an
+ * allocation, a wait and a launch per changed scene of the table).  Non-zero -- the DIRECT form: a cell is blocked iff
+ * the map's nearest-cell distance at its position is < 0.5, evaluated on the map's 32-byte records where the search needs
+ * it, by the very function the mask is built with; no mask is built or read for any scene of the table.  The results of
+ * the two forms are equal.  Direct is the form for maps that change between calls (onboard maps); the masked form
+ * reads less per expansion on a map that stays.
+ * Errors, before anything is launched: B < 1, count outside 0 .. B with a subset, max_expansions < 0 or a NULL
+ * required buffer (slots and subset may be NULL): NEO_ERR_INVALID; scene_id without a map: NEO_ERR_NO_MAP; a 3-D scene:
+ * NEO_ERR_UNSUPPORTED.  An empty list launches nothing. */
+int neo_geo_guess_dev(neo_ctx *ctx, int scene_id, const int32_t *slots, int B, const int32_t *subset, int count,
+                      const double *head, const double *tail, const double *tau3, int max_expansions, int direct,
+                      double *x0, double *key_pts, int32_t *path_len, double *path_cost, int32_t *expansions,
+                      int32_t *flags);
+/* blocked masks built since the context was created (a diagnostic: the direct form builds none) */
+int neo_geo_mask_builds(neo_ctx *ctx, int64_t *count);
 /* prune_path_nodes alone on caller-given host paths[b][path_stride][2] of path_len[b] (1 <= path_len[b] <= path_stride)
  * nodes: key_pts[b][4][2] */
 int neo_geo_prune_batch(neo_ctx *ctx, int scene_id, const int32_t *scene_ids, int B, const double *paths,

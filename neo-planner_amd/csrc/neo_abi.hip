@@ -961,9 +961,36 @@ int neo_geo_search_batch_dev(neo_ctx *c, int scene_id, const int32_t *scene_ids,
   if (rc) return rc;
   rc = geo_scene_kind(c, scene_id);
   if (rc) return rc;
-  const GeoArgs ga{B, scene_ids, start, target, max_expansions, path ? path_cap : 0, key_pts, path, path_cost,
-                   path_len, expansions, flags};
+  const GeoArgs ga{launch_list(B, nullptr, 0), scene_ids, start, target, 2, max_expansions, path ? path_cap : 0, key_pts,
+                   path, path_cost, path_len, expansions, flags, nullptr, nullptr, false};
   return geo_search(c, scene_id, ga);
+}
+
+int neo_geo_guess_dev(neo_ctx *c, int scene_id, const int32_t *slots, int B, const int32_t *subset, int count,
+                      const double *head, const double *tail, const double *tau3, int max_expansions, int direct,
+                      double *x0, double *key_pts, int32_t *path_len, double *path_cost, int32_t *expansions,
+                      int32_t *flags) {
+  int rc = list_check(c, "geo guess", B, 1, INT32_MAX, subset, count);
+  if (rc) return rc;
+  if (max_expansions < 0) return fail_locked(c, NEO_ERR_INVALID, "geo guess: max_expansions must be >= 0");
+  rc = null_check(c, "geo guess: null buffer", {head, tail, tau3, x0, key_pts, path_len, path_cost, expansions, flags});
+  if (rc) return rc;
+  return list_launch(c, B, subset, count, [&](const LaunchList &list) {
+    int rc2 = rebuild_tables(c);
+    if (rc2) return rc2;
+    rc2 = geo_scene_kind(c, scene_id);
+    if (rc2) return rc2;
+    const GeoArgs ga{list, slots, head, tail, 6, max_expansions, 0, key_pts, nullptr, path_cost, path_len, expansions,
+                     flags, x0, tau3, direct != 0};
+    return geo_search(c, scene_id, ga);
+  });
+}
+
+int neo_geo_mask_builds(neo_ctx *c, int64_t *count) {
+  if (!c || !count) return NEO_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  *count = c->geo.mask_builds;
+  return NEO_OK;
 }
 
 int neo_geo_search_batch(neo_ctx *c, int scene_id, const int32_t *scene_ids, int B, const double *start,

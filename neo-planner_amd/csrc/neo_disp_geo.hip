@@ -36,20 +36,25 @@ static int geo_mask(neo_ctx *c, int scene_id, const MapEntry &e, const unsigned 
   hipLaunchKernelGGL(geo_mask_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, e.m2, We, He,
                      e.m2.res, oxe, oye, static_cast<unsigned *>(gm.bits));
   HIPCHK(c, hipGetLastError());
+  ++c->geo.mask_builds;
   gm.version = e.version;
   bits = static_cast<const unsigned *>(gm.bits);
   return NEO_OK;
 }
 
-// the call's scene table on the device: every 2-D map by map-table slot (with slots), or the one map of scene_id
-static int geo_table(neo_ctx *c, int scene_id, bool with_slots, int &nscenes, size_t &max_cells) {
+// the call's scene table on the device: every 2-D map by map-table slot (with slots), or the one map of scene_id.
+// direct: the scenes carry no mask (GeoScene::mask NULL) and none is built, whichever scenes the table holds; the two
+// forms keep a table each, so that calls of both kinds do not evict one another's.
+static int geo_table(neo_ctx *c, int scene_id, bool with_slots, bool direct, int &nscenes, size_t &max_cells) {
   std::vector<GeoScene> t;
   for (auto &kv : c->maps) {
     const MapEntry &e = kv.second;
     if (e.kind != 0 || (!with_slots && kv.first != scene_id)) continue;
     GeoScene g{};
-    int rc = geo_mask(c, kv.first, e, g.mask);
-    if (rc) return rc;
+    if (!direct) {
+      int rc = geo_mask(c, kv.first, e, g.mask);
+      if (rc) return rc;
+    }
     g.m = e.m2;
     geo_grid(e.m2, g.We, g.He, g.oxe, g.oye);
     g.res = e.m2.res;
@@ -61,16 +66,17 @@ static int geo_table(neo_ctx *c, int scene_id, bool with_slots, int &nscenes, si
   max_cells = 0;
   for (const GeoScene &g : t) max_cells = std::max(max_cells, (size_t)g.We * g.He);
   const size_t bytes = t.size() * sizeof(GeoScene);
-  GeoState &gs = c->geo;
-  if (gs.table_host.size() != bytes || memcmp(gs.table_host.data(), t.data(), bytes) != 0) {
-    if (gs.table) {
+  void *&table = c->geo.table[direct];
+  std::vector<char> &host = c->geo.table_host[direct];
+  if (host.size() != bytes || memcmp(host.data(), t.data(), bytes) != 0) {
+    if (table) {
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      hipFree(gs.table);
-      gs.table = nullptr;
+      hipFree(table);
+      table = nullptr;
     }
-    gs.table_host.assign(reinterpret_cast<const char *>(t.data()), reinterpret_cast<const char *>(t.data()) + bytes);
-    HIPCHK(c, hipMalloc(&gs.table, bytes));
-    HIPCHK(c, hipMemcpyAsync(gs.table, gs.table_host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    host.assign(reinterpret_cast<const char *>(t.data()), reinterpret_cast<const char *>(t.data()) + bytes);
+    HIPCHK(c, hipMalloc(&table, bytes));
+    HIPCHK(c, hipMemcpyAsync(table, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
   }
   return NEO_OK;
 }
@@ -88,7 +94,7 @@ static void geo_free_workspace(GeoState &gs) {
 }
 
 // slots of `cells` cells each, as many as the byte budget holds (at most kGeoMaxSlots), stamps cleared
-static int geo_workspace(neo_ctx *c, size_t cells, int B) {
+static int geo_workspace(neo_ctx *c, size_t cells, int n) {
   GeoState &gs = c->geo;
   const size_t per_slot = cells * (sizeof(GeoCell) + sizeof(GeoHeapEnt));
   const size_t fit = per_slot ? gs.budget / per_slot : 0;
@@ -96,7 +102,7 @@ static int geo_workspace(neo_ctx *c, size_t cells, int B) {
   if (want < 1)
     return fail(c, NEO_ERR_HIP, "geo: the workspace budget (" + std::to_string(gs.budget) + " bytes) holds no slot of " +
                                     std::to_string(per_slot) + " bytes");
-  const bool wrap = gs.searches + (unsigned long long)B >= kGeoEpochMax;
+  const bool wrap = gs.searches + (unsigned long long)n >= kGeoEpochMax;
   if (gs.cells && gs.cells_cap >= cells && gs.nslots == want && !wrap) return NEO_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (!(gs.cells && gs.cells_cap >= cells && gs.nslots == want)) {
@@ -124,19 +130,27 @@ static int geo_workspace(neo_ctx *c, size_t cells, int B) {
 int geo_search(neo_ctx *c, int scene_id, const GeoArgs &a) {
   int nscenes;
   size_t cells;
-  int rc = geo_table(c, scene_id, a.slots != nullptr, nscenes, cells);
+  const int n = a.list.size();  // the searches of this launch: what the epochs are charged
+  int rc = geo_table(c, scene_id, a.slots != nullptr, a.direct, nscenes, cells);
   if (rc) return rc;
-  rc = geo_workspace(c, cells, a.B);
+  rc = geo_workspace(c, cells, n);
   if (rc) return rc;
   GeoState &gs = c->geo;
   HIPCHK(c, hipMemsetAsync(gs.work, 0, sizeof(int), c->stream));
   const GeoOut o{a.key_pts, a.path, a.path_cost, a.path_len, a.expansions, a.flags, a.path_cap};
-  const int grid = std::min(gs.nslots, a.B);
-  hipLaunchKernelGGL(geo_search_kernel, dim3(grid), dim3(kWave), 0, c->stream, static_cast<const GeoScene *>(gs.table),
-                     a.slots, nscenes, a.B, a.start, a.target, a.max_exp, o, static_cast<GeoCell *>(gs.cells),
-                     static_cast<GeoHeapEnt *>(gs.heap), gs.cells_cap, gs.epochs, gs.work);
+  GeoIn in{a.list, a.start, a.target, a.stride, a.x0, {0.0, 0.0, 0.0}};
+  if (a.x0)
+    for (int k = 0; k < 3; ++k) in.tau[k] = a.tau[k];
+  const int grid = std::min(gs.nslots, n);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWave), 0, c->stream, static_cast<const GeoScene *>(gs.table[a.direct]),
+                       a.slots, nscenes, in, a.max_exp, o, static_cast<GeoCell *>(gs.cells),
+                       static_cast<GeoHeapEnt *>(gs.heap), gs.cells_cap, gs.epochs, gs.work);
+  };
+  if (a.direct) launch(geo_search_kernel<true>);
+  else launch(geo_search_kernel<false>);
   HIPCHK(c, hipGetLastError());
-  gs.searches += (unsigned long long)a.B;
+  gs.searches += (unsigned long long)n;
   return NEO_OK;
 }
 
@@ -144,9 +158,9 @@ int geo_prune(neo_ctx *c, int scene_id, int B, const int *slots, const double *p
               double *key_pts) {
   int nscenes;
   size_t cells;
-  int rc = geo_table(c, scene_id, slots != nullptr, nscenes, cells);
+  int rc = geo_table(c, scene_id, slots != nullptr, false, nscenes, cells);
   if (rc) return rc;
-  hipLaunchKernelGGL(geo_prune_kernel, dim3(B), dim3(kWave), 0, c->stream, static_cast<const GeoScene *>(c->geo.table),
+  hipLaunchKernelGGL(geo_prune_kernel, dim3(B), dim3(kWave), 0, c->stream, static_cast<const GeoScene *>(c->geo.table[0]),
                      slots, nscenes, B, paths, path_len, stride, key_pts);
   HIPCHK(c, hipGetLastError());
   return NEO_OK;
@@ -165,9 +179,11 @@ void geo_release(neo_ctx *c) {
     if (kv.second.bits) hipFree(kv.second.bits);
   gs.masks.clear();
   geo_free_workspace(gs);
-  if (gs.table) hipFree(gs.table);
-  gs.table = nullptr;
-  gs.table_host.clear();
+  for (int k = 0; k < 2; ++k) {
+    if (gs.table[k]) hipFree(gs.table[k]);
+    gs.table[k] = nullptr;
+    gs.table_host[k].clear();
+  }
 }
 
 }  // namespace neo

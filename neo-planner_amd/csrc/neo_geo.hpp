@@ -17,9 +17,17 @@
 // epoch | state | parent direction) lives in the slot's global workspace; the epoch stamp of a search makes every cell
 // of earlier searches "unvisited", so nothing is cleared between requests.  After the search the whole wavefront prunes
 // the path, which lane 0 has written into the slot's (then unused) global heap.
+//
+// Two forms of one kernel.  geo_search_kernel<false> reads a cell's blocked bit from the scene's mask;
+// geo_search_kernel<true> (the DIRECT form) evaluates geo_cell_blocked, the expression the mask is built from, on the
+// map's records where it needs a cell: no mask has to exist, which is what a map that changes every tick wants.  The two
+// give equal results by construction.  The requests of a launch are a LaunchList (neo_launch_list.hpp) over rows of
+// caller arrays with a row stride (GeoIn): the dense (B, 2) starts and targets, or head / tail [B][3][2] where they
+// lie; with GeoIn::x0 the lanes that write the key nodes also write the optimiser's first guess.
 #pragma once
 #include <climits>
 #include "neo_kernels.hpp"
+#include "neo_launch_list.hpp"
 
 namespace neo {
 
@@ -72,23 +80,38 @@ __device__ __forceinline__ bool geo_less(const GeoHeapEnt &a, const GeoHeapEnt &
 // math.hypot of integer differences (|dx|, |dy| < 2^26): the exact sum of squares, correctly rounded square root
 __device__ __forceinline__ double geo_hypot(long long dx, long long dy) { return __dsqrt_rn((double)(dx * dx + dy * dy)); }
 
-// ---------------------------------------------------------------- blocked mask: one thread per 32-cell word
+// ---------------------------------------------------------------- blocked cells
+// has_collision of the expanded cell (x, y): the map's nearest-cell distance at its position is below kGeoSafeDis.
+// Split like the lookup itself -- geo_cell_addr (index arithmetic), Lookup2D::load (the gather), geo_blocked_from -- so
+// that the direct search can put the eight gathers of an expansion in flight together; geo_cell_blocked is the three in
+// a row, what the mask holds a bit of.  `on` false: no cell (the address of a point outside the map: record 0, ignored).
+using GeoLookup = Lookup2D<double>;
+__device__ __forceinline__ GeoLookup::Addr geo_cell_addr(const GeoLookup &lk, double oxe, double oye, double res, int x,
+                                                         int y, bool on = true) {
+  const double pos[2] = {geo_real(oxe, (double)x, res), geo_real(oye, (double)y, res)};
+  return lk.prepare<2>(pos, on);
+}
+__device__ __forceinline__ bool geo_blocked_from(const GeoLookup &lk, const GeoLookup::Addr &a, const GeoLookup::Raw &q) {
+  double g[2];
+  return lk.finish<2>(a, q, g) < kGeoSafeDis;
+}
+__device__ __forceinline__ bool geo_cell_blocked(const GeoLookup &lk, double oxe, double oye, double res, int x, int y) {
+  const GeoLookup::Addr a = geo_cell_addr(lk, oxe, oye, res, x, y);
+  return geo_blocked_from(lk, a, lk.load(a));
+}
+
+// the blocked mask: one thread per 32-cell word
 __global__ void __launch_bounds__(256) geo_mask_kernel(Map2D m, int We, int He, double res, double oxe, double oye,
                                                        unsigned *mask) {
   const long long ncell = (long long)We * He;
   const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (w * 32 >= ncell) return;
-  const Lookup2D<double> lk(m);
+  const GeoLookup lk(m);
   unsigned bits = 0;
   for (int b = 0; b < 32; ++b) {
     const long long k = w * 32 + b;
     if (k >= ncell) break;
-    const int x = (int)(k % We), y = (int)(k / We);
-    const double pos[2] = {geo_real(oxe, (double)x, res), geo_real(oye, (double)y, res)};
-    double g[2];
-    bool inside;
-    const double d = lk.fetch<2>(pos, g, inside);
-    if (d < kGeoSafeDis) bits |= 1u << b;
+    if (geo_cell_blocked(lk, oxe, oye, res, (int)(k % We), (int)(k / We))) bits |= 1u << b;
   }
   mask[w] = bits;
 }
@@ -210,9 +233,33 @@ struct GeoOut {
   int path_cap;
 };
 
-__global__ void __launch_bounds__(kWave) geo_search_kernel(const GeoScene *scenes, const int *slots, int nscenes, int B,
-                                                           const double *start, const double *target, int max_exp,
-                                                           GeoOut o, GeoCell *cells_all, GeoHeapEnt *heap_all,
+// the requests of a launch: position p of `list` works on request b, whose start is start[b * stride ..+2] and whose
+// target is target[b * stride ..+2] (stride 2: dense arrays; 6: head / tail [B][3][2], the position rows).  x0 non-NULL:
+// request b's row x0[b][7] = [k1.x, k2.x, k1.y, k2.y, tau[0], tau[1], tau[2]] is written with its key nodes.
+struct GeoIn {
+  LaunchList list;
+  const double *start, *target;
+  int stride;
+  double *x0;
+  double tau[3];
+};
+
+// the key nodes of a request (lanes 0 - 7: node k = lane >> 1, coordinate d = lane & 1; `v` the lane's value) and, with
+// x0, its first guess: the inner nodes' lanes write the waypoints, lanes 0, 1 and 6 the three tau
+__device__ __forceinline__ void geo_write_result(const GeoIn &in, const GeoOut &o, int b, double v) {
+  const int lane = lane_id();
+  if (lane >= 8) return;
+  o.key_pts[(size_t)b * 8 + lane] = v;
+  if (!in.x0) return;
+  double *x0 = in.x0 + (size_t)b * 7;
+  const int k = lane >> 1, d = lane & 1;
+  if (k == 1 || k == 2) x0[2 * d + (k - 1)] = v;
+  else if (lane != 7) x0[4 + (lane == 6 ? 2 : lane)] = lane == 0 ? in.tau[0] : lane == 1 ? in.tau[1] : in.tau[2];
+}
+
+template <bool kDirect>
+__global__ void __launch_bounds__(kWave) geo_search_kernel(const GeoScene *scenes, const int *slots, int nscenes, GeoIn in,
+                                                           int max_exp, GeoOut o, GeoCell *cells_all, GeoHeapEnt *heap_all,
                                                            size_t cells_cap, unsigned *epochs, int *work) {
   __shared__ GeoHeapEnt lheap[kGeoHeapLds];
   __shared__ int sh_b;
@@ -226,9 +273,12 @@ __global__ void __launch_bounds__(kWave) geo_search_kernel(const GeoScene *scene
   for (;;) {
     if (lead) sh_b = atomicAdd(work, 1);
     __syncthreads();
-    const int b = sh_b;
+    const int p = sh_b;
     __syncthreads();
-    if (b >= B) break;
+    if (p >= in.list.n) break;
+    // (both exits below come after the fetch's barriers and are taken by the whole workgroup: p is the same in every lane)
+    const int b = in.list.request(p);
+    if (b < 0) continue;  // an index outside 0 .. B - 1: skipped, its rows stay
     const int s = slots ? slots[b] : 0;
     if (s < 0 || s >= nscenes) {
       if (lead) {
@@ -237,20 +287,22 @@ __global__ void __launch_bounds__(kWave) geo_search_kernel(const GeoScene *scene
         o.expansions[b] = 0;
         o.flags[b] = NEO_GEO_FLAG_BAD_SCENE;
       }
-      if (lane_id() < 8) o.key_pts[(size_t)b * 8 + lane_id()] = NAN;
+      geo_write_result(in, o, b, NAN);
       continue;
     }
     const GeoScene sc = scenes[s];
     if (lead) {
       const int We = sc.We, He = sc.He;
       const long long ncell = (long long)We * He;
+      const GeoLookup lk(sc.m);
+      const double *from = in.start + (size_t)b * in.stride, *to = in.target + (size_t)b * in.stride;
       bool oks, okt;
-      const double sxd = geo_index(start[2 * b], sc.oxe, sc.res, oks);
-      const double syd = geo_index(start[2 * b + 1], sc.oye, sc.res, okt);
+      const double sxd = geo_index(from[0], sc.oxe, sc.res, oks);
+      const double syd = geo_index(from[1], sc.oye, sc.res, okt);
       const bool s_ok = oks && okt;
       bool okx, oky;
-      const double txd = geo_index(target[2 * b], sc.oxe, sc.res, okx);
-      const double tyd = geo_index(target[2 * b + 1], sc.oye, sc.res, oky);
+      const double txd = geo_index(to[0], sc.oxe, sc.res, okx);
+      const double tyd = geo_index(to[1], sc.oye, sc.res, oky);
       const bool t_ok = okx && oky;
       const int sx = s_ok ? (int)sxd : 0, sy = s_ok ? (int)syd : 0;
       const int tx = t_ok ? (int)txd : 0, ty = t_ok ? (int)tyd : 0;
@@ -264,7 +316,8 @@ __global__ void __launch_bounds__(kWave) geo_search_kernel(const GeoScene *scene
         found = true;  // start == target: the path is the target cell, cost 0
       } else if (!s_ok || skey < 0 || skey >= ncell) {
         flags = NEO_GEO_FLAG_START_OUTSIDE;
-      } else if (!t_in || ((sc.mask[tkey >> 5] >> (tkey & 31)) & 1u)) {
+      } else if (!t_in || (kDirect ? geo_cell_blocked(lk, sc.oxe, sc.oye, sc.res, tx, ty)
+                                   : (((sc.mask[tkey >> 5] >> (tkey & 31)) & 1u) != 0))) {
         flags = NEO_GEO_FLAG_NO_PATH;  // unreachable: only in-range, free cells ever enter the open set
       } else {
         epoch = epoch + 1;
@@ -335,22 +388,33 @@ __global__ void __launch_bounds__(kWave) geo_search_kernel(const GeoScene *scene
           cur.tag = ep | (kGeoClosed << 3) | (cur.tag & 7u);
           ++nexp;
           // the eight neighbours: all gathers first, then the updates in motion-model order
+          // (masked: eight mask words; direct: eight map records)
           long long nk[8];
           bool ok[8];
           unsigned mw[8], tg[8];
           double gn[8];
+          GeoLookup::Addr ma[8];
+          GeoLookup::Raw mq[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             const int nx = cx + geo_mdx(j), ny = cy + geo_mdy(j);
             ok[j] = nx >= 0 && nx < We && ny >= 0 && ny < He;
             nk[j] = ok[j] ? (long long)nx + (long long)ny * We : 0;
-            mw[j] = sc.mask[nk[j] >> 5];
+            if constexpr (kDirect) {
+              ma[j] = geo_cell_addr(lk, sc.oxe, sc.oye, sc.res, nx, ny, ok[j]);
+              mq[j] = lk.load(ma[j]);
+            } else {
+              mw[j] = sc.mask[nk[j] >> 5];
+            }
             tg[j] = cells[nk[j]].tag;
             gn[j] = cells[nk[j]].g;
           }
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
-            if (!ok[j] || ((mw[j] >> (nk[j] & 31)) & 1u)) continue;
+            bool blocked;
+            if constexpr (kDirect) blocked = geo_blocked_from(lk, ma[j], mq[j]);
+            else blocked = ((mw[j] >> (nk[j] & 31)) & 1u) != 0;
+            if (!ok[j] || blocked) continue;
             const bool cur_ep = (tg[j] >> 5) == epoch;
             const unsigned st = cur_ep ? (tg[j] >> 3) & 3u : 0u;
             if (st == kGeoClosed) continue;
@@ -419,7 +483,7 @@ __global__ void __launch_bounds__(kWave) geo_search_kernel(const GeoScene *scene
     const int len = sh_res[0];
     int idx[4];
     geo_prune(sc.m, pbuf, len, idx);
-    geo_write_keys(pbuf, idx, o.key_pts + (size_t)b * 8);
+    geo_write_result(in, o, b, lane_id() < 8 ? pbuf[2 * idx[lane_id() >> 1] + (lane_id() & 1)] : 0.0);
     if (o.path)  // rows past the path: NaN
       for (int i = 2 * len + lane_id(); i < 2 * o.path_cap; i += kWave) o.path[(size_t)b * o.path_cap * 2 + i] = NAN;
     if (lead) {

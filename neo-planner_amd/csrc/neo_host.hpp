@@ -43,8 +43,10 @@ struct GeoState {
   int nslots = 0;
   unsigned long long searches = 0;  // requests launched since the stamps were last cleared
   size_t budget = size_t(2) << 30;
-  void *table = nullptr;         // device GeoScene[]
-  std::vector<char> table_host;  // what `table` holds
+  // device GeoScene[] and what it holds: [0] with the scenes' masks, [1] the direct form's, without any
+  void *table[2] = {nullptr, nullptr};
+  std::vector<char> table_host[2];
+  long long mask_builds = 0;     // geo_mask_kernel launches since the context was created (neo_geo_mask_builds)
 };
 
 // the depth camera's device state (neo_disp_depth.hip): the pixel tables of a call, and the images' maxima when the
@@ -421,14 +423,21 @@ int adaptive_count(neo_ctx *c, const LaunchList &l, int D, const double *head, c
 int adaptive_bucket(neo_ctx *c, const LaunchList &l, const int *counts, int *order, int *bucket_begin, int *total);
 int adaptive_compact(neo_ctx *c, const int *seg_begin, const int *seg_len, int *pending, int *n_failed);
 
-// neo_geo_search_batch_dev / neo_geo_prune_batch (neo_disp_geo.hip); the context is locked and its tables rebuilt
+// neo_geo_search_batch_dev / neo_geo_guess_dev / neo_geo_prune_batch (neo_disp_geo.hip); the context is locked and its
+// tables rebuilt.  The requests are `list` over rows of start / target with `stride` doubles a request (2: dense (B, 2)
+// arrays; 6: head / tail [B][3][2] where they lie); x0 [B][7] or NULL; tau: the three start values of x0 (HOST, read
+// with x0 only); direct: the search reads the maps' records, and no mask is built or read
 struct GeoArgs {
-  int B;
+  LaunchList list;
   const int *slots;  // device array [B] of 2-D map-table slots, or NULL (all requests use scene_id)
   const double *start, *target;
+  int stride;
   int max_exp, path_cap;
   double *key_pts, *path, *path_cost;
   int *path_len, *expansions, *flags;
+  double *x0;
+  const double *tau;
+  bool direct;
 };
 int geo_search(neo_ctx *c, int scene_id, const GeoArgs &a);
 int geo_prune(neo_ctx *c, int scene_id, int B, const int *slots, const double *paths, const int *path_len, int stride,

@@ -10,6 +10,7 @@ from ._lib import Context, NeoError, default_context  # noqa: F401
 from .esdf import ESDF, ESDF3D  # noqa: F401
 from .planner import BatchPlanner, MinJerkPlanner, PlannerConfig  # noqa: F401
 from .geo import GeoPlanner  # noqa: F401
+from .geo_resident import BatchGeoPlanner  # noqa: F401
 from .fleet import FleetReplanLoop  # noqa: F401
 from .goal_routes import GoalRoutes  # noqa: F401
 from .goal_sequences import GoalSequences  # noqa: F401
@@ -21,5 +22,5 @@ from .training import train_initializer  # noqa: F401  (torch and the network ar
 # the initializer network (torch) is imported on demand: `from neo_planner_amd import initializer`
 
 __all__ = ["Context", "NeoError", "default_context", "ESDF", "ESDF3D", "BatchPlanner", "MinJerkPlanner",
-           "PlannerConfig", "GeoPlanner", "FleetReplanLoop", "GoalRoutes", "GoalSequences", "FlightModel", "DepthCamera", "OnboardMapper", "DemoRecorder",
+           "PlannerConfig", "GeoPlanner", "BatchGeoPlanner", "FleetReplanLoop", "GoalRoutes", "GoalSequences", "FlightModel", "DepthCamera", "OnboardMapper", "DemoRecorder",
            "train_initializer"]

@@ -82,6 +82,7 @@ EXPORTS = [
     "neo_fleet_track_audit_dev",
     "neo_fleet_leg_close_dev", "neo_fleet_leg_open_dev", "neo_fleet_leg_goal",
     "neo_fleet_fly_dev", "neo_fleet_fly_error_dev",
+    "neo_geo_guess_dev", "neo_geo_mask_builds",
 ]
 
 
@@ -162,6 +163,8 @@ def load():
     L.neo_geo_search_batch_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i] + [c_p] * 6
     L.neo_geo_prune_batch.argtypes = [c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p]
     L.neo_geo_workspace_budget.argtypes = [c_p, ctypes.c_size_t]
+    L.neo_geo_guess_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i] + [c_p] * 6
+    L.neo_geo_mask_builds.argtypes = [c_p, ctypes.POINTER(ctypes.c_int64)]
     L.neo_fleet_target_batch.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_d, c_d, c_d] + [c_p] * 4
     L.neo_fleet_target_batch_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_d, c_d, c_d] + [c_p] * 4
     L.neo_fleet_advance_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p]

@@ -100,6 +100,14 @@ The gust of sub-step t is keyed by (model seed, mission id, t): a mission flies 
 the ticks cut its flight.  Every mode and option works but goal_sequences (campaigns re-open legs from command rows;
 carrying a drone state across legs is left out).  Without flight no launch, host read or allocation is added.
 
+With geo=BatchGeoPlanner (mode "geo" only; fleet_geo.py) the geo plans run on the resident arrays: every target round
+the pending missions' A* searches, the prune and the pack of the first guess are ONE launch (neo_geo_guess_dev) over the
+round's launch list, on the look-ahead states, the targets and the missions' map slots where they lie, and plan_dev takes
+the guess as attempt 0's start -- the host form's flights bit for bit.  It may be combined with onboard=: targets, search
+and optimiser then read the missions' own maps, and the search takes its direct form, which needs no blocked mask.
+Without geo= nothing changes: mode "geo" plans through the host, and resident=True and onboard= are refused for it as
+they always were; no launch, wait or allocation is added.
+
 Two streams, one rule.  torch works on its own stream, the context launches on another, and nothing orders the two but
 the host.  Every stage of the loop therefore goes: torch work (uploads, gathers, scatters), then `_torch_done`, then the
 context's launches, then `_ctx_done`, then torch or host reads of what they wrote.  A launch may only read a tensor torch
@@ -113,7 +121,7 @@ import numpy as np
 
 from . import _lib, counter_rng
 from .goal_routes import GoalRoutes
-from . import fleet_legs, fleet_flight
+from . import fleet_legs, fleet_flight, fleet_geo
 
 MAX_TARGETS = 11        # :429-445: seed 0 .. 10 are planned, the mission is abandoned after the plan of target 10 fails
 
@@ -141,7 +149,7 @@ def plan_seed(seed, tick, target):
 
 
 def _check_arguments(batch_planner, goals, mode, seed, scene_ids, mission_ids, resident, onboard, scenes, scene_index,
-                     record, neo, jitter, goal_routes, track_radius, metric_weights):
+                     record, neo, jitter, goal_routes, track_radius, metric_weights, geo=None):
     """FleetReplanLoop's refusals, in the order its callers meet them; returns the arguments it had to bring into shape
     on the way, by name"""
     counter = counter_rng.check_jitter(jitter, "FleetReplanLoop")
@@ -182,9 +190,9 @@ def _check_arguments(batch_planner, goals, mode, seed, scene_ids, mission_ids, r
             raise ValueError("FleetReplanLoop: modes 'neo' and 'nn' need scenes=(boxes, box_begin), what the cameras see")
     # the network's guess and the carried plan live on the device: resident plans always
     resident = bool(resident) or learned or mode == "warmstart"
-    if resident and mode == "geo":
+    if resident and mode == "geo" and geo is None:
         raise ValueError("FleetReplanLoop: resident=True needs mode 'basic' or 'batch' (geo_plan has no resident form)")
-    if onboard is not None and mode == "geo":
+    if onboard is not None and mode == "geo" and geo is None:
         raise ValueError("FleetReplanLoop: onboard maps need mode 'basic' or 'batch' (geo on onboard maps is not built)")
     if (onboard is not None or record is not None) and scenes is None:
         raise ValueError("FleetReplanLoop: onboard and record need scenes=(boxes, box_begin), what the cameras see")
@@ -207,7 +215,7 @@ def _check_arguments(batch_planner, goals, mode, seed, scene_ids, mission_ids, r
         raise ValueError("FleetReplanLoop: the recorder's M must be the planner's init_wpts_num + 1")
     if record is not None and record.ctx is not batch_planner.ctx:
         raise ValueError("FleetReplanLoop: the recorder and the planner must share one context")
-    return dict(counter=counter, goals=goals, track_radius=track_radius, metric_weights=metric_weights, resident=resident,
+    return dict(counter=counter, goals=goals, track_radius=track_radius, metric_weights=metric_weights, resident=resident or geo is not None,
                 seed=seed, scene_index=scene_index, scene_ids=scene_ids, mission_ids=mission_ids)
 
 
@@ -292,18 +300,23 @@ class FleetReplanLoop:
     them (module docstring); settle_seconds: how long a landed mission may hold its last command until it is within
     target_reach_threshold of the goal.  The result gains fly_<field> for _lib.FLY_FIELDS, fly_count, fly_flags and
     fly_saturated; n_flown counts flown rows (a landed mission's settle rows included) and flown_rows(i) returns them.
-    Refused with goal_sequences."""
+    Refused with goal_sequences.
+    geo: a BatchGeoPlanner (geo_resident.py) built on this batch_planner, mode "geo" only, init_wpts_num = 2 -- the geo
+    plans run on the resident arrays (module docstring), the same flights as the host form's; resident plans always; may
+    be combined with onboard (the direct search on the missions' own maps), record, flight and either jitter.  Without
+    it mode "geo" still refuses resident=True and onboard, in the same words."""
 
     def __init__(self, batch_planner, map, goals, mode="basic", cmd_hz=60, replan_period=1.0, planning_time_ahead=1.0,
                  longitu_step_dis=5.0, lateral_step_length=1.0, target_reach_threshold=0.2, max_cmd_seconds=120, seed=0,
                  scene_ids=None, mission_ids=None, metric_eva_interval=0.1, resident=False, onboard=None, scenes=None,
                  scene_index=None, des_pos_z=2.0, record_poses=False, record=None, neo=None, jitter="numpy",
                  goal_routes=None, track_radius=1.0, metric_weights=None, goal_sequences=None, leg_timeout=None, max_legs=None,
-                 flight=None, settle_seconds=2.0):
+                 flight=None, settle_seconds=2.0, geo=None):
         self.flight, self.settle_seconds, self._fly_model = fleet_flight.check_arguments(flight, settle_seconds, goal_sequences, cmd_hz)
+        self.geo = fleet_geo.check_arguments(geo, mode, batch_planner)
         goals, self.leg_timeout, self.max_legs = fleet_legs.check_arguments(goal_sequences, leg_timeout, max_legs, goals, goal_routes, mode)
         a = _check_arguments(batch_planner, goals, mode, seed, scene_ids, mission_ids, resident, onboard, scenes, scene_index,
-                             record, neo, jitter, goal_routes, track_radius, metric_weights)
+                             record, neo, jitter, goal_routes, track_radius, metric_weights, self.geo)
         self.counter, self.jitter, self.seed = a["counter"], jitter, a["seed"]
         self.routes, self.track_radius, self.metric_weights = goal_routes, a["track_radius"], a["metric_weights"]
         self.bp, self.map, self.mode, self.resident = batch_planner, map, mode, a["resident"]
@@ -329,7 +342,7 @@ class FleetReplanLoop:
         # for the splice when it returns.  (The class's functions, not bound methods: the loop holds the command arrays, and
         # a reference to itself would leave their release to the cycle collector.)
         cls = type(self)
-        self._plan_step = {"basic": cls._plan_resident if self.resident else cls._plan_host, "geo": cls._plan_geo,
+        self._plan_step = {"basic": cls._plan_resident if self.resident else cls._plan_host, "geo": cls._plan_geo if self.geo is None else fleet_geo.plan_step,
                            "batch": cls._plan_batch, "neo": cls._plan_neo, "nn": cls._plan_nn, "warmstart": cls._plan_warm}[mode]
         self._fallback = cls._fallback_resident if self.resident else cls._fallback_host      # mode "batch"
         # who looks through the cameras once a tick, in this order: (its timing key, its function)
@@ -475,6 +488,8 @@ class FleetReplanLoop:
             self._dev.update(cur_vel=f(B, 2), feature=torch.zeros((B, 24), dtype=torch.float32, device=dev))
         if self.mode == "neo":      # the network's guess, attempt 0's start
             self._dev.update(x0=f(B, n))
+        if self.geo is not None:      # the geo guess, attempt 0's start
+            fleet_geo.alloc(self, f)
         if self.onboard is not None or self.record is not None or self.neo is not None:      # what the cameras see, and where from
             boxes, box_begin = self.scenes
             self._dev.update(pose=f(B, 5),
