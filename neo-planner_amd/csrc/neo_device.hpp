@@ -547,6 +547,7 @@ struct PlanDynamic {
   static constexpr bool fold_acc = false, fold_rows = false, pcr_mult = false, pcr_xch = false, sl_cache = false,
                         trace = false, coeff_out = false;  // (not read: every selector is the run-time value)
   static constexpr bool gather_ahead = false;  // the sample loop as it always was (minco_sample)
+  static constexpr bool hist_ahead = false;    // the two-loop recursion as loops for every col (DevBackend::direction)
 };
 // the plan opt_lds_plan produces for the all-fp32 kernels with lane = (piece, dimension) and n <= 128 variables:
 // accumulator fold, multipliers in LDS, exchange table in the staging buffer, lane cache, no trace, no coefficient store
@@ -557,6 +558,9 @@ struct PlanFixedX {
   // not a launch decision but a form of the sample loop only this plan's kernels take: the ESDF gathers of a round are
   // issued one round ahead of their use (minco_sample)
   static constexpr bool gather_ahead = true;
+  // likewise a form of the search direction: once the memory is full the two-loop recursion runs written out step by
+  // step, every (s, y) pair read from LDS once and one step ahead of its use (DevBackend::direction_full in neo_kernels.hpp)
+  static constexpr bool hist_ahead = true;
 };
 // a selector under a plan: its run-time value when the plan is dynamic, the plan's constant K otherwise
 template <class Plan, bool K>

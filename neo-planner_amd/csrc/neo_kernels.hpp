@@ -223,24 +223,31 @@ struct DevBackend {
   // pair of steps instead of ~90.  Same mathematics, another rounding (the fp64 modes keep the textbook form: their
   // iterates are pinned to SciPy's, tests/test_lbfgs_host.py).
   static constexpr bool kOwnDirection = sizeof(Num) == 4;
+  // the three dots of a pair of steps through one batched reduction
+  __device__ __forceinline__ void dot3(const Vec &a0, const Vec &b0, const Vec &a1, const Vec &b1, const Vec &a2, const Vec &b2,
+                                       Num &t0, Num &t1, Num &t2) const {
+    Num p0 = Num(0), p1 = Num(0), p2 = Num(0);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      p0 += a0.v[k] * b0.v[k];
+      p1 += a1.v[k] * b1.v[k];
+      p2 += a2.v[k] * b2.v[k];
+    }
+    Num unused;
+    wave_sum4((float)p0, (float)p1, (float)p2, 0.0f, t0, t1, t2, unused);
+  }
   __device__ __forceinline__ void direction(const Vec &g, Vec &d, int col, int head, int mm, Num theta) {
     if (col == 0) {
       neg(d, g);
       return;
     }
-    auto slot_of = [&](int k) { return head + k < mm ? head + k : head + k - mm; };
-    auto dot3 = [&](const Vec &a0, const Vec &b0, const Vec &a1, const Vec &b1, const Vec &a2, const Vec &b2, Num &t0, Num &t1,
-                    Num &t2) {
-      Num p0 = Num(0), p1 = Num(0), p2 = Num(0);
-#pragma unroll
-      for (int k = 0; k < NS; ++k) {
-        p0 += a0.v[k] * b0.v[k];
-        p1 += a1.v[k] * b1.v[k];
-        p2 += a2.v[k] * b2.v[k];
+    if constexpr (!Plan::dynamic && Plan::hist_ahead) {
+      if (col == NEO_LBFGS_M) {  // (mm is NEO_LBFGS_M: optimize_body)
+        direction_full(g, d, head, mm, theta);
+        return;
       }
-      Num unused;
-      wave_sum4((float)p0, (float)p1, (float)p2, 0.0f, t0, t1, t2, unused);
-    };
+    }
+    auto slot_of = [&](int k) { return head + k < mm ? head + k : head + k - mm; };
     copy(d, g);  // d plays q of the recursion
     Vec sA, yA, sB, yB;
     int k = col - 1;
@@ -283,6 +290,88 @@ struct DevBackend {
       const double b = rho_dot(A, yA, d);
       axpy(sdiff(mm + A, b), sA, d);
     }
+    scale(d, -1.0);
+  }
+  // ---- the same recursion for a full memory (col = m), written out step by step (a fixed plan's constant, Plan::hist_ahead).
+  // Above, every step begins with the LDS reads of its pairs and waits for them at once: the reduction, the coefficients and
+  // the axpy all follow that wait, 10 LDS round trips in series an iteration, and loop 2 reads every pair again.  The
+  // addresses depend on head and the lane alone, not on the recursion.  With col a constant every pair has registers of its
+  // own (4 NS a pair): each is read ONCE, one step ahead of its use in loop 1, and loop 2 reads nothing; alpha_k stays in a
+  // register between the loops instead of a lane of sreg; 1 / theta is formed ahead of the steps, off the chain between the
+  // loops.  The control flow is hist_walk_full (neo_lbfgs_dir.hpp), this struct its visitor.  Same pairs in the same order
+  // through the same expressions: the same bits as above (which optimize_dyn_kernel and the budgeted members keep for every
+  // col, and these kernels while the memory fills; tests/test_gpu_hist_ahead.py compares the two).
+  // No read has a condition around it -- a wait in front of a step's dots is a counted one, and one path into it that
+  // reads less makes it a wait for everything: the partly filled FLAT slot is read without an exec mask (a lane beyond n
+  // reads element 0 of the row) and `settle` puts the zeros of hist_get_sy there before the values are used.
+  template <int COL>
+  struct DirFull {
+    DevBackend &be;
+    Vec &d;
+    const Num inv_theta;
+    int off[NS];  // element of a FLAT slot this lane reads: its own, or 0 where it has none
+    Vec s[COL], y[COL];
+    Num alpha[COL];
+    __device__ __forceinline__ void settle(Vec &sv, Vec &yv) const {
+#pragma unroll
+      for (int k = kFull; k < NS; ++k)
+        if (lane_ge(be.t.n - k * kWave)) {
+          sv.v[k] = Num(0);
+          yv.v[k] = Num(0);
+        }
+    }
+    template <int K>
+    __device__ __forceinline__ void read(int slot) {
+      const Hist *ps = be.hist + slot * be.t.n, *py = be.hist + (be.m + slot) * be.t.n;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        s[K].v[k] = (Num)ps[off[k]];
+        y[K].v[k] = (Num)py[off[k]];
+      }
+    }
+    template <int KA, int KB>
+    __device__ __forceinline__ void pair1(int A, int B) {
+      settle(s[KA], y[KA]);
+      settle(s[KB], y[KB]);
+      Num t0, t1, t2;
+      be.dot3(s[KA], d, s[KB], d, s[KB], y[KA], t0, t1, t2);
+      const Num aA = rdlane(be.sreg, A) * t0;
+      const Num aB = rdlane(be.sreg, B) * (t1 - aA * t2);
+      alpha[KA] = aA;
+      alpha[KB] = aB;
+#pragma unroll
+      for (int q = 0; q < NS; ++q) d.v[q] = (d.v[q] - aA * y[KA].v[q]) - aB * y[KB].v[q];
+    }
+    template <int KA, int KB>
+    __device__ __forceinline__ void pair2(int A, int B) {
+      Num t0, t1, t2;
+      be.dot3(y[KA], d, y[KB], d, y[KB], s[KA], t0, t1, t2);
+      const Num cA = alpha[KA] - rdlane(be.sreg, A) * t0;              // alpha_k - beta_k
+      const Num cB = alpha[KB] - rdlane(be.sreg, B) * (t1 + cA * t2);
+#pragma unroll
+      for (int q = 0; q < NS; ++q) d.v[q] = (d.v[q] + cA * s[KA].v[q]) + cB * s[KB].v[q];
+    }
+    template <int K>
+    __device__ __forceinline__ void single1(int A) {
+      settle(s[K], y[K]);
+      const Num aA = (Num)be.rho_dot(A, s[K], d);
+      alpha[K] = aA;
+      be.axpy(-(double)aA, y[K], d);
+    }
+    template <int K>
+    __device__ __forceinline__ void single2(int A) {
+      const double b = be.rho_dot(A, y[K], d);
+      be.axpy((double)(alpha[K] - (Num)b), s[K], d);
+    }
+    __device__ __forceinline__ void seam() { be.scale(d, (double)inv_theta); }
+  };
+  __device__ __forceinline__ void direction_full(const Vec &g, Vec &d, int head, int mm, Num theta) {
+    copy(d, g);  // d plays q of the recursion
+    DirFull<NEO_LBFGS_M> w{*this, d, Num(1) / theta};
+    const int lane = lane_id();
+#pragma unroll
+    for (int k = 0; k < NS; ++k) w.off[k] = in_range(k, lane) ? k * kWave + lane : 0;
+    hist_walk_full<NEO_LBFGS_M>(head, mm, w);
     scale(d, -1.0);
   }
 

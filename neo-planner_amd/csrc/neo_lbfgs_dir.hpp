@@ -18,6 +18,55 @@ struct has_own_direction { static constexpr bool value = false; };
 template <class Backend>
 struct has_own_direction<Backend, std::enable_if_t<Backend::kOwnDirection>> { static constexpr bool value = true; };
 
+// ---- the paired recursion of the all-fp32 device backend (DevBackend::direction, neo_kernels.hpp) for a memory of exactly
+// COL pairs, written out step by step at compile time (Plan::hist_ahead: the form the fixed-plan kernels take once the
+// memory is full, col = m, which is where a run spends its iterations).  The control flow alone, host and device, with the
+// backend's work behind a visitor: tests/test_hist_schedule_cpu.py walks every COL in 1 .. 10 and every head with a visitor
+// that keeps books, DevBackend::direction_full with the one that computes (COL = m).
+// Loop 1 takes the pairs (k, k - 1) for k = COL - 1, COL - 3, ... and, for odd COL, ends on the single pair 0; then q is
+// scaled by 1 / theta; loop 2 takes (k, k + 1) for k = 0, 2, ... and, for odd COL, ends on the single pair COL - 1.  Pair
+// k lives in slot (head + k) mod m.  With every k a constant, every pair has registers of its own: a pair is read from
+// LDS ONCE, one step ahead of its use in loop 1, with no condition around any read, and loop 2 finds all of them where
+// loop 1 left them.
+//   V: template <int K> void read(int slot)                          issue the reads of pair K
+//      template <int KA, int KB> void pair1(int slotA, int slotB)    a loop 1 step on the pairs KA, KB (slots: the scalars)
+//      template <int KA, int KB> void pair2(int slotA, int slotB)    a loop 2 step
+//      template <int K> void single1(int slot), single2(int slot)    the single-pair steps
+//      void seam()                                                   q /= theta
+NEO_HD int hist_slot(int head, int k, int m) { return head + k < m ? head + k : head + k - m; }
+template <int K, class V>
+NEO_HD void hist_full_read1(int head, int m, V &v) {  // the pairs of the loop 1 step whose pair A is K (none: K < 0)
+  if constexpr (K >= 0) v.template read<K>(hist_slot(head, K, m));
+  if constexpr (K >= 1) v.template read<K - 1>(hist_slot(head, K - 1, m));
+}
+template <int K, class V>
+NEO_HD void hist_full_loop1(int head, int m, V &v) {
+  if constexpr (K >= 0) hist_full_read1<K - 2>(head, m, v);
+  if constexpr (K >= 1) {
+    v.template pair1<K, K - 1>(hist_slot(head, K, m), hist_slot(head, K - 1, m));
+    hist_full_loop1<K - 2>(head, m, v);
+  } else if constexpr (K == 0) {
+    v.template single1<0>(hist_slot(head, 0, m));
+  }
+}
+template <int COL, int K, class V>
+NEO_HD void hist_full_loop2(int head, int m, V &v) {
+  if constexpr (K + 1 < COL) {
+    v.template pair2<K, K + 1>(hist_slot(head, K, m), hist_slot(head, K + 1, m));
+    hist_full_loop2<COL, K + 2>(head, m, v);
+  } else if constexpr (K < COL) {
+    v.template single2<K>(hist_slot(head, K, m));
+  }
+}
+template <int COL, class V>
+NEO_HD void hist_walk_full(int head, int m, V &v) {
+  static_assert(COL >= 1, "at least one pair");
+  hist_full_read1<COL - 1>(head, m, v);
+  hist_full_loop1<COL - 1>(head, m, v);
+  v.seam();
+  hist_full_loop2<COL, 0>(head, m, v);
+}
+
 // d = -H g.  `scratch` vectors are the caller's (tmp, tmp2 of the run).
 template <class Backend>
 NEO_HD void lbfgs_direction(Backend &be, const typename Backend::Vec &g, typename Backend::Vec &d,
