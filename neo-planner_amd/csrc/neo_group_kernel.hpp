@@ -27,8 +27,11 @@ struct GroupBackend {
   double *sc;       // LDS [2m]
   LineSearch *lsp;  // LDS
   double *cst;      // LDS [12]
-  Hist *hist;       // LDS [2][m][n]
+  Hist *hist;       // LDS: fp32 pairs [m][n][2], records (s_e, y_e); fp64 pairs [2][m][n] (neo_lbfgs_dir.hpp hist_index, hist_index_rows)
   int m;
+  static constexpr bool kRecords = sizeof(Hist) == 4;  // (DevBackend::kRecords)
+  typedef Hist HistPair __attribute__((ext_vector_type(2)));  // (a group's region starts on a multiple of 8 bytes)
+  __device__ __forceinline__ HistPair *hist_rec(int slot) const { return reinterpret_cast<HistPair *>(hist) + hist_record(slot, 0, t.n); }
 
   __device__ GroupBackend(const DevParams &p, const MapT &mp) : prm(p), map(mp) {}
 
@@ -69,21 +72,41 @@ struct GroupBackend {
 #pragma unroll
     for (int k = 0; k < NS; ++k)
       if (k * W + gl < t.n) {
-        hist[slot * t.n + k * W + gl] = s.v[k];
-        hist[(m + slot) * t.n + k * W + gl] = y.v[k];
+        if constexpr (kRecords) {
+          hist_rec(slot)[k * W + gl] = HistPair{opaque(s.v[k]), opaque(y.v[k])};  // (opaque: DevBackend::hist_put)
+        } else {
+          hist[hist_index_rows(slot, k * W + gl, t.n, m, 0)] = s.v[k];
+          hist[hist_index_rows(slot, k * W + gl, t.n, m, 1)] = y.v[k];
+        }
       }
     lds_wave_sync();
   }
-  __device__ __forceinline__ void hist_get(int row, Vec &v) const {
+  template <int WHICH>
+  __device__ __forceinline__ void hist_get(int slot, Vec &v) const {
     const int gl = GroupLanes<W>::lane();
 #pragma unroll
-    for (int k = 0; k < NS; ++k) v.v[k] = (k * W + gl < t.n) ? hist[row * t.n + k * W + gl] : Num(0);
+    for (int k = 0; k < NS; ++k) {
+      const int e = k * W + gl;
+      v.v[k] = (e < t.n) ? hist[kRecords ? hist_index(slot, e, t.n, WHICH) : hist_index_rows(slot, e, t.n, m, WHICH)] : Num(0);
+    }
   }
-  __device__ __forceinline__ void hist_get_s(int slot, Vec &v) const { hist_get(slot, v); }
-  __device__ __forceinline__ void hist_get_y(int slot, Vec &v) const { hist_get(m + slot, v); }
+  __device__ __forceinline__ void hist_get_s(int slot, Vec &v) const { hist_get<0>(slot, v); }
+  __device__ __forceinline__ void hist_get_y(int slot, Vec &v) const { hist_get<1>(slot, v); }
+  // (fp32 pairs: a lane without an element reads record 0 of the pair and takes zeros, as in DevBackend::hist_get_sy)
   __device__ __forceinline__ void hist_get_sy(int slot, Vec &s, Vec &y) const {
-    hist_get(slot, s);
-    hist_get(m + slot, y);
+    if constexpr (kRecords) {
+      const int gl = GroupLanes<W>::lane();
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        const bool in = k * W + gl < t.n;
+        const HistPair r = hist_rec(slot)[in ? k * W + gl : 0];
+        s.v[k] = in ? r.x : Num(0);
+        y.v[k] = in ? r.y : Num(0);
+      }
+    } else {
+      hist_get<0>(slot, s);
+      hist_get<1>(slot, y);
+    }
   }
   __device__ __forceinline__ void sput(int i, double v) {
     sc[i] = v;

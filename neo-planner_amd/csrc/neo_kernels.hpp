@@ -116,7 +116,8 @@ struct DevBackend {
   using Scalar = opt_scalar_t<Num, NS>;
   LineSearchT<Scalar> *lsp;  // LDS: line-search state (wave-uniform)
   double *cst;      // LDS [12]: cost terms of the last evaluation / current x / previous x
-  // LDS [2][m][n]: the stored (s, y) pairs of this trajectory
+  // LDS: the stored (s, y) pairs of this trajectory -- fp32 pairs [m][n][2], element by element (neo_lbfgs_dir.hpp
+  // hist_index), fp64 pairs [2][m][n] (hist_index_rows)
   using Hist = std::conditional_t<PAIRS32, float, double>;
   Hist *hist;
   int npad, m;
@@ -170,34 +171,83 @@ struct DevBackend {
   // around their LDS accesses.
   static constexpr int kFull = NS == 3 ? 2 : NS / 2;
   __device__ __forceinline__ bool in_range(int k, int lane) const { return k < kFull || k * kWave + lane < t.n; }
+  // fp32 pairs lie in records (s_e, y_e) (neo_lbfgs_dir.hpp hist_index): a lane moves s and y of its element with one
+  // 8-byte access.  fp64 pairs keep the rows [2][m][n] (hist_index_rows) and their two 8-byte accesses: a record of doubles is
+  // one 16-byte read into four consecutive registers, and the members that have fp64 pairs fill their 256 registers --
+  // built and measured, they spilled more and cfg2 ran 0.6 - 0.8 % slower in the f32 and f64 modes (HISTORY.md).
+  static constexpr bool kRecords = sizeof(Hist) == 4;
+  typedef Hist HistPair __attribute__((ext_vector_type(2)));
+  __device__ __forceinline__ HistPair *hist_rec(int slot, int e) const {
+    return reinterpret_cast<HistPair *>(hist) + hist_record(slot, e, t.n);
+  }
   __device__ __forceinline__ void hist_put(int slot, const Vec &s, const Vec &y) {
     const int lane = lane_id();
+    if constexpr (kRecords) {
+      HistPair *p = hist_rec(slot, lane);
+      // (opaque: a record built straight from two elements of the caller's vectors is turned into a two-element LOAD of the
+      //  vector object plus an insert -- which then keeps that object, a vector of the optimiser's state, in private memory)
 #pragma unroll
-    for (int k = 0; k < NS; ++k)
-      if (in_range(k, lane)) {
-        hist[slot * t.n + k * kWave + lane] = (Hist)s.v[k];
-        hist[(m + slot) * t.n + k * kWave + lane] = (Hist)y.v[k];
-      }
+      for (int k = 0; k < NS; ++k)
+        if (in_range(k, lane)) p[k * kWave] = HistPair{(Hist)opaque(s.v[k]), (Hist)opaque(y.v[k])};
+    } else {
+#pragma unroll
+      for (int k = 0; k < NS; ++k)
+        if (in_range(k, lane)) {
+          hist[hist_index_rows(slot, k * kWave + lane, t.n, m, 0)] = (Hist)s.v[k];
+          hist[hist_index_rows(slot, k * kWave + lane, t.n, m, 1)] = (Hist)y.v[k];
+        }
+    }
     lds_wave_sync();
   }
-  __device__ __forceinline__ void hist_get(int row, Vec &v) const {
+  template <int WHICH>
+  __device__ __forceinline__ void hist_get(int slot, Vec &v) const {
     const int lane = lane_id();
-#pragma unroll
-    for (int k = 0; k < NS; ++k) v.v[k] = in_range(k, lane) ? (Num)hist[row * t.n + k * kWave + lane] : Num(0);
-  }
-  __device__ __forceinline__ void hist_get_s(int slot, Vec &v) const { hist_get(slot, v); }
-  __device__ __forceinline__ void hist_get_y(int slot, Vec &v) const { hist_get(m + slot, v); }
-  // s and y of one pair together: the partly filled last slot of both under ONE exec mask
-  __device__ __forceinline__ void hist_get_sy(int slot, Vec &s, Vec &y) const {
-    const int lane = lane_id();
-    const Hist *ps = hist + slot * t.n + lane, *py = hist + (m + slot) * t.n + lane;
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
-      s.v[k] = Num(0);
-      y.v[k] = Num(0);
-      if (in_range(k, lane)) {
-        s.v[k] = (Num)ps[k * kWave];
-        y.v[k] = (Num)py[k * kWave];
+      const int e = k * kWave + lane;
+      v.v[k] = in_range(k, lane) ? (Num)hist[kRecords ? hist_index(slot, e, t.n, WHICH) : hist_index_rows(slot, e, t.n, m, WHICH)] : Num(0);
+    }
+  }
+  __device__ __forceinline__ void hist_get_s(int slot, Vec &v) const { hist_get<0>(slot, v); }
+  __device__ __forceinline__ void hist_get_y(int slot, Vec &v) const { hist_get<1>(slot, v); }
+  // s and y of one pair together.  fp32 pairs: one record a FLAT slot; in the all-fp32 members no read has a condition -- a
+  // lane without an element in the partly filled last slot reads record 0 of the pair (inside the region, whatever lies
+  // behind it) and takes zeros.  The members with fp64 arithmetic fill the register file, and the two-waves ones with three
+  // FLAT slots (cfg5's) pay the address select and its selects to zero in spilled registers (57 and 63 -> 74): they read
+  // the record under the lane's mask (57 and 63); with four slots the select is the better one (47 and 80 -> 43;
+  // profiles/hist_pairs_kernel_resource_usage.txt).  fp64 pairs: the partly filled last slot of both rows under ONE exec mask.
+  static constexpr bool kMaskedRead = sizeof(Num) == 8 && NS == 3;
+  __device__ __forceinline__ void hist_get_sy(int slot, Vec &s, Vec &y) const {
+    const int lane = lane_id();
+    if constexpr (kRecords) {
+      const HistPair *p = hist_rec(slot, 0);
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        const bool in = in_range(k, lane);
+        if constexpr (kMaskedRead) {
+          s.v[k] = Num(0);
+          y.v[k] = Num(0);
+          if (in) {
+            const HistPair r = p[k * kWave + lane];
+            s.v[k] = (Num)r.x;
+            y.v[k] = (Num)r.y;
+          }
+        } else {
+          const HistPair r = p[in ? k * kWave + lane : 0];
+          s.v[k] = in ? (Num)r.x : Num(0);
+          y.v[k] = in ? (Num)r.y : Num(0);
+        }
+      }
+    } else {
+      const Hist *ps = hist + hist_index_rows(slot, lane, t.n, m, 0), *py = hist + hist_index_rows(slot, lane, t.n, m, 1);
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        s.v[k] = Num(0);
+        y.v[k] = Num(0);
+        if (in_range(k, lane)) {
+          s.v[k] = (Num)ps[k * kWave];
+          y.v[k] = (Num)py[k * kWave];
+        }
       }
     }
   }
@@ -302,14 +352,15 @@ struct DevBackend {
   // through the same expressions: the same bits as above (which optimize_dyn_kernel and the budgeted members keep for every
   // col, and these kernels while the memory fills; tests/test_gpu_hist_ahead.py compares the two).
   // No read has a condition around it -- a wait in front of a step's dots is a counted one, and one path into it that
-  // reads less makes it a wait for everything: the partly filled FLAT slot is read without an exec mask (a lane beyond n
-  // reads element 0 of the row) and `settle` puts the zeros of hist_get_sy there before the values are used.
+  // reads less makes it a wait for everything: the partly filled FLAT slot is read without an exec mask and without an
+  // address of its own (a lane beyond n reads the records that follow: the next pair's, behind the last pair
+  // hist_over_read_elems elements of whatever lies there -- the launcher admits this kernel only where that is the launch's
+  // own LDS, neo_launch_opt.hpp opt_plan_fixed) and `settle` puts the zeros of hist_get_sy there before the values are used.
   template <int COL>
   struct DirFull {
     DevBackend &be;
     Vec &d;
     const Num inv_theta;
-    int off[NS];  // element of a FLAT slot this lane reads: its own, or 0 where it has none
     Vec s[COL], y[COL];
     Num alpha[COL];
     __device__ __forceinline__ void settle(Vec &sv, Vec &yv) const {
@@ -322,11 +373,13 @@ struct DevBackend {
     }
     template <int K>
     __device__ __forceinline__ void read(int slot) {
-      const Hist *ps = be.hist + slot * be.t.n, *py = be.hist + (be.m + slot) * be.t.n;
+      // one address a pair: record `lane` of the slot, the next FLAT slot 64 records on (a compile-time offset)
+      const HistPair *p = be.hist_rec(slot, lane_id());
 #pragma unroll
       for (int k = 0; k < NS; ++k) {
-        s[K].v[k] = (Num)ps[off[k]];
-        y[K].v[k] = (Num)py[off[k]];
+        const HistPair r = p[k * kWave];
+        s[K].v[k] = (Num)r.x;
+        y[K].v[k] = (Num)r.y;
       }
     }
     template <int KA, int KB>
@@ -368,9 +421,6 @@ struct DevBackend {
   __device__ __forceinline__ void direction_full(const Vec &g, Vec &d, int head, int mm, Num theta) {
     copy(d, g);  // d plays q of the recursion
     DirFull<NEO_LBFGS_M> w{*this, d, Num(1) / theta};
-    const int lane = lane_id();
-#pragma unroll
-    for (int k = 0; k < NS; ++k) w.off[k] = in_range(k, lane) ? k * kWave + lane : 0;
     hist_walk_full<NEO_LBFGS_M>(head, mm, w);
     scale(d, -1.0);
   }
@@ -558,6 +608,8 @@ struct DevBackend {
 // evaluations -- the machine's vectors and scalars, the line search, the stored pairs and their rho, the cost terms --
 // goes to `st` (doubles: every fp32 value converts exactly both ways) and a later launch picks the run up at the very
 // evaluation it was about to make.  Layout: [64 scalars | x g t r d (n each) | rho / alpha lanes (64) | pairs (2 m n)].
+// The pairs are the LDS region as it stands, element for element (hist_index / hist_index_rows decide where a value lies,
+// here as there: a state is read by the build that wrote it).
 __host__ __device__ inline size_t opt_state_doubles(int n, int m) { return 64 + 5 * (size_t)n + kWave + 2 * (size_t)m * (size_t)n; }
 
 template <class BE, class Mach>

@@ -50,6 +50,19 @@ OptLds opt_lds_plan(int M, int flags, int stash = 0) {
   return l;
 }
 
+// The launch may run optimize_kernel's fixed plan (neo_kernels.hpp opt_plan_t): accumulator fold and multipliers in LDS
+// (pcr_off), the exchange table and the velocity stash within the staging buffer, and the written-out recursion's reads of
+// the partly filled FLAT slot -- which run past the last pair by hist_over_read_elems elements (neo_lbfgs_dir.hpp) --
+// inside the launch's own dynamic LDS: they land in the multipliers behind the pairs.  (M = 2 with one FLAT slot: 472 bytes
+// against 48 of multipliers -- not fixed.)  `plain`: no trace buffer, no flags bit 4096.
+template <int D, int NS, class LG, typename Num>
+bool opt_plan_fixed(const OptLds &l, int M, int stash, bool plain) {
+  const int n = D * (M - 1) + M;
+  const size_t pairs_end = (size_t)l.stage * 8 + (size_t)2 * NEO_LBFGS_M * n * sizeof(Num);  // (a fixed plan's pairs are Num = float)
+  return l.pcr_off != 0 && pcr_xch_elems(M, LG::dl(D)) * (int)sizeof(Num) <= l.stage * 8 && stash <= l.stage * 8 &&
+         pairs_end + (size_t)hist_over_read_elems(n, NS * kWave) * sizeof(Num) <= l.dyn && plain;
+}
+
 // one optimize_kernel instantiation on the context's stream
 template <int D, int NS, typename Real, class MapT, class LookupT, int WAVES, class LG, typename Num, bool BUDGET>
 int launch_opt_kernel(neo_ctx *c, const OptArgs &a) {
@@ -60,15 +73,13 @@ int launch_opt_kernel(neo_ctx *c, const OptArgs &a) {
   constexpr int stash = opt_gather_ahead<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>() ? velocity_stash_bytes(D) : 0;
   const OptLds l = opt_lds_plan<D, NS, Real, WAVES, LG, Num>(a.M, c->params.flags, stash);
   // optimize_kernel is compiled for ONE plan (neo_kernels.hpp opt_plan_t).  Where that is a fixed plan, it runs only the
-  // launches whose plan -- decided here, on the host -- is that one: accumulator fold and multipliers in LDS (pcr_off), the
-  // exchange table and the velocity stash within the staging buffer, no trace buffer.  Everything else (flags bit 4096,
-  // traces, an M whose multipliers do not fit) goes to optimize_dyn_kernel, which tests the selectors at run time.  The
-  // kernel checks nothing.
+  // launches whose plan -- decided here, on the host -- is that one (opt_plan_fixed).  Everything else (flags bit 4096,
+  // traces, an M whose multipliers do not fit or do not cover the recursion's reads behind the pairs) goes to
+  // optimize_dyn_kernel, which tests the selectors at run time.  The kernel checks nothing.
   using Plan = opt_plan_t<NS, LG, Num, BUDGET>;
   bool fixed = !Plan::dynamic;
   if constexpr (!Plan::dynamic)
-    fixed = l.pcr_off != 0 && pcr_xch_elems(a.M, LG::dl(D)) * (int)sizeof(Num) <= l.stage * 8 && stash <= l.stage * 8 &&
-            !c->trace && !c->trace_xg && !(c->params.flags & 4096);
+    fixed = opt_plan_fixed<D, NS, LG, Num>(l, a.M, stash, !c->trace && !c->trace_xg && !(c->params.flags & 4096));
   auto kernel = optimize_kernel<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>;
   if constexpr (!Plan::dynamic)  // (only the members with a fixed plan have the second form)
     if (!fixed) kernel = optimize_dyn_kernel<D, NS, Real, MapT, LookupT, WAVES, LG, Num, BUDGET>;

@@ -34,6 +34,21 @@ struct has_own_direction<Backend, std::enable_if_t<Backend::kOwnDirection>> { st
 //      template <int K> void single1(int slot), single2(int slot)    the single-pair steps
 //      void seam()                                                   q /= theta
 NEO_HD int hist_slot(int head, int k, int m) { return head + k < m ? head + k : head + k - m; }
+
+// ---- where the pairs live (every device backend; tests/test_hist_layout_cpu.py).  The region holds 2 m n elements.  fp32
+// pairs: the m pairs one after the other, and within a pair element e of s next to element e of y -- the two-element record (s_e, y_e).
+// A lane that holds element e of a FLAT slot fetches both with ONE access of twice the width, and the records of the FLAT
+// slots of a pair lie a compile-time distance apart (64 records): one address a pair.
+NEO_HD int hist_record(int slot, int e, int n) { return slot * n + e; }                                    // in records
+NEO_HD int hist_index(int slot, int e, int n, int which) { return hist_record(slot, e, n) * 2 + which; }  // which: 0 s, 1 y
+// fp64 pairs: the m rows of s, then the m rows of y (a 16-byte record is one read into four consecutive registers, which the
+// register-bound members that store fp64 pairs paid in spills and time: DevBackend::kRecords)
+NEO_HD int hist_index_rows(int slot, int e, int n, int m, int which) { return (which * m + slot) * n + e; }
+// The written-out recursion (hist_walk_full below, DevBackend::DirFull) reads the partly filled last FLAT slot without a
+// condition: a lane beyond n reads the records that follow, and behind the last pair that is memory behind the region --
+// so many elements of it (`lanes` = 64 * FLAT slots).  The launcher admits the form only where they lie inside the launch's
+// own dynamic LDS (neo_launch_opt.hpp); the values are replaced by zeros before any use.
+NEO_HD int hist_over_read_elems(int n, int lanes) { return (lanes - n) * 2; }
 template <int K, class V>
 NEO_HD void hist_full_read1(int head, int m, V &v) {  // the pairs of the loop 1 step whose pair A is K (none: K < 0)
   if constexpr (K >= 0) v.template read<K>(hist_slot(head, K, m));

@@ -49,6 +49,10 @@ __device__ __forceinline__ float opaque(float v) {
   asm volatile("" : "+v"(v));
   return v;
 }
+__device__ __forceinline__ double opaque(double v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
 // the same for a wave-uniform value (it stays in a scalar register)
 __device__ __forceinline__ int opaque_uniform(int v) {
   asm volatile("" : "+s"(v));
