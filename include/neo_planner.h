@@ -816,7 +816,8 @@ int neo_record_commit_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subs
  * What NeoPlanner.enhanced_traj_plan does between the depth image's 24 features and the optimiser, for B requests:
  *   motion (form_nn_input's vector) -> head (PlannerNet's dense layers) -> guess (the first guess neo_plan_guess_dev
  *   takes as x_init).
- * The image backbone is not part of it: its features come in as an array.  Device pointers only, asynchronous on the
+ * The image backbone is not part of it: its features come in as an array (neo_backbone_features_dev, below, makes
+ * them from the depth images).  Device pointers only, asynchronous on the
  * context's stream, one launch each.  Every array is indexed by REQUEST; `subset` (n_subset request indices, a device
  * array) names the requests launched, NULL = all B; an index outside 0 .. B - 1 is skipped and its rows stay.  A
  * request's results depend on neither B, the subset nor its position.  M = 3 pieces, D = 2.
@@ -850,6 +851,44 @@ int neo_init_head_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, 
  * fp64 log of the same argument. */
 int neo_init_guess_dev(neo_ctx *ctx, int B, const int32_t *subset, int n_subset, const float *out, const double *pose,
                        double *x0);
+
+/* ---- the image backbone in front of the warm start (nn_trainer/nn_trainer.py:119-122) --------------------------
+ * The `feature` rows neo_init_head_dev takes, from the depth images: the inference form of PlannerNet.img_backbone, a
+ * ResNet-18 with a one-channel stem and a 24-wide fc, in eval mode, all fp32.  Every BatchNorm is folded into the
+ * convolution in front of it when the blob is packed (w' = w g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps)):
+ * the device sees convolutions with a bias.  Activations are channels-last, [image][y][x][c].
+ * NEO_BACKBONE_FLOATS floats of the weight blob, in forward order:
+ *   the stem            W[7][7][1][64], b[64]
+ *   layer1 .. layer4    (64, 128, 256, 512 channels), two blocks each; a block is conv1 W[3][3][cin][cout], b[cout];
+ *                       conv2 W[3][3][cout][cout], b[cout]; and, in the first block of layers 2 .. 4 (stride 2), the
+ *                       downsample branch W[1][1][cin][cout], b[cout]
+ *   fc                  W[24][512] row-major, b[24]
+ * A convolution's W is [ky][kx][ci][co], the output channel fastest (torch's weight[co][ci][ky][kx], permuted).
+ * Summation: an output element of a convolution is one fp32 fmaf chain from its bias over the taps (ky, kx) row-major
+ * and, inside a tap, over the input channels in groups of 32, a group in the order 0, 16, 1, 17, ..., 15, 31; a padding tap
+ * contributes products with +0.  The average pool adds a channel's pixels in ascending order and divides by their count;
+ * the fc is one fmaf chain from its bias over k ascending.  So an image's features depend on neither n nor the image's
+ * position among the n: they are the same bits in any batch. */
+#define NEO_BACKBONE_FLOATS 11177752
+/* bytes of `workspace` for n images of H x W: three activation buffers of the largest layer output (the 64-channel
+ * output of the stem's pool for every but the smallest images).  0 for n <= 0, H or W < 1, or n * H * W >= 2^31. */
+size_t neo_backbone_workspace_bytes(int n, int H, int W);
+/* feature_out[n][24] from images_u8[n][H][W]: device pointers, 21 launches, asynchronous on the context's stream.  The
+ * stem (uint8 -> float, 7 x 7 stride 2, ReLU, 3 x 3 stride-2 max pool) is one fused kernel; the 3 x 3 and 1 x 1
+ * convolutions are implicit GEMMs on the f32 matrix instructions, columns = the flattened (image, y, x) of the output,
+ * with bias, residual and ReLU in the epilogue; the last kernel is the global average pool and the fc.  `workspace`
+ * (16-byte aligned, at least neo_backbone_workspace_bytes(n, H, W) bytes) is written and holds nothing afterwards; no other
+ * memory is touched.  Any H, W >= 1 is valid.  n = 0 launches nothing.
+ * NEO_ERR_INVALID before any launch, with a neo_last_error message: a NULL pointer, n < 0, H or W < 1,
+ * n * H * W >= 2^31, n_weights != NEO_BACKBONE_FLOATS, a misaligned or too small workspace. */
+int neo_backbone_features_dev(neo_ctx *ctx, const float *weights, size_t n_weights, const uint8_t *images_u8, int n, int H,
+                              int W, void *workspace, size_t workspace_bytes, float *feature_out);
+/* The same call for measurements: an event in front of the chain and one behind every launch, then it WAITS for the stream
+ * and writes the NEO_BACKBONE_LAUNCHES times between them, in milliseconds, to the HOST array launch_ms -- the stem;
+ * conv1, [downsample,] conv2 of the eight blocks in forward order; the pool and fc.  n >= 1. */
+#define NEO_BACKBONE_LAUNCHES 21
+int neo_backbone_launch_times(neo_ctx *ctx, const float *weights, size_t n_weights, const uint8_t *images_u8, int n, int H,
+                              int W, void *workspace, size_t workspace_bytes, float *feature_out, float *launch_ms);
 
 /* ---- the `batch` planner mode on resident arrays (traj_planner/expert_planner.py:103-168) ----------------
  * MinJerkPlanner.batch_plan optimises K laterally shifted initial guesses of one request and keeps the cheapest

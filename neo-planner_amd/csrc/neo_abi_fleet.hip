@@ -1,7 +1,7 @@
 // neo_abi_fleet.hip -- C ABI of libneo_planner_hip.so (include/neo_planner.h), the unit of the closed-loop missions: the
 // depth camera, onboard integration, the fleet replan loop, its goal routes and its campaigns, record mode and the learned warm start.
 // Argument checks here, the skeletons in neo_abi_util.hpp, the kernels behind the launchers of neo_disp_depth.hip,
-// neo_disp_onboard.hip, neo_disp_fleet.hip, neo_disp_record.hip and neo_disp_init.hip.
+// neo_disp_onboard.hip, neo_disp_fleet.hip, neo_disp_record.hip, neo_disp_init.hip and neo_disp_backbone.hip.
 #include "neo_abi_util.hpp"
 
 using namespace neo;
@@ -711,5 +711,61 @@ int neo_init_guess_dev(neo_ctx *c, int B, const int32_t *subset, int n_subset, c
   return list_launch(c, B, subset, n_subset, [&](const LaunchList &list) { return init_guess(c, list, out, pose, x0); });
 }
 
-}  // extern "C"
+// ---- the image backbone in front of the warm start (nn_trainer/nn_trainer.py:119-122; kernels: neo_backbone.hpp)
+size_t neo_backbone_workspace_bytes(int n, int H, int W) {
+  if (n <= 0 || H < 1 || W < 1 || (size_t)n * H * W > (size_t)INT32_MAX) return 0;
+  return backbone_workspace_bytes(n, H, W);
+}
 
+// the checks of a backbone call (context unlocked); n = 0 passes them
+static int backbone_check(neo_ctx *c, const float *weights, size_t n_weights, const uint8_t *images_u8, int n, int H, int W,
+                          void *workspace, size_t workspace_bytes, float *feature_out) {
+  if (!c) return NEO_ERR_INVALID;
+  if (n < 0 || H < 1 || W < 1) return fail_locked(c, NEO_ERR_INVALID, "backbone: n must be >= 0, H and W >= 1");
+  if ((size_t)n * H * W > (size_t)INT32_MAX)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone: n * H * W must stay below 2^31 (split the images over several calls)");
+  int rc = null_check(c, "backbone: null buffer", {weights, images_u8, workspace, feature_out});
+  if (rc) return rc;
+  if (n_weights != (size_t)NEO_BACKBONE_FLOATS)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone: n_weights must be NEO_BACKBONE_FLOATS (11177752)");
+  if (reinterpret_cast<uintptr_t>(workspace) % 16 || reinterpret_cast<uintptr_t>(weights) % 4)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone: workspace must be 16-byte aligned, weights 4-byte");
+  if (n > 0 && workspace_bytes < backbone_workspace_bytes(n, H, W))
+    return fail_locked(c, NEO_ERR_INVALID, "backbone: workspace smaller than neo_backbone_workspace_bytes(n, H, W)");
+  return NEO_OK;
+}
+
+int neo_backbone_features_dev(neo_ctx *c, const float *weights, size_t n_weights, const uint8_t *images_u8, int n, int H,
+                              int W, void *workspace, size_t workspace_bytes, float *feature_out) {
+  const int rc = backbone_check(c, weights, n_weights, images_u8, n, H, W, workspace, workspace_bytes, feature_out);
+  if (rc || n == 0) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  return launched(c, backbone_features(c, weights, images_u8, n, H, W, workspace, feature_out));
+}
+
+int neo_backbone_launch_times(neo_ctx *c, const float *weights, size_t n_weights, const uint8_t *images_u8, int n, int H, int W,
+                              void *workspace, size_t workspace_bytes, float *feature_out, float *launch_ms) {
+  int rc = backbone_check(c, weights, n_weights, images_u8, n, H, W, workspace, workspace_bytes, feature_out);
+  if (rc) return rc;
+  if (!launch_ms || n == 0) return fail_locked(c, NEO_ERR_INVALID, "backbone: launch times need launch_ms and n >= 1");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  // every exit destroys the events created so far; the first failing HIP call is the one reported
+  hipEvent_t ev[NEO_BACKBONE_LAUNCHES + 1] = {};
+  hipError_t e = hipSuccess;
+  const char *what = "hipEventCreate";
+  for (int i = 0; e == hipSuccess && i <= NEO_BACKBONE_LAUNCHES; ++i) e = hipEventCreate(&ev[i]);
+  if (e == hipSuccess) {
+    rc = launched(c, backbone_features(c, weights, images_u8, n, H, W, workspace, feature_out, ev));
+    if (!rc) what = "hipStreamSynchronize", e = hipStreamSynchronize(c->stream);
+    for (int i = 0; !rc && e == hipSuccess && i < NEO_BACKBONE_LAUNCHES; ++i)
+      what = "hipEventElapsedTime", e = hipEventElapsedTime(&launch_ms[i], ev[i], ev[i + 1]);
+  }
+  for (hipEvent_t &v : ev)
+    if (v) hipEventDestroy(v);
+  if (!rc && e != hipSuccess) rc = fail(c, NEO_ERR_HIP, std::string("backbone: ") + what + ": " + hipGetErrorString(e));
+  return rc;
+}
+
+}  // extern "C"

@@ -360,6 +360,13 @@ int init_head(neo_ctx *c, const LaunchList &l, const float *weights, const float
               const float *motion, float *out);
 int init_guess(neo_ctx *c, const LaunchList &l, const float *out, const double *pose, double *x0);  // T_min, T_max: the context's
 
+// neo_backbone_*: the image backbone in front of them (neo_disp_backbone.hip, kernels in neo_backbone.hpp): n uint8
+// images of H x W -> feature_out [n][24], 21 launches; `workspace` holds backbone_workspace_bytes(n, H, W) bytes.
+// events: NULL, or NEO_BACKBONE_LAUNCHES + 1 events recorded in front of the chain and behind every launch
+size_t backbone_workspace_bytes(int n, int H, int W);
+int backbone_features(neo_ctx *c, const float *weights, const unsigned char *images, int n, int H, int W, void *workspace,
+                      float *feature_out, hipEvent_t *events = nullptr);
+
 // neo_batch_*_dev: the `batch` planner mode on resident arrays (neo_disp_batch.hip, kernels in neo_batch.hpp).  P =
 // the list's n requests; tau, off and w are HOST arrays (M, K and 4 values), handed to the kernels by value.
 struct BatchCandArgs {

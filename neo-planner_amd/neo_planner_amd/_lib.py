@@ -51,6 +51,7 @@ NEO_BATCH_MAX_CANDIDATES = 8       # neo_batch_*: candidates a request
 NEO_DEPTH_MAX_BOXES = 1024         # neo_depth_*: boxes a scene
 # neo_init_*: sizes of the motion vector, a feature row, the network's output, x0, and the head's weight blob
 NEO_INIT_MOTION, NEO_INIT_FEATURE, NEO_INIT_OUTPUT, NEO_INIT_X, NEO_INIT_HEAD_FLOATS = 24, 24, 9, 7, 20817
+NEO_BACKBONE_FLOATS, NEO_BACKBONE_LAUNCHES = 11177752, 21     # neo_backbone_*: the weight blob, launches a call
 
 # every symbol include/neo_planner.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -83,6 +84,7 @@ EXPORTS = [
     "neo_fleet_leg_close_dev", "neo_fleet_leg_open_dev", "neo_fleet_leg_goal",
     "neo_fleet_fly_dev", "neo_fleet_fly_error_dev",
     "neo_geo_guess_dev", "neo_geo_mask_builds",
+    "neo_backbone_workspace_bytes", "neo_backbone_features_dev", "neo_backbone_launch_times",
 ]
 
 
@@ -216,6 +218,10 @@ def load():
     L.neo_init_motion_dev.argtypes = [c_p, c_i, c_p, c_i] + [c_p] * 5
     L.neo_init_head_dev.argtypes = [c_p, c_i, c_p, c_i, c_p, ctypes.c_size_t, c_p, c_i, c_p, c_p]
     L.neo_init_guess_dev.argtypes = [c_p, c_i, c_p, c_i] + [c_p] * 3
+    L.neo_backbone_workspace_bytes.argtypes = [c_i, c_i, c_i]
+    L.neo_backbone_workspace_bytes.restype = ctypes.c_size_t
+    L.neo_backbone_features_dev.argtypes = [c_p, c_p, ctypes.c_size_t, c_p, c_i, c_i, c_i, c_p, ctypes.c_size_t, c_p]
+    L.neo_backbone_launch_times.argtypes = L.neo_backbone_features_dev.argtypes + [c_p]
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]
@@ -293,6 +299,10 @@ class Context:
         """the status-returning entry point `name` on this context; raises on its error code.  `lib` is looked up at
         call time: a recording proxy stands in by replacing it"""
         self.check(getattr(self.lib, name)(self.h, *args))
+
+    def backbone_workspace_bytes(self, n, H, W):
+        """neo_backbone_workspace_bytes: what neo_backbone_features_dev needs for n images of H x W"""
+        return int(self.lib.neo_backbone_workspace_bytes(int(n), int(H), int(W)))
 
     def set_params(self, **kw):
         for k, v in kw.items():

@@ -21,7 +21,7 @@ SOURCES = ["neo_abi.hip", "neo_disp_eval.hip", "neo_disp_sample.hip", "neo_disp_
            "neo_disp_opt3d_f64.hip", "neo_disp_opt3d_w2.hip", "neo_disp_opt3d_x.hip", "neo_disp_group.hip", "neo_disp_opt3d_b.hip",
            "neo_disp_audit.hip", "neo_disp_geo.hip", "neo_disp_fleet.hip", "neo_disp_batch.hip", "neo_disp_esdf.hip",
            "neo_disp_plan.hip", "neo_disp_depth.hip", "neo_disp_onboard.hip", "neo_disp_record.hip", "neo_disp_init.hip",
-           "neo_disp_adaptive.hip",
+           "neo_disp_adaptive.hip", "neo_disp_backbone.hip",
            # (the kernel-less units of the C ABI last: the units with device code keep their places in the link)
            "neo_abi_fleet.hip", "neo_abi_plan.hip"]
 HEADERS = ["neo_wave.hpp", "neo_device.hpp", "neo_kernels.hpp", "neo_host.hpp", "neo_launch_list.hpp", "neo_launch_opt.hpp", "neo_lbfgs.hpp",
@@ -68,7 +68,7 @@ UNIT_HEADERS = {"neo_abi.hip": ["neo_abi_util.hpp"], "neo_abi_fleet.hip": ["neo_
                 "neo_disp_esdf.hip": ["neo_esdf.hpp"], "neo_disp_plan.hip": ["neo_plan.hpp"],
                 "neo_disp_depth.hip": ["neo_depth.hpp"], "neo_disp_onboard.hip": ["neo_onboard.hpp"],
                 "neo_disp_record.hip": ["neo_record.hpp"], "neo_disp_init.hip": ["neo_init.hpp", "neo_record.hpp"],
-                "neo_disp_adaptive.hip": ["neo_adaptive.hpp"]}
+                "neo_disp_adaptive.hip": ["neo_adaptive.hpp"], "neo_disp_backbone.hip": ["neo_backbone.hpp"]}
 
 
 def _headers(src=None):

@@ -276,6 +276,105 @@ def pack_head_weights(net):
     return blob.contiguous()
 
 
+BACKBONE_FLOATS = 11177752      # NEO_BACKBONE_FLOATS (include/neo_planner.h)
+_BACKBONE_CHANNELS = (64, 128, 256, 512)
+
+
+def _fold_bn(conv, bn):
+    """conv + BatchNorm in eval mode as one convolution with a bias, in fp64: w' = w g / sqrt(var + eps) as
+    [ky][kx][ci][co], b' = beta - mean g / sqrt(var + eps)"""
+    w = conv.weight.detach().double().cpu()
+    scale = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    bias = bn.bias.detach().double().cpu() - bn.running_mean.detach().double().cpu() * scale
+    if conv.bias is not None:
+        bias = bias + conv.bias.detach().double().cpu() * scale
+    return (w * scale[:, None, None, None]).permute(2, 3, 1, 0).reshape(-1), bias
+
+
+def pack_backbone_weights(net, dtype=torch.float32):
+    """the weight blob of neo_backbone_features_dev (include/neo_planner.h): `net`.img_backbone (a PlannerNet's or a
+    PlannerNetConv's: the backbone is the same) with every BatchNorm folded into the convolution in front of it, folded in
+    fp64 and cast once -- NEO_BACKBONE_FLOATS float32 values in one tensor on `net`'s device.  Forward order: the stem,
+    the eight blocks (conv1, conv2, then the downsample branch where there is one), the fc; a convolution as
+    W [ky][kx][ci][co], then b [co]; the fc as W [24][512], then b [24].  dtype torch.float64 returns the fold before the
+    cast (what the fp32 blob is the once-rounded image of; the kernels take float32 only)."""
+    bb = net.img_backbone if hasattr(net, "img_backbone") else net
+    if not isinstance(bb, ResNet18OneChannel):
+        raise ValueError("pack_backbone_weights: a PlannerNet, a PlannerNetConv or their ResNet18OneChannel (got %s)"
+                         % type(net).__name__)
+    parts = list(_fold_bn(bb.conv1, bb.bn1))
+    for layer in (bb.layer1, bb.layer2, bb.layer3, bb.layer4):
+        for blk in layer:
+            parts += _fold_bn(blk.conv1, blk.bn1)
+            parts += _fold_bn(blk.conv2, blk.bn2)
+            if blk.downsample is not None:
+                parts += _fold_bn(blk.downsample[0], blk.downsample[1])
+    parts += [bb.fc.weight.detach().double().cpu().reshape(-1), bb.fc.bias.detach().double().cpu()]
+    blob = torch.cat(parts).to(dtype).contiguous()
+    if blob.numel() != BACKBONE_FLOATS:
+        raise ValueError("pack_backbone_weights: %d values, not NEO_BACKBONE_FLOATS: not the reference's ResNet-18" % blob.numel())
+    return blob.to(next(bb.parameters()).device)
+
+
+def backbone_model(blob, images):
+    """What the blob of pack_backbone_weights MEANS: the features (n, 24) float64 of images (n, H, W) (uint8 values), from
+    the blob alone, in fp64 on the CPU -- convolutions with a bias, ReLU, the 3 x 3 stride-2 max pool, the residual sums,
+    the mean over the pixels and the fc.  The yardstick of the kernels (tests/test_gpu_backbone.py)."""
+    F = torch.nn.functional
+    blob = torch.as_tensor(blob).detach().cpu().double().reshape(-1)
+    if blob.numel() != BACKBONE_FLOATS:
+        raise ValueError("backbone_model: the blob has NEO_BACKBONE_FLOATS = %d values" % BACKBONE_FLOATS)
+    x = torch.as_tensor(np.asarray(images.detach().cpu() if torch.is_tensor(images) else images)).double()
+    x = x.reshape(-1, 1, *x.shape[-2:])
+    at = [0]
+
+    def conv(x, ks, cin, cout, stride):
+        w = blob[at[0]:at[0] + ks * ks * cin * cout].reshape(ks, ks, cin, cout).permute(3, 2, 0, 1)
+        at[0] += ks * ks * cin * cout
+        b = blob[at[0]:at[0] + cout]
+        at[0] += cout
+        return F.conv2d(x, w, b, stride=stride, padding=ks // 2)
+
+    x = F.max_pool2d(F.relu(conv(x, 7, 1, 64, 2)), 3, 2, 1)
+    cin = 64
+    for li, cout in enumerate(_BACKBONE_CHANNELS):
+        for blk in range(2):
+            stride = 2 if (li > 0 and blk == 0) else 1
+            y = conv(F.relu(conv(x, 3, cin, cout, stride)), 3, cout, cout, 1)
+            idt = conv(x, 1, cin, cout, stride) if (stride != 1 or cin != cout) else x
+            x, cin = F.relu(y + idt), cout
+    w = blob[at[0]:at[0] + 24 * 512].reshape(24, 512)
+    b = blob[at[0] + 24 * 512:]
+    return (x.mean(dim=(2, 3)) @ w.T + b).numpy()
+
+
+def backbone_features_kernel(ctx, blob, images, out=None, chunk=512, workspace=None):
+    """neo_backbone_features_dev on `ctx`'s stream, `chunk` images a call: blob (pack_backbone_weights) and images (n, H, W)
+    uint8 are contiguous device tensors that are READY (torch.cuda.synchronize after torch wrote them).  Returns
+    (features (n, 24) float32, the workspace tensor used -- hand it back in to reuse it).  Asynchronous: ctx.synchronize()
+    before torch reads the features."""
+    from . import _lib
+    n, H, W = (int(s) for s in images.shape)
+    if images.dtype != torch.uint8 or not images.is_contiguous() or blob.dtype != torch.float32 or not blob.is_contiguous():
+        raise ValueError("backbone_features_kernel: contiguous tensors, images (n, H, W) uint8 and a float32 blob")
+    chunk = max(1, min(int(chunk), max(n, 1)))
+    need = ctx.backbone_workspace_bytes(chunk, H, W)
+    fresh = out is None
+    if out is None:
+        out = torch.empty((n, IMG_FEATURE_SIZE), dtype=torch.float32, device=images.device)
+    if workspace is None or workspace.numel() < need or workspace.device != images.device:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=images.device)
+        fresh = True
+    if fresh:
+        torch.cuda.synchronize(images.device)      # (the allocations are torch's: ready before the context's stream starts)
+    p = _lib.dev_ptr
+    for b0 in range(0, n, chunk):
+        k = min(chunk, n - b0)
+        ctx.call("neo_backbone_features_dev", p(blob), int(blob.numel()), p(images[b0:b0 + k]), k, H, W, p(workspace),
+                 int(workspace.numel()), p(out[b0:b0 + k]))
+    return out, workspace
+
+
 def raycast_depth(pillars, canopy=(), eye=(1.5, 0.0, 2.0), yaw=0.0, hfov_deg=87.0, max_range=20.0,
                   height=IMG_HEIGHT, width=IMG_WIDTH):
     """Synthetic depth image of a forest scene ("ray-cast of the pillars, 480 x 640"): a pinhole camera
@@ -385,6 +484,7 @@ class BatchInitializer:
             net = PlannerNet() if variant == "mlp" else PlannerNetConv()
         self.net = net.to(self.device).eval()
         self.T_min, self.T_max = T_min, T_max
+        self._backbone_blob = self._workspace = None      # the kernel backbone's packed weights and its activation buffers
 
     @torch.no_grad()
     def scene_feature(self, depth_norm):
@@ -392,14 +492,42 @@ class BatchInitializer:
         return self.net.image_features(img.reshape(1, 1, *img.shape[-2:]))
 
     @torch.no_grad()
-    def image_features(self, depth_u8, chunk=64):
+    def image_features(self, depth_u8, chunk=None, impl="torch", ctx=None):
         """features (B, 24) of B images (B, H, W), a device tensor or an array (DepthCamera's depth_u8): one feature per
-        request for `warm_start`.  The backbone runs `chunk` images at a time."""
+        request for `warm_start`.  The backbone runs `chunk` images at a time (None: 64 on the torch module, 512 on the
+        kernels, which fill the machine only across many images).  impl "torch" (the default): the torch
+        module; "kernel": neo_backbone_features_dev (csrc/neo_backbone.hpp) on `ctx`'s stream (None: the default
+        context) from uint8 images, float32 features that are complete when it returns."""
+        if impl not in ("torch", "kernel"):
+            raise ValueError("BatchInitializer.image_features: impl must be 'torch' or 'kernel'")
         img = torch.as_tensor(depth_u8) if not torch.is_tensor(depth_u8) else depth_u8
+        chunk = (512 if impl == "kernel" else 64) if chunk is None else chunk
+        if impl == "kernel":
+            from . import _lib
+            if self.device.type != "cuda":
+                raise ValueError("BatchInitializer.image_features: impl 'kernel' runs on the GPU (there is no CPU fallback)")
+            if img.dtype != torch.uint8:
+                raise ValueError("BatchInitializer.image_features: impl 'kernel' takes uint8 images")
+            ctx = ctx if ctx is not None else _lib.default_context(self.device.index or 0)
+            img = img.reshape(-1, *img.shape[-2:]).to(self.device).contiguous()
+            torch.cuda.synchronize(self.device)
+            feat, self._workspace = backbone_features_kernel(ctx, self.backbone_weights(), img, chunk=chunk,
+                                                             workspace=self._workspace)
+            ctx.synchronize()
+            return feat
         img = img.reshape(-1, 1, *img.shape[-2:])
         out = [self.net.image_features(img[b0:b0 + chunk].to(self.device, dtype=torch.float32))
                for b0 in range(0, img.shape[0], max(1, int(chunk)))]
         return torch.cat(out, dim=0)
+
+    def backbone_weights(self, refresh=False):
+        """the network's blob for neo_backbone_features_dev (pack_backbone_weights), packed at first use; refresh=True
+        packs it again after the network's parameters changed"""
+        if self._backbone_blob is None or refresh:
+            self._backbone_blob = pack_backbone_weights(self.net)
+            if self._backbone_blob.is_cuda:
+                torch.cuda.synchronize(self._backbone_blob.device)
+        return self._backbone_blob
 
     @torch.no_grad()
     def warm_start(self, scene_feature, motion, attitude_R, global_pos, clamp_ts=True):
@@ -430,7 +558,12 @@ class BatchNeoPlanner:
     vector, the network's dense layers and the first guess are the neo_init_* kernels on the context's stream
     (csrc/neo_init.hpp), and the guess goes to BatchPlanner.plan_dev as `x0` without passing through the host."""
 
-    def __init__(self, batch_planner, initializer, camera, des_pos_z=2.0):
+    def __init__(self, batch_planner, initializer, camera, des_pos_z=2.0, backbone_impl="torch"):
+        """backbone_impl: how `features_dev` runs the image backbone -- "torch" (the default: the torch module, im2col and
+        a GEMM per convolution on torch's stream) or "kernel" (neo_backbone_features_dev on the camera's context,
+        `backbone_chunk` images a call)"""
+        if backbone_impl not in ("torch", "kernel"):
+            raise ValueError("BatchNeoPlanner: backbone_impl must be 'torch' or 'kernel'")
         net = initializer.net
         if (camera.height, camera.width) != (net.img_height, net.img_width):
             raise ValueError("BatchNeoPlanner: the camera renders %d x %d, the network takes %d x %d"
@@ -439,6 +572,13 @@ class BatchNeoPlanner:
         self.chunk = 64          # images per render launch and backbone pass
         self.motion = self.out = self.x0 = None      # what the last warm_start_dev wrote: (B, 24) and (B, 9) float32, (B, 7) float64
         self._weights = self._own_x0 = None
+        self.backbone_impl = backbone_impl
+        # images per neo_backbone_features_dev call.  Measured on the MI355X (profiles/backbone.json, kernel_ms_by_chunk),
+        # 512 images of 160 x 120: 41.3 ms in chunks of 32, 22.6 of 64, 13.8 of 128, 10.4 of 256, 9.07 in one call -- the
+        # deeper layers fill the machine only across many images.  The workspace grows with it: 0.92 MB an image at
+        # 160 x 120 (472 MB for 512), 14.7 MB an image at 640 x 480; a caller short of memory lowers it.
+        self.backbone_chunk = 512
+        self._workspace = None
 
     def warm_start(self, scenes, drone_pos, drone_vel, local_vel, yaw, head, tail, scene_index=None):
         """scenes: the camera's scenes (DepthCamera.pack_scenes), scene_index (B,) the scene each request sees (None:
@@ -486,11 +626,30 @@ class BatchNeoPlanner:
             torch.cuda.synchronize(self._weights.device)
         return self._weights
 
+    def backbone_weights(self, refresh=False):
+        """the network's blob for neo_backbone_features_dev (pack_backbone_weights), packed at first use; refresh=True
+        packs it again after the network's parameters changed"""
+        return self.init.backbone_weights(refresh)
+
     @torch.no_grad()
     def features_dev(self, boxes, box_begin, pose, scene_index=None):
         """the image features (n, 24) float32 of what the camera sees from pose (n, 5): DepthCamera.render_dev's uint8
         images through the backbone, `chunk` images at a time (device tensors in and out; torch's stream has finished
-        when it returns)"""
+        when it returns).  With backbone_impl "kernel" the render launches and the backbone's are queued on the camera's
+        context one after the other, `backbone_chunk` images a call out of a workspace kept here, and the context's
+        stream has finished when it returns: nothing is handed over to torch's stream in between."""
+        if self.backbone_impl == "kernel":
+            weights = self.backbone_weights()
+            n, dev, ctx = int(pose.shape[0]), pose.device, self.camera.ctx
+            # (everything torch allocates comes first: render_dev waits for torch once, then both stages only queue)
+            feat = torch.empty((n, IMG_FEATURE_SIZE), dtype=torch.float32, device=dev)
+            need = ctx.backbone_workspace_bytes(max(1, min(self.backbone_chunk, n)), self.camera.height, self.camera.width)
+            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
+                self._workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            img = self.camera.render_dev(boxes, box_begin, pose, scene_index, chunk=self.chunk, want_m=False, sync=False)["depth_u8"]
+            backbone_features_kernel(ctx, weights, img, out=feat, chunk=self.backbone_chunk, workspace=self._workspace)
+            ctx.synchronize()
+            return feat
         img = self.camera.render_dev(boxes, box_begin, pose, scene_index, chunk=self.chunk, want_m=False)["depth_u8"]
         feat = self.init.image_features(img, chunk=self.chunk).to(torch.float32).contiguous()
         torch.cuda.synchronize(feat.device)

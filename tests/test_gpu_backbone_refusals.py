@@ -1,0 +1,61 @@
+"""neo_backbone_features_dev's argument errors: every refusal include/neo_planner.h lists returns NEO_ERR_INVALID with a
+neo_last_error text before anything is launched, and n = 0 is a no-op."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from neo_planner_amd import _lib
+
+pytestmark = pytest.mark.gpu
+
+NEO_ERR_INVALID = 1
+N, H, W = 2, 9, 13
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def test_refusals_and_the_empty_call():
+    import torch
+    dev = torch.device("cuda", 0)
+    c = _lib.default_context()
+    L = c.lib
+    need = int(L.neo_backbone_workspace_bytes(N, H, W))
+    blob = torch.zeros(_lib.NEO_BACKBONE_FLOATS, dtype=torch.float32, device=dev)
+    img = torch.zeros((N, H, W), dtype=torch.uint8, device=dev)
+    ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+    out = torch.full((N, 24), -7.25, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    good = dict(weights=_p(blob), n_weights=blob.numel(), images=_p(img), n=N, H=H, W=W, workspace=_p(ws), workspace_bytes=need,
+                out=_p(out))
+
+    def call(**change):
+        a = dict(good, **change)
+        return L.neo_backbone_features_dev(c.h, a["weights"], a["n_weights"], a["images"], a["n"], a["H"], a["W"], a["workspace"],
+                                           a["workspace_bytes"], a["out"])
+
+    bad = [dict(weights=None), dict(images=None), dict(workspace=None), dict(out=None), dict(n=-1), dict(H=0), dict(W=0),
+           dict(H=-3), dict(n_weights=blob.numel() - 1), dict(n_weights=blob.numel() + 1), dict(n_weights=0),
+           dict(workspace_bytes=need - 1), dict(workspace_bytes=0)]
+    for change in bad:
+        assert call(**change) == NEO_ERR_INVALID, change
+        assert b"backbone" in L.neo_last_error(c.h), change
+    assert L.neo_backbone_features_dev(None, *[good[k] for k in ("weights", "n_weights", "images", "n", "H", "W", "workspace",
+                                                                 "workspace_bytes", "out")]) == NEO_ERR_INVALID
+    assert call(n=0) == _lib.NEO_OK and call(n=0, workspace_bytes=0) == _lib.NEO_OK
+    c.synchronize()
+    assert (out.cpu().numpy() == np.float32(-7.25)).all()          # nothing was launched by any of them
+    assert call() == _lib.NEO_OK
+    c.synchronize()
+    got = out.cpu().numpy()
+    assert np.isfinite(got).all() and (got == 0.0).all()            # a zero blob: zero features
+    # the measuring form: the same checks, the same features, and a time for each of the 21 launches
+    ms = (ctypes.c_float * _lib.NEO_BACKBONE_LAUNCHES)()
+    a = good
+    args = (a["weights"], a["n_weights"], a["images"], a["n"], a["H"], a["W"], a["workspace"], a["workspace_bytes"], a["out"])
+    assert L.neo_backbone_launch_times(c.h, *args, None) == NEO_ERR_INVALID
+    assert L.neo_backbone_launch_times(c.h, *args[:1], 5, *args[2:], ms) == NEO_ERR_INVALID
+    assert L.neo_backbone_launch_times(c.h, *args, ms) == _lib.NEO_OK
+    assert all(0.0 < t < 1e3 for t in ms) and (out.cpu().numpy() == 0.0).all()

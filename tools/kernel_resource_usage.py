@@ -6,14 +6,14 @@
     python tools/kernel_resource_usage.py neo_disp_fleet.hip > profiles/flight_kernel_resource_usage.txt   (the named units only)
 
 Listed: the brick-layout instantiations of the bench's configurations, the budgeted kernels, the ESDF-lookup kernels,
-the depth camera's kernels, the record kernels, the warm-start (init) kernels, the two counter-based jitter kernels, the three goal-route kernels next to the flight audit's, the adaptive-count kernels, the plan chain's merge and the two compactions, the two flight-model kernels next to the advance."""
+the depth camera's kernels, the record kernels, the warm-start (init) kernels, the two counter-based jitter kernels, the three goal-route kernels next to the flight audit's, the adaptive-count kernels, the plan chain's merge and the two compactions, the two flight-model kernels next to the advance, the image backbone's kernels."""
 import concurrent.futures, os, re, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "neo-planner_amd"))
 from neo_planner_amd import build as b
 
 UNITS = ["neo_disp_opt3d_x.hip", "neo_disp_opt3d_w2.hip", "neo_disp_opt3d_f64.hip", "neo_disp_opt3d_b.hip", "neo_disp_sample.hip",
-         "neo_disp_group.hip", "neo_disp_depth.hip", "neo_disp_record.hip", "neo_disp_init.hip", "neo_disp_plan.hip", "neo_disp_fleet.hip", "neo_disp_adaptive.hip", "neo_disp_batch.hip"]
+         "neo_disp_group.hip", "neo_disp_depth.hip", "neo_disp_record.hip", "neo_disp_init.hip", "neo_disp_plan.hip", "neo_disp_fleet.hip", "neo_disp_adaptive.hip", "neo_disp_batch.hip", "neo_disp_backbone.hip"]
 JITTER_UNITS = ("neo_disp_plan.hip", "neo_disp_fleet.hip")
 if len(sys.argv) > 1:
     UNITS = [u for u in UNITS if u in sys.argv[1:]]
@@ -46,7 +46,7 @@ for src, err in results:
                                         "fleet_track_audit_kernel", "fleet_audit_kernel", "fleet_advance_kernel", "fleet_fly_kernel",
                                         "fleet_fly_error_kernel")):
                 continue
-        elif not ("_compact_kernel" in n or ", 3>" in n or "sample_kernel" in n or "group" in n or "depth_" in n or "record_" in n or "init_" in n or "adaptive_" in n):
+        elif not ("_compact_kernel" in n or ", 3>" in n or "sample_kernel" in n or "group" in n or "depth_" in n or "record_" in n or "init_" in n or "adaptive_" in n or "bb_" in n):
             continue
         if "sample_kernel" in n and "Lookup3D" in n and not re.search(r"Lookup3D<\w+, \w+, 3>", n):
             continue
