@@ -11,7 +11,7 @@
 // Included by neo_disp_adaptive.hip only.  fp64, D = 2 or 3.  Request-indexed arrays are indexed by request b; packed
 // arrays by the request's position p in the launch list (neo_launch_list.hpp).  No atomics, no scratch.
 #pragma once
-#include "neo_device.hpp"
+#include "neo_wave.hpp"
 #include "neo_launch_list.hpp"
 
 namespace neo {

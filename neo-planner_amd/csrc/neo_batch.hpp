@@ -11,7 +11,7 @@
 // writes) are indexed by request b; packed arrays by row p * K + k, p the request's position in the launch list
 // (neo_launch_list.hpp).  No atomics: the order of the compacted list follows from the positions alone.
 #pragma once
-#include "neo_device.hpp"
+#include "neo_wave.hpp"
 #include "neo_launch_list.hpp"
 
 namespace neo {

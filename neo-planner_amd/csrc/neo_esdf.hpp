@@ -7,7 +7,7 @@
 //
 // Launched from neo_disp_esdf.hip; the C ABI (neo_abi.hip) checks arguments and carves the scratch.
 #pragma once
-#include "neo_device.hpp"
+#include "neo_wave.hpp"
 
 namespace neo {
 

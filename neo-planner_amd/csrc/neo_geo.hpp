@@ -26,7 +26,7 @@
 // lie; with GeoIn::x0 the lanes that write the key nodes also write the optimiser's first guess.
 #pragma once
 #include <climits>
-#include "neo_kernels.hpp"
+#include "neo_map.hpp"
 #include "neo_launch_list.hpp"
 
 namespace neo {

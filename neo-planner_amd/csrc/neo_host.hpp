@@ -15,10 +15,16 @@
 #include <vector>
 
 #include "../../include/neo_planner.h"
-#include "neo_device.hpp"
+#include "neo_map.hpp"
 #include "neo_launch_list.hpp"
 
 namespace neo {
+// the lane-group policies of neo_device.hpp: visit_slots below only names them, the units that launch MINCO kernels
+// include their definitions
+struct WaveLanes;
+template <int>
+struct WaveLanesPD;
+
 struct MapEntry {
   int kind = -1;  // 0 = 2-D reference map, 1 = 3-D field
   int elem = NEO_F64;

@@ -11,7 +11,6 @@
 // order written here: NumPy gives the same bits (tests/init_oracle_np.py), the device's fp64 log apart.  Request-indexed
 // arrays throughout; lane / workgroup position p works on request list.request(p) (neo_launch_list.hpp).
 #pragma once
-#include "neo_device.hpp"
 #include "neo_launch_list.hpp"
 #define NEO_RECORD_HELPERS_ONLY  // record_to_body and the kRecord* sizes, not the recorder's kernels
 #include "neo_record.hpp"

@@ -1,6 +1,6 @@
 // neo_launch_list.hpp -- what the kernels that run on RESIDENT arrays share (fleet, record, onboard, batch, plan,
 // init and adaptive units): the list of a launch, the map table of a call, the six result arrays of an optimiser launch,
-// and the one-workgroup ordered rank with the in-place compaction built on it.  Included by neo_host.hpp and by the seven kernel headers; it needs nothing but HIP.
+// and the one-workgroup ordered rank with the in-place compaction built on it.  Included by neo_host.hpp and by the seven kernel headers; it needs nothing but HIP and the cross-lane layer (neo_wave.hpp).
 //
 // A launch covers n positions.  Position p works on request (mission) subset[p], or on p when there is no subset.  An
 // index outside 0 .. B - 1 is skipped: request() answers -1, the kernel returns, and every row of that index -- the
@@ -8,6 +8,8 @@
 // rows; packed arrays are indexed by position.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "neo_wave.hpp"
 
 namespace neo {
 

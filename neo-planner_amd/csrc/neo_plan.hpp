@@ -15,7 +15,7 @@
 // arrays by the request's position p in the launch list (neo_launch_list.hpp).  No atomics, no scratch.
 #pragma once
 #include "neo_counter_rng.hpp"
-#include "neo_device.hpp"
+#include "neo_wave.hpp"
 #include "neo_launch_list.hpp"
 
 namespace neo {

@@ -12,7 +12,6 @@
 // follows from its position in the launch and the counters alone.  Mission-indexed arrays are indexed by mission b; workgroup / lane k works on the mission at
 // position k of the launch list (neo_launch_list.hpp).
 #pragma once
-#include "neo_device.hpp"
 #include "neo_launch_list.hpp"
 
 namespace neo {

@@ -3,11 +3,13 @@
 The library is several translation units -- the C ABI in three (neo_abi.hip, neo_abi_fleet.hip, neo_abi_plan.hip, which
 share neo_abi_util.hpp and nobody else sees it) plus one unit per kernel family (neo_disp_*.hip) -- compiled
 in parallel and linked into one shared object.  Objects are cached under csrc/build/ by CONTENT: an object's name carries a
-hash of its command line, its source and every header; the library's stamp file the hash of all of them.  Time stamps
+hash of its command line, its source and the headers it includes -- read off the #include "..." lines themselves, so a
+header recompiles exactly the units that see it; the library's stamp file the hash of all of them.  Time stamps
 play no part (a checkout that restores a file, or a copy of the tree that does not keep them, rebuilds nothing)."""
 import concurrent.futures
 import hashlib
 import os
+import re
 import shutil
 import subprocess
 
@@ -24,11 +26,7 @@ SOURCES = ["neo_abi.hip", "neo_disp_eval.hip", "neo_disp_sample.hip", "neo_disp_
            "neo_disp_adaptive.hip", "neo_disp_backbone.hip",
            # (the kernel-less units of the C ABI last: the units with device code keep their places in the link)
            "neo_abi_fleet.hip", "neo_abi_plan.hip"]
-HEADERS = ["neo_wave.hpp", "neo_device.hpp", "neo_kernels.hpp", "neo_host.hpp", "neo_launch_list.hpp", "neo_launch_opt.hpp", "neo_lbfgs.hpp",
-           "neo_linesearch.hpp", "neo_lbfgs_sm.hpp", "neo_lbfgs_dir.hpp", "neo_group_kernel.hpp",
-           # (the counter-based jitter, included by the plan and the fleet unit; small enough to sit with the shared ones)
-           "neo_counter_rng.hpp"]
-STAMP = LIB + ".stamp"    # hash of command lines + sources + headers the library was built from (travels with the library)
+STAMP = LIB + ".stamp"    # hash of command lines + sources + included headers the library was built from (travels with the library)
 
 
 def _hipcc():
@@ -61,29 +59,28 @@ def _flags():
         os.environ.get("NEO_BUILD_DEFS", "").split()
 
 
-# headers only one unit (or the three of the C ABI) includes: a change there recompiles those alone
-UNIT_HEADERS = {"neo_abi.hip": ["neo_abi_util.hpp"], "neo_abi_fleet.hip": ["neo_abi_util.hpp"], "neo_abi_plan.hip": ["neo_abi_util.hpp"],
-                "neo_disp_audit.hip": ["neo_audit.hpp"], "neo_disp_geo.hip": ["neo_geo.hpp"],
-                "neo_disp_fleet.hip": ["neo_fleet.hpp", "neo_audit.hpp", "neo_track.hpp", "neo_legs.hpp", "neo_flight.hpp"], "neo_disp_batch.hip": ["neo_batch.hpp"],
-                "neo_disp_esdf.hip": ["neo_esdf.hpp"], "neo_disp_plan.hip": ["neo_plan.hpp"],
-                "neo_disp_depth.hip": ["neo_depth.hpp"], "neo_disp_onboard.hip": ["neo_onboard.hpp"],
-                "neo_disp_record.hip": ["neo_record.hpp"], "neo_disp_init.hip": ["neo_init.hpp", "neo_record.hpp"],
-                "neo_disp_adaptive.hip": ["neo_adaptive.hpp"], "neo_disp_backbone.hip": ["neo_backbone.hpp"]}
+_INCLUDE = re.compile(rb'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 
 
-def _headers(src=None):
-    """the headers every unit sees (src None) or the ones only `src` includes.  (The experiment bodies of rounds 3 - 5 are
-    patches under tools/probe/ -- sample_experiment_hooks.patch re-adds their hooks -- and no longer part of any build.)"""
-    if src is not None:
-        return [os.path.join(CSRC, h) for h in UNIT_HEADERS.get(src, [])]
-    return [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(INCLUDE, "neo_planner.h")]
+def _read(path):
+    return open(path, "rb").read()
 
 
-def _headers_hash(src=None):
-    h = hashlib.sha256()
-    for d in _headers(src):
-        h.update(os.path.basename(d).encode() + b"\0" + open(d, "rb").read() + b"\0")
-    return h.hexdigest()
+def _closure(path, seen=None):
+    """{path: contents} of `path` and of every file its #include "..." lines reach, each resolved against the including
+    file's directory.  Whole files are scanned (some headers include from the middle), an include under an #if counts as
+    included, <...> includes are the system's; a quoted include that is not there fails the read"""
+    seen = {} if seen is None else seen
+    if path not in seen:
+        seen[path] = _read(path)
+        for name in _INCLUDE.findall(seen[path]):
+            _closure(os.path.normpath(os.path.join(os.path.dirname(path), name.decode())), seen)
+    return seen
+
+
+def headers_of(src):
+    """base names of the headers unit `src` includes, directly or through another header"""
+    return sorted(os.path.basename(p) for p in _closure(os.path.join(CSRC, src)) if os.path.basename(p) != src)
 
 
 # per-unit compiler options: the all-fp32 optimiser kernels are allocated for three wavefronts per SIMD (168 registers);
@@ -115,17 +112,18 @@ def _compile(src, obj, verbose):
     os.replace(obj + ".tmp", obj)
 
 
-def _key(src=None, headers_hash=None):
-    """hash of everything that decides what the compiler produces: this file (options, per-unit options, source list), the
-    experiment definitions, the headers and the source(s) -- of unit `src`, or of the whole library (src None).  An object
-    or library built from anything else is not reused (options; round 5: contents instead of time stamps)"""
+def _key(src=None):
+    """hash of everything that decides what the compiler produces for unit `src`: this file (options, per-unit options,
+    source list), the experiment definitions, the unit and the headers it includes (_closure); of the whole library (src
+    None): the hash of the units' keys.  An object or library built from anything else is not reused (ADVICE r2: options;
+    round 5: contents instead of time stamps)"""
+    if src is None:
+        return hashlib.sha256("".join(_key(s) for s in SOURCES).encode()).hexdigest()[:12]
     h = hashlib.sha256()
-    h.update(open(os.path.abspath(__file__), "rb").read())
-    h.update(" ".join(_flags() + (_unit_flags(src) if src else [])).encode())
-    h.update((headers_hash or _headers_hash()).encode())
-    for s in ([src] if src else SOURCES):
-        h.update(s.encode() + b"\0" + open(os.path.join(CSRC, s), "rb").read() + b"\0")
-        h.update(_headers_hash(s).encode())
+    h.update(_read(os.path.abspath(__file__)))
+    h.update(" ".join(_flags() + _unit_flags(src)).encode())
+    for path, text in sorted(_closure(os.path.join(CSRC, src)).items()):
+        h.update(os.path.basename(path).encode() + b"\0" + text + b"\0")
     return h.hexdigest()[:12]
 
 
@@ -136,15 +134,14 @@ def build(force=False, verbose=False, jobs=None):
         # an experiment build must never replace the in-tree product library: _lib.load() would silently use it
         raise RuntimeError("NEO_BUILD_DEFS is for experiment builds: set NEO_BUILD_OUT=<path of the experiment library> as well "
                            "(and NEO_PLANNER_LIB=<that path> when running it)")
-    hh = _headers_hash()
-    lib_key = _key(None, hh)
+    lib_key = _key()
     stamp = open(STAMP).read().strip() if os.path.exists(STAMP) else ""
     if not force and os.path.exists(LIB) and stamp == lib_key:
         return LIB          # (the GPU box receives the built library and its stamp without the object cache)
     os.makedirs(OBJDIR, exist_ok=True)
     todo, objs = [], []
     for s in SOURCES:
-        obj = os.path.join(OBJDIR, s.replace(".hip", "." + _key(s, hh) + ".o"))
+        obj = os.path.join(OBJDIR, s.replace(".hip", "." + _key(s) + ".o"))
         objs.append(obj)
         if force or not os.path.exists(obj):
             todo.append((s, obj))

@@ -140,14 +140,14 @@ def test_one_source_for_the_lane_group_kernel():
     assert "struct WaveLanes" in dev and "struct GroupLanes" in dev
 
 
-def test_build_cache_is_keyed_by_content_not_by_time_stamps(tmp_path, monkeypatch):
+def test_build_cache_is_keyed_by_content_not_by_time_stamps(monkeypatch):
     """neo_planner_amd/build.py: the library is up to date when its stamp equals the hash of command lines, sources and
-    headers -- touching a file changes nothing, changing a header or an option changes every key (no hipcc run here)"""
-    import shutil
+    the headers they include -- touching a file changes nothing, changing a header changes the keys of the units that
+    include it and of the library and no other unit's, changing an option changes every key (no hipcc run here)"""
     from neo_planner_amd import build as b
     if os.path.exists(b.STAMP) and os.path.exists(b.LIB):
         assert open(b.STAMP).read().strip() == b._key()        # the in-tree library is the one these sources build
-    k_lib, k_unit = b._key(), b._key("neo_disp_sample.hip")
+    k_lib, k_unit, k_other = b._key(), b._key("neo_disp_sample.hip"), b._key("neo_disp_backbone.hip")
     hdr = os.path.join(b.CSRC, "neo_linesearch.hpp")
     st = os.stat(hdr)
     os.utime(hdr, (st.st_atime, st.st_mtime + 1000))           # a newer time stamp ...
@@ -155,16 +155,25 @@ def test_build_cache_is_keyed_by_content_not_by_time_stamps(tmp_path, monkeypatc
         assert b._key() == k_lib and b._key("neo_disp_sample.hip") == k_unit   # ... is no change
     finally:
         os.utime(hdr, (st.st_atime, st.st_mtime))
-    copy = tmp_path / "neo_linesearch.hpp"
-    shutil.copy(hdr, copy)
-    with open(copy, "a") as f:
-        f.write("// edited\n")
-    real = b._headers
-    monkeypatch.setattr(b, "_headers", lambda src=None: [str(copy) if os.path.basename(d) == "neo_linesearch.hpp" else d for d in real(src)])
-    assert b._key() != k_lib and b._key("neo_disp_sample.hip") != k_unit       # a changed header: every key changes
-    monkeypatch.setattr(b, "_headers", real)
+    real = b._read
+    monkeypatch.setattr(b, "_read", lambda path: real(path) + (b"// edited\n" if path == hdr else b""))
+    assert b._key() != k_lib and b._key("neo_disp_sample.hip") != k_unit       # a changed header: its includers' keys change ...
+    assert b._key("neo_disp_backbone.hip") == k_other                           # ... and nobody else's
+    monkeypatch.setattr(b, "_read", real)
     monkeypatch.setenv("NEO_FP_CONTRACT", "fast")
     assert b._key() != k_lib                                                    # and so does a changed option
+
+
+def test_units_without_minco_do_not_see_its_headers():
+    """the maps, lookups and parameters are neo_map.hpp; the units that launch no MINCO arithmetic include neither
+    neo_device.hpp nor the optimiser's headers, so an edit there does not recompile them"""
+    from neo_planner_amd import build as b
+    for unit in ("neo_disp_esdf", "neo_disp_depth", "neo_disp_onboard", "neo_disp_backbone", "neo_disp_record", "neo_disp_init",
+                 "neo_disp_plan", "neo_disp_batch", "neo_disp_adaptive", "neo_abi_fleet", "neo_abi_plan"):
+        seen = b.headers_of(unit + ".hip")
+        assert "neo_map.hpp" in seen and "neo_wave.hpp" in seen, unit
+        assert not [h for h in seen if h in ("neo_device.hpp", "neo_kernels.hpp", "neo_group_kernel.hpp", "neo_linesearch.hpp")
+                    or h.startswith("neo_lbfgs")], unit
 
 
 def test_trace_parity_cases_reach_the_kernels_they_name():

@@ -136,8 +136,9 @@ def test_pack_head_weights():
 
 def test_init_entry_points_in_the_abi():
     assert "neo_disp_init.hip" in build.SOURCES
-    assert build.UNIT_HEADERS["neo_disp_init.hip"] == ["neo_init.hpp", "neo_record.hpp"]
-    assert build.UNIT_HEADERS["neo_disp_record.hip"] == ["neo_record.hpp"]
+    # the family's header recompiles this unit alone, the recorder's helpers this unit and the recorder
+    assert [s for s in build.SOURCES if "neo_init.hpp" in build.headers_of(s)] == ["neo_disp_init.hip"]
+    assert [s for s in build.SOURCES if "neo_record.hpp" in build.headers_of(s)] == ["neo_disp_record.hip", "neo_disp_init.hip"]
     build.build()
     lib = _lib.load()
     header = open(os.path.join(REPO, "include", "neo_planner.h")).read()

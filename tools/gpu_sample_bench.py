@@ -21,7 +21,7 @@ PROBE_LIB = os.path.join(REPO, "tools", "probe", "_build", "libsample_variants.s
 
 
 def build_probe():
-    deps = [PROBE_SRC, os.path.join(REPO, "neo-planner_amd", "csrc", "neo_device.hpp")]
+    deps = [PROBE_SRC] + [os.path.join(REPO, "neo-planner_amd", "csrc", h) for h in ("neo_device.hpp", "neo_map.hpp")]
     if os.path.exists(PROBE_LIB) and all(os.path.getmtime(PROBE_LIB) > os.path.getmtime(d) for d in deps):
         return
     os.makedirs(os.path.dirname(PROBE_LIB), exist_ok=True)

@@ -23,7 +23,7 @@
 // bound by instruction issue, not by the latency of its gathers; the product's answer is fewer idle lane-rounds
 // (csrc/neo_sample_chunk.hpp).  Kept here, outside the library, as the experiment it was: a library built with
 // -DNEO_SAMPLE_EXPERIMENTS dispatches to it when NEO_SAMPLE_VARIANT is set.  Lookup3D::load_async / read_staged are no
-// longer in csrc/neo_device.hpp: `git apply tools/probe/lds_dma_gather.patch` first.
+// longer in csrc/neo_map.hpp: `git apply tools/probe/lds_dma_gather.patch` first.
 #pragma once
 #include "../../neo-planner_amd/csrc/neo_kernels.hpp"
 
