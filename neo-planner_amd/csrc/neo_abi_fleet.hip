@@ -768,4 +768,31 @@ int neo_backbone_launch_times(neo_ctx *c, const float *weights, size_t n_weights
   return rc;
 }
 
+int neo_backbone_activation_shape(int launch, int H, int W, int *h, int *w, int *c) {
+  if (launch < 0 || launch >= NEO_BACKBONE_LAUNCHES || H < 1 || W < 1 || !h || !w || !c) return NEO_ERR_INVALID;
+  backbone_activation_shape(launch, H, W, h, w, c);
+  return NEO_OK;
+}
+
+int neo_backbone_activation_dev(neo_ctx *c, const float *weights, size_t n_weights, const uint8_t *images_u8, int n, int H, int W,
+                                void *workspace, size_t workspace_bytes, int launch, float *act_out, size_t act_floats) {
+  int rc = backbone_check(c, weights, n_weights, images_u8, n, H, W, workspace, workspace_bytes, act_out);
+  if (rc) return rc;
+  if (launch < 0 || launch >= NEO_BACKBONE_LAUNCHES)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone: launch must be 0 .. NEO_BACKBONE_LAUNCHES - 1");
+  int h, w, ch;
+  backbone_activation_shape(launch, H, W, &h, &w, &ch);
+  if (act_floats != (size_t)n * h * w * ch)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone: act_floats must be n * h * w * c of neo_backbone_activation_shape");
+  if (n == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  // the pool + fc writes act_out itself; a stem's or a convolution's buffer of the workspace is copied behind the launch
+  const float *written = nullptr;
+  rc = launched(c, backbone_features(c, weights, images_u8, n, H, W, workspace, act_out, nullptr, launch, &written));
+  if (rc || written == act_out) return rc;
+  HIPCHK(c, hipMemcpyAsync(act_out, written, act_floats * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  return NEO_OK;
+}
+
 }  // extern "C"

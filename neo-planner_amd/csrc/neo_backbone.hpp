@@ -20,7 +20,13 @@
 // input channels in groups of 32, a group in the order 0, 16, 1, 17, ..., 15, 31 (the two k of an MFMA step are the lane
 // halves, each holding 16 consecutive channels).  K is never split across waves or blocks, padding taps contribute
 // +0 * w products, and no value depends on which other columns share a tile: an image's features depend on neither the
-// batch nor the image's position in it.  No global atomics, no scratch.
+// batch nor the image's position in it.  No global atomics, no scratch.  The stem is one fmaf chain from its bias over
+// its 49 taps row-major; the pool + fc adds a channel's pixels in ascending order, divides once, and runs an fc row as
+// one chain from its bias over k ascending.
+// The rule is ASSERTED, launch by launch: tests/host_harness/backbone_host.cpp restates it as plain host loops of
+// std::fmaf (from this text, not from the kernels), and tests/test_gpu_backbone_launches.py requires every launch's output
+// on the MI355X to equal that program's values from the same inputs (neo_backbone_activation_dev) -- which the f32 MFMA of
+// gfx950 does, to the last bit, in all 171 convolution launches tested.  A change that keeps "the same bits" keeps that test.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -369,9 +369,14 @@ int init_guess(neo_ctx *c, const LaunchList &l, const float *out, const double *
 // neo_backbone_*: the image backbone in front of them (neo_disp_backbone.hip, kernels in neo_backbone.hpp): n uint8
 // images of H x W -> feature_out [n][24], 21 launches; `workspace` holds backbone_workspace_bytes(n, H, W) bytes.
 // events: NULL, or NEO_BACKBONE_LAUNCHES + 1 events recorded in front of the chain and behind every launch
+// last: the chain ends behind launch `last` (neo_backbone_activation_dev; 0 .. NEO_BACKBONE_LAUNCHES - 1, the default is the
+// whole chain); written: NULL, or where the buffer that launch wrote is returned (feature_out for the pool + fc)
 size_t backbone_workspace_bytes(int n, int H, int W);
 int backbone_features(neo_ctx *c, const float *weights, const unsigned char *images, int n, int H, int W, void *workspace,
-                      float *feature_out, hipEvent_t *events = nullptr);
+                      float *feature_out, hipEvent_t *events = nullptr, int last = NEO_BACKBONE_LAUNCHES - 1,
+                      const float **written = nullptr);
+// h, w, c of what launch `launch` writes an image of H x W ([h][w][c] channels-last; 1, 1, 24 for the pool + fc)
+void backbone_activation_shape(int launch, int H, int W, int *h, int *w, int *c);
 
 // neo_batch_*_dev: the `batch` planner mode on resident arrays (neo_disp_batch.hip, kernels in neo_batch.hpp).  P =
 // the list's n requests; tau, off and w are HOST arrays (M, K and 4 values), handed to the kernels by value.

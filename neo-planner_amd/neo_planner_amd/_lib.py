@@ -85,6 +85,7 @@ EXPORTS = [
     "neo_fleet_fly_dev", "neo_fleet_fly_error_dev",
     "neo_geo_guess_dev", "neo_geo_mask_builds",
     "neo_backbone_workspace_bytes", "neo_backbone_features_dev", "neo_backbone_launch_times",
+    "neo_backbone_activation_dev", "neo_backbone_activation_shape",
 ]
 
 
@@ -222,6 +223,8 @@ def load():
     L.neo_backbone_workspace_bytes.restype = ctypes.c_size_t
     L.neo_backbone_features_dev.argtypes = [c_p, c_p, ctypes.c_size_t, c_p, c_i, c_i, c_i, c_p, ctypes.c_size_t, c_p]
     L.neo_backbone_launch_times.argtypes = L.neo_backbone_features_dev.argtypes + [c_p]
+    L.neo_backbone_activation_dev.argtypes = L.neo_backbone_features_dev.argtypes[:-1] + [c_i, c_p, ctypes.c_size_t]
+    L.neo_backbone_activation_shape.argtypes = [c_i, c_i, c_i] + [ctypes.POINTER(ctypes.c_int)] * 3
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]

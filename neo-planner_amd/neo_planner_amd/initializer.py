@@ -21,6 +21,8 @@ unpinned, parity of the *architecture and data flow* is tested against an fp64 N
 same weights (tests/test_initializer.py).  torchvision is not available in this image: the ResNet-18
 below is written out with torchvision's parameter names.
 """
+import collections
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -319,33 +321,105 @@ def pack_backbone_weights(net, dtype=torch.float32):
 def backbone_model(blob, images):
     """What the blob of pack_backbone_weights MEANS: the features (n, 24) float64 of images (n, H, W) (uint8 values), from
     the blob alone, in fp64 on the CPU -- convolutions with a bias, ReLU, the 3 x 3 stride-2 max pool, the residual sums,
-    the mean over the pixels and the fc.  The yardstick of the kernels (tests/test_gpu_backbone.py)."""
-    F = torch.nn.functional
+    the mean over the pixels and the fc: the launches of backbone_launches, one after the other.  The yardstick of the
+    kernels (tests/test_gpu_backbone.py)."""
     blob = torch.as_tensor(blob).detach().cpu().double().reshape(-1)
     if blob.numel() != BACKBONE_FLOATS:
         raise ValueError("backbone_model: the blob has NEO_BACKBONE_FLOATS = %d values" % BACKBONE_FLOATS)
     x = torch.as_tensor(np.asarray(images.detach().cpu() if torch.is_tensor(images) else images)).double()
     x = x.reshape(-1, 1, *x.shape[-2:])
+    table = backbone_launches(*x.shape[-2:])
+    # a launch's output is kept until the last launch that reads it
+    last_use = {}
+    for k, rec in enumerate(table):
+        last_use[rec.src] = last_use[rec.resid] = k
+    outs = {-1: x}
+    for k, rec in enumerate(table):
+        outs[k] = _launch64(blob, rec, outs[rec.src], None if rec.resid is None else outs[rec.resid])
+        for j in [j for j in outs if last_use.get(j, len(table)) <= k]:
+            del outs[j]
+    return outs[len(table) - 1].numpy()
+
+
+BackboneLaunch = collections.namedtuple(
+    "BackboneLaunch", "kind ks cin cout stride relu hin win hout wout w_off b_off src resid")
+
+
+def backbone_launches(H, W):
+    """The NEO_BACKBONE_LAUNCHES = 21 launches of neo_backbone_features_dev for images of H x W, in launch order (the
+    order of neo_backbone_launch_times and neo_backbone_activation_dev), as BackboneLaunch records:
+      kind            "stem" (7 x 7 stride-2 convolution, ReLU, 3 x 3 stride-2 max pool), "conv", or "poolfc" (the mean over
+                      the pixels, then the fc)
+      ks cin cout stride relu    the convolution (the fc: ks 1, cin 512, cout 24)
+      hin win hout wout          the input's and the output's size (stem: the image's and the pooled one's; poolfc: 1 x 1 out)
+      w_off b_off     where W [ks][ks][cin][cout] (the fc: [24][512]) and b [cout] start in the blob
+      src             the launch whose output is the input (-1: the images)
+      resid           the launch whose output is added before the ReLU, or None
+    The blob holds a block as conv1, conv2, downsample; the launches run conv1, downsample, conv2."""
+    size = lambda s, stride: (s - 1) // stride + 1
     at = [0]
 
-    def conv(x, ks, cin, cout, stride):
-        w = blob[at[0]:at[0] + ks * ks * cin * cout].reshape(ks, ks, cin, cout).permute(3, 2, 0, 1)
-        at[0] += ks * ks * cin * cout
-        b = blob[at[0]:at[0] + cout]
-        at[0] += cout
-        return F.conv2d(x, w, b, stride=stride, padding=ks // 2)
+    def take(ks, cin, cout):
+        w_off = at[0]
+        at[0] += ks * ks * cin * cout + cout
+        return w_off, at[0] - cout
 
-    x = F.max_pool2d(F.relu(conv(x, 7, 1, 64, 2)), 3, 2, 1)
-    cin = 64
+    h, w = size(size(H, 2), 2), size(size(W, 2), 2)
+    recs = [BackboneLaunch("stem", 7, 1, 64, 2, 1, H, W, h, w, *take(7, 1, 64), -1, None)]
+    cin, x = 64, 0                                  # x: the launch that wrote the block's input
     for li, cout in enumerate(_BACKBONE_CHANNELS):
         for blk in range(2):
             stride = 2 if (li > 0 and blk == 0) else 1
-            y = conv(F.relu(conv(x, 3, cin, cout, stride)), 3, cout, cout, 1)
-            idt = conv(x, 1, cin, cout, stride) if (stride != 1 or cin != cout) else x
-            x, cin = F.relu(y + idt), cout
-    w = blob[at[0]:at[0] + 24 * 512].reshape(24, 512)
-    b = blob[at[0] + 24 * 512:]
-    return (x.mean(dim=(2, 3)) @ w.T + b).numpy()
+            ho, wo = size(h, stride), size(w, stride)
+            o1, o2 = take(3, cin, cout), take(3, cout, cout)
+            recs.append(BackboneLaunch("conv", 3, cin, cout, stride, 1, h, w, ho, wo, *o1, x, None))
+            c1, idt = len(recs) - 1, x
+            if stride != 1 or cin != cout:
+                recs.append(BackboneLaunch("conv", 1, cin, cout, stride, 0, h, w, ho, wo, *take(1, cin, cout), x, None))
+                idt = len(recs) - 1
+            recs.append(BackboneLaunch("conv", 3, cout, cout, 1, 1, ho, wo, ho, wo, *o2, c1, idt))
+            x, h, w, cin = len(recs) - 1, ho, wo, cout
+    recs.append(BackboneLaunch("poolfc", 1, 512, IMG_FEATURE_SIZE, 1, 0, h, w, 1, 1, *take(1, 512, IMG_FEATURE_SIZE), x, None))
+    return recs
+
+
+def _launch64(blob, rec, x, resid, absolute=False):
+    """one launch in fp64 on torch's layout: blob a float64 tensor, x (n, cin, hin, win) (the stem: (n, 1, H, W)), resid
+    None or (n, cout, hout, wout); returns (n, cout, hout, wout), the poolfc (n, 24).  absolute: on |W| and |b|"""
+    F = torch.nn.functional
+    w, b = blob[rec.w_off:rec.b_off], blob[rec.b_off:rec.b_off + rec.cout]
+    if absolute:
+        w, b = w.abs(), b.abs()
+    if rec.kind == "poolfc":
+        return x.mean(dim=(2, 3)) @ w.reshape(rec.cout, rec.cin).T + b
+    w = w.reshape(rec.ks, rec.ks, rec.cin, rec.cout).permute(3, 2, 0, 1)
+    y = F.conv2d(x, w, b, stride=rec.stride, padding=rec.ks // 2)
+    if rec.kind == "stem":
+        return F.max_pool2d(F.relu(y), 3, 2, 1)
+    if resid is not None:
+        y = y + resid
+    return F.relu(y) if rec.relu else y
+
+
+def backbone_launch_model(blob, rec, act_in, resid=None, absolute=False):
+    """ONE launch of the chain in fp64 from given inputs, in the device's layout: rec a record of backbone_launches,
+    act_in the output of launch rec.src, [n][hin][win][cin] channels-last (the stem: the images, [n][H][W]), resid the
+    output of launch rec.resid or None.  Returns float64 [n][hout][wout][cout], the poolfc [n][24].  absolute=True runs
+    the same launch on the absolute values of the weights, the bias and the inputs: |b| + sum |w| |x| + |resid|, the
+    scale of an fp32 summation's rounding error.  (A float64 CPU tensor as the blob is used as it is: callers of many
+    launches convert once.)"""
+    blob = torch.as_tensor(blob).detach().cpu().double().reshape(-1)
+    if blob.numel() != BACKBONE_FLOATS:
+        raise ValueError("backbone_launch_model: the blob has NEO_BACKBONE_FLOATS = %d values" % BACKBONE_FLOATS)
+    if (rec.resid is None) != (resid is None):
+        raise ValueError("backbone_launch_model: launches with rec.resid take a residual, the others none")
+    x = torch.as_tensor(np.asarray(act_in)).double()
+    x = x.reshape(-1, 1, rec.hin, rec.win) if rec.kind == "stem" else x.reshape(-1, rec.hin, rec.win, rec.cin).permute(0, 3, 1, 2)
+    r = None if resid is None else torch.as_tensor(np.asarray(resid)).double().reshape(-1, rec.hout, rec.wout, rec.cout).permute(0, 3, 1, 2)
+    if absolute:
+        x, r = x.abs(), None if r is None else r.abs()
+    y = _launch64(blob, rec, x.contiguous(), None if r is None else r.contiguous(), absolute)
+    return (y if rec.kind == "poolfc" else y.permute(0, 2, 3, 1)).contiguous().numpy()
 
 
 def backbone_features_kernel(ctx, blob, images, out=None, chunk=512, workspace=None):

@@ -1,5 +1,6 @@
 """The image backbone of the learned warm start, off the GPU: the folded weight blob (pack_backbone_weights), its fp64
-restatement (backbone_model) against the torch module in fp64, and the two entry points in the C ABI."""
+restatement (backbone_model) against the torch module in fp64, the launch table behind it (backbone_launches) against the
+blob's size and the C shape query, and the entry points in the C ABI."""
 import os
 import re
 
@@ -131,7 +132,8 @@ def test_backbone_entry_points_in_the_abi():
     lib = _lib.load()
     header = open(os.path.join(REPO, "include", "neo_planner.h")).read()
     for kind, name, count in (("size_t", "neo_backbone_workspace_bytes", 3), ("int", "neo_backbone_features_dev", 10),
-                              ("int", "neo_backbone_launch_times", 11)):
+                              ("int", "neo_backbone_launch_times", 11), ("int", "neo_backbone_activation_dev", 12),
+                              ("int", "neo_backbone_activation_shape", 6)):
         assert name in _lib.EXPORTS
         decl = re.search(r"\b" + kind + r"\s+" + name + r"\s*\(([^)]*)\)", header)
         assert decl, name
@@ -144,3 +146,43 @@ def test_backbone_entry_points_in_the_abi():
     assert lib.neo_backbone_workspace_bytes(0, 120, 160) == 0 and lib.neo_backbone_workspace_bytes(4, 0, 160) == 0
     tool = open(os.path.join(REPO, "tools", "kernel_resource_usage.py")).read()
     assert "neo_disp_backbone.hip" in tool
+
+
+# the sizes the launches are tested at on the GPU (tests/test_gpu_backbone_launches.py), and the sizes above
+LAUNCH_SIZES = [(1, 1), (1, 13), (9, 1), (2, 2), (16, 32), (17, 33), (33, 47)]
+
+
+def test_launch_table_ends_at_the_blob_size_and_has_the_c_shapes():
+    """initializer.backbone_launches: 21 launches, whose weights tile the blob without a gap (in the blob's order: a
+    block's conv2 before its downsample branch, which is launched first), whose inputs are their sources' outputs, and
+    whose output shapes are neo_backbone_activation_shape's at every size"""
+    import ctypes
+    build.build()
+    lib = _lib.load()
+    for H, W in LAUNCH_SIZES + SIZES + [(32, 40), (480, 640)]:
+        table = ini.backbone_launches(H, W)
+        assert len(table) == _lib.NEO_BACKBONE_LAUNCHES == 21
+        assert [r.kind for r in table] == ["stem"] + ["conv"] * 19 + ["poolfc"]
+        at = 0
+        for r in sorted(table, key=lambda r: r.w_off):
+            assert r.w_off == at and r.b_off == at + r.ks * r.ks * r.cin * r.cout, r
+            at = r.b_off + r.cout
+        assert at == ini.BACKBONE_FLOATS
+        assert [k for k, r in enumerate(table) if r.ks == 1 and r.kind == "conv"] == [6, 11, 16]
+        for k, r in enumerate(table):
+            h, w, c = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+            assert lib.neo_backbone_activation_shape(k, H, W, ctypes.byref(h), ctypes.byref(w), ctypes.byref(c)) == _lib.NEO_OK
+            assert (h.value, w.value, c.value) == (r.hout, r.wout, r.cout), (H, W, k)
+            assert -1 <= r.src < k and (r.resid is None or 0 <= r.resid < k)
+            if r.src >= 0:
+                s = table[r.src]
+                assert (s.hout, s.wout, s.cout) == (r.hin, r.win, r.cin), (H, W, k)
+            if r.resid is not None:
+                s = table[r.resid]
+                assert (s.hout, s.wout, s.cout) == (r.hout, r.wout, r.cout), (H, W, k)
+        assert (table[0].hin, table[0].win, table[0].src) == (H, W, -1) and table[-1].src == 19
+    h = ctypes.c_int(-1)
+    p = ctypes.byref(h)
+    for bad in ((-1, 9, 13), (21, 9, 13), (0, 0, 13), (0, 9, 0)):
+        assert lib.neo_backbone_activation_shape(*bad, p, p, p) == 1, bad          # NEO_ERR_INVALID
+    assert lib.neo_backbone_activation_shape(0, 9, 13, None, p, p) == 1 and h.value == -1

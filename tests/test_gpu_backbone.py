@@ -13,7 +13,9 @@ from test_gpu_record import _fleet_setup
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [(9, 13), (33, 47), (120, 160)]
+# (the last four: one-pixel and even images, the pooled image that exactly fills the stem's 8 x 4 tile and the one that passes it
+# by a pixel; tests/test_gpu_backbone_launches.py takes them launch by launch)
+SIZES = [(9, 13), (33, 47), (120, 160), (1, 1), (2, 2), (16, 32), (17, 33)]
 N_MOST = 70
 GUARD = 64
 
@@ -112,6 +114,25 @@ def test_an_images_features_do_not_depend_on_the_batch(H, W):
             moved[pos] = img[i]
             assert np.array_equal(bits(run_kernel(blob, torch.from_numpy(moved).to(dev))[pos]), bits(whole[i])), (i, pos)
     assert len({row.tobytes() for row in whole}) == N_MOST      # (the features do tell the images apart)
+
+
+def test_a_one_pixel_images_features_do_not_depend_on_the_batch():
+    """1 x 1 images, 129 of them: every convolution has one column an image, so a column tile spans 128 images and the
+    129th is the one live column of a second tile.  Image i alone and at positions 0, 127 and 128: the same bits"""
+    torch, dev = _torch()
+    n = 129
+    r = reference(1, 1)
+    blob = r["blob"].to(dev)
+    img = batch_images(1, 1, n=n, seed=1)
+    whole = run_kernel(blob, torch.from_numpy(img).to(dev))
+    for i in (0, 5, 127, 128):
+        alone = run_kernel(blob, torch.from_numpy(img[i:i + 1]).to(dev))
+        assert np.array_equal(bits(alone[0]), bits(whole[i])), i
+        for pos in (0, 127, 128):
+            moved = img[::-1].copy()
+            moved[pos] = img[i]
+            assert np.array_equal(bits(run_kernel(blob, torch.from_numpy(moved).to(dev))[pos]), bits(whole[i])), (i, pos)
+    assert len({row.tobytes() for row in whole}) == len(np.unique(img)) > 90      # (the features tell the pixel values apart)
 
 
 @pytest.mark.parametrize("H,W,n", [(33, 47, 3), (9, 13, 70)])
