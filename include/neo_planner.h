@@ -307,8 +307,8 @@ int neo_eval_traj_batch(neo_ctx *ctx, int B, int M, int D, const double *x, cons
  * The reference's flight metric of every planned trajectory under perfect tracking, one record per trajectory:
  *   1. the coefficients are solved from x, head, tail as neo_eval_traj_batch solves them (fp64);
  *   2. samples at t_k = k * (1 / hz), k < count[b] = len(np.arange(0, sum(T), 1/hz)) -- any number of them;
- *   3. the sample states are those of neo_eval_traj_batch's rows at the same hz, bit for bit (same piece search,
- *      same expressions);
+ *   3. the sample states are those of neo_eval_traj_batch's rows at the same hz, bit for bit (one piece table for
+ *      both, csrc/neo_pieces.hpp: the same solve, piece search and expressions);
  *   4. d_k = the map's point lookup of the sample position in neo_esdf_query's arithmetic: the nearest cell on the
  *      2-D reference map (the first two axes, as the sampled cost projects them; 10000 outside), trilinear on 3-D
  *      fields (fp32 / fp16, every layout);

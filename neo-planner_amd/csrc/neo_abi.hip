@@ -3,100 +3,15 @@
 // and the trace / counter / order / profile calls.  neo_abi_fleet.hip has the depth camera, onboard maps, the fleet,
 // record and init entry points, neo_abi_plan.hip the batch, plan and adaptive ones.  Argument checks, locking, scratch
 // layout and host copies and the map bookkeeping are shared (neo_abi_util.hpp); every entry point makes one call into
-// the kernel family's unit (neo_disp_*.hip).  The kernels this unit still holds are the small ones around the
-// optimiser's results:
+// the kernel family's unit (neo_disp_*.hip).  No device header is included here: the kernels this unit still holds are
+// rocPRIM's sort of the dispatch order with pack_results_kernel and effort_keys_kernel around it.
 //
-//   traj_state_kernel   get_full_state_cmd                      (traj_utils.py:85-195)
-//   pack_results_kernel, effort_keys_kernel and the rocPRIM sort of the dispatch order
-//
-// The map kernels are in neo_esdf.hpp (launched from neo_disp_esdf.hip); the fused kernels (eval / optimize / sample)
-// are templates in neo_kernels.hpp, instantiated per family in the neo_disp_*.hip translation units.
+// The map kernels are in neo_esdf.hpp (launched from neo_disp_esdf.hip); traj_state_kernel (neo_pieces.hpp) and
+// audit_kernel (neo_audit.hpp) are launched from neo_disp_audit.hip; the fused kernels (eval / optimize / sample) are
+// templates in neo_kernels.hpp, instantiated per family in the neo_disp_*.hip translation units.
 #include <cstring>
 #include "neo_abi_util.hpp"
 #include <rocprim/device/device_radix_sort.hpp>
-#include "neo_kernels.hpp"
-
-namespace neo {
-
-// get_full_state_cmd (traj_utils.py:85-195): one wavefront per trajectory solves the
-// coefficients, then its lanes walk the sample times.
-template <int D>
-__global__ __launch_bounds__(kWave) void traj_state_kernel(int B, int M, DevParams prm,
-                                                            const double *__restrict__ x,
-                                                            const double *__restrict__ head,
-                                                            const double *__restrict__ tail, double hz, int K,
-                                                            double *__restrict__ state, int *__restrict__ count) {
-  __shared__ double xs[kSlots * kWave];
-  __shared__ double cs[kWave * 6 * D];
-  __shared__ double tcum[kWave + 1];
-  const int b = blockIdx.x;
-  if (b >= B) return;
-  struct NoMap {};
-  struct NoLookup {
-    __device__ explicit NoLookup(const NoMap &) {}
-  };
-  DevParams p = prm;
-  NoMap nm;
-  DevBackend<D, kSlots, double, NoMap, NoLookup> be(p, nm);
-  be.xs = xs;
-  be.hist = nullptr;
-  be.m = NEO_LBFGS_M;
-  be.coeff_out = nullptr;
-  load_boundary(be.t, head + (size_t)b * 3 * D, tail + (size_t)b * 3 * D, M);
-  const int n = be.t.n;
-  const int lane = lane_id();
-  typename DevBackend<D, kSlots, double, NoMap, NoLookup>::Vec xv;
-#pragma unroll
-  for (int k = 0; k < kSlots; ++k) xv.v[k] = (k * kWave + lane < n) ? x[(size_t)b * n + k * kWave + lane] : 0.0;
-  be.scatter_x(xv);
-  double e, ts;
-  const int st = minco_forward<D>(be.t, p, e, ts);
-  if (st != 0) {
-    if (lane == 0) count[b] = -1;
-    return;
-  }
-  if (lane < M) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-#pragma unroll
-      for (int d = 0; d < D; ++d) cs[(lane * 6 + k) * D + d] = be.t.c[k][d];
-  }
-  // sequential prefix sums like Python's sum(ts[:k]) (traj_utils.py:98-101)
-  if (lane == 0) tcum[0] = 0.0;
-  for (int pce = 0; pce < M; ++pce) {
-    const double Tp = rdlane(be.t.T, pce);
-    if (lane == 0) tcum[pce + 1] = tcum[pce] + Tp;
-  }
-  __syncthreads();
-  const double total = tcum[M];
-  const double step = 1.0 / hz;
-  const int cnt = (int)ceil(total / step);  // len(np.arange(0, total, 1/hz))
-  if (lane == 0) count[b] = cnt;
-  for (int k = lane; k < K; k += kWave) {
-    double *out = state + ((size_t)b * K + k) * 3 * D;
-    if (k >= cnt) {
-#pragma unroll
-      for (int q = 0; q < 3 * D; ++q) out[q] = 0.0;
-      continue;
-    }
-    double tt = (double)k * step;
-    if (tt > total) tt = total;
-    int pc = 0;
-    while (pc < M - 1 && tcum[pc + 1] < tt) ++pc;
-    const double T = tt - tcum[pc];
-    const double T2 = T * T, T3 = T2 * T, T4 = T2 * T2, T5 = T4 * T;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      const double c0 = cs[(pc * 6 + 0) * D + d], c1 = cs[(pc * 6 + 1) * D + d], c2 = cs[(pc * 6 + 2) * D + d];
-      const double c3 = cs[(pc * 6 + 3) * D + d], c4 = cs[(pc * 6 + 4) * D + d], c5 = cs[(pc * 6 + 5) * D + d];
-      out[0 * D + d] = c0 + c1 * T + c2 * T2 + c3 * T3 + c4 * T4 + c5 * T5;
-      out[1 * D + d] = c1 + 2.0 * c2 * T + 3.0 * c3 * T2 + 4.0 * c4 * T3 + 5.0 * c5 * T4;
-      out[2 * D + d] = 2.0 * c2 + 6.0 * c3 * T + 12.0 * c4 * T2 + 20.0 * c5 * T3;
-    }
-  }
-}
-
-}  // namespace neo
 
 // =================================================================== host side
 using namespace neo;
@@ -861,16 +776,7 @@ int neo_eval_traj_batch(neo_ctx *c, int B, int M, int D, const double *x, const 
   const auto fs = st.out(state, bs * K * 3 * D);
   const auto fcnt = st.out(count, bs);
   return st.run([&]() -> int {
-    double *dx = st.dev(fx), *dh = st.dev(fh), *dt = st.dev(ft), *ds = st.dev(fs);
-    int *dcnt = st.dev(fcnt);
-    if (D == 2)
-      hipLaunchKernelGGL((traj_state_kernel<2>), dim3(B), dim3(kWave), 0, c->stream, B, M, c->dev, dx, dh, dt, hz, K, ds,
-                         dcnt);
-    else
-      hipLaunchKernelGGL((traj_state_kernel<3>), dim3(B), dim3(kWave), 0, c->stream, B, M, c->dev, dx, dh, dt, hz, K, ds,
-                         dcnt);
-    HIPCHK(c, hipGetLastError());
-    return NEO_OK;
+    return launched(c, dispatch_traj_state(c, D, {B, M, st.dev(fx), st.dev(fh), st.dev(ft), hz, K, st.dev(fs), st.dev(fcnt)}));
   });
 }
 

@@ -243,6 +243,19 @@ __device__ __forceinline__ void stage_boundary(Traj<D, DL, Num> &t, Num *lds) {
   }
 }
 
+// bnd_lds: 6 * D elements of LDS for the layouts with one dimension per lane (stage_boundary), unused otherwise
+template <class LG = WaveLanes, int D, int DL, typename Num>
+__device__ __forceinline__ void load_boundary(Traj<D, DL, Num> &t, const double *head, const double *tail, int M,
+                                              Num *bnd_lds = nullptr) {
+  t.M = M;
+  t.nq = D * (M - 1);
+  t.n = t.nq + M;
+  t.L = sample_lanes_per_piece_fwd(M);
+  t.head = head;
+  t.tail = tail;
+  stage_boundary<D, LG>(t, bnd_lds);
+}
+
 // Block-tridiagonal systems with 2x2 blocks on the interior joints p = 1..M-1 (blocks on lane p):
 //     Lo_p y_{p-1} + Di_p y_p + Up_p y_{p+1} = R_p,      y_0 and y_M given.
 // Block Thomas, no pivoting across blocks.  thomas_factor runs the right-hand-side independent part

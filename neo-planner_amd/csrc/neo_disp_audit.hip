@@ -1,9 +1,21 @@
-// neo_disp_audit.hip -- audit_kernel family: the reference's flight metric (ros_node/traj_planner_node.py:333-363) for a
-// batch of trajectories (neo_audit.hpp), one instantiation per map kind, D, element type and layout
+// neo_disp_audit.hip -- the kernels over a planned trajectory's piece table: traj_state_kernel, its sample rows
+// (neo_pieces.hpp), and the audit_kernel family, the reference's flight metric (ros_node/traj_planner_node.py:333-363) for
+// a batch of trajectories (neo_audit.hpp), one instantiation per map kind, D, element type and layout
 #include "neo_host.hpp"
 #include "neo_audit.hpp"
 
 namespace neo {
+
+template <int D>
+static int launch_traj_state(neo_ctx *c, const TrajStateArgs &a) {
+  hipLaunchKernelGGL((traj_state_kernel<D>), dim3(a.B), dim3(kWave), 0, c->stream, a.B, a.M, c->dev, a.x, a.head, a.tail,
+                     a.hz, a.K, a.state, a.count);
+  return NEO_OK;
+}
+
+int dispatch_traj_state(neo_ctx *c, int D, const TrajStateArgs &a) {
+  return D == 2 ? launch_traj_state<2>(c, a) : launch_traj_state<3>(c, a);
+}
 
 template <int D, class MapT, class LookupT>
 static int launch_audit(neo_ctx *c, const AuditArgs &a) {

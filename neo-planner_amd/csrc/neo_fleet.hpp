@@ -13,7 +13,8 @@
 //   fleet_fly_kernel       the advance with a flight model: lag, saturation, drag, gusts   one lane per mission
 //   fleet_fly_error_kernel save_tracking_err (:310-331) reduced per mission             one wavefront per mission
 //
-// Included by neo_disp_fleet.hip only.  2-D reference map, D = 2, fp64.  No floating-point atomics, fixed summation
+// Included by neo_disp_fleet.hip only; the solve of the splice is the piece table's (neo_pieces.hpp, through neo_audit.hpp):
+// nothing of the optimiser is included.  2-D reference map, D = 2, fp64.  No floating-point atomics, fixed summation
 // order: a mission's results depend on neither the batch, the subset nor the launch.  All arrays are indexed by mission;
 // workgroup / lane i works on the mission at position i of the launch list (neo_launch_list.hpp).  A mission is owned
 // by one lane (target, advance) or one wavefront (splice, audit) of a launch, so its flags word is updated with a plain
@@ -266,73 +267,37 @@ __global__ __launch_bounds__(kFleetThreads) void fleet_warm_carry_kernel(
   }
 }
 
-// The solve and the rows are traj_state_kernel's (neo_abi.hip) through audit_sample_state, its expressions written out
-// again in neo_audit.hpp: compiled with the units' -ffp-contract=on and no pragma here, they round as its rows do.
+// The solve and the rows are the piece table's (neo_pieces.hpp), as traj_state_kernel's: the same bits as its rows.
 __global__ __launch_bounds__(kWave) void fleet_splice_kernel(
     LaunchList list, int M, DevParams prm, const double *__restrict__ x,
     const double *__restrict__ head, const double *__restrict__ tail, const int *__restrict__ solved, double hz, int first,
     double *__restrict__ cmd, int cap, int *__restrict__ cmd_len, int *__restrict__ cmd_index,
     int *__restrict__ future_index, int *__restrict__ flags) {
   constexpr int D = kFleetD;
-  __shared__ double xs[kSlots * kWave];
-  __shared__ double cs[kWave * 6 * D];
-  __shared__ double tcum[kWave + 1];
+  NEO_PIECE_LDS(D, lds);
   const int b = list.request(blockIdx.x);  // wave-uniform
   if (b < 0) return;
   if (solved && !solved[b]) return;
   const int lane = lane_id();
-  struct NoMap {};
-  struct NoLookup {
-    __device__ explicit NoLookup(const NoMap &) {}
-  };
-  DevParams p = prm;
-  NoMap nm;
-  DevBackend<D, kSlots, double, NoMap, NoLookup> be(p, nm);
-  be.xs = xs;
-  be.hist = nullptr;
-  be.m = NEO_LBFGS_M;
-  be.coeff_out = nullptr;
-  load_boundary(be.t, head + (size_t)b * 3 * D, tail + (size_t)b * 3 * D, M);
-  const int n = be.t.n;
-  typename DevBackend<D, kSlots, double, NoMap, NoLookup>::Vec xv;
-#pragma unroll
-  for (int k = 0; k < kSlots; ++k) xv.v[k] = (k * kWave + lane < n) ? x[(size_t)b * n + k * kWave + lane] : 0.0;
-  be.scatter_x(xv);
-  double e, ts;
   // no trajectory to splice (exp(-tau) overflow, or below a duration that is not finite): the array stays as it is
   auto refuse = [&]() {
     if (lane == 0) flags[b] |= NEO_FLEET_FLAG_SPLICE_FAILED;
   };
-  if (minco_forward<D>(be.t, p, e, ts) != 0) return refuse();
-  if (lane < M) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-#pragma unroll
-      for (int d = 0; d < D; ++d) cs[(lane * 6 + k) * D + d] = be.t.c[k][d];
-  }
-  if (lane == 0) tcum[0] = 0.0;
-  for (int pce = 0; pce < M; ++pce) {
-    const double Tp = rdlane(be.t.T, pce);
-    if (lane == 0) tcum[pce + 1] = tcum[pce] + Tp;
-  }
-  __syncthreads();
-  const double total = tcum[M];
+  PieceTable<D> pt(lds, M);
+  if (pt.solve(b, prm, x, head, tail) != 0) return refuse();
   const double step = 1.0 / hz;
-  const double cnt_d = ceil(total / step);  // len(np.arange(0, total, 1/hz))
-  if (!(cnt_d >= 0.0 && cnt_d <= (double)(1 << 30))) return refuse();
-  const int cnt = (int)cnt_d;
+  int cnt;
+  if (!pt.sample_count(step, cnt)) return refuse();
   int at = first ? 0 : future_index[b];
   at = at < 0 ? 0 : (at > cap ? cap : at);
   const int room = cap - at;
   const int wr = cnt < room ? cnt : room;  // rows beyond the buffer are dropped
   double *out0 = cmd + ((size_t)b * cap + at) * kFleetRow;
   for (int k = lane; k < wr; k += kWave) {
-    double tt = (double)k * step;
-    if (tt > total) tt = total;
-    int pc = 0;
-    while (pc < M - 1 && tcum[pc + 1] < tt) ++pc;
+    const double tt = pt.time_of(k, step);
+    const int pc = pt.seek(0, tt);
     double pos[D], vel[D], acc[D];
-    audit_sample_state<D>(cs, pc, tt - tcum[pc], pos, vel, acc);
+    pt.state(pc, tt, pos, vel, acc);
     double *out = out0 + (size_t)k * kFleetRow;
 #pragma unroll
     for (int d = 0; d < D; ++d) {
@@ -348,9 +313,9 @@ __global__ __launch_bounds__(kWave) void fleet_splice_kernel(
   }
 }
 
-// audit_kernel's accumulation (neo_audit.hpp) over GIVEN rows: sample j is row j * stride of the mission's command
-// array, j < count = ceil(n_flown / stride).  Per round a lane loads the rows of its kAuditU samples, then has their
-// kAuditU map gathers in flight before the first is consumed.
+// audit_kernel's accumulation (neo_audit.hpp AuditAcc) over GIVEN rows: sample j is row j * stride of the mission's
+// command array, j < count = ceil(n_flown / stride).  Per round a lane loads the rows of its kAuditU samples, then has
+// their kAuditU map gathers in flight before the first is consumed.
 __global__ __launch_bounds__(kWave) void fleet_audit_kernel(
     LaunchList list, DevParams prm, const Map2D *__restrict__ maps,
     const int *__restrict__ scene_slot, int nmaps, const double *__restrict__ cmd, int cap,
@@ -361,16 +326,8 @@ __global__ __launch_bounds__(kWave) void fleet_audit_kernel(
   const int b = list.request(blockIdx.x);  // wave-uniform
   if (b < 0) return;
   const int lane = lane_id();
-  double *rec = audit + (size_t)b * NEO_AUDIT_FIELDS;
-  auto reject = [&]() {
-    if (lane < NEO_AUDIT_FIELDS) rec[lane] = __builtin_nan("");
-    if (lane == 0) {
-      count[b] = 0;
-      flags[b] = NEO_AUDIT_FLAG_NONFINITE;
-    }
-  };
   const int slot = scene_slot ? scene_slot[b] : 0;
-  if (slot < 0 || slot >= nmaps) return reject();
+  if (slot < 0 || slot >= nmaps) return audit_reject(b, audit, count, flags);
   const Map2D map = maps[slot];
   int nf = n_flown[b];
   nf = nf < 0 ? 0 : (nf > cap ? cap : nf);
@@ -379,11 +336,7 @@ __global__ __launch_bounds__(kWave) void fleet_audit_kernel(
 
   const Lookup2D<double> lk(map);
   const double vmax2 = prm.v_max * prm.v_max, safe = prm.safe_dis;
-  double path = 0.0, feas = 0.0, coll = 0.0, speed_max = 0.0, acc_max = 0.0, dmin = __builtin_inf();
-  int kmin = INT_MAX, kunsafe = -1, outside = 0, bad = 0;
-  double carry[D];  // position of the sample before this sub-round's lane 0 (lane 63 of the one before)
-#pragma unroll
-  for (int d = 0; d < D; ++d) carry[d] = 0.0;
+  AuditAcc<D> acc;
   for (int base = 0; base < cnt; base += kAuditU * kWave) {
     double st[kAuditU][kFleetRow];
     bool on[kAuditU];
@@ -406,69 +359,18 @@ __global__ __launch_bounds__(kWave) void fleet_audit_kernel(
     for (int u = 0; u < kAuditU; ++u) rw[u] = lk.load(ad[u]);
 #pragma unroll
     for (int u = 0; u < kAuditU; ++u) {
-      const int k = base + u * kWave + lane;
-      const double pos[D] = {st[u][0], st[u][1]}, vel[D] = {st[u][2], st[u][3]}, acc[D] = {st[u][4], st[u][5]};
-      double prev[D];
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        prev[d] = from_prev(pos[d], carry[d]);
-        carry[d] = rdlane(pos[d], kWave - 1);
-      }
-      double gdrop[D];
+      const double pos[D] = {st[u][0], st[u][1]}, vel[D] = {st[u][2], st[u][3]}, ac[D] = {st[u][4], st[u][5]};
+      double prev[D], gdrop[D];
+      acc.neighbour(pos, prev);
       const double dk = lk.finish<D>(ad[u], rw[u], gdrop);
       if (on[u]) {
-#pragma unroll
-        for (int q = 0; q < kFleetRow; ++q)
-          if (!__builtin_isfinite(st[u][q])) bad = 1;
-        const double v2 = audit_norm2<D>(vel), a2 = audit_norm2<D>(acc);
-        const double speed = sqrt(v2), accn = sqrt(a2);
-        speed_max = speed > speed_max ? speed : speed_max;
-        acc_max = accn > acc_max ? accn : acc_max;
-        const double vv = v2 - vmax2;  // :346-348
-        if (vv > 0.0) feas += vv * vv * vv;
-        if (k >= 1) {  // :341-343
-          double dp[D];
-#pragma unroll
-          for (int d = 0; d < D; ++d) dp[d] = pos[d] - prev[d];
-          path += sqrt(audit_norm2<D>(dp));
-        }
-        const double vd = safe - dk;  // :351-355
-        if (vd > 0.0) {
-          coll += vd * vd * vd;
-          if (kunsafe < 0) kunsafe = k;
-        }
-        if (dk < dmin) {
-          dmin = dk;
-          kmin = k;
-        }
-        if (!ad[u].inside) outside = 1;
+        acc.kinematics(pos, vel, ac, vmax2);
+        acc.clearance(base + u * kWave + lane, pos, prev, dk, ad[u].inside, safe);
       }
     }
   }
-  if (wave_max_nonneg(bad)) return reject();
-  double s_path, s_feas, s_coll, s_unused;
-  wave_sum4(path, feas, coll, 0.0, s_path, s_feas, s_coll, s_unused);
-  const double vmx = wave_max_nonneg(speed_max), amx = wave_max_nonneg(acc_max);
-  wave_min_first(dmin, kmin);
-  const int ukey = wave_max_nonneg(kunsafe >= 0 ? INT_MAX - kunsafe : 0);  // largest key = earliest unsafe sample
-  const int outs = wave_max_nonneg(outside);
-  if (lane == 0) {
-    auto t_of = [&](int k) { return (double)(k * stride) / hz; };  // the time of command row k * stride
-    const double weighted = w0 * s_path + w1 * s_feas + w2 * s_coll;  // np.dot(raw_cost, metric_weights) (:357)
-    rec[NEO_AUDIT_PATH_LENGTH] = s_path;
-    rec[NEO_AUDIT_FEASIBILITY] = s_feas;
-    rec[NEO_AUDIT_COLLISION] = s_coll;
-    rec[NEO_AUDIT_WEIGHTED] = weighted;
-    rec[NEO_AUDIT_MIN_CLEARANCE] = dmin;
-    rec[NEO_AUDIT_T_MIN_CLEARANCE] = cnt > 0 ? t_of(kmin) : -1.0;
-    rec[NEO_AUDIT_MAX_SPEED] = vmx;
-    rec[NEO_AUDIT_MAX_ACC] = amx;
-    rec[NEO_AUDIT_T_FIRST_UNSAFE] = ukey > 0 ? t_of(INT_MAX - ukey) : -1.0;
-    rec[NEO_AUDIT_DURATION] = (double)nf / hz;
-    count[b] = cnt;
-    flags[b] = (ukey > 0 ? NEO_AUDIT_FLAG_UNSAFE : 0) | (weighted > 10.0 * prm.coll_tol ? NEO_AUDIT_FLAG_METRIC_FAIL : 0) |
-               (outs ? NEO_AUDIT_FLAG_OUTSIDE_MAP : 0);
-  }
+  acc.finish(b, cnt, (double)nf / hz, [&](int k) { return (double)(k * stride) / hz; },  // the time of command row k * stride
+             w0, w1, w2, prm.coll_tol, audit, count, flags);
 }
 
 }  // namespace neo

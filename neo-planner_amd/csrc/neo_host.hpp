@@ -206,6 +206,16 @@ struct SampleArgs {
   bool io32 = false;      // neo_sampled_terms_batch_f32_dev (fp32 sampling only)
 };
 
+// neo_eval_traj_batch: one traj_state_kernel launch (neo_disp_audit.hip)
+struct TrajStateArgs {
+  int B, M;
+  const double *x, *head, *tail;
+  double hz;
+  int K;
+  double *state;
+  int *count;
+};
+
 // neo_audit_traj_batch_dev: one audit_kernel launch (neo_disp_audit.hip)
 struct AuditArgs {
   int B, M;
@@ -530,6 +540,9 @@ inline int slots_for(int M, int D) {
   return ns <= 3 ? (ns < 1 ? 1 : ns) : 4;  // (3: cfg5's n = 161 -- a quarter fewer optimiser-vector instructions than 4 slots)
 }
 
+// doubles of a suspended run's state (neo_optimize_batch_budget_dev; layout: neo_kernels.hpp save_run), n variables and m pairs
+inline size_t opt_state_doubles(int n, int m) { return 64 + 5 * (size_t)n + kWave + 2 * (size_t)m * (size_t)n; }
+
 // ---- run-time values to template arguments: the one place where a field's (element type, layout) and a problem's
 // (FLAT slots, lane layout) become types.  Each visitor calls f with empty tag values; the unit's lambda reads the types
 // off them and names the kernel it owns.  Templates and inlined lambdas only: nothing is allocated, no std::function.
@@ -596,6 +609,7 @@ int visit_slots(int M, int flags, F f) {
 int dispatch_eval(neo_ctx *c, const MapEntry &e, int D, const EvalArgs &a);
 int dispatch_sample(neo_ctx *c, const MapEntry &e, int D, const SampleArgs &a);
 int dispatch_audit(neo_ctx *c, int kind, int elem, int layout, int D, const AuditArgs &a);  // neo_disp_audit.hip
+int dispatch_traj_state(neo_ctx *c, int D, const TrajStateArgs &a);                         // neo_disp_audit.hip
 // the families behind dispatch_opt (neo_abi.hip)
 int launch_opt_2d(neo_ctx *c, int D, bool f32, const OptArgs &a);           // neo_disp_opt2d.hip
 int launch_opt_3d_f32(neo_ctx *c, int elem, int layout, const OptArgs &a);  // neo_disp_opt3d_f32.hip

@@ -35,12 +35,6 @@
 // 889 k at two per SIMD without spills; LDS: fp32 pairs + staging = 12.6 KB of the 13.3 KB a twelfth of a CU has
 #define NEO_X_OCC 3
 #endif
-#ifndef NEO_SM_MAX_SLOTS
-#define NEO_SM_MAX_SLOTS 2  // FLAT slots up to which the optimiser runs as the resumable state machine (neo_lbfgs_sm.hpp)
-#endif
-#ifndef NEO_W2_MAX_SLOTS
-#define NEO_W2_MAX_SLOTS 4  // two waves per SIMD for every n <= 256 (four FLAT slots: with fp32 pairs, pairs_in_f32)
-#endif
 #include "neo_device.hpp"
 #include "neo_lbfgs.hpp"
 #include "neo_lbfgs_sm.hpp"
@@ -609,8 +603,7 @@ struct DevBackend {
 // goes to `st` (doubles: every fp32 value converts exactly both ways) and a later launch picks the run up at the very
 // evaluation it was about to make.  Layout: [64 scalars | x g t r d (n each) | rho / alpha lanes (64) | pairs (2 m n)].
 // The pairs are the LDS region as it stands, element for element (hist_index / hist_index_rows decide where a value lies,
-// here as there: a state is read by the build that wrote it).
-__host__ __device__ inline size_t opt_state_doubles(int n, int m) { return 64 + 5 * (size_t)n + kWave + 2 * (size_t)m * (size_t)n; }
+// here as there: a state is read by the build that wrote it).  Its size is opt_state_doubles (neo_host.hpp).
 
 template <class BE, class Mach>
 __device__ __forceinline__ void save_run(BE &be, const Mach &mc, double *st) {
@@ -689,19 +682,6 @@ __device__ __forceinline__ void load_run(BE &be, Mach &mc, const double *st) {
   const double *h = v + 5 * n + kWave;
   for (int i = lane; i < 2 * be.m * n; i += kWave) be.hist[i] = (typename BE::Hist)h[i];
   lds_wave_sync();
-}
-
-// bnd_lds: 6 * D elements of LDS for the layouts with one dimension per lane (stage_boundary), unused otherwise
-template <class LG = WaveLanes, int D, int DL, typename Num>
-__device__ __forceinline__ void load_boundary(Traj<D, DL, Num> &t, const double *head, const double *tail, int M,
-                                              Num *bnd_lds = nullptr) {
-  t.M = M;
-  t.nq = D * (M - 1);
-  t.n = t.nq + M;
-  t.L = sample_lanes_per_piece(M);
-  t.head = head;
-  t.tail = tail;
-  stage_boundary<D, LG>(t, bnd_lds);
 }
 
 struct MapTable {

@@ -12,6 +12,13 @@
 namespace neo {
 
 constexpr int kSlots = 4;  // FLAT layout: n <= 256
+// limits on FLAT slots the host's dispatch and the kernels agree on
+#ifndef NEO_SM_MAX_SLOTS
+#define NEO_SM_MAX_SLOTS 2  // FLAT slots up to which the optimiser runs as the resumable state machine (neo_lbfgs_sm.hpp)
+#endif
+#ifndef NEO_W2_MAX_SLOTS
+#define NEO_W2_MAX_SLOTS 4  // two waves per SIMD for every n <= 256 (four FLAT slots: with fp32 pairs, pairs_in_f32)
+#endif
 
 struct DevParams {
   double v_max, T_min, T_max, safe_dis, delta_t;

@@ -4,7 +4,8 @@ The library is several translation units -- the C ABI in three (neo_abi.hip, neo
 share neo_abi_util.hpp and nobody else sees it) plus one unit per kernel family (neo_disp_*.hip) -- compiled
 in parallel and linked into one shared object.  Objects are cached under csrc/build/ by CONTENT: an object's name carries a
 hash of its command line, its source and the headers it includes -- read off the #include "..." lines themselves, so a
-header recompiles exactly the units that see it; the library's stamp file the hash of all of them.  Time stamps
+header recompiles exactly the units that see it (the optimiser's headers: the ten units that launch a fused kernel;
+neo_device.hpp: those and the audit and fleet units, which solve through neo_pieces.hpp; the C ABI units: neither); the library's stamp file the hash of all of them.  Time stamps
 play no part (a checkout that restores a file, or a copy of the tree that does not keep them, rebuilds nothing)."""
 import concurrent.futures
 import hashlib

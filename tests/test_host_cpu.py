@@ -169,11 +169,26 @@ def test_units_without_minco_do_not_see_its_headers():
     neo_device.hpp nor the optimiser's headers, so an edit there does not recompile them"""
     from neo_planner_amd import build as b
     for unit in ("neo_disp_esdf", "neo_disp_depth", "neo_disp_onboard", "neo_disp_backbone", "neo_disp_record", "neo_disp_init",
-                 "neo_disp_plan", "neo_disp_batch", "neo_disp_adaptive", "neo_abi_fleet", "neo_abi_plan"):
+                 "neo_disp_plan", "neo_disp_batch", "neo_disp_adaptive", "neo_abi", "neo_abi_fleet", "neo_abi_plan"):
         seen = b.headers_of(unit + ".hip")
         assert "neo_map.hpp" in seen and "neo_wave.hpp" in seen, unit
         assert not [h for h in seen if h in ("neo_device.hpp", "neo_kernels.hpp", "neo_group_kernel.hpp", "neo_linesearch.hpp")
                     or h.startswith("neo_lbfgs")], unit
+
+
+def test_only_the_optimiser_units_see_the_optimiser_headers():
+    """neo_kernels.hpp (DevBackend, L-BFGS, the line search) reaches the ten units that launch a fused kernel and no other;
+    the audit and fleet units solve a trajectory through the piece table (neo_pieces.hpp over neo_device.hpp) alone"""
+    from neo_planner_amd import build as b
+    fused = {s for s in b.SOURCES if "neo_kernels.hpp" in b.headers_of(s)}
+    assert fused == {"neo_disp_eval.hip", "neo_disp_sample.hip", "neo_disp_group.hip", "neo_disp_opt2d.hip", "neo_disp_opt2d_x.hip",
+                     "neo_disp_opt3d_f32.hip", "neo_disp_opt3d_f64.hip", "neo_disp_opt3d_w2.hip", "neo_disp_opt3d_x.hip",
+                     "neo_disp_opt3d_b.hip"}
+    assert len([s for s in fused if s.startswith("neo_disp_opt")]) == 7
+    for unit in ("neo_disp_audit.hip", "neo_disp_fleet.hip"):
+        seen = b.headers_of(unit)
+        assert "neo_device.hpp" in seen and "neo_pieces.hpp" in seen, unit
+        assert not [h for h in seen if h in ("neo_kernels.hpp", "neo_linesearch.hpp") or h.startswith("neo_lbfgs")], unit
 
 
 def test_trace_parity_cases_reach_the_kernels_they_name():

@@ -3,7 +3,9 @@
 libneo_planner_hip.so (llvm-objdump -d on the entries of the library's offload bundles; no GPU needed) and compares
 the instructions symbol by symbol: mnemonics, operands and encodings.  The address a listing line carries is left out --
 where a kernel sits in its code object follows the order in which the unit instantiates its templates, and branch targets
-are printed relative to their symbol; so is the padding behind the last kernel of a code object.
+are printed relative to their symbol; so is the padding behind the last kernel of a code object, and so is the literal of
+the s_add_u32 behind an s_getpc_b64 (the distance to a table elsewhere in the code object: it moves when a kernel leaves
+the unit).
 
     python tools/compare_device_code.py old.so [new.so]      (default new = the in-tree build)
 """
@@ -45,6 +47,13 @@ def kernels(lib):
                     syms[cur] = []
                 elif cur:
                     syms[cur].append(re.sub(r"// [0-9A-F]{12}: ", "// ", line))
+    for lines in syms.values():
+        # s_getpc_b64 / s_add_u32 lo, lo, literal / s_addc_u32 hi, hi, ...: the distance from here to a table or function
+        # elsewhere in the code object -- layout, as the addresses are.  Only this exact triple is masked.
+        for i in range(1, len(lines) - 1):
+            if ("s_getpc_b64" in lines[i - 1] and re.match(r"\s*s_add_u32 s\d+, s\d+, 0x[0-9a-f]+\s", lines[i])
+                    and re.match(r"\s*s_addc_u32 s\d+, s\d+, ", lines[i + 1])):
+                lines[i] = re.sub(r"0x[0-9a-f]+(\s+// [0-9A-F]{8}) [0-9A-F]{8}", r"<pcrel>\1", lines[i])
     for lines in syms.values():  # (the zero padding objdump prints as "..." behind a code object's last kernel)
         while lines and lines[-1].strip() in ("", "..."):
             lines.pop()
