@@ -902,6 +902,54 @@ int neo_backbone_activation_dev(neo_ctx *ctx, const float *weights, size_t n_wei
  * NEO_ERR_INVALID: a launch outside 0 .. NEO_BACKBONE_LAUNCHES - 1, H or W < 1, a NULL pointer. */
 int neo_backbone_activation_shape(int launch, int H, int W, int *h, int *w, int *c);
 
+/* ---- the same backbone with bf16 storage, on the bf16 matrix instructions: a second, opt-in route ----------------
+ * The same network, the same 21 launches in the same order and the same fp32 features out; the fp32 calls above keep
+ * their bits.  Weights of the 19 convolutions and every stored activation are bf16 (fp32's exponent range: no input and
+ * no set of weights overflows a stored activation); accumulators, biases, the residual sum, the ReLU, the stem's
+ * arithmetic, the average pool and the fc are fp32.
+ * NEO_BACKBONE_BF16_BYTES bytes of the PACKED blob, made from the fp32 blob by neo_backbone_pack_bf16_dev, the parts in
+ * the fp32 blob's order, back to back (every part's size is a multiple of 16 bytes, so every part starts 16-byte aligned):
+ *   the stem           W[49][64] fp32, b[64] fp32, verbatim
+ *   a convolution      W as bf16 (round to nearest even) in the layout [ky][kx][cin / 8][cout][8], the value at
+ *                      [ky][kx][g][co][j] being the fp32 blob's W[ky][kx][ci = 8 g + j][co]; then b[cout] fp32, verbatim
+ *   the fc             W[24][512] fp32, b[24] fp32, verbatim
+ * 11 157 504 bf16 values and 20 248 floats.  Activations are channels-last bf16, [image][y][x][c].
+ * Summation: an output element of a convolution is accumulated in fp32 from its fp32 bias over the taps (ky, kx)
+ * row-major and, inside a tap, over the input channels ascending, 16 a matrix instruction; K is never split, a padding tap
+ * contributes zeros, and an image's features depend on neither n nor the image's position among the n.  The products
+ * are exact in fp32, so a launch's fp32 value differs from the exact sum of its products by the accumulation's rounding
+ * alone; HOW the instruction adds its 16 products is not promised (it is held to the bound of any fp32 accumulation,
+ * launch by launch, through neo_backbone_bf16_activation_dev).  The residual is added and the ReLU applied in fp32, and
+ * the result is rounded to bf16 once, to nearest even, at the store; so is the stem's pooled value. */
+#define NEO_BACKBONE_BF16_BYTES 22396000
+/* packed_out[NEO_BACKBONE_BF16_BYTES] (16-byte aligned) from weights_f32[NEO_BACKBONE_FLOATS]: device pointers,
+ * asynchronous on the context's stream.  NEO_ERR_INVALID before any launch: a NULL pointer, another n_weights or
+ * packed_bytes, a misaligned pointer. */
+int neo_backbone_pack_bf16_dev(neo_ctx *ctx, const float *weights_f32, size_t n_weights, void *packed_out, size_t packed_bytes);
+/* bytes of `workspace` for n images of H x W: three bf16 activation buffers of the largest layer output.  0 where
+ * neo_backbone_workspace_bytes returns 0. */
+size_t neo_backbone_bf16_workspace_bytes(int n, int H, int W);
+/* feature_out[n][24] fp32 from images_u8[n][H][W] and the packed blob: device pointers, NEO_BACKBONE_LAUNCHES launches,
+ * asynchronous on the context's stream.  `workspace` (16-byte aligned, at least neo_backbone_bf16_workspace_bytes(n, H, W)
+ * bytes) is written and holds nothing afterwards; no other memory is touched.  Any H, W >= 1 is valid.  n = 0 launches
+ * nothing.  NEO_ERR_INVALID before any launch, with a neo_last_error message: a NULL pointer, n < 0, H or W < 1,
+ * n * H * W >= 2^31, packed_bytes != NEO_BACKBONE_BF16_BYTES, a misaligned blob, a misaligned or too small workspace. */
+int neo_backbone_features_bf16_dev(neo_ctx *ctx, const void *packed, size_t packed_bytes, const uint8_t *images_u8, int n, int H,
+                                   int W, void *workspace, size_t workspace_bytes, float *feature_out);
+/* The same call for measurements, as neo_backbone_launch_times: it WAITS for the stream and writes the
+ * NEO_BACKBONE_LAUNCHES times, in milliseconds, to the HOST array launch_ms.  n >= 1. */
+int neo_backbone_bf16_launch_times(neo_ctx *ctx, const void *packed, size_t packed_bytes, const uint8_t *images_u8, int n, int H,
+                                   int W, void *workspace, size_t workspace_bytes, float *feature_out, float *launch_ms);
+/* One launch's output, for tests: runs launches 0 .. `launch` of the chain and hands out what launch `launch` stored, as
+ * uint16 bf16 bits in act_bf16_out, and the fp32 values it rounded (written by the same launch, on the same path up to
+ * the store) in act_f32_out; both device arrays of act_elems = n * h * w * c elements of neo_backbone_activation_shape.
+ * Either pointer may be NULL, not both.  Launch 20 (the pool and fc) has fp32 values only: act_bf16_out must be NULL.
+ * The refusals of neo_backbone_features_bf16_dev, and NEO_ERR_INVALID before any launch for a launch outside
+ * 0 .. NEO_BACKBONE_LAUNCHES - 1 and another act_elems. */
+int neo_backbone_bf16_activation_dev(neo_ctx *ctx, const void *packed, size_t packed_bytes, const uint8_t *images_u8, int n,
+                                     int H, int W, void *workspace, size_t workspace_bytes, int launch, uint16_t *act_bf16_out,
+                                     float *act_f32_out, size_t act_elems);
+
 /* ---- the `batch` planner mode on resident arrays (traj_planner/expert_planner.py:103-168) ----------------
  * MinJerkPlanner.batch_plan optimises K laterally shifted initial guesses of one request and keeps the cheapest
  * feasible one.  These two calls are what surrounds the optimiser launch for P requests at once, 2-D (D = 2), fp64:

@@ -795,4 +795,104 @@ int neo_backbone_activation_dev(neo_ctx *c, const float *weights, size_t n_weigh
   return NEO_OK;
 }
 
+// ---- the same backbone on bf16 storage and the bf16 matrix cores (kernels: neo_backbone_bf16.hpp)
+int neo_backbone_pack_bf16_dev(neo_ctx *c, const float *weights_f32, size_t n_weights, void *packed_out, size_t packed_bytes) {
+  if (!c) return NEO_ERR_INVALID;
+  int rc = null_check(c, "backbone bf16 pack: null buffer", {weights_f32, packed_out});
+  if (rc) return rc;
+  if (n_weights != (size_t)NEO_BACKBONE_FLOATS)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone bf16 pack: n_weights must be NEO_BACKBONE_FLOATS (11177752)");
+  if (packed_bytes != (size_t)NEO_BACKBONE_BF16_BYTES)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone bf16 pack: packed_bytes must be NEO_BACKBONE_BF16_BYTES (22396000)");
+  if (reinterpret_cast<uintptr_t>(packed_out) % 16 || reinterpret_cast<uintptr_t>(weights_f32) % 4)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone bf16 pack: packed_out must be 16-byte aligned, weights 4-byte");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  return launched(c, backbone_bf16_pack(c, weights_f32, packed_out));
+}
+
+size_t neo_backbone_bf16_workspace_bytes(int n, int H, int W) {
+  if (n <= 0 || H < 1 || W < 1 || (size_t)n * H * W > (size_t)INT32_MAX) return 0;
+  return backbone_bf16_workspace_bytes(n, H, W);
+}
+
+// the checks of a bf16 backbone call (context unlocked); n = 0 passes them.  `out`: the call's required output
+static int backbone_bf16_check(neo_ctx *c, const void *packed, size_t packed_bytes, const uint8_t *images_u8, int n, int H,
+                               int W, void *workspace, size_t workspace_bytes, const void *out) {
+  if (!c) return NEO_ERR_INVALID;
+  if (n < 0 || H < 1 || W < 1) return fail_locked(c, NEO_ERR_INVALID, "backbone bf16: n must be >= 0, H and W >= 1");
+  if ((size_t)n * H * W > (size_t)INT32_MAX)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone bf16: n * H * W must stay below 2^31 (split the images over several calls)");
+  int rc = null_check(c, "backbone bf16: null buffer", {packed, images_u8, workspace, out});
+  if (rc) return rc;
+  if (packed_bytes != (size_t)NEO_BACKBONE_BF16_BYTES)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone bf16: packed_bytes must be NEO_BACKBONE_BF16_BYTES (22396000)");
+  if (reinterpret_cast<uintptr_t>(workspace) % 16 || reinterpret_cast<uintptr_t>(packed) % 16)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone bf16: workspace and packed must be 16-byte aligned");
+  if (n > 0 && workspace_bytes < backbone_bf16_workspace_bytes(n, H, W))
+    return fail_locked(c, NEO_ERR_INVALID, "backbone bf16: workspace smaller than neo_backbone_bf16_workspace_bytes(n, H, W)");
+  return NEO_OK;
+}
+
+int neo_backbone_features_bf16_dev(neo_ctx *c, const void *packed, size_t packed_bytes, const uint8_t *images_u8, int n, int H,
+                                   int W, void *workspace, size_t workspace_bytes, float *feature_out) {
+  const int rc = backbone_bf16_check(c, packed, packed_bytes, images_u8, n, H, W, workspace, workspace_bytes, feature_out);
+  if (rc || n == 0) return rc;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  return launched(c, backbone_bf16_features(c, packed, images_u8, n, H, W, workspace, feature_out));
+}
+
+int neo_backbone_bf16_launch_times(neo_ctx *c, const void *packed, size_t packed_bytes, const uint8_t *images_u8, int n, int H,
+                                   int W, void *workspace, size_t workspace_bytes, float *feature_out, float *launch_ms) {
+  int rc = backbone_bf16_check(c, packed, packed_bytes, images_u8, n, H, W, workspace, workspace_bytes, feature_out);
+  if (rc) return rc;
+  if (!launch_ms || n == 0) return fail_locked(c, NEO_ERR_INVALID, "backbone bf16: launch times need launch_ms and n >= 1");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  // every exit destroys the events created so far; the first failing HIP call is the one reported
+  hipEvent_t ev[NEO_BACKBONE_LAUNCHES + 1] = {};
+  hipError_t e = hipSuccess;
+  const char *what = "hipEventCreate";
+  for (int i = 0; e == hipSuccess && i <= NEO_BACKBONE_LAUNCHES; ++i) e = hipEventCreate(&ev[i]);
+  if (e == hipSuccess) {
+    rc = launched(c, backbone_bf16_features(c, packed, images_u8, n, H, W, workspace, feature_out, ev));
+    if (!rc) what = "hipStreamSynchronize", e = hipStreamSynchronize(c->stream);
+    for (int i = 0; !rc && e == hipSuccess && i < NEO_BACKBONE_LAUNCHES; ++i)
+      what = "hipEventElapsedTime", e = hipEventElapsedTime(&launch_ms[i], ev[i], ev[i + 1]);
+  }
+  for (hipEvent_t &v : ev)
+    if (v) hipEventDestroy(v);
+  if (!rc && e != hipSuccess) rc = fail(c, NEO_ERR_HIP, std::string("backbone bf16: ") + what + ": " + hipGetErrorString(e));
+  return rc;
+}
+
+int neo_backbone_bf16_activation_dev(neo_ctx *c, const void *packed, size_t packed_bytes, const uint8_t *images_u8, int n, int H,
+                                     int W, void *workspace, size_t workspace_bytes, int launch, uint16_t *act_bf16_out,
+                                     float *act_f32_out, size_t act_elems) {
+  const void *some = act_bf16_out ? static_cast<const void *>(act_bf16_out) : act_f32_out;
+  int rc = backbone_bf16_check(c, packed, packed_bytes, images_u8, n, H, W, workspace, workspace_bytes, some);
+  if (rc) return rc;
+  if (launch < 0 || launch >= NEO_BACKBONE_LAUNCHES)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone bf16: launch must be 0 .. NEO_BACKBONE_LAUNCHES - 1");
+  const bool fc = launch == NEO_BACKBONE_LAUNCHES - 1;
+  if (fc && (act_bf16_out || !act_f32_out))
+    return fail_locked(c, NEO_ERR_INVALID, "backbone bf16: the pool and fc write fp32 only: act_bf16_out NULL, act_f32_out given");
+  int h, w, ch;
+  backbone_activation_shape(launch, H, W, &h, &w, &ch);
+  if (act_elems != (size_t)n * h * w * ch)
+    return fail_locked(c, NEO_ERR_INVALID, "backbone bf16: act_elems must be n * h * w * c of neo_backbone_activation_shape");
+  if (n == 0) return NEO_OK;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  // the pool + fc writes act_f32_out itself; a stem or a convolution writes its fp32 values there through its debug
+  // epilogue, and its bf16 buffer of the workspace is copied behind the launch
+  const void *written = nullptr;
+  rc = launched(c, backbone_bf16_features(c, packed, images_u8, n, H, W, workspace, fc ? act_f32_out : nullptr, nullptr, launch,
+                                          &written, fc ? nullptr : act_f32_out));
+  if (rc || fc || !act_bf16_out) return rc;
+  HIPCHK(c, hipMemcpyAsync(act_bf16_out, written, act_elems * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
+  return NEO_OK;
+}
+
 }  // extern "C"

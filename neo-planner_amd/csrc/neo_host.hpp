@@ -388,6 +388,17 @@ int backbone_features(neo_ctx *c, const float *weights, const unsigned char *ima
 // h, w, c of what launch `launch` writes an image of H x W ([h][w][c] channels-last; 1, 1, 24 for the pool + fc)
 void backbone_activation_shape(int launch, int H, int W, int *h, int *w, int *c);
 
+// neo_backbone_*bf16*: the same chain on bf16 storage and the bf16 matrix cores (neo_disp_backbone_bf16.hip, kernels in
+// neo_backbone_bf16.hpp).  packed: NEO_BACKBONE_BF16_BYTES bytes (backbone_bf16_pack makes them from the fp32 blob);
+// `workspace` holds backbone_bf16_workspace_bytes(n, H, W) bytes.  events, last, written: as above (a bf16 buffer of the
+// workspace, or feature_out); dbg_last: NULL, or where launch `last` (a stem or a convolution) also writes its fp32
+// values before the rounding
+size_t backbone_bf16_workspace_bytes(int n, int H, int W);
+int backbone_bf16_pack(neo_ctx *c, const float *weights, void *packed);
+int backbone_bf16_features(neo_ctx *c, const void *packed, const unsigned char *images, int n, int H, int W, void *workspace,
+                           float *feature_out, hipEvent_t *events = nullptr, int last = NEO_BACKBONE_LAUNCHES - 1,
+                           const void **written = nullptr, float *dbg_last = nullptr);
+
 // neo_batch_*_dev: the `batch` planner mode on resident arrays (neo_disp_batch.hip, kernels in neo_batch.hpp).  P =
 // the list's n requests; tau, off and w are HOST arrays (M, K and 4 values), handed to the kernels by value.
 struct BatchCandArgs {

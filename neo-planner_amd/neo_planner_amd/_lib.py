@@ -52,6 +52,7 @@ NEO_DEPTH_MAX_BOXES = 1024         # neo_depth_*: boxes a scene
 # neo_init_*: sizes of the motion vector, a feature row, the network's output, x0, and the head's weight blob
 NEO_INIT_MOTION, NEO_INIT_FEATURE, NEO_INIT_OUTPUT, NEO_INIT_X, NEO_INIT_HEAD_FLOATS = 24, 24, 9, 7, 20817
 NEO_BACKBONE_FLOATS, NEO_BACKBONE_LAUNCHES = 11177752, 21     # neo_backbone_*: the weight blob, launches a call
+NEO_BACKBONE_BF16_BYTES = 22396000                            # neo_backbone_*bf16*: the packed blob
 
 # every symbol include/neo_planner.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -86,6 +87,8 @@ EXPORTS = [
     "neo_geo_guess_dev", "neo_geo_mask_builds",
     "neo_backbone_workspace_bytes", "neo_backbone_features_dev", "neo_backbone_launch_times",
     "neo_backbone_activation_dev", "neo_backbone_activation_shape",
+    "neo_backbone_pack_bf16_dev", "neo_backbone_bf16_workspace_bytes", "neo_backbone_features_bf16_dev",
+    "neo_backbone_bf16_launch_times", "neo_backbone_bf16_activation_dev",
 ]
 
 
@@ -225,6 +228,12 @@ def load():
     L.neo_backbone_launch_times.argtypes = L.neo_backbone_features_dev.argtypes + [c_p]
     L.neo_backbone_activation_dev.argtypes = L.neo_backbone_features_dev.argtypes[:-1] + [c_i, c_p, ctypes.c_size_t]
     L.neo_backbone_activation_shape.argtypes = [c_i, c_i, c_i] + [ctypes.POINTER(ctypes.c_int)] * 3
+    L.neo_backbone_pack_bf16_dev.argtypes = [c_p, c_p, ctypes.c_size_t, c_p, ctypes.c_size_t]
+    L.neo_backbone_bf16_workspace_bytes.argtypes = [c_i, c_i, c_i]
+    L.neo_backbone_bf16_workspace_bytes.restype = ctypes.c_size_t
+    L.neo_backbone_features_bf16_dev.argtypes = list(L.neo_backbone_features_dev.argtypes)
+    L.neo_backbone_bf16_launch_times.argtypes = L.neo_backbone_features_bf16_dev.argtypes + [c_p]
+    L.neo_backbone_bf16_activation_dev.argtypes = L.neo_backbone_features_bf16_dev.argtypes[:-1] + [c_i, c_p, c_p, ctypes.c_size_t]
     L.neo_profile_enable.argtypes = [c_p, c_i]
     L.neo_profile_read.argtypes = [c_p, c_i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_d)]
     L.neo_profile_reset.argtypes = [c_p]
@@ -306,6 +315,10 @@ class Context:
     def backbone_workspace_bytes(self, n, H, W):
         """neo_backbone_workspace_bytes: what neo_backbone_features_dev needs for n images of H x W"""
         return int(self.lib.neo_backbone_workspace_bytes(int(n), int(H), int(W)))
+
+    def backbone_bf16_workspace_bytes(self, n, H, W):
+        """neo_backbone_bf16_workspace_bytes: what neo_backbone_features_bf16_dev needs for n images of H x W"""
+        return int(self.lib.neo_backbone_bf16_workspace_bytes(int(n), int(H), int(W)))
 
     def set_params(self, **kw):
         for k, v in kw.items():

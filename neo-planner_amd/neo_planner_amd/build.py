@@ -24,7 +24,7 @@ SOURCES = ["neo_abi.hip", "neo_disp_eval.hip", "neo_disp_sample.hip", "neo_disp_
            "neo_disp_opt3d_f64.hip", "neo_disp_opt3d_w2.hip", "neo_disp_opt3d_x.hip", "neo_disp_group.hip", "neo_disp_opt3d_b.hip",
            "neo_disp_audit.hip", "neo_disp_geo.hip", "neo_disp_fleet.hip", "neo_disp_batch.hip", "neo_disp_esdf.hip",
            "neo_disp_plan.hip", "neo_disp_depth.hip", "neo_disp_onboard.hip", "neo_disp_record.hip", "neo_disp_init.hip",
-           "neo_disp_adaptive.hip", "neo_disp_backbone.hip",
+           "neo_disp_adaptive.hip", "neo_disp_backbone.hip", "neo_disp_backbone_bf16.hip",
            # (the kernel-less units of the C ABI last: the units with device code keep their places in the link)
            "neo_abi_fleet.hip", "neo_abi_plan.hip"]
 STAMP = LIB + ".stamp"    # hash of command lines + sources + included headers the library was built from (travels with the library)

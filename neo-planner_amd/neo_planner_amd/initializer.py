@@ -422,17 +422,128 @@ def backbone_launch_model(blob, rec, act_in, resid=None, absolute=False):
     return (y if rec.kind == "poolfc" else y.permute(0, 2, 3, 1)).contiguous().numpy()
 
 
-def backbone_features_kernel(ctx, blob, images, out=None, chunk=512, workspace=None):
+BACKBONE_BF16_BYTES = 22396000      # NEO_BACKBONE_BF16_BYTES (include/neo_planner.h)
+
+
+def bf16_bits(a):
+    """float32 values -> their bf16 bit patterns (uint16), round to nearest even, in integer arithmetic: the upper half of
+    the word after adding 0x7FFF plus the lowest kept bit; a NaN stays a NaN (quiet bit set, payload's upper bits kept)"""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    rounded = (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    return np.where(nan, (u >> 16) | 0x40, rounded).astype(np.uint16)
+
+
+def bf16_from_bits(b):
+    """bf16 bit patterns (uint16) -> the float32 values they are"""
+    return (np.ascontiguousarray(b, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
+
+
+def bf16_round(a):
+    """float32 -> float32 holding bf16 values: round to nearest even, as the device's conversion at a store"""
+    return bf16_from_bits(bf16_bits(a))
+
+
+def _bf16_parts():
+    """the parts of the packed blob in order (csrc/neo_backbone_bf16.hpp, PACKED BLOB), as (kind, f32 offset, floats,
+    byte offset, (taps, cin, cout) or None): kind "f32" is copied verbatim, "w" is a convolution's W"""
+    parts, at32, at = [], 0, 0
+
+    def add(kind, floats, shape=None):
+        nonlocal at32, at
+        parts.append((kind, at32, floats, at, shape))
+        at32 += floats
+        at += floats * (2 if kind == "w" else 4)
+
+    add("f32", 49 * 64 + 64)
+    cin = 64
+    for cout in _BACKBONE_CHANNELS:
+        for blk in range(2):
+            convs = [(9, cin, cout), (9, cout, cout)] + ([(1, cin, cout)] if cin != cout else [])
+            for taps, ci, co in convs:
+                add("w", taps * ci * co, (taps, ci, co))
+                add("f32", co)
+            cin = cout
+    add("f32", 24 * 512 + 24)
+    assert at32 == BACKBONE_FLOATS and at == BACKBONE_BF16_BYTES
+    return parts
+
+
+def pack_backbone_weights_bf16(blob32):
+    """the packed blob of neo_backbone_features_bf16_dev from the float32 blob of pack_backbone_weights: a uint8 tensor
+    of NEO_BACKBONE_BF16_BYTES on the blob's device.  The NumPy twin of neo_backbone_pack_bf16_dev, written from the
+    layout text of csrc/neo_backbone_bf16.hpp: the stem, the biases and the fc verbatim; a convolution's W
+    [ky][kx][ci][co] as bf16 [ky][kx][ci / 8][co][8], ci = 8 g + j, rounded to nearest even."""
+    t = torch.as_tensor(blob32)
+    src = np.ascontiguousarray(t.detach().cpu().numpy()).reshape(-1)
+    if src.dtype != np.float32 or src.size != BACKBONE_FLOATS:
+        raise ValueError("pack_backbone_weights_bf16: the float32 blob of NEO_BACKBONE_FLOATS = %d values" % BACKBONE_FLOATS)
+    out = np.empty(BACKBONE_BF16_BYTES, dtype=np.uint8)
+    for kind, o32, floats, at, shape in _bf16_parts():
+        part = src[o32:o32 + floats]
+        if kind == "f32":
+            out[at:at + 4 * floats] = part.view(np.uint8)
+        else:
+            taps, cin, cout = shape
+            w = bf16_bits(part).reshape(taps, cin // 8, 8, cout).transpose(0, 1, 3, 2)
+            out[at:at + 2 * floats] = np.ascontiguousarray(w).reshape(-1).view(np.uint8)
+    return torch.from_numpy(out).to(t.device if torch.is_tensor(blob32) else "cpu")
+
+
+def unpack_backbone_weights_bf16(packed):
+    """the float64 blob of the quantised network, in the float32 blob's order (NEO_BACKBONE_FLOATS values): what the packed
+    blob means.  backbone_launch_model, backbone_launches and backbone_model work on it unchanged."""
+    raw = np.ascontiguousarray(torch.as_tensor(packed).detach().cpu().numpy()).reshape(-1)
+    if raw.dtype != np.uint8 or raw.size != BACKBONE_BF16_BYTES:
+        raise ValueError("unpack_backbone_weights_bf16: the uint8 blob of NEO_BACKBONE_BF16_BYTES = %d bytes" % BACKBONE_BF16_BYTES)
+    out = np.empty(BACKBONE_FLOATS, dtype=np.float64)
+    for kind, o32, floats, at, shape in _bf16_parts():
+        if kind == "f32":
+            out[o32:o32 + floats] = raw[at:at + 4 * floats].view(np.float32)
+        else:
+            taps, cin, cout = shape
+            w = bf16_from_bits(raw[at:at + 2 * floats].view(np.uint16)).reshape(taps, cin // 8, cout, 8).transpose(0, 1, 3, 2)
+            out[o32:o32 + floats] = w.reshape(-1)
+    return torch.from_numpy(out)
+
+
+def backbone_bf16_model(packed, images):
+    """What the bf16 route COSTS, without a GPU: the features (n, 24) float64 of images (n, H, W) from the packed blob's
+    quantised weights, every launch in fp64 and every STORED activation (the stem's and the convolutions' outputs) rounded
+    with bf16_round behind it; the pool and fc's features stay as they are."""
+    blob = unpack_backbone_weights_bf16(packed)
+    x = torch.as_tensor(np.asarray(images.detach().cpu() if torch.is_tensor(images) else images)).double()
+    x = x.reshape(-1, 1, *x.shape[-2:])
+    table = backbone_launches(*x.shape[-2:])
+    outs = {-1: x}
+    for k, rec in enumerate(table):
+        y = _launch64(blob, rec, outs[rec.src], None if rec.resid is None else outs[rec.resid])
+        if rec.kind != "poolfc":
+            y = torch.from_numpy(bf16_round(y.numpy().astype(np.float32)).astype(np.float64))
+        outs[k] = y
+    return outs[len(table) - 1].numpy()
+
+
+def backbone_features_kernel(ctx, blob, images, out=None, chunk=512, workspace=None, precision="f32"):
     """neo_backbone_features_dev on `ctx`'s stream, `chunk` images a call: blob (pack_backbone_weights) and images (n, H, W)
     uint8 are contiguous device tensors that are READY (torch.cuda.synchronize after torch wrote them).  Returns
     (features (n, 24) float32, the workspace tensor used -- hand it back in to reuse it).  Asynchronous: ctx.synchronize()
-    before torch reads the features."""
+    before torch reads the features.  precision "bf16": neo_backbone_features_bf16_dev, and the blob is the packed one
+    (pack_backbone_weights_bf16 or neo_backbone_pack_bf16_dev: a uint8 tensor)."""
     from . import _lib
+    if precision not in ("f32", "bf16"):
+        raise ValueError("backbone_features_kernel: precision must be 'f32' or 'bf16'")
     n, H, W = (int(s) for s in images.shape)
-    if images.dtype != torch.uint8 or not images.is_contiguous() or blob.dtype != torch.float32 or not blob.is_contiguous():
-        raise ValueError("backbone_features_kernel: contiguous tensors, images (n, H, W) uint8 and a float32 blob")
+    if precision == "bf16":
+        if images.dtype != torch.uint8 or not images.is_contiguous() or blob.dtype != torch.uint8 or not blob.is_contiguous():
+            raise ValueError("backbone_features_kernel: contiguous tensors, images (n, H, W) uint8 and the packed uint8 blob")
+        entry, bytes_of = "neo_backbone_features_bf16_dev", ctx.backbone_bf16_workspace_bytes
+    else:
+        if images.dtype != torch.uint8 or not images.is_contiguous() or blob.dtype != torch.float32 or not blob.is_contiguous():
+            raise ValueError("backbone_features_kernel: contiguous tensors, images (n, H, W) uint8 and a float32 blob")
+        entry, bytes_of = "neo_backbone_features_dev", ctx.backbone_workspace_bytes
     chunk = max(1, min(int(chunk), max(n, 1)))
-    need = ctx.backbone_workspace_bytes(chunk, H, W)
+    need = bytes_of(chunk, H, W)
     fresh = out is None
     if out is None:
         out = torch.empty((n, IMG_FEATURE_SIZE), dtype=torch.float32, device=images.device)
@@ -444,7 +555,7 @@ def backbone_features_kernel(ctx, blob, images, out=None, chunk=512, workspace=N
     p = _lib.dev_ptr
     for b0 in range(0, n, chunk):
         k = min(chunk, n - b0)
-        ctx.call("neo_backbone_features_dev", p(blob), int(blob.numel()), p(images[b0:b0 + k]), k, H, W, p(workspace),
+        ctx.call(entry, p(blob), int(blob.numel()), p(images[b0:b0 + k]), k, H, W, p(workspace),
                  int(workspace.numel()), p(out[b0:b0 + k]))
     return out, workspace
 
@@ -559,6 +670,7 @@ class BatchInitializer:
         self.net = net.to(self.device).eval()
         self.T_min, self.T_max = T_min, T_max
         self._backbone_blob = self._workspace = None      # the kernel backbone's packed weights and its activation buffers
+        self._backbone_bf16 = None                        # ... and the bf16 route's packed blob
 
     @torch.no_grad()
     def scene_feature(self, depth_norm):
@@ -571,12 +683,13 @@ class BatchInitializer:
         request for `warm_start`.  The backbone runs `chunk` images at a time (None: 64 on the torch module, 512 on the
         kernels, which fill the machine only across many images).  impl "torch" (the default): the torch
         module; "kernel": neo_backbone_features_dev (csrc/neo_backbone.hpp) on `ctx`'s stream (None: the default
-        context) from uint8 images, float32 features that are complete when it returns."""
-        if impl not in ("torch", "kernel"):
-            raise ValueError("BatchInitializer.image_features: impl must be 'torch' or 'kernel'")
+        context) from uint8 images, float32 features that are complete when it returns; "kernel_bf16": the same on
+        neo_backbone_features_bf16_dev (csrc/neo_backbone_bf16.hpp: bf16 weights and activations)."""
+        if impl not in ("torch", "kernel", "kernel_bf16"):
+            raise ValueError("BatchInitializer.image_features: impl must be 'torch', 'kernel' or 'kernel_bf16'")
         img = torch.as_tensor(depth_u8) if not torch.is_tensor(depth_u8) else depth_u8
-        chunk = (512 if impl == "kernel" else 64) if chunk is None else chunk
-        if impl == "kernel":
+        chunk = (64 if impl == "torch" else 512) if chunk is None else chunk
+        if impl != "torch":
             from . import _lib
             if self.device.type != "cuda":
                 raise ValueError("BatchInitializer.image_features: impl 'kernel' runs on the GPU (there is no CPU fallback)")
@@ -585,8 +698,10 @@ class BatchInitializer:
             ctx = ctx if ctx is not None else _lib.default_context(self.device.index or 0)
             img = img.reshape(-1, *img.shape[-2:]).to(self.device).contiguous()
             torch.cuda.synchronize(self.device)
-            feat, self._workspace = backbone_features_kernel(ctx, self.backbone_weights(), img, chunk=chunk,
-                                                             workspace=self._workspace)
+            bf16 = impl == "kernel_bf16"
+            feat, self._workspace = backbone_features_kernel(ctx, self.backbone_weights(precision="bf16" if bf16 else "f32"),
+                                                             img, chunk=chunk, workspace=self._workspace,
+                                                             precision="bf16" if bf16 else "f32")
             ctx.synchronize()
             return feat
         img = img.reshape(-1, 1, *img.shape[-2:])
@@ -594,14 +709,24 @@ class BatchInitializer:
                for b0 in range(0, img.shape[0], max(1, int(chunk)))]
         return torch.cat(out, dim=0)
 
-    def backbone_weights(self, refresh=False):
+    def backbone_weights(self, refresh=False, precision="f32"):
         """the network's blob for neo_backbone_features_dev (pack_backbone_weights), packed at first use; refresh=True
-        packs it again after the network's parameters changed"""
+        packs it again after the network's parameters changed.  precision "bf16": the packed blob of
+        neo_backbone_features_bf16_dev (pack_backbone_weights_bf16 of the same float32 blob), cached likewise"""
+        if precision not in ("f32", "bf16"):
+            raise ValueError("BatchInitializer.backbone_weights: precision must be 'f32' or 'bf16'")
         if self._backbone_blob is None or refresh:
             self._backbone_blob = pack_backbone_weights(self.net)
+            self._backbone_bf16 = None
             if self._backbone_blob.is_cuda:
                 torch.cuda.synchronize(self._backbone_blob.device)
-        return self._backbone_blob
+        if precision == "f32":
+            return self._backbone_blob
+        if self._backbone_bf16 is None:
+            self._backbone_bf16 = pack_backbone_weights_bf16(self._backbone_blob)
+            if self._backbone_bf16.is_cuda:
+                torch.cuda.synchronize(self._backbone_bf16.device)
+        return self._backbone_bf16
 
     @torch.no_grad()
     def warm_start(self, scene_feature, motion, attitude_R, global_pos, clamp_ts=True):
@@ -635,9 +760,10 @@ class BatchNeoPlanner:
     def __init__(self, batch_planner, initializer, camera, des_pos_z=2.0, backbone_impl="torch"):
         """backbone_impl: how `features_dev` runs the image backbone -- "torch" (the default: the torch module, im2col and
         a GEMM per convolution on torch's stream) or "kernel" (neo_backbone_features_dev on the camera's context,
-        `backbone_chunk` images a call)"""
-        if backbone_impl not in ("torch", "kernel"):
-            raise ValueError("BatchNeoPlanner: backbone_impl must be 'torch' or 'kernel'")
+        `backbone_chunk` images a call) or "kernel_bf16" (the same on neo_backbone_features_bf16_dev: bf16 weights and
+        activations on the bf16 matrix cores, fp32 features that differ from "kernel"'s by the format's rounding)"""
+        if backbone_impl not in ("torch", "kernel", "kernel_bf16"):
+            raise ValueError("BatchNeoPlanner: backbone_impl must be 'torch', 'kernel' or 'kernel_bf16'")
         net = initializer.net
         if (camera.height, camera.width) != (net.img_height, net.img_width):
             raise ValueError("BatchNeoPlanner: the camera renders %d x %d, the network takes %d x %d"
@@ -700,10 +826,10 @@ class BatchNeoPlanner:
             torch.cuda.synchronize(self._weights.device)
         return self._weights
 
-    def backbone_weights(self, refresh=False):
+    def backbone_weights(self, refresh=False, precision="f32"):
         """the network's blob for neo_backbone_features_dev (pack_backbone_weights), packed at first use; refresh=True
-        packs it again after the network's parameters changed"""
-        return self.init.backbone_weights(refresh)
+        packs it again after the network's parameters changed; precision "bf16": the packed blob of the bf16 route"""
+        return self.init.backbone_weights(refresh, precision)
 
     @torch.no_grad()
     def features_dev(self, boxes, box_begin, pose, scene_index=None):
@@ -712,16 +838,19 @@ class BatchNeoPlanner:
         when it returns).  With backbone_impl "kernel" the render launches and the backbone's are queued on the camera's
         context one after the other, `backbone_chunk` images a call out of a workspace kept here, and the context's
         stream has finished when it returns: nothing is handed over to torch's stream in between."""
-        if self.backbone_impl == "kernel":
-            weights = self.backbone_weights()
+        if self.backbone_impl != "torch":
+            precision = "bf16" if self.backbone_impl == "kernel_bf16" else "f32"
+            weights = self.backbone_weights(precision=precision)
             n, dev, ctx = int(pose.shape[0]), pose.device, self.camera.ctx
             # (everything torch allocates comes first: render_dev waits for torch once, then both stages only queue)
             feat = torch.empty((n, IMG_FEATURE_SIZE), dtype=torch.float32, device=dev)
-            need = ctx.backbone_workspace_bytes(max(1, min(self.backbone_chunk, n)), self.camera.height, self.camera.width)
+            bytes_of = ctx.backbone_bf16_workspace_bytes if precision == "bf16" else ctx.backbone_workspace_bytes
+            need = bytes_of(max(1, min(self.backbone_chunk, n)), self.camera.height, self.camera.width)
             if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
                 self._workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
             img = self.camera.render_dev(boxes, box_begin, pose, scene_index, chunk=self.chunk, want_m=False, sync=False)["depth_u8"]
-            backbone_features_kernel(ctx, weights, img, out=feat, chunk=self.backbone_chunk, workspace=self._workspace)
+            backbone_features_kernel(ctx, weights, img, out=feat, chunk=self.backbone_chunk, workspace=self._workspace,
+                                     precision=precision)
             ctx.synchronize()
             return feat
         img = self.camera.render_dev(boxes, box_begin, pose, scene_index, chunk=self.chunk, want_m=False)["depth_u8"]

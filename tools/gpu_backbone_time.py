@@ -11,6 +11,11 @@
            mode `neo` with the trained network on the torch backbone and on the kernel backbone, and in mode `basic`:
            tick, neo_s and plan_s a tick
 
+  --bf16   kernels: next to the fp32 kernels the bf16 route (neo_backbone_features_bf16_dev, csrc/neo_backbone_bf16.hpp),
+           every launch with its share of the 2.5 PF bf16 matrix peak, and MIOpen, without the chunk sweep and the torch
+           GEMM route (profiles/backbone_bf16.json); fleet: `basic`, `neo` on "kernel" and `neo` on "kernel_bf16"
+           (profiles/backbone_bf16_fleet.json)
+
 Each part is one process; run them one after the other, every one under its own time limit, e.g.
   timeout -k 10 600 python tools/gpu_backbone_time.py kernels --json profiles/backbone.json && \\
   timeout -k 10 900 python tools/gpu_backbone_time.py fleet --json profiles/backbone_fleet.json
@@ -30,6 +35,9 @@ ap.add_argument("what", choices=["kernels", "fleet"])
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--no-miopen", action="store_true")
+ap.add_argument("--bf16", action="store_true",
+                help="kernels: also the bf16 route (neo_backbone_features_bf16_dev), without the chunk sweep and the torch GEMM "
+                     "route; fleet: basic, neo on 'kernel' and neo on 'kernel_bf16'")
 ap.add_argument("--scenes", type=int, default=8)
 ap.add_argument("--per-scene", type=int, default=64)
 ap.add_argument("--max-replans", type=int, default=60)
@@ -42,6 +50,7 @@ dev = torch.device("cuda", 0)
 ctx = _lib.default_context()
 p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
 PEAK_TFLOPS = 157.3
+PEAK_BF16_TFLOPS = 2500.0        # dense bf16 matrix peak of the chip
 
 
 def dump(obj):
@@ -120,12 +129,42 @@ if a.what == "kernels":
         for l in r["launches"]:
             print(f"  {key} {l['name']}: {l['ms']:.4f} ms, {l['tflops']:.1f} TF", flush=True)
         del ws
+        if a.bf16:
+            packed = init.backbone_weights(precision="bf16")
+            ws = torch.empty(int(ctx.lib.neo_backbone_bf16_workspace_bytes(n, H, W)), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)
+            rows = []
+            for k in range(a.warmup + a.reps):
+                ctx.call("neo_backbone_bf16_launch_times", p(packed), packed.numel(), p(img), n, H, W, p(ws), ws.numel(), p(out), ms)
+                if k >= a.warmup:
+                    rows.append(list(ms))
+            med = np.median(np.asarray(rows), axis=0)
+            r["bf16_launches"] = [dict(name=name, ms=round(float(t), 4), tflops=round(f / (t * 1e-3) / 1e12, 2),
+                                       fraction_of_bf16_peak=round(f / (t * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4))
+                                  for (name, f), t in zip(layers, med)]
+            r["bf16_launches_sum_ms"] = round(float(med.sum()), 3)
+            for l in r["bf16_launches"]:
+                print(f"  {key} bf16 {l['name']}: {l['ms']:.4f} ms, {l['tflops']:.1f} TF, "
+                      f"{100 * l['fraction_of_bf16_peak']:.1f} % of the bf16 peak", flush=True)
+            t = events(lambda: ini.backbone_features_kernel(ctx, packed, img, out=out, chunk=n, workspace=ws, precision="bf16"))
+            r["bf16_ms"] = round(t, 3)
+            r["bf16_tflops"] = round(flops / (t * 1e-3) / 1e12, 2)
+            print(f"{key}: bf16 backbone {t:.3f} ms in one call, {r['bf16_tflops']} TF (launches add up to "
+                  f"{r['bf16_launches_sum_ms']} ms)", flush=True)
+            del ws, packed
         t = whole(n)
         r["kernel_ms"] = round(t, 3)
         r["kernel_tflops"] = round(flops / (t * 1e-3) / 1e12, 2)
         r["kernel_fraction_of_peak"] = round(r["kernel_tflops"] / PEAK_TFLOPS, 3)
         print(f"{key}: kernel backbone {t:.3f} ms in one call, {r['kernel_tflops']} TF = {100 * r['kernel_fraction_of_peak']:.1f} % of the "
               f"matrix peak (launches add up to {r['launches_sum_ms']} ms)", flush=True)
+        if a.bf16:
+            print(f"{key}: bf16 route {r['kernel_ms'] / r['bf16_ms']:.2f} x as fast as the fp32 kernels", flush=True)
+            res["sizes"][key] = r
+            dump(res)
+            del net, init, blob, img, out
+            torch.cuda.empty_cache()
+            continue
         if n > 64:
             r["kernel_ms_by_chunk"] = {}
             for chunk in (32, 64, 128, 256, 512):
@@ -193,7 +232,8 @@ del inputs, rec
 torch.cuda.empty_cache()
 make = lambda impl: ini.BatchNeoPlanner(bp, ini.BatchInitializer(net=net, device=dev, T_min=bp.cfg.T_min, T_max=bp.cfg.T_max), cam,
                                         backbone_impl=impl)
-for name, mode, kw in (("basic_resident", "basic", dict(resident=True)), ("neo_torch_backbone", "neo", dict(neo=make("torch"))),
+second = ("neo_kernel_bf16_backbone", "kernel_bf16") if a.bf16 else ("neo_torch_backbone", "torch")
+for name, mode, kw in (("basic_resident", "basic", dict(resident=True)), (second[0], "neo", dict(neo=make(second[1]))),
                        ("neo_kernel_backbone", "neo", dict(neo=make("kernel")))):
     fly(1, mode, **kw)                                       # warm-up: first-use allocations and caches
     flights = []

@@ -13,7 +13,8 @@ sys.path.insert(0, os.path.join(REPO, "neo-planner_amd"))
 from neo_planner_amd import build as b
 
 UNITS = ["neo_disp_opt3d_x.hip", "neo_disp_opt3d_w2.hip", "neo_disp_opt3d_f64.hip", "neo_disp_opt3d_b.hip", "neo_disp_sample.hip",
-         "neo_disp_group.hip", "neo_disp_depth.hip", "neo_disp_record.hip", "neo_disp_init.hip", "neo_disp_plan.hip", "neo_disp_fleet.hip", "neo_disp_adaptive.hip", "neo_disp_batch.hip", "neo_disp_backbone.hip"]
+         "neo_disp_group.hip", "neo_disp_depth.hip", "neo_disp_record.hip", "neo_disp_init.hip", "neo_disp_plan.hip", "neo_disp_fleet.hip", "neo_disp_adaptive.hip", "neo_disp_batch.hip", "neo_disp_backbone.hip",
+         "neo_disp_backbone_bf16.hip"]
 JITTER_UNITS = ("neo_disp_plan.hip", "neo_disp_fleet.hip")
 if len(sys.argv) > 1:
     UNITS = [u for u in UNITS if u in sys.argv[1:]]
